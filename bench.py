@@ -136,6 +136,43 @@ def stage_traffic(args, world: int, mode: str):
     return (allj.get(f"{workload_key(args, world)}:{mode}") or {}).get("stages", {})
 
 
+DUMP_SAMPLE = 1 << 20  # entries per sampled array: 4 arrays x 8 MB of float64 stay well inside the 64 MB a dump may take
+DUMP_SEED = 20240601
+
+
+def _checksum(a: np.ndarray) -> float:
+    """Position-weighted sum of all entries, mod 2^52 (exact in float64): a change anywhere in the array changes it."""
+    acc, chunk = np.uint64(0), 1 << 23
+    with np.errstate(over="ignore"):
+        for lo in range(0, len(a), chunk):
+            v = a[lo:lo + chunk].astype(np.uint64) + np.uint64(1)
+            w = np.arange(lo, lo + len(v), dtype=np.uint64) * np.uint64(0x9E3779B97F4A7C15) + np.uint64(1)
+            acc = acc + np.sum(v * w, dtype=np.uint64)
+    return float(int(acc) & ((1 << 52) - 1))
+
+
+def _sample(a: np.ndarray, rng) -> tuple[np.ndarray, np.ndarray]:
+    """All of `a` when it is small, else DUMP_SAMPLE entries at sorted positions drawn from `rng`: (positions, values) as float64."""
+    n = len(a)
+    idx = np.arange(n, dtype=np.int64) if n <= DUMP_SAMPLE else np.sort(rng.integers(0, n, size=DUMP_SAMPLE, dtype=np.int64))
+    return idx.astype(np.float64), a[idx].astype(np.float64)
+
+
+def dump_outputs(out_dir: Path, limits: np.ndarray, edges: np.ndarray) -> None:
+    """The tigs of the last timed step, as a caller receives them (limits[i] = exclusive end of tig i in edges[], edges = edge ids),
+    in float64 .npy files for an output-for-output comparison of two builds: tig_summary = [#tigs, #edges, checksum(limits),
+    checksum(edges)] over the whole arrays; tig_limits / tig_edges = the arrays themselves, or a fixed seeded sample of positions
+    (tig_limits_index / tig_edges_index) when they are larger than DUMP_SAMPLE."""
+    out_dir.mkdir(parents=True, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    li_idx, li_val = _sample(limits, rng)
+    ed_idx, ed_val = _sample(edges, rng)
+    files = {"tig_summary": np.array([len(limits), len(edges), _checksum(limits), _checksum(edges)], dtype=np.float64),
+             "tig_limits_index": li_idx, "tig_limits": li_val, "tig_edges_index": ed_idx, "tig_edges": ed_val}
+    for name, arr in files.items():
+        np.save(out_dir / f"{name}.npy", arr)
+
+
 def host_cores() -> int:
     """CPU cores this process may really use: the cgroup quota if there is one (16 on a 1-GPU box of the pool), else the count."""
     n = os.cpu_count() or 1
@@ -187,7 +224,11 @@ def main():
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only for functional checks)")
     ap.add_argument("--single-device", action="store_true",
                     help="functional check of the N>1 code path on a 1-GPU box: every rank uses GPU 0 (needs --backend gloo)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the tigs of the last timed step as DIR/<name>.npy (float64; see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -262,7 +303,8 @@ def main():
 
     stage_ms: dict[str, dict[str, list]] = {"host": {}, "device": {}}  # per Euler mode: stage -> GPU ms (HIP events) of every timed step
 
-    def step(mode, acc, kernel_ms=None, level_ms=None, stages=None, tig_download_ms=None):
+    def step(mode, acc, kernel_ms=None, level_ms=None, stages=None, tig_download_ms=None, keep=None):
+        """One step; with `keep` (a list) rank 0 leaves the step's tigs in it -- what a caller of the path receives."""
         nonlocal bufs
         ph = {}
         t0 = time.perf_counter()
@@ -322,10 +364,14 @@ def main():
                     t_dl = time.perf_counter()
                     tigs.arrays()
                     tig_download_ms.append((time.perf_counter() - t_dl) * 1e3)
+                if keep is not None:  # (the handle owns its device arrays: it stays valid across the graph's reset below)
+                    keep.append(tigs)
                 del tigs
             else:
                 tigs_lim, tigs_edges = api.finish_greedytigs_np(graph, pairs, k, mode, local_rank, finish_stage)
                 n_tigs, n_tig_edges = len(tigs_lim), len(tigs_edges)
+                if keep is not None:
+                    keep.append((tigs_lim, tigs_edges))
                 del tigs_lim, tigs_edges
             t6 = time.perf_counter()
             ph["finish"] = t6 - t5
@@ -349,15 +395,15 @@ def main():
         for kk, v in ph.items():
             acc[kk] = acc.get(kk, 0.0) + v
 
-    def timed_region(mode, n_warm, n_steps, kernel_ms=None, level_ms=None):
+    def timed_region(mode, n_warm, n_steps, kernel_ms=None, level_ms=None, keep=None):
         acc: dict[str, float] = {}
         for _ in range(n_warm):
             step(mode, {})
         sync_barrier()
         stages = stage_ms["device" if mode == api.EulerMode.Device else "host"]
         t_begin = time.perf_counter()
-        for _ in range(n_steps):
-            step(mode, acc, kernel_ms, level_ms, stages)
+        for i in range(n_steps):
+            step(mode, acc, kernel_ms, level_ms, stages, keep=keep if i == n_steps - 1 else None)
         sync_barrier()
         elapsed = time.perf_counter() - t_begin
         if world > 1:
@@ -429,7 +475,12 @@ def main():
     # ---- the headline: K timed steps in the selected mode (default: the reference's walk order, bit-exact tigs) ----
     kernel_ms: list[float] = []
     level_ms: list[list[dict]] = []
-    ms_per_step, phases_acc = timed_region(euler_mode, args.warmup, args.steps, kernel_ms, level_ms)
+    last_tigs: list | None = [] if args.dump_outputs else None  # (kept only for a dump: else the step frees its tigs as before)
+    ms_per_step, phases_acc = timed_region(euler_mode, args.warmup, args.steps, kernel_ms, level_ms, keep=last_tigs)
+    if last_tigs:
+        t = last_tigs[0]
+        dump_outputs(Path(args.dump_outputs), *(t if isinstance(t, tuple) else t.arrays()))
+    del last_tigs
     # what delivering the step's tigs to the host as walks costs on top (the reference's compute_tigs always ends with them in host
     # memory; rounds 1-4 ended every timed step with that copy): the same arrays in either Euler mode, so the device-mode measurement
     # is reused when there is one, else one more untimed step measures it

@@ -66,3 +66,77 @@ def test_bench_json_line(product_lib):
     cb = d["cpu_baseline"]
     assert cb["kind"] == "port" and cb["cores"] == 1 and cb["value"] > 0 and cb["sample"]
     assert cb["pairs"] == d["config"]["pairs"] and cb["tigs"] == d["config"]["tigs"]   # the CPU port and the GPU path agree
+
+
+def _load_bench():
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("bench_under_test", ROOT / "bench.py")
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def _read_dump(d: Path) -> dict:
+    import numpy as np
+
+    return {p.stem: np.load(p) for p in sorted(d.glob("*.npy"))}
+
+
+def test_dump_outputs_small_and_sampled(tmp_path):
+    """--dump-outputs' writer: float64 files only; small outputs whole, large ones as a fixed seeded sample with its positions;
+    the same arrays give the same files, a change anywhere in them changes the summary."""
+    import numpy as np
+
+    bench = _load_bench()
+    rng = np.random.default_rng(5)
+    lens = rng.integers(1, 6, size=1000)
+    small_lim, small_ed = np.cumsum(lens).astype(np.uint64), rng.integers(0, 1 << 31, size=int(lens.sum()), dtype=np.uint64).astype(np.uint32)
+    bench.dump_outputs(tmp_path / "small", small_lim, small_ed)
+    d = _read_dump(tmp_path / "small")
+    assert set(d) == {"tig_summary", "tig_limits", "tig_limits_index", "tig_edges", "tig_edges_index"}
+    assert all(a.dtype == np.float64 for a in d.values())
+    assert np.array_equal(d["tig_limits"], small_lim.astype(np.float64)) and np.array_equal(d["tig_edges"], small_ed.astype(np.float64))
+    assert d["tig_summary"][:2].tolist() == [len(small_lim), len(small_ed)]
+
+    n = 3 * bench.DUMP_SAMPLE
+    big_lim = np.arange(1, n + 1, dtype=np.uint64) * np.uint64(3)
+    big_ed = (np.arange(3 * n, dtype=np.uint64) * np.uint64(2654435761) % np.uint64(1 << 30)).astype(np.uint32)
+    for name in ("a", "b"):
+        bench.dump_outputs(tmp_path / name, big_lim, big_ed)
+    a, b = _read_dump(tmp_path / "a"), _read_dump(tmp_path / "b")
+    assert all(np.array_equal(a[key], b[key]) for key in a)
+    assert sum(p.stat().st_size for p in (tmp_path / "a").glob("*.npy")) <= 64 << 20
+    assert len(a["tig_edges"]) == len(a["tig_limits"]) == bench.DUMP_SAMPLE
+    assert np.array_equal(a["tig_edges"], big_ed[a["tig_edges_index"].astype(np.int64)].astype(np.float64))
+    assert np.array_equal(a["tig_limits"], big_lim[a["tig_limits_index"].astype(np.int64)].astype(np.float64))
+    changed = big_ed.copy()
+    changed[n // 2 + 7] ^= 1
+    bench.dump_outputs(tmp_path / "c", big_lim, changed)
+    assert _read_dump(tmp_path / "c")["tig_summary"][3] != a["tig_summary"][3]
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_repeatable(product_lib, tmp_path):
+    """--dump-outputs on a small graph: the tigs of the last timed step, whole at this size, the same in two runs with the same
+    arguments; --steps sets the number of timed steps."""
+    import numpy as np
+
+    if product_lib.mtg_device_count() < 1:
+        pytest.fail("needs a GPU")
+    runs = []
+    for name in ("a", "b"):
+        r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--log2-edges", "19",
+                            "--no-cpu-baseline", "--no-cold-steps", "--no-one-shot", "--extra-seeds", "", "--device-mode-steps", "0",
+                            "--dump-outputs", str(tmp_path / name)], capture_output=True, text=True, cwd=str(ROOT), timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, r.stdout[-2000:]
+        runs.append((json.loads(lines[0]), _read_dump(tmp_path / name)))
+    (da, a), (db, b) = runs
+    assert da["steps"] == 3 and da["ms_per_step"] > 0
+    assert set(a) == set(b) == {"tig_summary", "tig_limits", "tig_limits_index", "tig_edges", "tig_edges_index"}
+    assert all(v.dtype == np.float64 and np.array_equal(v, b[key]) for key, v in a.items())
+    n_tigs, n_edges = int(a["tig_summary"][0]), int(a["tig_summary"][1])
+    assert n_tigs == da["config"]["tigs"] == db["config"]["tigs"] and len(a["tig_limits"]) == n_tigs and len(a["tig_edges"]) == n_edges
+    assert a["tig_limits"][-1] == n_edges and np.all(np.diff(a["tig_limits"]) > 0)
