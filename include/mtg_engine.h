@@ -18,6 +18,7 @@
  *   mtg_compute_eulertigs          eulertigs/mod.rs:48-198                          host (C++); idem
  *   mtg_write_walks_fasta / _gfa   bin.rs:466-606 / 667-818                         host (C++)
  *   mtg_read_bcalm2                bin.rs:902-912 (genome-graph bcalm2 reader)      host (C++)
+ *   mtg_read_fasta                 bin.rs:891-901 (genome-graph fasta reader)       GPU (HIP) join, host (C++) parse
  *
  * All pointers are plain host pointers unless the name starts with d_ (device pointer in the
  * HBM of the GPU the mtg_device was created on). `stream` is a hipStream_t passed as void*
@@ -447,6 +448,19 @@ uint64_t mtg_write_walks_fasta(const mtg_graph *g, uint64_t n_walks, const uint6
  * sequence store (free with mtg_unitigs_free). Aborts on malformed input, non-ACGT characters, sequences shorter than k. */
 typedef struct mtg_unitigs mtg_unitigs;
 mtg_graph *mtg_read_bcalm2(const char *path, uint64_t k, mtg_unitigs **unitigs_out);
+/* Plain unitig FASTA input (the `--fa-in X -k K` route, bin.rs:71-75, 891-901): no topology in the file -- every pair of unitig
+ * ends that share a (k-1)-mer, in either orientation, is joined on GPU `device_id` (there is no CPU path). Nodes are oriented
+ * (k-1)-mers numbered in first-occurrence order of their class {x, rc(x)} (first k-1 bases of record u = occurrence
+ * 2u, last k-1 = 2u + 1); edges 2u / 2u+1 as above, weight len + 1 - k. Headers may hold any text (`L:` annotations are ignored),
+ * sequences may span lines and be lower case, `.gz` files are inflated. Aborts on non-ACGT characters, records shorter than k,
+ * k < 2 and graphs past the 32-bit ids. */
+mtg_graph *mtg_read_fasta(const char *path, uint64_t k, int device_id, mtg_unitigs **unitigs_out);
+/* The same join over records held in memory: record u is data[offsets[u], offsets[u + 1]), offsets[0] = 0 (n + 1 offsets, the
+ * layout of mtg_unitigs_data / _offsets). */
+mtg_graph *mtg_graph_from_sequences(const char *data, const uint64_t *offsets, uint64_t n, uint64_t k, int device_id);
+/* Of the last mtg_read_fasta / mtg_graph_from_sequences on this thread: {parse ms (0 for the in-memory entry), upload ms, join
+ * kernels ms (HIP events), download ms, graph build ms, bytes the join kernels must move at the least}. */
+void mtg_last_fasta_in_times(double out[6]);
 uint64_t mtg_unitigs_count(const mtg_unitigs *u);
 const char *mtg_unitigs_data(const mtg_unitigs *u);        /* concatenated ASCII sequences */
 const uint64_t *mtg_unitigs_offsets(const mtg_unitigs *u); /* count + 1 offsets into data */

@@ -1,9 +1,10 @@
 """`python -m matchtigs_amd` -- the reference CLI's flag surface for the path this engine serves.
 
 Flag names, defaults and exclusivity rules follow /root/reference/src/bin.rs:56-205, 850-862 for the subset that maps onto
-the engine (the rest of the reference CLI -- GFA/plain-FASTA input, pathtigs, optimal matchtigs, bitvectors -- is out of
-scope). All work happens inside libmatchtigs.so; this file only parses flags and prints the reference's
-closing log line (bin.rs:1209-1211).
+the engine (the rest of the reference CLI -- GFA input, pathtigs -- is out of scope). Two inputs are served:
+`--bcalm-in` (BCALM2/GGCAT FASTA whose `L:` annotations carry the links) and `--fa-in` (plain unitig FASTA, no topology: the
+graph comes from the (k-1)-mer overlaps of the unitig ends, joined on the GPU). All work happens inside
+libmatchtigs.so; this file only parses flags and prints the reference's closing log line (bin.rs:1209-1211).
 """
 from __future__ import annotations
 
@@ -16,7 +17,7 @@ def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="matchtigs_amd", description=__doc__.split("\n\n")[0])
     ap.add_argument("--bcalm-in", help="bcalm2/GGCAT unitig fasta (optionally .gz); requires -k (bin.rs:76-83)")
     ap.add_argument("--gfa-in", help="(not served by this engine)")
-    ap.add_argument("--fa-in", help="(not served by this engine)")
+    ap.add_argument("--fa-in", help="plain unitig fasta (optionally .gz), graph from (k-1)-mer overlaps on the GPU; requires -k (bin.rs:71-75)")
     ap.add_argument("-k", type=int, help="k-mer size used to build the de Bruijn graph (bin.rs:139-141)")
     ap.add_argument("-t", "--threads", type=int, default=1, help="accepted; results always equal the 1-thread order (bin.rs:148-149)")
     ap.add_argument("--greedytigs-fa-out", help="write greedy matchtigs as fasta (.gz => gzip) (bin.rs:107-109)")
@@ -38,10 +39,10 @@ def main(argv=None) -> int:
         ap.error("Missing input argument. Specify exactly least one of --fa-in, --gfa-in or --bcalm-in")
     if n_inputs > 1:  # bin.rs:860-862
         ap.error("Too many input arguments. Specify exactly least one of --fa-in, --gfa-in or --bcalm-in")
-    if args.bcalm_in is None:
-        ap.error("only --bcalm-in is served by the MI355X engine (SURVEY.md 8 f-2)")
+    if args.gfa_in is not None:
+        ap.error("only --bcalm-in and --fa-in are served by the MI355X engine (SURVEY.md 8 f-2)")
     if args.k is None:
-        ap.error("--bcalm-in requires -k")
+        ap.error("--bcalm-in requires -k" if args.bcalm_in is not None else "--fa-in requires -k")
     if not 0 <= args.compression_level <= 9:
         ap.error("compression level must be in 0..9")
     if args.matchtigs_duplication_bitvector_out and not (args.matchtigs_fa_out or args.matchtigs_gfa_out):
@@ -53,7 +54,10 @@ def main(argv=None) -> int:
     from . import api
 
     t0 = time.perf_counter()
-    graph, store = api.read_bcalm2(args.bcalm_in, args.k)
+    if args.bcalm_in is not None:
+        graph, store = api.read_bcalm2(args.bcalm_in, args.k)
+    else:
+        graph, store = api.read_fasta(args.fa_in, args.k, args.device)
     print(f"Loaded {len(store)} unitigs: {graph.node_count()} nodes, {graph.edge_count()} edges in {time.perf_counter() - t0:.1f}s",
           file=sys.stderr)
     for name, alg, out, gfa, dup in (("matchtigs", 4, args.matchtigs_fa_out, args.matchtigs_gfa_out,

@@ -203,6 +203,9 @@ def load():
         "mtg_flatten_clib": (u64, [vp, vp, vp, vp, vp]),
         "mtg_write_walks_fasta": (u64, [vp, u64, vp, vp, u64, C.c_char_p, vp, P(vp)]),
         "mtg_read_bcalm2": (vp, [C.c_char_p, u64, P(vp)]),
+        "mtg_read_fasta": (vp, [C.c_char_p, u64, C.c_int, P(vp)]),
+        "mtg_graph_from_sequences": (vp, [vp, vp, u64, u64, C.c_int]),
+        "mtg_last_fasta_in_times": (None, [P(C.c_double)]),
         "mtg_unitigs_count": (u64, [vp]),
         "mtg_unitigs_data": (vp, [vp]),
         "mtg_unitigs_offsets": (vp, [vp]),

@@ -233,6 +233,25 @@ class Bigraph:
         L.mtg_graph_builder_build(h, _ptr(w))
         return cls(h)
 
+    @classmethod
+    def from_sequences(cls, seqs, k: int, device_id: int = 0) -> "Bigraph":
+        """The plain-FASTA graph (`--fa-in`, read_fasta) of sequences held in memory: a list of str / bytes, or (data, offsets) with
+        record u = data[offsets[u]:offsets[u + 1]] (data: bytes or a uint8 array, offsets: U + 1 values from 0). Joined on the GPU."""
+        L = _lib.load()
+        if isinstance(seqs, tuple) and len(seqs) == 2:
+            data, off = seqs
+            data = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray)) else np.ascontiguousarray(data, dtype=np.uint8)
+            off = np.ascontiguousarray(off, dtype=np.uint64)
+        else:
+            parts = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
+            data = np.frombuffer(b"".join(parts), np.uint8)
+            off = np.zeros(len(parts) + 1, np.uint64)
+            np.cumsum([len(p) for p in parts], out=off[1:])
+        if len(off) < 1 or int(off[0]) != 0 or int(off[-1]) > len(data):
+            raise ValueError("offsets must start at 0 and end inside the data")
+        data = np.ascontiguousarray(data) if len(data) else np.zeros(1, np.uint8)
+        return cls(L.mtg_graph_from_sequences(_ptr(data), _ptr(off), len(off) - 1, k, device_id))
+
     @property
     def handle(self) -> int:
         return self._h
@@ -785,7 +804,7 @@ def last_performance_data() -> dict:
 
 
 class UnitigStore:
-    """Sequence store filled by read_bcalm2 (replaces DefaultSequenceStore<DnaAlphabet>, bin.rs:871)."""
+    """Sequence store filled by read_bcalm2 / read_fasta (replaces DefaultSequenceStore<DnaAlphabet>, bin.rs:871)."""
 
     def __init__(self, handle: int):
         self._h = handle
@@ -816,6 +835,22 @@ def read_bcalm2(path: str, k: int):
     st = C.c_void_p()
     g = L.mtg_read_bcalm2(str(path).encode(), k, C.byref(st))
     return Bigraph(g), UnitigStore(st.value)
+
+
+def read_fasta(path: str, k: int, device_id: int = 0):
+    """`--fa-in path -k k` (bin.rs:71-75, 891-901): plain unitig FASTA (optionally .gz) -> (Bigraph, UnitigStore). The graph
+    comes from the (k-1)-mer overlaps of the unitig ends, joined on GPU `device_id`."""
+    L = _lib.load()
+    st = C.c_void_p()
+    g = L.mtg_read_fasta(str(path).encode(), k, device_id, C.byref(st))
+    return Bigraph(g), UnitigStore(st.value)
+
+
+def last_fasta_in_times() -> dict:
+    """Phases of the last read_fasta / Bigraph.from_sequences on this thread (ms; bytes = what the join kernels must move)."""
+    out = (C.c_double * 6)()
+    _lib.load().mtg_last_fasta_in_times(out)
+    return dict(zip(("parse_ms", "upload_ms", "kernel_ms", "download_ms", "build_ms", "bytes"), list(out)))
 
 
 def compute_tigs_to_fasta_file(graph: Bigraph, store: UnitigStore, algorithm: int, k: int, path: Optional[str],

@@ -16,6 +16,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "fasta_lines.hpp"
 #include "host_graph.hpp"
 
 namespace mtg {
@@ -25,19 +26,6 @@ struct Link {
     uint64_t to_id;
     bool from_strand, to_strand;
 };
-
-static bool read_line(gzFile f, std::string &line) {
-    line.clear();
-    char buf[1 << 16];
-    for (;;) {
-        if (!gzgets(f, buf, sizeof buf)) return !line.empty();
-        const size_t n = std::strlen(buf);
-        line.append(buf, n);
-        if (n && buf[n - 1] == '\n') break;
-    }
-    while (!line.empty() && (line.back() == '\n' || line.back() == '\r')) line.pop_back();
-    return true;
-}
 
 HostGraph *read_bcalm2(const char *path, uint64_t k, UnitigStore **store_out) {
     if (!path || !store_out) MTG_DIE("mtg_read_bcalm2: null argument");

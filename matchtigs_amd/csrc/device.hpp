@@ -112,6 +112,16 @@ HostGraph *device_synth_g_csr(uint64_t n_binodes, uint64_t n_self_mirrors, uint6
 uint64_t device_write_walks_text(const HostGraph &g, uint64_t n_walks, const uint64_t *limits, const uint32_t *edges, uint64_t k,
                                  const char *seqs, const uint64_t *seq_off, bool gfa, const char *gfa_header, int device_id,
                                  char **out_buf, double *kernel_ms_out, uint64_t *bytes_out, const struct ResidentTigs *resident = nullptr);
+// fasta_in_device.hip: the plain unitig FASTA route -- graph of the (k-1)-mer overlaps of the unitig ends, joined on the GPU
+// (records: data[off[u], off[u + 1]), off[0] = 0). times: host wall clock of upload / download / graph build, HIP-event time of the
+// join kernels, and the bytes those kernels must move at the least.
+struct FastaJoinTimes {
+    double parse_ms = 0, upload_ms = 0, kernel_ms = 0, download_ms = 0, build_ms = 0;
+    uint64_t bytes = 0;
+};
+HostGraph *device_graph_from_sequences(const char *data, const uint64_t *off, uint64_t U, uint64_t k, int device_id, FastaJoinTimes *times);
+// fasta_in.cpp: parse a plain unitig FASTA file (.gz inflated) and join it on `device_id` (times->parse_ms: the parse)
+HostGraph *read_fasta(const char *path, uint64_t k, int device_id, UnitigStore **store_out, FastaJoinTimes *times);
 void device_candidates_to_host(Device *d, void *stream, std::vector<uint64_t> &cand_start,
                                std::vector<uint32_t> &cand_count, std::vector<uint64_t> &pool);
 

@@ -613,6 +613,27 @@ mtg_graph *mtg_read_bcalm2(const char *path, uint64_t k, mtg_unitigs **unitigs_o
     *unitigs_out = new mtg_unitigs{st};
     return g;
 }
+// ---- the plain unitig FASTA route: (k-1)-mer join on the GPU (fasta_in_device.hip) ----
+static thread_local FastaJoinTimes g_last_fasta_in;
+mtg_graph *mtg_read_fasta(const char *path, uint64_t k, int device_id, mtg_unitigs **unitigs_out) {
+    if (!unitigs_out) MTG_DIE("mtg_read_fasta: null argument");
+    UnitigStore *st = nullptr;
+    HostGraph *h = read_fasta(path, k, device_id, &st, &g_last_fasta_in);
+    mtg_graph *g = new mtg_graph{std::move(*h)};
+    delete h;
+    *unitigs_out = new mtg_unitigs{st};
+    return g;
+}
+mtg_graph *mtg_graph_from_sequences(const char *data, const uint64_t *offsets, uint64_t n, uint64_t k, int device_id) {
+    HostGraph *h = device_graph_from_sequences(data, offsets, n, k, device_id, &g_last_fasta_in);
+    mtg_graph *g = new mtg_graph{std::move(*h)};
+    delete h;
+    return g;
+}
+void mtg_last_fasta_in_times(double out[6]) {
+    const FastaJoinTimes &t = g_last_fasta_in;
+    out[0] = t.parse_ms; out[1] = t.upload_ms; out[2] = t.kernel_ms; out[3] = t.download_ms; out[4] = t.build_ms; out[5] = (double)t.bytes;
+}
 uint64_t mtg_unitigs_count(const mtg_unitigs *u) { return u->s->off.size() - 1; }
 const char *mtg_unitigs_data(const mtg_unitigs *u) { return u->s->data.data(); }
 const uint64_t *mtg_unitigs_offsets(const mtg_unitigs *u) { return u->s->off.data(); }

@@ -1,0 +1,58 @@
+// fasta_in.cpp -- the plain unitig FASTA input route (`--fa-in X -k K`, bin.rs:71-75, 891-901): the host half. Parses the records
+// into the sequence store; the graph comes from the (k-1)-mer join on the GPU (fasta_in_device.hip, whose header states the
+// contract).
+//
+// Format: `>` header lines with any text (BCALM2's `L:` annotations included: they are not read), then the sequence on one or
+// more lines, either case. Empty lines are skipped, `.gz` inputs are inflated with zlib (gzopen also reads plain files). The same
+// line reader and alphabet rule as the BCALM2 route (bcalm2.cpp).
+#include <zlib.h>
+
+#include <chrono>
+#include <string>
+
+#include "device.hpp"
+#include "fasta_lines.hpp"
+#include "host_graph.hpp"
+
+namespace mtg {
+
+HostGraph *read_fasta(const char *path, uint64_t k, int device_id, UnitigStore **store_out, FastaJoinTimes *times) {
+    if (!path || !store_out) MTG_DIE("mtg_read_fasta: null argument");
+    if (k < 2) MTG_DIE("mtg_read_fasta: k must be >= 2");
+    const auto t0 = std::chrono::steady_clock::now();
+    gzFile f = gzopen(path, "rb");
+    if (!f) MTG_DIE("cannot open %s", path);
+    gzbuffer(f, 1 << 20);
+    UnitigStore *st = new UnitigStore();
+    st->off.push_back(0);
+    std::string line;
+    bool have_record = false;
+    while (read_line(f, line)) {
+        if (line.empty()) continue;
+        if (line[0] == '>') {
+            if (have_record) st->off.push_back(st->data.size());
+            have_record = true;
+        } else {
+            if (!have_record) MTG_DIE("%s: sequence data before the first header", path);
+            for (char &c : line) {
+                if (c >= 'a' && c <= 'z') c = (char)(c - 'a' + 'A');
+                if (c != 'A' && c != 'C' && c != 'G' && c != 'T') MTG_DIE("%s: character '%c' is not in the DNA alphabet", path, c);
+            }
+            st->data += line;
+        }
+    }
+    gzclose(f);
+    if (have_record) st->off.push_back(st->data.size());
+    const uint64_t U = st->off.size() - 1;
+    for (uint64_t u = 0; u < U; u++) {
+        const uint64_t len = st->off[u + 1] - st->off[u];
+        if (len < k) MTG_DIE("%s: record %llu has length %llu < k = %llu", path, (unsigned long long)u, (unsigned long long)len, (unsigned long long)k);
+    }
+    const double parse_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    HostGraph *g = device_graph_from_sequences(st->data.data(), st->off.data(), U, k, device_id, times);
+    if (times) times->parse_ms = parse_ms;
+    *store_out = st;
+    return g;
+}
+
+}  // namespace mtg

@@ -5,7 +5,7 @@
 // overlap with what is already written (offset k-1 after an original edge, k-1-weight after a dummy edge, :533-537; a backwards
 // edge appends revcomp(seq[0..len-offset]), :567-596), nothing for dummy edges (:519-531), "\n" at the end (:601).
 //
-// Layout: the unitig store is packed to 2 bits per base on the device (only ACGT is representable, like the reference's
+// Layout: the unitig store is packed to 2 bits per base on the device (pack_device.hpp; only ACGT is representable, like the reference's
 // DnaAlphabet store; anything else aborts). Every walk position p (one edge of one walk) owns an output region
 //   [header bytes if p starts a walk (incl. the "\n" that closes the previous walk)] [its characters]
 // whose start is an exclusive prefix sum; the writing kernel is OUTPUT-centric: a workgroup takes 256 consecutive positions, its
@@ -19,6 +19,7 @@
 
 #include "device.hpp"
 #include "hip_util.hpp"
+#include "pack_device.hpp"
 
 namespace mtg {
 
@@ -31,30 +32,6 @@ namespace mtg {
 namespace {
 
 constexpr int SP_BLOCK = 256;
-
-__device__ __forceinline__ uint32_t base_code(unsigned char c) {  // A C G T (either case) -> 0..3, anything else -> 4
-    switch (c) {
-        case 'A': case 'a': return 0;
-        case 'C': case 'c': return 1;
-        case 'G': case 'g': return 2;
-        case 'T': case 't': return 3;
-        default: return 4;
-    }
-}
-
-// 16 bases per 32-bit word, base b at bits [2b, 2b+2)
-__global__ void pack_kernel(const char *ascii, uint64_t n_bases, uint32_t *packed, unsigned long long *bad) {
-    const uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const uint64_t b0 = w * 16;
-    if (b0 >= n_bases) return;
-    uint32_t v = 0;
-    for (int i = 0; i < 16 && b0 + i < n_bases; i++) {
-        const uint32_t c = base_code((unsigned char)ascii[b0 + i]);
-        if (c > 3) { atomicMin(bad, (unsigned long long)(b0 + i)); continue; }
-        v |= c << (2 * i);
-    }
-    packed[w] = v;
-}
 
 __device__ __forceinline__ uint32_t digits_of(uint64_t v) {
     uint32_t d = 1;
