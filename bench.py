@@ -7,7 +7,13 @@ rank's block of sources (GPU) -> [N>1: one all-gather of candidate lists over RC
 replay -> dummy insertion + Eulerisation -> Euler bicycle decomposition -> cut into tigs (host, rank 0)
 -> graph reset (drop the dummy edges again). Rank 0 prints ONE JSON line.
 
+A plain run does only what the headline needs: set up, warm up, time the steps, [--dump-outputs], count the step's SSSP edges
+(the unit of `value`) and print the line. `--full` adds everything else the line can carry, each measured in runs of its own:
+device_mode, tig_download_ms, cold_step_ms, one_shot, clib_route, roofline (+ visited_per_step), roofline_stages, cpu_baseline,
+seeds and full_size.
+
     python bench.py --gpus 1 --steps 3 --warmup 1
+    python bench.py --gpus 1 --steps 3 --warmup 1 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus 8 --steps 3 --warmup 1
 """
@@ -192,6 +198,10 @@ def host_cores() -> int:
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, measure every other block of the line (device_mode, cold steps, one_shot, clib_route, "
+                         "rooflines, cpu_baseline, seeds, full_size); the --no-* / --extra-seeds / --device-mode-steps / "
+                         "--full-size-log2 options below select among them")
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=2)  # (the second reference-order finish of a graph page-locks its record arena: ~0.5 s, once)
     ap.add_argument("--workload", choices=["g_csr", "g_seq"], default="g_csr",
@@ -253,8 +263,8 @@ def main():
     k = args.k
     # ---- the consuming one-shot call (clib.rs:280-291: every real call of the reference is a first call), each Euler mode in a
     # process of its own, before this process takes any device memory ----
-    one_shot = run_one_shot(args) if (world == 1 and args.one_shot and args.workload == "g_csr") else None
-    clib_route = run_clib_route(args) if (world == 1 and args.one_shot and args.workload == "g_csr") else None
+    one_shot = run_one_shot(args) if (args.full and world == 1 and args.one_shot and args.workload == "g_csr") else None
+    clib_route = run_clib_route(args) if (args.full and world == 1 and args.one_shot and args.workload == "g_csr") else None
     # fixed total graph (strong scaling): the same unitig graph on every rank, sources block-partitioned.
     # G-csr is generated ON each rank's GPU (csrc/synth_device.hip, the twin of synth.g_csr): seconds, no numpy argsort.
     t_gen = time.perf_counter()
@@ -416,7 +426,7 @@ def main():
     # nothing kept from an earlier call -- the library's device block cache is released, the graph has no device buckets, no
     # page-locked arena, the candidate buffers are new. Each mode gets a graph of its own; the device-graph build is reported beside.
     cold = None
-    if world == 1 and args.cold_steps and args.workload == "g_csr":
+    if args.full and world == 1 and args.cold_steps and args.workload == "g_csr":
         cold = {}
         for name, mode in (("device", api.EulerMode.Device), ("host", euler_mode)):
             if name == "host" and args.euler == "device":
@@ -453,7 +463,7 @@ def main():
     # pool serves a mode best right after that mode's own warm-up step. ----
     device_mode = None
     dm_steps = args.steps if args.device_mode_steps is None else args.device_mode_steps
-    if args.euler == "host" and dm_steps > 0:
+    if args.full and args.euler == "host" and dm_steps > 0:
         dm_kernel_ms: list[float] = []
         dm_ms, dm_acc = timed_region(api.EulerMode.Device, 1, dm_steps, dm_kernel_ms, [])
         tig_dl: list[float] = []
@@ -483,8 +493,10 @@ def main():
     del last_tigs
     # what delivering the step's tigs to the host as walks costs on top (the reference's compute_tigs always ends with them in host
     # memory; rounds 1-4 ended every timed step with that copy): the same arrays in either Euler mode, so the device-mode measurement
-    # is reused when there is one, else one more untimed step measures it
-    if device_mode is not None:  # (the same branch on every rank: the extra step below gathers and ends in a barrier)
+    # is reused when there is one, else one more untimed step measures it (--full only)
+    if not args.full:
+        tig_download_ms = None
+    elif device_mode is not None:  # (the same branch on every rank: the extra step below gathers and ends in a barrier)
         tig_download_ms = device_mode["tig_download_ms"]  # (measured on rank 0, which finishes; None elsewhere)
     elif not args.host_replay and not args.host_finish:
         tig_dl2: list[float] = []
@@ -499,7 +511,8 @@ def main():
     lo, hi = (ranges_by_work if ranges_by_work is not None else mdist.partition_sources(S, world))[rank]
     stats = dev.sssp_count(lo, hi, stream)
     # ... and what the goal-directed search really visits (pruned by the nearest-in-node lower bounds): the bytes the stage needs
-    visited = dev.sssp_count_visited(lo, hi, stream) if dev.prunes() else None
+    # (--full: the roofline's units)
+    visited = dev.sssp_count_visited(lo, hi, stream) if args.full and dev.prunes() else None
     local_kernel_ms = float(np.mean(kernel_ms)) if kernel_ms else 0.0
     vz = visited or {"relaxed_edges": 0, "settled_nodes": 0, "emitted": 0, "sources": 0}
     tot = torch.tensor([stats["relaxed_edges"], stats["settled_nodes"], stats["emitted"], stats["relax_attempts"],
@@ -516,7 +529,11 @@ def main():
     total_visited = dict(relaxed_edges=tot[5], settled_nodes=tot[6], emitted=tot[7], searched_sources=tot[8]) if visited else None
 
     device_graph_bytes = dev.graph_bytes()
-    if rank == 0:
+    # (the number of candidates = the sum of the lists' lengths; the pool holds them in per-wave chunks with unused tails, whose
+    # number depends on how the sources are split over ranks)
+    if rank == 0 and count_ref[0] is not None:
+        result_info["candidates"] = int(count_ref[0].to(torch.int64).sum().item())
+    if rank == 0 and args.full:
         # roofline of the dominant GPU stage of the sharded part (the SSSP stage = its level kernels) on THIS rank's launch.
         # Bytes: SURVEY 8d's per-unit figures x the units the launch really processes -- with the goal-directed pruning that is the
         # visited set (mtg_sssp_count_visited), not the full balls; the full-ball figure is kept beside it as the throughput in the
@@ -567,10 +584,6 @@ def main():
             roofline["pruned_search_pays_off_after_steps"] = (int(np.ceil(pre_ms / gain)) if gain > 0 and pre_ms > 0 else None)
         # ---- the other GPU stages of the step, each against the HBM roofline: GPU time from HIP events inside the engine (on the
         # stream the kernels run on), algorithmic bytes from stage_models(), counter traffic from profiles/stage_traffic.json ----
-        # (the number of candidates = the sum of the lists' lengths; the pool holds them in per-wave chunks with unused tails, whose
-        # number depends on how the sources are split over ranks)
-        if count_ref[0] is not None:
-            result_info["candidates"] = int(count_ref[0].to(torch.int64).sum().item())
         roofline_stages = None
         if world == 1 and (stage_ms["host"] or stage_ms["device"]):
             count_last = count_ref[0]
@@ -641,47 +654,51 @@ def main():
             api.release_device_memory(local_rank)
             time.sleep(1.0)  # (let the driver settle after ~30 GB of frees: DESIGN 9)
             full_size = full_size_step(args, k, local_rank)
+    if rank == 0:
         value = total_stats["relaxed_edges"] / (ms_per_step * 1e-3)
         out = {
             "metric": "greedy-matchtigs SSSP edges/s, full-ball-equivalent edges (the edges a full-ball Dijkstra of every source examines -- the "
                       "pruned search examines fewer for the same lists, 'visited_per_step') / whole hot-path step: classify+SSSP+claim+Euler+cut",
             "value": round(value, 1), "unit": "edges/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(ms_per_step, 3), "wall_clock_s": round(ms_per_step / 1e3, 4), "higher_is_better": True,
-            # (the timed step ends with the tigs in HBM; the variant that ends with them on the host as walks, comparable with rounds 1-4
-            # and with a CPU compute_tigs: ms_per_step + the measured copy)
-            "tig_download_ms": tig_download_ms,
-            "ms_per_step_with_tigs_on_host": None if tig_download_ms is None else round(ms_per_step + tig_download_ms, 3),
             "scaling": "strong", "vs_baseline": None, "dtype": "u32/u64 integer", "data": "synthetic",
             "config": {"workload": f"{workload}; |V|={n_nodes}, |E|={n_edges}; sources block-partitioned over ranks",
                        "V": n_nodes, "E": n_edges, "k": k, "sources": result_info.get("S"),
                        "pairs": result_info.get("pairs"), "tigs": result_info.get("tigs"),
                        "candidates": result_info.get("candidates"), "parallelism": f"sources/{world}"},
             "units_per_step": total_stats,
-            "visited_per_step": total_visited,
             "phases_ms": {kk: round(v / max(args.steps, 1) * 1e3, 3) for kk, v in phases_acc.items()},
             "euler_mode": args.euler,
-            "device_mode": device_mode,
-            "euler_device_ms_per_step": None if device_mode is None else device_mode["ms_per_step"],
             # the stages that shard over ranks, max over ranks (the whole-step curve is flat by design: rank 0 finishes alone)
             "scaling_stages_ms": {"sssp_kernels": round(kmax[0], 4), "sssp_stage": round(kmax[1], 4), "allgather": round(kmax[2], 4)},
-            "level0_finish_rate": (round(1.0 - kernels[1]["sources"] / max(kernels[0]["sources"], 1), 6) if len(kernels) > 1 else 1.0) if kernels else None,
             "setup_s": round(t_gen, 2), "setup_graph_s": round(t_graph, 2),
             "device_graph_bytes": device_graph_bytes,
-            "roofline": roofline,
-            "roofline_stages": roofline_stages,
-            "one_shot": one_shot,
-            "clib_route": clib_route,
-            "cold_step_ms": cold,
-            "full_size": full_size,
             # claim replay (one cooperative kernel): cost model = source visits x (32-B touch record + 8-B state and 8-B reservation
             # word for the source's own binode and for each of its ~1.2 live candidates) + 64-bit atomics of the failed visits
             "replay": {"rounds": result_info.get("replay_rounds"), "source_visits": result_info.get("replay_visits"),
                        "model_bytes": None if result_info.get("replay_visits") is None else int(result_info["replay_visits"] * (32 + 16 + 1.2 * 16)),
                        "ms": round(phases_acc.get("replay", 0.0) / max(args.steps, 1) * 1e3, 3)},
-            "cpu_baseline": cpu_baseline,
-            "vs_cpu_baseline_same_stage": None if not cpu_baseline else round(cpu_baseline["gpu_same_stage_edges_per_s"] / max(cpu_baseline["value"], 1e-9), 2),
-            "seeds": extra_seeds,
         }
+        if args.full:
+            out.update({
+                # (the timed step ends with the tigs in HBM; the variant that ends with them on the host as walks, comparable with rounds 1-4
+                # and with a CPU compute_tigs: ms_per_step + the measured copy)
+                "tig_download_ms": tig_download_ms,
+                "ms_per_step_with_tigs_on_host": None if tig_download_ms is None else round(ms_per_step + tig_download_ms, 3),
+                "visited_per_step": total_visited,
+                "device_mode": device_mode,
+                "euler_device_ms_per_step": None if device_mode is None else device_mode["ms_per_step"],
+                "level0_finish_rate": (round(1.0 - kernels[1]["sources"] / max(kernels[0]["sources"], 1), 6) if len(kernels) > 1 else 1.0) if kernels else None,
+                "roofline": roofline,
+                "roofline_stages": roofline_stages,
+                "one_shot": one_shot,
+                "clib_route": clib_route,
+                "cold_step_ms": cold,
+                "full_size": full_size,
+                "cpu_baseline": cpu_baseline,
+                "vs_cpu_baseline_same_stage": None if not cpu_baseline else round(cpu_baseline["gpu_same_stage_edges_per_s"] / max(cpu_baseline["value"], 1e-9), 2),
+                "seeds": extra_seeds,
+            })
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()

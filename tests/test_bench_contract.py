@@ -1,4 +1,5 @@
-"""bench.py's output contract (one JSON line with the driver's keys plus roofline and cpu_baseline), on a small graph."""
+"""bench.py's output contract on a small graph: one JSON line with the driver's keys; with --full also roofline, cpu_baseline and
+the other blocks that take runs of their own."""
 import json
 import subprocess
 import sys
@@ -14,7 +15,7 @@ def test_bench_json_line(product_lib):
     if product_lib.mtg_device_count() < 1:
         pytest.fail("needs a GPU")
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--log2-edges", "19",
-                        "--cpu-baseline-seconds", "2"], capture_output=True, text=True, cwd=str(ROOT), timeout=600)
+                        "--cpu-baseline-seconds", "2", "--full"], capture_output=True, text=True, cwd=str(ROOT), timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -66,6 +67,27 @@ def test_bench_json_line(product_lib):
     cb = d["cpu_baseline"]
     assert cb["kind"] == "port" and cb["cores"] == 1 and cb["value"] > 0 and cb["sample"]
     assert cb["pairs"] == d["config"]["pairs"] and cb["tigs"] == d["config"]["tigs"]   # the CPU port and the GPU path agree
+
+
+@pytest.mark.gpu
+def test_bench_plain_line(product_lib):
+    """Without --full the line carries the headline alone: the driver's keys, none of the blocks that take runs of their own."""
+    if product_lib.mtg_device_count() < 1:
+        pytest.fail("needs a GPU")
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--log2-edges", "19"],
+                       capture_output=True, text=True, cwd=str(ROOT), timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config", "units_per_step"):
+        assert key in d, key
+    assert d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1 and d["unit"] == "edges/s" and d["higher_is_better"] is True
+    assert d["ms_per_step"] > 0 and d["config"]["tigs"] > 0 and d["config"]["candidates"] > 0
+    assert abs(d["value"] - d["units_per_step"]["relaxed_edges"] / (d["ms_per_step"] * 1e-3)) <= 1e-3 * d["value"]
+    for key in ("roofline", "roofline_stages", "visited_per_step", "cpu_baseline", "device_mode", "tig_download_ms", "cold_step_ms",
+                "one_shot", "clib_route", "full_size", "seeds"):
+        assert key not in d, key
 
 
 def _load_bench():

@@ -68,7 +68,7 @@ def test_bench_two_ranks_one_process_per_gpu(product_lib):
     two = product_lib.mtg_device_count() >= 2
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29531", str(root / "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--log2-edges", "19",
-           "--no-cpu-baseline"] + ([] if two else ["--backend", "gloo", "--single-device"])
+           "--no-cpu-baseline", "--full"] + ([] if two else ["--backend", "gloo", "--single-device"])
     r = subprocess.run(cmd, capture_output=True, text=True, cwd=str(root), timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
