@@ -461,6 +461,33 @@ mtg_graph *mtg_graph_from_sequences(const char *data, const uint64_t *offsets, u
 /* Of the last mtg_read_fasta / mtg_graph_from_sequences on this thread: {parse ms (0 for the in-memory entry), upload ms, join
  * kernels ms (HIP events), download ms, graph build ms, bytes the join kernels must move at the least}. */
 void mtg_last_fasta_in_times(double out[6]);
+/* Any FASTA file (optionally `.gz`; headers with any text, sequences on one or more lines, either case) as a sequence store: no graph
+ * and no length rule -- a record shorter than k is legal in a file another tool wrote. Aborts on non-ACGT characters. */
+void mtg_read_sequences(const char *path, mtg_unitigs **store_out);
+/* Do two sequence sets hold the same k-mers? (kmer_compare_device.hip). A set is concatenated ASCII plus n + 1 offsets
+ * (offsets[0] = 0; the layout of mtg_unitigs_data / _offsets). Its k-mers are the windows of length k inside one record, compared by
+ * their canonical form (the lexicographically smaller of x and rc(x), A < C < G < T; lower case equals upper case). Records shorter
+ * than k contribute nothing; k >= 1, even k included; a character outside ACGT aborts. Exact (no probabilistic structure) and a
+ * function of the inputs alone. Computed on GPU `device_id`: there is no CPU path. Limit: fewer than 2^40 - 1 bases in A and B
+ * together. The sets are equal iff only_in_a == only_in_b == 0; B repeats occurrences_b - distinct_b k-mers. */
+typedef struct mtg_kmer_comparison {
+    uint64_t records_a, records_b;         /* as given */
+    uint64_t characters_a, characters_b;   /* as given */
+    uint64_t occurrences_a, occurrences_b; /* windows: sum over the records of max(0, len - k + 1) */
+    uint64_t distinct_a, distinct_b;       /* distinct canonical k-mers */
+    uint64_t common, only_in_a, only_in_b; /* sizes of A and B, A without B, B without A: distinct_a = common + only_in_a, likewise for b */
+    /* the occurrence in A with the smallest (record, position) whose k-mer is not in B; UINT64_MAX when there is none */
+    uint64_t first_only_in_a_record, first_only_in_a_pos;
+    uint64_t first_only_in_b_record, first_only_in_b_pos; /* the same for B */
+} mtg_kmer_comparison;
+void mtg_compare_kmer_sets(const char *seq_a, const uint64_t *off_a, uint64_t n_a, const char *seq_b, const uint64_t *off_b,
+                           uint64_t n_b, uint64_t k, int device_id, mtg_kmer_comparison *out);
+/* The same over two stores as mtg_read_bcalm2 / mtg_read_fasta / mtg_read_sequences hand them out. */
+void mtg_compare_kmer_sets_stores(const mtg_unitigs *store_a, const mtg_unitigs *store_b, uint64_t k, int device_id,
+                                  mtg_kmer_comparison *out);
+/* Of the last comparison on this thread, in ms: {upload (host clock), pack, insert A (with the table's fill), insert B, count (with
+ * the witness passes, when there is a difference) -- HIP events around the kernels --, the whole call (host clock)}. */
+void mtg_last_kmer_compare_times(double out[6]);
 uint64_t mtg_unitigs_count(const mtg_unitigs *u);
 const char *mtg_unitigs_data(const mtg_unitigs *u);        /* concatenated ASCII sequences */
 const uint64_t *mtg_unitigs_offsets(const mtg_unitigs *u); /* count + 1 offsets into data */

@@ -4,7 +4,8 @@ Flag names, defaults and exclusivity rules follow /root/reference/src/bin.rs:56-
 the engine (the rest of the reference CLI -- GFA input, pathtigs -- is out of scope). Two inputs are served:
 `--bcalm-in` (BCALM2/GGCAT FASTA whose `L:` annotations carry the links) and `--fa-in` (plain unitig FASTA, no topology: the
 graph comes from the (k-1)-mer overlaps of the unitig ends, joined on the GPU). All work happens inside
-libmatchtigs.so; this file only parses flags and prints the reference's closing log line (bin.rs:1209-1211).
+libmatchtigs.so; this file only parses flags and prints the reference's closing log line (bin.rs:1209-1211). `--verify` and
+`--verify-fa` (not in the reference) check on the GPU that tigs spell exactly the input's k-mer set.
 """
 from __future__ import annotations
 
@@ -32,6 +33,12 @@ def main(argv=None) -> int:
     ap.add_argument("--blossom5-command", default="blossom5", help="the command used to run blossom5 (bin.rs:151-153)")
     ap.add_argument("--compression-level", type=int, default=6, help="0-9 (bin.rs:203-218)")
     ap.add_argument("--device", type=int, default=0, help="GPU ordinal (not in the reference)")
+    ap.add_argument("--verify", action="store_true",
+                    help="after writing, check on the GPU that each algorithm's tigs spell exactly the input's k-mer set; exit 1 if not "
+                         "(not in the reference)")
+    ap.add_argument("--verify-fa", action="append", metavar="PATH",
+                    help="check an existing tig fasta (optionally .gz) against the input's k-mer set; repeatable; computes nothing "
+                         "(not in the reference)")
     args = ap.parse_args(argv)
 
     n_inputs = sum(x is not None for x in (args.bcalm_in, args.gfa_in, args.fa_in))
@@ -48,7 +55,7 @@ def main(argv=None) -> int:
     if args.matchtigs_duplication_bitvector_out and not (args.matchtigs_fa_out or args.matchtigs_gfa_out):
         ap.error("--matchtigs-duplication-bitvector-out needs --matchtigs-fa-out or --matchtigs-gfa-out (bin.rs:955-957)")
     if not (args.greedytigs_fa_out or args.eulertigs_fa_out or args.greedytigs_gfa_out or args.eulertigs_gfa_out
-            or args.greedytigs_duplication_bitvector_out or args.matchtigs_fa_out or args.matchtigs_gfa_out):
+            or args.greedytigs_duplication_bitvector_out or args.matchtigs_fa_out or args.matchtigs_gfa_out or args.verify_fa):
         ap.error("nothing to do: give --greedytigs-fa-out / --greedytigs-gfa-out and/or --eulertigs-fa-out / --eulertigs-gfa-out")
 
     from . import api
@@ -60,6 +67,23 @@ def main(argv=None) -> int:
         graph, store = api.read_fasta(args.fa_in, args.k, args.device)
     print(f"Loaded {len(store)} unitigs: {graph.node_count()} nodes, {graph.edge_count()} edges in {time.perf_counter() - t0:.1f}s",
           file=sys.stderr)
+
+    def report(what: str, tigs, cmp) -> bool:
+        """The verification line of one tig set; names the first missing and the first foreign k-mer when there is one."""
+        line = f"Verifying {what}: {cmp.describe()}"
+        if cmp.only_in_a:
+            line += (f"; first missing k-mer: input record {cmp.first_only_in_a_record + 1} position {cmp.first_only_in_a_pos} "
+                     f"{api.kmer_at(store, cmp.first_only_in_a_record, cmp.first_only_in_a_pos, args.k)}")
+        if cmp.only_in_b:
+            line += (f"; first foreign k-mer: tig record {cmp.first_only_in_b_record + 1} position {cmp.first_only_in_b_pos} "
+                     f"{api.kmer_at(tigs, cmp.first_only_in_b_record, cmp.first_only_in_b_pos, args.k)}")
+        print(line, file=sys.stderr)
+        return cmp.equal
+
+    all_equal = True
+    for path in args.verify_fa or ():
+        tigs = api.read_sequences(path)
+        all_equal &= report(path, tigs, api.compare_kmer_sets(store, tigs, args.k, args.device))
     for name, alg, out, gfa, dup in (("matchtigs", 4, args.matchtigs_fa_out, args.matchtigs_gfa_out,
                                       args.matchtigs_duplication_bitvector_out),
                                      ("eulertigs", 3, args.eulertigs_fa_out, args.eulertigs_gfa_out, None),
@@ -74,11 +98,13 @@ def main(argv=None) -> int:
             matcher = shutil.which(args.blossom5_command) or args.blossom5_command
             cfg = api.MatchtigAlgorithmConfiguration(args.threads, args.k, out or gfa, matcher, device_id=args.device)
         r = api.compute_tigs_to_fasta_file(graph, store, alg, args.k, out, args.compression_level, args.device, gfa_path=gfa,
-                                           duplication_bitvector_path=dup, configuration=cfg)
+                                           duplication_bitvector_path=dup, configuration=cfg, verify=args.verify)
         graph.reset()  # the reference clones the graph per algorithm (bin.rs:1069)
         print(f"Computing {name} took {r['compute_s']:.1f}s and writing took {r['write_s']:.1f}s "
               f"({r['tigs']} tigs, {r['fasta_bytes']} fasta bytes)", file=sys.stderr)
-    return 0
+        if args.verify:
+            all_equal &= report(f"{name} ({out or 'spelled in memory'})", r["verify_tigs"], r["verify"])
+    return 0 if all_equal else 1
 
 
 if __name__ == "__main__":

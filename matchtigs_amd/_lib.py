@@ -74,6 +74,18 @@ class MtgMatchingStats(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class MtgKmerComparison(C.Structure):
+    """mtg_kmer_comparison (include/mtg_engine.h)."""
+
+    _fields_ = [(n, C.c_uint64) for n in (
+        "records_a", "records_b", "characters_a", "characters_b", "occurrences_a", "occurrences_b", "distinct_a", "distinct_b",
+        "common", "only_in_a", "only_in_b", "first_only_in_a_record", "first_only_in_a_pos", "first_only_in_b_record",
+        "first_only_in_b_pos")]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class MtgDijkstraPerformanceData(C.Structure):
     _fields_ = [
         ("dijkstras", C.c_uint64),
@@ -206,6 +218,10 @@ def load():
         "mtg_read_fasta": (vp, [C.c_char_p, u64, C.c_int, P(vp)]),
         "mtg_graph_from_sequences": (vp, [vp, vp, u64, u64, C.c_int]),
         "mtg_last_fasta_in_times": (None, [P(C.c_double)]),
+        "mtg_read_sequences": (None, [C.c_char_p, P(vp)]),
+        "mtg_compare_kmer_sets": (None, [vp, vp, u64, vp, vp, u64, u64, C.c_int, P(MtgKmerComparison)]),
+        "mtg_compare_kmer_sets_stores": (None, [vp, vp, u64, C.c_int, P(MtgKmerComparison)]),
+        "mtg_last_kmer_compare_times": (None, [P(C.c_double)]),
         "mtg_unitigs_count": (u64, [vp]),
         "mtg_unitigs_data": (vp, [vp]),
         "mtg_unitigs_offsets": (vp, [vp]),

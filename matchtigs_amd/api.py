@@ -853,11 +853,113 @@ def last_fasta_in_times() -> dict:
     return dict(zip(("parse_ms", "upload_ms", "kernel_ms", "download_ms", "build_ms", "bytes"), list(out)))
 
 
+def read_sequences(path: str) -> UnitigStore:
+    """Any FASTA file (optionally .gz, multi-line records, either case) as a sequence store: no graph, no length rule, no GPU."""
+    st = C.c_void_p()
+    _lib.load().mtg_read_sequences(str(path).encode(), C.byref(st))
+    return UnitigStore(st.value)
+
+
+_NONE64 = 2 ** 64 - 1
+
+
+@dataclass(frozen=True)
+class KmerComparison:
+    """mtg_kmer_comparison (include/mtg_engine.h): the k-mer sets of two sequence sets A and B, in exact integers. The witnesses
+    (first_only_in_*: record and position of the first occurrence whose k-mer the other set lacks) are 2^64 - 1 when there is none."""
+
+    records_a: int
+    records_b: int
+    characters_a: int
+    characters_b: int
+    occurrences_a: int
+    occurrences_b: int
+    distinct_a: int
+    distinct_b: int
+    common: int
+    only_in_a: int
+    only_in_b: int
+    first_only_in_a_record: int
+    first_only_in_a_pos: int
+    first_only_in_b_record: int
+    first_only_in_b_pos: int
+
+    @property
+    def equal(self) -> bool:
+        return self.only_in_a == 0 and self.only_in_b == 0
+
+    @property
+    def repeated_a(self) -> int:
+        return self.occurrences_a - self.distinct_a
+
+    @property
+    def repeated_b(self) -> int:
+        return self.occurrences_b - self.distinct_b
+
+    def describe(self) -> str:
+        """One line: B (the tigs) against A (the input)."""
+        head = (f"{self.distinct_b} distinct k-mers in {self.occurrences_b} occurrences ({self.repeated_b} repeated), "
+                f"{self.characters_a} -> {self.characters_b} characters")
+        if self.equal:
+            return f"k-mer sets equal: {head}"
+        return f"k-mer sets DIFFER: {self.only_in_a} missing, {self.only_in_b} foreign; {head}"
+
+
+def _sequence_arrays(x):
+    """UnitigStore, list of str or (uint8 array, offsets) -> (data pointer or bytes, offsets pointer, count, keep-alive)."""
+    if isinstance(x, UnitigStore):
+        L = _lib.load()
+        return L.mtg_unitigs_data(x.handle), L.mtg_unitigs_offsets(x.handle), len(x), x
+    if isinstance(x, tuple):
+        cat = np.ascontiguousarray(x[0], np.uint8)
+        off = np.ascontiguousarray(x[1], np.uint64)
+    else:
+        cat = np.frombuffer("".join(x).encode(), np.uint8)
+        off = np.zeros(len(x) + 1, np.uint64)
+        off[1:] = np.cumsum([len(u) for u in x])
+    if len(off) < 1:
+        raise ValueError("offsets must hold count + 1 entries")
+    return (_ptr(cat) if len(cat) else None), _ptr(off), len(off) - 1, (cat, off)
+
+
+def compare_kmer_sets(a, b, k: int, device_id: int = 0) -> KmerComparison:
+    """Do the sequence sets a and b hold the same canonical k-mers? Computed on GPU `device_id` (mtg_compare_kmer_sets,
+    DESIGN.md 15). a, b: UnitigStore, list of str, or (uint8 array, offsets)."""
+    L = _lib.load()
+    da, oa, na, keep_a = _sequence_arrays(a)
+    db, ob, nb, keep_b = _sequence_arrays(b)
+    out = _lib.MtgKmerComparison()
+    L.mtg_compare_kmer_sets(da, oa, na, db, ob, nb, k, device_id, C.byref(out))
+    del keep_a, keep_b
+    return KmerComparison(**out.as_dict())
+
+
+def last_kmer_compare_times() -> dict:
+    """Phases of the last compare_kmer_sets on this thread, in ms (HIP events around the kernels; upload and total by the host clock)."""
+    out = (C.c_double * 6)()
+    _lib.load().mtg_last_kmer_compare_times(out)
+    return dict(zip(("upload_ms", "pack_ms", "insert_a_ms", "insert_b_ms", "count_ms", "total_ms"), list(out)))
+
+
+def kmer_at(seqs, record: int, pos: int, k: int) -> str:
+    """The window a witness of a KmerComparison names, as text (upper case)."""
+    if isinstance(seqs, UnitigStore):
+        L = _lib.load()
+        off = np.ctypeslib.as_array(C.cast(L.mtg_unitigs_offsets(seqs.handle), C.POINTER(C.c_uint64)), shape=(len(seqs) + 1,))
+        return C.string_at(L.mtg_unitigs_data(seqs.handle) + int(off[record]) + pos, k).decode().upper()
+    if isinstance(seqs, tuple):
+        start = int(seqs[1][record]) + pos
+        return np.asarray(seqs[0][start:start + k], np.uint8).tobytes().decode().upper()
+    return seqs[record][pos:pos + k].upper()
+
+
 def compute_tigs_to_fasta_file(graph: Bigraph, store: UnitigStore, algorithm: int, k: int, path: Optional[str],
                                compression_level: int = 6, device_id: int = 0, gfa_path: Optional[str] = None,
                                gfa_header: Optional[str] = None, duplication_bitvector_path: Optional[str] = None,
-                               configuration: Optional[GreedytigAlgorithmConfiguration] = None) -> dict:
-    """compute (3 = eulertigs, 5 = greedy matchtigs) + spell + write FASTA and/or GFA, all inside the library."""
+                               configuration: Optional[GreedytigAlgorithmConfiguration] = None, verify: bool = False) -> dict:
+    """compute (3 = eulertigs, 5 = greedy matchtigs) + spell + write FASTA and/or GFA, all inside the library. verify: the result
+    gains "verify", the KmerComparison of `store` with the FASTA file as written and read back (read_sequences) or, without a FASTA
+    path, with the tigs spelled to FASTA in memory on the same GPU."""
     import time
 
     L = _lib.load()
@@ -876,8 +978,24 @@ def compute_tigs_to_fasta_file(graph: Bigraph, store: UnitigStore, algorithm: in
     if duplication_bitvector_path:
         L.mtg_write_tigs_duplication_bitvector_file(graph.handle, w, str(duplication_bitvector_path).encode())
     t2 = time.perf_counter()
+    cmp = None
+    if verify:
+        if path:
+            tigs = read_sequences(path)
+        else:
+            lim, ed, text = C.c_void_p(), C.c_void_p(), C.c_void_p()
+            L.mtg_walks_data(w, C.byref(lim), C.byref(ed))
+            n = L.mtg_write_walks_text_device(graph.handle, n_tigs, lim, ed, k, C.cast(L.mtg_unitigs_data(store.handle), C.c_char_p),
+                                              L.mtg_unitigs_offsets(store.handle), 0, None, spell_dev, C.byref(text))
+            fa = C.string_at(text, n)
+            L.mtg_free(text)
+            tigs = fa.decode().split("\n")[1::2]
+        cmp = compare_kmer_sets(store, tigs, k, spell_dev)
     L.mtg_walks_free(w)
-    return {"tigs": n_tigs, "fasta_bytes": nbytes, "gfa_bytes": gbytes, "compute_s": t1 - t0, "write_s": t2 - t1}
+    r = {"tigs": n_tigs, "fasta_bytes": nbytes, "gfa_bytes": gbytes, "compute_s": t1 - t0, "write_s": t2 - t1}
+    if verify:
+        r["verify"], r["verify_tigs"], r["verify_s"] = cmp, tigs, time.perf_counter() - t2
+    return r
 
 
 def write_duplication_bitvector(graph: Bigraph, tigs) -> bytes:

@@ -122,6 +122,16 @@ struct FastaJoinTimes {
 HostGraph *device_graph_from_sequences(const char *data, const uint64_t *off, uint64_t U, uint64_t k, int device_id, FastaJoinTimes *times);
 // fasta_in.cpp: parse a plain unitig FASTA file (.gz inflated) and join it on `device_id` (times->parse_ms: the parse)
 HostGraph *read_fasta(const char *path, uint64_t k, int device_id, UnitigStore **store_out, FastaJoinTimes *times);
+// fasta_in.cpp: the records of any FASTA file (.gz inflated, multi-line, either case -> upper case) as a sequence store: no graph,
+// no length rule. The reader of read_fasta.
+UnitigStore *read_fasta_records(const char *path);
+// kmer_compare_device.hip: do two sequence sets hold the same canonical k-mers? (the file's header states the contract). times: host
+// wall clock of the upload and of the whole call, HIP-event time of the kernels.
+struct KmerCompareTimes {
+    double upload_ms = 0, pack_ms = 0, insert_a_ms = 0, insert_b_ms = 0, count_ms = 0, total_ms = 0;
+};
+void device_compare_kmer_sets(const char *seq_a, const uint64_t *off_a, uint64_t n_a, const char *seq_b, const uint64_t *off_b, uint64_t n_b,
+                              uint64_t k, int device_id, mtg_kmer_comparison *out, KmerCompareTimes *times);
 void device_candidates_to_host(Device *d, void *stream, std::vector<uint64_t> &cand_start,
                                std::vector<uint32_t> &cand_count, std::vector<uint64_t> &pool);
 

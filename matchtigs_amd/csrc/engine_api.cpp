@@ -634,6 +634,26 @@ void mtg_last_fasta_in_times(double out[6]) {
     const FastaJoinTimes &t = g_last_fasta_in;
     out[0] = t.parse_ms; out[1] = t.upload_ms; out[2] = t.kernel_ms; out[3] = t.download_ms; out[4] = t.build_ms; out[5] = (double)t.bytes;
 }
+// ---- k-mer set comparison on the GPU (kmer_compare_device.hip) ----
+static thread_local KmerCompareTimes g_last_kmer_compare;
+void mtg_compare_kmer_sets(const char *seq_a, const uint64_t *off_a, uint64_t n_a, const char *seq_b, const uint64_t *off_b, uint64_t n_b,
+                           uint64_t k, int device_id, mtg_kmer_comparison *out) {
+    device_compare_kmer_sets(seq_a, off_a, n_a, seq_b, off_b, n_b, k, device_id, out, &g_last_kmer_compare);
+}
+void mtg_compare_kmer_sets_stores(const mtg_unitigs *store_a, const mtg_unitigs *store_b, uint64_t k, int device_id, mtg_kmer_comparison *out) {
+    if (!store_a || !store_b) MTG_DIE("mtg_compare_kmer_sets_stores: null argument");
+    const UnitigStore &a = *store_a->s, &b = *store_b->s;
+    device_compare_kmer_sets(a.data.data(), a.off.data(), a.off.size() - 1, b.data.data(), b.off.data(), b.off.size() - 1, k, device_id, out,
+                             &g_last_kmer_compare);
+}
+void mtg_read_sequences(const char *path, mtg_unitigs **store_out) {
+    if (!path || !store_out) MTG_DIE("mtg_read_sequences: null argument");
+    *store_out = new mtg_unitigs{read_fasta_records(path)};
+}
+void mtg_last_kmer_compare_times(double out[6]) {
+    const KmerCompareTimes &t = g_last_kmer_compare;
+    out[0] = t.upload_ms; out[1] = t.pack_ms; out[2] = t.insert_a_ms; out[3] = t.insert_b_ms; out[4] = t.count_ms; out[5] = t.total_ms;
+}
 uint64_t mtg_unitigs_count(const mtg_unitigs *u) { return u->s->off.size() - 1; }
 const char *mtg_unitigs_data(const mtg_unitigs *u) { return u->s->data.data(); }
 const uint64_t *mtg_unitigs_offsets(const mtg_unitigs *u) { return u->s->off.data(); }

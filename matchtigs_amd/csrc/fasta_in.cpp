@@ -4,7 +4,8 @@
 //
 // Format: `>` header lines with any text (BCALM2's `L:` annotations included: they are not read), then the sequence on one or
 // more lines, either case. Empty lines are skipped, `.gz` inputs are inflated with zlib (gzopen also reads plain files). The same
-// line reader and alphabet rule as the BCALM2 route (bcalm2.cpp).
+// line reader and alphabet rule as the BCALM2 route (bcalm2.cpp). read_fasta_records is that reader on its own (mtg_read_sequences:
+// a tig file someone else wrote, for the k-mer set comparison); read_fasta adds the length rule and the join.
 #include <zlib.h>
 
 #include <chrono>
@@ -16,10 +17,7 @@
 
 namespace mtg {
 
-HostGraph *read_fasta(const char *path, uint64_t k, int device_id, UnitigStore **store_out, FastaJoinTimes *times) {
-    if (!path || !store_out) MTG_DIE("mtg_read_fasta: null argument");
-    if (k < 2) MTG_DIE("mtg_read_fasta: k must be >= 2");
-    const auto t0 = std::chrono::steady_clock::now();
+UnitigStore *read_fasta_records(const char *path) {
     gzFile f = gzopen(path, "rb");
     if (!f) MTG_DIE("cannot open %s", path);
     gzbuffer(f, 1 << 20);
@@ -43,6 +41,14 @@ HostGraph *read_fasta(const char *path, uint64_t k, int device_id, UnitigStore *
     }
     gzclose(f);
     if (have_record) st->off.push_back(st->data.size());
+    return st;
+}
+
+HostGraph *read_fasta(const char *path, uint64_t k, int device_id, UnitigStore **store_out, FastaJoinTimes *times) {
+    if (!path || !store_out) MTG_DIE("mtg_read_fasta: null argument");
+    if (k < 2) MTG_DIE("mtg_read_fasta: k must be >= 2");
+    const auto t0 = std::chrono::steady_clock::now();
+    UnitigStore *st = read_fasta_records(path);
     const uint64_t U = st->off.size() - 1;
     for (uint64_t u = 0; u < U; u++) {
         const uint64_t len = st->off[u + 1] - st->off[u];
