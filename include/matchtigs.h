@@ -16,6 +16,10 @@
  * `matcher_path` -- blossom5 or compatible, found through PATH like the reference's Command::new -- runs as a
  * child process, exactly as in the reference). Id 2 (pathtigs) is outside this engine's scope and aborts with
  * a message saying so.
+ *
+ * These entry points take a graph somebody else compacted. A caller that holds raw sequences (an assembly, haplotypes, another
+ * tool's tigs) gets the unitigs from mtg_compact_unitigs and the graph from mtg_graph_from_sequences (include/mtg_engine.h), both
+ * on the GPU.
  */
 #ifndef MATCHTIGS_H
 #define MATCHTIGS_H

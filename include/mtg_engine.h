@@ -488,6 +488,38 @@ void mtg_compare_kmer_sets_stores(const mtg_unitigs *store_a, const mtg_unitigs 
 /* Of the last comparison on this thread, in ms: {upload (host clock), pack, insert A (with the table's fill), insert B, count (with
  * the witness passes, when there is a difference) -- HIP events around the kernels --, the whole call (host clock)}. */
 void mtg_last_kmer_compare_times(double out[6]);
+/* mtg_read_sequences where a run of characters outside ACGT (the `N` of real assemblies) ends a piece instead of aborting: every
+ * maximal ACGT stretch of a record becomes a record of the store, in file order; empty pieces are dropped. *pieces_cut (may be NULL)
+ * = the runs met. */
+void mtg_read_sequences_split(const char *path, mtg_unitigs **store_out, uint64_t *pieces_cut);
+/* The maximal unitigs of the k-mer set of arbitrary sequences, compacted on GPU `device_id` (compact_device.hip; there
+ * is no CPU path). Input: concatenated ASCII plus n + 1 offsets (offsets[0] = 0), either case; a window is a start position whose k
+ * bases lie inside one record, records shorter than k contribute nothing, a character outside ACGT aborts. S = the canonical k-mers
+ * of all windows. creator(x) = the smallest window start (in the concatenation) whose k-mer is x or rc(x); reading(x) = the string
+ * there. The graph is the one mtg_graph_from_sequences builds from the readings (oriented (k-1)-mers as nodes, each k-mer the edge
+ * prefix -> suffix and its mirror). A node is passable iff it is not its own mirror and has in-degree 1 and out-degree 1 over all
+ * directed edges; a unitig is a maximal walk whose inner nodes are passable, closed when the node between its last and first edge is
+ * passable too. Its leader is its k-mer with the smallest creator; of the walk and its mirror the one on which the leader appears as
+ * reading(leader) is emitted, a closed walk starting at its leader and spelled linearly; unitigs come in increasing order of their
+ * leaders' creators, upper case, edges + k - 1 characters each. The result is a function of the input alone. *out is an ordinary
+ * store (mtg_unitigs_free) that mtg_graph_from_sequences, the writers and mtg_compare_kmer_sets_stores accept. 2 <= k < 2^31, fewer
+ * than 2^40 - 1 bases, fewer than 2^31 - 1 distinct k-mers. */
+typedef struct mtg_compaction {
+    uint64_t records, characters; /* as given */
+    uint64_t windows;             /* sum over the records of max(0, len - k + 1) */
+    uint64_t distinct_kmers;      /* |S| = unitig_characters - (k - 1) * unitigs */
+    uint64_t unitigs, unitig_characters;
+    uint64_t closed_walks;        /* unitigs whose walk is closed */
+    uint64_t longest_unitig_kmers;
+} mtg_compaction;
+void mtg_compact_unitigs(const char *data, const uint64_t *offsets, uint64_t n, uint64_t k, int device_id, mtg_unitigs **out,
+                         mtg_compaction *stats);
+/* The same over a store as mtg_read_sequences / mtg_read_sequences_split hand it out. */
+void mtg_compact_unitigs_store(const mtg_unitigs *in, uint64_t k, int device_id, mtg_unitigs **out, mtg_compaction *stats);
+/* Of the last compaction on this thread: {upload ms (host clock); pack, insert, ids, nodes (with succ), rank (pointer jumping), emit
+ * ms -- HIP events around the kernel phases --; download ms and the whole call (host clock); pointer-jumping rounds; bytes the
+ * kernels must move at the least; peak of live device-arena bytes}. */
+void mtg_last_compact_times(double out[12]);
 uint64_t mtg_unitigs_count(const mtg_unitigs *u);
 const char *mtg_unitigs_data(const mtg_unitigs *u);        /* concatenated ASCII sequences */
 const uint64_t *mtg_unitigs_offsets(const mtg_unitigs *u); /* count + 1 offsets into data */

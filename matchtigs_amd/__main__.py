@@ -3,7 +3,10 @@
 Flag names, defaults and exclusivity rules follow /root/reference/src/bin.rs:56-205, 850-862 for the subset that maps onto
 the engine (the rest of the reference CLI -- GFA input, pathtigs -- is out of scope). Two inputs are served:
 `--bcalm-in` (BCALM2/GGCAT FASTA whose `L:` annotations carry the links) and `--fa-in` (plain unitig FASTA, no topology: the
-graph comes from the (k-1)-mer overlaps of the unitig ends, joined on the GPU). All work happens inside
+graph comes from the (k-1)-mer overlaps of the unitig ends, joined on the GPU). A third, `--seq-in` (not in the
+reference), takes ANY sequences -- an assembly, haplotypes, another tool's tigs; `N` runs split records -- and compacts their k-mer
+set into maximal unitigs on the GPU first, then goes the `--fa-in` way; `--unitigs-fa-out` writes the unitigs of
+any input. All work happens inside
 libmatchtigs.so; this file only parses flags and prints the reference's closing log line (bin.rs:1209-1211). `--verify` and
 `--verify-fa` (not in the reference) check on the GPU that tigs spell exactly the input's k-mer set.
 """
@@ -19,6 +22,10 @@ def main(argv=None) -> int:
     ap.add_argument("--bcalm-in", help="bcalm2/GGCAT unitig fasta (optionally .gz); requires -k (bin.rs:76-83)")
     ap.add_argument("--gfa-in", help="(not served by this engine)")
     ap.add_argument("--fa-in", help="plain unitig fasta (optionally .gz), graph from (k-1)-mer overlaps on the GPU; requires -k (bin.rs:71-75)")
+    ap.add_argument("--seq-in", help="any sequences as fasta (optionally .gz; non-ACGT runs split records): their k-mer set is compacted "
+                                     "into maximal unitigs on the GPU, then as --fa-in; requires -k (not in the reference)")
+    ap.add_argument("--unitigs-fa-out", help="write the input's unitigs as fasta (.gz => gzip): with --seq-in, the GPU compactor's output "
+                                             "(not in the reference)")
     ap.add_argument("-k", type=int, help="k-mer size used to build the de Bruijn graph (bin.rs:139-141)")
     ap.add_argument("-t", "--threads", type=int, default=1, help="accepted; results always equal the 1-thread order (bin.rs:148-149)")
     ap.add_argument("--greedytigs-fa-out", help="write greedy matchtigs as fasta (.gz => gzip) (bin.rs:107-109)")
@@ -41,7 +48,7 @@ def main(argv=None) -> int:
                          "(not in the reference)")
     args = ap.parse_args(argv)
 
-    n_inputs = sum(x is not None for x in (args.bcalm_in, args.gfa_in, args.fa_in))
+    n_inputs = sum(x is not None for x in (args.bcalm_in, args.gfa_in, args.fa_in, args.seq_in))
     if n_inputs == 0:  # bin.rs:855-858
         ap.error("Missing input argument. Specify exactly least one of --fa-in, --gfa-in or --bcalm-in")
     if n_inputs > 1:  # bin.rs:860-862
@@ -49,13 +56,14 @@ def main(argv=None) -> int:
     if args.gfa_in is not None:
         ap.error("only --bcalm-in and --fa-in are served by the MI355X engine (SURVEY.md 8 f-2)")
     if args.k is None:
-        ap.error("--bcalm-in requires -k" if args.bcalm_in is not None else "--fa-in requires -k")
+        ap.error("--bcalm-in requires -k" if args.bcalm_in is not None else
+                 "--seq-in requires -k" if args.seq_in is not None else "--fa-in requires -k")
     if not 0 <= args.compression_level <= 9:
         ap.error("compression level must be in 0..9")
     if args.matchtigs_duplication_bitvector_out and not (args.matchtigs_fa_out or args.matchtigs_gfa_out):
         ap.error("--matchtigs-duplication-bitvector-out needs --matchtigs-fa-out or --matchtigs-gfa-out (bin.rs:955-957)")
     if not (args.greedytigs_fa_out or args.eulertigs_fa_out or args.greedytigs_gfa_out or args.eulertigs_gfa_out
-            or args.greedytigs_duplication_bitvector_out or args.matchtigs_fa_out or args.matchtigs_gfa_out or args.verify_fa):
+            or args.greedytigs_duplication_bitvector_out or args.matchtigs_fa_out or args.matchtigs_gfa_out or args.verify_fa or args.unitigs_fa_out):
         ap.error("nothing to do: give --greedytigs-fa-out / --greedytigs-gfa-out and/or --eulertigs-fa-out / --eulertigs-gfa-out")
 
     from . import api
@@ -63,17 +71,25 @@ def main(argv=None) -> int:
     t0 = time.perf_counter()
     if args.bcalm_in is not None:
         graph, store = api.read_bcalm2(args.bcalm_in, args.k)
+    elif args.seq_in is not None:  # sequences -> unitigs (GPU compaction) -> graph (the --fa-in join on the same store)
+        seqs = api.read_sequences(args.seq_in, split_non_acgt=True)
+        store, compaction = api.compact_unitigs(seqs, args.k, args.device)
+        graph = api.Bigraph.from_sequences(store.arrays(), args.k, args.device)
     else:
         graph, store = api.read_fasta(args.fa_in, args.k, args.device)
-    print(f"Loaded {len(store)} unitigs: {graph.node_count()} nodes, {graph.edge_count()} edges in {time.perf_counter() - t0:.1f}s",
-          file=sys.stderr)
+    loaded = f"Loaded {len(store)} unitigs: {graph.node_count()} nodes, {graph.edge_count()} edges in {time.perf_counter() - t0:.1f}s"
+    if args.seq_in is not None:
+        loaded += f" (compacted from {compaction.describe()}; {seqs.pieces_cut} non-ACGT runs cut)"
+    print(loaded, file=sys.stderr)
+    # what the tigs are verified against: the input as given -- on the --seq-in route the sequences, so that the check covers the compaction
+    truth = seqs if args.seq_in is not None else store
 
     def report(what: str, tigs, cmp) -> bool:
         """The verification line of one tig set; names the first missing and the first foreign k-mer when there is one."""
         line = f"Verifying {what}: {cmp.describe()}"
         if cmp.only_in_a:
             line += (f"; first missing k-mer: input record {cmp.first_only_in_a_record + 1} position {cmp.first_only_in_a_pos} "
-                     f"{api.kmer_at(store, cmp.first_only_in_a_record, cmp.first_only_in_a_pos, args.k)}")
+                     f"{api.kmer_at(truth, cmp.first_only_in_a_record, cmp.first_only_in_a_pos, args.k)}")
         if cmp.only_in_b:
             line += (f"; first foreign k-mer: tig record {cmp.first_only_in_b_record + 1} position {cmp.first_only_in_b_pos} "
                      f"{api.kmer_at(tigs, cmp.first_only_in_b_record, cmp.first_only_in_b_pos, args.k)}")
@@ -83,7 +99,11 @@ def main(argv=None) -> int:
     all_equal = True
     for path in args.verify_fa or ():
         tigs = api.read_sequences(path)
-        all_equal &= report(path, tigs, api.compare_kmer_sets(store, tigs, args.k, args.device))
+        all_equal &= report(path, tigs, api.compare_kmer_sets(truth, tigs, args.k, args.device))
+    if args.unitigs_fa_out:  # one walk per unitig through the tig writer (algorithm 1)
+        r = api.compute_tigs_to_fasta_file(graph, store, 1, args.k, args.unitigs_fa_out, args.compression_level, args.device)
+        graph.reset()
+        print(f"Writing unitigs took {r['write_s']:.1f}s ({r['tigs']} unitigs, {r['fasta_bytes']} fasta bytes)", file=sys.stderr)
     for name, alg, out, gfa, dup in (("matchtigs", 4, args.matchtigs_fa_out, args.matchtigs_gfa_out,
                                       args.matchtigs_duplication_bitvector_out),
                                      ("eulertigs", 3, args.eulertigs_fa_out, args.eulertigs_gfa_out, None),
@@ -98,7 +118,7 @@ def main(argv=None) -> int:
             matcher = shutil.which(args.blossom5_command) or args.blossom5_command
             cfg = api.MatchtigAlgorithmConfiguration(args.threads, args.k, out or gfa, matcher, device_id=args.device)
         r = api.compute_tigs_to_fasta_file(graph, store, alg, args.k, out, args.compression_level, args.device, gfa_path=gfa,
-                                           duplication_bitvector_path=dup, configuration=cfg, verify=args.verify)
+                                           duplication_bitvector_path=dup, configuration=cfg, verify=args.verify, verify_against=truth)
         graph.reset()  # the reference clones the graph per algorithm (bin.rs:1069)
         print(f"Computing {name} took {r['compute_s']:.1f}s and writing took {r['write_s']:.1f}s "
               f"({r['tigs']} tigs, {r['fasta_bytes']} fasta bytes)", file=sys.stderr)

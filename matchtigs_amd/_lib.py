@@ -86,6 +86,16 @@ class MtgKmerComparison(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class MtgCompaction(C.Structure):
+    """mtg_compaction (include/mtg_engine.h)."""
+
+    _fields_ = [(n, C.c_uint64) for n in (
+        "records", "characters", "windows", "distinct_kmers", "unitigs", "unitig_characters", "closed_walks", "longest_unitig_kmers")]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class MtgDijkstraPerformanceData(C.Structure):
     _fields_ = [
         ("dijkstras", C.c_uint64),
@@ -222,6 +232,10 @@ def load():
         "mtg_compare_kmer_sets": (None, [vp, vp, u64, vp, vp, u64, u64, C.c_int, P(MtgKmerComparison)]),
         "mtg_compare_kmer_sets_stores": (None, [vp, vp, u64, C.c_int, P(MtgKmerComparison)]),
         "mtg_last_kmer_compare_times": (None, [P(C.c_double)]),
+        "mtg_read_sequences_split": (None, [C.c_char_p, P(vp), P(u64)]),
+        "mtg_compact_unitigs": (None, [vp, vp, u64, u64, C.c_int, P(vp), P(MtgCompaction)]),
+        "mtg_compact_unitigs_store": (None, [vp, u64, C.c_int, P(vp), P(MtgCompaction)]),
+        "mtg_last_compact_times": (None, [P(C.c_double)]),
         "mtg_unitigs_count": (u64, [vp]),
         "mtg_unitigs_data": (vp, [vp]),
         "mtg_unitigs_offsets": (vp, [vp]),

@@ -822,6 +822,15 @@ class UnitigStore:
     def __len__(self) -> int:
         return int(self._L.mtg_unitigs_count(self._h))
 
+    def arrays(self):
+        """(uint8 data, uint64 offsets) as views of the store's memory: valid while the store lives."""
+        n = len(self)
+        off = np.ctypeslib.as_array(C.cast(self._L.mtg_unitigs_offsets(self._h), C.POINTER(C.c_uint64)), shape=(n + 1,))
+        total = int(off[n])
+        if total == 0:
+            return np.zeros(0, np.uint8), off
+        return np.ctypeslib.as_array(C.cast(self._L.mtg_unitigs_data(self._h), C.POINTER(C.c_uint8)), shape=(total,)), off
+
     def sequences(self) -> list[str]:
         n = len(self)
         off = np.ctypeslib.as_array(C.cast(self._L.mtg_unitigs_offsets(self._h), C.POINTER(C.c_uint64)), shape=(n + 1,))
@@ -853,11 +862,68 @@ def last_fasta_in_times() -> dict:
     return dict(zip(("parse_ms", "upload_ms", "kernel_ms", "download_ms", "build_ms", "bytes"), list(out)))
 
 
-def read_sequences(path: str) -> UnitigStore:
-    """Any FASTA file (optionally .gz, multi-line records, either case) as a sequence store: no graph, no length rule, no GPU."""
+def read_sequences(path: str, split_non_acgt: bool = False) -> UnitigStore:
+    """Any FASTA file (optionally .gz, multi-line records, either case) as a sequence store: no graph, no length rule, no GPU.
+    split_non_acgt: a run of characters outside ACGT (the `N` of real assemblies) ends a piece instead of aborting; every maximal
+    ACGT stretch becomes a record, empty pieces are dropped, and the store's `pieces_cut` holds the number of runs met."""
     st = C.c_void_p()
+    if split_non_acgt:
+        cut = C.c_uint64()
+        _lib.load().mtg_read_sequences_split(str(path).encode(), C.byref(st), C.byref(cut))
+        store = UnitigStore(st.value)
+        store.pieces_cut = int(cut.value)
+        return store
     _lib.load().mtg_read_sequences(str(path).encode(), C.byref(st))
     return UnitigStore(st.value)
+
+
+@dataclass(frozen=True)
+class Compaction:
+    """mtg_compaction (include/mtg_engine.h): the counts of one unitig compaction, in exact integers.
+    distinct_kmers == unitig_characters - (k - 1) * unitigs."""
+
+    records: int
+    characters: int
+    windows: int
+    distinct_kmers: int
+    unitigs: int
+    unitig_characters: int
+    closed_walks: int
+    longest_unitig_kmers: int
+
+    def describe(self) -> str:
+        return (f"{self.records} records, {self.characters} characters, {self.windows} windows -> {self.distinct_kmers} distinct k-mers "
+                f"in {self.unitigs} unitigs of {self.unitig_characters} characters ({self.closed_walks} closed, longest "
+                f"{self.longest_unitig_kmers} k-mers)")
+
+
+def compact_unitigs(seqs_or_store, k: int, device_id: int = 0):
+    """The maximal unitigs of the k-mer set of arbitrary sequences, compacted on GPU `device_id` (mtg_compact_unitigs)
+    -> (UnitigStore, Compaction). seqs_or_store: UnitigStore, list of str, or (uint8 array, offsets). The store is an ordinary one:
+    Bigraph.from_sequences((data, offsets) of it), the writers and compare_kmer_sets take it."""
+    L = _lib.load()
+    out, stats = C.c_void_p(), _lib.MtgCompaction()
+    if isinstance(seqs_or_store, UnitigStore):
+        L.mtg_compact_unitigs_store(seqs_or_store.handle, k, device_id, C.byref(out), C.byref(stats))
+    else:
+        d, o, n, keep = _sequence_arrays(seqs_or_store)
+        L.mtg_compact_unitigs(d, o, n, k, device_id, C.byref(out), C.byref(stats))
+        del keep
+    return UnitigStore(out.value), Compaction(**stats.as_dict())
+
+
+def last_compact_times() -> dict:
+    """Phases of the last compact_unitigs on this thread: ms by HIP events around the kernel phases (pack, insert, ids, nodes, rank,
+    emit), upload / download / total by the host clock, the pointer-jumping rounds, the least bytes the kernels must move and the
+    peak of live device-arena bytes."""
+    out = (C.c_double * 12)()
+    _lib.load().mtg_last_compact_times(out)
+    names = ("upload_ms", "pack_ms", "insert_ms", "ids_ms", "nodes_ms", "rank_ms", "emit_ms", "download_ms", "total_ms", "rounds", "bytes",
+             "peak_arena_bytes")
+    d = dict(zip(names, list(out)))
+    for n in names[9:]:
+        d[n] = int(d[n])
+    return d
 
 
 _NONE64 = 2 ** 64 - 1
@@ -956,10 +1022,12 @@ def kmer_at(seqs, record: int, pos: int, k: int) -> str:
 def compute_tigs_to_fasta_file(graph: Bigraph, store: UnitigStore, algorithm: int, k: int, path: Optional[str],
                                compression_level: int = 6, device_id: int = 0, gfa_path: Optional[str] = None,
                                gfa_header: Optional[str] = None, duplication_bitvector_path: Optional[str] = None,
-                               configuration: Optional[GreedytigAlgorithmConfiguration] = None, verify: bool = False) -> dict:
+                               configuration: Optional[GreedytigAlgorithmConfiguration] = None, verify: bool = False,
+                               verify_against=None) -> dict:
     """compute (3 = eulertigs, 5 = greedy matchtigs) + spell + write FASTA and/or GFA, all inside the library. verify: the result
     gains "verify", the KmerComparison of `store` with the FASTA file as written and read back (read_sequences) or, without a FASTA
-    path, with the tigs spelled to FASTA in memory on the same GPU."""
+    path, with the tigs spelled to FASTA in memory on the same GPU. verify_against: the sequences to compare with instead of `store`
+    (the `--seq-in` route: the input as given, so that the check covers the compaction too)."""
     import time
 
     L = _lib.load()
@@ -990,7 +1058,7 @@ def compute_tigs_to_fasta_file(graph: Bigraph, store: UnitigStore, algorithm: in
             fa = C.string_at(text, n)
             L.mtg_free(text)
             tigs = fa.decode().split("\n")[1::2]
-        cmp = compare_kmer_sets(store, tigs, k, spell_dev)
+        cmp = compare_kmer_sets(store if verify_against is None else verify_against, tigs, k, spell_dev)
     L.mtg_walks_free(w)
     r = {"tigs": n_tigs, "fasta_bytes": nbytes, "gfa_bytes": gbytes, "compute_s": t1 - t0, "write_s": t2 - t1}
     if verify:

@@ -1,0 +1,574 @@
+// compact_device.hip -- the maximal unitigs of the k-mer set of arbitrary sequences (`--seq-in`, mtg_compact_unitigs)
+//
+// The contract (stated in full in DESIGN.md 16). Input: concatenated ASCII plus n + 1 offsets, either case; a window is a start
+// position whose k bases lie inside one record; S is the set of canonical k-mers of all windows. creator(x) is the smallest window
+// start whose k-mer is x or rc(x), reading(x) the string there. G(S) is the bigraph mtg_graph_from_sequences builds from the readings:
+// nodes are oriented (k-1)-mers, every k-mer is the edge P -> S and its mirror. A node is PASSABLE iff it is not its own mirror and
+// has in-degree 1 and out-degree 1 over all directed edges. A unitig is a maximal walk whose inner nodes are passable (closed when
+// the node between its last and first edge is passable too); its leader is the k-mer with the smallest creator; of the walk and its
+// mirror the one that holds reading(leader) is emitted, a closed walk from its leader on, in increasing order of the leaders'
+// creators, spelled as the first edge's k bases plus the last base of every further edge.
+//
+// Kernels, on one stream:
+//   pack      ASCII -> 2 bits per base (pack_device.hpp), which also finds the first character outside ACGT
+//   insert    every window (kmer_window_device.hpp: the rolling walk of the k-mer set comparison) into an open-addressing table in
+//             HBM: slot = 24-bit hash tag << 40 | window start. An empty slot is claimed by CAS; a slot of the same class takes
+//             atomicMin, so it ends holding the class's creator whatever order the threads arrive in. Identity is decided base by base
+//             in the packed store (kw::same_class), for every k: a hash collision costs a compare, never a wrong answer.
+//   ids       the creators' positions are flagged from the table's slots and scanned: dense k-mer ids in creator order, so "smallest
+//             creator" is "smallest id"; kpos[id] = creator. The table is freed. Oriented k-mer 2 i is reading(i), 2 i + 1 its mirror.
+//   nodes     a table of (k-1)-mer classes fed by two insertions per distinct k-mer (prefix and suffix). Per class and side (edges
+//             that leave / enter the class's canonical orientation) one word: none, the one incident oriented k-mer, or "several".
+//             Key: the canonical 2-bit code for k - 1 <= 32 (exact), else tag | position with same_class over k - 1 bases.
+//   succ      per distinct k-mer two lookups: succ[o] = the one edge that leaves the head node of o if that node is passable, else
+//             none. pred(o) = mirror(succ(mirror(o))), so one array serves both directions.
+//   rank      pointer jumping over (jump, rank) pairs held in one 64-bit word, updated in place: a pair always says "jump is the
+//             rank-th predecessor", so any interleaving of the threads keeps it true, and the final state (jump = the walk's head,
+//             rank = the distance from it) is unique. A round at least doubles every open distance: ceil(log2(longest walk)) + 1
+//             rounds. What still moves after ceil(log2(2 N)) + 1 rounds lies on a closed walk; those elements are listed, the
+//             minimum oriented id of each cycle is found by doubling windows (ping-pong buffers), the cycle is cut in front of that
+//             element and ranked like a chain. No kernel walks a chain sequentially.
+//   emit      per walk the minimum oriented id (atomicMin at the head, one per wave where a wave lies on one walk) and the length
+//             (written by the tail); a walk is emitted iff that minimum is even (it holds the reading of its leader). Leaders'
+//             lengths are scanned in id order -> unitig numbers and character offsets; every oriented k-mer of an emitted walk writes
+//             its last base at offset + rank + k - 1, the head the first k - 1 bases too.
+// Nothing depends on the order in which atomics land: the k-mer slots end holding class minima, the node words depend only on
+// the multiset of insertions, the (jump, rank) fixpoint is unique, and the rest are minima, sums and scans.
+//
+// Limits: fewer than 2^40 - 1 bases, fewer than 2^31 - 1 distinct k-mers (oriented k-mer ids are 32-bit), 2 <= k < 2^31.
+// Device memory (arena, hip_util.hpp) per input base b, window w, distinct k-mer N: pack 1.25 b; insert 0.25 b + 16 w + 4 b;
+// later 0.25 b + N (8 kpos + 32 + 16 node table + 8 succ + 16 pairs [+ 16 + 8 with closed walks] + 8 wmin/wlen + 16 leaders).
+// There is no host path: without a GPU a non-empty call aborts.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <chrono>
+#include <string>
+#include <vector>
+
+#include "device.hpp"
+#include "hip_util.hpp"
+#include "kmer_window_device.hpp"
+#include "pack_device.hpp"
+
+namespace mtg {
+
+namespace {
+
+using kw::POS_LIMIT;
+using kw::RUN;
+constexpr unsigned long long EMPTY_SLOT = ~0ull;
+constexpr uint32_t NONE32 = 0xFFFFFFFFu;   // no incident edge / no successor
+constexpr uint32_t MULTI32 = 0xFFFFFFFEu;  // two or more incident edges
+constexpr uint64_t MAX_KMERS = 0x7FFFFFFEull;
+
+struct KmerArgs : kw::WindowArgs {
+    unsigned long long *table;  // [slots] tag << 40 | creator
+    uint64_t slots;
+};
+
+__device__ __forceinline__ uint64_t pair_of(uint32_t jump, uint32_t rank) { return ((uint64_t)rank << 32) | jump; }
+__device__ __forceinline__ uint64_t load64(const unsigned long long *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void store64(unsigned long long *p, uint64_t v) { __hip_atomic_store(p, (unsigned long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+template <bool WIDE>
+__global__ __launch_bounds__(hu::EB) void insert_kernel(KmerArgs a, uint64_t n_bases, uint64_t n_rec, unsigned int *err) {
+    const uint64_t p0 = hu::gid() * RUN;
+    if (p0 >= n_bases) return;
+    kw::for_each_window<WIDE>(a, p0, p0 + RUN < n_bases ? p0 + RUN : n_bases, 0, n_rec, [&](uint64_t q, const kw::Window &w) {
+        const uint64_t tag = w.hash & 0xFFFFFFull;
+        const unsigned long long mine = (tag << 40) | q;
+        uint64_t s = __umul64hi(w.hash, a.slots);
+        for (uint64_t probe = 0; probe < a.slots; probe++) {
+            unsigned long long cur = load64(&a.table[s]);
+            if (cur == EMPTY_SLOT) {
+                const unsigned long long prev = atomicCAS(&a.table[s], EMPTY_SLOT, mine);
+                if (prev == EMPTY_SLOT) return;
+                cur = prev;
+            }
+            if ((cur >> 40) == tag && kw::same_class(a.packed, q, cur & POS_LIMIT, a.k)) {
+                if (mine < cur) atomicMin(&a.table[s], mine);
+                return;
+            }
+            if (++s == a.slots) s = 0;
+        }
+        atomicOr(err, 1u);  // (2 slots per window: never full)
+    });
+}
+
+// flag[creator] = 1 for every occupied slot; *count += occupied slots (grid-stride: one atomic per wave of the whole grid)
+__global__ __launch_bounds__(hu::EB) void mark_kernel(const unsigned long long *table, uint64_t slots, uint32_t *flag, unsigned long long *count) {
+    unsigned long long n = 0;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t s = hu::gid(); s < slots; s += stride) {
+        const unsigned long long cur = table[s];
+        if (cur == EMPTY_SLOT) continue;
+        flag[cur & POS_LIMIT] = 1u;
+        n++;
+    }
+    for (int d = warpSize / 2; d > 0; d /= 2) n += __shfl_down(n, d);
+    if (n && (threadIdx.x & (warpSize - 1)) == 0) atomicAdd(count, n);
+}
+__global__ __launch_bounds__(hu::EB) void kpos_kernel(const unsigned long long *table, uint64_t slots, const uint32_t *id_of_pos, unsigned long long *kpos) {
+    const uint64_t s = hu::gid();
+    if (s >= slots) return;
+    const unsigned long long cur = table[s];
+    if (cur != EMPTY_SLOT) kpos[id_of_pos[cur & POS_LIMIT]] = cur & POS_LIMIT;
+}
+
+struct NodeArgs {
+    const uint32_t *packed;
+    const unsigned long long *kpos;  // [N]
+    unsigned long long *table;       // [slots]
+    uint32_t *out_e, *in_e;          // [slots] the edge that leaves / enters the canonical orientation of the slot's class
+    uint32_t *succ;                  // [2 N]
+    uint64_t slots, N, L;            // L = k - 1
+};
+
+// The slot of the (k-1)-mer at pos (INSERT: claimed if absent); flip: the canonical form is its reverse complement; pal: it is its own.
+template <bool INSERT>
+__device__ __forceinline__ uint64_t find_node(const NodeArgs &a, uint64_t pos, bool &flip, bool &pal, unsigned int *err) {
+    unsigned long long key;
+    uint64_t h;
+    const bool narrow = a.L <= 32;
+    if (narrow) {
+        kw::BaseReader rd(a.packed, pos);
+        uint64_t fwd = 0, rc = 0;  // first base in the highest bits: numeric order is lexicographic order
+        for (uint64_t i = 0; i < a.L; i++) {
+            const uint64_t c = rd.next();
+            fwd = (fwd << 2) | c;
+            rc |= (3ull - c) << (2 * i);
+        }
+        flip = rc < fwd;
+        pal = rc == fwd;
+        key = flip ? rc : fwd;  // (never all ones: T...T is not canonical)
+        h = kw::mix64(key);
+    } else {
+        int cmp = 0;
+        for (uint64_t i = 0; i < a.L && !cmp; i++) {
+            const uint32_t x = packed_base(a.packed, pos + i), y = 3u - packed_base(a.packed, pos + a.L - 1 - i);
+            cmp = x < y ? -1 : (x > y ? 1 : 0);
+        }
+        flip = cmp > 0;
+        pal = cmp == 0;
+        kw::BaseReader rd(a.packed, pos);
+        uint64_t hf = 0, hr = 0, pw = 1;
+        for (uint64_t i = 0; i < a.L; i++) {
+            const uint64_t c = rd.next();
+            hf = hf * kw::POLY_BASE + (c + 1);
+            hr += (4 - c) * pw;
+            pw *= kw::POLY_BASE;
+        }
+        h = kw::mix64(hf) + kw::mix64(hr);  // the same for x and rc(x)
+        key = ((h & 0xFFFFFFull) << 40) | pos;
+    }
+    uint64_t s = __umul64hi(h, a.slots);
+    for (uint64_t probe = 0; probe < a.slots; probe++) {
+        unsigned long long cur = INSERT ? load64(&a.table[s]) : a.table[s];
+        if (cur == EMPTY_SLOT) {
+            if (!INSERT) break;
+            const unsigned long long prev = atomicCAS(&a.table[s], EMPTY_SLOT, key);
+            if (prev == EMPTY_SLOT) return s;
+            cur = prev;
+        }
+        if (narrow ? cur == key : ((cur >> 40) == (key >> 40) && kw::same_class(a.packed, pos, cur & POS_LIMIT, a.L))) return s;
+        if (++s == a.slots) s = 0;
+    }
+    atomicOr(err, INSERT ? 4u : 8u);
+    return 0;
+}
+// none -> o -> several
+__device__ __forceinline__ void add_incident(uint32_t *word, uint32_t o) {
+    const uint32_t prev = atomicCAS(word, NONE32, o);
+    if (prev != NONE32 && prev != MULTI32) atomicExch(word, MULTI32);
+}
+
+__global__ __launch_bounds__(hu::EB) void node_insert_kernel(NodeArgs a, unsigned int *err) {
+    const uint64_t i = hu::gid();
+    if (i >= a.N) return;
+    const uint64_t p = a.kpos[i];
+    const uint32_t fw = (uint32_t)(2 * i), mi = fw + 1;
+    bool flip, pal;
+    const uint64_t sa = find_node<true>(a, p, flip, pal, err);  // the reading leaves its prefix; its mirror enters the prefix's mirror
+    if (!flip) add_incident(&a.out_e[sa], fw);
+    else add_incident(&a.in_e[sa], mi);
+    const uint64_t sb = find_node<true>(a, p + 1, flip, pal, err);  // the reading enters its suffix; its mirror leaves the suffix's mirror
+    if (!flip) add_incident(&a.in_e[sb], fw);
+    else add_incident(&a.out_e[sb], mi);
+}
+
+__global__ __launch_bounds__(hu::EB) void succ_kernel(NodeArgs a, unsigned int *err) {
+    const uint64_t i = hu::gid();
+    if (i >= a.N) return;
+    const uint64_t p = a.kpos[i];
+    bool flip, pal;
+    const uint64_t sb = find_node<false>(a, p + 1, flip, pal, err);  // head of the reading: its suffix as read
+    uint32_t oe = a.out_e[sb], ie = a.in_e[sb];
+    a.succ[2 * i] = (!pal && oe < MULTI32 && ie < MULTI32) ? (flip ? ie ^ 1u : oe) : NONE32;
+    const uint64_t sa = find_node<false>(a, p, flip, pal, err);  // head of the mirror: the reverse complement of the prefix
+    oe = a.out_e[sa];
+    ie = a.in_e[sa];
+    a.succ[2 * i + 1] = (!pal && oe < MULTI32 && ie < MULTI32) ? (flip ? oe : ie ^ 1u) : NONE32;
+}
+
+__device__ __forceinline__ uint32_t pred_of(const uint32_t *succ, uint32_t o) {
+    const uint32_t s = succ[o ^ 1u];
+    return s == NONE32 ? NONE32 : s ^ 1u;
+}
+
+__global__ __launch_bounds__(hu::EB) void rank_init_kernel(const uint32_t *succ, uint64_t n, unsigned long long *pairs) {
+    const uint64_t o = hu::gid();
+    if (o >= n) return;
+    const uint32_t pr = pred_of(succ, (uint32_t)o);
+    pairs[o] = pair_of(pr, pr != NONE32);
+}
+// one round of pointer jumping over all n elements, or over those of `list`; stops in front of the head: jump ends as the head itself
+__global__ __launch_bounds__(hu::EB) void jump_kernel(unsigned long long *pairs, uint64_t n, const uint32_t *list, unsigned int *changed) {
+    const uint64_t g = hu::gid();
+    if (g >= n) return;
+    const uint64_t o = list ? list[g] : g;
+    const uint64_t mine = load64(&pairs[o]);
+    const uint32_t j = (uint32_t)mine;
+    if (j == NONE32) return;
+    const uint64_t theirs = load64(&pairs[j]);
+    if ((uint32_t)theirs == NONE32) return;
+    store64(&pairs[o], pair_of((uint32_t)theirs, (uint32_t)(mine >> 32) + (uint32_t)(theirs >> 32)));
+    *changed = 1u;
+}
+// the elements that still move after every chain has settled: jump is not a head
+__global__ __launch_bounds__(hu::EB) void cycle_list_kernel(const unsigned long long *pairs, const uint32_t *succ, uint64_t n, uint32_t *list,
+                                                             unsigned long long *count) {
+    const uint64_t o = hu::gid();
+    if (o >= n) return;
+    const uint32_t j = (uint32_t)pairs[o];
+    if (j != NONE32 && succ[j ^ 1u] != NONE32) list[atomicAdd(count, 1ull)] = (uint32_t)o;
+}
+__global__ __launch_bounds__(hu::EB) void cycle_min_init_kernel(const uint32_t *succ, const uint32_t *list, uint64_t n, unsigned long long *buf) {
+    const uint64_t g = hu::gid();
+    if (g >= n) return;
+    const uint32_t o = list[g];
+    buf[o] = pair_of(pred_of(succ, o), o);  // (jump, minimum over the window that ends at o)
+}
+__global__ __launch_bounds__(hu::EB) void cycle_min_kernel(const unsigned long long *src, unsigned long long *dst, const uint32_t *list, uint64_t n) {
+    const uint64_t g = hu::gid();
+    if (g >= n) return;
+    const uint32_t o = list[g];
+    const uint64_t mine = src[o], theirs = src[(uint32_t)mine];
+    dst[o] = pair_of((uint32_t)theirs, min((uint32_t)(mine >> 32), (uint32_t)(theirs >> 32)));
+}
+// cut every cycle in front of its minimum: that element becomes a head
+__global__ __launch_bounds__(hu::EB) void cycle_cut_kernel(const unsigned long long *mins, const uint32_t *succ, const uint32_t *list, uint64_t n,
+                                                            unsigned long long *pairs) {
+    const uint64_t g = hu::gid();
+    if (g >= n) return;
+    const uint32_t o = list[g];
+    const uint32_t m = (uint32_t)(mins[o] >> 32);
+    const uint32_t pr = o == m ? NONE32 : pred_of(succ, o);
+    pairs[o] = pair_of(pr, pr != NONE32);
+}
+
+// wmin[head] = the smallest oriented id on the walk, wlen[head] = its edges
+__global__ __launch_bounds__(hu::EB) void walk_kernel(const unsigned long long *pairs, const uint32_t *succ, uint64_t n, uint32_t *wmin, uint32_t *wlen) {
+    const uint64_t o = hu::gid();
+    const bool live = o < n;
+    uint32_t h = NONE32;
+    if (live) {
+        const uint64_t pr = pairs[o];
+        h = (uint32_t)pr == NONE32 ? (uint32_t)o : (uint32_t)pr;
+        const uint32_t s = succ[o];
+        if (s == NONE32 || s == h) wlen[h] = (uint32_t)(pr >> 32) + 1u;
+    }
+    const uint32_t h0 = __shfl(h, 0);
+    if (__all(live && h == h0)) {  // the whole wave lies on one walk: its first lane holds the smallest id
+        if ((threadIdx.x & (warpSize - 1)) == 0) atomicMin(&wmin[h], (uint32_t)o);
+    } else if (live) {
+        atomicMin(&wmin[h], (uint32_t)o);
+    }
+}
+// heads of emitted walks (the minimum is even: the walk holds the reading of its leader) leave their length at the leader's id
+// stats: [0] closed walks, [1] k-mers of the longest unitig
+__global__ __launch_bounds__(hu::EB) void leader_kernel(const unsigned long long *pairs, const uint32_t *succ, uint64_t n, const uint32_t *wmin,
+                                                         const uint32_t *wlen, uint32_t k, uint32_t *lead_flag, uint32_t *lead_chars,
+                                                         unsigned long long *stats) {
+    const uint64_t o = hu::gid();
+    if (o >= n || (uint32_t)pairs[o] != NONE32) return;
+    const uint32_t m = wmin[o];
+    if (m & 1u) return;
+    lead_flag[m >> 1] = 1u;
+    lead_chars[m >> 1] = wlen[o] + k - 1;
+    if (succ[o ^ 1u] != NONE32) atomicAdd(&stats[0], 1ull);  // a head with a predecessor: a cut cycle
+    if (wlen[o] > load64(&stats[1])) atomicMax(&stats[1], (unsigned long long)wlen[o]);  // (after a plain read: only improving lengths reach the atomic)
+}
+__global__ __launch_bounds__(hu::EB) void offsets_kernel(const uint32_t *lead_chars, const uint32_t *unitig_of, const uint64_t *char_off, uint64_t N,
+                                                          unsigned long long *out_off) {
+    const uint64_t i = hu::gid();
+    if (i < N && lead_chars[i]) out_off[unitig_of[i]] = char_off[i];
+}
+__global__ __launch_bounds__(hu::EB) void spell_kernel(const uint32_t *packed, const unsigned long long *kpos, const unsigned long long *pairs,
+                                                        const uint32_t *wmin, const uint64_t *char_off, uint64_t n, uint64_t k, char *out) {
+    const uint64_t o = hu::gid();
+    if (o >= n) return;
+    const uint64_t pr = pairs[o];
+    const uint32_t h = (uint32_t)pr == NONE32 ? (uint32_t)o : (uint32_t)pr, m = wmin[h];
+    if (m & 1u) return;
+    const uint64_t at = char_off[m >> 1], rank = pr >> 32, pos = kpos[o >> 1];
+    const bool mir = o & 1;
+    const char *abc = "ACGT";
+    out[at + rank + k - 1] = abc[mir ? 3u - packed_base(packed, pos) : packed_base(packed, pos + k - 1)];
+    if (rank == 0)
+        for (uint64_t j = 0; j + 1 < k; j++) out[at + j] = abc[mir ? 3u - packed_base(packed, pos + k - 1 - j) : packed_base(packed, pos + j)];
+}
+
+double ms_since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+int log2_ceil(uint64_t n) {
+    int r = 0;
+    while ((1ull << r) < n) r++;
+    return r;
+}
+
+}  // namespace
+
+UnitigStore *device_compact_unitigs(const char *data, const uint64_t *off, uint64_t n_rec, uint64_t k, int device_id, mtg_compaction *stats_out,
+                                    CompactTimes *times) {
+    if (!off || (n_rec && off[n_rec] && !data)) MTG_DIE("mtg_compact_unitigs: null argument");
+    if (k < 2) MTG_DIE("mtg_compact_unitigs: k must be >= 2");
+    if (k >= (1ull << 31)) MTG_DIE("mtg_compact_unitigs: k too large");
+    if (off[0] != 0) MTG_DIE("mtg_compact_unitigs: offsets must start at 0");
+    const auto t_total = std::chrono::steady_clock::now();
+    mtg_compaction r{};
+    r.records = n_rec;
+    for (uint64_t u = 0; u < n_rec; u++) {
+        if (off[u + 1] < off[u]) MTG_DIE("mtg_compact_unitigs: offsets decrease at record %llu", (unsigned long long)u);
+        const uint64_t len = off[u + 1] - off[u];
+        if (len >= k) r.windows += len - k + 1;
+    }
+    const uint64_t n_bases = r.characters = off[n_rec];
+    CompactTimes t{};
+    UnitigStore *store = new UnitigStore();
+    store->off.push_back(0);
+    auto finish = [&]() {
+        t.total_ms = ms_since(t_total);
+        if (stats_out) *stats_out = r;
+        if (times) *times = t;
+        return store;
+    };
+    if (n_bases == 0) return finish();
+    if (n_bases >= POS_LIMIT) MTG_DIE("mtg_compact_unitigs: %llu bases; the limit is 2^40 - 2", (unsigned long long)n_bases);
+    if (device_id < 0 || device_count() <= device_id) MTG_DIE("no HIP device %d for the unitig compaction (there is no CPU path)", device_id);
+    HIP_CHECK(hipSetDevice(device_id));
+    device_arena_reset_peak(device_id);
+    hipStream_t st = nullptr;
+    const uint64_t n_words = (n_bases + 15) / 16;
+
+    auto t0 = std::chrono::steady_clock::now();
+    char *d_ascii = nullptr;
+    uint32_t *d_packed = nullptr;
+    unsigned long long *d_off = nullptr, *d_small = nullptr;
+    hu::device_malloc(&d_ascii, n_bases);
+    hu::device_malloc(&d_packed, (n_words + 2) * 4);
+    hu::device_malloc(&d_off, (n_rec + 1) * 8);
+    hu::device_malloc(&d_small, 8 * 8);  // [0] first bad character, [1] error bits, [2] distinct k-mers, [3] changed, [4] cycle elements, [5] closed, [6] longest
+    HIP_CHECK(hipMemcpyAsync(d_off, off, (n_rec + 1) * 8, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemsetAsync(d_small, 0, 8 * 8, st));
+    HIP_CHECK(hipMemsetAsync(d_small, 0xFF, 8, st));
+    HIP_CHECK(hipMemsetAsync(d_packed + n_words, 0, 8, st));
+    hu::upload_sliced(d_ascii, data, n_bases, st, device_id);
+    HIP_CHECK(hipStreamSynchronize(st));
+    t.upload_ms = ms_since(t0);
+
+    hipEvent_t ev[7];
+    for (hipEvent_t &e : ev) HIP_CHECK(hipEventCreate(&e));
+    unsigned int *d_err = reinterpret_cast<unsigned int *>(d_small + 1);
+    unsigned int *d_changed = reinterpret_cast<unsigned int *>(d_small + 3);
+    unsigned long long h_small[8];
+    auto read_small = [&]() {
+        HIP_CHECK(hipMemcpyAsync(h_small, d_small, sizeof h_small, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        if (h_small[1] & 0xFFFFFFFFull) MTG_DIE("unitig compaction: internal error %llu (hash table)", h_small[1] & 0xFFFFFFFFull);
+    };
+    auto free_all = [&](std::initializer_list<const void *> ps) { for (const void *p : ps) hu::device_free(p); };
+    auto elapsed = [&](int a, int b) { float f = 0.f; HIP_CHECK(hipEventElapsedTime(&f, ev[a], ev[b])); return (double)f; };
+
+    // ---- pack ----
+    HIP_CHECK(hipEventRecord(ev[0], st));
+    pack_kernel<<<hu::grid_for(n_words), hu::EB, 0, st>>>(d_ascii, n_bases, d_packed, d_small);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipEventRecord(ev[1], st));
+    hu::device_free(d_ascii);  // (synchronises: the pack is done)
+    read_small();
+    if (h_small[0] != EMPTY_SLOT) MTG_DIE("sequences: character at offset %llu is not in the DNA alphabet (ACGT)", h_small[0]);
+    if (r.windows == 0) {  // nothing is as long as k
+        HIP_CHECK(hipEventRecord(ev[2], st));
+        HIP_CHECK(hipEventSynchronize(ev[2]));
+        t.pack_ms = elapsed(0, 1);
+        for (hipEvent_t &e : ev) HIP_CHECK(hipEventDestroy(e));
+        free_all({d_packed, d_off, d_small});
+        return finish();
+    }
+
+    // ---- insert: the creator of every k-mer class ----
+    const uint64_t slots = std::max<uint64_t>(8, (2 * r.windows + 7) / 8 * 8);
+    KmerArgs ka{};
+    ka.packed = d_packed; ka.off = d_off; ka.slots = slots;
+    kw::window_args_set_k(ka, k);
+    hu::device_malloc(&ka.table, slots * 8);
+    HIP_CHECK(hipMemsetAsync(ka.table, 0xFF, slots * 8, st));
+    {
+        const unsigned grid = hu::grid_for((n_bases + RUN - 1) / RUN);
+        if (k >= 32) insert_kernel<true><<<grid, hu::EB, 0, st>>>(ka, n_bases, n_rec, d_err);
+        else insert_kernel<false><<<grid, hu::EB, 0, st>>>(ka, n_bases, n_rec, d_err);
+        HIP_CHECK(hipGetLastError());
+    }
+    HIP_CHECK(hipEventRecord(ev[2], st));
+
+    // ---- ids in creator order ----
+    uint32_t *d_id_of_pos = nullptr;
+    hu::device_malloc(&d_id_of_pos, n_bases * 4);
+    HIP_CHECK(hipMemsetAsync(d_id_of_pos, 0, n_bases * 4, st));
+    mark_kernel<<<(unsigned)std::min<uint64_t>(hu::grid_for(slots), 16384), hu::EB, 0, st>>>(ka.table, slots, d_id_of_pos, d_small + 2);
+    HIP_CHECK(hipGetLastError());
+    read_small();
+    const uint64_t N = r.distinct_kmers = h_small[2], n_or = 2 * N;
+    if (N > MAX_KMERS) MTG_DIE("mtg_compact_unitigs: %llu distinct k-mers; oriented k-mer ids are 32-bit", (unsigned long long)N);
+    uint32_t *d_bsum32 = nullptr;
+    unsigned long long *d_kpos = nullptr;
+    hu::device_malloc(&d_bsum32, (hu::scan_blocks(n_bases) + 2) * 4);
+    hu::device_malloc(&d_kpos, N * 8);
+    hu::scan_u32<uint32_t>(st, d_id_of_pos, n_bases, d_id_of_pos, d_bsum32, d_bsum32 + hu::scan_blocks(n_bases) + 1);
+    kpos_kernel<<<hu::grid_for(slots), hu::EB, 0, st>>>(ka.table, slots, d_id_of_pos, d_kpos);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipEventRecord(ev[3], st));
+    free_all({ka.table, d_id_of_pos, d_bsum32, d_off});
+
+    // ---- the (k-1)-mer classes and succ ----
+    NodeArgs na{};
+    na.packed = d_packed; na.kpos = d_kpos; na.N = N; na.L = k - 1;
+    na.slots = std::max<uint64_t>(8, 4 * N);  // at most 2 N classes
+    hu::device_malloc(&na.table, na.slots * 8);
+    hu::device_malloc(&na.out_e, na.slots * 4);
+    hu::device_malloc(&na.in_e, na.slots * 4);
+    hu::device_malloc(&na.succ, n_or * 4);
+    HIP_CHECK(hipMemsetAsync(na.table, 0xFF, na.slots * 8, st));
+    HIP_CHECK(hipMemsetAsync(na.out_e, 0xFF, na.slots * 4, st));
+    HIP_CHECK(hipMemsetAsync(na.in_e, 0xFF, na.slots * 4, st));
+    node_insert_kernel<<<hu::grid_for(N), hu::EB, 0, st>>>(na, d_err);
+    succ_kernel<<<hu::grid_for(N), hu::EB, 0, st>>>(na, d_err);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipEventRecord(ev[4], st));
+    free_all({na.table, na.out_e, na.in_e});
+    read_small();
+
+    // ---- ranks by pointer jumping ----
+    unsigned long long *d_pairs = nullptr;
+    hu::device_malloc(&d_pairs, n_or * 8);
+    rank_init_kernel<<<hu::grid_for(n_or), hu::EB, 0, st>>>(na.succ, n_or, d_pairs);
+    HIP_CHECK(hipGetLastError());
+    int rounds = 0;
+    auto jump_rounds = [&](uint64_t n, const uint32_t *list, int max_rounds) {  // true: settled
+        for (int i = 0; i < max_rounds; i++) {
+            HIP_CHECK(hipMemsetAsync(d_changed, 0, 4, st));
+            jump_kernel<<<hu::grid_for(n), hu::EB, 0, st>>>(d_pairs, n, list, d_changed);
+            HIP_CHECK(hipGetLastError());
+            rounds++;
+            read_small();
+            if (!(h_small[3] & 0xFFFFFFFFull)) return true;
+        }
+        return false;
+    };
+    if (!jump_rounds(n_or, nullptr, log2_ceil(n_or) + 2)) {  // closed walks
+        uint32_t *d_list = nullptr;
+        unsigned long long *d_buf = nullptr;
+        hu::device_malloc(&d_list, n_or * 4);
+        cycle_list_kernel<<<hu::grid_for(n_or), hu::EB, 0, st>>>(d_pairs, na.succ, n_or, d_list, d_small + 4);
+        HIP_CHECK(hipGetLastError());
+        read_small();
+        const uint64_t C = h_small[4];
+        if (C == 0 || C > n_or) MTG_DIE("unitig compaction: internal error (%llu elements on closed walks)", (unsigned long long)C);
+        hu::device_malloc(&d_buf, n_or * 8);
+        cycle_min_init_kernel<<<hu::grid_for(C), hu::EB, 0, st>>>(na.succ, d_list, C, d_pairs);
+        unsigned long long *src = d_pairs, *dst = d_buf;
+        for (int i = 0, n = log2_ceil(C); i < n; i++, rounds++) {
+            cycle_min_kernel<<<hu::grid_for(C), hu::EB, 0, st>>>(src, dst, d_list, C);
+            std::swap(src, dst);
+        }
+        cycle_cut_kernel<<<hu::grid_for(C), hu::EB, 0, st>>>(src, na.succ, d_list, C, d_pairs);
+        HIP_CHECK(hipGetLastError());
+        if (!jump_rounds(C, d_list, log2_ceil(C) + 2)) MTG_DIE("unitig compaction: internal error (a cut cycle does not settle)");
+        free_all({d_list, d_buf});
+    }
+    HIP_CHECK(hipEventRecord(ev[5], st));
+
+    // ---- emit ----
+    uint32_t *d_wmin = nullptr, *d_wlen = nullptr, *d_lead_flag = nullptr, *d_lead_chars = nullptr;
+    uint64_t *d_char_off = nullptr, *d_bsum64 = nullptr;
+    hu::device_malloc(&d_wmin, n_or * 4);
+    hu::device_malloc(&d_wlen, n_or * 4);
+    hu::device_malloc(&d_lead_flag, N * 4);
+    hu::device_malloc(&d_lead_chars, N * 4);
+    hu::device_malloc(&d_char_off, N * 8);
+    hu::device_malloc(&d_bsum32, (hu::scan_blocks(N) + 2) * 4);
+    hu::device_malloc(&d_bsum64, (hu::scan_blocks(N) + 2) * 8);
+    HIP_CHECK(hipMemsetAsync(d_wmin, 0xFF, n_or * 4, st));
+    HIP_CHECK(hipMemsetAsync(d_wlen, 0, n_or * 4, st));
+    HIP_CHECK(hipMemsetAsync(d_lead_flag, 0, N * 4, st));
+    HIP_CHECK(hipMemsetAsync(d_lead_chars, 0, N * 4, st));
+    walk_kernel<<<hu::grid_for(n_or), hu::EB, 0, st>>>(d_pairs, na.succ, n_or, d_wmin, d_wlen);
+    leader_kernel<<<hu::grid_for(n_or), hu::EB, 0, st>>>(d_pairs, na.succ, n_or, d_wmin, d_wlen, (uint32_t)k, d_lead_flag, d_lead_chars, d_small + 5);
+    uint32_t *d_n_unitigs = d_bsum32 + hu::scan_blocks(N) + 1;
+    uint64_t *d_n_chars = d_bsum64 + hu::scan_blocks(N) + 1;
+    hu::scan_u32<uint32_t>(st, d_lead_flag, N, d_lead_flag, d_bsum32, d_n_unitigs);
+    hu::scan_u32<uint64_t>(st, d_lead_chars, N, d_char_off, d_bsum64, d_n_chars);
+    uint32_t n_unitigs = 0;
+    uint64_t n_chars = 0;
+    HIP_CHECK(hipMemcpyAsync(&n_unitigs, d_n_unitigs, 4, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(&n_chars, d_n_chars, 8, hipMemcpyDeviceToHost, st));
+    read_small();
+    r.unitigs = n_unitigs;
+    r.unitig_characters = n_chars;
+    r.closed_walks = h_small[5];
+    r.longest_unitig_kmers = h_small[6];
+    if (n_chars != N + (k - 1) * r.unitigs) MTG_DIE("unitig compaction: internal error (%llu characters for %llu k-mers in %llu unitigs)",
+                                                    (unsigned long long)n_chars, (unsigned long long)N, (unsigned long long)r.unitigs);
+    char *d_out = nullptr;
+    unsigned long long *d_out_off = nullptr;
+    hu::device_malloc(&d_out, n_chars);
+    hu::device_malloc(&d_out_off, (r.unitigs + 1) * 8);
+    offsets_kernel<<<hu::grid_for(N), hu::EB, 0, st>>>(d_lead_chars, d_lead_flag, d_char_off, N, d_out_off);
+    spell_kernel<<<hu::grid_for(n_or), hu::EB, 0, st>>>(d_packed, d_kpos, d_pairs, d_wmin, d_char_off, n_or, k, d_out);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipEventRecord(ev[6], st));
+    HIP_CHECK(hipStreamSynchronize(st));
+
+    t0 = std::chrono::steady_clock::now();
+    store->data.resize(n_chars);
+    store->off.resize(r.unitigs + 1);
+    hu::download_sliced(&store->data[0], d_out, n_chars, st, device_id);
+    hu::download_sliced(store->off.data(), d_out_off, r.unitigs * 8, st, device_id);
+    store->off[r.unitigs] = n_chars;
+    t.download_ms = ms_since(t0);
+    t.pack_ms = elapsed(0, 1);
+    t.insert_ms = elapsed(1, 2);
+    t.ids_ms = elapsed(2, 3);
+    t.nodes_ms = elapsed(3, 4);
+    t.rank_ms = elapsed(4, 5);
+    t.emit_ms = elapsed(5, 6);
+    t.rounds = rounds;
+    for (hipEvent_t &e : ev) HIP_CHECK(hipEventDestroy(e));
+    free_all({d_packed, d_small, d_kpos, na.succ, d_pairs, d_wmin, d_wlen, d_lead_flag, d_lead_chars, d_char_off, d_bsum32, d_bsum64, d_out, d_out_off});
+    uint64_t arena[4];
+    device_arena_stats(device_id, arena);
+    t.peak_arena_bytes = arena[2];
+    // What the kernels must move at the least: ASCII read and packed store written; per window the packed bases once (2 bits) and one
+    // slot; the table filled, then read twice (mark, kpos); per base the flag word written, scanned (read + written) and read per
+    // creator; per distinct k-mer its creator written and read twice with 2 (k + 15) / 16 packed words each time, two node slots
+    // and two incident words written and read, two succ words; per oriented k-mer one pair per round at the least (read), succ and the
+    // pair in the emit kernels, wmin / wlen; per leader flag, length and offset; and the output characters and offsets.
+    t.bytes = n_bases + n_words * 4 + r.windows * 8 + n_words * 4 + slots * 8 * 3 + n_bases * 4 * 3 + N * 4 +
+              N * (8 * 3 + 2 * 4 * ((k + 15) / 16 + 1) + 2 * (8 + 4) * 2 + 8) + n_or * 8 * (uint64_t)std::max(rounds, 1) +
+              n_or * (4 + 8 + 8 + 8 + 4) + N * (4 * 3 + 4 * 2 + 8 * 2) + n_chars + r.unitigs * 8;
+    return finish();
+}
+
+}  // namespace mtg

@@ -132,6 +132,18 @@ struct KmerCompareTimes {
 };
 void device_compare_kmer_sets(const char *seq_a, const uint64_t *off_a, uint64_t n_a, const char *seq_b, const uint64_t *off_b, uint64_t n_b,
                               uint64_t k, int device_id, mtg_kmer_comparison *out, KmerCompareTimes *times);
+// compact_device.hip: the maximal unitigs of the k-mer set of arbitrary sequences (the file's header and DESIGN.md 16 state the
+// contract), as an ordinary sequence store. times: host wall clock of upload, download and the whole call, HIP-event time of the
+// kernel phases, the pointer-jumping rounds, the bytes the kernels must move at the least, the arena's peak of live bytes.
+struct CompactTimes {
+    double upload_ms = 0, pack_ms = 0, insert_ms = 0, ids_ms = 0, nodes_ms = 0, rank_ms = 0, emit_ms = 0, download_ms = 0, total_ms = 0;
+    int rounds = 0;
+    uint64_t bytes = 0, peak_arena_bytes = 0;
+};
+UnitigStore *device_compact_unitigs(const char *data, const uint64_t *off, uint64_t n_rec, uint64_t k, int device_id, mtg_compaction *stats_out,
+                                    CompactTimes *times);
+// fasta_in.cpp: read_fasta_records where a run of characters outside ACGT ends a piece instead of aborting; empty pieces are dropped
+UnitigStore *read_fasta_records_split(const char *path, uint64_t *pieces_cut);
 void device_candidates_to_host(Device *d, void *stream, std::vector<uint64_t> &cand_start,
                                std::vector<uint32_t> &cand_count, std::vector<uint64_t> &pool);
 

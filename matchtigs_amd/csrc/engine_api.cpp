@@ -654,6 +654,26 @@ void mtg_last_kmer_compare_times(double out[6]) {
     const KmerCompareTimes &t = g_last_kmer_compare;
     out[0] = t.upload_ms; out[1] = t.pack_ms; out[2] = t.insert_a_ms; out[3] = t.insert_b_ms; out[4] = t.count_ms; out[5] = t.total_ms;
 }
+// ---- unitig compaction on the GPU (compact_device.hip) ----
+static thread_local CompactTimes g_last_compact;
+void mtg_compact_unitigs(const char *data, const uint64_t *offsets, uint64_t n, uint64_t k, int device_id, mtg_unitigs **out, mtg_compaction *stats) {
+    if (!out) MTG_DIE("mtg_compact_unitigs: null argument");
+    *out = new mtg_unitigs{device_compact_unitigs(data, offsets, n, k, device_id, stats, &g_last_compact)};
+}
+void mtg_compact_unitigs_store(const mtg_unitigs *in, uint64_t k, int device_id, mtg_unitigs **out, mtg_compaction *stats) {
+    if (!in || !out) MTG_DIE("mtg_compact_unitigs_store: null argument");
+    *out = new mtg_unitigs{device_compact_unitigs(in->s->data.data(), in->s->off.data(), in->s->off.size() - 1, k, device_id, stats, &g_last_compact)};
+}
+void mtg_last_compact_times(double out[12]) {
+    const CompactTimes &t = g_last_compact;
+    out[0] = t.upload_ms; out[1] = t.pack_ms; out[2] = t.insert_ms; out[3] = t.ids_ms; out[4] = t.nodes_ms; out[5] = t.rank_ms;
+    out[6] = t.emit_ms; out[7] = t.download_ms; out[8] = t.total_ms; out[9] = (double)t.rounds; out[10] = (double)t.bytes;
+    out[11] = (double)t.peak_arena_bytes;
+}
+void mtg_read_sequences_split(const char *path, mtg_unitigs **store_out, uint64_t *pieces_cut) {
+    if (!path || !store_out) MTG_DIE("mtg_read_sequences_split: null argument");
+    *store_out = new mtg_unitigs{read_fasta_records_split(path, pieces_cut)};
+}
 uint64_t mtg_unitigs_count(const mtg_unitigs *u) { return u->s->off.size() - 1; }
 const char *mtg_unitigs_data(const mtg_unitigs *u) { return u->s->data.data(); }
 const uint64_t *mtg_unitigs_offsets(const mtg_unitigs *u) { return u->s->off.data(); }

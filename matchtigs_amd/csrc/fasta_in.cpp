@@ -5,7 +5,8 @@
 // Format: `>` header lines with any text (BCALM2's `L:` annotations included: they are not read), then the sequence on one or
 // more lines, either case. Empty lines are skipped, `.gz` inputs are inflated with zlib (gzopen also reads plain files). The same
 // line reader and alphabet rule as the BCALM2 route (bcalm2.cpp). read_fasta_records is that reader on its own (mtg_read_sequences:
-// a tig file someone else wrote, for the k-mer set comparison); read_fasta adds the length rule and the join.
+// a tig file someone else wrote, for the k-mer set comparison), read_fasta_records_split the same reader where a run of characters
+// outside ACGT (the `N` of real assemblies) ends a piece instead of aborting (mtg_read_sequences_split, `--seq-in`); read_fasta adds the length rule and the join.
 #include <zlib.h>
 
 #include <chrono>
@@ -41,6 +42,45 @@ UnitigStore *read_fasta_records(const char *path) {
     }
     gzclose(f);
     if (have_record) st->off.push_back(st->data.size());
+    return st;
+}
+
+UnitigStore *read_fasta_records_split(const char *path, uint64_t *pieces_cut) {
+    gzFile f = gzopen(path, "rb");
+    if (!f) MTG_DIE("cannot open %s", path);
+    gzbuffer(f, 1 << 20);
+    UnitigStore *st = new UnitigStore();
+    st->off.push_back(0);
+    std::string line;
+    bool have_record = false, in_run = false;
+    uint64_t cuts = 0;
+    auto end_piece = [&]() {
+        if (st->data.size() > st->off.back()) st->off.push_back(st->data.size());
+    };
+    while (read_line(f, line)) {
+        if (line.empty()) continue;
+        if (line[0] == '>') {
+            end_piece();
+            have_record = true;
+            in_run = false;
+        } else {
+            if (!have_record) MTG_DIE("%s: sequence data before the first header", path);
+            for (char c : line) {
+                if (c >= 'a' && c <= 'z') c = (char)(c - 'a' + 'A');
+                if (c == 'A' || c == 'C' || c == 'G' || c == 'T') {
+                    st->data.push_back(c);
+                    in_run = false;
+                } else if (!in_run) {  // the first character of a run: the piece ends here
+                    end_piece();
+                    in_run = true;
+                    cuts++;
+                }
+            }
+        }
+    }
+    gzclose(f);
+    end_piece();
+    if (pieces_cut) *pieces_cut = cuts;
     return st;
 }
 
