@@ -10,16 +10,16 @@
 // creators, spelled as the first edge's k bases plus the last base of every further edge.
 //
 // Kernels, on one stream:
-//   pack      ASCII -> 2 bits per base (pack_device.hpp), which also finds the first character outside ACGT
-//   insert    every window (kmer_window_device.hpp: the rolling walk of the k-mer set comparison) into an open-addressing table in
-//             HBM: slot = 24-bit hash tag << 40 | window start. An empty slot is claimed by CAS; a slot of the same class takes
-//             atomicMin, so it ends holding the class's creator whatever order the threads arrive in. Identity is decided base by base
-//             in the packed store (kw::same_class), for every k: a hash collision costs a compare, never a wrong answer.
+//   pack      ASCII -> 2 bits per base (SeqStore, pack_device.hpp), which also finds the first character outside ACGT
+//   insert    every window (kw::for_each_window) into a table of classes (kw::find_slot in kmer_window_device.hpp, where the
+//             exactness and order-independence argument of both tables here is written down): slot = kw::tagged_pos of a window
+//             start, identity by kw::same_class for every k. A slot of the same class takes atomicMin: the tag is fixed per class,
+//             so the slot ends holding the class's creator.
 //   ids       the creators' positions are flagged from the table's slots and scanned: dense k-mer ids in creator order, so "smallest
 //             creator" is "smallest id"; kpos[id] = creator. The table is freed. Oriented k-mer 2 i is reading(i), 2 i + 1 its mirror.
 //   nodes     a table of (k-1)-mer classes fed by two insertions per distinct k-mer (prefix and suffix). Per class and side (edges
 //             that leave / enter the class's canonical orientation) one word: none, the one incident oriented k-mer, or "several".
-//             Key: the canonical 2-bit code for k - 1 <= 32 (exact), else tag | position with same_class over k - 1 bases.
+//             Key: kw::class_key (the canonical 2-bit code for k - 1 <= 32, else tagged_pos with same_class over k - 1 bases).
 //   succ      per distinct k-mer two lookups: succ[o] = the one edge that leaves the head node of o if that node is passable, else
 //             none. pred(o) = mirror(succ(mirror(o))), so one array serves both directions.
 //   rank      pointer jumping over (jump, rank) pairs held in one 64-bit word, updated in place: a pair always says "jump is the
@@ -57,13 +57,13 @@ namespace {
 
 using kw::POS_LIMIT;
 using kw::RUN;
-constexpr unsigned long long EMPTY_SLOT = ~0ull;
+using kw::EMPTY_SLOT;
 constexpr uint32_t NONE32 = 0xFFFFFFFFu;   // no incident edge / no successor
 constexpr uint32_t MULTI32 = 0xFFFFFFFEu;  // two or more incident edges
 constexpr uint64_t MAX_KMERS = 0x7FFFFFFEull;
 
 struct KmerArgs : kw::WindowArgs {
-    unsigned long long *table;  // [slots] tag << 40 | creator
+    unsigned long long *table;  // [slots] kw::tagged_pos of the class's creator
     uint64_t slots;
 };
 
@@ -76,23 +76,12 @@ __global__ __launch_bounds__(hu::EB) void insert_kernel(KmerArgs a, uint64_t n_b
     const uint64_t p0 = hu::gid() * RUN;
     if (p0 >= n_bases) return;
     kw::for_each_window<WIDE>(a, p0, p0 + RUN < n_bases ? p0 + RUN : n_bases, 0, n_rec, [&](uint64_t q, const kw::Window &w) {
-        const uint64_t tag = w.hash & 0xFFFFFFull;
-        const unsigned long long mine = (tag << 40) | q;
-        uint64_t s = __umul64hi(w.hash, a.slots);
-        for (uint64_t probe = 0; probe < a.slots; probe++) {
-            unsigned long long cur = load64(&a.table[s]);
-            if (cur == EMPTY_SLOT) {
-                const unsigned long long prev = atomicCAS(&a.table[s], EMPTY_SLOT, mine);
-                if (prev == EMPTY_SLOT) return;
-                cur = prev;
-            }
-            if ((cur >> 40) == tag && kw::same_class(a.packed, q, cur & POS_LIMIT, a.k)) {
-                if (mine < cur) atomicMin(&a.table[s], mine);
-                return;
-            }
-            if (++s == a.slots) s = 0;
-        }
-        atomicOr(err, 1u);  // (2 slots per window: never full)
+        const unsigned long long mine = kw::tagged_pos(w.hash, q);
+        const kw::Found f = kw::find_slot<true>(a.table, a.slots, w.hash, mine, [&](unsigned long long cur) {
+            return (cur >> 40) == (mine >> 40) && kw::same_class(a.packed, q, cur & POS_LIMIT, a.k);
+        });
+        if (f.slot == a.slots) atomicOr(err, 1u);  // (2 slots per window: never full)
+        else if (f.word != EMPTY_SLOT && mine < f.word) atomicMin(&a.table[f.slot], mine);
     });
 }
 
@@ -125,55 +114,14 @@ struct NodeArgs {
     uint64_t slots, N, L;            // L = k - 1
 };
 
-// The slot of the (k-1)-mer at pos (INSERT: claimed if absent); flip: the canonical form is its reverse complement; pal: it is its own.
+// The slot of the (k-1)-mer at pos (INSERT: claimed if absent) and its key (flip, pal).
 template <bool INSERT>
-__device__ __forceinline__ uint64_t find_node(const NodeArgs &a, uint64_t pos, bool &flip, bool &pal, unsigned int *err) {
-    unsigned long long key;
-    uint64_t h;
-    const bool narrow = a.L <= 32;
-    if (narrow) {
-        kw::BaseReader rd(a.packed, pos);
-        uint64_t fwd = 0, rc = 0;  // first base in the highest bits: numeric order is lexicographic order
-        for (uint64_t i = 0; i < a.L; i++) {
-            const uint64_t c = rd.next();
-            fwd = (fwd << 2) | c;
-            rc |= (3ull - c) << (2 * i);
-        }
-        flip = rc < fwd;
-        pal = rc == fwd;
-        key = flip ? rc : fwd;  // (never all ones: T...T is not canonical)
-        h = kw::mix64(key);
-    } else {
-        int cmp = 0;
-        for (uint64_t i = 0; i < a.L && !cmp; i++) {
-            const uint32_t x = packed_base(a.packed, pos + i), y = 3u - packed_base(a.packed, pos + a.L - 1 - i);
-            cmp = x < y ? -1 : (x > y ? 1 : 0);
-        }
-        flip = cmp > 0;
-        pal = cmp == 0;
-        kw::BaseReader rd(a.packed, pos);
-        uint64_t hf = 0, hr = 0, pw = 1;
-        for (uint64_t i = 0; i < a.L; i++) {
-            const uint64_t c = rd.next();
-            hf = hf * kw::POLY_BASE + (c + 1);
-            hr += (4 - c) * pw;
-            pw *= kw::POLY_BASE;
-        }
-        h = kw::mix64(hf) + kw::mix64(hr);  // the same for x and rc(x)
-        key = ((h & 0xFFFFFFull) << 40) | pos;
-    }
-    uint64_t s = __umul64hi(h, a.slots);
-    for (uint64_t probe = 0; probe < a.slots; probe++) {
-        unsigned long long cur = INSERT ? load64(&a.table[s]) : a.table[s];
-        if (cur == EMPTY_SLOT) {
-            if (!INSERT) break;
-            const unsigned long long prev = atomicCAS(&a.table[s], EMPTY_SLOT, key);
-            if (prev == EMPTY_SLOT) return s;
-            cur = prev;
-        }
-        if (narrow ? cur == key : ((cur >> 40) == (key >> 40) && kw::same_class(a.packed, pos, cur & POS_LIMIT, a.L))) return s;
-        if (++s == a.slots) s = 0;
-    }
+__device__ __forceinline__ uint64_t find_node(const NodeArgs &a, uint64_t pos, kw::ClassKey &key, unsigned int *err) {
+    key = kw::class_key(a.packed, pos, a.L);
+    const kw::Found f = kw::find_slot<INSERT>(a.table, a.slots, key.hash, key.ident, [&](unsigned long long cur) {
+        return a.L <= 32 ? cur == key.ident : ((cur >> 40) == (key.ident >> 40) && kw::same_class(a.packed, pos, cur & POS_LIMIT, a.L));
+    });
+    if (f.slot < a.slots) return f.slot;
     atomicOr(err, INSERT ? 4u : 8u);
     return 0;
 }
@@ -188,12 +136,12 @@ __global__ __launch_bounds__(hu::EB) void node_insert_kernel(NodeArgs a, unsigne
     if (i >= a.N) return;
     const uint64_t p = a.kpos[i];
     const uint32_t fw = (uint32_t)(2 * i), mi = fw + 1;
-    bool flip, pal;
-    const uint64_t sa = find_node<true>(a, p, flip, pal, err);  // the reading leaves its prefix; its mirror enters the prefix's mirror
-    if (!flip) add_incident(&a.out_e[sa], fw);
+    kw::ClassKey key;
+    const uint64_t sa = find_node<true>(a, p, key, err);  // the reading leaves its prefix; its mirror enters the prefix's mirror
+    if (!key.flip) add_incident(&a.out_e[sa], fw);
     else add_incident(&a.in_e[sa], mi);
-    const uint64_t sb = find_node<true>(a, p + 1, flip, pal, err);  // the reading enters its suffix; its mirror leaves the suffix's mirror
-    if (!flip) add_incident(&a.in_e[sb], fw);
+    const uint64_t sb = find_node<true>(a, p + 1, key, err);  // the reading enters its suffix; its mirror leaves the suffix's mirror
+    if (!key.flip) add_incident(&a.in_e[sb], fw);
     else add_incident(&a.out_e[sb], mi);
 }
 
@@ -201,14 +149,14 @@ __global__ __launch_bounds__(hu::EB) void succ_kernel(NodeArgs a, unsigned int *
     const uint64_t i = hu::gid();
     if (i >= a.N) return;
     const uint64_t p = a.kpos[i];
-    bool flip, pal;
-    const uint64_t sb = find_node<false>(a, p + 1, flip, pal, err);  // head of the reading: its suffix as read
+    kw::ClassKey key;
+    const uint64_t sb = find_node<false>(a, p + 1, key, err);  // head of the reading: its suffix as read
     uint32_t oe = a.out_e[sb], ie = a.in_e[sb];
-    a.succ[2 * i] = (!pal && oe < MULTI32 && ie < MULTI32) ? (flip ? ie ^ 1u : oe) : NONE32;
-    const uint64_t sa = find_node<false>(a, p, flip, pal, err);  // head of the mirror: the reverse complement of the prefix
+    a.succ[2 * i] = (!key.pal && oe < MULTI32 && ie < MULTI32) ? (key.flip ? ie ^ 1u : oe) : NONE32;
+    const uint64_t sa = find_node<false>(a, p, key, err);  // head of the mirror: the reverse complement of the prefix
     oe = a.out_e[sa];
     ie = a.in_e[sa];
-    a.succ[2 * i + 1] = (!pal && oe < MULTI32 && ie < MULTI32) ? (flip ? oe : ie ^ 1u) : NONE32;
+    a.succ[2 * i + 1] = (!key.pal && oe < MULTI32 && ie < MULTI32) ? (key.flip ? oe : ie ^ 1u) : NONE32;
 }
 
 __device__ __forceinline__ uint32_t pred_of(const uint32_t *succ, uint32_t o) {
@@ -319,9 +267,6 @@ __global__ __launch_bounds__(hu::EB) void spell_kernel(const uint32_t *packed, c
         for (uint64_t j = 0; j + 1 < k; j++) out[at + j] = abc[mir ? 3u - packed_base(packed, pos + k - 1 - j) : packed_base(packed, pos + j)];
 }
 
-double ms_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
 int log2_ceil(uint64_t n) {
     int r = 0;
     while ((1ull << r) < n) r++;
@@ -360,58 +305,25 @@ UnitigStore *device_compact_unitigs(const char *data, const uint64_t *off, uint6
     HIP_CHECK(hipSetDevice(device_id));
     device_arena_reset_peak(device_id);
     hipStream_t st = nullptr;
-    const uint64_t n_words = (n_bases + 15) / 16;
 
-    auto t0 = std::chrono::steady_clock::now();
-    char *d_ascii = nullptr;
-    uint32_t *d_packed = nullptr;
-    unsigned long long *d_off = nullptr, *d_small = nullptr;
-    hu::device_malloc(&d_ascii, n_bases);
-    hu::device_malloc(&d_packed, (n_words + 2) * 4);
-    hu::device_malloc(&d_off, (n_rec + 1) * 8);
-    hu::device_malloc(&d_small, 8 * 8);  // [0] first bad character, [1] error bits, [2] distinct k-mers, [3] changed, [4] cycle elements, [5] closed, [6] longest
-    HIP_CHECK(hipMemcpyAsync(d_off, off, (n_rec + 1) * 8, hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipMemsetAsync(d_small, 0, 8 * 8, st));
-    HIP_CHECK(hipMemsetAsync(d_small, 0xFF, 8, st));
-    HIP_CHECK(hipMemsetAsync(d_packed + n_words, 0, 8, st));
-    hu::upload_sliced(d_ascii, data, n_bases, st, device_id);
-    HIP_CHECK(hipStreamSynchronize(st));
-    t.upload_ms = ms_since(t0);
-
-    hipEvent_t ev[7];
-    for (hipEvent_t &e : ev) HIP_CHECK(hipEventCreate(&e));
-    unsigned int *d_err = reinterpret_cast<unsigned int *>(d_small + 1);
-    unsigned int *d_changed = reinterpret_cast<unsigned int *>(d_small + 3);
-    unsigned long long h_small[8];
-    auto read_small = [&]() {
-        HIP_CHECK(hipMemcpyAsync(h_small, d_small, sizeof h_small, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipStreamSynchronize(st));
-        if (h_small[1] & 0xFFFFFFFFull) MTG_DIE("unitig compaction: internal error %llu (hash table)", h_small[1] & 0xFFFFFFFFull);
-    };
+    // ---- upload and pack ----
+    SeqStore seq("sequences", data, off, n_rec, st, device_id);
+    const uint32_t *d_packed = seq.packed;
+    ScalarBlock &small = seq.small;  // [2] distinct k-mers, [3] changed, [4] cycle elements, [5] closed, [6] longest
+    const char *const stage = "unitig compaction";
+    unsigned int *d_err = small.err();
+    unsigned int *d_changed = reinterpret_cast<unsigned int *>(small.d + 3);
+    t.upload_ms = seq.upload_ms;
+    t.pack_ms = seq.pack_ms;
     auto free_all = [&](std::initializer_list<const void *> ps) { for (const void *p : ps) hu::device_free(p); };
-    auto elapsed = [&](int a, int b) { float f = 0.f; HIP_CHECK(hipEventElapsedTime(&f, ev[a], ev[b])); return (double)f; };
-
-    // ---- pack ----
-    HIP_CHECK(hipEventRecord(ev[0], st));
-    pack_kernel<<<hu::grid_for(n_words), hu::EB, 0, st>>>(d_ascii, n_bases, d_packed, d_small);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipEventRecord(ev[1], st));
-    hu::device_free(d_ascii);  // (synchronises: the pack is done)
-    read_small();
-    if (h_small[0] != EMPTY_SLOT) MTG_DIE("sequences: character at offset %llu is not in the DNA alphabet (ACGT)", h_small[0]);
-    if (r.windows == 0) {  // nothing is as long as k
-        HIP_CHECK(hipEventRecord(ev[2], st));
-        HIP_CHECK(hipEventSynchronize(ev[2]));
-        t.pack_ms = elapsed(0, 1);
-        for (hipEvent_t &e : ev) HIP_CHECK(hipEventDestroy(e));
-        free_all({d_packed, d_off, d_small});
-        return finish();
-    }
+    if (r.windows == 0) return finish();  // nothing is as long as k
+    PhaseEvents<6> ev;
+    ev.mark(0, st);
 
     // ---- insert: the creator of every k-mer class ----
     const uint64_t slots = std::max<uint64_t>(8, (2 * r.windows + 7) / 8 * 8);
     KmerArgs ka{};
-    ka.packed = d_packed; ka.off = d_off; ka.slots = slots;
+    ka.packed = d_packed; ka.off = seq.off; ka.slots = slots;
     kw::window_args_set_k(ka, k);
     hu::device_malloc(&ka.table, slots * 8);
     HIP_CHECK(hipMemsetAsync(ka.table, 0xFF, slots * 8, st));
@@ -421,16 +333,16 @@ UnitigStore *device_compact_unitigs(const char *data, const uint64_t *off, uint6
         else insert_kernel<false><<<grid, hu::EB, 0, st>>>(ka, n_bases, n_rec, d_err);
         HIP_CHECK(hipGetLastError());
     }
-    HIP_CHECK(hipEventRecord(ev[2], st));
+    ev.mark(1, st);
 
     // ---- ids in creator order ----
     uint32_t *d_id_of_pos = nullptr;
     hu::device_malloc(&d_id_of_pos, n_bases * 4);
     HIP_CHECK(hipMemsetAsync(d_id_of_pos, 0, n_bases * 4, st));
-    mark_kernel<<<(unsigned)std::min<uint64_t>(hu::grid_for(slots), 16384), hu::EB, 0, st>>>(ka.table, slots, d_id_of_pos, d_small + 2);
+    mark_kernel<<<(unsigned)std::min<uint64_t>(hu::grid_for(slots), 16384), hu::EB, 0, st>>>(ka.table, slots, d_id_of_pos, small.d + 2);
     HIP_CHECK(hipGetLastError());
-    read_small();
-    const uint64_t N = r.distinct_kmers = h_small[2], n_or = 2 * N;
+    small.read(st, stage);
+    const uint64_t N = r.distinct_kmers = small.h[2], n_or = 2 * N;
     if (N > MAX_KMERS) MTG_DIE("mtg_compact_unitigs: %llu distinct k-mers; oriented k-mer ids are 32-bit", (unsigned long long)N);
     uint32_t *d_bsum32 = nullptr;
     unsigned long long *d_kpos = nullptr;
@@ -439,8 +351,8 @@ UnitigStore *device_compact_unitigs(const char *data, const uint64_t *off, uint6
     hu::scan_u32<uint32_t>(st, d_id_of_pos, n_bases, d_id_of_pos, d_bsum32, d_bsum32 + hu::scan_blocks(n_bases) + 1);
     kpos_kernel<<<hu::grid_for(slots), hu::EB, 0, st>>>(ka.table, slots, d_id_of_pos, d_kpos);
     HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipEventRecord(ev[3], st));
-    free_all({ka.table, d_id_of_pos, d_bsum32, d_off});
+    ev.mark(2, st);
+    free_all({ka.table, d_id_of_pos, d_bsum32});
 
     // ---- the (k-1)-mer classes and succ ----
     NodeArgs na{};
@@ -456,9 +368,9 @@ UnitigStore *device_compact_unitigs(const char *data, const uint64_t *off, uint6
     node_insert_kernel<<<hu::grid_for(N), hu::EB, 0, st>>>(na, d_err);
     succ_kernel<<<hu::grid_for(N), hu::EB, 0, st>>>(na, d_err);
     HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipEventRecord(ev[4], st));
+    ev.mark(3, st);
     free_all({na.table, na.out_e, na.in_e});
-    read_small();
+    small.read(st, stage);
 
     // ---- ranks by pointer jumping ----
     unsigned long long *d_pairs = nullptr;
@@ -472,8 +384,8 @@ UnitigStore *device_compact_unitigs(const char *data, const uint64_t *off, uint6
             jump_kernel<<<hu::grid_for(n), hu::EB, 0, st>>>(d_pairs, n, list, d_changed);
             HIP_CHECK(hipGetLastError());
             rounds++;
-            read_small();
-            if (!(h_small[3] & 0xFFFFFFFFull)) return true;
+            small.read(st, stage);
+            if (!(small.h[3] & 0xFFFFFFFFull)) return true;
         }
         return false;
     };
@@ -481,10 +393,10 @@ UnitigStore *device_compact_unitigs(const char *data, const uint64_t *off, uint6
         uint32_t *d_list = nullptr;
         unsigned long long *d_buf = nullptr;
         hu::device_malloc(&d_list, n_or * 4);
-        cycle_list_kernel<<<hu::grid_for(n_or), hu::EB, 0, st>>>(d_pairs, na.succ, n_or, d_list, d_small + 4);
+        cycle_list_kernel<<<hu::grid_for(n_or), hu::EB, 0, st>>>(d_pairs, na.succ, n_or, d_list, small.d + 4);
         HIP_CHECK(hipGetLastError());
-        read_small();
-        const uint64_t C = h_small[4];
+        small.read(st, stage);
+        const uint64_t C = small.h[4];
         if (C == 0 || C > n_or) MTG_DIE("unitig compaction: internal error (%llu elements on closed walks)", (unsigned long long)C);
         hu::device_malloc(&d_buf, n_or * 8);
         cycle_min_init_kernel<<<hu::grid_for(C), hu::EB, 0, st>>>(na.succ, d_list, C, d_pairs);
@@ -498,7 +410,7 @@ UnitigStore *device_compact_unitigs(const char *data, const uint64_t *off, uint6
         if (!jump_rounds(C, d_list, log2_ceil(C) + 2)) MTG_DIE("unitig compaction: internal error (a cut cycle does not settle)");
         free_all({d_list, d_buf});
     }
-    HIP_CHECK(hipEventRecord(ev[5], st));
+    ev.mark(4, st);
 
     // ---- emit ----
     uint32_t *d_wmin = nullptr, *d_wlen = nullptr, *d_lead_flag = nullptr, *d_lead_chars = nullptr;
@@ -515,7 +427,7 @@ UnitigStore *device_compact_unitigs(const char *data, const uint64_t *off, uint6
     HIP_CHECK(hipMemsetAsync(d_lead_flag, 0, N * 4, st));
     HIP_CHECK(hipMemsetAsync(d_lead_chars, 0, N * 4, st));
     walk_kernel<<<hu::grid_for(n_or), hu::EB, 0, st>>>(d_pairs, na.succ, n_or, d_wmin, d_wlen);
-    leader_kernel<<<hu::grid_for(n_or), hu::EB, 0, st>>>(d_pairs, na.succ, n_or, d_wmin, d_wlen, (uint32_t)k, d_lead_flag, d_lead_chars, d_small + 5);
+    leader_kernel<<<hu::grid_for(n_or), hu::EB, 0, st>>>(d_pairs, na.succ, n_or, d_wmin, d_wlen, (uint32_t)k, d_lead_flag, d_lead_chars, small.d + 5);
     uint32_t *d_n_unitigs = d_bsum32 + hu::scan_blocks(N) + 1;
     uint64_t *d_n_chars = d_bsum64 + hu::scan_blocks(N) + 1;
     hu::scan_u32<uint32_t>(st, d_lead_flag, N, d_lead_flag, d_bsum32, d_n_unitigs);
@@ -524,11 +436,11 @@ UnitigStore *device_compact_unitigs(const char *data, const uint64_t *off, uint6
     uint64_t n_chars = 0;
     HIP_CHECK(hipMemcpyAsync(&n_unitigs, d_n_unitigs, 4, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipMemcpyAsync(&n_chars, d_n_chars, 8, hipMemcpyDeviceToHost, st));
-    read_small();
+    small.read(st, stage);
     r.unitigs = n_unitigs;
     r.unitig_characters = n_chars;
-    r.closed_walks = h_small[5];
-    r.longest_unitig_kmers = h_small[6];
+    r.closed_walks = small.h[5];
+    r.longest_unitig_kmers = small.h[6];
     if (n_chars != N + (k - 1) * r.unitigs) MTG_DIE("unitig compaction: internal error (%llu characters for %llu k-mers in %llu unitigs)",
                                                     (unsigned long long)n_chars, (unsigned long long)N, (unsigned long long)r.unitigs);
     char *d_out = nullptr;
@@ -538,25 +450,23 @@ UnitigStore *device_compact_unitigs(const char *data, const uint64_t *off, uint6
     offsets_kernel<<<hu::grid_for(N), hu::EB, 0, st>>>(d_lead_chars, d_lead_flag, d_char_off, N, d_out_off);
     spell_kernel<<<hu::grid_for(n_or), hu::EB, 0, st>>>(d_packed, d_kpos, d_pairs, d_wmin, d_char_off, n_or, k, d_out);
     HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipEventRecord(ev[6], st));
+    ev.mark(5, st);
     HIP_CHECK(hipStreamSynchronize(st));
 
-    t0 = std::chrono::steady_clock::now();
+    const auto t0 = std::chrono::steady_clock::now();
     store->data.resize(n_chars);
     store->off.resize(r.unitigs + 1);
     hu::download_sliced(&store->data[0], d_out, n_chars, st, device_id);
     hu::download_sliced(store->off.data(), d_out_off, r.unitigs * 8, st, device_id);
     store->off[r.unitigs] = n_chars;
     t.download_ms = ms_since(t0);
-    t.pack_ms = elapsed(0, 1);
-    t.insert_ms = elapsed(1, 2);
-    t.ids_ms = elapsed(2, 3);
-    t.nodes_ms = elapsed(3, 4);
-    t.rank_ms = elapsed(4, 5);
-    t.emit_ms = elapsed(5, 6);
+    t.insert_ms = ev.ms(0, 1);
+    t.ids_ms = ev.ms(1, 2);
+    t.nodes_ms = ev.ms(2, 3);
+    t.rank_ms = ev.ms(3, 4);
+    t.emit_ms = ev.ms(4, 5);
     t.rounds = rounds;
-    for (hipEvent_t &e : ev) HIP_CHECK(hipEventDestroy(e));
-    free_all({d_packed, d_small, d_kpos, na.succ, d_pairs, d_wmin, d_wlen, d_lead_flag, d_lead_chars, d_char_off, d_bsum32, d_bsum64, d_out, d_out_off});
+    free_all({d_kpos, na.succ, d_pairs, d_wmin, d_wlen, d_lead_flag, d_lead_chars, d_char_off, d_bsum32, d_bsum64, d_out, d_out_off});
     uint64_t arena[4];
     device_arena_stats(device_id, arena);
     t.peak_arena_bytes = arena[2];
@@ -565,7 +475,7 @@ UnitigStore *device_compact_unitigs(const char *data, const uint64_t *off, uint6
     // creator; per distinct k-mer its creator written and read twice with 2 (k + 15) / 16 packed words each time, two node slots
     // and two incident words written and read, two succ words; per oriented k-mer one pair per round at the least (read), succ and the
     // pair in the emit kernels, wmin / wlen; per leader flag, length and offset; and the output characters and offsets.
-    t.bytes = n_bases + n_words * 4 + r.windows * 8 + n_words * 4 + slots * 8 * 3 + n_bases * 4 * 3 + N * 4 +
+    t.bytes = n_bases + seq.n_words * 4 + r.windows * 8 + seq.n_words * 4 + slots * 8 * 3 + n_bases * 4 * 3 + N * 4 +
               N * (8 * 3 + 2 * 4 * ((k + 15) / 16 + 1) + 2 * (8 + 4) * 2 + 8) + n_or * 8 * (uint64_t)std::max(rounds, 1) +
               n_or * (4 + 8 + 8 + 8 + 4) + N * (4 * 3 + 4 * 2 + 8 * 2) + n_chars + r.unitigs * 8;
     return finish();

@@ -1,18 +1,22 @@
-// kmer_window_device.hpp -- the walk over the k-mer windows of a 2-bit packed sequence store (pack_device.hpp), shared by the k-mer
-// set comparison (kmer_compare_device.hip) and the unitig compaction (compact_device.hip).
+// kmer_window_device.hpp -- k-mer classes {x, rc(x)} over a 2-bit packed sequence store (pack_device.hpp), shared by the plain-FASTA
+// join (fasta_in_device.hip), the k-mer set comparison (kmer_compare_device.hip) and the unitig compaction (compact_device.hip):
+// the rolling walk over the windows of a record (for_each_window), the canonical key of the bases at one position (class_key) and the
+// open-addressing table of classes (find_slot, with the exactness argument every caller relies on).
 //
-// A thread owns RUN consecutive window start positions. It finds the record of the first one by a binary search in the offsets and
-// then cuts its run at every record end it meets (no per-base flag array). Inside a record it reads the packed words once, front to
-// back, and ROLLS the window: for k <= 31 the forward and the reverse-complement 2-bit codes (2 bits in, 2 bits out), beyond that two
-// polynomial hashes mod 2^64 of the forward and the reverse-complement string (one base in, one base out, whatever k is; a second
-// reader k bases behind supplies the base that leaves). Identity beyond what a hash can say is decided base by base in the packed
-// store (same_class: x == y or x == rc(y), 16 bases per compare), so nothing probabilistic remains.
+// The walk: a thread owns RUN consecutive window start positions. It finds the record of the first one by a binary search in the
+// offsets and then cuts its run at every record end it meets (no per-base flag array). Inside a record it reads the packed words once,
+// front to back, and ROLLS the window: for k <= 31 the forward and the reverse-complement 2-bit codes (2 bits in, 2 bits out), beyond
+// that two polynomial hashes mod 2^64 of the forward and the reverse-complement string (one base in, one base out, whatever k is; a
+// second reader k bases behind supplies the base that leaves). Identity beyond what a hash can say is decided base by base in the
+// packed store (same_class: x == y or x == rc(y), 16 bases per compare), so nothing probabilistic remains.
 // Everything here is a device inline or a template: each translation unit that includes the header gets its own copy.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+
+#include "pack_device.hpp"
 
 namespace mtg {
 namespace kw {
@@ -29,7 +33,7 @@ __device__ __forceinline__ uint64_t mix64(uint64_t z) {  // splitmix64's finalis
 
 // what the window walk reads
 struct WindowArgs {
-    const uint32_t *packed;         // the bases (one word of padding behind the last)
+    const uint32_t *packed;         // the bases (SeqStore::packed)
     const unsigned long long *off;  // [records + 1] global base offsets
     uint64_t k;
     uint64_t top;        // k <= 31: 2 (k - 1), where a base enters the reverse-complement code
@@ -94,7 +98,12 @@ __device__ inline bool same_class(const uint32_t *packed, uint64_t p, uint64_t q
     return true;
 }
 
-// What a window is to a table. k <= 31: `ident` is the canonical code. k >= 32: tag << 40 | position.
+// the two strand hashes of a string as one hash of its class (the same for x and rc(x)), and the identity word a table keeps for
+// a class too long for a code: 22 bits of that hash as a tag, then the position of one occurrence
+__device__ __forceinline__ uint64_t strands_hash(uint64_t hf, uint64_t hr) { return mix64(hf) + mix64(hr); }
+__device__ __forceinline__ uint64_t tagged_pos(uint64_t hash, uint64_t pos) { return ((hash & 0x3FFFFFull) << 40) | pos; }
+
+// What a window is to a table. k <= 31: `ident` is the canonical code. k >= 32: tagged_pos.
 struct Window {
     uint64_t hash, ident;
 };
@@ -143,8 +152,8 @@ __device__ __forceinline__ void for_each_window(const WindowArgs &a, uint64_t p0
                 pw *= POLY_BASE;
             }
             for (uint64_t q = p;;) {
-                const uint64_t h = mix64(hf) + mix64(hr);  // the same for x and rc(x)
-                op(q, Window{h, ((h & 0x3FFFFFull) << 40) | q});
+                const uint64_t h = strands_hash(hf, hr);
+                op(q, Window{h, tagged_pos(h, q)});
                 if (++q >= last) break;
                 const uint64_t o = trail.next(), c = lead.next();
                 hf = (hf - (o + 1) * a.pow_k1) * POLY_BASE + (c + 1);
@@ -153,6 +162,91 @@ __device__ __forceinline__ void for_each_window(const WindowArgs &a, uint64_t p0
         }
         p = last;
     }
+}
+
+// The key of the class of the L bases at `pos`, not rolled (the (k-1)-mer ends of the join and of the compaction's nodes).
+// flip: the canonical form (the lexicographically smaller of x and rc(x)) is rc(x); pal: x == rc(x). L <= 32: `ident` is the
+// canonical code (never all ones: T...T is not canonical) and `hash` a bijection of it, so equal hashes ARE equal classes. Beyond:
+// `hash` only places and pre-filters, `ident` is tagged_pos and identity is same_class.
+struct ClassKey {
+    uint64_t hash, ident;
+    bool flip, pal;
+};
+__device__ __forceinline__ ClassKey class_key(const uint32_t *packed, uint64_t pos, uint64_t L) {
+    ClassKey key;
+    BaseReader rd(packed, pos);
+    if (L <= 32) {
+        uint64_t fwd = 0, rc = 0;  // first base in the highest bits: numeric order is lexicographic order
+        for (uint64_t i = 0; i < L; i++) {
+            const uint64_t c = rd.next();
+            fwd = (fwd << 2) | c;
+            rc |= (3ull - c) << (2 * i);
+        }
+        key.flip = rc < fwd;
+        key.pal = rc == fwd;
+        key.ident = key.flip ? rc : fwd;
+        key.hash = mix64(key.ident);
+    } else {
+        int cmp = 0;
+        for (uint64_t i = 0; i < L && !cmp; i++) {
+            const uint32_t x = packed_base(packed, pos + i), y = 3u - packed_base(packed, pos + L - 1 - i);
+            cmp = x < y ? -1 : (x > y ? 1 : 0);
+        }
+        key.flip = cmp > 0;
+        key.pal = cmp == 0;
+        uint64_t hf = 0, hr = 0, pw = 1;
+        for (uint64_t i = 0; i < L; i++) {
+            const uint64_t c = rd.next();
+            hf = hf * POLY_BASE + (c + 1);
+            hr += (4 - c) * pw;
+            pw *= POLY_BASE;
+        }
+        key.hash = strands_hash(hf, hr);
+        key.ident = tagged_pos(key.hash, pos);
+    }
+    return key;
+}
+
+// ---- the table of classes ----
+// Open addressing in HBM: 64-bit slots, EMPTY_SLOT marks a free one (no caller's word is all ones: a canonical code is never T...T,
+// and every other word holds a position or an occurrence number below its field's all-ones value), linear probing from
+// umulhi(hash, slots) on a table of any size. A slot's word = what names the class (a code, or a tag plus where to find one of its
+// occurrences) | the caller's payload; `same(word)` says whether an occupied slot holds the caller's class.
+//
+// Exactness. `same` is exact for every caller: either it compares canonical codes (hashes that are bijections of them), or a tag
+// match only pre-filters and kw::same_class settles identity base by base in the packed store. A hash collision costs a compare,
+// never a wrong answer.
+//
+// Order independence. An empty slot is claimed by CAS, and a claimed slot never changes its class (callers only lower the
+// payload among occurrences of that class, or OR bits into it). A probe for class c starts at a slot that depends on c alone and
+// walks on until it meets a slot that is empty or holds c. Slots only go from empty to occupied, so what a probe for c has walked
+// over stays in its way: every later probe for c walks over the same slots and ends at the one that holds c.
+// Hence every class owns exactly one slot. WHICH slot, and which occurrence claimed it, depends on the order the CAS land in; the
+// callers take from a slot only what does not: a minimum (atomicMin), a union of bits (atomicOr), a multiset of insertions, or
+// -- after the inserting kernel has finished -- the slot as the class's name.
+//
+// find_slot returns the slot of the class and the word found there. CLAIM: an empty slot on the way is claimed with `mine`, and
+// the word returned is then EMPTY_SLOT (the caller's word is in, nothing to merge). slot == slots: the class is absent (!CLAIM) or
+// the table is full (CLAIM; callers size it at 2 slots per insertion at the least, so this is an internal error).
+constexpr unsigned long long EMPTY_SLOT = ~0ull;
+struct Found {
+    uint64_t slot;
+    unsigned long long word;
+};
+template <bool CLAIM, typename Same>
+__device__ __forceinline__ Found find_slot(unsigned long long *table, uint64_t slots, uint64_t hash, unsigned long long mine, Same same) {
+    uint64_t s = __umul64hi(hash, slots);
+    for (uint64_t probe = 0; probe < slots; probe++) {
+        unsigned long long cur = CLAIM ? __hip_atomic_load(&table[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : table[s];
+        if (cur == EMPTY_SLOT) {
+            if (!CLAIM) break;
+            cur = atomicCAS(&table[s], EMPTY_SLOT, mine);
+            if (cur == EMPTY_SLOT) return Found{s, EMPTY_SLOT};
+        }
+        if (same(cur)) return Found{s, cur};
+        if (++s == slots) s = 0;
+    }
+    return Found{slots, EMPTY_SLOT};
 }
 
 }  // namespace kw

@@ -5,7 +5,7 @@
 // overlap with what is already written (offset k-1 after an original edge, k-1-weight after a dummy edge, :533-537; a backwards
 // edge appends revcomp(seq[0..len-offset]), :567-596), nothing for dummy edges (:519-531), "\n" at the end (:601).
 //
-// Layout: the unitig store is packed to 2 bits per base on the device (pack_device.hpp; only ACGT is representable, like the reference's
+// Layout: the unitig store is packed to 2 bits per base on the device (SeqStore, pack_device.hpp; only ACGT is representable, like the reference's
 // DnaAlphabet store; anything else aborts). Every walk position p (one edge of one walk) owns an output region
 //   [header bytes if p starts a walk (incl. the "\n" that closes the previous walk)] [its characters]
 // whose start is an exclusive prefix sum; the writing kernel is OUTPUT-centric: a workgroup takes 256 consecutive positions, its
@@ -228,7 +228,6 @@ uint64_t device_write_walks_text(const HostGraph &g, uint64_t n_walks, const uin
     if (gfa) head = (gfa_header ? std::string(gfa_header) : "H\tKL:Z:" + std::to_string(k)) + "\n";
     const uint64_t P = resident ? resident->n_edges : (n_walks ? limits[n_walks - 1] : 0);
     const uint64_t n_orig = g.n_original_edges, n_dummy = g.edge_count() - n_orig, U = n_orig / 2;
-    const uint64_t n_bases = seq_off[U];
     uint64_t begin = 0;
     for (uint64_t i = 0; i < n_walks && !resident; i++) {  // the same input checks as the host path
         if (limits[i] <= begin) MTG_DIE("empty walk %llu", (unsigned long long)i);
@@ -236,24 +235,16 @@ uint64_t device_write_walks_text(const HostGraph &g, uint64_t n_walks, const uin
         begin = limits[i];
     }
     hipStream_t st = nullptr;
-    char *d_ascii = nullptr, *d_out = nullptr;
-    uint32_t *d_packed = nullptr, *d_edges = nullptr, *d_ws = nullptr, *d_unitig = nullptr, *d_dw = nullptr, *d_lo = nullptr, *d_hi = nullptr;
+    SeqStore seq("unitig sequences", seqs, seq_off, U, st, device_id);
+    char *d_out = nullptr;
+    uint32_t *d_edges = nullptr, *d_ws = nullptr, *d_unitig = nullptr, *d_dw = nullptr, *d_lo = nullptr, *d_hi = nullptr;
     uint8_t *d_fwd = nullptr;
-    unsigned long long *d_seq_off = nullptr, *d_limits = nullptr, *d_start = nullptr, *d_bsum = nullptr, *d_tot = nullptr;
-    const uint64_t n_words = (n_bases + 15) / 16;
-    hu::device_malloc(&d_ascii, std::max<uint64_t>(n_bases, 1));
-    hu::device_malloc(&d_packed, std::max<uint64_t>(n_words, 1) * 4);
-    hu::device_malloc(&d_tot, 16);
-    HIP_CHECK(hipMemcpyAsync(d_ascii, seqs, n_bases, hipMemcpyHostToDevice, st));
-    const unsigned long long none = ~0ull;
-    HIP_CHECK(hipMemcpyAsync(d_tot + 1, &none, 8, hipMemcpyHostToDevice, st));
-    if (n_words) hipLaunchKernelGGL(pack_kernel, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, st, d_ascii, n_bases, d_packed, d_tot + 1);
-    HIP_CHECK(hipGetLastError());
+    unsigned long long *d_limits = nullptr, *d_start = nullptr, *d_bsum = nullptr, *d_tot = nullptr;
+    hu::device_malloc(&d_tot, 8);
     // per-edge tables the positions index (u32 / u8 instead of the host graph's 64-bit fields)
     PodVec<uint32_t> h_dw(std::max<uint64_t>(n_dummy / 2, 1));
     for (uint64_t i = 0; i < n_dummy / 2; i++) h_dw[i] = (uint32_t)std::min<uint64_t>(g.w_biedge[n_orig / 2 + i], 0xFFFFFFFFull);
     hu::device_malloc(&d_dw, std::max<uint64_t>(n_dummy / 2, 1) * 4);
-    hu::device_malloc(&d_seq_off, (U + 1) * 8);
     if (!resident) {
         hu::device_malloc(&d_edges, std::max<uint64_t>(P, 1) * 4);
         hu::device_malloc(&d_limits, std::max<uint64_t>(n_walks, 1) * 8);
@@ -268,7 +259,6 @@ uint64_t device_write_walks_text(const HostGraph &g, uint64_t n_walks, const uin
     const uint64_t nb = (P + 1 + 1023) / 1024;
     hu::device_malloc(&d_bsum, nb * 8);
     if (n_dummy) HIP_CHECK(hipMemcpyAsync(d_dw, h_dw.data(), n_dummy / 2 * 4, hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipMemcpyAsync(d_seq_off, seq_off, (U + 1) * 8, hipMemcpyHostToDevice, st));
     HIP_CHECK(hipMemsetAsync(d_ws, 0, (P + 1) * 4, st));
     if (resident) {
         hipLaunchKernelGGL(mark_starts32_kernel, dim3((unsigned)((n_walks + 1 + 255) / 256)), dim3(256), 0, st, resident->d_limits, resident->d_edges, n_walks, P,
@@ -279,26 +269,23 @@ uint64_t device_write_walks_text(const HostGraph &g, uint64_t n_walks, const uin
         hipLaunchKernelGGL(mark_starts_kernel, dim3((unsigned)((n_walks + 1 + 255) / 256)), dim3(256), 0, st, d_limits, n_walks, P, d_ws);
     }
     SpellArgs a{};
-    a.edges = resident ? resident->d_edges : d_edges; a.walk_start = d_ws; a.dummy_w = d_dw; a.seq_off = d_seq_off; a.packed = d_packed;
+    a.edges = resident ? resident->d_edges : d_edges; a.walk_start = d_ws; a.dummy_w = d_dw; a.seq_off = seq.off; a.packed = seq.packed;
     a.n_pos = P; a.n_orig = n_orig; a.k = (uint32_t)k; a.rec_prefix = gfa ? 2 : 1; a.sep = gfa ? '\t' : '\n'; a.head_bytes = head.size();
     hipLaunchKernelGGL(extent_kernel, dim3((unsigned)((P + 1 + 255) / 256)), dim3(256), 0, st, a, d_lo, d_hi);
     hipLaunchKernelGGL(scan64_reduce_kernel, dim3((unsigned)nb), dim3(1024), 0, st, d_lo, d_hi, P + 1, d_bsum);
     hipLaunchKernelGGL(scan64_sums_kernel, dim3(1), dim3(1024), 0, st, d_bsum, nb, d_tot, (unsigned long long)head.size());
     hipLaunchKernelGGL(scan64_apply_kernel, dim3((unsigned)nb), dim3(1024), 0, st, d_lo, d_hi, P + 1, d_bsum, d_start);
     HIP_CHECK(hipGetLastError());
-    unsigned long long h_tot[2] = {0, 0}, h_err[2] = {~0ull, ~0ull};
-    HIP_CHECK(hipMemcpyAsync(h_tot, d_tot, 16, hipMemcpyDeviceToHost, st));
+    unsigned long long h_tot = 0, h_err[2] = {~0ull, ~0ull};
+    HIP_CHECK(hipMemcpyAsync(&h_tot, d_tot, 8, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipMemcpyAsync(h_err, d_err, 16, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
     hu::device_free(d_err);
     if (h_err[0] != ~0ull && h_err[0] < h_err[1]) MTG_DIE("empty walk %llu", h_err[0]);  // (the first offending walk, as the host loop reports it)
     if (h_err[1] != ~0ull) MTG_DIE("walk %llu starts with a dummy edge (bin.rs:489)", h_err[1]);
-    if (h_tot[1] != none) MTG_DIE("unitig sequences: character at offset %llu is not in the DNA alphabet (ACGT)", h_tot[1]);
-    const uint64_t total = n_walks ? h_tot[0] : head.size();
+    const uint64_t total = n_walks ? h_tot : head.size();
     char *out = static_cast<char *>(std::malloc(total + 1));
     if (!out) MTG_DIE("out of memory (%llu bytes)", (unsigned long long)total);
-    hu::device_free(d_ascii);
-    d_ascii = nullptr;
     double ms = 0.0;
     if (n_walks) {
         hu::device_malloc(&d_out, total);
@@ -320,9 +307,9 @@ uint64_t device_write_walks_text(const HostGraph &g, uint64_t n_walks, const uin
     } else if (head.size()) std::memcpy(out, head.data(), head.size());
     out[total] = '\0';
     if (kernel_ms_out) *kernel_ms_out = ms;
-    if (bytes_out) *bytes_out = total + n_bases / 4 + (P + 1) * (8 + 4 + 4);
-    for (void *p : {(void *)d_out, (void *)d_packed, (void *)d_edges, (void *)d_ws, (void *)d_unitig, (void *)d_dw, (void *)d_lo, (void *)d_hi,
-                    (void *)d_fwd, (void *)d_seq_off, (void *)d_limits, (void *)d_start, (void *)d_bsum, (void *)d_tot})
+    if (bytes_out) *bytes_out = total + seq.n_bases / 4 + (P + 1) * (8 + 4 + 4);
+    for (void *p : {(void *)d_out, (void *)d_edges, (void *)d_ws, (void *)d_unitig, (void *)d_dw, (void *)d_lo, (void *)d_hi,
+                    (void *)d_fwd, (void *)d_limits, (void *)d_start, (void *)d_bsum, (void *)d_tot})
         hu::device_free(p);
     *out_buf = out;
     return total;
