@@ -520,6 +520,39 @@ void mtg_compact_unitigs_store(const mtg_unitigs *in, uint64_t k, int device_id,
  * ms -- HIP events around the kernel phases --; download ms and the whole call (host clock); pointer-jumping rounds; bytes the
  * kernels must move at the least; peak of live device-arena bytes}. */
 void mtg_last_compact_times(double out[12]);
+/* A k-mer set kept on GPU `device_id` and asked which k-mers of other sequences it holds (kmer_query_device.hip; there
+ * is no CPU path). The indexed set is a set in mtg_compare_kmer_sets' sense: the canonical k-mers of the windows of length k inside
+ * one record; records shorter than k contribute nothing, a character outside ACGT aborts, k >= 1. The index holds device memory
+ * (info.device_bytes) until mtg_kmer_index_free; mtg_release_device_memory leaves it intact. Limits: fewer than 2^40 - 1 bases in
+ * the index and in one query call, k < 2^32. */
+typedef struct mtg_kmer_index mtg_kmer_index;
+typedef struct mtg_kmer_index_info {
+    uint64_t k, records, characters; /* as given */
+    uint64_t occurrences;            /* windows: sum over the records of max(0, len - k + 1) */
+    uint64_t distinct;               /* distinct canonical k-mers */
+    uint64_t slots, device_bytes;    /* of the table; what the index keeps on the device */
+} mtg_kmer_index_info;
+mtg_kmer_index *mtg_kmer_index_build(const char *seq, const uint64_t *off, uint64_t n, uint64_t k, int device_id);
+/* The same over a store as mtg_read_bcalm2 / mtg_read_fasta / mtg_read_sequences / mtg_compact_unitigs hand it out. */
+mtg_kmer_index *mtg_kmer_index_build_store(const mtg_unitigs *store, uint64_t k, int device_id);
+void mtg_kmer_index_get_info(const mtg_kmer_index *ix, mtg_kmer_index_info *out);
+/* The query: n records of ARBITRARY bytes (concatenated plus n + 1 offsets, off[0] = 0). For record r of length L: kmers[r] =
+ * max(0, L - k + 1); a window is valid iff all k of its characters are in ACGTacgt; valid[r] = the valid windows, found[r] = the
+ * valid windows whose canonical form is in the index. present_bits / valid_bits (each may be NULL; (off[n] + 63) / 64 words): over
+ * the global base positions of the query, bit p & 63 of word p >> 6 of valid_bits is set iff a valid window starts at p, of
+ * present_bits iff that window is in the index; every other bit is 0. Exact integers, a function of the inputs alone; the index is
+ * not changed. An empty index finds nothing; an empty query returns at once. */
+void mtg_kmer_index_query(const mtg_kmer_index *ix, const char *seq, const uint64_t *off, uint64_t n,
+                          uint64_t *kmers, uint64_t *valid, uint64_t *found, /* [n] each */
+                          uint64_t *present_bits, uint64_t *valid_bits);     /* nullable */
+void mtg_kmer_index_free(mtg_kmer_index *ix);
+/* Of the last index build and the last query on this thread, in ms: {build: upload (host clock), pack, insert (with the table's fill
+ * and the count); query: upload (host clock), pack, probe} -- HIP events around the kernels. */
+void mtg_last_kmer_query_times(double out[6]);
+/* mtg_read_sequences without an alphabet rule: every byte of a sequence line is kept as it is (`N`, IUPAC codes, lower case), for
+ * the queries of a k-mer index. *names_out = the record names as a second store with the same accessors: the header text behind `>`
+ * up to the first white space. */
+void mtg_read_sequences_named(const char *path, mtg_unitigs **seqs_out, mtg_unitigs **names_out);
 uint64_t mtg_unitigs_count(const mtg_unitigs *u);
 const char *mtg_unitigs_data(const mtg_unitigs *u);        /* concatenated ASCII sequences */
 const uint64_t *mtg_unitigs_offsets(const mtg_unitigs *u); /* count + 1 offsets into data */

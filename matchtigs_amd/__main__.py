@@ -9,6 +9,9 @@ set into maximal unitigs on the GPU first, then goes the `--fa-in
 any input. All work happens inside
 libmatchtigs.so; this file only parses flags and prints the reference's closing log line (bin.rs:1209-1211). `--verify` and
 `--verify-fa` (not in the reference) check on the GPU that tigs spell exactly the input's k-mer set.
+`--query-fa` with `--query-out` (not in the reference) asks, after the tig outputs, which k-mers of other sequences -- reads,
+contigs, `N` and all -- are in the input's k-mer set: per record the windows, the valid ones (ACGT only) and those found, as a TSV,
+and with `--query-presence-out` one `1` / `0` / `-` character per window; the set is indexed once on the GPU.
 """
 from __future__ import annotations
 
@@ -46,6 +49,13 @@ def main(argv=None) -> int:
     ap.add_argument("--verify-fa", action="append", metavar="PATH",
                     help="check an existing tig fasta (optionally .gz) against the input's k-mer set; repeatable; computes nothing "
                          "(not in the reference)")
+    ap.add_argument("--query-fa", action="append", metavar="PATH",
+                    help="sequences (fasta, optionally .gz; any characters) whose k-mers are looked up in the input's k-mer set on the "
+                         "GPU; repeatable; needs --query-out (not in the reference)")
+    ap.add_argument("--query-out", metavar="PATH",
+                    help="TSV (.gz => gzip) with one row per record of the --query-fa files: record, length, kmers, valid, found")
+    ap.add_argument("--query-presence-out", metavar="PATH",
+                    help="per query record a line with one character per k-mer: 1 in the set, 0 not, - holds a non-ACGT character (.gz => gzip)")
     args = ap.parse_args(argv)
 
     n_inputs = sum(x is not None for x in (args.bcalm_in, args.gfa_in, args.fa_in, args.seq_in))
@@ -62,7 +72,11 @@ def main(argv=None) -> int:
         ap.error("compression level must be in 0..9")
     if args.matchtigs_duplication_bitvector_out and not (args.matchtigs_fa_out or args.matchtigs_gfa_out):
         ap.error("--matchtigs-duplication-bitvector-out needs --matchtigs-fa-out or --matchtigs-gfa-out (bin.rs:955-957)")
-    if not (args.greedytigs_fa_out or args.eulertigs_fa_out or args.greedytigs_gfa_out or args.eulertigs_gfa_out
+    if bool(args.query_fa) != bool(args.query_out):
+        ap.error("--query-fa needs --query-out" if args.query_fa else "--query-out needs --query-fa")
+    if args.query_presence_out and not args.query_fa:
+        ap.error("--query-presence-out needs --query-fa and --query-out")
+    if not (args.query_fa or args.greedytigs_fa_out or args.eulertigs_fa_out or args.greedytigs_gfa_out or args.eulertigs_gfa_out
             or args.greedytigs_duplication_bitvector_out or args.matchtigs_fa_out or args.matchtigs_gfa_out or args.verify_fa or args.unitigs_fa_out):
         ap.error("nothing to do: give --greedytigs-fa-out / --greedytigs-gfa-out and/or --eulertigs-fa-out / --eulertigs-gfa-out")
 
@@ -124,7 +138,42 @@ def main(argv=None) -> int:
               f"({r['tigs']} tigs, {r['fasta_bytes']} fasta bytes)", file=sys.stderr)
         if args.verify:
             all_equal &= report(f"{name} ({out or 'spelled in memory'})", r["verify_tigs"], r["verify"])
+    if args.query_fa:
+        _query(api, args, store)
     return 0 if all_equal else 1
+
+
+def _query(api, args, store) -> None:
+    """`--query-fa`: the input's k-mer set (the unitig store) indexed once; one TSV row and one presence line per query record."""
+    import contextlib
+    import gzip
+
+    import numpy as np
+
+    def writer(path, mode):
+        return gzip.open(path, "w" + mode, compresslevel=args.compression_level) if path.endswith(".gz") else open(path, "w" + mode)
+
+    with contextlib.ExitStack() as stack:
+        index = stack.enter_context(api.KmerIndex(store, args.k, args.device))
+        tsv = stack.enter_context(writer(args.query_out, "t"))
+        presence = stack.enter_context(writer(args.query_presence_out, "b")) if args.query_presence_out else None
+        tsv.write("record\tlength\tkmers\tvalid\tfound\n")
+        for path in args.query_fa:
+            t0 = time.perf_counter()
+            seqs, names = api.read_sequences_named(path)
+            r = index.query(seqs, bits=presence is not None)
+            lengths = np.diff(r.offsets)
+            tsv.writelines(f"{name}\t{l}\t{n}\t{v}\t{f}\n"
+                           for name, l, n, v, f in zip(names, lengths.tolist(), r.kmers.tolist(), r.valid.tolist(), r.found.tolist()))
+            if presence is not None:  # in slices of about 2^24 bases, which bounds the unpacked bits held at once
+                at = 0
+                while at < len(names):
+                    end = max(at + 1, int(np.searchsorted(r.offsets, int(r.offsets[at]) + (1 << 24), side="right")) - 1)
+                    presence.write(r.presence_lines(at, end))
+                    at = end
+            valid, found = int(r.valid.sum()), int(r.found.sum())
+            print(f"Querying {path}: {len(names)} records, {int(r.kmers.sum())} k-mers, {valid} valid, {found} found "
+                  f"({100.0 * found / valid if valid else 0.0:.2f} %) in {time.perf_counter() - t0:.1f} s", file=sys.stderr)
 
 
 if __name__ == "__main__":

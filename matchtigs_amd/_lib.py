@@ -96,6 +96,15 @@ class MtgCompaction(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class MtgKmerIndexInfo(C.Structure):
+    """mtg_kmer_index_info (include/mtg_engine.h)."""
+
+    _fields_ = [(n, C.c_uint64) for n in ("k", "records", "characters", "occurrences", "distinct", "slots", "device_bytes")]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class MtgDijkstraPerformanceData(C.Structure):
     _fields_ = [
         ("dijkstras", C.c_uint64),
@@ -236,6 +245,13 @@ def load():
         "mtg_compact_unitigs": (None, [vp, vp, u64, u64, C.c_int, P(vp), P(MtgCompaction)]),
         "mtg_compact_unitigs_store": (None, [vp, u64, C.c_int, P(vp), P(MtgCompaction)]),
         "mtg_last_compact_times": (None, [P(C.c_double)]),
+        "mtg_kmer_index_build": (vp, [vp, vp, u64, u64, C.c_int]),
+        "mtg_kmer_index_build_store": (vp, [vp, u64, C.c_int]),
+        "mtg_kmer_index_get_info": (None, [vp, P(MtgKmerIndexInfo)]),
+        "mtg_kmer_index_query": (None, [vp, vp, vp, u64, vp, vp, vp, vp, vp]),
+        "mtg_kmer_index_free": (None, [vp]),
+        "mtg_last_kmer_query_times": (None, [P(C.c_double)]),
+        "mtg_read_sequences_named": (None, [C.c_char_p, P(vp), P(vp)]),
         "mtg_unitigs_count": (u64, [vp]),
         "mtg_unitigs_data": (vp, [vp]),
         "mtg_unitigs_offsets": (vp, [vp]),

@@ -1007,6 +1007,126 @@ def last_kmer_compare_times() -> dict:
     return dict(zip(("upload_ms", "pack_ms", "insert_a_ms", "insert_b_ms", "count_ms", "total_ms"), list(out)))
 
 
+def read_sequences_named(path: str):
+    """Any FASTA file (optionally .gz, multi-line records) -> (UnitigStore, names): read_sequences without an alphabet rule and
+    without case folding -- `N`, IUPAC codes and lower case stay as they are (the queries of a KmerIndex) -- plus the record names,
+    the header text behind `>` up to the first white space (mtg_read_sequences_named)."""
+    st, names = C.c_void_p(), C.c_void_p()
+    _lib.load().mtg_read_sequences_named(str(path).encode(), C.byref(st), C.byref(names))
+    return UnitigStore(st.value), UnitigStore(names.value).sequences()
+
+
+@dataclass(frozen=True)
+class KmerIndexInfo:
+    """mtg_kmer_index_info (include/mtg_engine.h)."""
+
+    k: int
+    records: int
+    characters: int
+    occurrences: int
+    distinct: int
+    slots: int
+    device_bytes: int
+
+
+@dataclass(frozen=True, eq=False)
+class KmerQueryResult:
+    """What KmerIndex.query found, per query record (numpy uint64 arrays): kmers = windows, valid = windows of ACGT only, found =
+    valid windows whose canonical k-mer is in the index. With bits=True also valid_bits / present_bits: one bit per global base
+    position of the query (bit p & 63 of word p >> 6), set where a valid / a found window starts."""
+
+    k: int
+    offsets: np.ndarray
+    kmers: np.ndarray
+    valid: np.ndarray
+    found: np.ndarray
+    valid_bits: Optional[np.ndarray] = None
+    present_bits: Optional[np.ndarray] = None
+
+    def presence(self, i: int) -> str:
+        """One character per window of record i: `1` in the index, `0` not, `-` invalid (a character outside ACGT in the window)."""
+        return self.presence_lines(i, i + 1)[:-1].decode()
+
+    def presence_lines(self, first: int = 0, last: Optional[int] = None) -> bytes:
+        """presence() of the records first .. last - 1, each followed by a newline, in one vectorised pass: only the bytes of the bit
+        arrays that cover those records are unpacked, so the cost is linear in their bases."""
+        if self.valid_bits is None or self.present_bits is None:
+            raise ValueError("presence() needs a query made with bits=True")
+        last = len(self.kmers) if last is None else last
+        if not 0 <= first <= last <= len(self.kmers):
+            raise IndexError(f"records {first} .. {last} of {len(self.kmers)}")
+        off = self.offsets[first:last + 1].astype(np.int64)
+        n = self.kmers[first:last].astype(np.int64)
+        byte_lo = int(off[0]) >> 3
+        byte_hi = (int(off[-1]) + 7) >> 3
+
+        def bits(a):
+            return np.unpackbits(a.view(np.uint8)[byte_lo:byte_hi], bitorder="little")
+
+        chars = np.where(bits(self.valid_bits) == 0, ord("-"), np.where(bits(self.present_bits) == 1, ord("1"), ord("0"))).astype(np.uint8)
+        line_at = np.cumsum(n + 1) - (n + 1)  # where each record's line starts in the output
+        out = np.full(int(n.sum()) + len(n), ord("\n"), np.uint8)
+        rec = np.repeat(np.arange(len(n)), n)
+        within = np.arange(len(rec)) - np.repeat(line_at - np.arange(len(n)), n)  # the window's number inside its record
+        out[line_at[rec] + within] = chars[off[rec] - (byte_lo << 3) + within]
+        return out.tobytes()
+
+
+class KmerIndex:
+    """The canonical k-mers of a sequence set, kept on GPU `device_id` and asked which k-mers of other sequences they hold
+    (mtg_kmer_index_*). seqs_or_store: UnitigStore, list of str, or (uint8 array, offsets); ACGT of either case only.
+    The index holds device memory until close() (or its collection); release_device_memory leaves it intact."""
+
+    def __init__(self, seqs_or_store, k: int, device_id: int = 0):
+        self._L = _lib.load()
+        self._h = None
+        if isinstance(seqs_or_store, UnitigStore):
+            self._h = self._L.mtg_kmer_index_build_store(seqs_or_store.handle, k, device_id)
+        else:
+            d, o, n, keep = _sequence_arrays(seqs_or_store)
+            self._h = self._L.mtg_kmer_index_build(d, o, n, k, device_id)
+            del keep
+        out = _lib.MtgKmerIndexInfo()
+        self._L.mtg_kmer_index_get_info(self._h, C.byref(out))
+        self.info = KmerIndexInfo(**out.as_dict())
+
+    def close(self) -> None:
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            self._L.mtg_kmer_index_free(h)
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def query(self, seqs_or_store, bits: bool = False) -> KmerQueryResult:
+        """Per record of seqs_or_store (UnitigStore, list of str, or (uint8 array, offsets); ANY bytes): windows, valid windows,
+        windows found in the index. bits: also the two bit arrays that presence() reads."""
+        if not self._h:
+            raise ValueError("the index is closed")
+        d, o, n, keep = _sequence_arrays(seqs_or_store)
+        off = np.ctypeslib.as_array(C.cast(o, C.POINTER(C.c_uint64)), shape=(n + 1,)).copy()
+        kmers, valid, found = (np.zeros(n, np.uint64) for _ in range(3))
+        words = (int(off[n]) + 63) // 64
+        vb, pb = (np.zeros(words, np.uint64), np.zeros(words, np.uint64)) if bits else (None, None)
+        self._L.mtg_kmer_index_query(self._h, d, o, n, _ptr(kmers), _ptr(valid), _ptr(found), _ptr(pb) if bits else None,
+                                     _ptr(vb) if bits else None)
+        del keep
+        return KmerQueryResult(self.info.k, off, kmers, valid, found, vb, pb)
+
+
+def last_kmer_query_times() -> dict:
+    """Phases of the last KmerIndex build and the last query on this thread, in ms (HIP events around the kernels; uploads by the
+    host clock)."""
+    out = (C.c_double * 6)()
+    _lib.load().mtg_last_kmer_query_times(out)
+    return dict(zip(("build_upload_ms", "build_pack_ms", "build_insert_ms", "query_upload_ms", "query_pack_ms", "query_probe_ms"), list(out)))
+
+
 def kmer_at(seqs, record: int, pos: int, k: int) -> str:
     """The window a witness of a KmerComparison names, as text (upper case)."""
     if isinstance(seqs, UnitigStore):

@@ -75,7 +75,7 @@ template <bool WIDE>
 __global__ __launch_bounds__(hu::EB) void insert_kernel(KmerArgs a, uint64_t n_bases, uint64_t n_rec, unsigned int *err) {
     const uint64_t p0 = hu::gid() * RUN;
     if (p0 >= n_bases) return;
-    kw::for_each_window<WIDE>(a, p0, p0 + RUN < n_bases ? p0 + RUN : n_bases, 0, n_rec, [&](uint64_t q, const kw::Window &w) {
+    kw::for_each_window<WIDE>(a, p0, p0 + RUN < n_bases ? p0 + RUN : n_bases, 0, n_rec, [&](uint64_t q, uint64_t, const kw::Window &w) {
         const unsigned long long mine = kw::tagged_pos(w.hash, q);
         const kw::Found f = kw::find_slot<true>(a.table, a.slots, w.hash, mine, [&](unsigned long long cur) {
             return (cur >> 40) == (mine >> 40) && kw::same_class(a.packed, q, cur & POS_LIMIT, a.k);

@@ -132,6 +132,18 @@ struct KmerCompareTimes {
 };
 void device_compare_kmer_sets(const char *seq_a, const uint64_t *off_a, uint64_t n_a, const char *seq_b, const uint64_t *off_b, uint64_t n_b,
                               uint64_t k, int device_id, mtg_kmer_comparison *out, KmerCompareTimes *times);
+// kmer_query_device.hip: a k-mer set kept on the device and asked, record by record, which k-mers of other sequences it holds (the
+// file's header states the contract). times: host wall clock of the uploads, HIP-event time of the kernels; a build sets the first
+// three, a query the last three.
+struct KmerQueryTimes {
+    double build_upload_ms = 0, build_pack_ms = 0, build_insert_ms = 0, query_upload_ms = 0, query_pack_ms = 0, query_probe_ms = 0;
+};
+struct KmerIndex;
+KmerIndex *device_kmer_index_build(const char *seq, const uint64_t *off, uint64_t n, uint64_t k, int device_id, KmerQueryTimes *times);
+void device_kmer_index_info(const KmerIndex *ix, mtg_kmer_index_info *out);
+void device_kmer_index_query(const KmerIndex *ix, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid,
+                             uint64_t *found, uint64_t *present_bits, uint64_t *valid_bits, KmerQueryTimes *times);
+void device_kmer_index_free(KmerIndex *ix);
 // compact_device.hip: the maximal unitigs of the k-mer set of arbitrary sequences (the file's header and DESIGN.md 16 state the
 // contract), as an ordinary sequence store. times: host wall clock of upload, download and the whole call, HIP-event time of the
 // kernel phases, the pointer-jumping rounds, the bytes the kernels must move at the least, the arena's peak of live bytes.
@@ -142,6 +154,9 @@ struct CompactTimes {
 };
 UnitigStore *device_compact_unitigs(const char *data, const uint64_t *off, uint64_t n_rec, uint64_t k, int device_id, mtg_compaction *stats_out,
                                     CompactTimes *times);
+// fasta_in.cpp: read_fasta_records without an alphabet rule and without case folding (the queries of the k-mer index), plus the
+// record names (the header text behind `>` up to the first white space) as a second store
+UnitigStore *read_fasta_records_named(const char *path, UnitigStore **names_out);
 // fasta_in.cpp: read_fasta_records where a run of characters outside ACGT ends a piece instead of aborting; empty pieces are dropped
 UnitigStore *read_fasta_records_split(const char *path, uint64_t *pieces_cut);
 void device_candidates_to_host(Device *d, void *stream, std::vector<uint64_t> &cand_start,

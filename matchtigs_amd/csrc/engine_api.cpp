@@ -654,6 +654,42 @@ void mtg_last_kmer_compare_times(double out[6]) {
     const KmerCompareTimes &t = g_last_kmer_compare;
     out[0] = t.upload_ms; out[1] = t.pack_ms; out[2] = t.insert_a_ms; out[3] = t.insert_b_ms; out[4] = t.count_ms; out[5] = t.total_ms;
 }
+// ---- k-mer index on the GPU (kmer_query_device.hip) ----
+struct mtg_kmer_index { KmerIndex *ix; };
+static thread_local KmerQueryTimes g_last_kmer_query;
+mtg_kmer_index *mtg_kmer_index_build(const char *seq, const uint64_t *off, uint64_t n, uint64_t k, int device_id) {
+    return new mtg_kmer_index{device_kmer_index_build(seq, off, n, k, device_id, &g_last_kmer_query)};
+}
+mtg_kmer_index *mtg_kmer_index_build_store(const mtg_unitigs *store, uint64_t k, int device_id) {
+    if (!store) MTG_DIE("mtg_kmer_index_build_store: null argument");
+    const UnitigStore &s = *store->s;
+    return new mtg_kmer_index{device_kmer_index_build(s.data.data(), s.off.data(), s.off.size() - 1, k, device_id, &g_last_kmer_query)};
+}
+void mtg_kmer_index_get_info(const mtg_kmer_index *ix, mtg_kmer_index_info *out) {
+    if (!ix || !out) MTG_DIE("mtg_kmer_index_get_info: null argument");
+    device_kmer_index_info(ix->ix, out);
+}
+void mtg_kmer_index_query(const mtg_kmer_index *ix, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid,
+                          uint64_t *found, uint64_t *present_bits, uint64_t *valid_bits) {
+    if (!ix) MTG_DIE("mtg_kmer_index_query: null argument");
+    device_kmer_index_query(ix->ix, seq, off, n, kmers, valid, found, present_bits, valid_bits, &g_last_kmer_query);
+}
+void mtg_kmer_index_free(mtg_kmer_index *ix) {
+    if (!ix) return;
+    device_kmer_index_free(ix->ix);
+    delete ix;
+}
+void mtg_last_kmer_query_times(double out[6]) {
+    const KmerQueryTimes &t = g_last_kmer_query;
+    out[0] = t.build_upload_ms; out[1] = t.build_pack_ms; out[2] = t.build_insert_ms;
+    out[3] = t.query_upload_ms; out[4] = t.query_pack_ms; out[5] = t.query_probe_ms;
+}
+void mtg_read_sequences_named(const char *path, mtg_unitigs **seqs_out, mtg_unitigs **names_out) {
+    if (!path || !seqs_out || !names_out) MTG_DIE("mtg_read_sequences_named: null argument");
+    UnitigStore *names = nullptr;
+    *seqs_out = new mtg_unitigs{read_fasta_records_named(path, &names)};
+    *names_out = new mtg_unitigs{names};
+}
 // ---- unitig compaction on the GPU (compact_device.hip) ----
 static thread_local CompactTimes g_last_compact;
 void mtg_compact_unitigs(const char *data, const uint64_t *offsets, uint64_t n, uint64_t k, int device_id, mtg_unitigs **out, mtg_compaction *stats) {

@@ -6,9 +6,11 @@
 // more lines, either case. Empty lines are skipped, `.gz` inputs are inflated with zlib (gzopen also reads plain files). The same
 // line reader and alphabet rule as the BCALM2 route (bcalm2.cpp). read_fasta_records is that reader on its own (mtg_read_sequences:
 // a tig file someone else wrote, for the k-mer set comparison), read_fasta_records_split the same reader where a run of characters
-// outside ACGT (the `N` of real assemblies) ends a piece instead of aborting (mtg_read_sequences_split, `--seq-in`); read_fasta adds the length rule and the join.
+// outside ACGT (the `N` of real assemblies) ends a piece instead of aborting (mtg_read_sequences_split, `--seq-in`), read_fasta_records_named the reader
+// without an alphabet rule that also hands out the record names (mtg_read_sequences_named, `--query-fa`); read_fasta adds the length rule and the join.
 #include <zlib.h>
 
+#include <cctype>
 #include <chrono>
 #include <string>
 
@@ -42,6 +44,35 @@ UnitigStore *read_fasta_records(const char *path) {
     }
     gzclose(f);
     if (have_record) st->off.push_back(st->data.size());
+    return st;
+}
+
+UnitigStore *read_fasta_records_named(const char *path, UnitigStore **names_out) {
+    gzFile f = gzopen(path, "rb");
+    if (!f) MTG_DIE("cannot open %s", path);
+    gzbuffer(f, 1 << 20);
+    UnitigStore *st = new UnitigStore(), *names = new UnitigStore();
+    st->off.push_back(0);
+    names->off.push_back(0);
+    std::string line;
+    bool have_record = false;
+    while (read_line(f, line)) {
+        if (line.empty()) continue;
+        if (line[0] == '>') {
+            if (have_record) st->off.push_back(st->data.size());
+            have_record = true;
+            size_t end = 1;
+            while (end < line.size() && !std::isspace((unsigned char)line[end])) end++;
+            names->data.append(line, 1, end - 1);
+            names->off.push_back(names->data.size());
+        } else {
+            if (!have_record) MTG_DIE("%s: sequence data before the first header", path);
+            st->data += line;
+        }
+    }
+    gzclose(f);
+    if (have_record) st->off.push_back(st->data.size());
+    *names_out = names;
     return st;
 }
 

@@ -69,7 +69,7 @@ __global__ __launch_bounds__(hu::EB) void insert_kernel(CompareArgs a, uint64_t 
     const uint64_t p0 = set_lo + hu::gid() * RUN;
     if (p0 >= set_hi) return;
     for_each_window<WIDE>(a, p0, p0 + RUN < set_hi ? p0 + RUN : set_hi, rec_lo, rec_hi,
-                          [&](uint64_t, const Window &w) {  // afterwards the slot of w's class has `bit` set
+                          [&](uint64_t, uint64_t, const Window &w) {  // afterwards the slot of w's class has `bit` set
                               const kw::Found f = find_window<WIDE, true>(a, w, (w.ident << 2) | bit);
                               if (f.slot == a.slots) atomicOr(err, 1u);  // (2 slots per window: never full)
                               else if (f.word != EMPTY_SLOT && !(f.word & bit)) atomicOr(&a.table[f.slot], bit);
@@ -84,7 +84,7 @@ __global__ __launch_bounds__(hu::EB) void witness_kernel(CompareArgs a, uint64_t
     if (p0 >= set_hi) return;
     if (p0 >= __hip_atomic_load(witness, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;  // (a smaller one is known already)
     bool found = false;
-    for_each_window<WIDE>(a, p0, p0 + RUN < set_hi ? p0 + RUN : set_hi, rec_lo, rec_hi, [&](uint64_t q, const Window &w) {
+    for_each_window<WIDE>(a, p0, p0 + RUN < set_hi ? p0 + RUN : set_hi, rec_lo, rec_hi, [&](uint64_t q, uint64_t, const Window &w) {
         if (found) return;  // (positions ascend within a thread)
         const kw::Found f = find_window<WIDE, false>(a, w, 0);
         if (f.slot == a.slots) atomicOr(err, 2u);  // (unreachable: every window was inserted)

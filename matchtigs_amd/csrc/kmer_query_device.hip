@@ -1,0 +1,275 @@
+// kmer_query_device.hip -- which k-mers of these sequences are in that set? (`--query-fa`, mtg_kmer_index_*)
+//
+// The contract. The INDEX is a sequence set in the comparison's sense (kmer_compare_device.hip): concatenated ASCII plus n + 1
+// offsets, its k-mers the windows of length k inside one record, taken by their canonical form (the lexicographically smaller of x
+// and rc(x), A < C < G < T, either case); records shorter than k contribute nothing, a character outside ACGT aborts, k >= 1.
+// A QUERY is n records of arbitrary bytes. For record r of length L: kmers[r] = max(0, L - k + 1) windows; a window is VALID iff
+// all k of its characters are in ACGTacgt; valid[r] counts the valid windows and found[r] those whose canonical form is in the
+// index. Optionally two bit arrays over the global base positions of the query: bit p & 63 of word p >> 6 of valid_bits is set iff
+// a valid window starts at p, of present_bits iff that window is in the index; every other bit is 0. Exact integers only, and
+// nothing depends on the launch geometry or on the order atomics land in (the counts are integer sums; a bit-array word has one
+// writer).
+//
+// Build (once per index):
+//   pack      ASCII -> 2 bits per base (SeqStore), which also finds the first character outside ACGT
+//   insert    every window into one open-addressing table in HBM (kw::find_slot), 2 slots per window. A slot names its class as
+//             in the comparison: k <= 31 the canonical code itself, k >= 32 kw::tagged_pos of one occurrence, identity settled by
+//             kw::same_class in the packed store
+//   count     one sweep over the table: the occupied slots are the distinct k-mers
+// The index then keeps the table and -- for k >= 32, where a slot points into them -- the packed bases; the ASCII, the offsets
+// and, for k <= 31, the packed bases go back to the arena. Both live until mtg_kmer_index_free: they are live ranges of the device
+// arena, which gives only entirely free chunks back to the driver (mtg_release_device_memory included).
+//
+// Query (any number of calls per index, read-only):
+//   pack      ASCII -> 2 bits per base plus one "bad" bit per base for what is not ACGT (MaskedSeqStore; packed as A)
+//   probe     a thread owns kw::RUN = 64 window starts, p0 = 64 gid: exactly one word of each bit array, which it writes with one
+//             plain store. It rolls over its windows (kw::for_each_window). Validity comes from the bad mask: the thread keeps
+//             `clear_from`, one past the last bad base at or before the window's last base q + k - 1; where the walk jumps (the
+//             start of the run, a new record) it finds that by scanning the mask words over [q, q + k - 1), from then on one bit
+//             per step. A window is valid iff clear_from <= q. Invalid windows are not probed. Valid ones are looked up
+//             (find_slot<false>: no write to the table); for k >= 32 identity compares the QUERY's packed bases with the INDEX's
+//             (the two-store kw::same_class). valid / found accumulate in registers and leave by one atomicAdd each per
+//             (thread, record), skipped when zero.
+//
+// Limits: fewer than 2^40 - 1 bases in the index and in one query call (the position field of a slot, the walk), k < 2^32.
+// Device memory of an index: 16 B per window (+ 0.25 B per base for k >= 32); its build peaks like the comparison. A query call
+// takes 1 B (ASCII, freed once packed) + 0.25 B + 0.125 B per base, 8 + 16 B per record and 0.25 B per base for the bit arrays.
+// There is no host path.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "device.hpp"
+#include "hip_util.hpp"
+#include "kmer_window_device.hpp"
+#include "pack_device.hpp"
+
+namespace mtg {
+
+namespace {
+
+using kw::EMPTY_SLOT;
+using kw::POS_LIMIT;
+using kw::RUN;
+using kw::Window;
+
+struct IndexArgs : kw::WindowArgs {  // packed / off: the sequences that are walked (build: the index's, query: the query's)
+    const uint32_t *index_packed;    // k >= 32: the bases the slots point into
+    unsigned long long *table;       // [slots]
+    uint64_t slots;
+};
+
+// the slot of w's class; w is a window of a.packed (CLAIM: taken with w.ident if the class has none)
+template <bool WIDE, bool CLAIM>
+__device__ __forceinline__ kw::Found find_window(const IndexArgs &a, const Window &w) {
+    return kw::find_slot<CLAIM>(a.table, a.slots, w.hash, w.ident, [&](unsigned long long cur) {
+        if (!WIDE) return cur == w.ident;
+        if ((cur >> 40) != (w.ident >> 40)) return false;
+        if (CLAIM) return kw::same_class(a.packed, w.ident & POS_LIMIT, cur & POS_LIMIT, a.k);
+        return kw::same_class(a.packed, w.ident & POS_LIMIT, a.index_packed, cur & POS_LIMIT, a.k);
+    });
+}
+
+template <bool WIDE>
+__global__ __launch_bounds__(hu::EB) void index_insert_kernel(IndexArgs a, uint64_t n_bases, uint64_t n_rec, unsigned int *err) {
+    const uint64_t p0 = hu::gid() * RUN;
+    if (p0 >= n_bases) return;
+    kw::for_each_window<WIDE>(a, p0, p0 + RUN < n_bases ? p0 + RUN : n_bases, 0, n_rec, [&](uint64_t, uint64_t, const Window &w) {
+        if (find_window<WIDE, true>(a, w).slot == a.slots) atomicOr(err, 1u);  // (2 slots per window: never full)
+    });
+}
+
+// *count += occupied slots
+__global__ __launch_bounds__(hu::EB) void index_count_kernel(const unsigned long long *table, uint64_t slots, unsigned long long *count) {
+    unsigned long long n = 0;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t s = hu::gid(); s < slots / 2; s += stride) {  // (slots is a multiple of 8)
+        const ulonglong2 v = reinterpret_cast<const ulonglong2 *>(table)[s];
+        n += (v.x != EMPTY_SLOT) + (v.y != EMPTY_SLOT);
+    }
+    for (int d = warpSize / 2; d > 0; d /= 2) n += __shfl_down(n, d);
+    if ((threadIdx.x & (warpSize - 1)) == 0 && n) atomicAdd(count, n);
+}
+
+// one past the last base of [lo, hi) whose bit is set in `bad`; lo if there is none
+__device__ __forceinline__ uint64_t past_last_bad(const unsigned long long *bad, uint64_t lo, uint64_t hi) {
+    if (hi <= lo) return lo;
+    uint64_t w = (hi - 1) >> 6;
+    const uint64_t w_lo = lo >> 6;
+    unsigned long long m = bad[w] & (~0ull >> (63 - ((hi - 1) & 63)));
+    for (;;) {
+        if (w == w_lo) m &= ~0ull << (lo & 63);
+        if (m) return (w << 6) + 64 - (uint64_t)__clzll((long long)m);
+        if (w == w_lo) return lo;
+        m = bad[--w];
+    }
+}
+
+// counts: [2 n_rec], valid then found; valid_bits / present_bits: [(n_bases + 63) / 64] or null
+template <bool WIDE>
+__global__ __launch_bounds__(hu::EB) void query_kernel(IndexArgs a, const unsigned long long *bad, uint64_t n_bases, uint64_t n_rec,
+                                                       unsigned long long *counts, unsigned long long *valid_bits,
+                                                       unsigned long long *present_bits) {
+    const uint64_t gid = hu::gid(), p0 = gid * RUN;
+    if (p0 >= n_bases) return;
+    unsigned long long vbits = 0, pbits = 0;
+    uint64_t rec = ~0ull, next_q = ~0ull, clear_from = 0;
+    uint32_t n_valid = 0, n_found = 0;  // (of the current record; at most RUN)
+    auto flush = [&]() {
+        if (n_valid) atomicAdd(&counts[rec], (unsigned long long)n_valid);
+        if (n_found) atomicAdd(&counts[n_rec + rec], (unsigned long long)n_found);
+        n_valid = n_found = 0;
+    };
+    kw::for_each_window<WIDE>(a, p0, p0 + RUN < n_bases ? p0 + RUN : n_bases, 0, n_rec, [&](uint64_t q, uint64_t r, const Window &w) {
+        const uint64_t last = q + a.k - 1;  // the window's last base
+        if (r != rec) {
+            flush();
+            rec = r;
+        }
+        if (q != next_q) clear_from = past_last_bad(bad, q, last);  // the walk jumped: what it knew lies behind q
+        next_q = q + 1;
+        if ((bad[last >> 6] >> (last & 63)) & 1) clear_from = last + 1;
+        if (clear_from > q) return;  // a bad base inside the window
+        const unsigned long long bit = 1ull << (q - p0);
+        n_valid++;
+        vbits |= bit;
+        if (find_window<WIDE, false>(a, w).slot != a.slots) {
+            n_found++;
+            pbits |= bit;
+        }
+    });
+    flush();
+    if (valid_bits) valid_bits[gid] = vbits;
+    if (present_bits) present_bits[gid] = pbits;
+}
+
+// offsets of one set: start at 0, do not decrease; returns its windows
+uint64_t check_offsets(const char *fn, const char *data, const uint64_t *off, uint64_t n, uint64_t k) {
+    if (!off || (n && off[n] && !data)) MTG_DIE("%s: null argument", fn);
+    if (off[0] != 0) MTG_DIE("%s: offsets must start at 0", fn);
+    uint64_t occ = 0;
+    for (uint64_t u = 0; u < n; u++) {
+        if (off[u + 1] < off[u]) MTG_DIE("%s: offsets decrease at record %llu", fn, (unsigned long long)u);
+        const uint64_t len = off[u + 1] - off[u];
+        if (len >= k) occ += len - k + 1;
+    }
+    return occ;
+}
+
+}  // namespace
+
+struct KmerIndex {
+    mtg_kmer_index_info info{};
+    int device_id = 0;
+    uint32_t *packed = nullptr;           // k >= 32 only
+    unsigned long long *table = nullptr;  // [info.slots]
+};
+
+KmerIndex *device_kmer_index_build(const char *seq, const uint64_t *off, uint64_t n, uint64_t k, int device_id, KmerQueryTimes *times) {
+    if (k < 1) MTG_DIE("mtg_kmer_index_build: k must be >= 1");
+    if (k > 0xFFFFFFFFull) MTG_DIE("mtg_kmer_index_build: k too large");
+    KmerIndex *ix = new KmerIndex();
+    mtg_kmer_index_info &info = ix->info;
+    info.k = k;
+    info.records = n;
+    info.occurrences = check_offsets("mtg_kmer_index_build", seq, off, n, k);
+    info.characters = off[n];
+    if (info.characters >= POS_LIMIT)
+        MTG_DIE("mtg_kmer_index_build: %llu bases; the limit is 2^40 - 2", (unsigned long long)info.characters);
+    if (device_id < 0 || device_count() <= device_id) MTG_DIE("no HIP device %d for the k-mer index (there is no CPU path)", device_id);
+    HIP_CHECK(hipSetDevice(device_id));
+    ix->device_id = device_id;
+    hipStream_t st = nullptr;
+    const bool wide = k >= 32;
+    info.slots = std::max<uint64_t>(8, (2 * info.occurrences + 7) / 8 * 8);
+
+    SeqStore store("indexed sequences", seq, off, n, st, device_id);
+    PhaseEvents<2> ev;
+    ev.mark(0, st);
+    hu::device_malloc(&ix->table, info.slots * 8);
+    HIP_CHECK(hipMemsetAsync(ix->table, 0xFF, info.slots * 8, st));
+    if (info.occurrences) {
+        IndexArgs a{};
+        a.packed = a.index_packed = store.packed; a.off = store.off; a.table = ix->table; a.slots = info.slots;
+        kw::window_args_set_k(a, k);
+        const unsigned grid = hu::grid_for((store.n_bases + RUN - 1) / RUN);
+        if (wide) index_insert_kernel<true><<<grid, hu::EB, 0, st>>>(a, store.n_bases, n, store.small.err());
+        else index_insert_kernel<false><<<grid, hu::EB, 0, st>>>(a, store.n_bases, n, store.small.err());
+        HIP_CHECK(hipGetLastError());
+        index_count_kernel<<<(unsigned)std::min<uint64_t>(hu::grid_for(info.slots / 2), 8192), hu::EB, 0, st>>>(ix->table, info.slots, store.small.d + 2);
+        HIP_CHECK(hipGetLastError());
+    }
+    ev.mark(1, st);
+    store.small.read(st, "k-mer index");
+    info.distinct = store.small.h[2];
+    if (times) {
+        times->build_upload_ms = store.upload_ms;
+        times->build_pack_ms = store.pack_ms;
+        times->build_insert_ms = ev.ms(0, 1);  // (with the table's fill and the count)
+    }
+    info.device_bytes = info.slots * 8;
+    if (wide && info.occurrences) {
+        ix->packed = store.take_packed();
+        info.device_bytes += (store.n_words + 2) * 4;
+    }
+    return ix;
+}
+
+void device_kmer_index_info(const KmerIndex *ix, mtg_kmer_index_info *out) { *out = ix->info; }
+
+void device_kmer_index_free(KmerIndex *ix) {
+    if (!ix) return;
+    hu::device_free_on(ix->device_id, ix->packed);
+    hu::device_free_on(ix->device_id, ix->table);
+    delete ix;
+}
+
+void device_kmer_index_query(const KmerIndex *ix, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid,
+                             uint64_t *found, uint64_t *present_bits, uint64_t *valid_bits, KmerQueryTimes *times) {
+    const uint64_t k = ix->info.k;
+    (void)check_offsets("mtg_kmer_index_query", seq, off, n, k);
+    if (n && (!kmers || !valid || !found)) MTG_DIE("mtg_kmer_index_query: null argument");
+    const uint64_t n_bases = off[n], bit_words = (n_bases + 63) / 64;
+    if (n_bases >= POS_LIMIT) MTG_DIE("mtg_kmer_index_query: %llu bases; the limit is 2^40 - 2", (unsigned long long)n_bases);
+    for (uint64_t r = 0; r < n; r++) {
+        const uint64_t len = off[r + 1] - off[r];
+        kmers[r] = len >= k ? len - k + 1 : 0;
+        valid[r] = found[r] = 0;
+    }
+    if (times) times->query_upload_ms = times->query_pack_ms = times->query_probe_ms = 0;
+    if (n_bases == 0) return;  // nothing to look at
+    HIP_CHECK(hipSetDevice(ix->device_id));
+    hipStream_t st = nullptr;
+    MaskedSeqStore store(seq, off, n, st, ix->device_id);
+    unsigned long long *d_counts = nullptr, *d_bits = nullptr;  // d_bits: valid_bits, then present_bits (those asked for)
+    const int n_arrays = (valid_bits != nullptr) + (present_bits != nullptr);
+    hu::device_malloc(&d_counts, 2 * n * 8);
+    if (n_arrays) hu::device_malloc(&d_bits, n_arrays * bit_words * 8);
+    unsigned long long *d_valid_bits = valid_bits ? d_bits : nullptr;
+    unsigned long long *d_present_bits = present_bits ? d_bits + (valid_bits ? bit_words : 0) : nullptr;
+    PhaseEvents<2> ev;
+    ev.mark(0, st);
+    HIP_CHECK(hipMemsetAsync(d_counts, 0, 2 * n * 8, st));
+    IndexArgs a{};
+    a.packed = store.packed; a.off = store.off; a.index_packed = ix->packed; a.table = ix->table; a.slots = ix->info.slots;
+    kw::window_args_set_k(a, k);
+    const unsigned grid = hu::grid_for(bit_words);  // (one thread per word: every word of the bit arrays is written)
+    if (k >= 32) query_kernel<true><<<grid, hu::EB, 0, st>>>(a, store.bad, n_bases, n, d_counts, d_valid_bits, d_present_bits);
+    else query_kernel<false><<<grid, hu::EB, 0, st>>>(a, store.bad, n_bases, n, d_counts, d_valid_bits, d_present_bits);
+    HIP_CHECK(hipGetLastError());
+    ev.mark(1, st);
+    HIP_CHECK(hipMemcpyAsync(valid, d_counts, n * 8, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(found, d_counts + n, n * 8, hipMemcpyDeviceToHost, st));
+    if (valid_bits) HIP_CHECK(hipMemcpyAsync(valid_bits, d_valid_bits, bit_words * 8, hipMemcpyDeviceToHost, st));
+    if (present_bits) HIP_CHECK(hipMemcpyAsync(present_bits, d_present_bits, bit_words * 8, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    if (times) {
+        times->query_upload_ms = store.upload_ms;
+        times->query_pack_ms = store.pack_ms;
+        times->query_probe_ms = ev.ms(0, 1);
+    }
+    hu::device_free(d_counts);
+    hu::device_free(d_bits);
+}
+
+}  // namespace mtg

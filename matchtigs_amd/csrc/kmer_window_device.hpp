@@ -1,5 +1,6 @@
 // kmer_window_device.hpp -- k-mer classes {x, rc(x)} over a 2-bit packed sequence store (pack_device.hpp), shared by the plain-FASTA
-// join (fasta_in_device.hip), the k-mer set comparison (kmer_compare_device.hip) and the unitig compaction (compact_device.hip):
+// join (fasta_in_device.hip), the k-mer set comparison (kmer_compare_device.hip), the unitig compaction (compact_device.hip) and the
+// k-mer index (kmer_query_device.hip):
 // the rolling walk over the windows of a record (for_each_window), the canonical key of the bases at one position (class_key) and the
 // open-addressing table of classes (find_slot, with the exactness argument every caller relies on).
 //
@@ -81,21 +82,24 @@ __device__ __forceinline__ uint32_t revcomp16(uint32_t v) {
     const uint32_t r = __brev(v);
     return ~(((r >> 1) & 0x55555555u) | ((r & 0x55555555u) << 1));
 }
-// the windows at p and q are the same k-mer class: x == y or x == rc(y)
-__device__ inline bool same_class(const uint32_t *packed, uint64_t p, uint64_t q, uint64_t k) {
-    if (p == q) return true;
+// the window x at p of the store px and the window y at q of the store py are the same k-mer class: x == y or x == rc(y)
+__device__ inline bool same_class(const uint32_t *px, uint64_t p, const uint32_t *py, uint64_t q, uint64_t k) {
     bool eq = true;
     for (uint64_t i = 0; i < k && eq; i += 16) {
         const uint32_t n = (uint32_t)(k - i < 16 ? k - i : 16), m = n == 16 ? ~0u : (1u << (2 * n)) - 1;
-        eq = ((bases16(packed, p + i) ^ bases16(packed, q + i)) & m) == 0;
+        eq = ((bases16(px, p + i) ^ bases16(py, q + i)) & m) == 0;
     }
     if (eq) return true;
     for (uint64_t i = 0; i < k; i += 16) {  // x[i .. i + n) against the reverse complement of y[k - i - n .. k - i)
         const uint32_t n = (uint32_t)(k - i < 16 ? k - i : 16), m = n == 16 ? ~0u : (1u << (2 * n)) - 1;
-        const uint32_t y = revcomp16(bases16(packed, q + k - i - n) & m) >> (2 * (16 - n));
-        if ((bases16(packed, p + i) ^ y) & m) return false;
+        const uint32_t y = revcomp16(bases16(py, q + k - i - n) & m) >> (2 * (16 - n));
+        if ((bases16(px, p + i) ^ y) & m) return false;
     }
     return true;
+}
+// ... both in one store
+__device__ inline bool same_class(const uint32_t *packed, uint64_t p, uint64_t q, uint64_t k) {
+    return p == q || same_class(packed, p, packed, q, k);
 }
 
 // the two strand hashes of a string as one hash of its class (the same for x and rc(x)), and the identity word a table keeps for
@@ -108,7 +112,8 @@ struct Window {
     uint64_t hash, ident;
 };
 
-// Calls op(q, window) for every window start q in [p0, p1) of the records [rec_lo, rec_hi), whose bases are [off[rec_lo], off[rec_hi]).
+// Calls op(q, r, window) for every window start q in [p0, p1) of the records [rec_lo, rec_hi), whose bases are [off[rec_lo], off[rec_hi]);
+// r is the record of q. q ascends; it skips whatever starts no window (the last k - 1 bases of a record, records shorter than k).
 template <bool WIDE, typename Op>
 __device__ __forceinline__ void for_each_window(const WindowArgs &a, uint64_t p0, uint64_t p1, uint64_t rec_lo, uint64_t rec_hi, Op op) {
     uint64_t lo = rec_lo, hi = rec_hi;  // the last record that starts at or before p0 (off[rec_lo] <= p0 < off[rec_hi])
@@ -140,7 +145,7 @@ __device__ __forceinline__ void for_each_window(const WindowArgs &a, uint64_t p0
                 fwd = ((fwd << 2) | c) & a.kmask;
                 rc = (rc >> 2) | ((3 - c) << a.top);
                 const uint64_t canon = fwd < rc ? fwd : rc;
-                op(q, Window{mix64(canon), canon});
+                op(q, r, Window{mix64(canon), canon});
             }
         } else {
             BaseReader trail(a.packed, p);
@@ -153,7 +158,7 @@ __device__ __forceinline__ void for_each_window(const WindowArgs &a, uint64_t p0
             }
             for (uint64_t q = p;;) {
                 const uint64_t h = strands_hash(hf, hr);
-                op(q, Window{h, tagged_pos(h, q)});
+                op(q, r, Window{h, tagged_pos(h, q)});
                 if (++q >= last) break;
                 const uint64_t o = trail.next(), c = lead.next();
                 hf = (hf - (o + 1) * a.pow_k1) * POLY_BASE + (c + 1);

@@ -1,7 +1,8 @@
 // pack_device.hpp -- the 2-bit packed sequence store on the device and the small host-side pieces every sequence stage needs around
 // it: the tig spelling (spell_device.hip), the plain-FASTA join (fasta_in_device.hip), the k-mer set comparison
-// (kmer_compare_device.hip) and the unitig compaction (compact_device.hip). Only ACGT (either case) is representable, like the
-// reference's DnaAlphabet store.
+// (kmer_compare_device.hip), the unitig compaction (compact_device.hip) and the k-mer index (kmer_query_device.hip). Only ACGT
+// (either case) is representable, like the reference's DnaAlphabet store; the queries of the index, which may hold anything, get a
+// mask of the unrepresentable bases beside the store (MaskedSeqStore).
 // Layout: 16 bases per 32-bit word, base b at bits [2b, 2b+2), A C G T = 0 1 2 3 (so the complement of c is 3 - c).
 // INVARIANT of the store: two zeroed words lie behind the word of the last base, so a reader may load one word past the one it
 // needs (kw::bases16, kw::BaseReader in kmer_window_device.hpp) without a bounds check. SeqStore is the only place that allocates it.
@@ -39,6 +40,23 @@ static __global__ void pack_kernel(const char *ascii, uint64_t n_bases, uint32_t
         v |= c << (2 * i);
     }
     packed[w] = v;
+}
+
+// pack_kernel for sequences that may hold anything (the queries of kmer_query_device.hip): a character outside ACGT is packed as
+// code 0 and marked in `bad`, one bit per base (base b: bit b & 15 of bad[b >> 4], which on this little-endian machine is bit b & 63
+// of the 64-bit word b >> 6). One thread per packed word; the bits behind the last base are 0.
+static __global__ void pack_masked_kernel(const char *ascii, uint64_t n_bases, uint32_t *packed, unsigned short *bad) {
+    const uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t b0 = w * 16;
+    if (b0 >= n_bases) return;
+    uint32_t v = 0, m = 0;
+    for (int i = 0; i < 16 && b0 + i < n_bases; i++) {
+        const uint32_t c = base_code((unsigned char)ascii[b0 + i]);
+        if (c > 3) m |= 1u << i;
+        else v |= c << (2 * i);
+    }
+    packed[w] = v;
+    bad[w] = (unsigned short)m;
 }
 
 __device__ __forceinline__ uint32_t packed_base(const uint32_t *packed, uint64_t b) { return (packed[b >> 4] >> (2 * (b & 15))) & 3u; }
@@ -124,6 +142,51 @@ struct SeqStore {
         hu::device_free(off);
     }
     SeqStore(const SeqStore &) = delete;
+    // the packed bases leave the store: the caller frees them (hu::device_free)
+    uint32_t *take_packed() {
+        uint32_t *p = packed;
+        packed = nullptr;
+        return p;
+    }
+};
+
+// SeqStore for records of arbitrary bytes: nothing aborts. A character outside ACGT is packed as A and has its bit set in `bad`
+// (bit b & 63 of word b >> 6 for base b; every bit from n_bases on is 0, and one zeroed word lies behind the last).
+struct MaskedSeqStore {
+    uint32_t *packed = nullptr;
+    unsigned long long *off = nullptr;  // [n_rec + 1]
+    unsigned long long *bad = nullptr;  // [(n_bases + 63) / 64 + 1]
+    uint64_t n_bases, n_words;
+    double upload_ms = 0.0, pack_ms = 0.0;
+
+    MaskedSeqStore(const char *ascii, const uint64_t *h_off, uint64_t n_rec, hipStream_t st, int device_id)
+        : n_bases(h_off[n_rec]), n_words((h_off[n_rec] + 15) / 16) {
+        const auto t0 = std::chrono::steady_clock::now();
+        const uint64_t bad_bytes = ((n_bases + 63) / 64 + 1) * 8;
+        char *d_ascii = nullptr;
+        hu::device_malloc(&d_ascii, n_bases ? n_bases : 1);
+        hu::device_malloc(&packed, (n_words + 2) * 4);
+        hu::device_malloc(&bad, bad_bytes);
+        hu::device_malloc(&off, (n_rec + 1) * 8);
+        HIP_CHECK(hipMemsetAsync(packed + n_words, 0, 8, st));
+        HIP_CHECK(hipMemsetAsync(bad, 0, bad_bytes, st));
+        hu::upload_sliced(off, h_off, (n_rec + 1) * 8, st, device_id);
+        hu::upload_sliced(d_ascii, ascii, n_bases, st, device_id);
+        upload_ms = ms_since(t0);
+        PhaseEvents<2> ev;
+        ev.mark(0, st);
+        if (n_words) pack_masked_kernel<<<hu::grid_for(n_words), hu::EB, 0, st>>>(d_ascii, n_bases, packed, reinterpret_cast<unsigned short *>(bad));
+        HIP_CHECK(hipGetLastError());
+        ev.mark(1, st);
+        hu::device_free(d_ascii);  // (synchronises: the pack is done)
+        pack_ms = ev.ms(0, 1);
+    }
+    ~MaskedSeqStore() {
+        hu::device_free(packed);
+        hu::device_free(bad);
+        hu::device_free(off);
+    }
+    MaskedSeqStore(const MaskedSeqStore &) = delete;
 };
 
 }  // namespace mtg
