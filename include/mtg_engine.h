@@ -549,6 +549,34 @@ void mtg_kmer_index_free(mtg_kmer_index *ix);
 /* Of the last index build and the last query on this thread, in ms: {build: upload (host clock), pack, insert (with the table's fill
  * and the count); query: upload (host clock), pack, probe} -- HIP events around the kernels. */
 void mtg_last_kmer_query_times(double out[6]);
+/* WHERE the k-mers of a query are in the indexed sequences. A LOCATING index is built by the two functions below;
+ * beside the table it keeps the smallest position of every class, the packed bases (for every k) and the record offsets, all counted
+ * in info.device_bytes. mtg_kmer_index_query answers on it exactly as on a plain index. */
+mtg_kmer_index *mtg_kmer_index_build_locating(const char *seq, const uint64_t *off, uint64_t n, uint64_t k, int device_id);
+mtg_kmer_index *mtg_kmer_index_build_locating_store(const mtg_unitigs *store, uint64_t k, int device_id);
+int mtg_kmer_index_is_locating(const mtg_kmer_index *ix);
+/* The query of mtg_kmer_index_query (kmers / valid / found as there) plus the maximal collinear runs of its found windows. For a
+ * found window w: loc(w) = the smallest global start position, in the index's concatenated bases, of a window of w's class;
+ * strand(w) = + iff the upper-cased query window equals the index window there base by base, else - (a palindrome is +). Window p
+ * continues window p - 1 iff both start in the same query record, both are found, have the same strand, loc(p) = loc(p - 1) + 1
+ * (+) or loc(p - 1) - 1 (-), and both locations lie in the same index record. A run starts at every found window that does not
+ * continue its predecessor; runs come in ascending query position. Per run: q_record, q_start (offset of its first window in that
+ * record), kmers (windows), strand (0 = +, 1 = -), t_record (0-based index record) and t_start (offset in it of the leftmost index
+ * base the run covers): query bases [q_start, q_start + kmers + k - 1) equal index bases [t_start, t_start + kmers + k - 1) of
+ * t_record, case-insensitively, for - as the reverse complement. A k-mer that occurs more than once is reported at its smallest
+ * position only, so repeats break runs. Exact integers, a function of the inputs alone. Dies if the index is not locating. */
+typedef struct mtg_kmer_runs mtg_kmer_runs;
+void mtg_kmer_index_locate(const mtg_kmer_index *ix, const char *seq, const uint64_t *off, uint64_t n,
+                           uint64_t *kmers, uint64_t *valid, uint64_t *found, /* [n] each */
+                           mtg_kmer_runs **out);                              /* mtg_kmer_runs_free */
+uint64_t mtg_kmer_runs_count(const mtg_kmer_runs *runs);
+/* count entries each; valid until mtg_kmer_runs_free */
+void mtg_kmer_runs_arrays(const mtg_kmer_runs *runs, const uint64_t **q_record, const uint64_t **q_start, const uint64_t **kmers,
+                          const uint8_t **strand, const uint64_t **t_record, const uint64_t **t_start);
+void mtg_kmer_runs_free(mtg_kmer_runs *runs);
+/* Of the last mtg_kmer_index_locate on this thread, in ms: {upload (host clock), pack, probe (with the fill of the hit array), runs
+ * (flag, scan, emit)} -- HIP events around the kernels. */
+void mtg_last_kmer_locate_times(double out[4]);
 /* mtg_read_sequences without an alphabet rule: every byte of a sequence line is kept as it is (`N`, IUPAC codes, lower case), for
  * the queries of a k-mer index. *names_out = the record names as a second store with the same accessors: the header text behind `>`
  * up to the first white space. */

@@ -12,6 +12,8 @@ libmatchtigs.so; this file only parses flags and prints the reference's closing 
 `--query-fa` with `--query-out` (not in the reference) asks, after the tig outputs, which k-mers of other sequences -- reads,
 contigs, `N` and all -- are in the input's k-mer set: per record the windows, the valid ones (ACGT only) and those found, as a TSV,
 and with `--query-presence-out` one `1` / `0` / `-` character per window; the set is indexed once on the GPU.
+`--query-locate-out` adds where those k-mers are: one TSV row per maximal run of consecutive query k-mers that lie one after the
+other in an input record, on either strand, with both half-open base intervals.
 """
 from __future__ import annotations
 
@@ -56,6 +58,10 @@ def main(argv=None) -> int:
                     help="TSV (.gz => gzip) with one row per record of the --query-fa files: record, length, kmers, valid, found")
     ap.add_argument("--query-presence-out", metavar="PATH",
                     help="per query record a line with one character per k-mer: 1 in the set, 0 not, - holds a non-ACGT character (.gz => gzip)")
+    ap.add_argument("--query-locate-out", metavar="PATH",
+                    help="TSV (.gz => gzip) with one row per maximal collinear run of found k-mers: record, qstart, qend, strand, target "
+                         "(0-based input record), tstart, tend, kmers; a repeated k-mer is placed at its first occurrence; "
+                         "needs --query-fa and --query-out")
     args = ap.parse_args(argv)
 
     n_inputs = sum(x is not None for x in (args.bcalm_in, args.gfa_in, args.fa_in, args.seq_in))
@@ -72,6 +78,8 @@ def main(argv=None) -> int:
         ap.error("compression level must be in 0..9")
     if args.matchtigs_duplication_bitvector_out and not (args.matchtigs_fa_out or args.matchtigs_gfa_out):
         ap.error("--matchtigs-duplication-bitvector-out needs --matchtigs-fa-out or --matchtigs-gfa-out (bin.rs:955-957)")
+    if args.query_locate_out and not (args.query_fa and args.query_out):
+        ap.error("--query-locate-out needs --query-fa and --query-out")
     if bool(args.query_fa) != bool(args.query_out):
         ap.error("--query-fa needs --query-out" if args.query_fa else "--query-out needs --query-fa")
     if args.query_presence_out and not args.query_fa:
@@ -144,7 +152,8 @@ def main(argv=None) -> int:
 
 
 def _query(api, args, store) -> None:
-    """`--query-fa`: the input's k-mer set (the unitig store) indexed once; one TSV row and one presence line per query record."""
+    """`--query-fa`: the input's k-mer set (the unitig store) indexed once; one TSV row and one presence line per query record, and
+    with `--query-locate-out` one row per run of located k-mers."""
     import contextlib
     import gzip
 
@@ -154,14 +163,23 @@ def _query(api, args, store) -> None:
         return gzip.open(path, "w" + mode, compresslevel=args.compression_level) if path.endswith(".gz") else open(path, "w" + mode)
 
     with contextlib.ExitStack() as stack:
-        index = stack.enter_context(api.KmerIndex(store, args.k, args.device))
+        index = stack.enter_context(api.KmerIndex(store, args.k, args.device, locate=bool(args.query_locate_out)))
         tsv = stack.enter_context(writer(args.query_out, "t"))
         presence = stack.enter_context(writer(args.query_presence_out, "b")) if args.query_presence_out else None
+        located = stack.enter_context(writer(args.query_locate_out, "t")) if args.query_locate_out else None
         tsv.write("record\tlength\tkmers\tvalid\tfound\n")
+        if located is not None:
+            located.write("record\tqstart\tqend\tstrand\ttarget\ttstart\ttend\tkmers\n")
         for path in args.query_fa:
             t0 = time.perf_counter()
             seqs, names = api.read_sequences_named(path)
-            r = index.query(seqs, bits=presence is not None)
+            if located is not None:  # the counts of the TSV come from the same call
+                loc = index.locate(seqs)
+                runs, span = loc.runs, loc.runs["kmers"] + np.uint64(args.k - 1)
+                located.writelines(f"{names[q]}\t{qs}\t{qe}\t{'-' if s else '+'}\t{t}\t{ts}\t{te}\t{n}\n" for q, qs, qe, s, t, ts, te, n in zip(
+                    runs["q_record"].tolist(), runs["q_start"].tolist(), (runs["q_start"] + span).tolist(), runs["strand"].tolist(),
+                    runs["t_record"].tolist(), runs["t_start"].tolist(), (runs["t_start"] + span).tolist(), runs["kmers"].tolist()))
+            r = index.query(seqs, bits=True) if presence is not None else loc if located is not None else index.query(seqs)
             lengths = np.diff(r.offsets)
             tsv.writelines(f"{name}\t{l}\t{n}\t{v}\t{f}\n"
                            for name, l, n, v, f in zip(names, lengths.tolist(), r.kmers.tolist(), r.valid.tolist(), r.found.tolist()))

@@ -251,6 +251,14 @@ def load():
         "mtg_kmer_index_query": (None, [vp, vp, vp, u64, vp, vp, vp, vp, vp]),
         "mtg_kmer_index_free": (None, [vp]),
         "mtg_last_kmer_query_times": (None, [P(C.c_double)]),
+        "mtg_kmer_index_build_locating": (vp, [vp, vp, u64, u64, C.c_int]),
+        "mtg_kmer_index_build_locating_store": (vp, [vp, u64, C.c_int]),
+        "mtg_kmer_index_is_locating": (C.c_int, [vp]),
+        "mtg_kmer_index_locate": (None, [vp, vp, vp, u64, vp, vp, vp, P(vp)]),
+        "mtg_kmer_runs_count": (u64, [vp]),
+        "mtg_kmer_runs_arrays": (None, [vp, P(vp), P(vp), P(vp), P(vp), P(vp), P(vp)]),
+        "mtg_kmer_runs_free": (None, [vp]),
+        "mtg_last_kmer_locate_times": (None, [P(C.c_double)]),
         "mtg_read_sequences_named": (None, [C.c_char_p, P(vp), P(vp)]),
         "mtg_unitigs_count": (u64, [vp]),
         "mtg_unitigs_data": (vp, [vp]),

@@ -1072,19 +1072,43 @@ class KmerQueryResult:
         return out.tobytes()
 
 
+KMER_RUN_DTYPE = np.dtype([("q_record", np.uint64), ("q_start", np.uint64), ("kmers", np.uint64), ("strand", np.uint8),
+                           ("t_record", np.uint64), ("t_start", np.uint64)])
+
+
+@dataclass(frozen=True, eq=False)
+class KmerLocateResult:
+    """What KmerIndex.locate found: kmers / valid / found per query record as KmerIndex.query gives them, and `runs`, a structured
+    array (KMER_RUN_DTYPE) with one entry per maximal collinear run of found windows, in ascending query position: the `kmers`
+    windows from offset q_start of query record q_record on lie, one after the other, from offset t_start of index record t_record
+    on -- read forwards (strand 0) or as the reverse complement (strand 1). Query bases [q_start, q_start + kmers + k - 1) equal
+    index bases [t_start, t_start + kmers + k - 1)."""
+
+    k: int
+    offsets: np.ndarray
+    kmers: np.ndarray
+    valid: np.ndarray
+    found: np.ndarray
+    runs: np.ndarray
+
+
 class KmerIndex:
     """The canonical k-mers of a sequence set, kept on GPU `device_id` and asked which k-mers of other sequences they hold
     (mtg_kmer_index_*). seqs_or_store: UnitigStore, list of str, or (uint8 array, offsets); ACGT of either case only.
-    The index holds device memory until close() (or its collection); release_device_memory leaves it intact."""
+    The index holds device memory until close() (or its collection); release_device_memory leaves it intact. locate=True: the index
+    also keeps where its k-mers are (more device memory, see info.device_bytes) and answers locate()."""
 
-    def __init__(self, seqs_or_store, k: int, device_id: int = 0):
+    def __init__(self, seqs_or_store, k: int, device_id: int = 0, locate: bool = False):
         self._L = _lib.load()
         self._h = None
+        self.locating = bool(locate)
         if isinstance(seqs_or_store, UnitigStore):
-            self._h = self._L.mtg_kmer_index_build_store(seqs_or_store.handle, k, device_id)
+            build = self._L.mtg_kmer_index_build_locating_store if locate else self._L.mtg_kmer_index_build_store
+            self._h = build(seqs_or_store.handle, k, device_id)
         else:
             d, o, n, keep = _sequence_arrays(seqs_or_store)
-            self._h = self._L.mtg_kmer_index_build(d, o, n, k, device_id)
+            build = self._L.mtg_kmer_index_build_locating if locate else self._L.mtg_kmer_index_build
+            self._h = build(d, o, n, k, device_id)
             del keep
         out = _lib.MtgKmerIndexInfo()
         self._L.mtg_kmer_index_get_info(self._h, C.byref(out))
@@ -1118,6 +1142,33 @@ class KmerIndex:
         del keep
         return KmerQueryResult(self.info.k, off, kmers, valid, found, vb, pb)
 
+    def locate(self, seqs_or_store) -> KmerLocateResult:
+        """query()'s counts per record plus where the found windows lie in the indexed sequences, folded into maximal collinear
+        runs (KmerLocateResult). A k-mer that occurs several times in the index is reported at its smallest position only. Needs
+        an index built with locate=True."""
+        if not self._h:
+            raise ValueError("the index is closed")
+        if not self.locating:
+            raise ValueError("locate() needs an index built with locate=True")
+        d, o, n, keep = _sequence_arrays(seqs_or_store)
+        off = np.ctypeslib.as_array(C.cast(o, C.POINTER(C.c_uint64)), shape=(n + 1,)).copy()
+        kmers, valid, found = (np.zeros(n, np.uint64) for _ in range(3))
+        h = C.c_void_p()
+        self._L.mtg_kmer_index_locate(self._h, d, o, n, _ptr(kmers), _ptr(valid), _ptr(found), C.byref(h))
+        del keep
+        try:
+            count = int(self._L.mtg_kmer_runs_count(h))
+            runs = np.zeros(count, KMER_RUN_DTYPE)
+            if count:
+                ptrs = [C.c_void_p() for _ in range(6)]
+                self._L.mtg_kmer_runs_arrays(h, *(C.byref(p) for p in ptrs))
+                for name, p in zip(("q_record", "q_start", "kmers", "strand", "t_record", "t_start"), ptrs):
+                    ctype = C.c_uint8 if name == "strand" else C.c_uint64
+                    runs[name] = np.ctypeslib.as_array(C.cast(p, C.POINTER(ctype)), shape=(count,))
+        finally:
+            self._L.mtg_kmer_runs_free(h)
+        return KmerLocateResult(self.info.k, off, kmers, valid, found, runs)
+
 
 def last_kmer_query_times() -> dict:
     """Phases of the last KmerIndex build and the last query on this thread, in ms (HIP events around the kernels; uploads by the
@@ -1125,6 +1176,14 @@ def last_kmer_query_times() -> dict:
     out = (C.c_double * 6)()
     _lib.load().mtg_last_kmer_query_times(out)
     return dict(zip(("build_upload_ms", "build_pack_ms", "build_insert_ms", "query_upload_ms", "query_pack_ms", "query_probe_ms"), list(out)))
+
+
+def last_kmer_locate_times() -> dict:
+    """Phases of the last KmerIndex.locate on this thread, in ms (HIP events around the kernels; the upload by the host clock):
+    probe = the lookup of every window with its position and strand, runs = folding the hits into runs."""
+    out = (C.c_double * 4)()
+    _lib.load().mtg_last_kmer_locate_times(out)
+    return dict(zip(("upload_ms", "pack_ms", "probe_ms", "runs_ms"), list(out)))
 
 
 def kmer_at(seqs, record: int, pos: int, k: int) -> str:

@@ -139,11 +139,25 @@ struct KmerQueryTimes {
     double build_upload_ms = 0, build_pack_ms = 0, build_insert_ms = 0, query_upload_ms = 0, query_pack_ms = 0, query_probe_ms = 0;
 };
 struct KmerIndex;
-KmerIndex *device_kmer_index_build(const char *seq, const uint64_t *off, uint64_t n, uint64_t k, int device_id, KmerQueryTimes *times);
+// locating: the index also keeps the smallest position of every class, the packed bases and the record offsets (device_kmer_index_locate)
+KmerIndex *device_kmer_index_build(const char *seq, const uint64_t *off, uint64_t n, uint64_t k, int device_id, bool locating,
+                                   KmerQueryTimes *times);
+bool device_kmer_index_is_locating(const KmerIndex *ix);
 void device_kmer_index_info(const KmerIndex *ix, mtg_kmer_index_info *out);
 void device_kmer_index_query(const KmerIndex *ix, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid,
                              uint64_t *found, uint64_t *present_bits, uint64_t *valid_bits, KmerQueryTimes *times);
 void device_kmer_index_free(KmerIndex *ix);
+// The maximal collinear runs of a query's found windows against a locating index, in ascending query position:
+// one entry per run in each array. times: host wall clock of the upload, HIP-event time of the kernels (runs: flag, scan, emit).
+struct KmerRuns {
+    std::vector<uint64_t> q_record, q_start, kmers, t_record, t_start;
+    std::vector<uint8_t> strand;  // 0 = +, 1 = -
+};
+struct KmerLocateTimes {
+    double upload_ms = 0, pack_ms = 0, probe_ms = 0, runs_ms = 0;
+};
+void device_kmer_index_locate(const KmerIndex *ix, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid,
+                              uint64_t *found, KmerRuns *runs, KmerLocateTimes *times);
 // compact_device.hip: the maximal unitigs of the k-mer set of arbitrary sequences (the file's header and DESIGN.md 16 state the
 // contract), as an ordinary sequence store. times: host wall clock of upload, download and the whole call, HIP-event time of the
 // kernel phases, the pointer-jumping rounds, the bytes the kernels must move at the least, the arena's peak of live bytes.

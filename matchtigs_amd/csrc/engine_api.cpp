@@ -658,12 +658,12 @@ void mtg_last_kmer_compare_times(double out[6]) {
 struct mtg_kmer_index { KmerIndex *ix; };
 static thread_local KmerQueryTimes g_last_kmer_query;
 mtg_kmer_index *mtg_kmer_index_build(const char *seq, const uint64_t *off, uint64_t n, uint64_t k, int device_id) {
-    return new mtg_kmer_index{device_kmer_index_build(seq, off, n, k, device_id, &g_last_kmer_query)};
+    return new mtg_kmer_index{device_kmer_index_build(seq, off, n, k, device_id, false, &g_last_kmer_query)};
 }
 mtg_kmer_index *mtg_kmer_index_build_store(const mtg_unitigs *store, uint64_t k, int device_id) {
     if (!store) MTG_DIE("mtg_kmer_index_build_store: null argument");
     const UnitigStore &s = *store->s;
-    return new mtg_kmer_index{device_kmer_index_build(s.data.data(), s.off.data(), s.off.size() - 1, k, device_id, &g_last_kmer_query)};
+    return new mtg_kmer_index{device_kmer_index_build(s.data.data(), s.off.data(), s.off.size() - 1, k, device_id, false, &g_last_kmer_query)};
 }
 void mtg_kmer_index_get_info(const mtg_kmer_index *ix, mtg_kmer_index_info *out) {
     if (!ix || !out) MTG_DIE("mtg_kmer_index_get_info: null argument");
@@ -678,6 +678,43 @@ void mtg_kmer_index_free(mtg_kmer_index *ix) {
     if (!ix) return;
     device_kmer_index_free(ix->ix);
     delete ix;
+}
+// ---- ... that also says where its k-mers are ----
+struct mtg_kmer_runs { KmerRuns r; };
+static thread_local KmerLocateTimes g_last_kmer_locate;
+mtg_kmer_index *mtg_kmer_index_build_locating(const char *seq, const uint64_t *off, uint64_t n, uint64_t k, int device_id) {
+    return new mtg_kmer_index{device_kmer_index_build(seq, off, n, k, device_id, true, &g_last_kmer_query)};
+}
+mtg_kmer_index *mtg_kmer_index_build_locating_store(const mtg_unitigs *store, uint64_t k, int device_id) {
+    if (!store) MTG_DIE("mtg_kmer_index_build_locating_store: null argument");
+    const UnitigStore &s = *store->s;
+    return new mtg_kmer_index{device_kmer_index_build(s.data.data(), s.off.data(), s.off.size() - 1, k, device_id, true, &g_last_kmer_query)};
+}
+int mtg_kmer_index_is_locating(const mtg_kmer_index *ix) {
+    if (!ix) MTG_DIE("mtg_kmer_index_is_locating: null argument");
+    return device_kmer_index_is_locating(ix->ix) ? 1 : 0;
+}
+void mtg_kmer_index_locate(const mtg_kmer_index *ix, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid,
+                           uint64_t *found, mtg_kmer_runs **out) {
+    if (!ix || !out) MTG_DIE("mtg_kmer_index_locate: null argument");
+    mtg_kmer_runs *runs = new mtg_kmer_runs();
+    device_kmer_index_locate(ix->ix, seq, off, n, kmers, valid, found, &runs->r, &g_last_kmer_locate);
+    *out = runs;
+}
+uint64_t mtg_kmer_runs_count(const mtg_kmer_runs *runs) {
+    if (!runs) MTG_DIE("mtg_kmer_runs_count: null argument");
+    return runs->r.kmers.size();
+}
+void mtg_kmer_runs_arrays(const mtg_kmer_runs *runs, const uint64_t **q_record, const uint64_t **q_start, const uint64_t **kmers,
+                          const uint8_t **strand, const uint64_t **t_record, const uint64_t **t_start) {
+    if (!runs || !q_record || !q_start || !kmers || !strand || !t_record || !t_start) MTG_DIE("mtg_kmer_runs_arrays: null argument");
+    *q_record = runs->r.q_record.data(); *q_start = runs->r.q_start.data(); *kmers = runs->r.kmers.data();
+    *strand = runs->r.strand.data(); *t_record = runs->r.t_record.data(); *t_start = runs->r.t_start.data();
+}
+void mtg_kmer_runs_free(mtg_kmer_runs *runs) { delete runs; }
+void mtg_last_kmer_locate_times(double out[4]) {
+    const KmerLocateTimes &t = g_last_kmer_locate;
+    out[0] = t.upload_ms; out[1] = t.pack_ms; out[2] = t.probe_ms; out[3] = t.runs_ms;
 }
 void mtg_last_kmer_query_times(double out[6]) {
     const KmerQueryTimes &t = g_last_kmer_query;

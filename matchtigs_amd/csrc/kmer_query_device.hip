@@ -35,6 +35,17 @@
 // Device memory of an index: 16 B per window (+ 0.25 B per base for k >= 32); its build peaks like the comparison. A query call
 // takes 1 B (ASCII, freed once packed) + 0.25 B + 0.125 B per base, 8 + 16 B per record and 0.25 B per base for the bit arrays.
 // There is no host path.
+//
+// Locate (a LOCATING index only, mtg_kmer_index_build_locating). Such an index also keeps where[slots], the smallest
+// window start of every class (atomicMin in the insert kernel), the packed bases for every k and the record offsets: 16 B more per
+// window, 0.25 B per base, 8 B per record. A locate call answers like a query without bit arrays and adds the maximal collinear
+// runs of the found windows (include/mtg_engine.h states the contract):
+//   pack      as the query
+//   probe     locate_kernel: the query's walk (probe_run, shared with query_kernel); per found window hit[p] = (t << 1) | strand,
+//             t = where[slot], strand from a forward compare of the query's packed bases with the index's at t
+//   runs      run_flag_kernel marks the windows that do not continue their predecessor, hu::scan_u32 ranks them,
+//             run_mark_kernel notes the first and last position of every run, run_emit_kernel writes the fields of each
+// Only the runs and the counts are downloaded. A call takes 8 + 4 + 8 B per query base beside the query's store.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -70,12 +81,17 @@ __device__ __forceinline__ kw::Found find_window(const IndexArgs &a, const Windo
     });
 }
 
-template <bool WIDE>
-__global__ __launch_bounds__(hu::EB) void index_insert_kernel(IndexArgs a, uint64_t n_bases, uint64_t n_rec, unsigned int *err) {
+// LOCATE: where[slot of the class] = the smallest window start of the class (where: [slots], all ones before). A claimed slot keeps
+// its class, and the minimum over the occurrences of a class does not depend on the order they arrive in.
+template <bool WIDE, bool LOCATE>
+__global__ __launch_bounds__(hu::EB) void index_insert_kernel(IndexArgs a, uint64_t n_bases, uint64_t n_rec, unsigned int *err,
+                                                              unsigned long long *where) {
     const uint64_t p0 = hu::gid() * RUN;
     if (p0 >= n_bases) return;
-    kw::for_each_window<WIDE>(a, p0, p0 + RUN < n_bases ? p0 + RUN : n_bases, 0, n_rec, [&](uint64_t, uint64_t, const Window &w) {
-        if (find_window<WIDE, true>(a, w).slot == a.slots) atomicOr(err, 1u);  // (2 slots per window: never full)
+    kw::for_each_window<WIDE>(a, p0, p0 + RUN < n_bases ? p0 + RUN : n_bases, 0, n_rec, [&](uint64_t q, uint64_t, const Window &w) {
+        const uint64_t slot = find_window<WIDE, true>(a, w).slot;
+        if (slot == a.slots) atomicOr(err, 1u);  // (2 slots per window: never full)
+        else if (LOCATE) atomicMin(&where[slot], (unsigned long long)q);
     });
 }
 
@@ -105,14 +121,12 @@ __device__ __forceinline__ uint64_t past_last_bad(const unsigned long long *bad,
     }
 }
 
-// counts: [2 n_rec], valid then found; valid_bits / present_bits: [(n_bases + 63) / 64] or null
-template <bool WIDE>
-__global__ __launch_bounds__(hu::EB) void query_kernel(IndexArgs a, const unsigned long long *bad, uint64_t n_bases, uint64_t n_rec,
-                                                       unsigned long long *counts, unsigned long long *valid_bits,
-                                                       unsigned long long *present_bits) {
-    const uint64_t gid = hu::gid(), p0 = gid * RUN;
-    if (p0 >= n_bases) return;
-    unsigned long long vbits = 0, pbits = 0;
+// The walk of both query kernels over the RUN window starts from p0 on: validity from the bad mask, the read-only lookup of the valid
+// windows, valid / found per record into counts ([2 n_rec], valid then found). vbits / pbits: bit q - p0 set for a valid / a found
+// window at q. hit(q, slot) is called for every found window with the slot of its class.
+template <bool WIDE, typename Hit>
+__device__ __forceinline__ void probe_run(const IndexArgs &a, const unsigned long long *bad, uint64_t p0, uint64_t n_bases, uint64_t n_rec,
+                                          unsigned long long *counts, unsigned long long &vbits, unsigned long long &pbits, Hit hit) {
     uint64_t rec = ~0ull, next_q = ~0ull, clear_from = 0;
     uint32_t n_valid = 0, n_found = 0;  // (of the current record; at most RUN)
     auto flush = [&]() {
@@ -133,14 +147,126 @@ __global__ __launch_bounds__(hu::EB) void query_kernel(IndexArgs a, const unsign
         const unsigned long long bit = 1ull << (q - p0);
         n_valid++;
         vbits |= bit;
-        if (find_window<WIDE, false>(a, w).slot != a.slots) {
+        const uint64_t slot = find_window<WIDE, false>(a, w).slot;
+        if (slot != a.slots) {
             n_found++;
             pbits |= bit;
+            hit(q, slot);
         }
     });
     flush();
+}
+
+// counts: [2 n_rec], valid then found; valid_bits / present_bits: [(n_bases + 63) / 64] or null
+template <bool WIDE>
+__global__ __launch_bounds__(hu::EB) void query_kernel(IndexArgs a, const unsigned long long *bad, uint64_t n_bases, uint64_t n_rec,
+                                                       unsigned long long *counts, unsigned long long *valid_bits,
+                                                       unsigned long long *present_bits) {
+    const uint64_t gid = hu::gid(), p0 = gid * RUN;
+    if (p0 >= n_bases) return;
+    unsigned long long vbits = 0, pbits = 0;
+    probe_run<WIDE>(a, bad, p0, n_bases, n_rec, counts, vbits, pbits, [](uint64_t, uint64_t) {});
     if (valid_bits) valid_bits[gid] = vbits;
     if (present_bits) present_bits[gid] = pbits;
+}
+
+// ---- locate ----
+constexpr unsigned long long NO_HIT = ~0ull;
+
+// the k bases at p of the store px equal those at q of the store py, 16 bases per compare (the first half of kw::same_class)
+__device__ inline bool same_forward(const uint32_t *px, uint64_t p, const uint32_t *py, uint64_t q, uint64_t k) {
+    for (uint64_t i = 0; i < k; i += 16) {
+        const uint32_t n = (uint32_t)(k - i < 16 ? k - i : 16), m = n == 16 ? ~0u : (1u << (2 * n)) - 1;
+        if ((kw::bases16(px, p + i) ^ kw::bases16(py, q + i)) & m) return false;
+    }
+    return true;
+}
+
+// query_kernel's walk; per found window at q: hit[q] = (t << 1) | strand, t = the smallest window start of its class in the index
+// (where[slot]), strand 0 iff the query's bases equal the index's at t one by one -- otherwise, the classes being equal, they are the
+// reverse complement. hit: [n_bases], NO_HIT before.
+template <bool WIDE>
+__global__ __launch_bounds__(hu::EB) void locate_kernel(IndexArgs a, const unsigned long long *bad, uint64_t n_bases, uint64_t n_rec,
+                                                        unsigned long long *counts, const unsigned long long *where, unsigned long long *hit) {
+    const uint64_t p0 = hu::gid() * RUN;
+    if (p0 >= n_bases) return;
+    unsigned long long vbits = 0, pbits = 0;
+    probe_run<WIDE>(a, bad, p0, n_bases, n_rec, counts, vbits, pbits, [&](uint64_t q, uint64_t slot) {
+        const uint64_t t = where[slot];
+        hit[q] = (t << 1) | (same_forward(a.packed, q, a.index_packed, t, a.k) ? 0ull : 1ull);
+    });
+}
+
+// what the run kernels read: the hits of the query's positions, the record offsets of the query and of the index
+struct RunArgs {
+    const unsigned long long *hit;    // [n_bases]
+    const unsigned long long *q_off;  // [q_rec + 1]
+    const unsigned long long *t_off;  // [t_rec + 1]
+    uint64_t n_bases, q_rec, t_rec, k;
+};
+// the last record that starts at or before x (n_rec >= 1)
+__device__ __forceinline__ uint64_t record_of(const unsigned long long *off, uint64_t n_rec, uint64_t x) {
+    uint64_t lo = 0, hi = n_rec;
+    while (hi - lo > 1) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (off[mid] <= x) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+// The found window at p (h = hit[p]) continues the window at p - 1: found too, same strand, the next location in the strand's
+// direction, and both pairs inside one record. For k >= 2 two neighbouring window starts always share their record (the last k - 1
+// bases of a record start no window), so only k = 1 has to look the records up.
+__device__ __forceinline__ bool continues(const RunArgs &a, uint64_t p, unsigned long long h) {
+    if (p == 0) return false;
+    const unsigned long long g = a.hit[p - 1];
+    if (g == NO_HIT || ((g ^ h) & 1)) return false;
+    const uint64_t t = h >> 1, tp = g >> 1;
+    if ((h & 1) ? t + 1 != tp : tp + 1 != t) return false;
+    if (a.k > 1) return true;
+    const uint64_t tl = t < tp ? t : tp;
+    return p < a.q_off[record_of(a.q_off, a.q_rec, p - 1) + 1] && tl + 1 < a.t_off[record_of(a.t_off, a.t_rec, tl) + 1];
+}
+// starts[p] = 1 iff a run starts at p
+__global__ __launch_bounds__(hu::EB) void run_flag_kernel(RunArgs a, uint32_t *starts) {
+    const uint64_t p = hu::gid();
+    if (p >= a.n_bases) return;
+    const unsigned long long h = a.hit[p];
+    starts[p] = h != NO_HIT && !continues(a, p, h);
+}
+// rank[p] = the runs that start before p. Run i starts at first[i] and ends at last[i] (starts and ends alternate, so the end at p
+// belongs to the run rank[p] + starts[p] - 1).
+__global__ __launch_bounds__(hu::EB) void run_mark_kernel(RunArgs a, const uint32_t *starts, const unsigned long long *rank, uint64_t n_runs,
+                                                          unsigned long long *first, unsigned long long *last) {
+    const uint64_t p = hu::gid();
+    if (p >= a.n_bases) return;
+    const unsigned long long h = a.hit[p];
+    if (h == NO_HIT) return;
+    const uint32_t s = starts[p];
+    const uint64_t i = rank[p];
+    if (s && i < n_runs) first[i] = p;
+    bool end = p + 1 == a.n_bases;
+    if (!end) {
+        const unsigned long long hn = a.hit[p + 1];
+        end = hn == NO_HIT || !continues(a, p + 1, hn);
+    }
+    if (end && i + s >= 1 && i + s - 1 < n_runs) last[i + s - 1] = p;
+}
+// the fields of run i; out: five arrays of n_runs words each -- q_record, q_start, kmers, t_record, t_start --, strand: [n_runs]
+__global__ __launch_bounds__(hu::EB) void run_emit_kernel(RunArgs a, uint64_t n_runs, const unsigned long long *first,
+                                                          const unsigned long long *last, unsigned long long *out, unsigned char *strand) {
+    const uint64_t i = hu::gid();
+    if (i >= n_runs) return;
+    const uint64_t qs = first[i], qe = last[i];
+    const unsigned long long hs = a.hit[qs], he = a.hit[qe];
+    const uint64_t t = (hs & 1) ? he >> 1 : hs >> 1;  // the leftmost index base: on the reverse strand the last window's
+    const uint64_t qr = record_of(a.q_off, a.q_rec, qs), tr = record_of(a.t_off, a.t_rec, t);
+    out[i] = qr;
+    out[n_runs + i] = qs - a.q_off[qr];
+    out[2 * n_runs + i] = qe - qs + 1;
+    out[3 * n_runs + i] = tr;
+    out[4 * n_runs + i] = t - a.t_off[tr];
+    strand[i] = (unsigned char)(hs & 1);
 }
 
 // offsets of one set: start at 0, do not decrease; returns its windows
@@ -161,11 +287,15 @@ uint64_t check_offsets(const char *fn, const char *data, const uint64_t *off, ui
 struct KmerIndex {
     mtg_kmer_index_info info{};
     int device_id = 0;
-    uint32_t *packed = nullptr;           // k >= 32 only
+    uint32_t *packed = nullptr;           // k >= 32, or locating
     unsigned long long *table = nullptr;  // [info.slots]
+    bool locating = false;
+    unsigned long long *where = nullptr;  // locating: [info.slots] the smallest window start of the slot's class
+    unsigned long long *off = nullptr;    // locating: [info.records + 1]
 };
 
-KmerIndex *device_kmer_index_build(const char *seq, const uint64_t *off, uint64_t n, uint64_t k, int device_id, KmerQueryTimes *times) {
+KmerIndex *device_kmer_index_build(const char *seq, const uint64_t *off, uint64_t n, uint64_t k, int device_id, bool locating,
+                                   KmerQueryTimes *times) {
     if (k < 1) MTG_DIE("mtg_kmer_index_build: k must be >= 1");
     if (k > 0xFFFFFFFFull) MTG_DIE("mtg_kmer_index_build: k too large");
     KmerIndex *ix = new KmerIndex();
@@ -188,13 +318,23 @@ KmerIndex *device_kmer_index_build(const char *seq, const uint64_t *off, uint64_
     ev.mark(0, st);
     hu::device_malloc(&ix->table, info.slots * 8);
     HIP_CHECK(hipMemsetAsync(ix->table, 0xFF, info.slots * 8, st));
+    ix->locating = locating;
+    if (locating) {
+        hu::device_malloc(&ix->where, info.slots * 8);
+        HIP_CHECK(hipMemsetAsync(ix->where, 0xFF, info.slots * 8, st));
+    }
     if (info.occurrences) {
         IndexArgs a{};
         a.packed = a.index_packed = store.packed; a.off = store.off; a.table = ix->table; a.slots = info.slots;
         kw::window_args_set_k(a, k);
         const unsigned grid = hu::grid_for((store.n_bases + RUN - 1) / RUN);
-        if (wide) index_insert_kernel<true><<<grid, hu::EB, 0, st>>>(a, store.n_bases, n, store.small.err());
-        else index_insert_kernel<false><<<grid, hu::EB, 0, st>>>(a, store.n_bases, n, store.small.err());
+        if (locating) {
+            if (wide) index_insert_kernel<true, true><<<grid, hu::EB, 0, st>>>(a, store.n_bases, n, store.small.err(), ix->where);
+            else index_insert_kernel<false, true><<<grid, hu::EB, 0, st>>>(a, store.n_bases, n, store.small.err(), ix->where);
+        } else {
+            if (wide) index_insert_kernel<true, false><<<grid, hu::EB, 0, st>>>(a, store.n_bases, n, store.small.err(), nullptr);
+            else index_insert_kernel<false, false><<<grid, hu::EB, 0, st>>>(a, store.n_bases, n, store.small.err(), nullptr);
+        }
         HIP_CHECK(hipGetLastError());
         index_count_kernel<<<(unsigned)std::min<uint64_t>(hu::grid_for(info.slots / 2), 8192), hu::EB, 0, st>>>(ix->table, info.slots, store.small.d + 2);
         HIP_CHECK(hipGetLastError());
@@ -208,12 +348,18 @@ KmerIndex *device_kmer_index_build(const char *seq, const uint64_t *off, uint64_
         times->build_insert_ms = ev.ms(0, 1);  // (with the table's fill and the count)
     }
     info.device_bytes = info.slots * 8;
-    if (wide && info.occurrences) {
+    if (locating || (wide && info.occurrences)) {
         ix->packed = store.take_packed();
         info.device_bytes += (store.n_words + 2) * 4;
     }
+    if (locating) {
+        ix->off = store.take_off();
+        info.device_bytes += info.slots * 8 + (n + 1) * 8;
+    }
     return ix;
 }
+
+bool device_kmer_index_is_locating(const KmerIndex *ix) { return ix->locating; }
 
 void device_kmer_index_info(const KmerIndex *ix, mtg_kmer_index_info *out) { *out = ix->info; }
 
@@ -221,6 +367,8 @@ void device_kmer_index_free(KmerIndex *ix) {
     if (!ix) return;
     hu::device_free_on(ix->device_id, ix->packed);
     hu::device_free_on(ix->device_id, ix->table);
+    hu::device_free_on(ix->device_id, ix->where);
+    hu::device_free_on(ix->device_id, ix->off);
     delete ix;
 }
 
@@ -270,6 +418,90 @@ void device_kmer_index_query(const KmerIndex *ix, const char *seq, const uint64_
     }
     hu::device_free(d_counts);
     hu::device_free(d_bits);
+}
+
+void device_kmer_index_locate(const KmerIndex *ix, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid,
+                              uint64_t *found, KmerRuns *runs, KmerLocateTimes *times) {
+    if (!ix->locating) MTG_DIE("mtg_kmer_index_locate: the index keeps no positions (build it with mtg_kmer_index_build_locating)");
+    const uint64_t k = ix->info.k;
+    (void)check_offsets("mtg_kmer_index_locate", seq, off, n, k);
+    if (!runs || (n && (!kmers || !valid || !found))) MTG_DIE("mtg_kmer_index_locate: null argument");
+    const uint64_t n_bases = off[n];
+    if (n_bases >= POS_LIMIT) MTG_DIE("mtg_kmer_index_locate: %llu bases; the limit is 2^40 - 2", (unsigned long long)n_bases);
+    for (uint64_t r = 0; r < n; r++) {
+        const uint64_t len = off[r + 1] - off[r];
+        kmers[r] = len >= k ? len - k + 1 : 0;
+        valid[r] = found[r] = 0;
+    }
+    *runs = KmerRuns();
+    if (times) *times = KmerLocateTimes();
+    if (n_bases == 0) return;  // nothing to look at
+    HIP_CHECK(hipSetDevice(ix->device_id));
+    hipStream_t st = nullptr;
+    MaskedSeqStore store(seq, off, n, st, ix->device_id);
+    unsigned long long *d_counts = nullptr, *d_hit = nullptr, *d_rank = nullptr, *d_sums = nullptr;  // d_sums: the scan's block sums, then its total
+    uint32_t *d_starts = nullptr;
+    const uint64_t n_sums = hu::scan_blocks(n_bases) + 1;
+    hu::device_malloc(&d_counts, 2 * n * 8);
+    hu::device_malloc(&d_hit, n_bases * 8);
+    hu::device_malloc(&d_starts, n_bases * 4);
+    hu::device_malloc(&d_rank, n_bases * 8);
+    hu::device_malloc(&d_sums, (n_sums + 1) * 8);
+    PhaseEvents<3> ev;
+    ev.mark(0, st);
+    HIP_CHECK(hipMemsetAsync(d_counts, 0, 2 * n * 8, st));
+    HIP_CHECK(hipMemsetAsync(d_hit, 0xFF, n_bases * 8, st));
+    IndexArgs a{};
+    a.packed = store.packed; a.off = store.off; a.index_packed = ix->packed; a.table = ix->table; a.slots = ix->info.slots;
+    kw::window_args_set_k(a, k);
+    const unsigned grid = hu::grid_for((n_bases + RUN - 1) / RUN);
+    if (k >= 32) locate_kernel<true><<<grid, hu::EB, 0, st>>>(a, store.bad, n_bases, n, d_counts, ix->where, d_hit);
+    else locate_kernel<false><<<grid, hu::EB, 0, st>>>(a, store.bad, n_bases, n, d_counts, ix->where, d_hit);
+    HIP_CHECK(hipGetLastError());
+    ev.mark(1, st);
+    RunArgs ra{d_hit, store.off, ix->off, n_bases, n, ix->info.records, k};
+    const unsigned base_grid = hu::grid_for(n_bases);
+    run_flag_kernel<<<base_grid, hu::EB, 0, st>>>(ra, d_starts);
+    HIP_CHECK(hipGetLastError());
+    hu::scan_u32<unsigned long long>(st, d_starts, n_bases, d_rank, d_sums, d_sums + n_sums);
+    uint64_t n_runs = 0;
+    HIP_CHECK(hipMemcpyAsync(&n_runs, d_sums + n_sums, 8, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    unsigned long long *d_ends = nullptr, *d_out = nullptr;  // d_ends: first then last position of every run; d_out: five fields, then the strands
+    if (n_runs) {
+        hu::device_malloc(&d_ends, 2 * n_runs * 8);
+        hu::device_malloc(&d_out, 5 * n_runs * 8 + n_runs);
+        unsigned char *d_strand = reinterpret_cast<unsigned char *>(d_out + 5 * n_runs);
+        run_mark_kernel<<<base_grid, hu::EB, 0, st>>>(ra, d_starts, d_rank, n_runs, d_ends, d_ends + n_runs);
+        run_emit_kernel<<<hu::grid_for(n_runs), hu::EB, 0, st>>>(ra, n_runs, d_ends, d_ends + n_runs, d_out, d_strand);
+        HIP_CHECK(hipGetLastError());
+    }
+    ev.mark(2, st);
+    HIP_CHECK(hipMemcpyAsync(valid, d_counts, n * 8, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(found, d_counts + n, n * 8, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    if (n_runs) {
+        std::vector<uint64_t> *fields[5] = {&runs->q_record, &runs->q_start, &runs->kmers, &runs->t_record, &runs->t_start};
+        for (int f = 0; f < 5; f++) {
+            fields[f]->resize(n_runs);
+            hu::download_sliced(fields[f]->data(), d_out + f * n_runs, n_runs * 8, st, ix->device_id);
+        }
+        runs->strand.resize(n_runs);
+        hu::download_sliced(runs->strand.data(), d_out + 5 * n_runs, n_runs, st, ix->device_id);
+    }
+    if (times) {
+        times->upload_ms = store.upload_ms;
+        times->pack_ms = store.pack_ms;
+        times->probe_ms = ev.ms(0, 1);
+        times->runs_ms = ev.ms(1, 2);
+    }
+    hu::device_free(d_counts);
+    hu::device_free(d_hit);
+    hu::device_free(d_starts);
+    hu::device_free(d_rank);
+    hu::device_free(d_sums);
+    hu::device_free(d_ends);
+    hu::device_free(d_out);
 }
 
 }  // namespace mtg

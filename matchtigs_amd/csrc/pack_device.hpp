@@ -148,6 +148,12 @@ struct SeqStore {
         packed = nullptr;
         return p;
     }
+    // ... and so do the offsets
+    unsigned long long *take_off() {
+        unsigned long long *p = off;
+        off = nullptr;
+        return p;
+    }
 };
 
 // SeqStore for records of arbitrary bytes: nothing aborts. A character outside ACGT is packed as A and has its bit set in `bad`
