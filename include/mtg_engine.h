@@ -516,10 +516,35 @@ void mtg_compact_unitigs(const char *data, const uint64_t *offsets, uint64_t n, 
                          mtg_compaction *stats);
 /* The same over a store as mtg_read_sequences / mtg_read_sequences_split hand it out. */
 void mtg_compact_unitigs_store(const mtg_unitigs *in, uint64_t k, int device_id, mtg_unitigs **out, mtg_compaction *stats);
-/* Of the last compaction on this thread: {upload ms (host clock); pack, insert, ids, nodes (with succ), rank (pointer jumping), emit
+/* Of the last compaction on this thread, counted or not: {upload ms (host clock); pack, insert, ids, nodes (with succ), rank (pointer jumping), emit
  * ms -- HIP events around the kernel phases --; download ms and the whole call (host clock); pointer-jumping rounds; bytes the
  * kernels must move at the least; peak of live device-arena bytes}. */
 void mtg_last_compact_times(double out[12]);
+/* The compaction with an abundance threshold. abundance(x), for a canonical k-mer x, = the number of windows whose
+ * k-mer is x or rc(x): repeats inside a record count, both strands count, a window whose k-mer is its own reverse complement counts
+ * once. S_m = { x : abundance(x) >= min_abundance }. creator(x) and reading(x) stay what mtg_compact_unitigs says, taken over ALL
+ * windows of the input; the rest of its contract (graph, passable nodes, unitigs, leaders, order, spelling) applies to S_m with those
+ * creators -- the removed k-mers take their edges with them. With min_abundance = 1 the store and `stats` are byte for byte those of
+ * mtg_compact_unitigs. stats->distinct_kmers = |S_m|; stats->windows stays the input's windows. *sums holds, per unitig in the
+ * store's record order, the sum of abundance over its k-mers; their total is kept_occurrences. Exact integers, a function of the
+ * input and min_abundance alone. An empty S_m gives an empty store. min_abundance >= 1; fewer than 2^32 windows (the counters are
+ * 32-bit and must not wrap); both abort with a message otherwise. */
+typedef struct mtg_abundance {
+    uint64_t distinct_all;     /* |S_1| */
+    uint64_t distinct_kept;    /* |S_m| */
+    uint64_t max_abundance;
+    uint64_t kept_occurrences; /* sum of abundance over S_m */
+    uint64_t spectrum[256];    /* over S_1: [c] = distinct k-mers with abundance c (1 <= c <= 254), [255] = with abundance >= 255, [0] = 0 */
+} mtg_abundance;
+typedef struct mtg_abundance_sums mtg_abundance_sums;
+void mtg_compact_unitigs_counted(const char *data, const uint64_t *offsets, uint64_t n, uint64_t k, uint64_t min_abundance, int device_id,
+                                 mtg_unitigs **out, mtg_compaction *stats, mtg_abundance *abundance,
+                                 mtg_abundance_sums **sums); /* mtg_abundance_sums_free */
+void mtg_compact_unitigs_counted_store(const mtg_unitigs *in, uint64_t k, uint64_t min_abundance, int device_id, mtg_unitigs **out,
+                                       mtg_compaction *stats, mtg_abundance *abundance, mtg_abundance_sums **sums);
+uint64_t mtg_abundance_sums_count(const mtg_abundance_sums *sums);        /* the store's unitigs */
+const uint64_t *mtg_abundance_sums_array(const mtg_abundance_sums *sums); /* count entries; valid until mtg_abundance_sums_free */
+void mtg_abundance_sums_free(mtg_abundance_sums *sums);
 /* A k-mer set kept on GPU `device_id` and asked which k-mers of other sequences it holds (kmer_query_device.hip; there
  * is no CPU path). The indexed set is a set in mtg_compare_kmer_sets' sense: the canonical k-mers of the windows of length k inside
  * one record; records shorter than k contribute nothing, a character outside ACGT aborts, k >= 1. The index holds device memory

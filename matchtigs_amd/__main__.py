@@ -14,6 +14,10 @@ contigs, `N` and all -- are in the input's k-mer set: per record the windows, th
 and with `--query-presence-out` one `1` / `0` / `-` character per window; the set is indexed once on the GPU.
 `--query-locate-out` adds where those k-mers are: one TSV row per maximal run of consecutive query k-mers that lie one after the
 other in an input record, on either strand, with both half-open base intervals.
+`--min-abundance N` (with `--seq-in`; not in the reference) keeps only the k-mers that at least N windows of the input show, on either
+strand -- sequencing reads, where a k-mer seen once is mostly an error -- before the unitigs are formed (DESIGN.md 19);
+`--kmer-spectrum-out` writes how many distinct k-mers have each abundance, `--unitig-abundance-out` the summed and mean abundance
+of every unitig.
 """
 from __future__ import annotations
 
@@ -62,6 +66,15 @@ def main(argv=None) -> int:
                     help="TSV (.gz => gzip) with one row per maximal collinear run of found k-mers: record, qstart, qend, strand, target "
                          "(0-based input record), tstart, tend, kmers; a repeated k-mer is placed at its first occurrence; "
                          "needs --query-fa and --query-out")
+    ap.add_argument("--min-abundance", type=int, metavar="N",
+                    help="with --seq-in: compact only the k-mers seen in at least N windows of the input, both strands counted "
+                         "(N >= 1; not in the reference)")
+    ap.add_argument("--kmer-spectrum-out", metavar="PATH",
+                    help="with --seq-in: TSV (.gz => gzip) abundance, kmers: the distinct k-mers of the input per abundance, before "
+                         "the filter; the last bin is 255+")
+    ap.add_argument("--unitig-abundance-out", metavar="PATH",
+                    help="with --seq-in: TSV (.gz => gzip) unitig, kmers, abundance, mean: per record of --unitigs-fa-out (0-based) "
+                         "its k-mers, the sum of their abundances and the mean")
     args = ap.parse_args(argv)
 
     n_inputs = sum(x is not None for x in (args.bcalm_in, args.gfa_in, args.fa_in, args.seq_in))
@@ -84,7 +97,13 @@ def main(argv=None) -> int:
         ap.error("--query-fa needs --query-out" if args.query_fa else "--query-out needs --query-fa")
     if args.query_presence_out and not args.query_fa:
         ap.error("--query-presence-out needs --query-fa and --query-out")
-    if not (args.query_fa or args.greedytigs_fa_out or args.eulertigs_fa_out or args.greedytigs_gfa_out or args.eulertigs_gfa_out
+    for flag, value in (("--min-abundance", args.min_abundance), ("--kmer-spectrum-out", args.kmer_spectrum_out),
+                        ("--unitig-abundance-out", args.unitig_abundance_out)):
+        if value is not None and args.seq_in is None:
+            ap.error(f"{flag} needs --seq-in")
+    if args.min_abundance is not None and args.min_abundance < 1:
+        ap.error("--min-abundance must be >= 1")
+    if not (args.kmer_spectrum_out or args.unitig_abundance_out or args.query_fa or args.greedytigs_fa_out or args.eulertigs_fa_out or args.greedytigs_gfa_out or args.eulertigs_gfa_out
             or args.greedytigs_duplication_bitvector_out or args.matchtigs_fa_out or args.matchtigs_gfa_out or args.verify_fa or args.unitigs_fa_out):
         ap.error("nothing to do: give --greedytigs-fa-out / --greedytigs-gfa-out and/or --eulertigs-fa-out / --eulertigs-gfa-out")
 
@@ -95,16 +114,33 @@ def main(argv=None) -> int:
         graph, store = api.read_bcalm2(args.bcalm_in, args.k)
     elif args.seq_in is not None:  # sequences -> unitigs (GPU compaction) -> graph (the --fa-in join on the same store)
         seqs = api.read_sequences(args.seq_in, split_non_acgt=True)
-        store, compaction = api.compact_unitigs(seqs, args.k, args.device)
+        abundance = None
+        if args.min_abundance is None and not (args.kmer_spectrum_out or args.unitig_abundance_out):
+            store, compaction = api.compact_unitigs(seqs, args.k, args.device)
+        else:  # the counted compaction; an output flag alone counts without filtering
+            min_abundance = args.min_abundance or 1
+            store, compaction, abundance = api.compact_unitigs_counted(seqs, args.k, min_abundance, args.device)
+            if args.kmer_spectrum_out:  # (also when nothing is kept: this is how a threshold that works is found)
+                _write_spectrum(args, abundance)
+            if abundance.distinct_kept == 0:
+                print(f"no k-mer reaches --min-abundance {min_abundance} ({abundance.describe()})", file=sys.stderr)
+                return 1
+            if args.unitig_abundance_out:
+                _write_unitig_abundance(args, store, abundance)
         graph = api.Bigraph.from_sequences(store.arrays(), args.k, args.device)
     else:
         graph, store = api.read_fasta(args.fa_in, args.k, args.device)
     loaded = f"Loaded {len(store)} unitigs: {graph.node_count()} nodes, {graph.edge_count()} edges in {time.perf_counter() - t0:.1f}s"
     if args.seq_in is not None:
-        loaded += f" (compacted from {compaction.describe()}; {seqs.pieces_cut} non-ACGT runs cut)"
+        loaded += f" (compacted from {compaction.describe()}; "
+        loaded += f"{abundance.describe()}; " if abundance is not None else ""
+        loaded += f"{seqs.pieces_cut} non-ACGT runs cut)"
     print(loaded, file=sys.stderr)
     # what the tigs are verified against: the input as given -- on the --seq-in route the sequences, so that the check covers the compaction
     truth = seqs if args.seq_in is not None else store
+    filtered = args.seq_in is not None and abundance is not None and min_abundance > 1
+    if filtered:  # the tigs spell S_m, not the input's set: they are held to the unitigs, and the unitigs to the input (below)
+        truth = store
 
     def report(what: str, tigs, cmp) -> bool:
         """The verification line of one tig set; names the first missing and the first foreign k-mer when there is one."""
@@ -119,6 +155,14 @@ def main(argv=None) -> int:
         return cmp.equal
 
     all_equal = True
+    if filtered and (args.verify or args.verify_fa):
+        # by the k-mer set comparison, a kernel the compaction does not share: no foreign k-mer survived, and exactly the dropped are gone
+        cmp = api.compare_kmer_sets(seqs, store, args.k, args.device)
+        ok = cmp.only_in_b == 0 and cmp.only_in_a == abundance.dropped
+        print(f"Verifying abundance filter: {cmp.distinct_b} of the input's {cmp.distinct_a} distinct k-mers are in the unitigs, "
+              f"{cmp.only_in_a} are not ({abundance.dropped} dropped by the filter), {cmp.only_in_b} foreign: "
+              f"{'as counted' if ok else 'MISMATCH'}", file=sys.stderr)
+        all_equal &= ok
     for path in args.verify_fa or ():
         tigs = api.read_sequences(path)
         all_equal &= report(path, tigs, api.compare_kmer_sets(truth, tigs, args.k, args.device))
@@ -149,6 +193,30 @@ def main(argv=None) -> int:
     if args.query_fa:
         _query(api, args, store)
     return 0 if all_equal else 1
+
+
+def _open_text(args, path):
+    import gzip
+
+    return gzip.open(path, "wt", compresslevel=args.compression_level) if path.endswith(".gz") else open(path, "w")
+
+
+def _write_spectrum(args, abundance) -> None:
+    """`--kmer-spectrum-out`: one row per non-empty bin, ascending; the last bin holds every abundance from 255 on."""
+    last = len(abundance.spectrum) - 1
+    with _open_text(args, args.kmer_spectrum_out) as f:
+        f.write("abundance\tkmers\n")
+        f.writelines(f"{c}{'+' if c == last else ''}\t{n}\n" for c, n in enumerate(abundance.spectrum.tolist()) if n)
+
+
+def _write_unitig_abundance(args, store, abundance) -> None:
+    """`--unitig-abundance-out`: row i describes record i of the unitig store (the order `--unitigs-fa-out` writes)."""
+    import numpy as np
+
+    kmers = (np.diff(store.arrays()[1]) - np.uint64(args.k - 1)).tolist()
+    with _open_text(args, args.unitig_abundance_out) as f:
+        f.write("unitig\tkmers\tabundance\tmean\n")
+        f.writelines(f"{i}\t{n}\t{a}\t{a / n:.3f}\n" for i, (n, a) in enumerate(zip(kmers, abundance.unitig_sums.tolist())))
 
 
 def _query(api, args, store) -> None:

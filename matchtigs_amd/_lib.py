@@ -96,6 +96,13 @@ class MtgCompaction(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class MtgAbundance(C.Structure):
+    """mtg_abundance (include/mtg_engine.h)."""
+
+    _fields_ = [(n, C.c_uint64) for n in ("distinct_all", "distinct_kept", "max_abundance", "kept_occurrences")] + [
+        ("spectrum", C.c_uint64 * 256)]
+
+
 class MtgKmerIndexInfo(C.Structure):
     """mtg_kmer_index_info (include/mtg_engine.h)."""
 
@@ -245,6 +252,11 @@ def load():
         "mtg_compact_unitigs": (None, [vp, vp, u64, u64, C.c_int, P(vp), P(MtgCompaction)]),
         "mtg_compact_unitigs_store": (None, [vp, u64, C.c_int, P(vp), P(MtgCompaction)]),
         "mtg_last_compact_times": (None, [P(C.c_double)]),
+        "mtg_compact_unitigs_counted": (None, [vp, vp, u64, u64, u64, C.c_int, P(vp), P(MtgCompaction), P(MtgAbundance), P(vp)]),
+        "mtg_compact_unitigs_counted_store": (None, [vp, u64, u64, C.c_int, P(vp), P(MtgCompaction), P(MtgAbundance), P(vp)]),
+        "mtg_abundance_sums_count": (u64, [vp]),
+        "mtg_abundance_sums_array": (vp, [vp]),
+        "mtg_abundance_sums_free": (None, [vp]),
         "mtg_kmer_index_build": (vp, [vp, vp, u64, u64, C.c_int]),
         "mtg_kmer_index_build_store": (vp, [vp, u64, C.c_int]),
         "mtg_kmer_index_get_info": (None, [vp, P(MtgKmerIndexInfo)]),

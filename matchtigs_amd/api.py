@@ -912,8 +912,56 @@ def compact_unitigs(seqs_or_store, k: int, device_id: int = 0):
     return UnitigStore(out.value), Compaction(**stats.as_dict())
 
 
+@dataclass(frozen=True, eq=False)
+class Abundance:
+    """mtg_abundance plus the per-unitig sums (include/mtg_engine.h): what a counted compaction counted, in exact
+    integers. spectrum[c] = distinct k-mers of the input with abundance c (the last bin: 255 or more), taken before the filter;
+    unitig_sums[u] = the sum of abundance over the k-mers of record u of the store; their total is kept_occurrences."""
+
+    distinct_all: int
+    distinct_kept: int
+    max_abundance: int
+    kept_occurrences: int
+    spectrum: np.ndarray     # uint64[256]
+    unitig_sums: np.ndarray  # uint64[unitigs]
+
+    @property
+    def dropped(self) -> int:
+        return self.distinct_all - self.distinct_kept
+
+    def describe(self) -> str:
+        return (f"{self.distinct_all} distinct k-mers -> {self.distinct_kept} kept, {self.dropped} dropped; "
+                f"max abundance {self.max_abundance}")
+
+
+def compact_unitigs_counted(seqs_or_store, k: int, min_abundance: int, device_id: int = 0):
+    """compact_unitigs over the k-mers whose abundance -- the windows that show them, on either strand -- is at least min_abundance
+    (mtg_compact_unitigs_counted) -> (UnitigStore, Compaction, Abundance). Creators and readings are taken over all
+    windows; with min_abundance = 1 store and Compaction equal compact_unitigs'. Compaction.distinct_kmers counts the kept k-mers."""
+    if min_abundance < 1:
+        raise ValueError("min_abundance must be >= 1")
+    L = _lib.load()
+    out, sums, stats, ab = C.c_void_p(), C.c_void_p(), _lib.MtgCompaction(), _lib.MtgAbundance()
+    if isinstance(seqs_or_store, UnitigStore):
+        L.mtg_compact_unitigs_counted_store(seqs_or_store.handle, k, min_abundance, device_id, C.byref(out), C.byref(stats), C.byref(ab),
+                                            C.byref(sums))
+    else:
+        d, o, n, keep = _sequence_arrays(seqs_or_store)
+        L.mtg_compact_unitigs_counted(d, o, n, k, min_abundance, device_id, C.byref(out), C.byref(stats), C.byref(ab), C.byref(sums))
+        del keep
+    try:
+        n = int(L.mtg_abundance_sums_count(sums))
+        unitig_sums = (np.ctypeslib.as_array(C.cast(L.mtg_abundance_sums_array(sums), C.POINTER(C.c_uint64)), shape=(n,)).copy()
+                       if n else np.zeros(0, np.uint64))
+    finally:
+        L.mtg_abundance_sums_free(sums)
+    abundance = Abundance(int(ab.distinct_all), int(ab.distinct_kept), int(ab.max_abundance), int(ab.kept_occurrences),
+                          np.array(ab.spectrum, dtype=np.uint64), unitig_sums)
+    return UnitigStore(out.value), Compaction(**stats.as_dict()), abundance
+
+
 def last_compact_times() -> dict:
-    """Phases of the last compact_unitigs on this thread: ms by HIP events around the kernel phases (pack, insert, ids, nodes, rank,
+    """Phases of the last compact_unitigs / compact_unitigs_counted on this thread: ms by HIP events around the kernel phases (pack, insert, ids, nodes, rank,
     emit), upload / download / total by the host clock, the pointer-jumping rounds, the least bytes the kernels must move and the
     peak of live device-arena bytes."""
     out = (C.c_double * 12)()

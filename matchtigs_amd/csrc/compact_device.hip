@@ -39,6 +39,17 @@
 // Device memory (arena, hip_util.hpp) per input base b, window w, distinct k-mer N: pack 1.25 b; insert 0.25 b + 16 w + 4 b;
 // later 0.25 b + N (8 kpos + 32 + 16 node table + 8 succ + 16 pairs [+ 16 + 8 with closed walks] + 8 wmin/wlen + 16 leaders).
 // There is no host path: without a GPU a non-empty call aborts.
+//
+// Counted calls (mtg_compact_unitigs_counted): abundance(x) = the windows whose k-mer is x or rc(x); the contract above
+// is applied to S_m = { x : abundance(x) >= m }, creators and readings still taken over ALL windows. insert<COUNTED> adds 1 to
+// count[slot] for every window behind the slot find_slot returns (a claimed slot keeps its class: the sum per slot is the class's
+// abundance in any order); one sweep of count[] gives the spectrum (256 bins in LDS per workgroup, then at most one global atomicAdd
+// per non-empty bin and workgroup), the largest abundance and the kept occurrences; mark<COUNTED> flags a creator only where count >= m
+// and kpos<COUNTED> carries kcount[id] = count[slot]; from there N = |S_m| and nodes, succ, rank and emit run unchanged. Per-unitig
+// sums: every kept k-mer writes its count at its place in unitig order (k-mer offset of its unitig + rank), one scan to 64 bits, and
+// differences at the unitig boundaries -- no atomic at all. Fewer than 2^32 windows (32-bit counters cannot wrap).
+// Memory added by a counted call: 4 B per slot (8 w) while inserting, freed with the table; 4 N (kcount) afterwards; 12 N + 8 per
+// unitig for the sums at the end of emit.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -71,8 +82,9 @@ __device__ __forceinline__ uint64_t pair_of(uint32_t jump, uint32_t rank) { retu
 __device__ __forceinline__ uint64_t load64(const unsigned long long *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void store64(unsigned long long *p, uint64_t v) { __hip_atomic_store(p, (unsigned long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-template <bool WIDE>
-__global__ __launch_bounds__(hu::EB) void insert_kernel(KmerArgs a, uint64_t n_bases, uint64_t n_rec, unsigned int *err) {
+// COUNTED: count[slot] += 1 per window (the class's abundance once the kernel has finished)
+template <bool WIDE, bool COUNTED>
+__global__ __launch_bounds__(hu::EB) void insert_kernel(KmerArgs a, uint64_t n_bases, uint64_t n_rec, unsigned int *err, uint32_t *count) {
     const uint64_t p0 = hu::gid() * RUN;
     if (p0 >= n_bases) return;
     kw::for_each_window<WIDE>(a, p0, p0 + RUN < n_bases ? p0 + RUN : n_bases, 0, n_rec, [&](uint64_t q, uint64_t, const kw::Window &w) {
@@ -80,29 +92,90 @@ __global__ __launch_bounds__(hu::EB) void insert_kernel(KmerArgs a, uint64_t n_b
         const kw::Found f = kw::find_slot<true>(a.table, a.slots, w.hash, mine, [&](unsigned long long cur) {
             return (cur >> 40) == (mine >> 40) && kw::same_class(a.packed, q, cur & POS_LIMIT, a.k);
         });
-        if (f.slot == a.slots) atomicOr(err, 1u);  // (2 slots per window: never full)
-        else if (f.word != EMPTY_SLOT && mine < f.word) atomicMin(&a.table[f.slot], mine);
+        if (f.slot == a.slots) {
+            atomicOr(err, 1u);  // (2 slots per window: never full)
+            return;
+        }
+        if (f.word != EMPTY_SLOT && mine < f.word) atomicMin(&a.table[f.slot], mine);
+        if (COUNTED) atomicAdd(&count[f.slot], 1u);
     });
 }
 
 // flag[creator] = 1 for every occupied slot; *count += occupied slots (grid-stride: one atomic per wave of the whole grid)
-__global__ __launch_bounds__(hu::EB) void mark_kernel(const unsigned long long *table, uint64_t slots, uint32_t *flag, unsigned long long *count) {
+// COUNTED: only the slots whose class has abundance >= m
+template <bool COUNTED>
+__global__ __launch_bounds__(hu::EB) void mark_kernel(const unsigned long long *table, uint64_t slots, uint32_t *flag, unsigned long long *count,
+                                                       const uint32_t *abundance, uint64_t m) {
     unsigned long long n = 0;
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t s = hu::gid(); s < slots; s += stride) {
         const unsigned long long cur = table[s];
         if (cur == EMPTY_SLOT) continue;
+        if (COUNTED && abundance[s] < m) continue;
         flag[cur & POS_LIMIT] = 1u;
         n++;
     }
     for (int d = warpSize / 2; d > 0; d /= 2) n += __shfl_down(n, d);
     if (n && (threadIdx.x & (warpSize - 1)) == 0) atomicAdd(count, n);
 }
-__global__ __launch_bounds__(hu::EB) void kpos_kernel(const unsigned long long *table, uint64_t slots, const uint32_t *id_of_pos, unsigned long long *kpos) {
+// COUNTED: kcount[id] = the abundance of k-mer id
+template <bool COUNTED>
+__global__ __launch_bounds__(hu::EB) void kpos_kernel(const unsigned long long *table, uint64_t slots, const uint32_t *id_of_pos, unsigned long long *kpos,
+                                                       const uint32_t *abundance, uint64_t m, uint32_t *kcount) {
     const uint64_t s = hu::gid();
     if (s >= slots) return;
     const unsigned long long cur = table[s];
-    if (cur != EMPTY_SLOT) kpos[id_of_pos[cur & POS_LIMIT]] = cur & POS_LIMIT;
+    if (cur == EMPTY_SLOT) return;
+    if (!COUNTED) {
+        kpos[id_of_pos[cur & POS_LIMIT]] = cur & POS_LIMIT;
+    } else if (abundance[s] >= m) {
+        const uint32_t id = id_of_pos[cur & POS_LIMIT];
+        kpos[id] = cur & POS_LIMIT;
+        kcount[id] = abundance[s];
+    }
+}
+
+// One sweep over the abundances of the table's slots (0 = empty). out[0 .. 256): the spectrum, bin min(c, 255); out[256] = the largest
+// abundance; out[257] = the sum of the abundances >= m. A workgroup counts into 256 bins in LDS and then issues at most one global
+// atomicAdd per non-empty bin; the maximum and the sum are reduced per wave, then per workgroup, and cost one atomic each.
+constexpr int SPECTRUM_BINS = 256;
+__global__ __launch_bounds__(hu::EB) void spectrum_kernel(const uint32_t *abundance, uint64_t slots, uint64_t m, unsigned long long *out) {
+    __shared__ uint32_t bins[SPECTRUM_BINS];  // (a workgroup sweeps fewer than 2^32 slots)
+    __shared__ unsigned long long wave_sum[hu::EB / 64];
+    __shared__ uint32_t wave_max[hu::EB / 64];
+    static_assert(hu::EB == SPECTRUM_BINS, "one thread per bin");
+    bins[threadIdx.x] = 0;
+    __syncthreads();
+    unsigned long long sum = 0;
+    uint32_t top = 0;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t s = hu::gid(); s < slots; s += stride) {
+        const uint32_t c = abundance[s];
+        if (!c) continue;
+        atomicAdd(&bins[c < SPECTRUM_BINS - 1 ? c : SPECTRUM_BINS - 1], 1u);
+        top = c > top ? c : top;
+        if (c >= m) sum += c;
+    }
+    for (int d = warpSize / 2; d > 0; d /= 2) {
+        sum += __shfl_down(sum, d);
+        const uint32_t o = __shfl_down(top, d);
+        top = o > top ? o : top;
+    }
+    const int lane = threadIdx.x & (warpSize - 1), wave = threadIdx.x / warpSize;
+    if (lane == 0) {
+        wave_sum[wave] = sum;
+        wave_max[wave] = top;
+    }
+    __syncthreads();
+    if (bins[threadIdx.x]) atomicAdd(&out[threadIdx.x], (unsigned long long)bins[threadIdx.x]);
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < hu::EB / warpSize; w++) {
+            sum += wave_sum[w];
+            top = wave_max[w] > top ? wave_max[w] : top;
+        }
+        if (sum) atomicAdd(&out[SPECTRUM_BINS + 1], sum);
+        if (top) atomicMax(&out[SPECTRUM_BINS], (unsigned long long)top);
+    }
 }
 
 struct NodeArgs {
@@ -267,16 +340,44 @@ __global__ __launch_bounds__(hu::EB) void spell_kernel(const uint32_t *packed, c
         for (uint64_t j = 0; j + 1 < k; j++) out[at + j] = abc[mir ? 3u - packed_base(packed, pos + k - 1 - j) : packed_base(packed, pos + j)];
 }
 
+// ---- per-unitig abundance sums (counted calls) ----
+// Every oriented k-mer of an emitted walk writes its k-mer's abundance at its place in unitig order: unitig u starts at character
+// offset char_off, i.e. at k-mer offset char_off - (k - 1) u, and the k-mer is `rank` steps behind the walk's head.
+__global__ __launch_bounds__(hu::EB) void order_counts_kernel(const unsigned long long *pairs, const uint32_t *wmin, const uint64_t *char_off,
+                                                               const uint32_t *unitig_of, const uint32_t *kcount, uint64_t n, uint64_t k,
+                                                               uint32_t *ordered) {
+    const uint64_t o = hu::gid();
+    if (o >= n) return;
+    const uint64_t pr = pairs[o];
+    const uint32_t h = (uint32_t)pr == NONE32 ? (uint32_t)o : (uint32_t)pr, m = wmin[h];
+    if (m & 1u) return;
+    ordered[char_off[m >> 1] - (k - 1) * unitig_of[m >> 1] + (pr >> 32)] = kcount[o >> 1];
+}
+// sums[u] = prefix[first k-mer of u + 1] - prefix[first k-mer of u] over the exclusive 64-bit prefix sums of `ordered`
+__global__ __launch_bounds__(hu::EB) void unitig_sums_kernel(const unsigned long long *out_off, const uint64_t *prefix, const uint64_t *total,
+                                                              uint64_t n_unitigs, uint64_t k, unsigned long long *sums) {
+    const uint64_t u = hu::gid();
+    if (u >= n_unitigs) return;
+    const uint64_t lo = prefix[out_off[u] - (k - 1) * u];
+    sums[u] = (u + 1 < n_unitigs ? prefix[out_off[u + 1] - (k - 1) * (u + 1)] : *total) - lo;
+}
+
 int log2_ceil(uint64_t n) {
     int r = 0;
     while ((1ull << r) < n) r++;
     return r;
 }
 
-}  // namespace
+// what a counted call adds: the threshold in, the statistics and the per-unitig sums out
+struct Counted {
+    uint64_t m;
+    mtg_abundance *abundance;
+    std::vector<uint64_t> *sums;
+};
 
-UnitigStore *device_compact_unitigs(const char *data, const uint64_t *off, uint64_t n_rec, uint64_t k, int device_id, mtg_compaction *stats_out,
-                                    CompactTimes *times) {
+// counted == nullptr: the plain compaction
+UnitigStore *compact(const char *data, const uint64_t *off, uint64_t n_rec, uint64_t k, int device_id, mtg_compaction *stats_out, CompactTimes *times,
+                     const Counted *counted) {
     if (!off || (n_rec && off[n_rec] && !data)) MTG_DIE("mtg_compact_unitigs: null argument");
     if (k < 2) MTG_DIE("mtg_compact_unitigs: k must be >= 2");
     if (k >= (1ull << 31)) MTG_DIE("mtg_compact_unitigs: k too large");
@@ -293,9 +394,17 @@ UnitigStore *device_compact_unitigs(const char *data, const uint64_t *off, uint6
     CompactTimes t{};
     UnitigStore *store = new UnitigStore();
     store->off.push_back(0);
+    mtg_abundance ab{};
+    if (counted) {
+        if (counted->m == 0) MTG_DIE("mtg_compact_unitigs_counted: min_abundance must be >= 1");
+        if (r.windows >= (1ull << 32)) MTG_DIE("mtg_compact_unitigs_counted: %llu windows; the abundance counters are 32-bit, the limit is 2^32 - 1",
+                                               (unsigned long long)r.windows);
+        counted->sums->clear();
+    }
     auto finish = [&]() {
         t.total_ms = ms_since(t_total);
         if (stats_out) *stats_out = r;
+        if (counted && counted->abundance) *counted->abundance = ab;
         if (times) *times = t;
         return store;
     };
@@ -327,32 +436,73 @@ UnitigStore *device_compact_unitigs(const char *data, const uint64_t *off, uint6
     kw::window_args_set_k(ka, k);
     hu::device_malloc(&ka.table, slots * 8);
     HIP_CHECK(hipMemsetAsync(ka.table, 0xFF, slots * 8, st));
+    uint32_t *d_count = nullptr, *d_kcount = nullptr;  // counted calls: [slots] abundance per slot, [N] per kept k-mer
+    if (counted) {
+        hu::device_malloc(&d_count, slots * 4);
+        HIP_CHECK(hipMemsetAsync(d_count, 0, slots * 4, st));
+    }
     {
         const unsigned grid = hu::grid_for((n_bases + RUN - 1) / RUN);
-        if (k >= 32) insert_kernel<true><<<grid, hu::EB, 0, st>>>(ka, n_bases, n_rec, d_err);
-        else insert_kernel<false><<<grid, hu::EB, 0, st>>>(ka, n_bases, n_rec, d_err);
+        if (counted) {
+            if (k >= 32) insert_kernel<true, true><<<grid, hu::EB, 0, st>>>(ka, n_bases, n_rec, d_err, d_count);
+            else insert_kernel<false, true><<<grid, hu::EB, 0, st>>>(ka, n_bases, n_rec, d_err, d_count);
+        } else {
+            if (k >= 32) insert_kernel<true, false><<<grid, hu::EB, 0, st>>>(ka, n_bases, n_rec, d_err, nullptr);
+            else insert_kernel<false, false><<<grid, hu::EB, 0, st>>>(ka, n_bases, n_rec, d_err, nullptr);
+        }
         HIP_CHECK(hipGetLastError());
     }
     ev.mark(1, st);
+
+    // ---- counted calls: the spectrum, before the filter ----
+    if (counted) {
+        unsigned long long *d_spec = nullptr;
+        std::vector<unsigned long long> h_spec(SPECTRUM_BINS + 2);
+        hu::device_malloc(&d_spec, h_spec.size() * 8);
+        HIP_CHECK(hipMemsetAsync(d_spec, 0, h_spec.size() * 8, st));
+        spectrum_kernel<<<(unsigned)std::min<uint64_t>(hu::grid_for(slots), 4096), hu::EB, 0, st>>>(d_count, slots, counted->m, d_spec);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpyAsync(h_spec.data(), d_spec, h_spec.size() * 8, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        hu::device_free(d_spec);
+        for (int c = 0; c < SPECTRUM_BINS; c++) ab.distinct_all += ab.spectrum[c] = h_spec[c];
+        ab.max_abundance = h_spec[SPECTRUM_BINS];
+        ab.kept_occurrences = h_spec[SPECTRUM_BINS + 1];
+    }
 
     // ---- ids in creator order ----
     uint32_t *d_id_of_pos = nullptr;
     hu::device_malloc(&d_id_of_pos, n_bases * 4);
     HIP_CHECK(hipMemsetAsync(d_id_of_pos, 0, n_bases * 4, st));
-    mark_kernel<<<(unsigned)std::min<uint64_t>(hu::grid_for(slots), 16384), hu::EB, 0, st>>>(ka.table, slots, d_id_of_pos, small.d + 2);
+    {
+        const unsigned grid = (unsigned)std::min<uint64_t>(hu::grid_for(slots), 16384);
+        if (counted) mark_kernel<true><<<grid, hu::EB, 0, st>>>(ka.table, slots, d_id_of_pos, small.d + 2, d_count, counted->m);
+        else mark_kernel<false><<<grid, hu::EB, 0, st>>>(ka.table, slots, d_id_of_pos, small.d + 2, nullptr, 0);
+    }
     HIP_CHECK(hipGetLastError());
     small.read(st, stage);
     const uint64_t N = r.distinct_kmers = small.h[2], n_or = 2 * N;
     if (N > MAX_KMERS) MTG_DIE("mtg_compact_unitigs: %llu distinct k-mers; oriented k-mer ids are 32-bit", (unsigned long long)N);
+    if (counted) ab.distinct_kept = N;
+    if (N == 0) {  // (counted calls only: no k-mer reaches the threshold)
+        free_all({ka.table, d_id_of_pos, d_count});
+        t.insert_ms = ev.ms(0, 1);
+        return finish();
+    }
     uint32_t *d_bsum32 = nullptr;
     unsigned long long *d_kpos = nullptr;
     hu::device_malloc(&d_bsum32, (hu::scan_blocks(n_bases) + 2) * 4);
     hu::device_malloc(&d_kpos, N * 8);
     hu::scan_u32<uint32_t>(st, d_id_of_pos, n_bases, d_id_of_pos, d_bsum32, d_bsum32 + hu::scan_blocks(n_bases) + 1);
-    kpos_kernel<<<hu::grid_for(slots), hu::EB, 0, st>>>(ka.table, slots, d_id_of_pos, d_kpos);
+    if (counted) {
+        hu::device_malloc(&d_kcount, N * 4);
+        kpos_kernel<true><<<hu::grid_for(slots), hu::EB, 0, st>>>(ka.table, slots, d_id_of_pos, d_kpos, d_count, counted->m, d_kcount);
+    } else {
+        kpos_kernel<false><<<hu::grid_for(slots), hu::EB, 0, st>>>(ka.table, slots, d_id_of_pos, d_kpos, nullptr, 0, nullptr);
+    }
     HIP_CHECK(hipGetLastError());
     ev.mark(2, st);
-    free_all({ka.table, d_id_of_pos, d_bsum32});
+    free_all({ka.table, d_id_of_pos, d_bsum32, d_count});
 
     // ---- the (k-1)-mer classes and succ ----
     NodeArgs na{};
@@ -450,6 +600,19 @@ UnitigStore *device_compact_unitigs(const char *data, const uint64_t *off, uint6
     offsets_kernel<<<hu::grid_for(N), hu::EB, 0, st>>>(d_lead_chars, d_lead_flag, d_char_off, N, d_out_off);
     spell_kernel<<<hu::grid_for(n_or), hu::EB, 0, st>>>(d_packed, d_kpos, d_pairs, d_wmin, d_char_off, n_or, k, d_out);
     HIP_CHECK(hipGetLastError());
+    unsigned long long *d_sums = nullptr;
+    if (counted) {  // the abundances in unitig order, their 64-bit prefix sums, differences at the unitig boundaries
+        uint32_t *d_ordered = nullptr;
+        uint64_t *d_prefix = nullptr;
+        hu::device_malloc(&d_ordered, N * 4);
+        hu::device_malloc(&d_prefix, N * 8);
+        hu::device_malloc(&d_sums, r.unitigs * 8);
+        order_counts_kernel<<<hu::grid_for(n_or), hu::EB, 0, st>>>(d_pairs, d_wmin, d_char_off, d_lead_flag, d_kcount, n_or, k, d_ordered);
+        hu::scan_u32<uint64_t>(st, d_ordered, N, d_prefix, d_bsum64, d_n_chars);  // (the block sums and the total's word are free again)
+        unitig_sums_kernel<<<hu::grid_for(r.unitigs), hu::EB, 0, st>>>(d_out_off, d_prefix, d_n_chars, r.unitigs, k, d_sums);
+        HIP_CHECK(hipGetLastError());
+        free_all({d_ordered, d_prefix});
+    }
     ev.mark(5, st);
     HIP_CHECK(hipStreamSynchronize(st));
 
@@ -459,6 +622,10 @@ UnitigStore *device_compact_unitigs(const char *data, const uint64_t *off, uint6
     hu::download_sliced(&store->data[0], d_out, n_chars, st, device_id);
     hu::download_sliced(store->off.data(), d_out_off, r.unitigs * 8, st, device_id);
     store->off[r.unitigs] = n_chars;
+    if (counted) {
+        counted->sums->resize(r.unitigs);
+        hu::download_sliced(counted->sums->data(), d_sums, r.unitigs * 8, st, device_id);
+    }
     t.download_ms = ms_since(t0);
     t.insert_ms = ev.ms(0, 1);
     t.ids_ms = ev.ms(1, 2);
@@ -466,7 +633,7 @@ UnitigStore *device_compact_unitigs(const char *data, const uint64_t *off, uint6
     t.rank_ms = ev.ms(3, 4);
     t.emit_ms = ev.ms(4, 5);
     t.rounds = rounds;
-    free_all({d_kpos, na.succ, d_pairs, d_wmin, d_wlen, d_lead_flag, d_lead_chars, d_char_off, d_bsum32, d_bsum64, d_out, d_out_off});
+    free_all({d_kpos, na.succ, d_pairs, d_wmin, d_wlen, d_lead_flag, d_lead_chars, d_char_off, d_bsum32, d_bsum64, d_out, d_out_off, d_kcount, d_sums});
     uint64_t arena[4];
     device_arena_stats(device_id, arena);
     t.peak_arena_bytes = arena[2];
@@ -479,6 +646,21 @@ UnitigStore *device_compact_unitigs(const char *data, const uint64_t *off, uint6
               N * (8 * 3 + 2 * 4 * ((k + 15) / 16 + 1) + 2 * (8 + 4) * 2 + 8) + n_or * 8 * (uint64_t)std::max(rounds, 1) +
               n_or * (4 + 8 + 8 + 8 + 4) + N * (4 * 3 + 4 * 2 + 8 * 2) + n_chars + r.unitigs * 8;
     return finish();
+}
+
+}  // namespace
+
+UnitigStore *device_compact_unitigs(const char *data, const uint64_t *off, uint64_t n_rec, uint64_t k, int device_id, mtg_compaction *stats_out,
+                                    CompactTimes *times) {
+    return compact(data, off, n_rec, k, device_id, stats_out, times, nullptr);
+}
+
+UnitigStore *device_compact_unitigs_counted(const char *data, const uint64_t *off, uint64_t n_rec, uint64_t k, uint64_t min_abundance, int device_id,
+                                            mtg_compaction *stats_out, mtg_abundance *abundance_out, std::vector<uint64_t> *unitig_sums,
+                                            CompactTimes *times) {
+    if (!unitig_sums) MTG_DIE("mtg_compact_unitigs_counted: null argument");
+    const Counted c{min_abundance, abundance_out, unitig_sums};
+    return compact(data, off, n_rec, k, device_id, stats_out, times, &c);
 }
 
 }  // namespace mtg

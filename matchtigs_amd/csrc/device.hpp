@@ -168,6 +168,11 @@ struct CompactTimes {
 };
 UnitigStore *device_compact_unitigs(const char *data, const uint64_t *off, uint64_t n_rec, uint64_t k, int device_id, mtg_compaction *stats_out,
                                     CompactTimes *times);
+// ... of the k-mers whose abundance reaches min_abundance: the statistics of the counting and, per unitig in the
+// store's order, the sum of its k-mers' abundances. The spectrum sweep is booked under ids_ms, the sums under emit_ms.
+UnitigStore *device_compact_unitigs_counted(const char *data, const uint64_t *off, uint64_t n_rec, uint64_t k, uint64_t min_abundance, int device_id,
+                                            mtg_compaction *stats_out, mtg_abundance *abundance_out, std::vector<uint64_t> *unitig_sums,
+                                            CompactTimes *times);
 // fasta_in.cpp: read_fasta_records without an alphabet rule and without case folding (the queries of the k-mer index), plus the
 // record names (the header text behind `>` up to the first white space) as a second store
 UnitigStore *read_fasta_records_named(const char *path, UnitigStore **names_out);

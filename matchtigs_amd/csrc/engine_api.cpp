@@ -737,6 +737,29 @@ void mtg_compact_unitigs_store(const mtg_unitigs *in, uint64_t k, int device_id,
     if (!in || !out) MTG_DIE("mtg_compact_unitigs_store: null argument");
     *out = new mtg_unitigs{device_compact_unitigs(in->s->data.data(), in->s->off.data(), in->s->off.size() - 1, k, device_id, stats, &g_last_compact)};
 }
+struct mtg_abundance_sums { std::vector<uint64_t> v; };
+void mtg_compact_unitigs_counted(const char *data, const uint64_t *offsets, uint64_t n, uint64_t k, uint64_t min_abundance, int device_id,
+                                 mtg_unitigs **out, mtg_compaction *stats, mtg_abundance *abundance, mtg_abundance_sums **sums) {
+    if (!out || !sums) MTG_DIE("mtg_compact_unitigs_counted: null argument");
+    if (min_abundance == 0) MTG_DIE("mtg_compact_unitigs_counted: min_abundance must be >= 1");
+    mtg_abundance_sums *s = new mtg_abundance_sums();
+    *out = new mtg_unitigs{device_compact_unitigs_counted(data, offsets, n, k, min_abundance, device_id, stats, abundance, &s->v, &g_last_compact)};
+    *sums = s;
+}
+void mtg_compact_unitigs_counted_store(const mtg_unitigs *in, uint64_t k, uint64_t min_abundance, int device_id, mtg_unitigs **out,
+                                       mtg_compaction *stats, mtg_abundance *abundance, mtg_abundance_sums **sums) {
+    if (!in) MTG_DIE("mtg_compact_unitigs_counted_store: null argument");
+    mtg_compact_unitigs_counted(in->s->data.data(), in->s->off.data(), in->s->off.size() - 1, k, min_abundance, device_id, out, stats, abundance, sums);
+}
+uint64_t mtg_abundance_sums_count(const mtg_abundance_sums *sums) {
+    if (!sums) MTG_DIE("mtg_abundance_sums_count: null argument");
+    return sums->v.size();
+}
+const uint64_t *mtg_abundance_sums_array(const mtg_abundance_sums *sums) {
+    if (!sums) MTG_DIE("mtg_abundance_sums_array: null argument");
+    return sums->v.data();
+}
+void mtg_abundance_sums_free(mtg_abundance_sums *sums) { delete sums; }
 void mtg_last_compact_times(double out[12]) {
     const CompactTimes &t = g_last_compact;
     out[0] = t.upload_ms; out[1] = t.pack_ms; out[2] = t.insert_ms; out[3] = t.ids_ms; out[4] = t.nodes_ms; out[5] = t.rank_ms;
