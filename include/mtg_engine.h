@@ -545,6 +545,20 @@ void mtg_compact_unitigs_counted_store(const mtg_unitigs *in, uint64_t k, uint64
 uint64_t mtg_abundance_sums_count(const mtg_abundance_sums *sums);        /* the store's unitigs */
 const uint64_t *mtg_abundance_sums_array(const mtg_abundance_sums *sums); /* count entries; valid until mtg_abundance_sums_free */
 void mtg_abundance_sums_free(mtg_abundance_sums *sums);
+/* mtg_compact_unitigs_counted, output for output, plus the abundance of every kept k-mer: *kmer_counts holds one
+ * uint32 per k-mer of S_m IN WINDOW ORDER OF THE OUTPUT STORE -- entry (sum over the unitigs v < u of len(v) - k + 1) + j is the
+ * abundance of the k-mer at offset j of unitig u; count = distinct_kept, the entries of unitig u add up to sums[u]. It is the weights
+ * array mtg_kmer_index_build_weighted_store takes for *out. An empty S_m gives a handle with zero entries. */
+typedef struct mtg_kmer_counts mtg_kmer_counts;
+void mtg_compact_unitigs_counted_kmers(const char *data, const uint64_t *offsets, uint64_t n, uint64_t k, uint64_t min_abundance, int device_id,
+                                       mtg_unitigs **out, mtg_compaction *stats, mtg_abundance *abundance, mtg_abundance_sums **sums,
+                                       mtg_kmer_counts **kmer_counts); /* mtg_kmer_counts_free */
+void mtg_compact_unitigs_counted_kmers_store(const mtg_unitigs *in, uint64_t k, uint64_t min_abundance, int device_id, mtg_unitigs **out,
+                                             mtg_compaction *stats, mtg_abundance *abundance, mtg_abundance_sums **sums,
+                                             mtg_kmer_counts **kmer_counts);
+uint64_t mtg_kmer_counts_count(const mtg_kmer_counts *counts);        /* the store's k-mers */
+const uint32_t *mtg_kmer_counts_array(const mtg_kmer_counts *counts); /* count entries; valid until mtg_kmer_counts_free */
+void mtg_kmer_counts_free(mtg_kmer_counts *counts);
 /* A k-mer set kept on GPU `device_id` and asked which k-mers of other sequences it holds (kmer_query_device.hip; there
  * is no CPU path). The indexed set is a set in mtg_compare_kmer_sets' sense: the canonical k-mers of the windows of length k inside
  * one record; records shorter than k contribute nothing, a character outside ACGT aborts, k >= 1. The index holds device memory
@@ -602,6 +616,32 @@ void mtg_kmer_runs_free(mtg_kmer_runs *runs);
 /* Of the last mtg_kmer_index_locate on this thread, in ms: {upload (host clock), pack, probe (with the fill of the hit array), runs
  * (flag, scan, emit)} -- HIP events around the kernels. */
 void mtg_last_kmer_locate_times(double out[4]);
+/* HOW HEAVY the k-mers of a query are. A WEIGHTED index is built by the two functions below from the sequences and
+ * one uint32 per window of them, in window order: a record shorter than k has no window, and the window at global position q of
+ * record r has the ordinal (windows of the records before r) + (q - off[r]). n_weights must equal info.occurrences, else the call
+ * aborts. weight(class) = weights[ordinal(loc)], loc = the class's smallest window start as mtg_kmer_index_locate defines it: a
+ * repeated k-mer takes the weight of its first occurrence, a function of the input alone. The index keeps 4 B per slot more (counted
+ * in info.device_bytes). locating = 0: it answers mtg_kmer_index_query and mtg_kmer_index_abundance and aborts on
+ * mtg_kmer_index_locate; locating != 0: it is a full locating index as well. Query and locate answer exactly as on an index built
+ * without weights. */
+mtg_kmer_index *mtg_kmer_index_build_weighted(const char *seq, const uint64_t *off, uint64_t n, uint64_t k, const uint32_t *weights,
+                                              uint64_t n_weights, int locating, int device_id);
+mtg_kmer_index *mtg_kmer_index_build_weighted_store(const mtg_unitigs *store, uint64_t k, const uint32_t *weights, uint64_t n_weights,
+                                                    int locating, int device_id);
+int mtg_kmer_index_is_weighted(const mtg_kmer_index *ix);
+/* The query of mtg_kmer_index_query (kmers / valid / found as there) plus, for record r over its found windows: sum[r] = the sum of
+ * weight(class of the window), in 64 bits; min[r] / max[r] = the smallest / largest such weight; all three 0 when found[r] = 0.
+ * per_window (may be NULL; off[n] entries, one per global base position of the query): [p] = the weight of the class of the window
+ * that starts at p if that window is valid and found, else 0 -- invalid and absent windows, the last k - 1 positions of a record and
+ * records shorter than k. Exact integers, a function of the inputs alone; the index is not changed. An empty query returns at once.
+ * Aborts if the index is not weighted. */
+void mtg_kmer_index_abundance(const mtg_kmer_index *ix, const char *seq, const uint64_t *off, uint64_t n,
+                              uint64_t *kmers, uint64_t *valid, uint64_t *found, /* [n] each */
+                              uint64_t *sum, uint32_t *min, uint32_t *max,       /* [n] each */
+                              uint32_t *per_window);                             /* nullable, [off[n]] */
+/* Of the last mtg_kmer_index_abundance on this thread, in ms: {upload (host clock), pack, probe -- HIP events around the kernels --,
+ * download (host clock)}. */
+void mtg_last_kmer_abundance_times(double out[4]);
 /* mtg_read_sequences without an alphabet rule: every byte of a sequence line is kept as it is (`N`, IUPAC codes, lower case), for
  * the queries of a k-mer index. *names_out = the record names as a second store with the same accessors: the header text behind `>`
  * up to the first white space. */

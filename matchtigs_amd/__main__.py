@@ -18,6 +18,10 @@ other in an input record, on either strand, with both half-open base intervals (
 strand -- sequencing reads, where a k-mer seen once is mostly an error -- before the unitigs are formed (DESIGN.md 19);
 `--kmer-spectrum-out` writes how many distinct k-mers have each abundance, `--unitig-abundance-out` the summed and mean abundance
 of every unitig.
+`--query-abundance-out` (with `--seq-in` and `--query-fa`) reports how often the k-mers of each query record were seen in the input: the
+index is weighted with the abundance of every kept k-mer, and a TSV row per query record gives the k-mers found and the sum, the
+smallest, the largest and the mean of their abundances; `--query-abundance-profile-out` adds one abundance per k-mer of every
+query record, and `--unitig-kmer-abundance-out` writes the abundance of every k-mer of every unitig.
 """
 from __future__ import annotations
 
@@ -75,6 +79,14 @@ def main(argv=None) -> int:
     ap.add_argument("--unitig-abundance-out", metavar="PATH",
                     help="with --seq-in: TSV (.gz => gzip) unitig, kmers, abundance, mean: per record of --unitigs-fa-out (0-based) "
                          "its k-mers, the sum of their abundances and the mean")
+    ap.add_argument("--query-abundance-out", metavar="PATH",
+                    help="with --seq-in, --query-fa and --query-out: TSV (.gz => gzip) with one row per query record: record, kmers, "
+                         "valid, found, then sum, min, max and mean of the input abundances of its found k-mers (mean `-` if none)")
+    ap.add_argument("--query-abundance-profile-out", metavar="PATH",
+                    help="per query record a line with one integer per k-mer: its abundance in the input, 0 not in the set, - holds a "
+                         "non-ACGT character (.gz => gzip); needs --query-abundance-out")
+    ap.add_argument("--unitig-kmer-abundance-out", metavar="PATH",
+                    help="with --seq-in: per record of --unitigs-fa-out a line with the abundance of each of its k-mers (.gz => gzip)")
     args = ap.parse_args(argv)
 
     n_inputs = sum(x is not None for x in (args.bcalm_in, args.gfa_in, args.fa_in, args.seq_in))
@@ -97,13 +109,17 @@ def main(argv=None) -> int:
         ap.error("--query-fa needs --query-out" if args.query_fa else "--query-out needs --query-fa")
     if args.query_presence_out and not args.query_fa:
         ap.error("--query-presence-out needs --query-fa and --query-out")
+    if args.query_abundance_out and not (args.seq_in and args.query_fa and args.query_out):
+        ap.error("--query-abundance-out needs --seq-in, --query-fa and --query-out")
+    if args.query_abundance_profile_out and not args.query_abundance_out:
+        ap.error("--query-abundance-profile-out needs --query-abundance-out")
     for flag, value in (("--min-abundance", args.min_abundance), ("--kmer-spectrum-out", args.kmer_spectrum_out),
-                        ("--unitig-abundance-out", args.unitig_abundance_out)):
+                        ("--unitig-abundance-out", args.unitig_abundance_out), ("--unitig-kmer-abundance-out", args.unitig_kmer_abundance_out)):
         if value is not None and args.seq_in is None:
             ap.error(f"{flag} needs --seq-in")
     if args.min_abundance is not None and args.min_abundance < 1:
         ap.error("--min-abundance must be >= 1")
-    if not (args.kmer_spectrum_out or args.unitig_abundance_out or args.query_fa or args.greedytigs_fa_out or args.eulertigs_fa_out or args.greedytigs_gfa_out or args.eulertigs_gfa_out
+    if not (args.kmer_spectrum_out or args.unitig_abundance_out or args.unitig_kmer_abundance_out or args.query_fa or args.greedytigs_fa_out or args.eulertigs_fa_out or args.greedytigs_gfa_out or args.eulertigs_gfa_out
             or args.greedytigs_duplication_bitvector_out or args.matchtigs_fa_out or args.matchtigs_gfa_out or args.verify_fa or args.unitigs_fa_out):
         ap.error("nothing to do: give --greedytigs-fa-out / --greedytigs-gfa-out and/or --eulertigs-fa-out / --eulertigs-gfa-out")
 
@@ -115,11 +131,15 @@ def main(argv=None) -> int:
     elif args.seq_in is not None:  # sequences -> unitigs (GPU compaction) -> graph (the --fa-in join on the same store)
         seqs = api.read_sequences(args.seq_in, split_non_acgt=True)
         abundance = None
-        if args.min_abundance is None and not (args.kmer_spectrum_out or args.unitig_abundance_out):
+        per_kmer = bool(args.query_abundance_out or args.unitig_kmer_abundance_out)  # 
+        if args.min_abundance is None and not (args.kmer_spectrum_out or args.unitig_abundance_out or per_kmer):
             store, compaction = api.compact_unitigs(seqs, args.k, args.device)
         else:  # the counted compaction; an output flag alone counts without filtering
             min_abundance = args.min_abundance or 1
-            store, compaction, abundance = api.compact_unitigs_counted(seqs, args.k, min_abundance, args.device)
+            if per_kmer:
+                store, compaction, abundance = api.compact_unitigs_counted(seqs, args.k, min_abundance, args.device, kmer_counts=True)
+            else:
+                store, compaction, abundance = api.compact_unitigs_counted(seqs, args.k, min_abundance, args.device)
             if args.kmer_spectrum_out:  # (also when nothing is kept: this is how a threshold that works is found)
                 _write_spectrum(args, abundance)
             if abundance.distinct_kept == 0:
@@ -127,6 +147,8 @@ def main(argv=None) -> int:
                 return 1
             if args.unitig_abundance_out:
                 _write_unitig_abundance(args, store, abundance)
+            if args.unitig_kmer_abundance_out:
+                _write_unitig_kmer_abundance(args, store, abundance)
         graph = api.Bigraph.from_sequences(store.arrays(), args.k, args.device)
     else:
         graph, store = api.read_fasta(args.fa_in, args.k, args.device)
@@ -191,7 +213,7 @@ def main(argv=None) -> int:
         if args.verify:
             all_equal &= report(f"{name} ({out or 'spelled in memory'})", r["verify_tigs"], r["verify"])
     if args.query_fa:
-        _query(api, args, store)
+        _query(api, args, store, abundance.kmer_counts if args.query_abundance_out else None)
     return 0 if all_equal else 1
 
 
@@ -219,9 +241,65 @@ def _write_unitig_abundance(args, store, abundance) -> None:
         f.writelines(f"{i}\t{n}\t{a}\t{a / n:.3f}\n" for i, (n, a) in enumerate(zip(kmers, abundance.unitig_sums.tolist())))
 
 
-def _query(api, args, store) -> None:
+def _integer_lines(values, counts, dash=None) -> bytes:
+    """The integers `values`, counts[i] of them on line i, space separated, each line followed by a newline; where `dash` is true the
+    entry is `-`. One vectorised pass: the decimal digits are laid out in a byte matrix and the used ones picked."""
+    import numpy as np
+
+    values = np.asarray(values, np.uint64)
+    counts = np.asarray(counts, np.int64)
+    width = 1
+    while values.size and int(values.max()) >= 10 ** width:
+        width += 1
+    digits = np.zeros((len(values), width + 1), np.uint8)  # right-aligned digits, then the separator
+    rest = values.copy()
+    for j in range(width - 1, -1, -1):
+        digits[:, j] = ord("0") + (rest % np.uint64(10)).astype(np.uint8)
+        rest //= np.uint64(10)
+    used = np.zeros((len(values), width + 1), bool)
+    lengths = np.ones(len(values), np.int64)
+    for j in range(1, width):
+        lengths += values >= np.uint64(10 ** j)
+    used[:, :width] = np.arange(width)[None, :] >= (width - lengths)[:, None]
+    if dash is not None:
+        dash = np.asarray(dash, bool)
+        digits[dash, width - 1] = ord("-")
+        used[dash, :width - 1] = False
+    used[:, width] = True
+    digits[:, width] = ord(" ")
+    ends = np.cumsum(counts)  # the last entry of a line ends it
+    digits[ends[counts > 0] - 1, width] = ord("\n")
+    body = digits[used]
+    empty = np.flatnonzero(counts == 0)  # an empty line is a newline of its own: before the entry that follows it
+    if len(empty) == 0:
+        return body.tobytes()
+    entry_start = np.concatenate([[0], np.cumsum(used.sum(axis=1))])
+    at = entry_start[(ends - counts)[empty]]
+    return np.insert(body, at, ord("\n")).tobytes()
+
+
+def _write_unitig_kmer_abundance(args, store, abundance) -> None:
+    """`--unitig-kmer-abundance-out`: line i holds the abundance of every k-mer of record i of the unitig store, left to right."""
+    import gzip
+
+    import numpy as np
+
+    path = args.unitig_kmer_abundance_out
+    kmers = (np.diff(store.arrays()[1]) - np.uint64(args.k - 1)).astype(np.int64)
+    ends = np.cumsum(kmers)
+    with (gzip.open(path, "wb", compresslevel=args.compression_level) if path.endswith(".gz") else open(path, "wb")) as f:
+        at = 0
+        while at < len(kmers):  # in slices of about 2^24 k-mers
+            end = max(at + 1, int(np.searchsorted(ends, (int(ends[at - 1]) if at else 0) + (1 << 24), side="right")))
+            lo, hi = (int(ends[at - 1]) if at else 0), int(ends[end - 1])
+            f.write(_integer_lines(abundance.kmer_counts[lo:hi], kmers[at:end]))
+            at = end
+
+
+def _query(api, args, store, kmer_counts=None) -> None:
     """`--query-fa`: the input's k-mer set (the unitig store) indexed once; one TSV row and one presence line per query record, and
-    with `--query-locate-out` one row per run of located k-mers."""
+    with `--query-locate-out` one row per run of located k-mers. kmer_counts (`--query-abundance-out`): the index is weighted with
+    them, and one more TSV row, and with `--query-abundance-profile-out` one line of integers, per query record."""
     import contextlib
     import gzip
 
@@ -231,11 +309,18 @@ def _query(api, args, store) -> None:
         return gzip.open(path, "w" + mode, compresslevel=args.compression_level) if path.endswith(".gz") else open(path, "w" + mode)
 
     with contextlib.ExitStack() as stack:
-        index = stack.enter_context(api.KmerIndex(store, args.k, args.device, locate=bool(args.query_locate_out)))
+        if kmer_counts is None:
+            index = stack.enter_context(api.KmerIndex(store, args.k, args.device, locate=bool(args.query_locate_out)))
+        else:
+            index = stack.enter_context(api.KmerIndex(store, args.k, args.device, locate=bool(args.query_locate_out), weights=kmer_counts))
         tsv = stack.enter_context(writer(args.query_out, "t"))
         presence = stack.enter_context(writer(args.query_presence_out, "b")) if args.query_presence_out else None
         located = stack.enter_context(writer(args.query_locate_out, "t")) if args.query_locate_out else None
+        weighed = stack.enter_context(writer(args.query_abundance_out, "t")) if kmer_counts is not None else None
+        profile = stack.enter_context(writer(args.query_abundance_profile_out, "b")) if args.query_abundance_profile_out else None
         tsv.write("record\tlength\tkmers\tvalid\tfound\n")
+        if weighed is not None:
+            weighed.write("record\tkmers\tvalid\tfound\tsum\tmin\tmax\tmean\n")
         if located is not None:
             located.write("record\tqstart\tqend\tstrand\ttarget\ttstart\ttend\tkmers\n")
         for path in args.query_fa:
@@ -257,9 +342,34 @@ def _query(api, args, store) -> None:
                     end = max(at + 1, int(np.searchsorted(r.offsets, int(r.offsets[at]) + (1 << 24), side="right")) - 1)
                     presence.write(r.presence_lines(at, end))
                     at = end
+            if weighed is not None:
+                _write_query_abundance(index, seqs, names, weighed, profile, getattr(r, "valid_bits", None))
             valid, found = int(r.valid.sum()), int(r.found.sum())
             print(f"Querying {path}: {len(names)} records, {int(r.kmers.sum())} k-mers, {valid} valid, {found} found "
                   f"({100.0 * found / valid if valid else 0.0:.2f} %) in {time.perf_counter() - t0:.1f} s", file=sys.stderr)
+
+
+def _write_query_abundance(index, seqs, names, weighed, profile, valid_bits) -> None:
+    """One `--query-abundance-out` row per record of one query file and, if asked for, its `--query-abundance-profile-out` lines.
+    valid_bits: those of the file's query if it made them, else None."""
+    import numpy as np
+
+    ab = index.abundance(seqs, per_window=profile is not None)
+    weighed.writelines(f"{name}\t{n}\t{v}\t{f}\t{s}\t{lo}\t{hi}\t{f'{s / f:.3f}' if f else '-'}\n" for name, n, v, f, s, lo, hi in zip(
+        names, ab.kmers.tolist(), ab.valid.tolist(), ab.found.tolist(), ab.sum.tolist(), ab.min.tolist(), ab.max.tolist()))
+    if profile is None:
+        return
+    bits = valid_bits if valid_bits is not None else index.query(seqs, bits=True).valid_bits  # a clear bit: a character outside ACGT
+    off, kmers = ab.offsets.astype(np.int64), ab.kmers.astype(np.int64)
+    at = 0
+    while at < len(names):  # in slices of about 2^24 bases, as the presence lines
+        end = max(at + 1, int(np.searchsorted(off, int(off[at]) + (1 << 24), side="right")) - 1)
+        n = kmers[at:end]
+        rec = np.repeat(np.arange(at, end), n)
+        pos = off[rec] + (np.arange(len(rec)) - np.repeat(np.cumsum(n) - n, n))  # the global start of every window of the slice
+        invalid = ((bits[pos >> 6] >> (pos & 63).astype(np.uint64)) & np.uint64(1)) == 0
+        profile.write(_integer_lines(ab.per_window[pos], n, invalid))
+        at = end
 
 
 if __name__ == "__main__":

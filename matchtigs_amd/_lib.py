@@ -257,6 +257,11 @@ def load():
         "mtg_abundance_sums_count": (u64, [vp]),
         "mtg_abundance_sums_array": (vp, [vp]),
         "mtg_abundance_sums_free": (None, [vp]),
+        "mtg_compact_unitigs_counted_kmers": (None, [vp, vp, u64, u64, u64, C.c_int, P(vp), P(MtgCompaction), P(MtgAbundance), P(vp), P(vp)]),
+        "mtg_compact_unitigs_counted_kmers_store": (None, [vp, u64, u64, C.c_int, P(vp), P(MtgCompaction), P(MtgAbundance), P(vp), P(vp)]),
+        "mtg_kmer_counts_count": (u64, [vp]),
+        "mtg_kmer_counts_array": (vp, [vp]),
+        "mtg_kmer_counts_free": (None, [vp]),
         "mtg_kmer_index_build": (vp, [vp, vp, u64, u64, C.c_int]),
         "mtg_kmer_index_build_store": (vp, [vp, u64, C.c_int]),
         "mtg_kmer_index_get_info": (None, [vp, P(MtgKmerIndexInfo)]),
@@ -271,6 +276,11 @@ def load():
         "mtg_kmer_runs_arrays": (None, [vp, P(vp), P(vp), P(vp), P(vp), P(vp), P(vp)]),
         "mtg_kmer_runs_free": (None, [vp]),
         "mtg_last_kmer_locate_times": (None, [P(C.c_double)]),
+        "mtg_kmer_index_build_weighted": (vp, [vp, vp, u64, u64, vp, u64, C.c_int, C.c_int]),
+        "mtg_kmer_index_build_weighted_store": (vp, [vp, u64, vp, u64, C.c_int, C.c_int]),
+        "mtg_kmer_index_is_weighted": (C.c_int, [vp]),
+        "mtg_kmer_index_abundance": (None, [vp, vp, vp, u64, vp, vp, vp, vp, vp, vp, vp]),
+        "mtg_last_kmer_abundance_times": (None, [P(C.c_double)]),
         "mtg_read_sequences_named": (None, [C.c_char_p, P(vp), P(vp)]),
         "mtg_unitigs_count": (u64, [vp]),
         "mtg_unitigs_data": (vp, [vp]),

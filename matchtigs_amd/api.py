@@ -916,7 +916,9 @@ def compact_unitigs(seqs_or_store, k: int, device_id: int = 0):
 class Abundance:
     """mtg_abundance plus the per-unitig sums (include/mtg_engine.h): what a counted compaction counted, in exact
     integers. spectrum[c] = distinct k-mers of the input with abundance c (the last bin: 255 or more), taken before the filter;
-    unitig_sums[u] = the sum of abundance over the k-mers of record u of the store; their total is kept_occurrences."""
+    unitig_sums[u] = the sum of abundance over the k-mers of record u of the store; their total is kept_occurrences. kmer_counts
+    (compact_unitigs_counted(..., kmer_counts=True); else None): the abundance of every kept k-mer in window order of
+    the store -- the k-mers of record 0 from left to right, then those of record 1, ... --, the `weights` a KmerIndex of the store takes."""
 
     distinct_all: int
     distinct_kept: int
@@ -924,6 +926,7 @@ class Abundance:
     kept_occurrences: int
     spectrum: np.ndarray     # uint64[256]
     unitig_sums: np.ndarray  # uint64[unitigs]
+    kmer_counts: Optional[np.ndarray] = None  # uint32[distinct_kept]
 
     @property
     def dropped(self) -> int:
@@ -934,29 +937,39 @@ class Abundance:
                 f"max abundance {self.max_abundance}")
 
 
-def compact_unitigs_counted(seqs_or_store, k: int, min_abundance: int, device_id: int = 0):
+def compact_unitigs_counted(seqs_or_store, k: int, min_abundance: int, device_id: int = 0, kmer_counts: bool = False):
     """compact_unitigs over the k-mers whose abundance -- the windows that show them, on either strand -- is at least min_abundance
     (mtg_compact_unitigs_counted) -> (UnitigStore, Compaction, Abundance). Creators and readings are taken over all
-    windows; with min_abundance = 1 store and Compaction equal compact_unitigs'. Compaction.distinct_kmers counts the kept k-mers."""
+    windows; with min_abundance = 1 store and Compaction equal compact_unitigs'. Compaction.distinct_kmers counts the kept k-mers.
+    kmer_counts=True (mtg_compact_unitigs_counted_kmers): Abundance.kmer_counts also holds every kept k-mer's abundance."""
     if min_abundance < 1:
         raise ValueError("min_abundance must be >= 1")
     L = _lib.load()
-    out, sums, stats, ab = C.c_void_p(), C.c_void_p(), _lib.MtgCompaction(), _lib.MtgAbundance()
+    out, sums, counts, stats, ab = C.c_void_p(), C.c_void_p(), C.c_void_p(), _lib.MtgCompaction(), _lib.MtgAbundance()
+    more = (C.byref(counts),) if kmer_counts else ()
     if isinstance(seqs_or_store, UnitigStore):
-        L.mtg_compact_unitigs_counted_store(seqs_or_store.handle, k, min_abundance, device_id, C.byref(out), C.byref(stats), C.byref(ab),
-                                            C.byref(sums))
+        call = L.mtg_compact_unitigs_counted_kmers_store if kmer_counts else L.mtg_compact_unitigs_counted_store
+        call(seqs_or_store.handle, k, min_abundance, device_id, C.byref(out), C.byref(stats), C.byref(ab), C.byref(sums), *more)
     else:
         d, o, n, keep = _sequence_arrays(seqs_or_store)
-        L.mtg_compact_unitigs_counted(d, o, n, k, min_abundance, device_id, C.byref(out), C.byref(stats), C.byref(ab), C.byref(sums))
+        call = L.mtg_compact_unitigs_counted_kmers if kmer_counts else L.mtg_compact_unitigs_counted
+        call(d, o, n, k, min_abundance, device_id, C.byref(out), C.byref(stats), C.byref(ab), C.byref(sums), *more)
         del keep
+    per_kmer = None
     try:
         n = int(L.mtg_abundance_sums_count(sums))
         unitig_sums = (np.ctypeslib.as_array(C.cast(L.mtg_abundance_sums_array(sums), C.POINTER(C.c_uint64)), shape=(n,)).copy()
                        if n else np.zeros(0, np.uint64))
+        if kmer_counts:
+            n = int(L.mtg_kmer_counts_count(counts))
+            per_kmer = (np.ctypeslib.as_array(C.cast(L.mtg_kmer_counts_array(counts), C.POINTER(C.c_uint32)), shape=(n,)).copy()
+                        if n else np.zeros(0, np.uint32))
     finally:
         L.mtg_abundance_sums_free(sums)
+        if kmer_counts:
+            L.mtg_kmer_counts_free(counts)
     abundance = Abundance(int(ab.distinct_all), int(ab.distinct_kept), int(ab.max_abundance), int(ab.kept_occurrences),
-                          np.array(ab.spectrum, dtype=np.uint64), unitig_sums)
+                          np.array(ab.spectrum, dtype=np.uint64), unitig_sums, per_kmer)
     return UnitigStore(out.value), Compaction(**stats.as_dict()), abundance
 
 
@@ -1140,17 +1153,68 @@ class KmerLocateResult:
     runs: np.ndarray
 
 
+@dataclass(frozen=True, eq=False)
+class KmerAbundanceResult:
+    """What KmerIndex.abundance found, per query record: kmers / valid / found as KmerIndex.query gives them (uint64), and over the
+    found windows of the record sum (uint64), min and max (uint32) of the weights of their k-mers -- all 0 where nothing was found.
+    With per_window=True also per_window (uint32, one entry per global base position of the query): the weight of the k-mer of the
+    window that starts there if it is valid and found, else 0."""
+
+    k: int
+    offsets: np.ndarray
+    kmers: np.ndarray
+    valid: np.ndarray
+    found: np.ndarray
+    sum: np.ndarray
+    min: np.ndarray
+    max: np.ndarray
+    per_window: Optional[np.ndarray] = None
+
+    @property
+    def mean(self) -> np.ndarray:
+        """sum / found per record as float64; nan where nothing was found."""
+        out = np.full(len(self.found), np.nan)
+        np.divide(self.sum, self.found, out=out, where=self.found > 0)
+        return out
+
+
+def _window_count(seqs_or_store, k: int) -> int:
+    """The windows of length k inside the records: what a KmerIndex of them reports as info.occurrences."""
+    if isinstance(seqs_or_store, UnitigStore):
+        lengths = np.diff(seqs_or_store.arrays()[1]).astype(np.int64)
+    elif isinstance(seqs_or_store, tuple):
+        lengths = np.diff(np.asarray(seqs_or_store[1], np.uint64)).astype(np.int64)
+    else:
+        lengths = np.array([len(s) for s in seqs_or_store], np.int64)
+    return int(np.maximum(lengths - (k - 1), 0).sum())
+
+
 class KmerIndex:
     """The canonical k-mers of a sequence set, kept on GPU `device_id` and asked which k-mers of other sequences they hold
     (mtg_kmer_index_*). seqs_or_store: UnitigStore, list of str, or (uint8 array, offsets); ACGT of either case only.
     The index holds device memory until close() (or its collection); release_device_memory leaves it intact. locate=True: the index
-    also keeps where its k-mers are (more device memory, see info.device_bytes) and answers locate()."""
+    also keeps where its k-mers are (more device memory, see info.device_bytes) and answers locate(). weights: an
+    array-like of uint32, one per window of the sequences in window order (the k-mers of record 0 from left to right, then record
+    1's, ...; a record shorter than k has none): the index also keeps a weight per k-mer -- that of its first occurrence -- and
+    answers abundance()."""
 
-    def __init__(self, seqs_or_store, k: int, device_id: int = 0, locate: bool = False):
+    def __init__(self, seqs_or_store, k: int, device_id: int = 0, locate: bool = False, weights=None):
         self._L = _lib.load()
         self._h = None
         self.locating = bool(locate)
-        if isinstance(seqs_or_store, UnitigStore):
+        self.weighted = weights is not None
+        if self.weighted:
+            w = np.ascontiguousarray(weights, np.uint32)
+            windows = _window_count(seqs_or_store, k) if k >= 1 else -1
+            if w.ndim != 1 or len(w) != windows:
+                raise ValueError(f"weights must hold one entry per window: {w.shape} for {windows} windows")
+            if isinstance(seqs_or_store, UnitigStore):
+                self._h = self._L.mtg_kmer_index_build_weighted_store(seqs_or_store.handle, k, _ptr(w), len(w), int(self.locating), device_id)
+            else:
+                d, o, n, keep = _sequence_arrays(seqs_or_store)
+                self._h = self._L.mtg_kmer_index_build_weighted(d, o, n, k, _ptr(w), len(w), int(self.locating), device_id)
+                del keep
+        elif isinstance(seqs_or_store, UnitigStore):
             build = self._L.mtg_kmer_index_build_locating_store if locate else self._L.mtg_kmer_index_build_store
             self._h = build(seqs_or_store.handle, k, device_id)
         else:
@@ -1217,6 +1281,23 @@ class KmerIndex:
             self._L.mtg_kmer_runs_free(h)
         return KmerLocateResult(self.info.k, off, kmers, valid, found, runs)
 
+    def abundance(self, seqs_or_store, per_window: bool = False) -> KmerAbundanceResult:
+        """query()'s counts per record plus the sum, the smallest and the largest weight over the record's found windows
+        (KmerAbundanceResult); per_window: also the weight at every window start. Needs an index built with weights."""
+        if not self._h:
+            raise ValueError("the index is closed")
+        if not self.weighted:
+            raise ValueError("abundance() needs an index built with weights")
+        d, o, n, keep = _sequence_arrays(seqs_or_store)
+        off = np.ctypeslib.as_array(C.cast(o, C.POINTER(C.c_uint64)), shape=(n + 1,)).copy()
+        kmers, valid, found, total = (np.zeros(n, np.uint64) for _ in range(4))
+        lo, hi = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        pw = np.zeros(int(off[n]), np.uint32) if per_window else None
+        self._L.mtg_kmer_index_abundance(self._h, d, o, n, _ptr(kmers), _ptr(valid), _ptr(found), _ptr(total), _ptr(lo), _ptr(hi),
+                                         _ptr(pw) if per_window else None)
+        del keep
+        return KmerAbundanceResult(self.info.k, off, kmers, valid, found, total, lo, hi, pw)
+
 
 def last_kmer_query_times() -> dict:
     """Phases of the last KmerIndex build and the last query on this thread, in ms (HIP events around the kernels; uploads by the
@@ -1232,6 +1313,14 @@ def last_kmer_locate_times() -> dict:
     out = (C.c_double * 4)()
     _lib.load().mtg_last_kmer_locate_times(out)
     return dict(zip(("upload_ms", "pack_ms", "probe_ms", "runs_ms"), list(out)))
+
+
+def last_kmer_abundance_times() -> dict:
+    """Phases of the last KmerIndex.abundance on this thread, in ms (HIP events around the kernels; upload and download by the host
+    clock)."""
+    out = (C.c_double * 4)()
+    _lib.load().mtg_last_kmer_abundance_times(out)
+    return dict(zip(("upload_ms", "pack_ms", "probe_ms", "download_ms"), list(out)))
 
 
 def kmer_at(seqs, record: int, pos: int, k: int) -> str:

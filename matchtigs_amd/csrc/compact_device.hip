@@ -49,7 +49,8 @@
 // sums: every kept k-mer writes its count at its place in unitig order (k-mer offset of its unitig + rank), one scan to 64 bits, and
 // differences at the unitig boundaries -- no atomic at all. Fewer than 2^32 windows (32-bit counters cannot wrap).
 // Memory added by a counted call: 4 B per slot (8 w) while inserting, freed with the table; 4 N (kcount) afterwards; 12 N + 8 per
-// unitig for the sums at the end of emit.
+// unitig for the sums at the end of emit. A call that hands out the count of every kept k-mer (mtg_compact_unitigs_counted_kmers,
+// DESIGN.md 20) downloads that array in unitig order, which is the store's window order, instead of freeing it after the scan.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -373,6 +374,7 @@ struct Counted {
     uint64_t m;
     mtg_abundance *abundance;
     std::vector<uint64_t> *sums;
+    std::vector<uint32_t> *kmer_counts;  // null, or: every kept k-mer's abundance in window order of the output store
 };
 
 // counted == nullptr: the plain compaction
@@ -400,6 +402,7 @@ UnitigStore *compact(const char *data, const uint64_t *off, uint64_t n_rec, uint
         if (r.windows >= (1ull << 32)) MTG_DIE("mtg_compact_unitigs_counted: %llu windows; the abundance counters are 32-bit, the limit is 2^32 - 1",
                                                (unsigned long long)r.windows);
         counted->sums->clear();
+        if (counted->kmer_counts) counted->kmer_counts->clear();
     }
     auto finish = [&]() {
         t.total_ms = ms_since(t_total);
@@ -601,8 +604,8 @@ UnitigStore *compact(const char *data, const uint64_t *off, uint64_t n_rec, uint
     spell_kernel<<<hu::grid_for(n_or), hu::EB, 0, st>>>(d_packed, d_kpos, d_pairs, d_wmin, d_char_off, n_or, k, d_out);
     HIP_CHECK(hipGetLastError());
     unsigned long long *d_sums = nullptr;
+    uint32_t *d_ordered = nullptr;
     if (counted) {  // the abundances in unitig order, their 64-bit prefix sums, differences at the unitig boundaries
-        uint32_t *d_ordered = nullptr;
         uint64_t *d_prefix = nullptr;
         hu::device_malloc(&d_ordered, N * 4);
         hu::device_malloc(&d_prefix, N * 8);
@@ -611,7 +614,11 @@ UnitigStore *compact(const char *data, const uint64_t *off, uint64_t n_rec, uint
         hu::scan_u32<uint64_t>(st, d_ordered, N, d_prefix, d_bsum64, d_n_chars);  // (the block sums and the total's word are free again)
         unitig_sums_kernel<<<hu::grid_for(r.unitigs), hu::EB, 0, st>>>(d_out_off, d_prefix, d_n_chars, r.unitigs, k, d_sums);
         HIP_CHECK(hipGetLastError());
-        free_all({d_ordered, d_prefix});
+        hu::device_free(d_prefix);
+        if (!counted->kmer_counts) {
+            hu::device_free(d_ordered);
+            d_ordered = nullptr;
+        }
     }
     ev.mark(5, st);
     HIP_CHECK(hipStreamSynchronize(st));
@@ -625,6 +632,10 @@ UnitigStore *compact(const char *data, const uint64_t *off, uint64_t n_rec, uint
     if (counted) {
         counted->sums->resize(r.unitigs);
         hu::download_sliced(counted->sums->data(), d_sums, r.unitigs * 8, st, device_id);
+        if (counted->kmer_counts) {  // (`ordered` itself: unitig order is the store's window order)
+            counted->kmer_counts->resize(N);
+            hu::download_sliced(counted->kmer_counts->data(), d_ordered, N * 4, st, device_id);
+        }
     }
     t.download_ms = ms_since(t0);
     t.insert_ms = ev.ms(0, 1);
@@ -633,7 +644,7 @@ UnitigStore *compact(const char *data, const uint64_t *off, uint64_t n_rec, uint
     t.rank_ms = ev.ms(3, 4);
     t.emit_ms = ev.ms(4, 5);
     t.rounds = rounds;
-    free_all({d_kpos, na.succ, d_pairs, d_wmin, d_wlen, d_lead_flag, d_lead_chars, d_char_off, d_bsum32, d_bsum64, d_out, d_out_off, d_kcount, d_sums});
+    free_all({d_kpos, na.succ, d_pairs, d_wmin, d_wlen, d_lead_flag, d_lead_chars, d_char_off, d_bsum32, d_bsum64, d_out, d_out_off, d_kcount, d_sums, d_ordered});
     uint64_t arena[4];
     device_arena_stats(device_id, arena);
     t.peak_arena_bytes = arena[2];
@@ -657,9 +668,9 @@ UnitigStore *device_compact_unitigs(const char *data, const uint64_t *off, uint6
 
 UnitigStore *device_compact_unitigs_counted(const char *data, const uint64_t *off, uint64_t n_rec, uint64_t k, uint64_t min_abundance, int device_id,
                                             mtg_compaction *stats_out, mtg_abundance *abundance_out, std::vector<uint64_t> *unitig_sums,
-                                            CompactTimes *times) {
+                                            CompactTimes *times, std::vector<uint32_t> *kmer_counts) {
     if (!unitig_sums) MTG_DIE("mtg_compact_unitigs_counted: null argument");
-    const Counted c{min_abundance, abundance_out, unitig_sums};
+    const Counted c{min_abundance, abundance_out, unitig_sums, kmer_counts};
     return compact(data, off, n_rec, k, device_id, stats_out, times, &c);
 }
 

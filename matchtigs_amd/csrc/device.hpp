@@ -140,9 +140,16 @@ struct KmerQueryTimes {
 };
 struct KmerIndex;
 // locating: the index also keeps the smallest position of every class, the packed bases and the record offsets (device_kmer_index_locate)
+// weights: one weight per window of the sequences, in window order; the index also keeps the weight of every class --
+// that of its smallest window start -- and answers device_kmer_index_abundance. n must equal the windows.
+struct KmerWeights {
+    const uint32_t *w;
+    uint64_t n;
+};
 KmerIndex *device_kmer_index_build(const char *seq, const uint64_t *off, uint64_t n, uint64_t k, int device_id, bool locating,
-                                   KmerQueryTimes *times);
+                                   KmerQueryTimes *times, const KmerWeights *weights = nullptr);
 bool device_kmer_index_is_locating(const KmerIndex *ix);
+bool device_kmer_index_is_weighted(const KmerIndex *ix);
 void device_kmer_index_info(const KmerIndex *ix, mtg_kmer_index_info *out);
 void device_kmer_index_query(const KmerIndex *ix, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid,
                              uint64_t *found, uint64_t *present_bits, uint64_t *valid_bits, KmerQueryTimes *times);
@@ -158,6 +165,14 @@ struct KmerLocateTimes {
 };
 void device_kmer_index_locate(const KmerIndex *ix, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid,
                               uint64_t *found, KmerRuns *runs, KmerLocateTimes *times);
+// The query plus, per record over its found windows, the sum, the smallest and the largest weight of their classes (all 0 where
+// nothing is found) and, if per_window is given ([off[n]]), the weight at every found window's global start position, 0 elsewhere.
+// times: host wall clock of the upload and the download, HIP-event time of the kernels.
+struct KmerAbundanceTimes {
+    double upload_ms = 0, pack_ms = 0, probe_ms = 0, download_ms = 0;
+};
+void device_kmer_index_abundance(const KmerIndex *ix, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid,
+                                 uint64_t *found, uint64_t *sum, uint32_t *min, uint32_t *max, uint32_t *per_window, KmerAbundanceTimes *times);
 // compact_device.hip: the maximal unitigs of the k-mer set of arbitrary sequences (the file's header and DESIGN.md 16 state the
 // contract), as an ordinary sequence store. times: host wall clock of upload, download and the whole call, HIP-event time of the
 // kernel phases, the pointer-jumping rounds, the bytes the kernels must move at the least, the arena's peak of live bytes.
@@ -170,9 +185,12 @@ UnitigStore *device_compact_unitigs(const char *data, const uint64_t *off, uint6
                                     CompactTimes *times);
 // ... of the k-mers whose abundance reaches min_abundance: the statistics of the counting and, per unitig in the
 // store's order, the sum of its k-mers' abundances. The spectrum sweep is booked under ids_ms, the sums under emit_ms.
+// kmer_counts, if given: every kept k-mer's abundance in window order of the store -- entry (windows of the earlier
+// unitigs) + j belongs to the k-mer at offset j of unitig u --, the array the sums are scanned from; its download is booked under
+// download_ms.
 UnitigStore *device_compact_unitigs_counted(const char *data, const uint64_t *off, uint64_t n_rec, uint64_t k, uint64_t min_abundance, int device_id,
                                             mtg_compaction *stats_out, mtg_abundance *abundance_out, std::vector<uint64_t> *unitig_sums,
-                                            CompactTimes *times);
+                                            CompactTimes *times, std::vector<uint32_t> *kmer_counts = nullptr);
 // fasta_in.cpp: read_fasta_records without an alphabet rule and without case folding (the queries of the k-mer index), plus the
 // record names (the header text behind `>` up to the first white space) as a second store
 UnitigStore *read_fasta_records_named(const char *path, UnitigStore **names_out);

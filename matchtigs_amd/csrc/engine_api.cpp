@@ -716,6 +716,32 @@ void mtg_last_kmer_locate_times(double out[4]) {
     const KmerLocateTimes &t = g_last_kmer_locate;
     out[0] = t.upload_ms; out[1] = t.pack_ms; out[2] = t.probe_ms; out[3] = t.runs_ms;
 }
+// ---- ... and how heavy they are ----
+static thread_local KmerAbundanceTimes g_last_kmer_abundance;
+mtg_kmer_index *mtg_kmer_index_build_weighted(const char *seq, const uint64_t *off, uint64_t n, uint64_t k, const uint32_t *weights,
+                                              uint64_t n_weights, int locating, int device_id) {
+    const KmerWeights w{weights, n_weights};
+    return new mtg_kmer_index{device_kmer_index_build(seq, off, n, k, device_id, locating != 0, &g_last_kmer_query, &w)};
+}
+mtg_kmer_index *mtg_kmer_index_build_weighted_store(const mtg_unitigs *store, uint64_t k, const uint32_t *weights, uint64_t n_weights,
+                                                    int locating, int device_id) {
+    if (!store) MTG_DIE("mtg_kmer_index_build_weighted_store: null argument");
+    const UnitigStore &s = *store->s;
+    return mtg_kmer_index_build_weighted(s.data.data(), s.off.data(), s.off.size() - 1, k, weights, n_weights, locating, device_id);
+}
+int mtg_kmer_index_is_weighted(const mtg_kmer_index *ix) {
+    if (!ix) MTG_DIE("mtg_kmer_index_is_weighted: null argument");
+    return device_kmer_index_is_weighted(ix->ix) ? 1 : 0;
+}
+void mtg_kmer_index_abundance(const mtg_kmer_index *ix, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid,
+                              uint64_t *found, uint64_t *sum, uint32_t *min, uint32_t *max, uint32_t *per_window) {
+    if (!ix) MTG_DIE("mtg_kmer_index_abundance: null argument");
+    device_kmer_index_abundance(ix->ix, seq, off, n, kmers, valid, found, sum, min, max, per_window, &g_last_kmer_abundance);
+}
+void mtg_last_kmer_abundance_times(double out[4]) {
+    const KmerAbundanceTimes &t = g_last_kmer_abundance;
+    out[0] = t.upload_ms; out[1] = t.pack_ms; out[2] = t.probe_ms; out[3] = t.download_ms;
+}
 void mtg_last_kmer_query_times(double out[6]) {
     const KmerQueryTimes &t = g_last_kmer_query;
     out[0] = t.build_upload_ms; out[1] = t.build_pack_ms; out[2] = t.build_insert_ms;
@@ -760,6 +786,34 @@ const uint64_t *mtg_abundance_sums_array(const mtg_abundance_sums *sums) {
     return sums->v.data();
 }
 void mtg_abundance_sums_free(mtg_abundance_sums *sums) { delete sums; }
+struct mtg_kmer_counts { std::vector<uint32_t> v; };
+void mtg_compact_unitigs_counted_kmers(const char *data, const uint64_t *offsets, uint64_t n, uint64_t k, uint64_t min_abundance, int device_id,
+                                       mtg_unitigs **out, mtg_compaction *stats, mtg_abundance *abundance, mtg_abundance_sums **sums,
+                                       mtg_kmer_counts **kmer_counts) {
+    if (!out || !sums || !kmer_counts) MTG_DIE("mtg_compact_unitigs_counted_kmers: null argument");
+    if (min_abundance == 0) MTG_DIE("mtg_compact_unitigs_counted_kmers: min_abundance must be >= 1");
+    mtg_abundance_sums *s = new mtg_abundance_sums();
+    mtg_kmer_counts *c = new mtg_kmer_counts();
+    *out = new mtg_unitigs{device_compact_unitigs_counted(data, offsets, n, k, min_abundance, device_id, stats, abundance, &s->v, &g_last_compact, &c->v)};
+    *sums = s;
+    *kmer_counts = c;
+}
+void mtg_compact_unitigs_counted_kmers_store(const mtg_unitigs *in, uint64_t k, uint64_t min_abundance, int device_id, mtg_unitigs **out,
+                                             mtg_compaction *stats, mtg_abundance *abundance, mtg_abundance_sums **sums,
+                                             mtg_kmer_counts **kmer_counts) {
+    if (!in) MTG_DIE("mtg_compact_unitigs_counted_kmers_store: null argument");
+    mtg_compact_unitigs_counted_kmers(in->s->data.data(), in->s->off.data(), in->s->off.size() - 1, k, min_abundance, device_id, out, stats, abundance,
+                                      sums, kmer_counts);
+}
+uint64_t mtg_kmer_counts_count(const mtg_kmer_counts *counts) {
+    if (!counts) MTG_DIE("mtg_kmer_counts_count: null argument");
+    return counts->v.size();
+}
+const uint32_t *mtg_kmer_counts_array(const mtg_kmer_counts *counts) {
+    if (!counts) MTG_DIE("mtg_kmer_counts_array: null argument");
+    return counts->v.data();
+}
+void mtg_kmer_counts_free(mtg_kmer_counts *counts) { delete counts; }
 void mtg_last_compact_times(double out[12]) {
     const CompactTimes &t = g_last_compact;
     out[0] = t.upload_ms; out[1] = t.pack_ms; out[2] = t.insert_ms; out[3] = t.ids_ms; out[4] = t.nodes_ms; out[5] = t.rank_ms;

@@ -46,6 +46,18 @@
 //   runs      run_flag_kernel marks the windows that do not continue their predecessor, hu::scan_u32 ranks them,
 //             run_mark_kernel notes the first and last position of every run, run_emit_kernel writes the fields of each
 // Only the runs and the counts are downloaded. A call takes 8 + 4 + 8 B per query base beside the query's store.
+//
+// Abundance (a WEIGHTED index only, mtg_kmer_index_build_weighted). The caller gives one uint32 per window of the indexed
+// sequences, in window order; weight(class) = the weight of the class's smallest window start, loc of DESIGN.md 18 -- a function of
+// the input alone. The build runs the locating insert and then weight_gather_kernel, one sweep over the slots: weight[s] =
+// weights[ordinal(where[s])], 4 B per slot = 8 B per window more. An index that is not also locating then gives where[], the offsets
+// and, for k <= 31, the packed bases back to the arena. An abundance call answers like a query without bit arrays and adds per record
+// the sum (64-bit), the smallest and the largest weight over its found windows, and optionally the weight at every window start:
+//   pack      as the query
+//   probe     abundance_kernel: the query's walk (probe_run); per found window weight[slot], folded into three registers per
+//             (thread, record) that leave by one atomicAdd, one atomicMin and one atomicMax when the record changes, never per window.
+//             per_window: a thread is the only writer of its RUN positions, zeros included
+// A call takes 8 + 4 + 4 B per record and, with per_window, 4 B per query base beside the query's store.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -123,7 +135,7 @@ __device__ __forceinline__ uint64_t past_last_bad(const unsigned long long *bad,
 
 // The walk of both query kernels over the RUN window starts from p0 on: validity from the bad mask, the read-only lookup of the valid
 // windows, valid / found per record into counts ([2 n_rec], valid then found). vbits / pbits: bit q - p0 set for a valid / a found
-// window at q. hit(q, slot) is called for every found window with the slot of its class.
+// window at q. hit(q, r, slot) is called for every found window with its record and the slot of its class.
 template <bool WIDE, typename Hit>
 __device__ __forceinline__ void probe_run(const IndexArgs &a, const unsigned long long *bad, uint64_t p0, uint64_t n_bases, uint64_t n_rec,
                                           unsigned long long *counts, unsigned long long &vbits, unsigned long long &pbits, Hit hit) {
@@ -151,7 +163,7 @@ __device__ __forceinline__ void probe_run(const IndexArgs &a, const unsigned lon
         if (slot != a.slots) {
             n_found++;
             pbits |= bit;
-            hit(q, slot);
+            hit(q, r, slot);
         }
     });
     flush();
@@ -165,7 +177,7 @@ __global__ __launch_bounds__(hu::EB) void query_kernel(IndexArgs a, const unsign
     const uint64_t gid = hu::gid(), p0 = gid * RUN;
     if (p0 >= n_bases) return;
     unsigned long long vbits = 0, pbits = 0;
-    probe_run<WIDE>(a, bad, p0, n_bases, n_rec, counts, vbits, pbits, [](uint64_t, uint64_t) {});
+    probe_run<WIDE>(a, bad, p0, n_bases, n_rec, counts, vbits, pbits, [](uint64_t, uint64_t, uint64_t) {});
     if (valid_bits) valid_bits[gid] = vbits;
     if (present_bits) present_bits[gid] = pbits;
 }
@@ -191,7 +203,7 @@ __global__ __launch_bounds__(hu::EB) void locate_kernel(IndexArgs a, const unsig
     const uint64_t p0 = hu::gid() * RUN;
     if (p0 >= n_bases) return;
     unsigned long long vbits = 0, pbits = 0;
-    probe_run<WIDE>(a, bad, p0, n_bases, n_rec, counts, vbits, pbits, [&](uint64_t q, uint64_t slot) {
+    probe_run<WIDE>(a, bad, p0, n_bases, n_rec, counts, vbits, pbits, [&](uint64_t q, uint64_t, uint64_t slot) {
         const uint64_t t = where[slot];
         hit[q] = (t << 1) | (same_forward(a.packed, q, a.index_packed, t, a.k) ? 0ull : 1ull);
     });
@@ -269,6 +281,62 @@ __global__ __launch_bounds__(hu::EB) void run_emit_kernel(RunArgs a, uint64_t n_
     strand[i] = (unsigned char)(hs & 1);
 }
 
+// ---- abundance ----
+// weight[s] = the caller's weight of the window where[s], the smallest window start of the slot's class; 0 for an empty slot.
+// win_off[r] = the windows of the records before r, so the window at t of record r has the ordinal win_off[r] + t - off[r].
+__global__ __launch_bounds__(hu::EB) void weight_gather_kernel(const unsigned long long *table, const unsigned long long *where,
+                                                                const unsigned long long *off, uint64_t n_rec, const unsigned long long *win_off,
+                                                                const uint32_t *weights, uint64_t n_weights, uint64_t slots, uint32_t *weight,
+                                                                unsigned int *err) {
+    const uint64_t s = hu::gid();
+    if (s >= slots) return;
+    uint32_t w = 0;
+    if (table[s] != EMPTY_SLOT) {
+        const uint64_t t = where[s], r = record_of(off, n_rec, t), i = win_off[r] + (t - off[r]);
+        if (i < n_weights) w = weights[i];
+        else atomicOr(err, 2u);  // (every occupied slot has a window's position: never)
+    }
+    weight[s] = w;
+}
+
+// query_kernel's walk; per found window the weight of its class. counts: [3 n_rec] valid, found, then the sum of the weights;
+// minmax: [2 n_rec] the smallest (all ones before) and the largest (0 before) weight; per_window: [n_bases] or null.
+template <bool WIDE>
+__global__ __launch_bounds__(hu::EB) void abundance_kernel(IndexArgs a, const unsigned long long *bad, uint64_t n_bases, uint64_t n_rec,
+                                                           unsigned long long *counts, const uint32_t *weight, uint32_t *minmax,
+                                                           uint32_t *per_window) {
+    const uint64_t p0 = hu::gid() * RUN;
+    if (p0 >= n_bases) return;
+    unsigned long long vbits = 0, pbits = 0;
+    uint64_t rec = 0, sum = 0, next_p = p0;  // next_p: the first position of the run that per_window has not been told yet
+    uint32_t lo = ~0u, hi = 0, hits = 0;     // (of the record `rec`; at most RUN hits)
+    auto flush = [&]() {
+        if (!hits) return;
+        atomicAdd(&counts[2 * n_rec + rec], (unsigned long long)sum);
+        atomicMin(&minmax[rec], lo);
+        atomicMax(&minmax[n_rec + rec], hi);
+        sum = 0; lo = ~0u; hi = 0; hits = 0;
+    };
+    probe_run<WIDE>(a, bad, p0, n_bases, n_rec, counts, vbits, pbits, [&](uint64_t q, uint64_t r, uint64_t slot) {
+        if (r != rec) {
+            flush();
+            rec = r;
+        }
+        const uint32_t w = weight[slot];
+        sum += w;
+        lo = w < lo ? w : lo;
+        hi = w > hi ? w : hi;
+        hits++;
+        if (per_window) {
+            for (; next_p < q; next_p++) per_window[next_p] = 0;
+            per_window[next_p++] = w;
+        }
+    });
+    flush();
+    if (per_window)
+        for (const uint64_t end = p0 + RUN < n_bases ? p0 + RUN : n_bases; next_p < end; next_p++) per_window[next_p] = 0;
+}
+
 // offsets of one set: start at 0, do not decrease; returns its windows
 uint64_t check_offsets(const char *fn, const char *data, const uint64_t *off, uint64_t n, uint64_t k) {
     if (!off || (n && off[n] && !data)) MTG_DIE("%s: null argument", fn);
@@ -292,10 +360,11 @@ struct KmerIndex {
     bool locating = false;
     unsigned long long *where = nullptr;  // locating: [info.slots] the smallest window start of the slot's class
     unsigned long long *off = nullptr;    // locating: [info.records + 1]
+    uint32_t *weight = nullptr;           // weighted: [info.slots] the weight of the slot's class
 };
 
 KmerIndex *device_kmer_index_build(const char *seq, const uint64_t *off, uint64_t n, uint64_t k, int device_id, bool locating,
-                                   KmerQueryTimes *times) {
+                                   KmerQueryTimes *times, const KmerWeights *weights) {
     if (k < 1) MTG_DIE("mtg_kmer_index_build: k must be >= 1");
     if (k > 0xFFFFFFFFull) MTG_DIE("mtg_kmer_index_build: k too large");
     KmerIndex *ix = new KmerIndex();
@@ -306,6 +375,9 @@ KmerIndex *device_kmer_index_build(const char *seq, const uint64_t *off, uint64_
     info.characters = off[n];
     if (info.characters >= POS_LIMIT)
         MTG_DIE("mtg_kmer_index_build: %llu bases; the limit is 2^40 - 2", (unsigned long long)info.characters);
+    if (weights && weights->n != info.occurrences)
+        MTG_DIE("mtg_kmer_index_build_weighted: %llu weights for %llu windows", (unsigned long long)weights->n, (unsigned long long)info.occurrences);
+    if (weights && weights->n && !weights->w) MTG_DIE("mtg_kmer_index_build_weighted: null argument");
     if (device_id < 0 || device_count() <= device_id) MTG_DIE("no HIP device %d for the k-mer index (there is no CPU path)", device_id);
     HIP_CHECK(hipSetDevice(device_id));
     ix->device_id = device_id;
@@ -319,7 +391,8 @@ KmerIndex *device_kmer_index_build(const char *seq, const uint64_t *off, uint64_
     hu::device_malloc(&ix->table, info.slots * 8);
     HIP_CHECK(hipMemsetAsync(ix->table, 0xFF, info.slots * 8, st));
     ix->locating = locating;
-    if (locating) {
+    const bool positions = locating || weights;  // the insert notes the smallest window start of every class
+    if (positions) {
         hu::device_malloc(&ix->where, info.slots * 8);
         HIP_CHECK(hipMemsetAsync(ix->where, 0xFF, info.slots * 8, st));
     }
@@ -328,7 +401,7 @@ KmerIndex *device_kmer_index_build(const char *seq, const uint64_t *off, uint64_
         a.packed = a.index_packed = store.packed; a.off = store.off; a.table = ix->table; a.slots = info.slots;
         kw::window_args_set_k(a, k);
         const unsigned grid = hu::grid_for((store.n_bases + RUN - 1) / RUN);
-        if (locating) {
+        if (positions) {
             if (wide) index_insert_kernel<true, true><<<grid, hu::EB, 0, st>>>(a, store.n_bases, n, store.small.err(), ix->where);
             else index_insert_kernel<false, true><<<grid, hu::EB, 0, st>>>(a, store.n_bases, n, store.small.err(), ix->where);
         } else {
@@ -339,13 +412,33 @@ KmerIndex *device_kmer_index_build(const char *seq, const uint64_t *off, uint64_
         index_count_kernel<<<(unsigned)std::min<uint64_t>(hu::grid_for(info.slots / 2), 8192), hu::EB, 0, st>>>(ix->table, info.slots, store.small.d + 2);
         HIP_CHECK(hipGetLastError());
     }
+    if (weights) {  // (also for an index without windows: its zeroed table is still probed)
+        hu::device_malloc(&ix->weight, info.slots * 4);
+        if (info.occurrences) {
+            std::vector<unsigned long long> win_off(n + 1, 0);
+            for (uint64_t r = 0; r < n; r++) win_off[r + 1] = win_off[r] + (off[r + 1] - off[r] >= k ? off[r + 1] - off[r] - k + 1 : 0);
+            unsigned long long *d_win_off = nullptr;
+            uint32_t *d_weights = nullptr;
+            hu::device_malloc(&d_win_off, (n + 1) * 8);
+            hu::device_malloc(&d_weights, weights->n * 4);
+            hu::upload_sliced(d_win_off, win_off.data(), (n + 1) * 8, st, device_id);
+            hu::upload_sliced(d_weights, weights->w, weights->n * 4, st, device_id);
+            weight_gather_kernel<<<hu::grid_for(info.slots), hu::EB, 0, st>>>(ix->table, ix->where, store.off, n, d_win_off, d_weights, weights->n,
+                                                                             info.slots, ix->weight, store.small.err());
+            HIP_CHECK(hipGetLastError());
+            hu::device_free(d_win_off);  // (synchronises: the gather is done)
+            hu::device_free(d_weights);
+        } else {
+            HIP_CHECK(hipMemsetAsync(ix->weight, 0, info.slots * 4, st));
+        }
+    }
     ev.mark(1, st);
     store.small.read(st, "k-mer index");
     info.distinct = store.small.h[2];
     if (times) {
         times->build_upload_ms = store.upload_ms;
         times->build_pack_ms = store.pack_ms;
-        times->build_insert_ms = ev.ms(0, 1);  // (with the table's fill and the count)
+        times->build_insert_ms = ev.ms(0, 1);  // (with the table's fill and the count; weighted: the weights' upload and the gather)
     }
     info.device_bytes = info.slots * 8;
     if (locating || (wide && info.occurrences)) {
@@ -355,11 +448,16 @@ KmerIndex *device_kmer_index_build(const char *seq, const uint64_t *off, uint64_
     if (locating) {
         ix->off = store.take_off();
         info.device_bytes += info.slots * 8 + (n + 1) * 8;
+    } else if (ix->where) {  // weighted only: the positions have done their work
+        hu::device_free(ix->where);
+        ix->where = nullptr;
     }
+    if (weights) info.device_bytes += info.slots * 4;
     return ix;
 }
 
 bool device_kmer_index_is_locating(const KmerIndex *ix) { return ix->locating; }
+bool device_kmer_index_is_weighted(const KmerIndex *ix) { return ix->weight != nullptr; }
 
 void device_kmer_index_info(const KmerIndex *ix, mtg_kmer_index_info *out) { *out = ix->info; }
 
@@ -369,6 +467,7 @@ void device_kmer_index_free(KmerIndex *ix) {
     hu::device_free_on(ix->device_id, ix->table);
     hu::device_free_on(ix->device_id, ix->where);
     hu::device_free_on(ix->device_id, ix->off);
+    hu::device_free_on(ix->device_id, ix->weight);
     delete ix;
 }
 
@@ -418,6 +517,65 @@ void device_kmer_index_query(const KmerIndex *ix, const char *seq, const uint64_
     }
     hu::device_free(d_counts);
     hu::device_free(d_bits);
+}
+
+void device_kmer_index_abundance(const KmerIndex *ix, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid,
+                                 uint64_t *found, uint64_t *sum, uint32_t *min, uint32_t *max, uint32_t *per_window, KmerAbundanceTimes *times) {
+    if (!ix->weight) MTG_DIE("mtg_kmer_index_abundance: the index keeps no weights (build it with mtg_kmer_index_build_weighted)");
+    const uint64_t k = ix->info.k;
+    (void)check_offsets("mtg_kmer_index_abundance", seq, off, n, k);
+    if (n && (!kmers || !valid || !found || !sum || !min || !max)) MTG_DIE("mtg_kmer_index_abundance: null argument");
+    const uint64_t n_bases = off[n];
+    if (n_bases >= POS_LIMIT) MTG_DIE("mtg_kmer_index_abundance: %llu bases; the limit is 2^40 - 2", (unsigned long long)n_bases);
+    for (uint64_t r = 0; r < n; r++) {
+        const uint64_t len = off[r + 1] - off[r];
+        kmers[r] = len >= k ? len - k + 1 : 0;
+        valid[r] = found[r] = sum[r] = 0;
+        min[r] = max[r] = 0;
+    }
+    if (times) *times = KmerAbundanceTimes();
+    if (n_bases == 0) return;  // nothing to look at
+    HIP_CHECK(hipSetDevice(ix->device_id));
+    hipStream_t st = nullptr;
+    MaskedSeqStore store(seq, off, n, st, ix->device_id);
+    unsigned long long *d_counts = nullptr;  // valid, found, sum
+    uint32_t *d_minmax = nullptr, *d_per_window = nullptr;
+    hu::device_malloc(&d_counts, 3 * n * 8);
+    hu::device_malloc(&d_minmax, 2 * n * 4);
+    if (per_window) hu::device_malloc(&d_per_window, n_bases * 4);
+    PhaseEvents<2> ev;
+    ev.mark(0, st);
+    HIP_CHECK(hipMemsetAsync(d_counts, 0, 3 * n * 8, st));
+    HIP_CHECK(hipMemsetAsync(d_minmax, 0xFF, n * 4, st));
+    HIP_CHECK(hipMemsetAsync(d_minmax + n, 0, n * 4, st));
+    IndexArgs a{};
+    a.packed = store.packed; a.off = store.off; a.index_packed = ix->packed; a.table = ix->table; a.slots = ix->info.slots;
+    kw::window_args_set_k(a, k);
+    const unsigned grid = hu::grid_for((n_bases + RUN - 1) / RUN);  // (one thread per run: every word of per_window is written)
+    if (k >= 32) abundance_kernel<true><<<grid, hu::EB, 0, st>>>(a, store.bad, n_bases, n, d_counts, ix->weight, d_minmax, d_per_window);
+    else abundance_kernel<false><<<grid, hu::EB, 0, st>>>(a, store.bad, n_bases, n, d_counts, ix->weight, d_minmax, d_per_window);
+    HIP_CHECK(hipGetLastError());
+    ev.mark(1, st);
+    HIP_CHECK(hipStreamSynchronize(st));
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_CHECK(hipMemcpyAsync(valid, d_counts, n * 8, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(found, d_counts + n, n * 8, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(sum, d_counts + 2 * n, n * 8, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(min, d_minmax, n * 4, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(max, d_minmax + n, n * 4, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    if (per_window) hu::download_sliced(per_window, d_per_window, n_bases * 4, st, ix->device_id);
+    for (uint64_t r = 0; r < n; r++)
+        if (!found[r]) min[r] = 0;  // (nothing lowered the all-ones word)
+    if (times) {
+        times->upload_ms = store.upload_ms;
+        times->pack_ms = store.pack_ms;
+        times->probe_ms = ev.ms(0, 1);
+        times->download_ms = ms_since(t0);
+    }
+    hu::device_free(d_counts);
+    hu::device_free(d_minmax);
+    hu::device_free(d_per_window);
 }
 
 void device_kmer_index_locate(const KmerIndex *ix, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid,
