@@ -646,6 +646,40 @@ void mtg_last_kmer_abundance_times(double out[4]);
  * the queries of a k-mer index. *names_out = the record names as a second store with the same accessors: the header text behind `>`
  * up to the first white space. */
 void mtg_read_sequences_named(const char *path, mtg_unitigs **seqs_out, mtg_unitigs **names_out);
+/* FASTQ reads, read on GPU `device_id` (fastq_device.hip; there is no CPU path). Strict four-line FASTQ, optionally
+ * `.gz`: the text is a sequence of lines ended by "\n", one "\r" before it belongs to the line end, a missing final "\n" is
+ * tolerated, and so are empty lines behind the last record. Record r is lines 4r .. 4r+3: the first begins with `@`, the third with
+ * `+` (what follows it is ignored), the second (bases) and the fourth (qualities, bytes '!' .. '~') have the same length, which may be
+ * 0. The kind of a line is its index mod 4 and nothing else. Base j of a record is good when it is one of ACGTacgt and
+ * quality[j] - 33 >= min_base_quality (0 .. 93; 0 keeps every ACGT base).
+ * mtg_read_fastq_split: the maximal runs of good bases of every record, upper-cased, in file order, as the records of an ordinary
+ * store -- mtg_read_sequences_split's rule with "not good" for "not ACGT"; with min_base_quality = 0 store and pieces_cut are what
+ * that reader gives for the same reads written as FASTA. mtg_read_fastq_named: the records whole with their characters as they are,
+ * a base whose quality is below the threshold replaced by `N`, plus the names (the header text behind `@` up to the first white
+ * space) -- mtg_read_sequences_named for FASTQ; there pieces = records and bases_kept = bases.
+ * Both return 0 and the store(s), or non-zero when the FILE is malformed: no store is allocated and err (may be NULL) holds
+ * "<path>: record <0-based r> (line <1-based l>): <reason>" for the smallest record that breaks a rule and, in it, the first rule
+ * broken in the order above; a line count that is no multiple of 4 is reported for the incomplete record with the file's last line.
+ * The process goes on. Null arguments, an unreadable path and min_base_quality > 93 abort as in the other readers. */
+typedef struct mtg_fastq_stats {
+    uint64_t records, bases;  /* records read; the characters of their sequence lines */
+    uint64_t non_acgt_bases;  /* bases outside ACGTacgt */
+    uint64_t masked_bases;    /* ACGT bases whose quality is below the threshold */
+    uint64_t pieces;          /* records of the store */
+    uint64_t bases_kept;      /* characters of the store */
+    uint64_t pieces_cut;      /* runs of bases that are not good, counted as mtg_read_sequences_split counts its runs */
+    uint64_t tile_bytes;      /* text bytes per block of the scan kernels (for tests that place data across tile edges) */
+} mtg_fastq_stats;
+int mtg_read_fastq_split(const char *path, uint64_t min_base_quality, int device_id, mtg_unitigs **store_out, mtg_fastq_stats *stats,
+                         char *err, uint64_t err_capacity);
+int mtg_read_fastq_named(const char *path, uint64_t min_base_quality, int device_id, mtg_unitigs **seqs_out, mtg_unitigs **names_out,
+                         mtg_fastq_stats *stats, char *err, uint64_t err_capacity);
+/* What the first byte that is no line end says about a sequence file (optionally `.gz`): 0 = there is none, 1 = FASTA (`>`),
+ * 2 = FASTQ (`@`), -1 = anything else. The file name plays no part. Aborts on an unreadable path. */
+int mtg_sequence_file_format(const char *path);
+/* Of the last mtg_read_fastq_* on this thread, in ms: {read + inflate (host clock), upload (host clock), lines + check, pieces -- HIP
+ * events around the kernels --, download with the name slicing (host clock), the whole call (host clock)}. */
+void mtg_last_fastq_times(double out[6]);
 uint64_t mtg_unitigs_count(const mtg_unitigs *u);
 const char *mtg_unitigs_data(const mtg_unitigs *u);        /* concatenated ASCII sequences */
 const uint64_t *mtg_unitigs_offsets(const mtg_unitigs *u); /* count + 1 offsets into data */

@@ -22,6 +22,10 @@ of every unitig.
 index is weighted with the abundance of every kept k-mer, and a TSV row per query record gives the k-mers found and the sum, the
 smallest, the largest and the mean of their abundances; `--query-abundance-profile-out` adds one abundance per k-mer of every
 query record, and `--unitig-kmer-abundance-out` writes the abundance of every k-mer of every unitig.
+`--seq-in` and `--query-fa` also take FASTQ reads (optionally `.gz`), told from FASTA by the first character of the content and read
+on the GPU; `--seq-in` may be given several times (R1 / R2; FASTA and FASTQ may be mixed), the records of the files
+follow each other in the order given. `--min-base-quality Q` treats a base of a `--seq-in` read whose Phred quality is below Q like
+an `N`, so that it never reaches a k-mer; `--query-min-base-quality Q` does the same to the `--query-fa` reads.
 """
 from __future__ import annotations
 
@@ -35,8 +39,14 @@ def main(argv=None) -> int:
     ap.add_argument("--bcalm-in", help="bcalm2/GGCAT unitig fasta (optionally .gz); requires -k (bin.rs:76-83)")
     ap.add_argument("--gfa-in", help="(not served by this engine)")
     ap.add_argument("--fa-in", help="plain unitig fasta (optionally .gz), graph from (k-1)-mer overlaps on the GPU; requires -k (bin.rs:71-75)")
-    ap.add_argument("--seq-in", help="any sequences as fasta (optionally .gz; non-ACGT runs split records): their k-mer set is compacted "
-                                     "into maximal unitigs on the GPU, then as --fa-in; requires -k (not in the reference)")
+    ap.add_argument("--seq-in", action="append", metavar="PATH",
+                    help="any sequences as fasta or fastq (optionally .gz; non-ACGT runs split records): their k-mer set is compacted "
+                         "into maximal unitigs on the GPU, then as --fa-in; repeatable; requires -k (not in the reference)")
+    ap.add_argument("--min-base-quality", type=int, metavar="Q",
+                    help="with fastq --seq-in files: a base whose Phred quality is below Q (0..93) splits a read like an N "
+                         "(not in the reference)")
+    ap.add_argument("--query-min-base-quality", type=int, metavar="Q",
+                    help="with fastq --query-fa files: a base whose Phred quality is below Q (0..93) is replaced by N")
     ap.add_argument("--unitigs-fa-out", help="write the input's unitigs as fasta (.gz => gzip): with --seq-in, the GPU compactor's output "
                                              "(not in the reference)")
     ap.add_argument("-k", type=int, help="k-mer size used to build the de Bruijn graph (bin.rs:139-141)")
@@ -119,17 +129,57 @@ def main(argv=None) -> int:
             ap.error(f"{flag} needs --seq-in")
     if args.min_abundance is not None and args.min_abundance < 1:
         ap.error("--min-abundance must be >= 1")
+    for flag, value in (("--min-base-quality", args.min_base_quality), ("--query-min-base-quality", args.query_min_base_quality)):
+        if value is not None and not 0 <= value <= 93:
+            ap.error(f"{flag} must be in 0..93")
     if not (args.kmer_spectrum_out or args.unitig_abundance_out or args.unitig_kmer_abundance_out or args.query_fa or args.greedytigs_fa_out or args.eulertigs_fa_out or args.greedytigs_gfa_out or args.eulertigs_gfa_out
             or args.greedytigs_duplication_bitvector_out or args.matchtigs_fa_out or args.matchtigs_gfa_out or args.verify_fa or args.unitigs_fa_out):
         ap.error("nothing to do: give --greedytigs-fa-out / --greedytigs-gfa-out and/or --eulertigs-fa-out / --eulertigs-gfa-out")
 
     from . import api
 
+    # FASTQ is told from FASTA by the content; the quality flags need a file they can apply to
+    fastq = {path for path in (args.seq_in or []) + (args.query_fa or []) if api.sequence_file_format(path) == 2}
+    if args.min_base_quality is not None and not fastq:
+        ap.error("--min-base-quality needs a fastq file among --seq-in / --query-fa")
+    if args.query_min_base_quality is not None and not fastq.intersection(args.query_fa or []):
+        ap.error("--query-min-base-quality needs a fastq file among --query-fa")
+    try:
+        return _run(api, args, fastq)
+    except api.FastqFormatError as e:  # an error of the input: the message names file, record, line and reason
+        print(e, file=sys.stderr)
+        return 2
+
+
+def _read_seq_in(api, args, fastq):
+    """The `--seq-in` files as one sequence set: the store of a single file as it is, else (data, offsets) of the files' stores one
+    after the other, and the non-ACGT / low-quality runs cut."""
+    import numpy as np
+
+    stores = []
+    for path in args.seq_in:
+        if path in fastq:
+            st, stats = api.read_fastq(path, args.min_base_quality or 0, args.device)
+            print(f"Read {path}: {stats.describe()}", file=sys.stderr)
+        else:
+            st = api.read_sequences(path, split_non_acgt=True)
+        stores.append(st)
+    cut = sum(st.pieces_cut for st in stores)
+    if len(stores) == 1:
+        return stores[0], cut
+    arrays = [st.arrays() for st in stores]
+    base = np.cumsum([0] + [len(d) for d, _ in arrays]).astype(np.uint64)
+    data = np.concatenate([d for d, _ in arrays])
+    off = np.concatenate([o[:-1] + b for (_, o), b in zip(arrays, base)] + [base[-1:]])
+    return (data, off), cut
+
+
+def _run(api, args, fastq) -> int:
     t0 = time.perf_counter()
     if args.bcalm_in is not None:
         graph, store = api.read_bcalm2(args.bcalm_in, args.k)
     elif args.seq_in is not None:  # sequences -> unitigs (GPU compaction) -> graph (the --fa-in join on the same store)
-        seqs = api.read_sequences(args.seq_in, split_non_acgt=True)
+        seqs, pieces_cut = _read_seq_in(api, args, fastq)
         abundance = None
         per_kmer = bool(args.query_abundance_out or args.unitig_kmer_abundance_out)  # (DESIGN.md 20)
         if args.min_abundance is None and not (args.kmer_spectrum_out or args.unitig_abundance_out or per_kmer):
@@ -156,7 +206,7 @@ def main(argv=None) -> int:
     if args.seq_in is not None:
         loaded += f" (compacted from {compaction.describe()}; "
         loaded += f"{abundance.describe()}; " if abundance is not None else ""
-        loaded += f"{seqs.pieces_cut} non-ACGT runs cut)"
+        loaded += f"{pieces_cut} non-ACGT runs cut)"
     print(loaded, file=sys.stderr)
     # what the tigs are verified against: the input as given -- on the --seq-in route the sequences, so that the check covers the compaction
     truth = seqs if args.seq_in is not None else store
@@ -213,7 +263,7 @@ def main(argv=None) -> int:
         if args.verify:
             all_equal &= report(f"{name} ({out or 'spelled in memory'})", r["verify_tigs"], r["verify"])
     if args.query_fa:
-        _query(api, args, store, abundance.kmer_counts if args.query_abundance_out else None)
+        _query(api, args, store, abundance.kmer_counts if args.query_abundance_out else None, fastq)
     return 0 if all_equal else 1
 
 
@@ -296,7 +346,7 @@ def _write_unitig_kmer_abundance(args, store, abundance) -> None:
             at = end
 
 
-def _query(api, args, store, kmer_counts=None) -> None:
+def _query(api, args, store, kmer_counts=None, fastq=()) -> None:
     """`--query-fa`: the input's k-mer set (the unitig store) indexed once; one TSV row and one presence line per query record, and
     with `--query-locate-out` one row per run of located k-mers. kmer_counts (`--query-abundance-out`): the index is weighted with
     them, and one more TSV row, and with `--query-abundance-profile-out` one line of integers, per query record."""
@@ -325,7 +375,10 @@ def _query(api, args, store, kmer_counts=None) -> None:
             located.write("record\tqstart\tqend\tstrand\ttarget\ttstart\ttend\tkmers\n")
         for path in args.query_fa:
             t0 = time.perf_counter()
-            seqs, names = api.read_sequences_named(path)
+            if path in fastq:
+                seqs, names, _ = api.read_fastq(path, args.query_min_base_quality or 0, args.device, named=True)
+            else:
+                seqs, names = api.read_sequences_named(path)
             if located is not None:  # the counts of the TSV come from the same call
                 loc = index.locate(seqs)
                 runs, span = loc.runs, loc.runs["kmers"] + np.uint64(args.k - 1)

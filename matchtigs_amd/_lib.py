@@ -103,6 +103,16 @@ class MtgAbundance(C.Structure):
         ("spectrum", C.c_uint64 * 256)]
 
 
+class MtgFastqStats(C.Structure):
+    """mtg_fastq_stats (include/mtg_engine.h)."""
+
+    _fields_ = [(n, C.c_uint64) for n in (
+        "records", "bases", "non_acgt_bases", "masked_bases", "pieces", "bases_kept", "pieces_cut", "tile_bytes")]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class MtgKmerIndexInfo(C.Structure):
     """mtg_kmer_index_info (include/mtg_engine.h)."""
 
@@ -282,6 +292,10 @@ def load():
         "mtg_kmer_index_abundance": (None, [vp, vp, vp, u64, vp, vp, vp, vp, vp, vp, vp]),
         "mtg_last_kmer_abundance_times": (None, [P(C.c_double)]),
         "mtg_read_sequences_named": (None, [C.c_char_p, P(vp), P(vp)]),
+        "mtg_read_fastq_split": (C.c_int, [C.c_char_p, u64, C.c_int, P(vp), P(MtgFastqStats), C.c_char_p, u64]),
+        "mtg_read_fastq_named": (C.c_int, [C.c_char_p, u64, C.c_int, P(vp), P(vp), P(MtgFastqStats), C.c_char_p, u64]),
+        "mtg_sequence_file_format": (C.c_int, [C.c_char_p]),
+        "mtg_last_fastq_times": (None, [P(C.c_double)]),
         "mtg_unitigs_count": (u64, [vp]),
         "mtg_unitigs_data": (vp, [vp]),
         "mtg_unitigs_offsets": (vp, [vp]),

@@ -1078,6 +1078,72 @@ def read_sequences_named(path: str):
 
 
 @dataclass(frozen=True)
+class FastqStats:
+    """mtg_fastq_stats (include/mtg_engine.h): what one read_fastq call met, in exact integers. bases = the characters of the sequence
+    lines; pieces / bases_kept = records and characters of the store; pieces_cut = the runs of bases that are not good (outside ACGT
+    or below the quality threshold), counted as read_sequences(split_non_acgt=True) counts its runs; tile_bytes = the text bytes one
+    block of the scan kernels takes."""
+
+    records: int
+    bases: int
+    non_acgt_bases: int
+    masked_bases: int
+    pieces: int
+    bases_kept: int
+    pieces_cut: int
+    tile_bytes: int
+
+    def describe(self) -> str:
+        return (f"{self.records} records, {self.bases} bases, {self.non_acgt_bases} non-ACGT bases, {self.masked_bases} bases masked by "
+                f"quality -> {self.pieces} pieces of {self.bases_kept} bases")
+
+
+class FastqFormatError(ValueError):
+    """A FASTQ file breaks a rule of the format (read_fastq): an error of the input, the process goes on."""
+
+
+def sequence_file_format(path: str) -> int:
+    """What the first byte that is no line end says about a sequence file (optionally .gz): 0 = there is none, 1 = FASTA (`>`),
+    2 = FASTQ (`@`), -1 = anything else (mtg_sequence_file_format). The file name plays no part."""
+    return int(_lib.load().mtg_sequence_file_format(str(path).encode()))
+
+
+def read_fastq(path: str, min_base_quality: int = 0, device_id: int = 0, named: bool = False):
+    """Strict four-line FASTQ (optionally .gz), read on GPU `device_id` (mtg_read_fastq_split / _named). A base is good
+    when it is one of ACGTacgt and its Phred quality (byte - 33) is at least min_base_quality (0 .. 93). named=False ->
+    (UnitigStore, FastqStats): the maximal runs of good bases, upper-cased, in file order -- with min_base_quality = 0 exactly
+    read_sequences(twin.fa, split_non_acgt=True); the store's `pieces_cut` is set as there. named=True -> (UnitigStore, names,
+    FastqStats): the records whole, characters as they are, a base below the threshold replaced by `N`, as read_sequences_named.
+    A malformed file raises ValueError naming the path, the first offending record (0-based), its line (1-based) and the reason."""
+    if not 0 <= int(min_base_quality) <= 93:
+        raise ValueError("min_base_quality must be in 0 .. 93")
+    L = _lib.load()
+    st, names, stats = C.c_void_p(), C.c_void_p(), _lib.MtgFastqStats()
+    err = C.create_string_buffer(4096)
+    if named:
+        status = L.mtg_read_fastq_named(str(path).encode(), int(min_base_quality), device_id, C.byref(st), C.byref(names), C.byref(stats),
+                                        err, len(err))
+    else:
+        status = L.mtg_read_fastq_split(str(path).encode(), int(min_base_quality), device_id, C.byref(st), C.byref(stats), err, len(err))
+    if status != 0:
+        raise FastqFormatError(err.value.decode(errors="replace"))
+    fs = FastqStats(**stats.as_dict())
+    store = UnitigStore(st.value)
+    if named:
+        return store, UnitigStore(names.value).sequences(), fs
+    store.pieces_cut = fs.pieces_cut
+    return store, fs
+
+
+def last_fastq_times() -> dict:
+    """Phases of the last read_fastq on this thread, in ms: read + inflate, upload, download and total by the host clock, lines (with
+    the structural check) and pieces by HIP events around the kernels."""
+    out = (C.c_double * 6)()
+    _lib.load().mtg_last_fastq_times(out)
+    return dict(zip(("read_ms", "upload_ms", "lines_ms", "pieces_ms", "download_ms", "total_ms"), list(out)))
+
+
+@dataclass(frozen=True)
 class KmerIndexInfo:
     """mtg_kmer_index_info (include/mtg_engine.h)."""
 

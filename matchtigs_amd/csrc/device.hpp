@@ -196,6 +196,14 @@ UnitigStore *device_compact_unitigs_counted(const char *data, const uint64_t *of
 UnitigStore *read_fasta_records_named(const char *path, UnitigStore **names_out);
 // fasta_in.cpp: read_fasta_records where a run of characters outside ACGT ends a piece instead of aborting; empty pieces are dropped
 UnitigStore *read_fasta_records_split(const char *path, uint64_t *pieces_cut);
+// fastq_device.hip: FASTQ reads read on the GPU (the file's header and DESIGN.md 21 state the contract). named: the records whole
+// plus their names, else the pieces of good bases. Returns 0, or 1 with the message of a malformed file in err and no store.
+// times: host wall clock of read + inflate, upload, download and the whole call, HIP-event time of the kernel phases.
+struct FastqTimes {
+    double read_ms = 0, upload_ms = 0, lines_ms = 0, pieces_ms = 0, download_ms = 0, total_ms = 0;
+};
+int device_read_fastq(const char *path, uint64_t min_base_quality, int device_id, bool named, UnitigStore **seqs_out, UnitigStore **names_out,
+                      mtg_fastq_stats *stats_out, FastqTimes *times, char *err, uint64_t err_capacity);
 void device_candidates_to_host(Device *d, void *stream, std::vector<uint64_t> &cand_start,
                                std::vector<uint32_t> &cand_count, std::vector<uint64_t> &pool);
 

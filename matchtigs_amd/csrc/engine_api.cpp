@@ -23,6 +23,7 @@
 #include "../../include/mtg_policy.h"
 #include "device.hpp"
 #include "euler_lean.hpp"
+#include "fastq_text.hpp"
 #include "host_graph.hpp"
 #include "hugebuf.hpp"
 #include "parallel.hpp"
@@ -823,6 +824,34 @@ void mtg_last_compact_times(double out[12]) {
 void mtg_read_sequences_split(const char *path, mtg_unitigs **store_out, uint64_t *pieces_cut) {
     if (!path || !store_out) MTG_DIE("mtg_read_sequences_split: null argument");
     *store_out = new mtg_unitigs{read_fasta_records_split(path, pieces_cut)};
+}
+static thread_local FastqTimes g_last_fastq;
+int mtg_read_fastq_split(const char *path, uint64_t min_base_quality, int device_id, mtg_unitigs **store_out, mtg_fastq_stats *stats, char *err,
+                         uint64_t err_capacity) {
+    if (!path || !store_out) MTG_DIE("mtg_read_fastq_split: null argument");
+    UnitigStore *st = nullptr;
+    const int status = device_read_fastq(path, min_base_quality, device_id, false, &st, nullptr, stats, &g_last_fastq, err, err_capacity);
+    if (status == 0) *store_out = new mtg_unitigs{st};
+    return status;
+}
+int mtg_read_fastq_named(const char *path, uint64_t min_base_quality, int device_id, mtg_unitigs **seqs_out, mtg_unitigs **names_out,
+                         mtg_fastq_stats *stats, char *err, uint64_t err_capacity) {
+    if (!path || !seqs_out || !names_out) MTG_DIE("mtg_read_fastq_named: null argument");
+    UnitigStore *st = nullptr, *names = nullptr;
+    const int status = device_read_fastq(path, min_base_quality, device_id, true, &st, &names, stats, &g_last_fastq, err, err_capacity);
+    if (status == 0) {
+        *seqs_out = new mtg_unitigs{st};
+        *names_out = new mtg_unitigs{names};
+    }
+    return status;
+}
+int mtg_sequence_file_format(const char *path) {
+    if (!path) MTG_DIE("mtg_sequence_file_format: null argument");
+    return fq::format_of_file(path);
+}
+void mtg_last_fastq_times(double out[6]) {
+    const FastqTimes &t = g_last_fastq;
+    out[0] = t.read_ms; out[1] = t.upload_ms; out[2] = t.lines_ms; out[3] = t.pieces_ms; out[4] = t.download_ms; out[5] = t.total_ms;
 }
 uint64_t mtg_unitigs_count(const mtg_unitigs *u) { return u->s->off.size() - 1; }
 const char *mtg_unitigs_data(const mtg_unitigs *u) { return u->s->data.data(); }
