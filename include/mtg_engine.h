@@ -642,6 +642,61 @@ void mtg_kmer_index_abundance(const mtg_kmer_index *ix, const char *seq, const u
 /* Of the last mtg_kmer_index_abundance on this thread, in ms: {upload (host clock), pack, probe -- HIP events around the kernels --,
  * download (host clock)}. */
 void mtg_last_kmer_abundance_times(double out[4]);
+/* WHICH INPUTS carry a k-mer. Every input record r has a colour c(r), 0 <= c(r) < n_colors, 1 <= n_colors <= 64 (a
+ * file, a sample, a haplotype). colors(x), for a canonical k-mer x, = the 64-bit mask with bit c(r) for every window of record r
+ * whose k-mer is x or rc(x): both strands count, repeats add nothing, and the mask -- like the abundance that decides membership in
+ * S_m -- is taken over ALL windows. mtg_compact_unitigs_colored is mtg_compact_unitigs_counted_kmers at the same min_abundance,
+ * output for output and byte for byte, plus: *kmer_colors, one mask per k-mer of S_m indexed like *kmer_counts (window order of
+ * *out), and *color_stats over the kept k-mers: per_color[c] = those whose mask has bit c; shared[i * 64 + j] = those with bits i and j
+ * (symmetric, the diagonal equals per_color; entries with i or j >= n_colors are 0); occupancy[j] = those carried by exactly j colours
+ * (occupancy[0] = 0, occupancy[n_colors] the core, occupancy[1] the private ones, the sum distinct_kept). A colour no record has, or
+ * whose records are all shorter than k, gives a zero row. Exact integers, a function of the input, min_abundance and the colouring
+ * alone. record_colors: n entries; an entry >= n_colors, or n_colors outside 1 .. 64, aborts. */
+typedef struct mtg_color_stats {
+    uint64_t n_colors;
+    uint64_t per_color[64];
+    uint64_t occupancy[65];
+    uint64_t shared[64 * 64];
+} mtg_color_stats;
+typedef struct mtg_kmer_colors mtg_kmer_colors;
+void mtg_compact_unitigs_colored(const char *data, const uint64_t *offsets, uint64_t n, uint64_t k, uint64_t min_abundance,
+                                 const uint8_t *record_colors, uint64_t n_colors, int device_id, mtg_unitigs **out, mtg_compaction *stats,
+                                 mtg_abundance *abundance, mtg_abundance_sums **sums, mtg_kmer_counts **kmer_counts,
+                                 mtg_kmer_colors **kmer_colors, /* mtg_kmer_colors_free */
+                                 mtg_color_stats *color_stats);
+void mtg_compact_unitigs_colored_store(const mtg_unitigs *in, uint64_t k, uint64_t min_abundance, const uint8_t *record_colors,
+                                       uint64_t n_colors, int device_id, mtg_unitigs **out, mtg_compaction *stats, mtg_abundance *abundance,
+                                       mtg_abundance_sums **sums, mtg_kmer_counts **kmer_counts, mtg_kmer_colors **kmer_colors,
+                                       mtg_color_stats *color_stats);
+uint64_t mtg_kmer_colors_count(const mtg_kmer_colors *colors);        /* the store's k-mers */
+const uint64_t *mtg_kmer_colors_array(const mtg_kmer_colors *colors); /* count entries; valid until mtg_kmer_colors_free */
+void mtg_kmer_colors_free(mtg_kmer_colors *colors);
+/* An index with any of the two payloads. weights (NULL: none) as mtg_kmer_index_build_weighted takes them. colors (NULL: none): one
+ * 64-bit mask per window of the sequences, in window order; n_color_words must equal info.occurrences, 1 <= n_colors <= 64 and no
+ * mask may have a bit from n_colors on, else the call aborts. color(class) = colors[ordinal(loc)], loc as for the weights: the mask
+ * of the class's first occurrence. A coloured index keeps 8 B per slot more. Query, locate and abundance answer exactly as on an
+ * index without colours. A payload whose sequences have no window is an array of no entries: any non-NULL pointer and a count of 0. */
+mtg_kmer_index *mtg_kmer_index_build_annotated(const char *seq, const uint64_t *off, uint64_t n, uint64_t k, const uint32_t *weights,
+                                               uint64_t n_weights, const uint64_t *colors, uint64_t n_color_words, uint64_t n_colors,
+                                               int locating, int device_id);
+mtg_kmer_index *mtg_kmer_index_build_annotated_store(const mtg_unitigs *store, uint64_t k, const uint32_t *weights, uint64_t n_weights,
+                                                     const uint64_t *colors, uint64_t n_color_words, uint64_t n_colors, int locating,
+                                                     int device_id);
+int mtg_kmer_index_is_colored(const mtg_kmer_index *ix);
+uint64_t mtg_kmer_index_n_colors(const mtg_kmer_index *ix); /* 0: not coloured */
+/* The query of mtg_kmer_index_query (kmers / valid / found as there) plus per_color (n * n_colors entries, row-major): [r * n_colors +
+ * c] = the found windows of record r whose class's mask has bit c. A mask of 0 is a mask: such a
+ * window counts as found and touches no column. per_window (may be NULL; off[n] entries): [p] = the mask of the class of the window
+ * that starts at p if that window is valid and found, else 0 -- the positions of mtg_kmer_index_abundance's per_window. Exact
+ * integers, a function of the inputs alone; the index is not changed. A record has fewer than 2^32 windows. An empty query returns
+ * at once. Aborts if the index is not coloured. */
+void mtg_kmer_index_colors(const mtg_kmer_index *ix, const char *seq, const uint64_t *off, uint64_t n,
+                           uint64_t *kmers, uint64_t *valid, uint64_t *found, /* [n] each */
+                           uint32_t *per_color,                               /* [n * n_colors] */
+                           uint64_t *per_window);                             /* nullable, [off[n]] */
+/* In ms: {the colour statistics kernel of the last mtg_compact_unitigs_colored on this thread (HIP events); of the last
+ * mtg_kmer_index_colors: upload (host clock), pack, probe -- HIP events around the kernels --, download (host clock)}. */
+void mtg_last_kmer_color_times(double out[5]);
 /* mtg_read_sequences without an alphabet rule: every byte of a sequence line is kept as it is (`N`, IUPAC codes, lower case), for
  * the queries of a k-mer index. *names_out = the record names as a second store with the same accessors: the header text behind `>`
  * up to the first white space. */

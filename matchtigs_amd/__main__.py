@@ -26,12 +26,19 @@ query record, and `--unitig-kmer-abundance-out` writes the abundance of every k-
 on the GPU; `--seq-in` may be given several times (R1 / R2; FASTA and FASTQ may be mixed), the records of the files
 follow each other in the order given. `--min-base-quality Q` treats a base of a `--seq-in` read whose Phred quality is below Q like
 an `N`, so that it never reaches a k-mer; `--query-min-base-quality Q` does the same to the `--query-fa` reads.
+With several `--seq-in` files every file is a COLOUR (a sample, a haplotype; at most 64), in the order given, and every k-mer knows which
+files show it, on either strand: `--color-matrix-out` writes how many k-mers each file has and each pair of files
+shares, `--unitig-colors-out` the colours along every unitig as runs `count:hexmask` (bit i = file i), and `--query-colors-out` (with
+`--query-fa`) per query record how many of its k-mers each file carries.
 """
 from __future__ import annotations
 
 import argparse
 import sys
 import time
+
+
+MAX_COLORS = 64  # the colours of one call: the bits of a mask (DESIGN.md 22)
 
 
 def main(argv=None) -> int:
@@ -97,7 +104,21 @@ def main(argv=None) -> int:
                          "non-ACGT character (.gz => gzip); needs --query-abundance-out")
     ap.add_argument("--unitig-kmer-abundance-out", metavar="PATH",
                     help="with --seq-in: per record of --unitigs-fa-out a line with the abundance of each of its k-mers (.gz => gzip)")
+    ap.add_argument("--color-matrix-out", metavar="PATH",
+                    help="with --seq-in, each file one colour (at most 64): TSV (.gz => gzip) color, kmers, then one column per file: "
+                         "the k-mers of file i and those it shares with every file; a closing row #occupancy: the k-mers carried by "
+                         "exactly 1, 2, ... files (not in the reference)")
+    ap.add_argument("--unitig-colors-out", metavar="PATH",
+                    help="with --seq-in: per record of --unitigs-fa-out a line of runs count:hexmask over its k-mers, left to right; "
+                         "bit i of a mask = --seq-in file i (.gz => gzip)")
+    ap.add_argument("--query-colors-out", metavar="PATH",
+                    help="with --seq-in, --query-fa and --query-out: TSV (.gz => gzip) with one row per query record: record, kmers, "
+                         "valid, found, then per --seq-in file the found k-mers that file carries")
     args = ap.parse_args(argv)
+
+    colored = bool(args.color_matrix_out or args.unitig_colors_out or args.query_colors_out)
+    if colored and args.seq_in is not None and len(args.seq_in) > MAX_COLORS:
+        ap.error(f"{len(args.seq_in)} --seq-in files: at most {MAX_COLORS} files can be told apart as colours")
 
     n_inputs = sum(x is not None for x in (args.bcalm_in, args.gfa_in, args.fa_in, args.seq_in))
     if n_inputs == 0:  # bin.rs:855-858
@@ -123,8 +144,11 @@ def main(argv=None) -> int:
         ap.error("--query-abundance-out needs --seq-in, --query-fa and --query-out")
     if args.query_abundance_profile_out and not args.query_abundance_out:
         ap.error("--query-abundance-profile-out needs --query-abundance-out")
+    if args.query_colors_out and not (args.seq_in and args.query_fa and args.query_out):
+        ap.error("--query-colors-out needs --seq-in, --query-fa and --query-out")
     for flag, value in (("--min-abundance", args.min_abundance), ("--kmer-spectrum-out", args.kmer_spectrum_out),
-                        ("--unitig-abundance-out", args.unitig_abundance_out), ("--unitig-kmer-abundance-out", args.unitig_kmer_abundance_out)):
+                        ("--unitig-abundance-out", args.unitig_abundance_out), ("--unitig-kmer-abundance-out", args.unitig_kmer_abundance_out),
+                        ("--color-matrix-out", args.color_matrix_out), ("--unitig-colors-out", args.unitig_colors_out)):
         if value is not None and args.seq_in is None:
             ap.error(f"{flag} needs --seq-in")
     if args.min_abundance is not None and args.min_abundance < 1:
@@ -132,7 +156,7 @@ def main(argv=None) -> int:
     for flag, value in (("--min-base-quality", args.min_base_quality), ("--query-min-base-quality", args.query_min_base_quality)):
         if value is not None and not 0 <= value <= 93:
             ap.error(f"{flag} must be in 0..93")
-    if not (args.kmer_spectrum_out or args.unitig_abundance_out or args.unitig_kmer_abundance_out or args.query_fa or args.greedytigs_fa_out or args.eulertigs_fa_out or args.greedytigs_gfa_out or args.eulertigs_gfa_out
+    if not (args.color_matrix_out or args.unitig_colors_out or args.kmer_spectrum_out or args.unitig_abundance_out or args.unitig_kmer_abundance_out or args.query_fa or args.greedytigs_fa_out or args.eulertigs_fa_out or args.greedytigs_gfa_out or args.eulertigs_gfa_out
             or args.greedytigs_duplication_bitvector_out or args.matchtigs_fa_out or args.matchtigs_gfa_out or args.verify_fa or args.unitigs_fa_out):
         ap.error("nothing to do: give --greedytigs-fa-out / --greedytigs-gfa-out and/or --eulertigs-fa-out / --eulertigs-gfa-out")
 
@@ -151,9 +175,9 @@ def main(argv=None) -> int:
         return 2
 
 
-def _read_seq_in(api, args, fastq):
+def _read_seq_in(api, args, fastq, record_colors=None):
     """The `--seq-in` files as one sequence set: the store of a single file as it is, else (data, offsets) of the files' stores one
-    after the other, and the non-ACGT / low-quality runs cut."""
+    after the other, and the non-ACGT / low-quality runs cut. record_colors: a list that takes, per record, the number of its file."""
     import numpy as np
 
     stores = []
@@ -164,6 +188,8 @@ def _read_seq_in(api, args, fastq):
         else:
             st = api.read_sequences(path, split_non_acgt=True)
         stores.append(st)
+    if record_colors is not None:  # every piece of a file has the file's colour
+        record_colors.extend(np.repeat(np.arange(len(stores)), [len(st) for st in stores]).tolist())
     cut = sum(st.pieces_cut for st in stores)
     if len(stores) == 1:
         return stores[0], cut
@@ -179,14 +205,20 @@ def _run(api, args, fastq) -> int:
     if args.bcalm_in is not None:
         graph, store = api.read_bcalm2(args.bcalm_in, args.k)
     elif args.seq_in is not None:  # sequences -> unitigs (GPU compaction) -> graph (the --fa-in join on the same store)
-        seqs, pieces_cut = _read_seq_in(api, args, fastq)
-        abundance = None
+        colored = bool(args.color_matrix_out or args.unitig_colors_out or args.query_colors_out)  # 
+        record_colors = [] if colored else None
+        seqs, pieces_cut = _read_seq_in(api, args, fastq, record_colors)
+        abundance = colors = None
         per_kmer = bool(args.query_abundance_out or args.unitig_kmer_abundance_out)  # 
-        if args.min_abundance is None and not (args.kmer_spectrum_out or args.unitig_abundance_out or per_kmer):
+        counted = not (args.min_abundance is None and not (args.kmer_spectrum_out or args.unitig_abundance_out or per_kmer))
+        if not counted and not colored:
             store, compaction = api.compact_unitigs(seqs, args.k, args.device)
         else:  # the counted compaction; an output flag alone counts without filtering
             min_abundance = args.min_abundance or 1
-            if per_kmer:
+            if colored:  # (the counted call that hands out the counts, plus the colours)
+                store, compaction, abundance, colors = api.compact_unitigs_colored(seqs, args.k, record_colors, len(args.seq_in), min_abundance,
+                                                                                   args.device)
+            elif per_kmer:
                 store, compaction, abundance = api.compact_unitigs_counted(seqs, args.k, min_abundance, args.device, kmer_counts=True)
             else:
                 store, compaction, abundance = api.compact_unitigs_counted(seqs, args.k, min_abundance, args.device)
@@ -199,13 +231,17 @@ def _run(api, args, fastq) -> int:
                 _write_unitig_abundance(args, store, abundance)
             if args.unitig_kmer_abundance_out:
                 _write_unitig_kmer_abundance(args, store, abundance)
+            if args.color_matrix_out:
+                _write_color_matrix(args, colors)
+            if args.unitig_colors_out:
+                _write_unitig_colors(args, store, colors)
         graph = api.Bigraph.from_sequences(store.arrays(), args.k, args.device)
     else:
         graph, store = api.read_fasta(args.fa_in, args.k, args.device)
     loaded = f"Loaded {len(store)} unitigs: {graph.node_count()} nodes, {graph.edge_count()} edges in {time.perf_counter() - t0:.1f}s"
     if args.seq_in is not None:
         loaded += f" (compacted from {compaction.describe()}; "
-        loaded += f"{abundance.describe()}; " if abundance is not None else ""
+        loaded += f"{abundance.describe()}; " if abundance is not None and counted else ""
         loaded += f"{pieces_cut} non-ACGT runs cut)"
     print(loaded, file=sys.stderr)
     # what the tigs are verified against: the input as given -- on the --seq-in route the sequences, so that the check covers the compaction
@@ -263,7 +299,8 @@ def _run(api, args, fastq) -> int:
         if args.verify:
             all_equal &= report(f"{name} ({out or 'spelled in memory'})", r["verify_tigs"], r["verify"])
     if args.query_fa:
-        _query(api, args, store, abundance.kmer_counts if args.query_abundance_out else None, fastq)
+        _query(api, args, store, abundance.kmer_counts if args.query_abundance_out else None, fastq,
+               colors if args.query_colors_out else None)
     return 0 if all_equal else 1
 
 
@@ -346,10 +383,87 @@ def _write_unitig_kmer_abundance(args, store, abundance) -> None:
             at = end
 
 
-def _query(api, args, store, kmer_counts=None, fastq=()) -> None:
+def _hex_runs(masks, counts) -> bytes:
+    """Line i: the runs of equal masks among its counts[i] (>= 1) masks, left to right, as `length:hexmask`, space separated. One
+    vectorised pass: the digits of both numbers are laid out in a byte matrix and the used ones picked."""
+    import numpy as np
+
+    masks = np.asarray(masks, np.uint64)
+    ends = np.cumsum(np.asarray(counts, np.int64))
+    first = np.ones(len(masks), bool)  # the first mask of a run: that of a line, or one that differs from the mask before it
+    first[1:] = masks[1:] != masks[:-1]
+    first[ends[:-1]] = True
+    starts = np.flatnonzero(first)
+    lengths = np.diff(np.append(starts, len(masks))).astype(np.uint64)
+    run_masks = masks[starts]
+    width = 1
+    while lengths.size and int(lengths.max()) >= 10 ** width:
+        width += 1
+    cells = np.zeros((len(starts), width + 1 + 16 + 1), np.uint8)  # decimal digits, `:`, hex digits, the separator
+    used = np.zeros(cells.shape, bool)
+    rest, n_digits = lengths.copy(), np.ones(len(starts), np.int64)
+    for j in range(width - 1, -1, -1):
+        cells[:, j] = ord("0") + (rest % np.uint64(10)).astype(np.uint8)
+        rest //= np.uint64(10)
+    for j in range(1, width):
+        n_digits += lengths >= np.uint64(10 ** j)
+    used[:, :width] = np.arange(width)[None, :] >= (width - n_digits)[:, None]
+    cells[:, width] = ord(":")
+    hex_digits, n_hex = np.frombuffer(b"0123456789abcdef", np.uint8), np.ones(len(starts), np.int64)
+    for j in range(16):
+        cells[:, width + 1 + j] = hex_digits[((run_masks >> np.uint64(4 * (15 - j))) & np.uint64(15)).astype(np.int64)]
+    for j in range(1, 16):
+        n_hex += run_masks >= np.uint64(16 ** j)
+    used[:, width + 1:width + 17] = np.arange(16)[None, :] >= (16 - n_hex)[:, None]
+    used[:, width] = used[:, -1] = True
+    cells[:, -1] = ord(" ")
+    cells[np.searchsorted(starts, ends, side="left") - 1, -1] = ord("\n")  # the last run of a line ends it
+    return cells[used].tobytes()
+
+
+def _write_unitig_colors(args, store, colors) -> None:
+    """`--unitig-colors-out`: line i describes the k-mers of record i of the unitig store, left to right, as runs of equal masks."""
+    import gzip
+
+    import numpy as np
+
+    path = args.unitig_colors_out
+    kmers = (np.diff(store.arrays()[1]) - np.uint64(args.k - 1)).astype(np.int64)
+    ends = np.cumsum(kmers)
+    with (gzip.open(path, "wb", compresslevel=args.compression_level) if path.endswith(".gz") else open(path, "wb")) as f:
+        at = 0
+        while at < len(kmers):  # in slices of about 2^24 k-mers
+            end = max(at + 1, int(np.searchsorted(ends, (int(ends[at - 1]) if at else 0) + (1 << 24), side="right")))
+            lo, hi = (int(ends[at - 1]) if at else 0), int(ends[end - 1])
+            f.write(_hex_runs(colors.kmer_colors[lo:hi], kmers[at:end]))
+            at = end
+
+
+def _write_color_matrix(args, colors) -> None:
+    """`--color-matrix-out`: row i = file i, its k-mers and those it shares with every file; the closing row: the k-mers carried by
+    exactly 1 .. C files. One stderr line sums it up."""
+    import numpy as np
+
+    names, n = args.seq_in, colors.n_colors
+    with _open_text(args, args.color_matrix_out) as f:
+        f.write("\t".join(["color", "kmers"] + names) + "\n")
+        f.writelines("\t".join([names[i], str(int(colors.per_color[i]))] + [str(x) for x in colors.shared[i].tolist()]) + "\n" for i in range(n))
+        f.write("\t".join(["#occupancy"] + [str(x) for x in colors.occupancy[1:n + 1].tolist()]) + "\n")
+    line = f"Colours: {int(colors.occupancy.sum())} k-mers kept in {n} colours, {colors.core} core, {colors.private} private"
+    jac = colors.jaccard()
+    pairs = [(jac[i, j], i, j) for i in range(n) for j in range(i + 1, n) if not np.isnan(jac[i, j])]
+    if pairs:  # (ties: the first pair in the order of the files)
+        hi, lo = max(pairs, key=lambda t: (t[0], -t[1], -t[2])), min(pairs)
+        line += (f"; closest pair {names[hi[1]]} / {names[hi[2]]} (Jaccard {hi[0]:.4f}), most distant {names[lo[1]]} / {names[lo[2]]} "
+                 f"(Jaccard {lo[0]:.4f})")
+    print(line, file=sys.stderr)
+
+
+def _query(api, args, store, kmer_counts=None, fastq=(), colors=None) -> None:
     """`--query-fa`: the input's k-mer set (the unitig store) indexed once; one TSV row and one presence line per query record, and
     with `--query-locate-out` one row per run of located k-mers. kmer_counts (`--query-abundance-out`): the index is weighted with
-    them, and one more TSV row, and with `--query-abundance-profile-out` one line of integers, per query record."""
+    them, and one more TSV row, and with `--query-abundance-profile-out` one line of integers, per query record. colors
+    (`--query-colors-out`): the index carries their masks, and one more TSV row per query record."""
     import contextlib
     import gzip
 
@@ -359,7 +473,10 @@ def _query(api, args, store, kmer_counts=None, fastq=()) -> None:
         return gzip.open(path, "w" + mode, compresslevel=args.compression_level) if path.endswith(".gz") else open(path, "w" + mode)
 
     with contextlib.ExitStack() as stack:
-        if kmer_counts is None:
+        if colors is not None:  # (the masks, and the counts too when abundances are asked for)
+            index = stack.enter_context(api.KmerIndex(store, args.k, args.device, locate=bool(args.query_locate_out), weights=kmer_counts,
+                                                      colors=colors.kmer_colors, n_colors=colors.n_colors))
+        elif kmer_counts is None:
             index = stack.enter_context(api.KmerIndex(store, args.k, args.device, locate=bool(args.query_locate_out)))
         else:
             index = stack.enter_context(api.KmerIndex(store, args.k, args.device, locate=bool(args.query_locate_out), weights=kmer_counts))
@@ -368,6 +485,9 @@ def _query(api, args, store, kmer_counts=None, fastq=()) -> None:
         located = stack.enter_context(writer(args.query_locate_out, "t")) if args.query_locate_out else None
         weighed = stack.enter_context(writer(args.query_abundance_out, "t")) if kmer_counts is not None else None
         profile = stack.enter_context(writer(args.query_abundance_profile_out, "b")) if args.query_abundance_profile_out else None
+        coloured = stack.enter_context(writer(args.query_colors_out, "t")) if colors is not None else None
+        if coloured is not None:
+            coloured.write("\t".join(["record", "kmers", "valid", "found"] + args.seq_in) + "\n")
         tsv.write("record\tlength\tkmers\tvalid\tfound\n")
         if weighed is not None:
             weighed.write("record\tkmers\tvalid\tfound\tsum\tmin\tmax\tmean\n")
@@ -397,6 +517,10 @@ def _query(api, args, store, kmer_counts=None, fastq=()) -> None:
                     at = end
             if weighed is not None:
                 _write_query_abundance(index, seqs, names, weighed, profile, getattr(r, "valid_bits", None))
+            if coloured is not None:
+                ch = index.color_hits(seqs)
+                coloured.writelines("\t".join([name, str(n), str(v), str(f)] + [str(x) for x in row]) + "\n" for name, n, v, f, row in zip(
+                    names, ch.kmers.tolist(), ch.valid.tolist(), ch.found.tolist(), ch.per_color.tolist()))
             valid, found = int(r.valid.sum()), int(r.found.sum())
             print(f"Querying {path}: {len(names)} records, {int(r.kmers.sum())} k-mers, {valid} valid, {found} found "
                   f"({100.0 * found / valid if valid else 0.0:.2f} %) in {time.perf_counter() - t0:.1f} s", file=sys.stderr)

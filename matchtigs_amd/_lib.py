@@ -103,6 +103,12 @@ class MtgAbundance(C.Structure):
         ("spectrum", C.c_uint64 * 256)]
 
 
+class MtgColorStats(C.Structure):
+    """mtg_color_stats (include/mtg_engine.h)."""
+
+    _fields_ = [("n_colors", C.c_uint64), ("per_color", C.c_uint64 * 64), ("occupancy", C.c_uint64 * 65), ("shared", C.c_uint64 * (64 * 64))]
+
+
 class MtgFastqStats(C.Structure):
     """mtg_fastq_stats (include/mtg_engine.h)."""
 
@@ -291,6 +297,19 @@ def load():
         "mtg_kmer_index_is_weighted": (C.c_int, [vp]),
         "mtg_kmer_index_abundance": (None, [vp, vp, vp, u64, vp, vp, vp, vp, vp, vp, vp]),
         "mtg_last_kmer_abundance_times": (None, [P(C.c_double)]),
+        "mtg_compact_unitigs_colored": (None, [vp, vp, u64, u64, u64, vp, u64, C.c_int, P(vp), P(MtgCompaction), P(MtgAbundance), P(vp), P(vp),
+                                               P(vp), P(MtgColorStats)]),
+        "mtg_compact_unitigs_colored_store": (None, [vp, u64, u64, vp, u64, C.c_int, P(vp), P(MtgCompaction), P(MtgAbundance), P(vp), P(vp), P(vp),
+                                                     P(MtgColorStats)]),
+        "mtg_kmer_colors_count": (u64, [vp]),
+        "mtg_kmer_colors_array": (vp, [vp]),
+        "mtg_kmer_colors_free": (None, [vp]),
+        "mtg_kmer_index_build_annotated": (vp, [vp, vp, u64, u64, vp, u64, vp, u64, u64, C.c_int, C.c_int]),
+        "mtg_kmer_index_build_annotated_store": (vp, [vp, u64, vp, u64, vp, u64, u64, C.c_int, C.c_int]),
+        "mtg_kmer_index_is_colored": (C.c_int, [vp]),
+        "mtg_kmer_index_n_colors": (u64, [vp]),
+        "mtg_kmer_index_colors": (None, [vp, vp, vp, u64, vp, vp, vp, vp, vp]),
+        "mtg_last_kmer_color_times": (None, [P(C.c_double)]),
         "mtg_read_sequences_named": (None, [C.c_char_p, P(vp), P(vp)]),
         "mtg_read_fastq_split": (C.c_int, [C.c_char_p, u64, C.c_int, P(vp), P(MtgFastqStats), C.c_char_p, u64]),
         "mtg_read_fastq_named": (C.c_int, [C.c_char_p, u64, C.c_int, P(vp), P(vp), P(MtgFastqStats), C.c_char_p, u64]),

@@ -973,6 +973,98 @@ def compact_unitigs_counted(seqs_or_store, k: int, min_abundance: int, device_id
     return UnitigStore(out.value), Compaction(**stats.as_dict()), abundance
 
 
+MAX_COLORS = 64
+
+
+@dataclass(frozen=True, eq=False)
+class Colors:
+    """What a coloured compaction knows about the inputs of every kept k-mer (mtg_compact_unitigs_colored), in exact
+    integers. kmer_colors[i] = the mask of k-mer i in window order of the store (the indexing of Abundance.kmer_counts): bit c is set
+    iff a window of a record of colour c shows the k-mer, on either strand. per_color[c] = the kept k-mers with bit c; shared[i, j] =
+    those with bits i and j (symmetric, the diagonal is per_color); occupancy[j] = those carried by exactly j colours."""
+
+    n_colors: int
+    kmer_colors: np.ndarray  # uint64[distinct_kept]
+    per_color: np.ndarray    # uint64[n_colors]
+    occupancy: np.ndarray    # uint64[65]
+    shared: np.ndarray       # uint64[n_colors, n_colors]
+
+    @property
+    def core(self) -> int:
+        """The kept k-mers every colour carries."""
+        return int(self.occupancy[self.n_colors])
+
+    @property
+    def private(self) -> int:
+        """The kept k-mers exactly one colour carries."""
+        return int(self.occupancy[1])
+
+    def jaccard(self) -> np.ndarray:
+        """|i and j| / |i or j| over the kept k-mers as float64[n_colors, n_colors]; nan where both colours are empty."""
+        inter = self.shared.astype(np.float64)
+        union = self.per_color[:, None].astype(np.float64) + self.per_color[None, :].astype(np.float64) - inter
+        out = np.full(inter.shape, np.nan)
+        np.divide(inter, union, out=out, where=union > 0)
+        return out
+
+    def describe(self) -> str:
+        return (f"{self.n_colors} colours over {int(self.occupancy.sum())} k-mers: {self.core} core, {self.private} private")
+
+
+def _record_colors(record_colors, n_colors, n_records: int) -> np.ndarray:
+    """The colours of a coloured call as uint8[n_records]; ValueError for what the library would abort on."""
+    if isinstance(n_colors, bool) or not isinstance(n_colors, (int, np.integer)) or not 1 <= n_colors <= MAX_COLORS:
+        raise ValueError(f"n_colors must be in 1..{MAX_COLORS}, not {n_colors!r}")
+    wide = np.asarray(record_colors)
+    if wide.ndim != 1 or len(wide) != n_records:
+        raise ValueError(f"record_colors must hold one entry per record: {wide.shape} for {n_records} records")
+    if len(wide) and (wide.dtype.kind not in "iu" or int(wide.min()) < 0 or int(wide.max()) >= n_colors):
+        raise ValueError(f"every colour must be an integer in 0..{n_colors - 1}")
+    return np.ascontiguousarray(wide, np.uint8)
+
+
+def compact_unitigs_colored(seqs_or_store, k: int, record_colors, n_colors: int, min_abundance: int = 1, device_id: int = 0):
+    """compact_unitigs_counted(..., kmer_counts=True) -- the same store, Compaction and Abundance -- that also tells which inputs carry
+    every kept k-mer (mtg_compact_unitigs_colored) -> (UnitigStore, Compaction, Abundance, Colors). record_colors: one
+    integer in 0..n_colors - 1 per input record (its file, sample or haplotype), n_colors in 1..64."""
+    if min_abundance < 1:
+        raise ValueError("min_abundance must be >= 1")
+    if isinstance(seqs_or_store, UnitigStore):
+        n_records = len(seqs_or_store)
+    elif isinstance(seqs_or_store, tuple):
+        n_records = len(seqs_or_store[1]) - 1
+    else:
+        n_records = len(seqs_or_store)
+    rc = _record_colors(record_colors, n_colors, n_records)
+    L = _lib.load()
+    out, sums, counts, masks = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+    stats, ab, cs = _lib.MtgCompaction(), _lib.MtgAbundance(), _lib.MtgColorStats()
+    tail = (device_id, C.byref(out), C.byref(stats), C.byref(ab), C.byref(sums), C.byref(counts), C.byref(masks), C.byref(cs))
+    if isinstance(seqs_or_store, UnitigStore):
+        L.mtg_compact_unitigs_colored_store(seqs_or_store.handle, k, min_abundance, _ptr(rc), n_colors, *tail)
+    else:
+        d, o, n, keep = _sequence_arrays(seqs_or_store)
+        L.mtg_compact_unitigs_colored(d, o, n, k, min_abundance, _ptr(rc), n_colors, *tail)
+        del keep
+    try:
+        def taken(count, array, handle, ctype, dtype):
+            n = int(count(handle))
+            return np.ctypeslib.as_array(C.cast(array(handle), C.POINTER(ctype)), shape=(n,)).copy() if n else np.zeros(0, dtype)
+
+        unitig_sums = taken(L.mtg_abundance_sums_count, L.mtg_abundance_sums_array, sums, C.c_uint64, np.uint64)
+        per_kmer = taken(L.mtg_kmer_counts_count, L.mtg_kmer_counts_array, counts, C.c_uint32, np.uint32)
+        kmer_colors = taken(L.mtg_kmer_colors_count, L.mtg_kmer_colors_array, masks, C.c_uint64, np.uint64)
+    finally:
+        L.mtg_abundance_sums_free(sums)
+        L.mtg_kmer_counts_free(counts)
+        L.mtg_kmer_colors_free(masks)
+    abundance = Abundance(int(ab.distinct_all), int(ab.distinct_kept), int(ab.max_abundance), int(ab.kept_occurrences),
+                          np.array(ab.spectrum, dtype=np.uint64), unitig_sums, per_kmer)
+    colors = Colors(int(n_colors), kmer_colors, np.array(cs.per_color, dtype=np.uint64)[:n_colors].copy(), np.array(cs.occupancy, dtype=np.uint64),
+                    np.array(cs.shared, dtype=np.uint64).reshape(MAX_COLORS, MAX_COLORS)[:n_colors, :n_colors].copy())
+    return UnitigStore(out.value), Compaction(**stats.as_dict()), abundance, colors
+
+
 def last_compact_times() -> dict:
     """Phases of the last compact_unitigs / compact_unitigs_counted on this thread: ms by HIP events around the kernel phases (pack, insert, ids, nodes, rank,
     emit), upload / download / total by the host clock, the pointer-jumping rounds, the least bytes the kernels must move and the
@@ -1244,6 +1336,22 @@ class KmerAbundanceResult:
         return out
 
 
+@dataclass(frozen=True, eq=False)
+class KmerColorResult:
+    """What KmerIndex.color_hits found, per query record: kmers / valid / found as KmerIndex.query gives them (uint64), and per_color
+    (uint32[records, n_colors]): the found windows of the record whose k-mer's mask has bit c -- a mask of 0 is found and touches no
+    column. With per_window=True also per_window (uint64, one entry per global base position of the query): the mask of the k-mer of
+    the window that starts there if it is valid and found, else 0."""
+
+    k: int
+    offsets: np.ndarray
+    kmers: np.ndarray
+    valid: np.ndarray
+    found: np.ndarray
+    per_color: np.ndarray
+    per_window: Optional[np.ndarray] = None
+
+
 def _window_count(seqs_or_store, k: int) -> int:
     """The windows of length k inside the records: what a KmerIndex of them reports as info.occurrences."""
     if isinstance(seqs_or_store, UnitigStore):
@@ -1262,14 +1370,40 @@ class KmerIndex:
     also keeps where its k-mers are (more device memory, see info.device_bytes) and answers locate(). weights: an
     array-like of uint32, one per window of the sequences in window order (the k-mers of record 0 from left to right, then record
     1's, ...; a record shorter than k has none): the index also keeps a weight per k-mer -- that of its first occurrence -- and
-    answers abundance()."""
+    answers abundance(). colors with n_colors (1..64): an array-like of uint64, one mask per window in the same order:
+    the index also keeps a mask per k-mer -- that of its first occurrence -- and answers color_hits(). An index may
+    carry weights, colours, both or neither."""
 
-    def __init__(self, seqs_or_store, k: int, device_id: int = 0, locate: bool = False, weights=None):
+    def __init__(self, seqs_or_store, k: int, device_id: int = 0, locate: bool = False, weights=None, colors=None, n_colors=None):
         self._L = _lib.load()
         self._h = None
         self.locating = bool(locate)
         self.weighted = weights is not None
-        if self.weighted:
+        self.colored = colors is not None
+        self.n_colors = 0
+        if self.colored:
+            if isinstance(n_colors, bool) or not isinstance(n_colors, (int, np.integer)) or not 1 <= n_colors <= MAX_COLORS:
+                raise ValueError(f"n_colors must be in 1..{MAX_COLORS}, not {n_colors!r}")
+            windows = _window_count(seqs_or_store, k) if k >= 1 else -1
+            c = np.ascontiguousarray(colors, np.uint64)
+            w = np.ascontiguousarray(weights, np.uint32) if self.weighted else None
+            if c.ndim != 1 or len(c) != windows:
+                raise ValueError(f"colors must hold one entry per window: {c.shape} for {windows} windows")
+            if n_colors < MAX_COLORS and len(c) and int(c.max()) >> int(n_colors):
+                raise ValueError(f"a mask has a colour beyond the {n_colors} given")
+            if w is not None and (w.ndim != 1 or len(w) != windows):
+                raise ValueError(f"weights must hold one entry per window: {w.shape} for {windows} windows")
+            payload = (_ptr(w), len(w) if w is not None else 0, _ptr(c), len(c), int(n_colors), int(self.locating), device_id)
+            if isinstance(seqs_or_store, UnitigStore):
+                self._h = self._L.mtg_kmer_index_build_annotated_store(seqs_or_store.handle, k, *payload)
+            else:
+                d, o, n, keep = _sequence_arrays(seqs_or_store)
+                self._h = self._L.mtg_kmer_index_build_annotated(d, o, n, k, *payload)
+                del keep
+            self.n_colors = int(n_colors)
+        elif n_colors is not None:
+            raise ValueError("n_colors needs colors")
+        elif self.weighted:
             w = np.ascontiguousarray(weights, np.uint32)
             windows = _window_count(seqs_or_store, k) if k >= 1 else -1
             if w.ndim != 1 or len(w) != windows:
@@ -1363,6 +1497,30 @@ class KmerIndex:
                                          _ptr(pw) if per_window else None)
         del keep
         return KmerAbundanceResult(self.info.k, off, kmers, valid, found, total, lo, hi, pw)
+
+    def color_hits(self, seqs_or_store, per_window: bool = False) -> KmerColorResult:
+        """query()'s counts per record plus, per record and colour, the found windows whose k-mer that colour carries
+        (KmerColorResult); per_window: also the mask at every window start. Needs an index built with colors."""
+        if not self._h:
+            raise ValueError("the index is closed")
+        if not self.colored:
+            raise ValueError("color_hits() needs an index built with colors")
+        d, o, n, keep = _sequence_arrays(seqs_or_store)
+        off = np.ctypeslib.as_array(C.cast(o, C.POINTER(C.c_uint64)), shape=(n + 1,)).copy()
+        kmers, valid, found = (np.zeros(n, np.uint64) for _ in range(3))
+        per_color = np.zeros((n, self.n_colors), np.uint32)
+        pw = np.zeros(int(off[n]), np.uint64) if per_window else None
+        self._L.mtg_kmer_index_colors(self._h, d, o, n, _ptr(kmers), _ptr(valid), _ptr(found), _ptr(per_color), _ptr(pw) if per_window else None)
+        del keep
+        return KmerColorResult(self.info.k, off, kmers, valid, found, per_color, pw)
+
+
+def last_kmer_color_times() -> dict:
+    """In ms: stats = the colour statistics kernel of the last compact_unitigs_colored on this thread (HIP events); the phases of the
+    last KmerIndex.color_hits (HIP events around the kernels; upload and download by the host clock)."""
+    out = (C.c_double * 5)()
+    _lib.load().mtg_last_kmer_color_times(out)
+    return dict(zip(("stats_ms", "upload_ms", "pack_ms", "probe_ms", "download_ms"), list(out)))
 
 
 def last_kmer_query_times() -> dict:

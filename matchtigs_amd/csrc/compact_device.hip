@@ -51,6 +51,14 @@
 // Memory added by a counted call: 4 B per slot (8 w) while inserting, freed with the table; 4 N (kcount) afterwards; 12 N + 8 per
 // unitig for the sums at the end of emit. A call that hands out the count of every kept k-mer (mtg_compact_unitigs_counted_kmers,
 // DESIGN.md 20) downloads that array in unitig order, which is the store's window order, instead of freeing it after the scan.
+//
+// Coloured calls (mtg_compact_unitigs_colored): every record has a colour below C <= 64; colors(x) = the 64-bit mask of the
+// colours of the windows whose k-mer is x or rc(x). It is a counted call that hands out the counts, plus: insert<COLORED> ORs the
+// record's bit into colors[slot] (a plain read first, atomicOr only where the bit is missing: bits only appear, so a stale read costs
+// one redundant atomic; the final word is an OR over the class's windows in any order); kpos<COLORED> carries kcolor[id] = colors[slot];
+// color_stats_kernel sweeps kcolor[N] once for per-colour counts, the C x C matrix of shared k-mers and the occupancy histogram, as a
+// product of 64 x 64 bit blocks (ballots, popcounts), never a loop over set bits; order_kernel<uint64_t> puts the masks into unitig
+// order, which is downloaded. Memory added: 8 B per slot (16 w) while inserting, freed with the table; 8 N (kcolor) and 8 N (ordered).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -84,11 +92,16 @@ __device__ __forceinline__ uint64_t load64(const unsigned long long *p) { return
 __device__ __forceinline__ void store64(unsigned long long *p, uint64_t v) { __hip_atomic_store(p, (unsigned long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // COUNTED: count[slot] += 1 per window (the class's abundance once the kernel has finished)
-template <bool WIDE, bool COUNTED>
-__global__ __launch_bounds__(hu::EB) void insert_kernel(KmerArgs a, uint64_t n_bases, uint64_t n_rec, unsigned int *err, uint32_t *count) {
+// COLORED: colors[slot] |= 1 << record_colors[record of the window] (record_colors: [n_rec], each < 64; colors: [slots], zeroed). The
+// record's colour is read again only where the record changes inside the thread's run.
+template <bool WIDE, bool COUNTED, bool COLORED>
+__global__ __launch_bounds__(hu::EB) void insert_kernel(KmerArgs a, uint64_t n_bases, uint64_t n_rec, unsigned int *err, uint32_t *count,
+                                                         const uint8_t *record_colors, unsigned long long *colors) {
     const uint64_t p0 = hu::gid() * RUN;
     if (p0 >= n_bases) return;
-    kw::for_each_window<WIDE>(a, p0, p0 + RUN < n_bases ? p0 + RUN : n_bases, 0, n_rec, [&](uint64_t q, uint64_t, const kw::Window &w) {
+    uint64_t bit_rec = ~0ull;
+    unsigned long long bit = 0;
+    kw::for_each_window<WIDE>(a, p0, p0 + RUN < n_bases ? p0 + RUN : n_bases, 0, n_rec, [&](uint64_t q, uint64_t r, const kw::Window &w) {
         const unsigned long long mine = kw::tagged_pos(w.hash, q);
         const kw::Found f = kw::find_slot<true>(a.table, a.slots, w.hash, mine, [&](unsigned long long cur) {
             return (cur >> 40) == (mine >> 40) && kw::same_class(a.packed, q, cur & POS_LIMIT, a.k);
@@ -99,6 +112,13 @@ __global__ __launch_bounds__(hu::EB) void insert_kernel(KmerArgs a, uint64_t n_b
         }
         if (f.word != EMPTY_SLOT && mine < f.word) atomicMin(&a.table[f.slot], mine);
         if (COUNTED) atomicAdd(&count[f.slot], 1u);
+        if (COLORED) {
+            if (r != bit_rec) {
+                bit_rec = r;
+                bit = 1ull << record_colors[r];
+            }
+            if (!(colors[f.slot] & bit)) atomicOr(&colors[f.slot], bit);
+        }
     });
 }
 
@@ -119,10 +139,11 @@ __global__ __launch_bounds__(hu::EB) void mark_kernel(const unsigned long long *
     for (int d = warpSize / 2; d > 0; d /= 2) n += __shfl_down(n, d);
     if (n && (threadIdx.x & (warpSize - 1)) == 0) atomicAdd(count, n);
 }
-// COUNTED: kcount[id] = the abundance of k-mer id
-template <bool COUNTED>
+// COUNTED: kcount[id] = the abundance of k-mer id; COLORED (counted calls): kcolor[id] = its colour mask
+template <bool COUNTED, bool COLORED>
 __global__ __launch_bounds__(hu::EB) void kpos_kernel(const unsigned long long *table, uint64_t slots, const uint32_t *id_of_pos, unsigned long long *kpos,
-                                                       const uint32_t *abundance, uint64_t m, uint32_t *kcount) {
+                                                       const uint32_t *abundance, uint64_t m, uint32_t *kcount, const unsigned long long *colors,
+                                                       unsigned long long *kcolor) {
     const uint64_t s = hu::gid();
     if (s >= slots) return;
     const unsigned long long cur = table[s];
@@ -133,6 +154,7 @@ __global__ __launch_bounds__(hu::EB) void kpos_kernel(const unsigned long long *
         const uint32_t id = id_of_pos[cur & POS_LIMIT];
         kpos[id] = cur & POS_LIMIT;
         kcount[id] = abundance[s];
+        if (COLORED) kcolor[id] = colors[s];
     }
 }
 
@@ -177,6 +199,51 @@ __global__ __launch_bounds__(hu::EB) void spectrum_kernel(const uint32_t *abunda
         if (sum) atomicAdd(&out[SPECTRUM_BINS + 1], sum);
         if (top) atomicMax(&out[SPECTRUM_BINS], (unsigned long long)top);
     }
+}
+
+// One sweep over the colour masks of the kept k-mers. out[i * 64 + j], i, j < C: the k-mers whose mask has bits i and
+// j (the diagonal: bit i); out[COLOR_OCC + n], n <= 64: the k-mers with n bits set. A wave takes 64 masks at a time, one per lane (0
+// behind N): T_i = the ballot of bit i is column i of that 64 x 64 bit block, kept by lane i, and lane i adds popcount(T_i & T_j) for
+// every j < C to its accumulator j, T_j coming from lane j by readlane -- C ballots and C (readlane, and, popcount, add) per block
+// whatever the masks hold. The accumulators (fewer than 2^31 k-mers: they cannot wrap) stay in registers over all blocks of the wave,
+// are then added up per workgroup in LDS and leave by at most one global atomicAdd per non-zero entry and workgroup.
+constexpr int MAX_COLORS = 64, COLOR_OCC = MAX_COLORS * MAX_COLORS, COLOR_STATS_WORDS = COLOR_OCC + MAX_COLORS + 1;
+__global__ __launch_bounds__(hu::EB) void color_stats_kernel(const unsigned long long *kcolor, uint64_t N, int C, unsigned long long *out) {
+    __shared__ uint32_t mat[COLOR_OCC];
+    __shared__ uint32_t occ[MAX_COLORS + 1];
+    for (int e = threadIdx.x; e < COLOR_OCC; e += hu::EB) mat[e] = 0;
+    if (threadIdx.x <= MAX_COLORS) occ[threadIdx.x] = 0;
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    uint32_t acc[MAX_COLORS];
+#pragma unroll
+    for (int j = 0; j < MAX_COLORS; j++) acc[j] = 0;
+    const uint64_t stride = (uint64_t)gridDim.x * hu::EB;  // (a multiple of 64: the lanes of a wave leave the loop together)
+    for (uint64_t at = hu::gid() - lane; at < N; at += stride) {
+        const bool live = at + lane < N;
+        const unsigned long long mask = live ? kcolor[at + lane] : 0ull;
+        if (live) atomicAdd(&occ[__popcll(mask)], 1u);
+        unsigned long long mine = 0;
+        for (int i = 0; i < C; i++) {
+            const unsigned long long t = __ballot((mask >> i) & 1);
+            mine = lane == i ? t : mine;
+        }
+        const uint32_t lo = (uint32_t)mine, hi = (uint32_t)(mine >> 32);
+#pragma unroll
+        for (int j = 0; j < MAX_COLORS; j++) {
+            if (j < C) {  // (uniform)
+                const uint32_t tl = __builtin_amdgcn_readlane(lo, j), th = __builtin_amdgcn_readlane(hi, j);
+                acc[j] += __popc(lo & tl) + __popc(hi & th);
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < MAX_COLORS; j++)
+        if (j < C && acc[j]) atomicAdd(&mat[j * MAX_COLORS + lane], acc[j]);  // (entry (j, lane) of a symmetric matrix: one bank per lane)
+    __syncthreads();
+    for (int e = threadIdx.x; e < COLOR_OCC; e += hu::EB)
+        if (mat[e]) atomicAdd(&out[e], (unsigned long long)mat[e]);
+    if (threadIdx.x <= MAX_COLORS && occ[threadIdx.x]) atomicAdd(&out[COLOR_OCC + threadIdx.x], (unsigned long long)occ[threadIdx.x]);
 }
 
 struct NodeArgs {
@@ -344,9 +411,10 @@ __global__ __launch_bounds__(hu::EB) void spell_kernel(const uint32_t *packed, c
 // ---- per-unitig abundance sums (counted calls) ----
 // Every oriented k-mer of an emitted walk writes its k-mer's abundance at its place in unitig order: unitig u starts at character
 // offset char_off, i.e. at k-mer offset char_off - (k - 1) u, and the k-mer is `rank` steps behind the walk's head.
+// (T: uint32_t abundances, unsigned long long colour masks)
+template <typename T>
 __global__ __launch_bounds__(hu::EB) void order_counts_kernel(const unsigned long long *pairs, const uint32_t *wmin, const uint64_t *char_off,
-                                                               const uint32_t *unitig_of, const uint32_t *kcount, uint64_t n, uint64_t k,
-                                                               uint32_t *ordered) {
+                                                               const uint32_t *unitig_of, const T *kcount, uint64_t n, uint64_t k, T *ordered) {
     const uint64_t o = hu::gid();
     if (o >= n) return;
     const uint64_t pr = pairs[o];
@@ -376,10 +444,19 @@ struct Counted {
     std::vector<uint64_t> *sums;
     std::vector<uint32_t> *kmer_counts;  // null, or: every kept k-mer's abundance in window order of the output store
 };
+// what a coloured call adds to a counted one
+struct Colored {
+    const uint8_t *record_colors;  // [n_rec], each < n_colors
+    uint64_t n_colors;
+    std::vector<uint64_t> *kmer_colors;  // every kept k-mer's mask, indexed like kmer_counts
+    mtg_color_stats *stats;
+    double *stats_ms;  // HIP-event time of color_stats_kernel
+};
 
 // counted == nullptr: the plain compaction
+// colored != nullptr: counted too
 UnitigStore *compact(const char *data, const uint64_t *off, uint64_t n_rec, uint64_t k, int device_id, mtg_compaction *stats_out, CompactTimes *times,
-                     const Counted *counted) {
+                     const Counted *counted, const Colored *colored = nullptr) {
     if (!off || (n_rec && off[n_rec] && !data)) MTG_DIE("mtg_compact_unitigs: null argument");
     if (k < 2) MTG_DIE("mtg_compact_unitigs: k must be >= 2");
     if (k >= (1ull << 31)) MTG_DIE("mtg_compact_unitigs: k too large");
@@ -403,6 +480,19 @@ UnitigStore *compact(const char *data, const uint64_t *off, uint64_t n_rec, uint
                                                (unsigned long long)r.windows);
         counted->sums->clear();
         if (counted->kmer_counts) counted->kmer_counts->clear();
+    }
+    if (colored) {
+        if (colored->n_colors < 1 || colored->n_colors > MAX_COLORS)
+            MTG_DIE("mtg_compact_unitigs_colored: %llu colours; 1 .. %d are served", (unsigned long long)colored->n_colors, MAX_COLORS);
+        if (n_rec && !colored->record_colors) MTG_DIE("mtg_compact_unitigs_colored: null argument");
+        for (uint64_t u = 0; u < n_rec; u++)
+            if (colored->record_colors[u] >= colored->n_colors)
+                MTG_DIE("mtg_compact_unitigs_colored: record %llu has colour %u of %llu", (unsigned long long)u, (unsigned)colored->record_colors[u],
+                        (unsigned long long)colored->n_colors);
+        colored->kmer_colors->clear();
+        *colored->stats = mtg_color_stats{};
+        colored->stats->n_colors = colored->n_colors;
+        *colored->stats_ms = 0;
     }
     auto finish = [&]() {
         t.total_ms = ms_since(t_total);
@@ -444,14 +534,25 @@ UnitigStore *compact(const char *data, const uint64_t *off, uint64_t n_rec, uint
         hu::device_malloc(&d_count, slots * 4);
         HIP_CHECK(hipMemsetAsync(d_count, 0, slots * 4, st));
     }
+    uint8_t *d_rec_colors = nullptr;
+    unsigned long long *d_colors = nullptr, *d_kcolor = nullptr;  // coloured calls: [slots] mask per slot, [N] per kept k-mer
+    if (colored) {
+        hu::device_malloc(&d_rec_colors, n_rec);
+        hu::device_malloc(&d_colors, slots * 8);
+        hu::upload_sliced(d_rec_colors, colored->record_colors, n_rec, st, device_id);
+        HIP_CHECK(hipMemsetAsync(d_colors, 0, slots * 8, st));
+    }
     {
         const unsigned grid = hu::grid_for((n_bases + RUN - 1) / RUN);
-        if (counted) {
-            if (k >= 32) insert_kernel<true, true><<<grid, hu::EB, 0, st>>>(ka, n_bases, n_rec, d_err, d_count);
-            else insert_kernel<false, true><<<grid, hu::EB, 0, st>>>(ka, n_bases, n_rec, d_err, d_count);
+        if (colored) {
+            if (k >= 32) insert_kernel<true, true, true><<<grid, hu::EB, 0, st>>>(ka, n_bases, n_rec, d_err, d_count, d_rec_colors, d_colors);
+            else insert_kernel<false, true, true><<<grid, hu::EB, 0, st>>>(ka, n_bases, n_rec, d_err, d_count, d_rec_colors, d_colors);
+        } else if (counted) {
+            if (k >= 32) insert_kernel<true, true, false><<<grid, hu::EB, 0, st>>>(ka, n_bases, n_rec, d_err, d_count, nullptr, nullptr);
+            else insert_kernel<false, true, false><<<grid, hu::EB, 0, st>>>(ka, n_bases, n_rec, d_err, d_count, nullptr, nullptr);
         } else {
-            if (k >= 32) insert_kernel<true, false><<<grid, hu::EB, 0, st>>>(ka, n_bases, n_rec, d_err, nullptr);
-            else insert_kernel<false, false><<<grid, hu::EB, 0, st>>>(ka, n_bases, n_rec, d_err, nullptr);
+            if (k >= 32) insert_kernel<true, false, false><<<grid, hu::EB, 0, st>>>(ka, n_bases, n_rec, d_err, nullptr, nullptr, nullptr);
+            else insert_kernel<false, false, false><<<grid, hu::EB, 0, st>>>(ka, n_bases, n_rec, d_err, nullptr, nullptr, nullptr);
         }
         HIP_CHECK(hipGetLastError());
     }
@@ -488,7 +589,7 @@ UnitigStore *compact(const char *data, const uint64_t *off, uint64_t n_rec, uint
     if (N > MAX_KMERS) MTG_DIE("mtg_compact_unitigs: %llu distinct k-mers; oriented k-mer ids are 32-bit", (unsigned long long)N);
     if (counted) ab.distinct_kept = N;
     if (N == 0) {  // (counted calls only: no k-mer reaches the threshold)
-        free_all({ka.table, d_id_of_pos, d_count});
+        free_all({ka.table, d_id_of_pos, d_count, d_rec_colors, d_colors});
         t.insert_ms = ev.ms(0, 1);
         return finish();
     }
@@ -497,15 +598,19 @@ UnitigStore *compact(const char *data, const uint64_t *off, uint64_t n_rec, uint
     hu::device_malloc(&d_bsum32, (hu::scan_blocks(n_bases) + 2) * 4);
     hu::device_malloc(&d_kpos, N * 8);
     hu::scan_u32<uint32_t>(st, d_id_of_pos, n_bases, d_id_of_pos, d_bsum32, d_bsum32 + hu::scan_blocks(n_bases) + 1);
-    if (counted) {
+    if (colored) {
         hu::device_malloc(&d_kcount, N * 4);
-        kpos_kernel<true><<<hu::grid_for(slots), hu::EB, 0, st>>>(ka.table, slots, d_id_of_pos, d_kpos, d_count, counted->m, d_kcount);
+        hu::device_malloc(&d_kcolor, N * 8);
+        kpos_kernel<true, true><<<hu::grid_for(slots), hu::EB, 0, st>>>(ka.table, slots, d_id_of_pos, d_kpos, d_count, counted->m, d_kcount, d_colors, d_kcolor);
+    } else if (counted) {
+        hu::device_malloc(&d_kcount, N * 4);
+        kpos_kernel<true, false><<<hu::grid_for(slots), hu::EB, 0, st>>>(ka.table, slots, d_id_of_pos, d_kpos, d_count, counted->m, d_kcount, nullptr, nullptr);
     } else {
-        kpos_kernel<false><<<hu::grid_for(slots), hu::EB, 0, st>>>(ka.table, slots, d_id_of_pos, d_kpos, nullptr, 0, nullptr);
+        kpos_kernel<false, false><<<hu::grid_for(slots), hu::EB, 0, st>>>(ka.table, slots, d_id_of_pos, d_kpos, nullptr, 0, nullptr, nullptr, nullptr);
     }
     HIP_CHECK(hipGetLastError());
     ev.mark(2, st);
-    free_all({ka.table, d_id_of_pos, d_bsum32, d_count});
+    free_all({ka.table, d_id_of_pos, d_bsum32, d_count, d_rec_colors, d_colors});
 
     // ---- the (k-1)-mer classes and succ ----
     NodeArgs na{};
@@ -610,7 +715,7 @@ UnitigStore *compact(const char *data, const uint64_t *off, uint64_t n_rec, uint
         hu::device_malloc(&d_ordered, N * 4);
         hu::device_malloc(&d_prefix, N * 8);
         hu::device_malloc(&d_sums, r.unitigs * 8);
-        order_counts_kernel<<<hu::grid_for(n_or), hu::EB, 0, st>>>(d_pairs, d_wmin, d_char_off, d_lead_flag, d_kcount, n_or, k, d_ordered);
+        order_counts_kernel<uint32_t><<<hu::grid_for(n_or), hu::EB, 0, st>>>(d_pairs, d_wmin, d_char_off, d_lead_flag, d_kcount, n_or, k, d_ordered);
         hu::scan_u32<uint64_t>(st, d_ordered, N, d_prefix, d_bsum64, d_n_chars);  // (the block sums and the total's word are free again)
         unitig_sums_kernel<<<hu::grid_for(r.unitigs), hu::EB, 0, st>>>(d_out_off, d_prefix, d_n_chars, r.unitigs, k, d_sums);
         HIP_CHECK(hipGetLastError());
@@ -619,6 +724,20 @@ UnitigStore *compact(const char *data, const uint64_t *off, uint64_t n_rec, uint
             hu::device_free(d_ordered);
             d_ordered = nullptr;
         }
+    }
+    unsigned long long *d_ordered_colors = nullptr, *d_color_stats = nullptr;
+    if (colored) {  // the masks in unitig order, and the statistics over kcolor (any order serves)
+        PhaseEvents<2> ev_stats;
+        hu::device_malloc(&d_color_stats, COLOR_STATS_WORDS * 8);
+        hu::device_malloc(&d_ordered_colors, N * 8);
+        HIP_CHECK(hipMemsetAsync(d_color_stats, 0, COLOR_STATS_WORDS * 8, st));
+        order_counts_kernel<unsigned long long><<<hu::grid_for(n_or), hu::EB, 0, st>>>(d_pairs, d_wmin, d_char_off, d_lead_flag, d_kcolor, n_or, k,
+                                                                                         d_ordered_colors);
+        ev_stats.mark(0, st);
+        color_stats_kernel<<<(unsigned)std::min<uint64_t>(hu::grid_for(N), 512), hu::EB, 0, st>>>(d_kcolor, N, (int)colored->n_colors, d_color_stats);
+        ev_stats.mark(1, st);
+        HIP_CHECK(hipGetLastError());
+        *colored->stats_ms = ev_stats.ms(0, 1);
     }
     ev.mark(5, st);
     HIP_CHECK(hipStreamSynchronize(st));
@@ -637,6 +756,18 @@ UnitigStore *compact(const char *data, const uint64_t *off, uint64_t n_rec, uint
             hu::download_sliced(counted->kmer_counts->data(), d_ordered, N * 4, st, device_id);
         }
     }
+    if (colored) {
+        std::vector<unsigned long long> h(COLOR_STATS_WORDS);
+        hu::download_sliced(h.data(), d_color_stats, h.size() * 8, st, device_id);
+        mtg_color_stats &cs = *colored->stats;
+        for (int i = 0; i < MAX_COLORS; i++) {
+            cs.per_color[i] = h[i * MAX_COLORS + i];
+            for (int j = 0; j < MAX_COLORS; j++) cs.shared[i * MAX_COLORS + j] = h[i * MAX_COLORS + j];
+        }
+        for (int j = 0; j <= MAX_COLORS; j++) cs.occupancy[j] = h[COLOR_OCC + j];
+        colored->kmer_colors->resize(N);
+        hu::download_sliced(colored->kmer_colors->data(), d_ordered_colors, N * 8, st, device_id);
+    }
     t.download_ms = ms_since(t0);
     t.insert_ms = ev.ms(0, 1);
     t.ids_ms = ev.ms(1, 2);
@@ -644,7 +775,8 @@ UnitigStore *compact(const char *data, const uint64_t *off, uint64_t n_rec, uint
     t.rank_ms = ev.ms(3, 4);
     t.emit_ms = ev.ms(4, 5);
     t.rounds = rounds;
-    free_all({d_kpos, na.succ, d_pairs, d_wmin, d_wlen, d_lead_flag, d_lead_chars, d_char_off, d_bsum32, d_bsum64, d_out, d_out_off, d_kcount, d_sums, d_ordered});
+    free_all({d_kpos, na.succ, d_pairs, d_wmin, d_wlen, d_lead_flag, d_lead_chars, d_char_off, d_bsum32, d_bsum64, d_out, d_out_off, d_kcount, d_sums, d_ordered, d_kcolor,
+              d_ordered_colors, d_color_stats});
     uint64_t arena[4];
     device_arena_stats(device_id, arena);
     t.peak_arena_bytes = arena[2];
@@ -672,6 +804,16 @@ UnitigStore *device_compact_unitigs_counted(const char *data, const uint64_t *of
     if (!unitig_sums) MTG_DIE("mtg_compact_unitigs_counted: null argument");
     const Counted c{min_abundance, abundance_out, unitig_sums, kmer_counts};
     return compact(data, off, n_rec, k, device_id, stats_out, times, &c);
+}
+
+UnitigStore *device_compact_unitigs_colored(const char *data, const uint64_t *off, uint64_t n_rec, uint64_t k, uint64_t min_abundance,
+                                            const uint8_t *record_colors, uint64_t n_colors, int device_id, mtg_compaction *stats_out,
+                                            mtg_abundance *abundance_out, std::vector<uint64_t> *unitig_sums, std::vector<uint32_t> *kmer_counts,
+                                            std::vector<uint64_t> *kmer_colors, mtg_color_stats *color_stats, CompactTimes *times, double *stats_ms) {
+    if (!unitig_sums || !kmer_counts || !kmer_colors || !color_stats || !stats_ms) MTG_DIE("mtg_compact_unitigs_colored: null argument");
+    const Counted c{min_abundance, abundance_out, unitig_sums, kmer_counts};
+    const Colored col{record_colors, n_colors, kmer_colors, color_stats, stats_ms};
+    return compact(data, off, n_rec, k, device_id, stats_out, times, &c, &col);
 }
 
 }  // namespace mtg

@@ -146,10 +146,17 @@ struct KmerWeights {
     const uint32_t *w;
     uint64_t n;
 };
+// colors: one 64-bit mask per window, in window order; the index also keeps the mask of every class -- that of its
+// smallest window start -- and answers device_kmer_index_colors. n must equal the windows, 1 <= n_colors <= 64.
+struct KmerColors {
+    const uint64_t *c;
+    uint64_t n, n_colors;
+};
 KmerIndex *device_kmer_index_build(const char *seq, const uint64_t *off, uint64_t n, uint64_t k, int device_id, bool locating,
-                                   KmerQueryTimes *times, const KmerWeights *weights = nullptr);
+                                   KmerQueryTimes *times, const KmerWeights *weights = nullptr, const KmerColors *colors = nullptr);
 bool device_kmer_index_is_locating(const KmerIndex *ix);
 bool device_kmer_index_is_weighted(const KmerIndex *ix);
+uint64_t device_kmer_index_n_colors(const KmerIndex *ix);  // 0: not coloured
 void device_kmer_index_info(const KmerIndex *ix, mtg_kmer_index_info *out);
 void device_kmer_index_query(const KmerIndex *ix, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid,
                              uint64_t *found, uint64_t *present_bits, uint64_t *valid_bits, KmerQueryTimes *times);
@@ -173,6 +180,13 @@ struct KmerAbundanceTimes {
 };
 void device_kmer_index_abundance(const KmerIndex *ix, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid,
                                  uint64_t *found, uint64_t *sum, uint32_t *min, uint32_t *max, uint32_t *per_window, KmerAbundanceTimes *times);
+// The query plus per_color ([n * n_colors], row-major): the found windows of record r whose class's mask has bit c; per_window, if
+// given ([off[n]]): the mask at every found window's global start position, 0 elsewhere. stats_ms belongs to the coloured compaction.
+struct KmerColorTimes {
+    double stats_ms = 0, upload_ms = 0, pack_ms = 0, probe_ms = 0, download_ms = 0;
+};
+void device_kmer_index_colors(const KmerIndex *ix, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid,
+                              uint64_t *found, uint32_t *per_color, uint64_t *per_window, KmerColorTimes *times);
 // compact_device.hip: the maximal unitigs of the k-mer set of arbitrary sequences (the file's header and DESIGN.md 16 state the
 // contract), as an ordinary sequence store. times: host wall clock of upload, download and the whole call, HIP-event time of the
 // kernel phases, the pointer-jumping rounds, the bytes the kernels must move at the least, the arena's peak of live bytes.
@@ -191,6 +205,12 @@ UnitigStore *device_compact_unitigs(const char *data, const uint64_t *off, uint6
 UnitigStore *device_compact_unitigs_counted(const char *data, const uint64_t *off, uint64_t n_rec, uint64_t k, uint64_t min_abundance, int device_id,
                                             mtg_compaction *stats_out, mtg_abundance *abundance_out, std::vector<uint64_t> *unitig_sums,
                                             CompactTimes *times, std::vector<uint32_t> *kmer_counts = nullptr);
+// ... with a colour per record: the counted call that hands out the counts, plus every kept k-mer's colour mask
+// (indexed like kmer_counts) and the statistics over the masks. stats_ms: HIP-event time of the statistics kernel (part of emit_ms).
+UnitigStore *device_compact_unitigs_colored(const char *data, const uint64_t *off, uint64_t n_rec, uint64_t k, uint64_t min_abundance,
+                                            const uint8_t *record_colors, uint64_t n_colors, int device_id, mtg_compaction *stats_out,
+                                            mtg_abundance *abundance_out, std::vector<uint64_t> *unitig_sums, std::vector<uint32_t> *kmer_counts,
+                                            std::vector<uint64_t> *kmer_colors, mtg_color_stats *color_stats, CompactTimes *times, double *stats_ms);
 // fasta_in.cpp: read_fasta_records without an alphabet rule and without case folding (the queries of the k-mer index), plus the
 // record names (the header text behind `>` up to the first white space) as a second store
 UnitigStore *read_fasta_records_named(const char *path, UnitigStore **names_out);

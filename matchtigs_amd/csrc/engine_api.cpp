@@ -743,6 +743,43 @@ void mtg_last_kmer_abundance_times(double out[4]) {
     const KmerAbundanceTimes &t = g_last_kmer_abundance;
     out[0] = t.upload_ms; out[1] = t.pack_ms; out[2] = t.probe_ms; out[3] = t.download_ms;
 }
+// ---- ... and which inputs carry them ----
+static thread_local KmerColorTimes g_last_kmer_color;
+mtg_kmer_index *mtg_kmer_index_build_annotated(const char *seq, const uint64_t *off, uint64_t n, uint64_t k, const uint32_t *weights,
+                                               uint64_t n_weights, const uint64_t *colors, uint64_t n_color_words, uint64_t n_colors,
+                                               int locating, int device_id) {
+    if (!weights && n_weights) MTG_DIE("mtg_kmer_index_build_annotated: %llu weights but no array", (unsigned long long)n_weights);
+    if (!colors && n_color_words) MTG_DIE("mtg_kmer_index_build_annotated: %llu colour words but no array", (unsigned long long)n_color_words);
+    const KmerWeights w{weights, n_weights};
+    const KmerColors c{colors, n_color_words, n_colors};
+    return new mtg_kmer_index{device_kmer_index_build(seq, off, n, k, device_id, locating != 0, &g_last_kmer_query, weights ? &w : nullptr,
+                                                      colors ? &c : nullptr)};
+}
+mtg_kmer_index *mtg_kmer_index_build_annotated_store(const mtg_unitigs *store, uint64_t k, const uint32_t *weights, uint64_t n_weights,
+                                                     const uint64_t *colors, uint64_t n_color_words, uint64_t n_colors, int locating,
+                                                     int device_id) {
+    if (!store) MTG_DIE("mtg_kmer_index_build_annotated_store: null argument");
+    const UnitigStore &s = *store->s;
+    return mtg_kmer_index_build_annotated(s.data.data(), s.off.data(), s.off.size() - 1, k, weights, n_weights, colors, n_color_words, n_colors,
+                                          locating, device_id);
+}
+int mtg_kmer_index_is_colored(const mtg_kmer_index *ix) {
+    if (!ix) MTG_DIE("mtg_kmer_index_is_colored: null argument");
+    return device_kmer_index_n_colors(ix->ix) ? 1 : 0;
+}
+uint64_t mtg_kmer_index_n_colors(const mtg_kmer_index *ix) {
+    if (!ix) MTG_DIE("mtg_kmer_index_n_colors: null argument");
+    return device_kmer_index_n_colors(ix->ix);
+}
+void mtg_kmer_index_colors(const mtg_kmer_index *ix, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid,
+                           uint64_t *found, uint32_t *per_color, uint64_t *per_window) {
+    if (!ix) MTG_DIE("mtg_kmer_index_colors: null argument");
+    device_kmer_index_colors(ix->ix, seq, off, n, kmers, valid, found, per_color, per_window, &g_last_kmer_color);
+}
+void mtg_last_kmer_color_times(double out[5]) {
+    const KmerColorTimes &t = g_last_kmer_color;
+    out[0] = t.stats_ms; out[1] = t.upload_ms; out[2] = t.pack_ms; out[3] = t.probe_ms; out[4] = t.download_ms;
+}
 void mtg_last_kmer_query_times(double out[6]) {
     const KmerQueryTimes &t = g_last_kmer_query;
     out[0] = t.build_upload_ms; out[1] = t.build_pack_ms; out[2] = t.build_insert_ms;
@@ -815,6 +852,39 @@ const uint32_t *mtg_kmer_counts_array(const mtg_kmer_counts *counts) {
     return counts->v.data();
 }
 void mtg_kmer_counts_free(mtg_kmer_counts *counts) { delete counts; }
+struct mtg_kmer_colors { std::vector<uint64_t> v; };
+void mtg_compact_unitigs_colored(const char *data, const uint64_t *offsets, uint64_t n, uint64_t k, uint64_t min_abundance,
+                                 const uint8_t *record_colors, uint64_t n_colors, int device_id, mtg_unitigs **out, mtg_compaction *stats,
+                                 mtg_abundance *abundance, mtg_abundance_sums **sums, mtg_kmer_counts **kmer_counts,
+                                 mtg_kmer_colors **kmer_colors, mtg_color_stats *color_stats) {
+    if (!out || !sums || !kmer_counts || !kmer_colors || !color_stats) MTG_DIE("mtg_compact_unitigs_colored: null argument");
+    if (min_abundance == 0) MTG_DIE("mtg_compact_unitigs_colored: min_abundance must be >= 1");
+    mtg_abundance_sums *s = new mtg_abundance_sums();
+    mtg_kmer_counts *c = new mtg_kmer_counts();
+    mtg_kmer_colors *m = new mtg_kmer_colors();
+    *out = new mtg_unitigs{device_compact_unitigs_colored(data, offsets, n, k, min_abundance, record_colors, n_colors, device_id, stats, abundance,
+                                                          &s->v, &c->v, &m->v, color_stats, &g_last_compact, &g_last_kmer_color.stats_ms)};
+    *sums = s;
+    *kmer_counts = c;
+    *kmer_colors = m;
+}
+void mtg_compact_unitigs_colored_store(const mtg_unitigs *in, uint64_t k, uint64_t min_abundance, const uint8_t *record_colors,
+                                       uint64_t n_colors, int device_id, mtg_unitigs **out, mtg_compaction *stats, mtg_abundance *abundance,
+                                       mtg_abundance_sums **sums, mtg_kmer_counts **kmer_counts, mtg_kmer_colors **kmer_colors,
+                                       mtg_color_stats *color_stats) {
+    if (!in) MTG_DIE("mtg_compact_unitigs_colored_store: null argument");
+    mtg_compact_unitigs_colored(in->s->data.data(), in->s->off.data(), in->s->off.size() - 1, k, min_abundance, record_colors, n_colors, device_id,
+                                out, stats, abundance, sums, kmer_counts, kmer_colors, color_stats);
+}
+uint64_t mtg_kmer_colors_count(const mtg_kmer_colors *colors) {
+    if (!colors) MTG_DIE("mtg_kmer_colors_count: null argument");
+    return colors->v.size();
+}
+const uint64_t *mtg_kmer_colors_array(const mtg_kmer_colors *colors) {
+    if (!colors) MTG_DIE("mtg_kmer_colors_array: null argument");
+    return colors->v.data();
+}
+void mtg_kmer_colors_free(mtg_kmer_colors *colors) { delete colors; }
 void mtg_last_compact_times(double out[12]) {
     const CompactTimes &t = g_last_compact;
     out[0] = t.upload_ms; out[1] = t.pack_ms; out[2] = t.insert_ms; out[3] = t.ids_ms; out[4] = t.nodes_ms; out[5] = t.rank_ms;

@@ -58,6 +58,16 @@
 //             (thread, record) that leave by one atomicAdd, one atomicMin and one atomicMax when the record changes, never per window.
 //             per_window: a thread is the only writer of its RUN positions, zeros included
 // A call takes 8 + 4 + 4 B per record and, with per_window, 4 B per query base beside the query's store.
+//
+// Colours (a COLOURED index only, mtg_kmer_index_build_annotated). The caller gives one 64-bit mask per window of the
+// indexed sequences; color(class) = the mask of the class's smallest window start, gathered like the weights (color_gather_kernel,
+// 8 B per slot; an index with both payloads runs both gathers off one where[]). A colour call answers like a query without bit arrays
+// and adds per record and colour c < n_colors the found windows whose class's mask has bit c, and optionally the mask at every window:
+//   probe     color_query_kernel: the query's walk (probe_run); the thread keeps (record, mask, run length): a found window with the
+//             same record and mask only lengthens the run -- absent and invalid windows in between do not break it, only sums leave
+//             --, and a change of either, or the end of the walk, flushes it: one atomicAdd(per_color[r C + c], run) per set bit c.
+//             Worst case: masks that alternate from window to window cost popcount(mask) atomics per window.
+// A call takes 4 C B per record and, with per_window, 8 B per query base beside the query's store.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -337,6 +347,57 @@ __global__ __launch_bounds__(hu::EB) void abundance_kernel(IndexArgs a, const un
         for (const uint64_t end = p0 + RUN < n_bases ? p0 + RUN : n_bases; next_p < end; next_p++) per_window[next_p] = 0;
 }
 
+// ---- colours ----
+// weight_gather_kernel for a 64-bit payload: color[s] = the caller's mask of the window where[s]; 0 for an empty slot
+__global__ __launch_bounds__(hu::EB) void color_gather_kernel(const unsigned long long *table, const unsigned long long *where,
+                                                               const unsigned long long *off, uint64_t n_rec, const unsigned long long *win_off,
+                                                               const unsigned long long *colors, uint64_t n_colors_words, uint64_t slots,
+                                                               unsigned long long *color, unsigned int *err) {
+    const uint64_t s = hu::gid();
+    if (s >= slots) return;
+    unsigned long long c = 0;
+    if (table[s] != EMPTY_SLOT) {
+        const uint64_t t = where[s], r = record_of(off, n_rec, t), i = win_off[r] + (t - off[r]);
+        if (i < n_colors_words) c = colors[i];
+        else atomicOr(err, 2u);  // (every occupied slot has a window's position: never)
+    }
+    color[s] = c;
+}
+
+// query_kernel's walk; per found window the mask of its class. counts: [2 n_rec] valid, found; per_color: [n_rec * C], zeroed;
+// (no mask has a bit from C on: the build checked); per_window: [n_bases] or null.
+template <bool WIDE>
+__global__ __launch_bounds__(hu::EB) void color_query_kernel(IndexArgs a, const unsigned long long *bad, uint64_t n_bases, uint64_t n_rec,
+                                                             unsigned long long *counts, const unsigned long long *color, uint32_t C,
+                                                             uint32_t *per_color, unsigned long long *per_window) {
+    const uint64_t p0 = hu::gid() * RUN;
+    if (p0 >= n_bases) return;
+    unsigned long long vbits = 0, pbits = 0, mask = 0;
+    uint64_t rec = 0, next_p = p0;  // next_p: the first position of the run that per_window has not been told yet
+    uint32_t run = 0;               // found windows of record `rec` with the mask `mask` since the last flush (at most RUN)
+    auto flush = [&]() {
+        for (unsigned long long m = run ? mask : 0ull; m; m &= m - 1)
+            atomicAdd(&per_color[rec * C + (uint32_t)__builtin_ctzll(m)], run);
+        run = 0;
+    };
+    probe_run<WIDE>(a, bad, p0, n_bases, n_rec, counts, vbits, pbits, [&](uint64_t q, uint64_t r, uint64_t slot) {
+        const unsigned long long m = color[slot];
+        if (r != rec || m != mask) {
+            flush();
+            rec = r;
+            mask = m;
+        }
+        run++;
+        if (per_window) {
+            for (; next_p < q; next_p++) per_window[next_p] = 0;
+            per_window[next_p++] = m;
+        }
+    });
+    flush();
+    if (per_window)
+        for (const uint64_t end = p0 + RUN < n_bases ? p0 + RUN : n_bases; next_p < end; next_p++) per_window[next_p] = 0;
+}
+
 // offsets of one set: start at 0, do not decrease; returns its windows
 uint64_t check_offsets(const char *fn, const char *data, const uint64_t *off, uint64_t n, uint64_t k) {
     if (!off || (n && off[n] && !data)) MTG_DIE("%s: null argument", fn);
@@ -361,10 +422,12 @@ struct KmerIndex {
     unsigned long long *where = nullptr;  // locating: [info.slots] the smallest window start of the slot's class
     unsigned long long *off = nullptr;    // locating: [info.records + 1]
     uint32_t *weight = nullptr;           // weighted: [info.slots] the weight of the slot's class
+    unsigned long long *color = nullptr;  // coloured: [info.slots] the colour mask of the slot's class
+    uint64_t n_colors = 0;                // coloured: 1 .. 64
 };
 
 KmerIndex *device_kmer_index_build(const char *seq, const uint64_t *off, uint64_t n, uint64_t k, int device_id, bool locating,
-                                   KmerQueryTimes *times, const KmerWeights *weights) {
+                                   KmerQueryTimes *times, const KmerWeights *weights, const KmerColors *colors) {
     if (k < 1) MTG_DIE("mtg_kmer_index_build: k must be >= 1");
     if (k > 0xFFFFFFFFull) MTG_DIE("mtg_kmer_index_build: k too large");
     KmerIndex *ix = new KmerIndex();
@@ -378,6 +441,16 @@ KmerIndex *device_kmer_index_build(const char *seq, const uint64_t *off, uint64_
     if (weights && weights->n != info.occurrences)
         MTG_DIE("mtg_kmer_index_build_weighted: %llu weights for %llu windows", (unsigned long long)weights->n, (unsigned long long)info.occurrences);
     if (weights && weights->n && !weights->w) MTG_DIE("mtg_kmer_index_build_weighted: null argument");
+    if (colors && (colors->n_colors < 1 || colors->n_colors > 64))
+        MTG_DIE("mtg_kmer_index_build_annotated: %llu colours; 1 .. 64 are served", (unsigned long long)colors->n_colors);
+    if (colors && colors->n != info.occurrences)
+        MTG_DIE("mtg_kmer_index_build_annotated: %llu colour words for %llu windows", (unsigned long long)colors->n, (unsigned long long)info.occurrences);
+    if (colors && colors->n && !colors->c) MTG_DIE("mtg_kmer_index_build_annotated: null argument");
+    if (colors && colors->n_colors < 64)  // (the probe adds into per_color[r C + c] for every set bit c)
+        for (uint64_t i = 0; i < colors->n; i++)
+            if (colors->c[i] >> colors->n_colors)
+                MTG_DIE("mtg_kmer_index_build_annotated: mask %llu has a colour beyond the %llu given", (unsigned long long)i,
+                        (unsigned long long)colors->n_colors);
     if (device_id < 0 || device_count() <= device_id) MTG_DIE("no HIP device %d for the k-mer index (there is no CPU path)", device_id);
     HIP_CHECK(hipSetDevice(device_id));
     ix->device_id = device_id;
@@ -391,7 +464,7 @@ KmerIndex *device_kmer_index_build(const char *seq, const uint64_t *off, uint64_
     hu::device_malloc(&ix->table, info.slots * 8);
     HIP_CHECK(hipMemsetAsync(ix->table, 0xFF, info.slots * 8, st));
     ix->locating = locating;
-    const bool positions = locating || weights;  // the insert notes the smallest window start of every class
+    const bool positions = locating || weights || colors;  // the insert notes the smallest window start of every class
     if (positions) {
         hu::device_malloc(&ix->where, info.slots * 8);
         HIP_CHECK(hipMemsetAsync(ix->where, 0xFF, info.slots * 8, st));
@@ -412,24 +485,38 @@ KmerIndex *device_kmer_index_build(const char *seq, const uint64_t *off, uint64_
         index_count_kernel<<<(unsigned)std::min<uint64_t>(hu::grid_for(info.slots / 2), 8192), hu::EB, 0, st>>>(ix->table, info.slots, store.small.d + 2);
         HIP_CHECK(hipGetLastError());
     }
-    if (weights) {  // (also for an index without windows: its zeroed table is still probed)
-        hu::device_malloc(&ix->weight, info.slots * 4);
+    if (weights || colors) {  // (also for an index without windows: its zeroed table is still probed)
+        if (weights) hu::device_malloc(&ix->weight, info.slots * 4);
+        if (colors) {
+            hu::device_malloc(&ix->color, info.slots * 8);
+            ix->n_colors = colors->n_colors;
+        }
         if (info.occurrences) {
             std::vector<unsigned long long> win_off(n + 1, 0);
             for (uint64_t r = 0; r < n; r++) win_off[r + 1] = win_off[r] + (off[r + 1] - off[r] >= k ? off[r + 1] - off[r] - k + 1 : 0);
-            unsigned long long *d_win_off = nullptr;
+            unsigned long long *d_win_off = nullptr, *d_colors = nullptr;
             uint32_t *d_weights = nullptr;
             hu::device_malloc(&d_win_off, (n + 1) * 8);
-            hu::device_malloc(&d_weights, weights->n * 4);
             hu::upload_sliced(d_win_off, win_off.data(), (n + 1) * 8, st, device_id);
-            hu::upload_sliced(d_weights, weights->w, weights->n * 4, st, device_id);
-            weight_gather_kernel<<<hu::grid_for(info.slots), hu::EB, 0, st>>>(ix->table, ix->where, store.off, n, d_win_off, d_weights, weights->n,
-                                                                             info.slots, ix->weight, store.small.err());
+            if (weights) {
+                hu::device_malloc(&d_weights, weights->n * 4);
+                hu::upload_sliced(d_weights, weights->w, weights->n * 4, st, device_id);
+                weight_gather_kernel<<<hu::grid_for(info.slots), hu::EB, 0, st>>>(ix->table, ix->where, store.off, n, d_win_off, d_weights, weights->n,
+                                                                                 info.slots, ix->weight, store.small.err());
+            }
+            if (colors) {
+                hu::device_malloc(&d_colors, colors->n * 8);
+                hu::upload_sliced(d_colors, colors->c, colors->n * 8, st, device_id);
+                color_gather_kernel<<<hu::grid_for(info.slots), hu::EB, 0, st>>>(ix->table, ix->where, store.off, n, d_win_off, d_colors, colors->n,
+                                                                                info.slots, ix->color, store.small.err());
+            }
             HIP_CHECK(hipGetLastError());
-            hu::device_free(d_win_off);  // (synchronises: the gather is done)
+            hu::device_free(d_win_off);  // (synchronises: the gathers are done)
             hu::device_free(d_weights);
+            hu::device_free(d_colors);
         } else {
-            HIP_CHECK(hipMemsetAsync(ix->weight, 0, info.slots * 4, st));
+            if (weights) HIP_CHECK(hipMemsetAsync(ix->weight, 0, info.slots * 4, st));
+            if (colors) HIP_CHECK(hipMemsetAsync(ix->color, 0, info.slots * 8, st));
         }
     }
     ev.mark(1, st);
@@ -448,16 +535,18 @@ KmerIndex *device_kmer_index_build(const char *seq, const uint64_t *off, uint64_
     if (locating) {
         ix->off = store.take_off();
         info.device_bytes += info.slots * 8 + (n + 1) * 8;
-    } else if (ix->where) {  // weighted only: the positions have done their work
+    } else if (ix->where) {  // weighted or coloured only: the positions have done their work
         hu::device_free(ix->where);
         ix->where = nullptr;
     }
     if (weights) info.device_bytes += info.slots * 4;
+    if (colors) info.device_bytes += info.slots * 8;
     return ix;
 }
 
 bool device_kmer_index_is_locating(const KmerIndex *ix) { return ix->locating; }
 bool device_kmer_index_is_weighted(const KmerIndex *ix) { return ix->weight != nullptr; }
+uint64_t device_kmer_index_n_colors(const KmerIndex *ix) { return ix->color ? ix->n_colors : 0; }
 
 void device_kmer_index_info(const KmerIndex *ix, mtg_kmer_index_info *out) { *out = ix->info; }
 
@@ -468,6 +557,7 @@ void device_kmer_index_free(KmerIndex *ix) {
     hu::device_free_on(ix->device_id, ix->where);
     hu::device_free_on(ix->device_id, ix->off);
     hu::device_free_on(ix->device_id, ix->weight);
+    hu::device_free_on(ix->device_id, ix->color);
     delete ix;
 }
 
@@ -575,6 +665,62 @@ void device_kmer_index_abundance(const KmerIndex *ix, const char *seq, const uin
     }
     hu::device_free(d_counts);
     hu::device_free(d_minmax);
+    hu::device_free(d_per_window);
+}
+
+void device_kmer_index_colors(const KmerIndex *ix, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid,
+                              uint64_t *found, uint32_t *per_color, uint64_t *per_window, KmerColorTimes *times) {
+    if (!ix->color) MTG_DIE("mtg_kmer_index_colors: the index keeps no colours (build it with mtg_kmer_index_build_annotated)");
+    const uint64_t k = ix->info.k, C = ix->n_colors;
+    (void)check_offsets("mtg_kmer_index_colors", seq, off, n, k);
+    if (n && (!kmers || !valid || !found || !per_color)) MTG_DIE("mtg_kmer_index_colors: null argument");
+    const uint64_t n_bases = off[n];
+    if (n_bases >= POS_LIMIT) MTG_DIE("mtg_kmer_index_colors: %llu bases; the limit is 2^40 - 2", (unsigned long long)n_bases);
+    for (uint64_t r = 0; r < n; r++) {
+        const uint64_t len = off[r + 1] - off[r];
+        kmers[r] = len >= k ? len - k + 1 : 0;
+        if (kmers[r] >> 32) MTG_DIE("mtg_kmer_index_colors: record %llu has %llu windows; the per-colour counters are 32-bit",
+                                    (unsigned long long)r, (unsigned long long)kmers[r]);
+        valid[r] = found[r] = 0;
+    }
+    std::fill(per_color, per_color + n * C, 0u);
+    if (times) times->upload_ms = times->pack_ms = times->probe_ms = times->download_ms = 0;
+    if (n_bases == 0) return;  // nothing to look at
+    HIP_CHECK(hipSetDevice(ix->device_id));
+    hipStream_t st = nullptr;
+    MaskedSeqStore store(seq, off, n, st, ix->device_id);
+    unsigned long long *d_counts = nullptr, *d_per_window = nullptr;  // d_counts: valid, found
+    uint32_t *d_per_color = nullptr;
+    hu::device_malloc(&d_counts, 2 * n * 8);
+    hu::device_malloc(&d_per_color, n * C * 4);
+    if (per_window) hu::device_malloc(&d_per_window, n_bases * 8);
+    PhaseEvents<2> ev;
+    ev.mark(0, st);
+    HIP_CHECK(hipMemsetAsync(d_counts, 0, 2 * n * 8, st));
+    HIP_CHECK(hipMemsetAsync(d_per_color, 0, n * C * 4, st));
+    IndexArgs a{};
+    a.packed = store.packed; a.off = store.off; a.index_packed = ix->packed; a.table = ix->table; a.slots = ix->info.slots;
+    kw::window_args_set_k(a, k);
+    const unsigned grid = hu::grid_for((n_bases + RUN - 1) / RUN);  // (one thread per run: every word of per_window is written)
+    if (k >= 32) color_query_kernel<true><<<grid, hu::EB, 0, st>>>(a, store.bad, n_bases, n, d_counts, ix->color, (uint32_t)C, d_per_color, d_per_window);
+    else color_query_kernel<false><<<grid, hu::EB, 0, st>>>(a, store.bad, n_bases, n, d_counts, ix->color, (uint32_t)C, d_per_color, d_per_window);
+    HIP_CHECK(hipGetLastError());
+    ev.mark(1, st);
+    HIP_CHECK(hipStreamSynchronize(st));
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_CHECK(hipMemcpyAsync(valid, d_counts, n * 8, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(found, d_counts + n, n * 8, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    hu::download_sliced(per_color, d_per_color, n * C * 4, st, ix->device_id);
+    if (per_window) hu::download_sliced(per_window, d_per_window, n_bases * 8, st, ix->device_id);
+    if (times) {
+        times->upload_ms = store.upload_ms;
+        times->pack_ms = store.pack_ms;
+        times->probe_ms = ev.ms(0, 1);
+        times->download_ms = ms_since(t0);
+    }
+    hu::device_free(d_counts);
+    hu::device_free(d_per_color);
     hu::device_free(d_per_window);
 }
 
