@@ -697,6 +697,48 @@ void mtg_kmer_index_colors(const mtg_kmer_index *ix, const char *seq, const uint
 /* In ms: {the colour statistics kernel of the last mtg_compact_unitigs_colored on this thread (HIP events); of the last
  * mtg_kmer_index_colors: upload (host clock), pack, probe -- HIP events around the kernels --, download (host clock)}. */
 void mtg_last_kmer_color_times(double out[5]);
+/* MONOCHROMATIC UNITIGS and COLOUR CLASSES. mtg_compact_unitigs_colored_classes is mtg_compact_unitigs_colored plus
+ * *classes, the dictionary of the output store's masks. Number the windows of *out i = 0 .. N - 1 in window order (the indexing of
+ * *kmer_colors). A RUN is a maximal stretch of consecutive windows of ONE unitig with equal masks. The classes are the distinct masks,
+ * numbered 0, 1, ... in the order of the first window that shows them; per class c: masks[c], kmers[c] (the windows with that mask; the
+ * sum is N), runs[c] (the sum is the number of runs), first[c] (the first window that shows it: strictly increasing in c); per
+ * window: kmer_class[i], so masks[kmer_class[i]] = kmer_colors[i].
+ * split = 0: *out, *stats, *abundance, *sums, *kmer_counts, *kmer_colors and *color_stats are mtg_compact_unitigs_colored's, byte for
+ * byte. split = 1: the compaction's rule for a passable node gains a clause -- the k-mer that enters the node and the k-mer that
+ * leaves it have equal masks -- so every unitig of *out is MONOCHROMATIC (one run; the sum of runs is stats->unitigs); a closed walk
+ * whose k-mers do not share one mask opens into chains, each with its own leader, direction and place in the order. *out, *stats,
+ * *sums, *kmer_counts and *kmer_colors then describe the split store; the scalars and the spectrum of *abundance and all of *color_stats
+ * are functions of the k-mer set and equal the unsplit call's. With one colour, or wherever no passable node separates two masks, the
+ * split store is the unsplit one. Exact integers that depend on the input, min_abundance, the colours and split alone. split outside
+ * {0, 1} or a null out-pointer aborts; the other arguments as for mtg_compact_unitigs_colored. */
+typedef struct mtg_color_classes mtg_color_classes;
+void mtg_compact_unitigs_colored_classes(const char *data, const uint64_t *offsets, uint64_t n, uint64_t k, uint64_t min_abundance,
+                                         const uint8_t *record_colors, uint64_t n_colors, int split, int device_id, mtg_unitigs **out,
+                                         mtg_compaction *stats, mtg_abundance *abundance, mtg_abundance_sums **sums,
+                                         mtg_kmer_counts **kmer_counts, mtg_kmer_colors **kmer_colors, mtg_color_stats *color_stats,
+                                         mtg_color_classes **classes /* mtg_color_classes_free */);
+void mtg_compact_unitigs_colored_classes_store(const mtg_unitigs *in, uint64_t k, uint64_t min_abundance, const uint8_t *record_colors,
+                                               uint64_t n_colors, int split, int device_id, mtg_unitigs **out, mtg_compaction *stats,
+                                               mtg_abundance *abundance, mtg_abundance_sums **sums, mtg_kmer_counts **kmer_counts,
+                                               mtg_kmer_colors **kmer_colors, mtg_color_stats *color_stats, mtg_color_classes **classes);
+/* The same dictionary for masks handed in: kmer_colors, n masks in window order of a store whose unitig u has unitig_kmers[u] k-mers
+ * (n_unitigs entries >= 1 that sum to n; fewer than 2^31 - 1 k-mers). A mask of 0, or lengths that do not fit, abort. What
+ * mtg_compact_unitigs_colored_classes returns equals this call on its own *kmer_colors and unitig lengths. */
+void mtg_color_classes_build(const uint64_t *kmer_colors, uint64_t n, const uint64_t *unitig_kmers, uint64_t n_unitigs, int device_id,
+                             mtg_color_classes **classes);
+uint64_t mtg_color_classes_count(const mtg_color_classes *classes);        /* the classes */
+const uint64_t *mtg_color_classes_masks(const mtg_color_classes *classes); /* count entries each; valid until mtg_color_classes_free */
+const uint64_t *mtg_color_classes_kmers(const mtg_color_classes *classes);
+const uint64_t *mtg_color_classes_runs(const mtg_color_classes *classes);
+const uint64_t *mtg_color_classes_first(const mtg_color_classes *classes);
+uint64_t mtg_color_classes_kmer_class_count(const mtg_color_classes *classes); /* the store's k-mers */
+const uint32_t *mtg_color_classes_kmer_class(const mtg_color_classes *classes);
+void mtg_color_classes_free(mtg_color_classes *classes);
+/* In ms, of the last mtg_compact_unitigs_colored_classes on this thread: {run heads, class table, class ids, counts -- HIP events
+ * around the kernels --, download (host clock)}. */
+void mtg_last_color_class_times(double out[5]);
+/* {the classes the counts kernel keeps in LDS, its largest grid, its block}: what an input must exceed to reach the kernel's other paths. */
+void mtg_color_class_limits(uint64_t out[3]);
 /* mtg_read_sequences without an alphabet rule: every byte of a sequence line is kept as it is (`N`, IUPAC codes, lower case), for
  * the queries of a k-mer index. *names_out = the record names as a second store with the same accessors: the header text behind `>`
  * up to the first white space. */

@@ -30,6 +30,9 @@ With several `--seq-in` files every file is a COLOUR (a sample, a haplotype; at 
 files show it, on either strand: `--color-matrix-out` writes how many k-mers each file has and each pair of files
 shares, `--unitig-colors-out` the colours along every unitig as runs `count:hexmask` (bit i = file i), and `--query-colors-out` (with
 `--query-fa`) per query record how many of its k-mers each file carries.
+`--monochromatic-unitigs` cuts the unitigs wherever the set of files changes, so that every k-mer of a unitig is carried by the same
+files; `--color-classes-out` writes the distinct sets of files (the colour classes, numbered in the order the unitigs show them) with
+their k-mers and runs, and `--unitig-color-classes-out` the classes along every unitig as runs `count:class`.
 """
 from __future__ import annotations
 
@@ -114,9 +117,19 @@ def main(argv=None) -> int:
     ap.add_argument("--query-colors-out", metavar="PATH",
                     help="with --seq-in, --query-fa and --query-out: TSV (.gz => gzip) with one row per query record: record, kmers, "
                          "valid, found, then per --seq-in file the found k-mers that file carries")
+    ap.add_argument("--monochromatic-unitigs", action="store_true",
+                    help="with --seq-in, each file one colour: cut the unitigs wherever the set of files that carry the k-mers changes; "
+                         "every output then sees the split unitigs (not in the reference)")
+    ap.add_argument("--color-classes-out", metavar="PATH",
+                    help="with --seq-in: TSV (.gz => gzip) class, mask, carriers, kmers, runs: one row per distinct set of files, numbered "
+                         "in the order the unitigs show them; mask as in --unitig-colors-out, carriers its files")
+    ap.add_argument("--unitig-color-classes-out", metavar="PATH",
+                    help="with --seq-in: per record of --unitigs-fa-out a line of runs count:class over its k-mers, left to right; the "
+                         "classes are those of --color-classes-out (.gz => gzip)")
     args = ap.parse_args(argv)
 
-    colored = bool(args.color_matrix_out or args.unitig_colors_out or args.query_colors_out)
+    classed = bool(args.monochromatic_unitigs or args.color_classes_out or args.unitig_color_classes_out)
+    colored = bool(args.color_matrix_out or args.unitig_colors_out or args.query_colors_out or classed)
     if colored and args.seq_in is not None and len(args.seq_in) > MAX_COLORS:
         ap.error(f"{len(args.seq_in)} --seq-in files: at most {MAX_COLORS} files can be told apart as colours")
 
@@ -148,7 +161,9 @@ def main(argv=None) -> int:
         ap.error("--query-colors-out needs --seq-in, --query-fa and --query-out")
     for flag, value in (("--min-abundance", args.min_abundance), ("--kmer-spectrum-out", args.kmer_spectrum_out),
                         ("--unitig-abundance-out", args.unitig_abundance_out), ("--unitig-kmer-abundance-out", args.unitig_kmer_abundance_out),
-                        ("--color-matrix-out", args.color_matrix_out), ("--unitig-colors-out", args.unitig_colors_out)):
+                        ("--color-matrix-out", args.color_matrix_out), ("--unitig-colors-out", args.unitig_colors_out),
+                        ("--monochromatic-unitigs", args.monochromatic_unitigs or None), ("--color-classes-out", args.color_classes_out),
+                        ("--unitig-color-classes-out", args.unitig_color_classes_out)):
         if value is not None and args.seq_in is None:
             ap.error(f"{flag} needs --seq-in")
     if args.min_abundance is not None and args.min_abundance < 1:
@@ -156,7 +171,7 @@ def main(argv=None) -> int:
     for flag, value in (("--min-base-quality", args.min_base_quality), ("--query-min-base-quality", args.query_min_base_quality)):
         if value is not None and not 0 <= value <= 93:
             ap.error(f"{flag} must be in 0..93")
-    if not (args.color_matrix_out or args.unitig_colors_out or args.kmer_spectrum_out or args.unitig_abundance_out or args.unitig_kmer_abundance_out or args.query_fa or args.greedytigs_fa_out or args.eulertigs_fa_out or args.greedytigs_gfa_out or args.eulertigs_gfa_out
+    if not (args.color_classes_out or args.unitig_color_classes_out or args.color_matrix_out or args.unitig_colors_out or args.kmer_spectrum_out or args.unitig_abundance_out or args.unitig_kmer_abundance_out or args.query_fa or args.greedytigs_fa_out or args.eulertigs_fa_out or args.greedytigs_gfa_out or args.eulertigs_gfa_out
             or args.greedytigs_duplication_bitvector_out or args.matchtigs_fa_out or args.matchtigs_gfa_out or args.verify_fa or args.unitigs_fa_out):
         ap.error("nothing to do: give --greedytigs-fa-out / --greedytigs-gfa-out and/or --eulertigs-fa-out / --eulertigs-gfa-out")
 
@@ -205,7 +220,8 @@ def _run(api, args, fastq) -> int:
     if args.bcalm_in is not None:
         graph, store = api.read_bcalm2(args.bcalm_in, args.k)
     elif args.seq_in is not None:  # sequences -> unitigs (GPU compaction) -> graph (the --fa-in join on the same store)
-        colored = bool(args.color_matrix_out or args.unitig_colors_out or args.query_colors_out)  # 
+        classed = bool(args.monochromatic_unitigs or args.color_classes_out or args.unitig_color_classes_out)  # 
+        colored = bool(args.color_matrix_out or args.unitig_colors_out or args.query_colors_out or classed)  # 
         record_colors = [] if colored else None
         seqs, pieces_cut = _read_seq_in(api, args, fastq, record_colors)
         abundance = colors = None
@@ -215,7 +231,10 @@ def _run(api, args, fastq) -> int:
             store, compaction = api.compact_unitigs(seqs, args.k, args.device)
         else:  # the counted compaction; an output flag alone counts without filtering
             min_abundance = args.min_abundance or 1
-            if colored:  # (the counted call that hands out the counts, plus the colours)
+            if classed:  # (the coloured call plus the class dictionary, over unitigs cut at the colour changes if asked for)
+                store, compaction, abundance, colors, classes = api.compact_unitigs_colored_classes(
+                    seqs, args.k, record_colors, len(args.seq_in), min_abundance, args.monochromatic_unitigs, args.device)
+            elif colored:  # (the counted call that hands out the counts, plus the colours)
                 store, compaction, abundance, colors = api.compact_unitigs_colored(seqs, args.k, record_colors, len(args.seq_in), min_abundance,
                                                                                    args.device)
             elif per_kmer:
@@ -235,12 +254,19 @@ def _run(api, args, fastq) -> int:
                 _write_color_matrix(args, colors)
             if args.unitig_colors_out:
                 _write_unitig_colors(args, store, colors)
+            if classed:
+                if args.color_classes_out:
+                    _write_color_classes(args, classes)
+                if args.unitig_color_classes_out:
+                    _write_unitig_color_classes(args, store, classes)
+                print(f"Colour classes: {classes.describe()}", file=sys.stderr)
         graph = api.Bigraph.from_sequences(store.arrays(), args.k, args.device)
     else:
         graph, store = api.read_fasta(args.fa_in, args.k, args.device)
     loaded = f"Loaded {len(store)} unitigs: {graph.node_count()} nodes, {graph.edge_count()} edges in {time.perf_counter() - t0:.1f}s"
     if args.seq_in is not None:
         loaded += f" (compacted from {compaction.describe()}; "
+        loaded += f"cut into {compaction.unitigs} monochromatic unitigs; " if args.monochromatic_unitigs else ""
         loaded += f"{abundance.describe()}; " if abundance is not None and counted else ""
         loaded += f"{pieces_cut} non-ACGT runs cut)"
     print(loaded, file=sys.stderr)
@@ -437,6 +463,34 @@ def _write_unitig_colors(args, store, colors) -> None:
             lo, hi = (int(ends[at - 1]) if at else 0), int(ends[end - 1])
             f.write(_hex_runs(colors.kmer_colors[lo:hi], kmers[at:end]))
             at = end
+
+
+def _write_color_classes(args, classes) -> None:
+    """`--color-classes-out`: one row per colour class, in the order the unitigs show them."""
+    with _open_text(args, args.color_classes_out) as f:
+        f.write("class\tmask\tcarriers\tkmers\truns\n")
+        f.writelines(f"{c}\t{m:x}\t{bin(m).count('1')}\t{n}\t{r}\n" for c, (m, n, r) in enumerate(zip(
+            classes.masks.tolist(), classes.kmers.tolist(), classes.runs.tolist())))
+
+
+def _write_unitig_color_classes(args, store, classes) -> None:
+    """`--unitig-color-classes-out`: line i describes the k-mers of record i of the unitig store, left to right, as runs of one class."""
+    import numpy as np
+
+    kmers = (np.diff(store.arrays()[1]) - np.uint64(args.k - 1)).astype(np.int64)
+    cls = classes.kmer_class
+    first = np.ones(len(cls), bool)  # the first k-mer of a run: that of a line, or one whose class differs from the one before it
+    first[1:] = cls[1:] != cls[:-1]
+    first[np.cumsum(kmers) - kmers] = True
+    starts = np.flatnonzero(first)
+    lengths = np.diff(np.append(starts, len(cls))).tolist()
+    run_class = cls[starts].tolist()
+    per_line = np.add.reduceat(first.astype(np.int64), np.cumsum(kmers) - kmers).tolist() if len(kmers) else []
+    with _open_text(args, args.unitig_color_classes_out) as f:
+        at = 0
+        for n in per_line:
+            f.write(" ".join(f"{l}:{c}" for l, c in zip(lengths[at:at + n], run_class[at:at + n])) + "\n")
+            at += n
 
 
 def _write_color_matrix(args, colors) -> None:

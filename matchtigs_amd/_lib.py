@@ -301,6 +301,21 @@ def load():
                                                P(vp), P(MtgColorStats)]),
         "mtg_compact_unitigs_colored_store": (None, [vp, u64, u64, vp, u64, C.c_int, P(vp), P(MtgCompaction), P(MtgAbundance), P(vp), P(vp), P(vp),
                                                      P(MtgColorStats)]),
+        "mtg_compact_unitigs_colored_classes": (None, [vp, vp, u64, u64, u64, vp, u64, C.c_int, C.c_int, P(vp), P(MtgCompaction), P(MtgAbundance),
+                                                       P(vp), P(vp), P(vp), P(MtgColorStats), P(vp)]),
+        "mtg_compact_unitigs_colored_classes_store": (None, [vp, u64, u64, vp, u64, C.c_int, C.c_int, P(vp), P(MtgCompaction), P(MtgAbundance),
+                                                             P(vp), P(vp), P(vp), P(MtgColorStats), P(vp)]),
+        "mtg_color_classes_build": (None, [vp, u64, vp, u64, C.c_int, P(vp)]),
+        "mtg_color_classes_count": (u64, [vp]),
+        "mtg_color_classes_masks": (vp, [vp]),
+        "mtg_color_classes_kmers": (vp, [vp]),
+        "mtg_color_classes_runs": (vp, [vp]),
+        "mtg_color_classes_first": (vp, [vp]),
+        "mtg_color_classes_kmer_class_count": (u64, [vp]),
+        "mtg_color_classes_kmer_class": (vp, [vp]),
+        "mtg_color_classes_free": (None, [vp]),
+        "mtg_last_color_class_times": (None, [P(C.c_double)]),
+        "mtg_color_class_limits": (None, [P(u64)]),
         "mtg_kmer_colors_count": (u64, [vp]),
         "mtg_kmer_colors_array": (vp, [vp]),
         "mtg_kmer_colors_free": (None, [vp]),

@@ -1065,6 +1065,136 @@ def compact_unitigs_colored(seqs_or_store, k: int, record_colors, n_colors: int,
     return UnitigStore(out.value), Compaction(**stats.as_dict()), abundance, colors
 
 
+# the counts kernel of the class dictionary (compact_device.hip): the classes it keeps in LDS, its largest grid, its block
+COLOR_CLASS_LDS = 2048
+COLOR_CLASS_GRID = 512
+COLOR_CLASS_BLOCK = 256
+
+
+@dataclass(frozen=True, eq=False)
+class ColorClasses:
+    """The dictionary of a coloured store's masks (mtg_compact_unitigs_colored_classes), in exact integers. The classes
+    are the distinct masks, numbered in the order of the first window of the store that shows them; a run is a maximal stretch of
+    consecutive windows of one unitig with equal masks. masks[c], kmers[c] = the windows of class c, runs[c] = its runs, first[c] =
+    the first window that shows it (strictly increasing); kmer_class[i] = the class of window i: masks[kmer_class] == kmer_colors."""
+
+    masks: np.ndarray       # uint64[classes]
+    kmers: np.ndarray       # uint64[classes]
+    runs: np.ndarray        # uint64[classes]
+    first: np.ndarray       # uint64[classes]
+    kmer_class: np.ndarray  # uint32[distinct_kept]
+
+    def unitig_classes(self, unitig_kmers) -> np.ndarray:
+        """The class of each unitig's first k-mer as uint32[unitigs] (unitig_kmers: the k-mers of every unitig in the store's order)
+        -- on a split store the class of the whole unitig."""
+        n = np.asarray(unitig_kmers, np.int64)
+        if n.ndim != 1 or int(n.sum()) != len(self.kmer_class) or (len(n) and int(n.min()) < 1):
+            raise ValueError(f"unitig_kmers must hold the k-mers of every unitig: they sum to {int(n.sum())}, the store has {len(self.kmer_class)}")
+        return self.kmer_class[np.cumsum(n) - n]
+
+    def describe(self) -> str:
+        if not len(self.masks):
+            return "0 classes in 0 runs"
+        top = int(np.argmax(self.kmers))  # (ties: the first class)
+        return (f"{len(self.masks)} classes in {int(self.runs.sum())} runs, the largest class {top} (mask {int(self.masks[top]):x}, "
+                f"{bin(int(self.masks[top])).count('1')} carriers) with {int(self.kmers[top])} of {int(self.kmers.sum())} k-mers")
+
+
+def _color_classes_taken(L, classes) -> ColorClasses:
+    """The arrays of an mtg_color_classes handle, copied."""
+    def taken(n, pointer, ctype, dtype):
+        n = int(n)
+        return np.ctypeslib.as_array(C.cast(pointer, C.POINTER(ctype)), shape=(n,)).copy() if n else np.zeros(0, dtype)
+
+    nc = L.mtg_color_classes_count(classes)
+    return ColorClasses(*(taken(nc, f(classes), C.c_uint64, np.uint64) for f in (L.mtg_color_classes_masks, L.mtg_color_classes_kmers,
+                                                                                   L.mtg_color_classes_runs, L.mtg_color_classes_first)),
+                        taken(L.mtg_color_classes_kmer_class_count(classes), L.mtg_color_classes_kmer_class(classes), C.c_uint32, np.uint32))
+
+
+def color_classes(kmer_colors, unitig_kmers, device_id: int = 0) -> ColorClasses:
+    """The colour classes of masks handed in (mtg_color_classes_build): kmer_colors, one non-zero mask per k-mer in window
+    order of a store (Colors.kmer_colors), and unitig_kmers, the k-mers of every unitig of that store."""
+    masks = np.ascontiguousarray(kmer_colors, np.uint64)
+    n = np.asarray(unitig_kmers)
+    if masks.ndim != 1 or n.ndim != 1 or (len(n) and (n.dtype.kind not in "iu" or int(n.min()) < 1)) or int(n.sum()) != len(masks):
+        raise ValueError("unitig_kmers must hold the k-mers (>= 1) of every unitig and sum to len(kmer_colors)")
+    if len(masks) and not masks.all():
+        raise ValueError("a kept k-mer's mask is never 0")
+    n = np.ascontiguousarray(n, np.uint64)
+    L = _lib.load()
+    classes = C.c_void_p()
+    L.mtg_color_classes_build(_ptr(masks), len(masks), _ptr(n), len(n), device_id, C.byref(classes))
+    try:
+        return _color_classes_taken(L, classes)
+    finally:
+        L.mtg_color_classes_free(classes)
+
+
+def compact_unitigs_colored_classes(seqs_or_store, k: int, record_colors, n_colors: int, min_abundance: int = 1, split: bool = False,
+                                    device_id: int = 0):
+    """compact_unitigs_colored plus the colour classes of the output store (mtg_compact_unitigs_colored_classes) ->
+    (UnitigStore, Compaction, Abundance, Colors, ColorClasses). split=False: the first four are compact_unitigs_colored's. split=True:
+    the unitigs are cut wherever the colour set changes, so that each is monochromatic -- one run, one class --, and store, Compaction,
+    unitig_sums, kmer_counts and kmer_colors describe the split store."""
+    if min_abundance < 1:
+        raise ValueError("min_abundance must be >= 1")
+    if not isinstance(split, (bool, np.bool_)):
+        raise ValueError(f"split must be True or False, not {split!r}")
+    if isinstance(seqs_or_store, UnitigStore):
+        n_records = len(seqs_or_store)
+    elif isinstance(seqs_or_store, tuple):
+        n_records = len(seqs_or_store[1]) - 1
+    else:
+        n_records = len(seqs_or_store)
+    rc = _record_colors(record_colors, n_colors, n_records)
+    L = _lib.load()
+    out, sums, counts, masks, classes = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+    stats, ab, cs = _lib.MtgCompaction(), _lib.MtgAbundance(), _lib.MtgColorStats()
+    tail = (int(bool(split)), device_id, C.byref(out), C.byref(stats), C.byref(ab), C.byref(sums), C.byref(counts), C.byref(masks), C.byref(cs),
+            C.byref(classes))
+    if isinstance(seqs_or_store, UnitigStore):
+        L.mtg_compact_unitigs_colored_classes_store(seqs_or_store.handle, k, min_abundance, _ptr(rc), n_colors, *tail)
+    else:
+        d, o, n, keep = _sequence_arrays(seqs_or_store)
+        L.mtg_compact_unitigs_colored_classes(d, o, n, k, min_abundance, _ptr(rc), n_colors, *tail)
+        del keep
+    try:
+        def taken(n, pointer, ctype, dtype):
+            n = int(n)
+            return np.ctypeslib.as_array(C.cast(pointer, C.POINTER(ctype)), shape=(n,)).copy() if n else np.zeros(0, dtype)
+
+        unitig_sums = taken(L.mtg_abundance_sums_count(sums), L.mtg_abundance_sums_array(sums), C.c_uint64, np.uint64)
+        per_kmer = taken(L.mtg_kmer_counts_count(counts), L.mtg_kmer_counts_array(counts), C.c_uint32, np.uint32)
+        kmer_colors = taken(L.mtg_kmer_colors_count(masks), L.mtg_kmer_colors_array(masks), C.c_uint64, np.uint64)
+        cc = _color_classes_taken(L, classes)
+    finally:
+        L.mtg_abundance_sums_free(sums)
+        L.mtg_kmer_counts_free(counts)
+        L.mtg_kmer_colors_free(masks)
+        L.mtg_color_classes_free(classes)
+    abundance = Abundance(int(ab.distinct_all), int(ab.distinct_kept), int(ab.max_abundance), int(ab.kept_occurrences),
+                          np.array(ab.spectrum, dtype=np.uint64), unitig_sums, per_kmer)
+    colors = Colors(int(n_colors), kmer_colors, np.array(cs.per_color, dtype=np.uint64)[:n_colors].copy(), np.array(cs.occupancy, dtype=np.uint64),
+                    np.array(cs.shared, dtype=np.uint64).reshape(MAX_COLORS, MAX_COLORS)[:n_colors, :n_colors].copy())
+    return UnitigStore(out.value), Compaction(**stats.as_dict()), abundance, colors, cc
+
+
+def last_color_class_times() -> dict:
+    """In ms, the class dictionary of the last compact_unitigs_colored_classes on this thread: run heads, class table, class ids,
+    counts (HIP events around the kernels), download (host clock)."""
+    out = (C.c_double * 5)()
+    _lib.load().mtg_last_color_class_times(out)
+    return dict(zip(("heads_ms", "table_ms", "ids_ms", "counts_ms", "download_ms"), map(float, out)))
+
+
+def color_class_limits() -> dict:
+    """The library's own values of COLOR_CLASS_LDS, COLOR_CLASS_GRID and COLOR_CLASS_BLOCK."""
+    out = (C.c_uint64 * 3)()
+    _lib.load().mtg_color_class_limits(out)
+    return dict(zip(("lds", "grid", "block"), map(int, out)))
+
+
 def last_compact_times() -> dict:
     """Phases of the last compact_unitigs / compact_unitigs_counted on this thread: ms by HIP events around the kernel phases (pack, insert, ids, nodes, rank,
     emit), upload / download / total by the host clock, the pointer-jumping rounds, the least bytes the kernels must move and the

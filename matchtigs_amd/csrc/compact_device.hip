@@ -59,6 +59,11 @@
 // color_stats_kernel sweeps kcolor[N] once for per-colour counts, the C x C matrix of shared k-mers and the occupancy histogram, as a
 // product of 64 x 64 bit blocks (ballots, popcounts), never a loop over set bits; order_kernel<uint64_t> puts the masks into unitig
 // order, which is downloaded. Memory added: 8 B per slot (16 w) while inserting, freed with the table; 8 N (kcolor) and 8 N (ordered).
+//
+// Calls with colour classes (mtg_compact_unitigs_colored_classes): a coloured call plus the dictionary of the ordered
+// masks (the kernels under "colour classes" below: per run of equal masks, never per k-mer), and with split = 1 succ_kernel<true>,
+// which keeps a successor only where both k-mers have one mask, so that every unitig is monochromatic; rank, emit, sums, counts and
+// ordered masks follow from succ unchanged. Memory added after emit: 12 N + 48 per run + 32 per class.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -286,18 +291,26 @@ __global__ __launch_bounds__(hu::EB) void node_insert_kernel(NodeArgs a, unsigne
     else add_incident(&a.out_e[sb], mi);
 }
 
-__global__ __launch_bounds__(hu::EB) void succ_kernel(NodeArgs a, unsigned int *err) {
+// SPLIT: a successor is kept only where its k-mer has the mask of this one (kcolor: [N]) -- the node between them is
+// passable only if the k-mer that enters it and the one that leaves it have equal masks. Masks belong to canonical k-mers, so the
+// rule holds for the mirror walk too and pred(o) = mirror(succ(mirror(o))) stays true.
+template <bool SPLIT>
+__global__ __launch_bounds__(hu::EB) void succ_kernel(NodeArgs a, unsigned int *err, const unsigned long long *kcolor) {
     const uint64_t i = hu::gid();
     if (i >= a.N) return;
     const uint64_t p = a.kpos[i];
     kw::ClassKey key;
     const uint64_t sb = find_node<false>(a, p + 1, key, err);  // head of the reading: its suffix as read
     uint32_t oe = a.out_e[sb], ie = a.in_e[sb];
-    a.succ[2 * i] = (!key.pal && oe < MULTI32 && ie < MULTI32) ? (key.flip ? ie ^ 1u : oe) : NONE32;
+    uint32_t s = (!key.pal && oe < MULTI32 && ie < MULTI32) ? (key.flip ? ie ^ 1u : oe) : NONE32;
+    if (SPLIT && s != NONE32 && kcolor[s >> 1] != kcolor[i]) s = NONE32;
+    a.succ[2 * i] = s;
     const uint64_t sa = find_node<false>(a, p, key, err);  // head of the mirror: the reverse complement of the prefix
     oe = a.out_e[sa];
     ie = a.in_e[sa];
-    a.succ[2 * i + 1] = (!key.pal && oe < MULTI32 && ie < MULTI32) ? (key.flip ? oe : ie ^ 1u) : NONE32;
+    s = (!key.pal && oe < MULTI32 && ie < MULTI32) ? (key.flip ? oe : ie ^ 1u) : NONE32;
+    if (SPLIT && s != NONE32 && kcolor[s >> 1] != kcolor[i]) s = NONE32;
+    a.succ[2 * i + 1] = s;
 }
 
 __device__ __forceinline__ uint32_t pred_of(const uint32_t *succ, uint32_t o) {
@@ -431,6 +444,143 @@ __global__ __launch_bounds__(hu::EB) void unitig_sums_kernel(const unsigned long
     sums[u] = (u + 1 < n_unitigs ? prefix[out_off[u + 1] - (k - 1) * (u + 1)] : *total) - lo;
 }
 
+// ---- colour classes ----
+// A RUN is a maximal stretch of consecutive windows of one unitig with equal masks; the classes are the distinct masks, numbered in
+// the order of the first window that shows them. Everything is computed per run, never per k-mer, and no kernel walks a run.
+//   heads     head[i] = 1 where window i opens a unitig (one thread per unitig) or its mask differs from that of window i - 1 (one
+//             thread per window); the exclusive scan of head is, at a head, its run's number; run_start[r] = the head of run r.
+//   table     one insertion per run into an open-addressing table keyed by the mask (0 = empty, kept masks are never 0; 2 slots per
+//             run). The slot keeps the smallest run number by atomicMin behind a plain compare -- run starts ascend with the run
+//             number, so that is the run of the class's first window, and as runs arrive in ascending order almost every later one
+//             fails the compare and issues no atomic (the insert idiom of the k-mer table above).
+//   ids       every occupied slot flags its smallest run; the scan of the flags numbers the classes in first-appearance order.
+//   counts    a grid-stride sweep over the runs: kmers[c] += length, runs[c] += 1. Equal classes are combined inside the wave first,
+//             then in an LDS table per workgroup indexed by the class number, which leaves by at most one 64-bit global atomicAdd per
+//             touched class, counter and workgroup; classes from CLASS_LDS on go to global memory directly.
+//   window    kmer_class[i] = the class of window i's run.
+// Order independence: a slot's key is written once (CAS from 0) and compared by value, so which slot a mask ends in may vary with the
+// order but nothing that leaves the table does: the smallest run is a minimum, the ids come from a scan over run numbers, the
+// counters are integer sums, and run_start, run_slot, run_class, the per-class words and kmer_class are single-writer words.
+constexpr int CLASS_LDS = 2048;   // classes 0 .. CLASS_LDS - 1 are counted in LDS (16 KiB per workgroup)
+constexpr int CLASS_GRID = 512;   // the counts kernel's largest grid
+constexpr int CLASS_PEEL = 2;     // classes combined across the wave before the lanes left add on their own
+
+__device__ __forceinline__ uint64_t mix64(uint64_t x) {
+    x ^= x >> 33; x *= 0xFF51AFD7ED558CCDull;
+    x ^= x >> 33; x *= 0xC4CEB9FE1A85EC53ull;
+    return x ^ (x >> 33);
+}
+__global__ __launch_bounds__(hu::EB) void unitig_heads_kernel(const unsigned long long *out_off, uint64_t n_unitigs, uint64_t k, uint32_t *head) {
+    const uint64_t u = hu::gid();
+    if (u < n_unitigs) head[out_off[u] - (k - 1) * u] = 1u;
+}
+__global__ __launch_bounds__(hu::EB) void run_heads_kernel(const unsigned long long *ordered, uint64_t N, uint32_t *head) {
+    const uint64_t i = hu::gid();
+    if (i && i < N && ordered[i] != ordered[i - 1]) head[i] = 1u;
+}
+__global__ __launch_bounds__(hu::EB) void run_starts_kernel(const uint32_t *head, const uint32_t *run_of, uint64_t N, uint64_t R, uint32_t *run_start) {
+    const uint64_t i = hu::gid();
+    if (i < N && head[i]) run_start[run_of[i]] = (uint32_t)i;
+    if (i == 0) run_start[R] = (uint32_t)N;
+}
+__global__ __launch_bounds__(hu::EB) void class_insert_kernel(const unsigned long long *ordered, const uint32_t *run_start, uint64_t R,
+                                                               unsigned long long *keys, uint32_t *min_run, uint64_t slots, uint32_t *run_slot,
+                                                               unsigned int *err) {
+    const uint64_t r = hu::gid();
+    if (r >= R) return;
+    const unsigned long long mask = ordered[run_start[r]];
+    uint64_t s = mix64(mask) % slots;
+    for (uint64_t probe = 0; probe < slots; probe++, s = s + 1 == slots ? 0 : s + 1) {
+        unsigned long long cur = load64(&keys[s]);
+        if (cur == 0) {
+            cur = atomicCAS(&keys[s], 0ull, mask);
+            if (cur == 0) cur = mask;
+        }
+        if (cur != mask) continue;
+        run_slot[r] = (uint32_t)s;
+        if ((uint32_t)r < __hip_atomic_load(&min_run[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(&min_run[s], (uint32_t)r);
+        return;
+    }
+    atomicOr(err, 16u);  // (2 slots per run: never full)
+}
+__global__ __launch_bounds__(hu::EB) void class_flag_kernel(const unsigned long long *keys, const uint32_t *min_run, uint64_t slots, uint32_t *flag) {
+    const uint64_t s = hu::gid();
+    if (s < slots && keys[s]) flag[min_run[s]] = 1u;
+}
+// per occupied slot: its class number, and the class's mask and first window
+__global__ __launch_bounds__(hu::EB) void class_ids_kernel(const unsigned long long *keys, const uint32_t *min_run, uint64_t slots, const uint32_t *id_of_run,
+                                                            const uint32_t *run_start, uint32_t *slot_class, unsigned long long *masks,
+                                                            unsigned long long *first) {
+    const uint64_t s = hu::gid();
+    if (s >= slots || !keys[s]) return;
+    const uint32_t c = id_of_run[min_run[s]];
+    slot_class[s] = c;
+    masks[c] = keys[s];
+    first[c] = run_start[min_run[s]];
+}
+// out: [0 .. n_classes) kmers, [n_classes .. 2 n_classes) runs
+__global__ __launch_bounds__(hu::EB) void class_counts_kernel(const uint32_t *run_start, const uint32_t *run_slot, const uint32_t *slot_class, uint64_t R,
+                                                               uint64_t n_classes, uint32_t *run_class, unsigned long long *out) {
+    __shared__ uint32_t lds_kmers[CLASS_LDS];  // (fewer than 2^31 k-mers: they cannot wrap)
+    __shared__ uint32_t lds_runs[CLASS_LDS];
+    for (int e = threadIdx.x; e < CLASS_LDS; e += hu::EB) lds_kmers[e] = lds_runs[e] = 0;
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const uint64_t stride = (uint64_t)gridDim.x * hu::EB;  // (a multiple of 64: the lanes of a wave leave the loop together)
+    for (uint64_t at = hu::gid() - lane; at < R; at += stride) {
+        const uint64_t r = at + lane;
+        bool todo = r < R;
+        uint32_t c = 0, len = 0;
+        if (todo) {
+            c = slot_class[run_slot[r]];
+            len = run_start[r + 1] - run_start[r];
+            run_class[r] = c;
+        }
+        for (int round = 0; round < CLASS_PEEL; round++) {  // the class of the first lane left, summed over the wave by a butterfly
+            const unsigned long long left = __ballot(todo);
+            if (!left) break;  // (uniform)
+            const int leader = __ffsll(left) - 1;
+            const uint32_t cl = __shfl(c, leader);
+            const bool same = todo && c == cl;
+            const unsigned long long group = __ballot(same);
+            if (__popcll(group) < 4) break;  // (uniform) too few to be worth the butterfly
+            uint32_t sum = same ? len : 0u;
+            for (int d = 32; d > 0; d /= 2) sum += __shfl_xor(sum, d);
+            if (lane == leader) {
+                if (cl < CLASS_LDS) {
+                    atomicAdd(&lds_kmers[cl], sum);
+                    atomicAdd(&lds_runs[cl], (uint32_t)__popcll(group));
+                } else {
+                    atomicAdd(&out[cl], (unsigned long long)sum);
+                    atomicAdd(&out[n_classes + cl], (unsigned long long)__popcll(group));
+                }
+            }
+            todo = todo && !same;
+        }
+        if (todo) {
+            if (c < CLASS_LDS) {
+                atomicAdd(&lds_kmers[c], len);
+                atomicAdd(&lds_runs[c], 1u);
+            } else {
+                atomicAdd(&out[c], (unsigned long long)len);
+                atomicAdd(&out[n_classes + c], 1ull);
+            }
+        }
+    }
+    __syncthreads();
+    for (uint64_t e = threadIdx.x; e < CLASS_LDS && e < n_classes; e += hu::EB) {
+        if (lds_runs[e]) {
+            atomicAdd(&out[e], (unsigned long long)lds_kmers[e]);
+            atomicAdd(&out[n_classes + e], (unsigned long long)lds_runs[e]);
+        }
+    }
+}
+__global__ __launch_bounds__(hu::EB) void window_class_kernel(const uint32_t *head, const uint32_t *run_of, const uint32_t *run_class, uint64_t N,
+                                                               uint32_t *kmer_class) {
+    const uint64_t i = hu::gid();
+    if (i < N) kmer_class[i] = run_class[run_of[i] + head[i] - 1u];  // (exclusive scan: a head has its own number, the others the next one)
+}
+
 int log2_ceil(uint64_t n) {
     int r = 0;
     while ((1ull << r) < n) r++;
@@ -452,11 +602,112 @@ struct Colored {
     mtg_color_stats *stats;
     double *stats_ms;  // HIP-event time of color_stats_kernel
 };
+// what a call with colour classes adds to a coloured one
+struct Classed {
+    bool split;  // monochromatic unitigs: succ_kernel<true>
+    ColorClasses *out;
+    ColorClassTimes *times;
+};
+
+// The class dictionary of a store's masks in window order (ordered: [N], out_off: the unitigs' character offsets). Device memory, all
+// from the arena: 8 B per k-mer (head, run number) and 4 B more for kmer_class; per run R 4 (start) + 4 (slot) + 4 (class) + 4 (flag,
+// scanned in place) + 2 x (8 + 4 + 4) (the table: key, smallest run, class per slot); per class 32 B.
+void color_classes(const unsigned long long *d_ordered, const unsigned long long *d_out_off, uint64_t N, uint64_t n_unitigs, uint64_t k, bool split,
+                   hipStream_t st, ScalarBlock &small, int device_id, ColorClasses *out, ColorClassTimes *times) {
+    const char *const stage = "colour classes";
+    PhaseEvents<5> ev;
+    ev.mark(0, st);
+    // ---- run heads ----
+    uint32_t *d_head = nullptr, *d_run_of = nullptr, *d_bsum = nullptr, *d_run_start = nullptr;
+    hu::device_malloc(&d_head, N * 4);
+    hu::device_malloc(&d_run_of, N * 4);
+    hu::device_malloc(&d_bsum, (hu::scan_blocks(N) + 2) * 4);
+    uint32_t *d_total = d_bsum + hu::scan_blocks(N) + 1;
+    HIP_CHECK(hipMemsetAsync(d_head, 0, N * 4, st));
+    unitig_heads_kernel<<<hu::grid_for(n_unitigs), hu::EB, 0, st>>>(d_out_off, n_unitigs, k, d_head);
+    run_heads_kernel<<<hu::grid_for(N), hu::EB, 0, st>>>(d_ordered, N, d_head);
+    hu::scan_u32<uint32_t>(st, d_head, N, d_run_of, d_bsum, d_total);
+    uint32_t n_runs = 0;
+    HIP_CHECK(hipMemcpyAsync(&n_runs, d_total, 4, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    const uint64_t R = n_runs;
+    if (R < n_unitigs || R > N || (split && R != n_unitigs))
+        MTG_DIE("colour classes: internal error (%llu runs in %llu unitigs of %llu k-mers%s)", (unsigned long long)R, (unsigned long long)n_unitigs,
+                (unsigned long long)N, split ? ", split" : "");
+    hu::device_malloc(&d_run_start, (R + 1) * 4);
+    run_starts_kernel<<<hu::grid_for(N), hu::EB, 0, st>>>(d_head, d_run_of, N, R, d_run_start);
+    HIP_CHECK(hipGetLastError());
+    ev.mark(1, st);
+    // ---- the class table: one insertion per run ----
+    const uint64_t slots = std::max<uint64_t>(8, 2 * R);
+    unsigned long long *d_keys = nullptr;
+    uint32_t *d_min_run = nullptr, *d_run_slot = nullptr;
+    hu::device_malloc(&d_keys, slots * 8);
+    hu::device_malloc(&d_min_run, slots * 4);
+    hu::device_malloc(&d_run_slot, R * 4);
+    HIP_CHECK(hipMemsetAsync(d_keys, 0, slots * 8, st));
+    HIP_CHECK(hipMemsetAsync(d_min_run, 0xFF, slots * 4, st));
+    class_insert_kernel<<<hu::grid_for(R), hu::EB, 0, st>>>(d_ordered, d_run_start, R, d_keys, d_min_run, slots, d_run_slot, small.err());
+    HIP_CHECK(hipGetLastError());
+    ev.mark(2, st);
+    // ---- class ids in first-appearance order ----
+    uint32_t *d_flag = nullptr, *d_bsum_r = nullptr, *d_slot_class = nullptr;
+    hu::device_malloc(&d_flag, R * 4);
+    hu::device_malloc(&d_bsum_r, (hu::scan_blocks(R) + 2) * 4);
+    hu::device_malloc(&d_slot_class, slots * 4);
+    uint32_t *d_n_classes = d_bsum_r + hu::scan_blocks(R) + 1;
+    HIP_CHECK(hipMemsetAsync(d_flag, 0, R * 4, st));
+    class_flag_kernel<<<hu::grid_for(slots), hu::EB, 0, st>>>(d_keys, d_min_run, slots, d_flag);
+    hu::scan_u32<uint32_t>(st, d_flag, R, d_flag, d_bsum_r, d_n_classes);
+    uint32_t n_classes32 = 0;
+    HIP_CHECK(hipMemcpyAsync(&n_classes32, d_n_classes, 4, hipMemcpyDeviceToHost, st));
+    small.read(st, stage);
+    const uint64_t n_classes = n_classes32;
+    if (n_classes == 0 || n_classes > R) MTG_DIE("colour classes: internal error (%llu classes in %llu runs)", (unsigned long long)n_classes, (unsigned long long)R);
+    unsigned long long *d_masks = nullptr, *d_first = nullptr, *d_sums = nullptr;
+    hu::device_malloc(&d_masks, n_classes * 8);
+    hu::device_malloc(&d_first, n_classes * 8);
+    hu::device_malloc(&d_sums, 2 * n_classes * 8);
+    HIP_CHECK(hipMemsetAsync(d_sums, 0, 2 * n_classes * 8, st));
+    class_ids_kernel<<<hu::grid_for(slots), hu::EB, 0, st>>>(d_keys, d_min_run, slots, d_flag, d_run_start, d_slot_class, d_masks, d_first);
+    HIP_CHECK(hipGetLastError());
+    ev.mark(3, st);
+    // ---- counts per class, and the class of every window ----
+    uint32_t *d_run_class = nullptr, *d_kmer_class = nullptr;
+    hu::device_malloc(&d_run_class, R * 4);
+    hu::device_malloc(&d_kmer_class, N * 4);
+    class_counts_kernel<<<(unsigned)std::min<uint64_t>(hu::grid_for(R), CLASS_GRID), hu::EB, 0, st>>>(d_run_start, d_run_slot, d_slot_class, R, n_classes,
+                                                                                                      d_run_class, d_sums);
+    window_class_kernel<<<hu::grid_for(N), hu::EB, 0, st>>>(d_head, d_run_of, d_run_class, N, d_kmer_class);
+    HIP_CHECK(hipGetLastError());
+    ev.mark(4, st);
+    HIP_CHECK(hipStreamSynchronize(st));
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<uint64_t> sums(2 * n_classes);
+    out->masks.resize(n_classes);
+    out->first.resize(n_classes);
+    out->kmer_class.resize(N);
+    hu::download_sliced(out->masks.data(), d_masks, n_classes * 8, st, device_id);
+    hu::download_sliced(out->first.data(), d_first, n_classes * 8, st, device_id);
+    hu::download_sliced(sums.data(), d_sums, 2 * n_classes * 8, st, device_id);
+    hu::download_sliced(out->kmer_class.data(), d_kmer_class, N * 4, st, device_id);
+    out->kmers.assign(sums.begin(), sums.begin() + n_classes);
+    out->runs.assign(sums.begin() + n_classes, sums.end());
+    out->n_runs = R;
+    times->download_ms = ms_since(t0);
+    times->heads_ms = ev.ms(0, 1);
+    times->table_ms = ev.ms(1, 2);
+    times->ids_ms = ev.ms(2, 3);
+    times->counts_ms = ev.ms(3, 4);
+    for (const void *p : std::initializer_list<const void *>{d_head, d_run_of, d_bsum, d_run_start, d_keys, d_min_run, d_run_slot, d_flag, d_bsum_r, d_slot_class,
+                                                             d_masks, d_first, d_sums, d_run_class, d_kmer_class})
+        hu::device_free(p);
+}
 
 // counted == nullptr: the plain compaction
 // colored != nullptr: counted too
 UnitigStore *compact(const char *data, const uint64_t *off, uint64_t n_rec, uint64_t k, int device_id, mtg_compaction *stats_out, CompactTimes *times,
-                     const Counted *counted, const Colored *colored = nullptr) {
+                     const Counted *counted, const Colored *colored = nullptr, const Classed *classed = nullptr) {
     if (!off || (n_rec && off[n_rec] && !data)) MTG_DIE("mtg_compact_unitigs: null argument");
     if (k < 2) MTG_DIE("mtg_compact_unitigs: k must be >= 2");
     if (k >= (1ull << 31)) MTG_DIE("mtg_compact_unitigs: k too large");
@@ -493,6 +744,10 @@ UnitigStore *compact(const char *data, const uint64_t *off, uint64_t n_rec, uint
         *colored->stats = mtg_color_stats{};
         colored->stats->n_colors = colored->n_colors;
         *colored->stats_ms = 0;
+    }
+    if (classed) {
+        *classed->out = ColorClasses{};
+        *classed->times = ColorClassTimes{};
     }
     auto finish = [&]() {
         t.total_ms = ms_since(t_total);
@@ -624,7 +879,8 @@ UnitigStore *compact(const char *data, const uint64_t *off, uint64_t n_rec, uint
     HIP_CHECK(hipMemsetAsync(na.out_e, 0xFF, na.slots * 4, st));
     HIP_CHECK(hipMemsetAsync(na.in_e, 0xFF, na.slots * 4, st));
     node_insert_kernel<<<hu::grid_for(N), hu::EB, 0, st>>>(na, d_err);
-    succ_kernel<<<hu::grid_for(N), hu::EB, 0, st>>>(na, d_err);
+    if (classed && classed->split) succ_kernel<true><<<hu::grid_for(N), hu::EB, 0, st>>>(na, d_err, d_kcolor);
+    else succ_kernel<false><<<hu::grid_for(N), hu::EB, 0, st>>>(na, d_err, nullptr);
     HIP_CHECK(hipGetLastError());
     ev.mark(3, st);
     free_all({na.table, na.out_e, na.in_e});
@@ -741,6 +997,7 @@ UnitigStore *compact(const char *data, const uint64_t *off, uint64_t n_rec, uint
     }
     ev.mark(5, st);
     HIP_CHECK(hipStreamSynchronize(st));
+    if (classed) color_classes(d_ordered_colors, d_out_off, N, r.unitigs, k, classed->split, st, small, device_id, classed->out, classed->times);
 
     const auto t0 = std::chrono::steady_clock::now();
     store->data.resize(n_chars);
@@ -815,5 +1072,51 @@ UnitigStore *device_compact_unitigs_colored(const char *data, const uint64_t *of
     const Colored col{record_colors, n_colors, kmer_colors, color_stats, stats_ms};
     return compact(data, off, n_rec, k, device_id, stats_out, times, &c, &col);
 }
+
+UnitigStore *device_compact_unitigs_colored_classes(const char *data, const uint64_t *off, uint64_t n_rec, uint64_t k, uint64_t min_abundance,
+                                                    const uint8_t *record_colors, uint64_t n_colors, bool split, int device_id,
+                                                    mtg_compaction *stats_out, mtg_abundance *abundance_out, std::vector<uint64_t> *unitig_sums,
+                                                    std::vector<uint32_t> *kmer_counts, std::vector<uint64_t> *kmer_colors,
+                                                    mtg_color_stats *color_stats, ColorClasses *classes, CompactTimes *times, double *stats_ms,
+                                                    ColorClassTimes *class_times) {
+    if (!unitig_sums || !kmer_counts || !kmer_colors || !color_stats || !classes || !stats_ms || !class_times)
+        MTG_DIE("mtg_compact_unitigs_colored_classes: null argument");
+    const Counted c{min_abundance, abundance_out, unitig_sums, kmer_counts};
+    const Colored col{record_colors, n_colors, kmer_colors, color_stats, stats_ms};
+    const Classed cl{split, classes, class_times};
+    return compact(data, off, n_rec, k, device_id, stats_out, times, &c, &col, &cl);
+}
+
+void device_color_classes(const uint64_t *kmer_colors, uint64_t n, const uint64_t *unitig_kmers, uint64_t n_unitigs, int device_id, ColorClasses *out,
+                          ColorClassTimes *times) {
+    if (!out || !times || (n && !kmer_colors) || (n_unitigs && !unitig_kmers)) MTG_DIE("mtg_color_classes_build: null argument");
+    *out = ColorClasses{};
+    *times = ColorClassTimes{};
+    if (n > MAX_KMERS) MTG_DIE("mtg_color_classes_build: %llu k-mers; window numbers are 32-bit", (unsigned long long)n);
+    std::vector<unsigned long long> off(n_unitigs + 1, 0);  // window offsets: character offsets at k = 1
+    for (uint64_t u = 0; u < n_unitigs; u++) {
+        if (unitig_kmers[u] == 0 || unitig_kmers[u] > n - off[u]) MTG_DIE("mtg_color_classes_build: unitig %llu has %llu k-mers of the %llu left",
+                                                                         (unsigned long long)u, (unsigned long long)unitig_kmers[u], (unsigned long long)(n - off[u]));
+        off[u + 1] = off[u] + unitig_kmers[u];
+    }
+    if (off[n_unitigs] != n) MTG_DIE("mtg_color_classes_build: the unitigs hold %llu k-mers, the masks %llu", (unsigned long long)off[n_unitigs], (unsigned long long)n);
+    for (uint64_t i = 0; i < n; i++)
+        if (kmer_colors[i] == 0) MTG_DIE("mtg_color_classes_build: k-mer %llu has the empty mask", (unsigned long long)i);
+    if (n == 0) return;
+    if (device_id < 0 || device_count() <= device_id) MTG_DIE("no HIP device %d for the colour classes (there is no CPU path)", device_id);
+    HIP_CHECK(hipSetDevice(device_id));
+    hipStream_t st = nullptr;
+    ScalarBlock small(st);
+    unsigned long long *d_masks = nullptr, *d_off = nullptr;
+    hu::device_malloc(&d_masks, n * 8);
+    hu::device_malloc(&d_off, (n_unitigs + 1) * 8);
+    hu::upload_sliced(d_masks, kmer_colors, n * 8, st, device_id);
+    hu::upload_sliced(d_off, off.data(), (n_unitigs + 1) * 8, st, device_id);
+    color_classes(d_masks, d_off, n, n_unitigs, 1, false, st, small, device_id, out, times);
+    hu::device_free(d_masks);
+    hu::device_free(d_off);
+}
+
+uint64_t device_color_class_limit(int which) { return which == 0 ? CLASS_LDS : which == 1 ? CLASS_GRID : hu::EB; }
 
 }  // namespace mtg

@@ -211,6 +211,29 @@ UnitigStore *device_compact_unitigs_colored(const char *data, const uint64_t *of
                                             const uint8_t *record_colors, uint64_t n_colors, int device_id, mtg_compaction *stats_out,
                                             mtg_abundance *abundance_out, std::vector<uint64_t> *unitig_sums, std::vector<uint32_t> *kmer_counts,
                                             std::vector<uint64_t> *kmer_colors, mtg_color_stats *color_stats, CompactTimes *times, double *stats_ms);
+// ... with the colour classes of the output store: the distinct masks numbered in the order of the first window that
+// shows them; per class its mask, k-mers, runs (maximal stretches of consecutive windows of one unitig with equal masks) and first
+// window; per window its class. split: a node is passable only if the k-mers that enter and leave it have equal masks, so every unitig
+// is one run. class_times: HIP-event time of the dictionary's phases, its download by the host clock.
+struct ColorClasses {
+    std::vector<uint64_t> masks, kmers, runs, first;
+    std::vector<uint32_t> kmer_class;
+    uint64_t n_runs = 0;
+};
+struct ColorClassTimes {
+    double heads_ms = 0, table_ms = 0, ids_ms = 0, counts_ms = 0, download_ms = 0;
+};
+UnitigStore *device_compact_unitigs_colored_classes(const char *data, const uint64_t *off, uint64_t n_rec, uint64_t k, uint64_t min_abundance,
+                                                    const uint8_t *record_colors, uint64_t n_colors, bool split, int device_id,
+                                                    mtg_compaction *stats_out, mtg_abundance *abundance_out, std::vector<uint64_t> *unitig_sums,
+                                                    std::vector<uint32_t> *kmer_counts, std::vector<uint64_t> *kmer_colors,
+                                                    mtg_color_stats *color_stats, ColorClasses *classes, CompactTimes *times, double *stats_ms,
+                                                    ColorClassTimes *class_times);
+// ... of masks and unitig lengths handed in (kmer_colors: n masks in window order, none 0; unitig_kmers: n_unitigs lengths that sum to n)
+void device_color_classes(const uint64_t *kmer_colors, uint64_t n, const uint64_t *unitig_kmers, uint64_t n_unitigs, int device_id, ColorClasses *out,
+                          ColorClassTimes *times);
+// the counts kernel's LDS table (classes), largest grid and block: what a test must exceed to reach the kernel's other paths
+uint64_t device_color_class_limit(int which);
 // fasta_in.cpp: read_fasta_records without an alphabet rule and without case folding (the queries of the k-mer index), plus the
 // record names (the header text behind `>` up to the first white space) as a second store
 UnitigStore *read_fasta_records_named(const char *path, UnitigStore **names_out);

@@ -885,6 +885,67 @@ const uint64_t *mtg_kmer_colors_array(const mtg_kmer_colors *colors) {
     return colors->v.data();
 }
 void mtg_kmer_colors_free(mtg_kmer_colors *colors) { delete colors; }
+// ---- monochromatic unitigs and colour classes ----
+struct mtg_color_classes { ColorClasses c; };
+static thread_local ColorClassTimes g_last_color_class;
+void mtg_compact_unitigs_colored_classes(const char *data, const uint64_t *offsets, uint64_t n, uint64_t k, uint64_t min_abundance,
+                                         const uint8_t *record_colors, uint64_t n_colors, int split, int device_id, mtg_unitigs **out,
+                                         mtg_compaction *stats, mtg_abundance *abundance, mtg_abundance_sums **sums,
+                                         mtg_kmer_counts **kmer_counts, mtg_kmer_colors **kmer_colors, mtg_color_stats *color_stats,
+                                         mtg_color_classes **classes) {
+    if (!out || !sums || !kmer_counts || !kmer_colors || !color_stats || !classes) MTG_DIE("mtg_compact_unitigs_colored_classes: null argument");
+    if (min_abundance == 0) MTG_DIE("mtg_compact_unitigs_colored_classes: min_abundance must be >= 1");
+    if (split != 0 && split != 1) MTG_DIE("mtg_compact_unitigs_colored_classes: split must be 0 or 1, not %d", split);
+    mtg_abundance_sums *s = new mtg_abundance_sums();
+    mtg_kmer_counts *c = new mtg_kmer_counts();
+    mtg_kmer_colors *m = new mtg_kmer_colors();
+    mtg_color_classes *cl = new mtg_color_classes();
+    *out = new mtg_unitigs{device_compact_unitigs_colored_classes(data, offsets, n, k, min_abundance, record_colors, n_colors, split == 1, device_id, stats,
+                                                                  abundance, &s->v, &c->v, &m->v, color_stats, &cl->c, &g_last_compact,
+                                                                  &g_last_kmer_color.stats_ms, &g_last_color_class)};
+    *sums = s;
+    *kmer_counts = c;
+    *kmer_colors = m;
+    *classes = cl;
+}
+void mtg_compact_unitigs_colored_classes_store(const mtg_unitigs *in, uint64_t k, uint64_t min_abundance, const uint8_t *record_colors,
+                                               uint64_t n_colors, int split, int device_id, mtg_unitigs **out, mtg_compaction *stats,
+                                               mtg_abundance *abundance, mtg_abundance_sums **sums, mtg_kmer_counts **kmer_counts,
+                                               mtg_kmer_colors **kmer_colors, mtg_color_stats *color_stats, mtg_color_classes **classes) {
+    if (!in) MTG_DIE("mtg_compact_unitigs_colored_classes_store: null argument");
+    mtg_compact_unitigs_colored_classes(in->s->data.data(), in->s->off.data(), in->s->off.size() - 1, k, min_abundance, record_colors, n_colors, split,
+                                        device_id, out, stats, abundance, sums, kmer_counts, kmer_colors, color_stats, classes);
+}
+void mtg_color_classes_build(const uint64_t *kmer_colors, uint64_t n, const uint64_t *unitig_kmers, uint64_t n_unitigs, int device_id,
+                             mtg_color_classes **classes) {
+    if (!classes) MTG_DIE("mtg_color_classes_build: null argument");
+    mtg_color_classes *cl = new mtg_color_classes();
+    device_color_classes(kmer_colors, n, unitig_kmers, n_unitigs, device_id, &cl->c, &g_last_color_class);
+    *classes = cl;
+}
+static const ColorClasses &classes_of(const mtg_color_classes *classes, const char *who) {
+    if (!classes) MTG_DIE("%s: null argument", who);
+    return classes->c;
+}
+uint64_t mtg_color_classes_count(const mtg_color_classes *classes) { return classes_of(classes, "mtg_color_classes_count").masks.size(); }
+const uint64_t *mtg_color_classes_masks(const mtg_color_classes *classes) { return classes_of(classes, "mtg_color_classes_masks").masks.data(); }
+const uint64_t *mtg_color_classes_kmers(const mtg_color_classes *classes) { return classes_of(classes, "mtg_color_classes_kmers").kmers.data(); }
+const uint64_t *mtg_color_classes_runs(const mtg_color_classes *classes) { return classes_of(classes, "mtg_color_classes_runs").runs.data(); }
+const uint64_t *mtg_color_classes_first(const mtg_color_classes *classes) { return classes_of(classes, "mtg_color_classes_first").first.data(); }
+uint64_t mtg_color_classes_kmer_class_count(const mtg_color_classes *classes) {
+    return classes_of(classes, "mtg_color_classes_kmer_class_count").kmer_class.size();
+}
+const uint32_t *mtg_color_classes_kmer_class(const mtg_color_classes *classes) {
+    return classes_of(classes, "mtg_color_classes_kmer_class").kmer_class.data();
+}
+void mtg_color_classes_free(mtg_color_classes *classes) { delete classes; }
+void mtg_last_color_class_times(double out[5]) {
+    const ColorClassTimes &t = g_last_color_class;
+    out[0] = t.heads_ms; out[1] = t.table_ms; out[2] = t.ids_ms; out[3] = t.counts_ms; out[4] = t.download_ms;
+}
+void mtg_color_class_limits(uint64_t out[3]) {
+    for (int i = 0; i < 3; i++) out[i] = device_color_class_limit(i);
+}
 void mtg_last_compact_times(double out[12]) {
     const CompactTimes &t = g_last_compact;
     out[0] = t.upload_ms; out[1] = t.pack_ms; out[2] = t.insert_ms; out[3] = t.ids_ms; out[4] = t.nodes_ms; out[5] = t.rank_ms;
