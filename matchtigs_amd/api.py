@@ -901,15 +901,7 @@ def compact_unitigs(seqs_or_store, k: int, device_id: int = 0):
     """The maximal unitigs of the k-mer set of arbitrary sequences, compacted on GPU `device_id` (mtg_compact_unitigs)
     -> (UnitigStore, Compaction). seqs_or_store: UnitigStore, list of str, or (uint8 array, offsets). The store is an ordinary one:
     Bigraph.from_sequences((data, offsets) of it), the writers and compare_kmer_sets take it."""
-    L = _lib.load()
-    out, stats = C.c_void_p(), _lib.MtgCompaction()
-    if isinstance(seqs_or_store, UnitigStore):
-        L.mtg_compact_unitigs_store(seqs_or_store.handle, k, device_id, C.byref(out), C.byref(stats))
-    else:
-        d, o, n, keep = _sequence_arrays(seqs_or_store)
-        L.mtg_compact_unitigs(d, o, n, k, device_id, C.byref(out), C.byref(stats))
-        del keep
-    return UnitigStore(out.value), Compaction(**stats.as_dict())
+    return _compact(_PLAIN, seqs_or_store, k, device_id)[:2]
 
 
 @dataclass(frozen=True, eq=False)
@@ -944,33 +936,7 @@ def compact_unitigs_counted(seqs_or_store, k: int, min_abundance: int, device_id
     kmer_counts=True (mtg_compact_unitigs_counted_kmers): Abundance.kmer_counts also holds every kept k-mer's abundance."""
     if min_abundance < 1:
         raise ValueError("min_abundance must be >= 1")
-    L = _lib.load()
-    out, sums, counts, stats, ab = C.c_void_p(), C.c_void_p(), C.c_void_p(), _lib.MtgCompaction(), _lib.MtgAbundance()
-    more = (C.byref(counts),) if kmer_counts else ()
-    if isinstance(seqs_or_store, UnitigStore):
-        call = L.mtg_compact_unitigs_counted_kmers_store if kmer_counts else L.mtg_compact_unitigs_counted_store
-        call(seqs_or_store.handle, k, min_abundance, device_id, C.byref(out), C.byref(stats), C.byref(ab), C.byref(sums), *more)
-    else:
-        d, o, n, keep = _sequence_arrays(seqs_or_store)
-        call = L.mtg_compact_unitigs_counted_kmers if kmer_counts else L.mtg_compact_unitigs_counted
-        call(d, o, n, k, min_abundance, device_id, C.byref(out), C.byref(stats), C.byref(ab), C.byref(sums), *more)
-        del keep
-    per_kmer = None
-    try:
-        n = int(L.mtg_abundance_sums_count(sums))
-        unitig_sums = (np.ctypeslib.as_array(C.cast(L.mtg_abundance_sums_array(sums), C.POINTER(C.c_uint64)), shape=(n,)).copy()
-                       if n else np.zeros(0, np.uint64))
-        if kmer_counts:
-            n = int(L.mtg_kmer_counts_count(counts))
-            per_kmer = (np.ctypeslib.as_array(C.cast(L.mtg_kmer_counts_array(counts), C.POINTER(C.c_uint32)), shape=(n,)).copy()
-                        if n else np.zeros(0, np.uint32))
-    finally:
-        L.mtg_abundance_sums_free(sums)
-        if kmer_counts:
-            L.mtg_kmer_counts_free(counts)
-    abundance = Abundance(int(ab.distinct_all), int(ab.distinct_kept), int(ab.max_abundance), int(ab.kept_occurrences),
-                          np.array(ab.spectrum, dtype=np.uint64), unitig_sums, per_kmer)
-    return UnitigStore(out.value), Compaction(**stats.as_dict()), abundance
+    return _compact(_COUNTED_KMERS if kmer_counts else _COUNTED, seqs_or_store, k, device_id, min_abundance)[:3]
 
 
 MAX_COLORS = 64
@@ -1011,6 +977,11 @@ class Colors:
         return (f"{self.n_colors} colours over {int(self.occupancy.sum())} k-mers: {self.core} core, {self.private} private")
 
 
+def _record_count(seqs_or_store) -> int:
+    """The records of a UnitigStore, a list of str or (uint8 array, offsets)."""
+    return len(seqs_or_store[1]) - 1 if isinstance(seqs_or_store, tuple) else len(seqs_or_store)
+
+
 def _record_colors(record_colors, n_colors, n_records: int) -> np.ndarray:
     """The colours of a coloured call as uint8[n_records]; ValueError for what the library would abort on."""
     if isinstance(n_colors, bool) or not isinstance(n_colors, (int, np.integer)) or not 1 <= n_colors <= MAX_COLORS:
@@ -1029,40 +1000,8 @@ def compact_unitigs_colored(seqs_or_store, k: int, record_colors, n_colors: int,
     integer in 0..n_colors - 1 per input record (its file, sample or haplotype), n_colors in 1..64."""
     if min_abundance < 1:
         raise ValueError("min_abundance must be >= 1")
-    if isinstance(seqs_or_store, UnitigStore):
-        n_records = len(seqs_or_store)
-    elif isinstance(seqs_or_store, tuple):
-        n_records = len(seqs_or_store[1]) - 1
-    else:
-        n_records = len(seqs_or_store)
-    rc = _record_colors(record_colors, n_colors, n_records)
-    L = _lib.load()
-    out, sums, counts, masks = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
-    stats, ab, cs = _lib.MtgCompaction(), _lib.MtgAbundance(), _lib.MtgColorStats()
-    tail = (device_id, C.byref(out), C.byref(stats), C.byref(ab), C.byref(sums), C.byref(counts), C.byref(masks), C.byref(cs))
-    if isinstance(seqs_or_store, UnitigStore):
-        L.mtg_compact_unitigs_colored_store(seqs_or_store.handle, k, min_abundance, _ptr(rc), n_colors, *tail)
-    else:
-        d, o, n, keep = _sequence_arrays(seqs_or_store)
-        L.mtg_compact_unitigs_colored(d, o, n, k, min_abundance, _ptr(rc), n_colors, *tail)
-        del keep
-    try:
-        def taken(count, array, handle, ctype, dtype):
-            n = int(count(handle))
-            return np.ctypeslib.as_array(C.cast(array(handle), C.POINTER(ctype)), shape=(n,)).copy() if n else np.zeros(0, dtype)
-
-        unitig_sums = taken(L.mtg_abundance_sums_count, L.mtg_abundance_sums_array, sums, C.c_uint64, np.uint64)
-        per_kmer = taken(L.mtg_kmer_counts_count, L.mtg_kmer_counts_array, counts, C.c_uint32, np.uint32)
-        kmer_colors = taken(L.mtg_kmer_colors_count, L.mtg_kmer_colors_array, masks, C.c_uint64, np.uint64)
-    finally:
-        L.mtg_abundance_sums_free(sums)
-        L.mtg_kmer_counts_free(counts)
-        L.mtg_kmer_colors_free(masks)
-    abundance = Abundance(int(ab.distinct_all), int(ab.distinct_kept), int(ab.max_abundance), int(ab.kept_occurrences),
-                          np.array(ab.spectrum, dtype=np.uint64), unitig_sums, per_kmer)
-    colors = Colors(int(n_colors), kmer_colors, np.array(cs.per_color, dtype=np.uint64)[:n_colors].copy(), np.array(cs.occupancy, dtype=np.uint64),
-                    np.array(cs.shared, dtype=np.uint64).reshape(MAX_COLORS, MAX_COLORS)[:n_colors, :n_colors].copy())
-    return UnitigStore(out.value), Compaction(**stats.as_dict()), abundance, colors
+    rc = _record_colors(record_colors, n_colors, _record_count(seqs_or_store))
+    return _compact(_COLORED, seqs_or_store, k, device_id, min_abundance, rc, int(n_colors))[:4]
 
 
 # the counts kernel of the class dictionary (compact_device.hip, DESIGN.md 23): the classes it keeps in LDS, its largest grid, its block
@@ -1100,16 +1039,18 @@ class ColorClasses:
                 f"{bin(int(self.masks[top])).count('1')} carriers) with {int(self.kmers[top])} of {int(self.kmers.sum())} k-mers")
 
 
+def _taken(n, pointer, dtype) -> np.ndarray:
+    """A copy of the n entries of a vector behind one of the library's handles."""
+    ctype = np.ctypeslib.as_ctypes_type(dtype)
+    return np.ctypeslib.as_array(C.cast(pointer, C.POINTER(ctype)), shape=(int(n),)).copy() if n else np.zeros(0, dtype)
+
+
 def _color_classes_taken(L, classes) -> ColorClasses:
     """The arrays of an mtg_color_classes handle, copied."""
-    def taken(n, pointer, ctype, dtype):
-        n = int(n)
-        return np.ctypeslib.as_array(C.cast(pointer, C.POINTER(ctype)), shape=(n,)).copy() if n else np.zeros(0, dtype)
-
     nc = L.mtg_color_classes_count(classes)
-    return ColorClasses(*(taken(nc, f(classes), C.c_uint64, np.uint64) for f in (L.mtg_color_classes_masks, L.mtg_color_classes_kmers,
-                                                                                   L.mtg_color_classes_runs, L.mtg_color_classes_first)),
-                        taken(L.mtg_color_classes_kmer_class_count(classes), L.mtg_color_classes_kmer_class(classes), C.c_uint32, np.uint32))
+    return ColorClasses(*(_taken(nc, f(classes), np.uint64) for f in (L.mtg_color_classes_masks, L.mtg_color_classes_kmers,
+                                                                        L.mtg_color_classes_runs, L.mtg_color_classes_first)),
+                        _taken(L.mtg_color_classes_kmer_class_count(classes), L.mtg_color_classes_kmer_class(classes), np.uint32))
 
 
 def color_classes(kmer_colors, unitig_kmers, device_id: int = 0) -> ColorClasses:
@@ -1141,42 +1082,61 @@ def compact_unitigs_colored_classes(seqs_or_store, k: int, record_colors, n_colo
         raise ValueError("min_abundance must be >= 1")
     if not isinstance(split, (bool, np.bool_)):
         raise ValueError(f"split must be True or False, not {split!r}")
-    if isinstance(seqs_or_store, UnitigStore):
-        n_records = len(seqs_or_store)
-    elif isinstance(seqs_or_store, tuple):
-        n_records = len(seqs_or_store[1]) - 1
-    else:
-        n_records = len(seqs_or_store)
-    rc = _record_colors(record_colors, n_colors, n_records)
+    rc = _record_colors(record_colors, n_colors, _record_count(seqs_or_store))
+    return _compact(_CLASSES, seqs_or_store, k, device_id, min_abundance, rc, int(n_colors), split)
+
+
+# The rungs of the compaction ladder and the C symbol each reaches (+ "_store" for a UnitigStore). The argument list of a rung is
+# the one below it plus its own (_compact): a new rung is one row here and one `if` there.
+_PLAIN, _COUNTED, _COUNTED_KMERS, _COLORED, _CLASSES = range(5)
+_COMPACT_SYMBOLS = ("mtg_compact_unitigs", "mtg_compact_unitigs_counted", "mtg_compact_unitigs_counted_kmers", "mtg_compact_unitigs_colored",
+                    "mtg_compact_unitigs_colored_classes")
+
+
+def _compact(rung: int, seqs_or_store, k: int, device_id: int, min_abundance: int = 1, record_colors=None, n_colors: int = 0,
+             split: bool = False):
+    """The one body of compact_unitigs* -> (UnitigStore, Compaction, Abundance, Colors, ColorClasses), None above the rung. The
+    arguments are the callers' to check."""
     L = _lib.load()
-    out, sums, counts, masks, classes = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+    out, sums, counts, masks, classes = (C.c_void_p() for _ in range(5))
     stats, ab, cs = _lib.MtgCompaction(), _lib.MtgAbundance(), _lib.MtgColorStats()
-    tail = (int(bool(split)), device_id, C.byref(out), C.byref(stats), C.byref(ab), C.byref(sums), C.byref(counts), C.byref(masks), C.byref(cs),
-            C.byref(classes))
+    ins, outs = [k], [C.byref(out), C.byref(stats)]
+    if rung >= _COUNTED:
+        ins += [min_abundance]
+        outs += [C.byref(ab), C.byref(sums)]
+    if rung >= _COUNTED_KMERS:
+        outs += [C.byref(counts)]
+    if rung >= _COLORED:
+        ins += [_ptr(record_colors), n_colors]
+        outs += [C.byref(masks), C.byref(cs)]
+    if rung >= _CLASSES:
+        ins += [int(bool(split))]
+        outs += [C.byref(classes)]
+    ins += [device_id]
     if isinstance(seqs_or_store, UnitigStore):
-        L.mtg_compact_unitigs_colored_classes_store(seqs_or_store.handle, k, min_abundance, _ptr(rc), n_colors, *tail)
+        getattr(L, _COMPACT_SYMBOLS[rung] + "_store")(seqs_or_store.handle, *ins, *outs)
     else:
         d, o, n, keep = _sequence_arrays(seqs_or_store)
-        L.mtg_compact_unitigs_colored_classes(d, o, n, k, min_abundance, _ptr(rc), n_colors, *tail)
+        getattr(L, _COMPACT_SYMBOLS[rung])(d, o, n, *ins, *outs)
         del keep
-    try:
-        def taken(n, pointer, ctype, dtype):
-            n = int(n)
-            return np.ctypeslib.as_array(C.cast(pointer, C.POINTER(ctype)), shape=(n,)).copy() if n else np.zeros(0, dtype)
-
-        unitig_sums = taken(L.mtg_abundance_sums_count(sums), L.mtg_abundance_sums_array(sums), C.c_uint64, np.uint64)
-        per_kmer = taken(L.mtg_kmer_counts_count(counts), L.mtg_kmer_counts_array(counts), C.c_uint32, np.uint32)
-        kmer_colors = taken(L.mtg_kmer_colors_count(masks), L.mtg_kmer_colors_array(masks), C.c_uint64, np.uint64)
-        cc = _color_classes_taken(L, classes)
+    abundance = colors = cc = None
+    try:  # (a handle the rung does not reach is still null: nothing to take, and freeing it is a no-op)
+        if rung >= _COUNTED:
+            per_kmer = _taken(L.mtg_kmer_counts_count(counts), L.mtg_kmer_counts_array(counts), np.uint32) if rung >= _COUNTED_KMERS else None
+            abundance = Abundance(int(ab.distinct_all), int(ab.distinct_kept), int(ab.max_abundance), int(ab.kept_occurrences),
+                                  np.array(ab.spectrum, dtype=np.uint64),
+                                  _taken(L.mtg_abundance_sums_count(sums), L.mtg_abundance_sums_array(sums), np.uint64), per_kmer)
+        if rung >= _COLORED:
+            colors = Colors(n_colors, _taken(L.mtg_kmer_colors_count(masks), L.mtg_kmer_colors_array(masks), np.uint64),
+                            np.array(cs.per_color, dtype=np.uint64)[:n_colors].copy(), np.array(cs.occupancy, dtype=np.uint64),
+                            np.array(cs.shared, dtype=np.uint64).reshape(MAX_COLORS, MAX_COLORS)[:n_colors, :n_colors].copy())
+        if rung >= _CLASSES:
+            cc = _color_classes_taken(L, classes)
     finally:
         L.mtg_abundance_sums_free(sums)
         L.mtg_kmer_counts_free(counts)
         L.mtg_kmer_colors_free(masks)
         L.mtg_color_classes_free(classes)
-    abundance = Abundance(int(ab.distinct_all), int(ab.distinct_kept), int(ab.max_abundance), int(ab.kept_occurrences),
-                          np.array(ab.spectrum, dtype=np.uint64), unitig_sums, per_kmer)
-    colors = Colors(int(n_colors), kmer_colors, np.array(cs.per_color, dtype=np.uint64)[:n_colors].copy(), np.array(cs.occupancy, dtype=np.uint64),
-                    np.array(cs.shared, dtype=np.uint64).reshape(MAX_COLORS, MAX_COLORS)[:n_colors, :n_colors].copy())
     return UnitigStore(out.value), Compaction(**stats.as_dict()), abundance, colors, cc
 
 
@@ -1514,43 +1474,35 @@ class KmerIndex:
         if self.colored:
             if isinstance(n_colors, bool) or not isinstance(n_colors, (int, np.integer)) or not 1 <= n_colors <= MAX_COLORS:
                 raise ValueError(f"n_colors must be in 1..{MAX_COLORS}, not {n_colors!r}")
+        elif n_colors is not None:
+            raise ValueError("n_colors needs colors")
+        c = w = None
+        if self.colored or self.weighted:
             windows = _window_count(seqs_or_store, k) if k >= 1 else -1
+        if self.colored:
             c = np.ascontiguousarray(colors, np.uint64)
-            w = np.ascontiguousarray(weights, np.uint32) if self.weighted else None
             if c.ndim != 1 or len(c) != windows:
                 raise ValueError(f"colors must hold one entry per window: {c.shape} for {windows} windows")
             if n_colors < MAX_COLORS and len(c) and int(c.max()) >> int(n_colors):
                 raise ValueError(f"a mask has a colour beyond the {n_colors} given")
-            if w is not None and (w.ndim != 1 or len(w) != windows):
-                raise ValueError(f"weights must hold one entry per window: {w.shape} for {windows} windows")
-            payload = (_ptr(w), len(w) if w is not None else 0, _ptr(c), len(c), int(n_colors), int(self.locating), device_id)
-            if isinstance(seqs_or_store, UnitigStore):
-                self._h = self._L.mtg_kmer_index_build_annotated_store(seqs_or_store.handle, k, *payload)
-            else:
-                d, o, n, keep = _sequence_arrays(seqs_or_store)
-                self._h = self._L.mtg_kmer_index_build_annotated(d, o, n, k, *payload)
-                del keep
-            self.n_colors = int(n_colors)
-        elif n_colors is not None:
-            raise ValueError("n_colors needs colors")
-        elif self.weighted:
+        if self.weighted:
             w = np.ascontiguousarray(weights, np.uint32)
-            windows = _window_count(seqs_or_store, k) if k >= 1 else -1
             if w.ndim != 1 or len(w) != windows:
                 raise ValueError(f"weights must hold one entry per window: {w.shape} for {windows} windows")
-            if isinstance(seqs_or_store, UnitigStore):
-                self._h = self._L.mtg_kmer_index_build_weighted_store(seqs_or_store.handle, k, _ptr(w), len(w), int(self.locating), device_id)
-            else:
-                d, o, n, keep = _sequence_arrays(seqs_or_store)
-                self._h = self._L.mtg_kmer_index_build_weighted(d, o, n, k, _ptr(w), len(w), int(self.locating), device_id)
-                del keep
-        elif isinstance(seqs_or_store, UnitigStore):
-            build = self._L.mtg_kmer_index_build_locating_store if locate else self._L.mtg_kmer_index_build_store
-            self._h = build(seqs_or_store.handle, k, device_id)
+        # one symbol (+ "_store" for a UnitigStore) and what it takes behind k, per kind of index
+        if self.colored:
+            build, payload = "mtg_kmer_index_build_annotated", (_ptr(w), len(w) if self.weighted else 0, _ptr(c), len(c), int(n_colors),
+                                                                int(self.locating), device_id)
+            self.n_colors = int(n_colors)
+        elif self.weighted:
+            build, payload = "mtg_kmer_index_build_weighted", (_ptr(w), len(w), int(self.locating), device_id)
+        else:
+            build, payload = "mtg_kmer_index_build_locating" if locate else "mtg_kmer_index_build", (device_id,)
+        if isinstance(seqs_or_store, UnitigStore):
+            self._h = getattr(self._L, build + "_store")(seqs_or_store.handle, k, *payload)
         else:
             d, o, n, keep = _sequence_arrays(seqs_or_store)
-            build = self._L.mtg_kmer_index_build_locating if locate else self._L.mtg_kmer_index_build
-            self._h = build(d, o, n, k, device_id)
+            self._h = getattr(self._L, build)(d, o, n, k, *payload)
             del keep
         out = _lib.MtgKmerIndexInfo()
         self._L.mtg_kmer_index_get_info(self._h, C.byref(out))
@@ -1569,14 +1521,21 @@ class KmerIndex:
     def __exit__(self, *exc):
         self.close()
 
+    def _probe_inputs(self, seqs_or_store, able: bool = True, needs: str = ""):
+        """What every probe starts from -- the index open (checked first) and `able` to answer, else ValueError(needs) -- as (data,
+        offsets pointer, records, keep-alive, a copy of the offsets, and kmers, valid, found: zeroed uint64 per record)."""
+        if not self._h:
+            raise ValueError("the index is closed")
+        if not able:
+            raise ValueError(needs)
+        d, o, n, keep = _sequence_arrays(seqs_or_store)
+        off = np.ctypeslib.as_array(C.cast(o, C.POINTER(C.c_uint64)), shape=(n + 1,)).copy()
+        return (d, o, n, keep, off, *(np.zeros(n, np.uint64) for _ in range(3)))
+
     def query(self, seqs_or_store, bits: bool = False) -> KmerQueryResult:
         """Per record of seqs_or_store (UnitigStore, list of str, or (uint8 array, offsets); ANY bytes): windows, valid windows,
         windows found in the index. bits: also the two bit arrays that presence() reads."""
-        if not self._h:
-            raise ValueError("the index is closed")
-        d, o, n, keep = _sequence_arrays(seqs_or_store)
-        off = np.ctypeslib.as_array(C.cast(o, C.POINTER(C.c_uint64)), shape=(n + 1,)).copy()
-        kmers, valid, found = (np.zeros(n, np.uint64) for _ in range(3))
+        d, o, n, keep, off, kmers, valid, found = self._probe_inputs(seqs_or_store)
         words = (int(off[n]) + 63) // 64
         vb, pb = (np.zeros(words, np.uint64), np.zeros(words, np.uint64)) if bits else (None, None)
         self._L.mtg_kmer_index_query(self._h, d, o, n, _ptr(kmers), _ptr(valid), _ptr(found), _ptr(pb) if bits else None,
@@ -1588,13 +1547,7 @@ class KmerIndex:
         """query()'s counts per record plus where the found windows lie in the indexed sequences, folded into maximal collinear
         runs (KmerLocateResult). A k-mer that occurs several times in the index is reported at its smallest position only. Needs
         an index built with locate=True."""
-        if not self._h:
-            raise ValueError("the index is closed")
-        if not self.locating:
-            raise ValueError("locate() needs an index built with locate=True")
-        d, o, n, keep = _sequence_arrays(seqs_or_store)
-        off = np.ctypeslib.as_array(C.cast(o, C.POINTER(C.c_uint64)), shape=(n + 1,)).copy()
-        kmers, valid, found = (np.zeros(n, np.uint64) for _ in range(3))
+        d, o, n, keep, off, kmers, valid, found = self._probe_inputs(seqs_or_store, self.locating, "locate() needs an index built with locate=True")
         h = C.c_void_p()
         self._L.mtg_kmer_index_locate(self._h, d, o, n, _ptr(kmers), _ptr(valid), _ptr(found), C.byref(h))
         del keep
@@ -1614,14 +1567,8 @@ class KmerIndex:
     def abundance(self, seqs_or_store, per_window: bool = False) -> KmerAbundanceResult:
         """query()'s counts per record plus the sum, the smallest and the largest weight over the record's found windows
         (KmerAbundanceResult); per_window: also the weight at every window start. Needs an index built with weights."""
-        if not self._h:
-            raise ValueError("the index is closed")
-        if not self.weighted:
-            raise ValueError("abundance() needs an index built with weights")
-        d, o, n, keep = _sequence_arrays(seqs_or_store)
-        off = np.ctypeslib.as_array(C.cast(o, C.POINTER(C.c_uint64)), shape=(n + 1,)).copy()
-        kmers, valid, found, total = (np.zeros(n, np.uint64) for _ in range(4))
-        lo, hi = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        d, o, n, keep, off, kmers, valid, found = self._probe_inputs(seqs_or_store, self.weighted, "abundance() needs an index built with weights")
+        total, lo, hi = np.zeros(n, np.uint64), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
         pw = np.zeros(int(off[n]), np.uint32) if per_window else None
         self._L.mtg_kmer_index_abundance(self._h, d, o, n, _ptr(kmers), _ptr(valid), _ptr(found), _ptr(total), _ptr(lo), _ptr(hi),
                                          _ptr(pw) if per_window else None)
@@ -1631,13 +1578,7 @@ class KmerIndex:
     def color_hits(self, seqs_or_store, per_window: bool = False) -> KmerColorResult:
         """query()'s counts per record plus, per record and colour, the found windows whose k-mer that colour carries
         (KmerColorResult); per_window: also the mask at every window start. Needs an index built with colors."""
-        if not self._h:
-            raise ValueError("the index is closed")
-        if not self.colored:
-            raise ValueError("color_hits() needs an index built with colors")
-        d, o, n, keep = _sequence_arrays(seqs_or_store)
-        off = np.ctypeslib.as_array(C.cast(o, C.POINTER(C.c_uint64)), shape=(n + 1,)).copy()
-        kmers, valid, found = (np.zeros(n, np.uint64) for _ in range(3))
+        d, o, n, keep, off, kmers, valid, found = self._probe_inputs(seqs_or_store, self.colored, "color_hits() needs an index built with colors")
         per_color = np.zeros((n, self.n_colors), np.uint32)
         pw = np.zeros(int(off[n]), np.uint64) if per_window else None
         self._L.mtg_kmer_index_colors(self._h, d, o, n, _ptr(kmers), _ptr(valid), _ptr(found), _ptr(per_color), _ptr(pw) if per_window else None)

@@ -64,6 +64,9 @@
 // masks (the kernels under "colour classes" below: per run of equal masks, never per k-mer), and with split = 1 succ_kernel<true>,
 // which keeps a successor only where both k-mers have one mask, so that every unitig is monochromatic; rank, emit, sums, counts and
 // ordered masks follow from succ unchanged. Memory added after emit: 12 N + 48 per run + 32 per class.
+//
+// All of these enter through device_compact_unitigs(CompactRequest) (device.hpp): one rung of the ladder per pointer of the request --
+// Counted, Colored, Classed --, null where the call does not climb that far.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -587,28 +590,6 @@ int log2_ceil(uint64_t n) {
     return r;
 }
 
-// what a counted call adds: the threshold in, the statistics and the per-unitig sums out
-struct Counted {
-    uint64_t m;
-    mtg_abundance *abundance;
-    std::vector<uint64_t> *sums;
-    std::vector<uint32_t> *kmer_counts;  // null, or: every kept k-mer's abundance in window order of the output store
-};
-// what a coloured call adds to a counted one
-struct Colored {
-    const uint8_t *record_colors;  // [n_rec], each < n_colors
-    uint64_t n_colors;
-    std::vector<uint64_t> *kmer_colors;  // every kept k-mer's mask, indexed like kmer_counts
-    mtg_color_stats *stats;
-    double *stats_ms;  // HIP-event time of color_stats_kernel
-};
-// what a call with colour classes adds to a coloured one
-struct Classed {
-    bool split;  // monochromatic unitigs: succ_kernel<true>
-    ColorClasses *out;
-    ColorClassTimes *times;
-};
-
 // The class dictionary of a store's masks in window order (ordered: [N], out_off: the unitigs' character offsets). Device memory, all
 // from the arena: 8 B per k-mer (head, run number) and 4 B more for kmer_class; per run R 4 (start) + 4 (slot) + 4 (class) + 4 (flag,
 // scanned in place) + 2 x (8 + 4 + 4) (the table: key, smallest run, class per slot); per class 32 B.
@@ -1050,41 +1031,14 @@ UnitigStore *compact(const char *data, const uint64_t *off, uint64_t n_rec, uint
 
 }  // namespace
 
-UnitigStore *device_compact_unitigs(const char *data, const uint64_t *off, uint64_t n_rec, uint64_t k, int device_id, mtg_compaction *stats_out,
-                                    CompactTimes *times) {
-    return compact(data, off, n_rec, k, device_id, stats_out, times, nullptr);
-}
-
-UnitigStore *device_compact_unitigs_counted(const char *data, const uint64_t *off, uint64_t n_rec, uint64_t k, uint64_t min_abundance, int device_id,
-                                            mtg_compaction *stats_out, mtg_abundance *abundance_out, std::vector<uint64_t> *unitig_sums,
-                                            CompactTimes *times, std::vector<uint32_t> *kmer_counts) {
-    if (!unitig_sums) MTG_DIE("mtg_compact_unitigs_counted: null argument");
-    const Counted c{min_abundance, abundance_out, unitig_sums, kmer_counts};
-    return compact(data, off, n_rec, k, device_id, stats_out, times, &c);
-}
-
-UnitigStore *device_compact_unitigs_colored(const char *data, const uint64_t *off, uint64_t n_rec, uint64_t k, uint64_t min_abundance,
-                                            const uint8_t *record_colors, uint64_t n_colors, int device_id, mtg_compaction *stats_out,
-                                            mtg_abundance *abundance_out, std::vector<uint64_t> *unitig_sums, std::vector<uint32_t> *kmer_counts,
-                                            std::vector<uint64_t> *kmer_colors, mtg_color_stats *color_stats, CompactTimes *times, double *stats_ms) {
-    if (!unitig_sums || !kmer_counts || !kmer_colors || !color_stats || !stats_ms) MTG_DIE("mtg_compact_unitigs_colored: null argument");
-    const Counted c{min_abundance, abundance_out, unitig_sums, kmer_counts};
-    const Colored col{record_colors, n_colors, kmer_colors, color_stats, stats_ms};
-    return compact(data, off, n_rec, k, device_id, stats_out, times, &c, &col);
-}
-
-UnitigStore *device_compact_unitigs_colored_classes(const char *data, const uint64_t *off, uint64_t n_rec, uint64_t k, uint64_t min_abundance,
-                                                    const uint8_t *record_colors, uint64_t n_colors, bool split, int device_id,
-                                                    mtg_compaction *stats_out, mtg_abundance *abundance_out, std::vector<uint64_t> *unitig_sums,
-                                                    std::vector<uint32_t> *kmer_counts, std::vector<uint64_t> *kmer_colors,
-                                                    mtg_color_stats *color_stats, ColorClasses *classes, CompactTimes *times, double *stats_ms,
-                                                    ColorClassTimes *class_times) {
-    if (!unitig_sums || !kmer_counts || !kmer_colors || !color_stats || !classes || !stats_ms || !class_times)
-        MTG_DIE("mtg_compact_unitigs_colored_classes: null argument");
-    const Counted c{min_abundance, abundance_out, unitig_sums, kmer_counts};
-    const Colored col{record_colors, n_colors, kmer_colors, color_stats, stats_ms};
-    const Classed cl{split, classes, class_times};
-    return compact(data, off, n_rec, k, device_id, stats_out, times, &c, &col, &cl);
+UnitigStore *device_compact_unitigs(const CompactRequest &rq) {
+    const Counted *c = rq.counted;
+    const Colored *col = rq.colored;
+    const Classed *cl = rq.classed;
+    if ((c && !c->sums) || (col && (!c || !c->kmer_counts || !col->kmer_colors || !col->stats || !col->stats_ms)) ||
+        (cl && (!col || !cl->out || !cl->times)))
+        MTG_DIE("%s: null argument", rq.who);
+    return compact(rq.data, rq.off, rq.n_rec, rq.k, rq.device_id, rq.stats_out, rq.times, c, col, cl);
 }
 
 void device_color_classes(const uint64_t *kmer_colors, uint64_t n, const uint64_t *unitig_kmers, uint64_t n_unitigs, int device_id, ColorClasses *out,

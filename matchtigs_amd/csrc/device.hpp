@@ -195,26 +195,29 @@ struct CompactTimes {
     int rounds = 0;
     uint64_t bytes = 0, peak_arena_bytes = 0;
 };
-UnitigStore *device_compact_unitigs(const char *data, const uint64_t *off, uint64_t n_rec, uint64_t k, int device_id, mtg_compaction *stats_out,
-                                    CompactTimes *times);
-// ... of the k-mers whose abundance reaches min_abundance: the statistics of the counting and, per unitig in the
+// What a counted call adds: the k-mers whose abundance reaches m, the statistics of the counting and, per unitig in the
 // store's order, the sum of its k-mers' abundances. The spectrum sweep is booked under ids_ms, the sums under emit_ms.
-// kmer_counts, if given: every kept k-mer's abundance in window order of the store -- entry (windows of the earlier
-// unitigs) + j belongs to the k-mer at offset j of unitig u --, the array the sums are scanned from; its download is booked under
-// download_ms.
-UnitigStore *device_compact_unitigs_counted(const char *data, const uint64_t *off, uint64_t n_rec, uint64_t k, uint64_t min_abundance, int device_id,
-                                            mtg_compaction *stats_out, mtg_abundance *abundance_out, std::vector<uint64_t> *unitig_sums,
-                                            CompactTimes *times, std::vector<uint32_t> *kmer_counts = nullptr);
-// ... with a colour per record: the counted call that hands out the counts, plus every kept k-mer's colour mask
-// (indexed like kmer_counts) and the statistics over the masks. stats_ms: HIP-event time of the statistics kernel (part of emit_ms).
-UnitigStore *device_compact_unitigs_colored(const char *data, const uint64_t *off, uint64_t n_rec, uint64_t k, uint64_t min_abundance,
-                                            const uint8_t *record_colors, uint64_t n_colors, int device_id, mtg_compaction *stats_out,
-                                            mtg_abundance *abundance_out, std::vector<uint64_t> *unitig_sums, std::vector<uint32_t> *kmer_counts,
-                                            std::vector<uint64_t> *kmer_colors, mtg_color_stats *color_stats, CompactTimes *times, double *stats_ms);
-// ... with the colour classes of the output store: the distinct masks numbered in the order of the first window that
-// shows them; per class its mask, k-mers, runs (maximal stretches of consecutive windows of one unitig with equal masks) and first
-// window; per window its class. split: a node is passable only if the k-mers that enter and leave it have equal masks, so every unitig
-// is one run. class_times: HIP-event time of the dictionary's phases, its download by the host clock.
+struct Counted {
+    uint64_t m;
+    mtg_abundance *abundance;
+    std::vector<uint64_t> *sums;
+    // null, or: every kept k-mer's abundance in window order of the output store -- entry (windows of the earlier
+    // unitigs) + j belongs to the k-mer at offset j of unitig u --, the array the sums are scanned from; its download is booked
+    // under download_ms
+    std::vector<uint32_t> *kmer_counts;
+};
+// What a coloured call adds to a counted one that hands out the counts: a colour per record in, every kept k-mer's
+// colour mask (indexed like kmer_counts) and the statistics over the masks out.
+struct Colored {
+    const uint8_t *record_colors;  // [n_rec], each < n_colors
+    uint64_t n_colors;
+    std::vector<uint64_t> *kmer_colors;
+    mtg_color_stats *stats;
+    double *stats_ms;  // HIP-event time of color_stats_kernel (part of emit_ms)
+};
+// What a call with colour classes adds to a coloured one: the distinct masks of the output store numbered in the order
+// of the first window that shows them; per class its mask, k-mers, runs (maximal stretches of consecutive windows of one unitig with
+// equal masks) and first window; per window its class. times: HIP-event time of the dictionary's phases, its download by the host clock.
 struct ColorClasses {
     std::vector<uint64_t> masks, kmers, runs, first;
     std::vector<uint32_t> kmer_class;
@@ -223,12 +226,26 @@ struct ColorClasses {
 struct ColorClassTimes {
     double heads_ms = 0, table_ms = 0, ids_ms = 0, counts_ms = 0, download_ms = 0;
 };
-UnitigStore *device_compact_unitigs_colored_classes(const char *data, const uint64_t *off, uint64_t n_rec, uint64_t k, uint64_t min_abundance,
-                                                    const uint8_t *record_colors, uint64_t n_colors, bool split, int device_id,
-                                                    mtg_compaction *stats_out, mtg_abundance *abundance_out, std::vector<uint64_t> *unitig_sums,
-                                                    std::vector<uint32_t> *kmer_counts, std::vector<uint64_t> *kmer_colors,
-                                                    mtg_color_stats *color_stats, ColorClasses *classes, CompactTimes *times, double *stats_ms,
-                                                    ColorClassTimes *class_times);
+struct Classed {
+    bool split;  // a node is passable only if the k-mers that enter and leave it have equal masks: every unitig is one run
+    ColorClasses *out;
+    ColorClassTimes *times;
+};
+// One compaction. who: the public entry point that was called, for the messages. Each rung of the ladder is one pointer, null where
+// the call does not climb that far; a rung needs the ones below it.
+struct CompactRequest {
+    const char *who;
+    const char *data;
+    const uint64_t *off;
+    uint64_t n_rec, k;
+    int device_id;
+    mtg_compaction *stats_out;
+    CompactTimes *times;
+    const Counted *counted;
+    const Colored *colored;
+    const Classed *classed;
+};
+UnitigStore *device_compact_unitigs(const CompactRequest &rq);
 // ... of masks and unitig lengths handed in (kmer_colors: n masks in window order, none 0; unitig_kmers: n_unitigs lengths that sum to n)
 void device_color_classes(const uint64_t *kmer_colors, uint64_t n, const uint64_t *unitig_kmers, uint64_t n_unitigs, int device_id, ColorClasses *out,
                           ColorClassTimes *times);

@@ -793,48 +793,76 @@ void mtg_read_sequences_named(const char *path, mtg_unitigs **seqs_out, mtg_unit
 }
 // ---- unitig compaction on the GPU (compact_device.hip) ----
 static thread_local CompactTimes g_last_compact;
+static thread_local ColorClassTimes g_last_color_class;
+struct mtg_abundance_sums { std::vector<uint64_t> v; };
+struct mtg_kmer_counts { std::vector<uint32_t> v; };
+struct mtg_kmer_colors { std::vector<uint64_t> v; };
+struct mtg_color_classes { ColorClasses c; };  // 
+// The ladder of the compaction's entry points: each rung takes and hands out what the one below does, and more. A new rung is one
+// value here, its fields behind the others in CompactIn / CompactOut and its lines in compact_call.
+enum CompactRung { PLAIN, COUNTED, COUNTED_KMERS, COLORED, CLASSES };
+struct CompactIn {
+    const char *data;
+    const uint64_t *offsets;
+    uint64_t n, k;
+    int device_id;
+    uint64_t min_abundance = 1;              // from COUNTED on
+    const uint8_t *record_colors = nullptr;  // from COLORED on
+    uint64_t n_colors = 0;
+    int split = 0;                           // CLASSES
+};
+struct CompactOut {
+    mtg_unitigs **out;
+    mtg_compaction *stats;
+    mtg_abundance *abundance = nullptr;       // from COUNTED on
+    mtg_abundance_sums **sums = nullptr;
+    mtg_kmer_counts **kmer_counts = nullptr;  // from COUNTED_KMERS on
+    mtg_kmer_colors **kmer_colors = nullptr;  // from COLORED on
+    mtg_color_stats *color_stats = nullptr;
+    mtg_color_classes **classes = nullptr;    // CLASSES
+};
+// what all mtg_compact_unitigs* share: the argument checks, the handles and their way to the out-pointers (who: the entry point)
+static void compact_call(const char *who, CompactRung rung, const CompactIn &in, const CompactOut &o) {
+    if (!o.out || (rung >= COUNTED && !o.sums) || (rung >= COUNTED_KMERS && !o.kmer_counts) ||
+        (rung >= COLORED && (!o.kmer_colors || !o.color_stats)) || (rung >= CLASSES && !o.classes))
+        MTG_DIE("%s: null argument", who);
+    if (rung >= COUNTED && in.min_abundance == 0) MTG_DIE("%s: min_abundance must be >= 1", who);
+    if (rung >= CLASSES && in.split != 0 && in.split != 1) MTG_DIE("%s: split must be 0 or 1, not %d", who, in.split);
+    mtg_abundance_sums *s = rung >= COUNTED ? new mtg_abundance_sums() : nullptr;
+    mtg_kmer_counts *c = rung >= COUNTED_KMERS ? new mtg_kmer_counts() : nullptr;
+    mtg_kmer_colors *m = rung >= COLORED ? new mtg_kmer_colors() : nullptr;
+    mtg_color_classes *cl = rung >= CLASSES ? new mtg_color_classes() : nullptr;
+    const Counted counted{in.min_abundance, o.abundance, s ? &s->v : nullptr, c ? &c->v : nullptr};
+    const Colored colored{in.record_colors, in.n_colors, m ? &m->v : nullptr, o.color_stats, &g_last_kmer_color.stats_ms};
+    const Classed classed{in.split == 1, cl ? &cl->c : nullptr, &g_last_color_class};
+    *o.out = new mtg_unitigs{device_compact_unitigs({who, in.data, in.offsets, in.n, in.k, in.device_id, o.stats, &g_last_compact, s ? &counted : nullptr,
+                                                     m ? &colored : nullptr, cl ? &classed : nullptr})};
+    if (s) *o.sums = s;
+    if (c) *o.kmer_counts = c;
+    if (m) *o.kmer_colors = m;
+    if (cl) *o.classes = cl;
+}
 void mtg_compact_unitigs(const char *data, const uint64_t *offsets, uint64_t n, uint64_t k, int device_id, mtg_unitigs **out, mtg_compaction *stats) {
-    if (!out) MTG_DIE("mtg_compact_unitigs: null argument");
-    *out = new mtg_unitigs{device_compact_unitigs(data, offsets, n, k, device_id, stats, &g_last_compact)};
+    compact_call("mtg_compact_unitigs", PLAIN, {data, offsets, n, k, device_id}, {out, stats});
 }
 void mtg_compact_unitigs_store(const mtg_unitigs *in, uint64_t k, int device_id, mtg_unitigs **out, mtg_compaction *stats) {
     if (!in || !out) MTG_DIE("mtg_compact_unitigs_store: null argument");
-    *out = new mtg_unitigs{device_compact_unitigs(in->s->data.data(), in->s->off.data(), in->s->off.size() - 1, k, device_id, stats, &g_last_compact)};
+    mtg_compact_unitigs(in->s->data.data(), in->s->off.data(), in->s->off.size() - 1, k, device_id, out, stats);
 }
-struct mtg_abundance_sums { std::vector<uint64_t> v; };
 void mtg_compact_unitigs_counted(const char *data, const uint64_t *offsets, uint64_t n, uint64_t k, uint64_t min_abundance, int device_id,
                                  mtg_unitigs **out, mtg_compaction *stats, mtg_abundance *abundance, mtg_abundance_sums **sums) {
-    if (!out || !sums) MTG_DIE("mtg_compact_unitigs_counted: null argument");
-    if (min_abundance == 0) MTG_DIE("mtg_compact_unitigs_counted: min_abundance must be >= 1");
-    mtg_abundance_sums *s = new mtg_abundance_sums();
-    *out = new mtg_unitigs{device_compact_unitigs_counted(data, offsets, n, k, min_abundance, device_id, stats, abundance, &s->v, &g_last_compact)};
-    *sums = s;
+    compact_call("mtg_compact_unitigs_counted", COUNTED, {data, offsets, n, k, device_id, min_abundance}, {out, stats, abundance, sums});
 }
 void mtg_compact_unitigs_counted_store(const mtg_unitigs *in, uint64_t k, uint64_t min_abundance, int device_id, mtg_unitigs **out,
                                        mtg_compaction *stats, mtg_abundance *abundance, mtg_abundance_sums **sums) {
     if (!in) MTG_DIE("mtg_compact_unitigs_counted_store: null argument");
     mtg_compact_unitigs_counted(in->s->data.data(), in->s->off.data(), in->s->off.size() - 1, k, min_abundance, device_id, out, stats, abundance, sums);
 }
-uint64_t mtg_abundance_sums_count(const mtg_abundance_sums *sums) {
-    if (!sums) MTG_DIE("mtg_abundance_sums_count: null argument");
-    return sums->v.size();
-}
-const uint64_t *mtg_abundance_sums_array(const mtg_abundance_sums *sums) {
-    if (!sums) MTG_DIE("mtg_abundance_sums_array: null argument");
-    return sums->v.data();
-}
-void mtg_abundance_sums_free(mtg_abundance_sums *sums) { delete sums; }
-struct mtg_kmer_counts { std::vector<uint32_t> v; };
 void mtg_compact_unitigs_counted_kmers(const char *data, const uint64_t *offsets, uint64_t n, uint64_t k, uint64_t min_abundance, int device_id,
                                        mtg_unitigs **out, mtg_compaction *stats, mtg_abundance *abundance, mtg_abundance_sums **sums,
                                        mtg_kmer_counts **kmer_counts) {
-    if (!out || !sums || !kmer_counts) MTG_DIE("mtg_compact_unitigs_counted_kmers: null argument");
-    if (min_abundance == 0) MTG_DIE("mtg_compact_unitigs_counted_kmers: min_abundance must be >= 1");
-    mtg_abundance_sums *s = new mtg_abundance_sums();
-    mtg_kmer_counts *c = new mtg_kmer_counts();
-    *out = new mtg_unitigs{device_compact_unitigs_counted(data, offsets, n, k, min_abundance, device_id, stats, abundance, &s->v, &g_last_compact, &c->v)};
-    *sums = s;
-    *kmer_counts = c;
+    compact_call("mtg_compact_unitigs_counted_kmers", COUNTED_KMERS, {data, offsets, n, k, device_id, min_abundance},
+                 {out, stats, abundance, sums, kmer_counts});
 }
 void mtg_compact_unitigs_counted_kmers_store(const mtg_unitigs *in, uint64_t k, uint64_t min_abundance, int device_id, mtg_unitigs **out,
                                              mtg_compaction *stats, mtg_abundance *abundance, mtg_abundance_sums **sums,
@@ -843,30 +871,12 @@ void mtg_compact_unitigs_counted_kmers_store(const mtg_unitigs *in, uint64_t k, 
     mtg_compact_unitigs_counted_kmers(in->s->data.data(), in->s->off.data(), in->s->off.size() - 1, k, min_abundance, device_id, out, stats, abundance,
                                       sums, kmer_counts);
 }
-uint64_t mtg_kmer_counts_count(const mtg_kmer_counts *counts) {
-    if (!counts) MTG_DIE("mtg_kmer_counts_count: null argument");
-    return counts->v.size();
-}
-const uint32_t *mtg_kmer_counts_array(const mtg_kmer_counts *counts) {
-    if (!counts) MTG_DIE("mtg_kmer_counts_array: null argument");
-    return counts->v.data();
-}
-void mtg_kmer_counts_free(mtg_kmer_counts *counts) { delete counts; }
-struct mtg_kmer_colors { std::vector<uint64_t> v; };
 void mtg_compact_unitigs_colored(const char *data, const uint64_t *offsets, uint64_t n, uint64_t k, uint64_t min_abundance,
                                  const uint8_t *record_colors, uint64_t n_colors, int device_id, mtg_unitigs **out, mtg_compaction *stats,
                                  mtg_abundance *abundance, mtg_abundance_sums **sums, mtg_kmer_counts **kmer_counts,
                                  mtg_kmer_colors **kmer_colors, mtg_color_stats *color_stats) {
-    if (!out || !sums || !kmer_counts || !kmer_colors || !color_stats) MTG_DIE("mtg_compact_unitigs_colored: null argument");
-    if (min_abundance == 0) MTG_DIE("mtg_compact_unitigs_colored: min_abundance must be >= 1");
-    mtg_abundance_sums *s = new mtg_abundance_sums();
-    mtg_kmer_counts *c = new mtg_kmer_counts();
-    mtg_kmer_colors *m = new mtg_kmer_colors();
-    *out = new mtg_unitigs{device_compact_unitigs_colored(data, offsets, n, k, min_abundance, record_colors, n_colors, device_id, stats, abundance,
-                                                          &s->v, &c->v, &m->v, color_stats, &g_last_compact, &g_last_kmer_color.stats_ms)};
-    *sums = s;
-    *kmer_counts = c;
-    *kmer_colors = m;
+    compact_call("mtg_compact_unitigs_colored", COLORED, {data, offsets, n, k, device_id, min_abundance, record_colors, n_colors},
+                 {out, stats, abundance, sums, kmer_counts, kmer_colors, color_stats});
 }
 void mtg_compact_unitigs_colored_store(const mtg_unitigs *in, uint64_t k, uint64_t min_abundance, const uint8_t *record_colors,
                                        uint64_t n_colors, int device_id, mtg_unitigs **out, mtg_compaction *stats, mtg_abundance *abundance,
@@ -876,37 +886,13 @@ void mtg_compact_unitigs_colored_store(const mtg_unitigs *in, uint64_t k, uint64
     mtg_compact_unitigs_colored(in->s->data.data(), in->s->off.data(), in->s->off.size() - 1, k, min_abundance, record_colors, n_colors, device_id,
                                 out, stats, abundance, sums, kmer_counts, kmer_colors, color_stats);
 }
-uint64_t mtg_kmer_colors_count(const mtg_kmer_colors *colors) {
-    if (!colors) MTG_DIE("mtg_kmer_colors_count: null argument");
-    return colors->v.size();
-}
-const uint64_t *mtg_kmer_colors_array(const mtg_kmer_colors *colors) {
-    if (!colors) MTG_DIE("mtg_kmer_colors_array: null argument");
-    return colors->v.data();
-}
-void mtg_kmer_colors_free(mtg_kmer_colors *colors) { delete colors; }
-// ---- monochromatic unitigs and colour classes (DESIGN.md 23) ----
-struct mtg_color_classes { ColorClasses c; };
-static thread_local ColorClassTimes g_last_color_class;
 void mtg_compact_unitigs_colored_classes(const char *data, const uint64_t *offsets, uint64_t n, uint64_t k, uint64_t min_abundance,
                                          const uint8_t *record_colors, uint64_t n_colors, int split, int device_id, mtg_unitigs **out,
                                          mtg_compaction *stats, mtg_abundance *abundance, mtg_abundance_sums **sums,
                                          mtg_kmer_counts **kmer_counts, mtg_kmer_colors **kmer_colors, mtg_color_stats *color_stats,
                                          mtg_color_classes **classes) {
-    if (!out || !sums || !kmer_counts || !kmer_colors || !color_stats || !classes) MTG_DIE("mtg_compact_unitigs_colored_classes: null argument");
-    if (min_abundance == 0) MTG_DIE("mtg_compact_unitigs_colored_classes: min_abundance must be >= 1");
-    if (split != 0 && split != 1) MTG_DIE("mtg_compact_unitigs_colored_classes: split must be 0 or 1, not %d", split);
-    mtg_abundance_sums *s = new mtg_abundance_sums();
-    mtg_kmer_counts *c = new mtg_kmer_counts();
-    mtg_kmer_colors *m = new mtg_kmer_colors();
-    mtg_color_classes *cl = new mtg_color_classes();
-    *out = new mtg_unitigs{device_compact_unitigs_colored_classes(data, offsets, n, k, min_abundance, record_colors, n_colors, split == 1, device_id, stats,
-                                                                  abundance, &s->v, &c->v, &m->v, color_stats, &cl->c, &g_last_compact,
-                                                                  &g_last_kmer_color.stats_ms, &g_last_color_class)};
-    *sums = s;
-    *kmer_counts = c;
-    *kmer_colors = m;
-    *classes = cl;
+    compact_call("mtg_compact_unitigs_colored_classes", CLASSES, {data, offsets, n, k, device_id, min_abundance, record_colors, n_colors, split},
+                 {out, stats, abundance, sums, kmer_counts, kmer_colors, color_stats, classes});
 }
 void mtg_compact_unitigs_colored_classes_store(const mtg_unitigs *in, uint64_t k, uint64_t min_abundance, const uint8_t *record_colors,
                                                uint64_t n_colors, int split, int device_id, mtg_unitigs **out, mtg_compaction *stats,
@@ -916,6 +902,24 @@ void mtg_compact_unitigs_colored_classes_store(const mtg_unitigs *in, uint64_t k
     mtg_compact_unitigs_colored_classes(in->s->data.data(), in->s->off.data(), in->s->off.size() - 1, k, min_abundance, record_colors, n_colors, split,
                                         device_id, out, stats, abundance, sums, kmer_counts, kmer_colors, color_stats, classes);
 }
+// the vector behind one of the handles above (who: the entry point, for the message)
+extern "C++" {
+template <class Handle>
+static const auto &vector_of(const Handle *h, const char *who) {
+    if (!h) MTG_DIE("%s: null argument", who);
+    return h->v;
+}
+}
+uint64_t mtg_abundance_sums_count(const mtg_abundance_sums *sums) { return vector_of(sums, "mtg_abundance_sums_count").size(); }
+const uint64_t *mtg_abundance_sums_array(const mtg_abundance_sums *sums) { return vector_of(sums, "mtg_abundance_sums_array").data(); }
+void mtg_abundance_sums_free(mtg_abundance_sums *sums) { delete sums; }
+uint64_t mtg_kmer_counts_count(const mtg_kmer_counts *counts) { return vector_of(counts, "mtg_kmer_counts_count").size(); }
+const uint32_t *mtg_kmer_counts_array(const mtg_kmer_counts *counts) { return vector_of(counts, "mtg_kmer_counts_array").data(); }
+void mtg_kmer_counts_free(mtg_kmer_counts *counts) { delete counts; }
+uint64_t mtg_kmer_colors_count(const mtg_kmer_colors *colors) { return vector_of(colors, "mtg_kmer_colors_count").size(); }
+const uint64_t *mtg_kmer_colors_array(const mtg_kmer_colors *colors) { return vector_of(colors, "mtg_kmer_colors_array").data(); }
+void mtg_kmer_colors_free(mtg_kmer_colors *colors) { delete colors; }
+// ---- monochromatic unitigs and colour classes (DESIGN.md 23) ----
 void mtg_color_classes_build(const uint64_t *kmer_colors, uint64_t n, const uint64_t *unitig_kmers, uint64_t n_unitigs, int device_id,
                              mtg_color_classes **classes) {
     if (!classes) MTG_DIE("mtg_color_classes_build: null argument");

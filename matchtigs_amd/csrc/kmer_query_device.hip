@@ -426,6 +426,67 @@ struct KmerIndex {
     uint64_t n_colors = 0;                // coloured: 1 .. 64
 };
 
+namespace {
+
+// What the probe calls of an index share (query, abundance, colors, locate). probe_windows: the checks of the query, kmers[] filled,
+// valid[] and found[] zeroed; returns the query's bases (missing: an out-pointer of the caller's own is null).
+uint64_t probe_windows(const char *fn, uint64_t k, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid, uint64_t *found,
+                       bool missing) {
+    (void)check_offsets(fn, seq, off, n, k);
+    if (missing || (n && (!kmers || !valid || !found))) MTG_DIE("%s: null argument", fn);
+    if (off[n] >= POS_LIMIT) MTG_DIE("%s: %llu bases; the limit is 2^40 - 2", fn, (unsigned long long)off[n]);
+    for (uint64_t r = 0; r < n; r++) {
+        const uint64_t len = off[r + 1] - off[r];
+        kmers[r] = len >= k ? len - k + 1 : 0;
+        valid[r] = found[r] = 0;
+    }
+    return off[n];
+}
+
+int on_device(int device_id) {
+    HIP_CHECK(hipSetDevice(device_id));
+    return device_id;
+}
+
+// ... and one probe of a query that has bases: the query on the index's device, the kernels' arguments and the counters ([words * n]:
+// valid, found, then the caller's own). The caller allocates what else it needs, calls start(), launches its kernels between the marks
+// of ev and fetches valid and found with download_counts(); the phases every probe reports are in booked().
+template <int EVENTS = 2>
+struct Probe {
+    const uint64_t n, words;
+    const bool wide;  // the kernels' WIDE
+    const int device_id;
+    hipStream_t st = nullptr;
+    MaskedSeqStore store;
+    unsigned long long *d_counts = nullptr;
+    IndexArgs a{};
+    PhaseEvents<EVENTS> ev;
+
+    Probe(const KmerIndex *ix, const char *seq, const uint64_t *off, uint64_t n, uint64_t words)
+        : n(n), words(words), wide(ix->info.k >= 32), device_id(on_device(ix->device_id)), store(seq, off, n, st, device_id) {
+        hu::device_malloc(&d_counts, words * n * 8);
+        a.packed = store.packed; a.off = store.off; a.index_packed = ix->packed; a.table = ix->table; a.slots = ix->info.slots;
+        kw::window_args_set_k(a, ix->info.k);
+    }
+    ~Probe() { hu::device_free(d_counts); }
+    unsigned run_grid() const { return hu::grid_for((store.n_bases + RUN - 1) / RUN); }  // one thread per run of window starts
+    void start() {
+        ev.mark(0, st);
+        HIP_CHECK(hipMemsetAsync(d_counts, 0, words * n * 8, st));
+    }
+    void download_counts(uint64_t *valid, uint64_t *found) {
+        HIP_CHECK(hipMemcpyAsync(valid, d_counts, n * 8, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(found, d_counts + n, n * 8, hipMemcpyDeviceToHost, st));
+    }
+    void booked(double *upload_ms, double *pack_ms, double *probe_ms) {
+        *upload_ms = store.upload_ms;
+        *pack_ms = store.pack_ms;
+        *probe_ms = ev.ms(0, 1);
+    }
+};
+
+}  // namespace
+
 KmerIndex *device_kmer_index_build(const char *seq, const uint64_t *off, uint64_t n, uint64_t k, int device_id, bool locating,
                                    KmerQueryTimes *times, const KmerWeights *weights, const KmerColors *colors) {
     if (k < 1) MTG_DIE("mtg_kmer_index_build: k must be >= 1");
@@ -563,107 +624,65 @@ void device_kmer_index_free(KmerIndex *ix) {
 
 void device_kmer_index_query(const KmerIndex *ix, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid,
                              uint64_t *found, uint64_t *present_bits, uint64_t *valid_bits, KmerQueryTimes *times) {
-    const uint64_t k = ix->info.k;
-    (void)check_offsets("mtg_kmer_index_query", seq, off, n, k);
-    if (n && (!kmers || !valid || !found)) MTG_DIE("mtg_kmer_index_query: null argument");
-    const uint64_t n_bases = off[n], bit_words = (n_bases + 63) / 64;
-    if (n_bases >= POS_LIMIT) MTG_DIE("mtg_kmer_index_query: %llu bases; the limit is 2^40 - 2", (unsigned long long)n_bases);
-    for (uint64_t r = 0; r < n; r++) {
-        const uint64_t len = off[r + 1] - off[r];
-        kmers[r] = len >= k ? len - k + 1 : 0;
-        valid[r] = found[r] = 0;
-    }
+    const uint64_t n_bases = probe_windows("mtg_kmer_index_query", ix->info.k, seq, off, n, kmers, valid, found, false);
+    const uint64_t bit_words = (n_bases + 63) / 64;
     if (times) times->query_upload_ms = times->query_pack_ms = times->query_probe_ms = 0;
     if (n_bases == 0) return;  // nothing to look at
-    HIP_CHECK(hipSetDevice(ix->device_id));
-    hipStream_t st = nullptr;
-    MaskedSeqStore store(seq, off, n, st, ix->device_id);
-    unsigned long long *d_counts = nullptr, *d_bits = nullptr;  // d_bits: valid_bits, then present_bits (those asked for)
+    Probe<> p(ix, seq, off, n, 2);
+    unsigned long long *d_bits = nullptr;  // valid_bits, then present_bits (those asked for)
     const int n_arrays = (valid_bits != nullptr) + (present_bits != nullptr);
-    hu::device_malloc(&d_counts, 2 * n * 8);
     if (n_arrays) hu::device_malloc(&d_bits, n_arrays * bit_words * 8);
     unsigned long long *d_valid_bits = valid_bits ? d_bits : nullptr;
     unsigned long long *d_present_bits = present_bits ? d_bits + (valid_bits ? bit_words : 0) : nullptr;
-    PhaseEvents<2> ev;
-    ev.mark(0, st);
-    HIP_CHECK(hipMemsetAsync(d_counts, 0, 2 * n * 8, st));
-    IndexArgs a{};
-    a.packed = store.packed; a.off = store.off; a.index_packed = ix->packed; a.table = ix->table; a.slots = ix->info.slots;
-    kw::window_args_set_k(a, k);
+    p.start();
     const unsigned grid = hu::grid_for(bit_words);  // (one thread per word: every word of the bit arrays is written)
-    if (k >= 32) query_kernel<true><<<grid, hu::EB, 0, st>>>(a, store.bad, n_bases, n, d_counts, d_valid_bits, d_present_bits);
-    else query_kernel<false><<<grid, hu::EB, 0, st>>>(a, store.bad, n_bases, n, d_counts, d_valid_bits, d_present_bits);
+    if (p.wide) query_kernel<true><<<grid, hu::EB, 0, p.st>>>(p.a, p.store.bad, n_bases, n, p.d_counts, d_valid_bits, d_present_bits);
+    else query_kernel<false><<<grid, hu::EB, 0, p.st>>>(p.a, p.store.bad, n_bases, n, p.d_counts, d_valid_bits, d_present_bits);
     HIP_CHECK(hipGetLastError());
-    ev.mark(1, st);
-    HIP_CHECK(hipMemcpyAsync(valid, d_counts, n * 8, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipMemcpyAsync(found, d_counts + n, n * 8, hipMemcpyDeviceToHost, st));
-    if (valid_bits) HIP_CHECK(hipMemcpyAsync(valid_bits, d_valid_bits, bit_words * 8, hipMemcpyDeviceToHost, st));
-    if (present_bits) HIP_CHECK(hipMemcpyAsync(present_bits, d_present_bits, bit_words * 8, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    if (times) {
-        times->query_upload_ms = store.upload_ms;
-        times->query_pack_ms = store.pack_ms;
-        times->query_probe_ms = ev.ms(0, 1);
-    }
-    hu::device_free(d_counts);
+    p.ev.mark(1, p.st);
+    p.download_counts(valid, found);
+    if (valid_bits) HIP_CHECK(hipMemcpyAsync(valid_bits, d_valid_bits, bit_words * 8, hipMemcpyDeviceToHost, p.st));
+    if (present_bits) HIP_CHECK(hipMemcpyAsync(present_bits, d_present_bits, bit_words * 8, hipMemcpyDeviceToHost, p.st));
+    HIP_CHECK(hipStreamSynchronize(p.st));
+    if (times) p.booked(&times->query_upload_ms, &times->query_pack_ms, &times->query_probe_ms);  // (the build fields stay)
     hu::device_free(d_bits);
 }
 
 void device_kmer_index_abundance(const KmerIndex *ix, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid,
                                  uint64_t *found, uint64_t *sum, uint32_t *min, uint32_t *max, uint32_t *per_window, KmerAbundanceTimes *times) {
     if (!ix->weight) MTG_DIE("mtg_kmer_index_abundance: the index keeps no weights (build it with mtg_kmer_index_build_weighted)");
-    const uint64_t k = ix->info.k;
-    (void)check_offsets("mtg_kmer_index_abundance", seq, off, n, k);
-    if (n && (!kmers || !valid || !found || !sum || !min || !max)) MTG_DIE("mtg_kmer_index_abundance: null argument");
-    const uint64_t n_bases = off[n];
-    if (n_bases >= POS_LIMIT) MTG_DIE("mtg_kmer_index_abundance: %llu bases; the limit is 2^40 - 2", (unsigned long long)n_bases);
-    for (uint64_t r = 0; r < n; r++) {
-        const uint64_t len = off[r + 1] - off[r];
-        kmers[r] = len >= k ? len - k + 1 : 0;
-        valid[r] = found[r] = sum[r] = 0;
-        min[r] = max[r] = 0;
-    }
+    const uint64_t n_bases = probe_windows("mtg_kmer_index_abundance", ix->info.k, seq, off, n, kmers, valid, found, n && (!sum || !min || !max));
+    std::fill(sum, sum + n, 0ull);
+    std::fill(min, min + n, 0u);
+    std::fill(max, max + n, 0u);
     if (times) *times = KmerAbundanceTimes();
     if (n_bases == 0) return;  // nothing to look at
-    HIP_CHECK(hipSetDevice(ix->device_id));
-    hipStream_t st = nullptr;
-    MaskedSeqStore store(seq, off, n, st, ix->device_id);
-    unsigned long long *d_counts = nullptr;  // valid, found, sum
+    Probe<> p(ix, seq, off, n, 3);  // valid, found, sum
     uint32_t *d_minmax = nullptr, *d_per_window = nullptr;
-    hu::device_malloc(&d_counts, 3 * n * 8);
     hu::device_malloc(&d_minmax, 2 * n * 4);
     if (per_window) hu::device_malloc(&d_per_window, n_bases * 4);
-    PhaseEvents<2> ev;
-    ev.mark(0, st);
-    HIP_CHECK(hipMemsetAsync(d_counts, 0, 3 * n * 8, st));
-    HIP_CHECK(hipMemsetAsync(d_minmax, 0xFF, n * 4, st));
-    HIP_CHECK(hipMemsetAsync(d_minmax + n, 0, n * 4, st));
-    IndexArgs a{};
-    a.packed = store.packed; a.off = store.off; a.index_packed = ix->packed; a.table = ix->table; a.slots = ix->info.slots;
-    kw::window_args_set_k(a, k);
-    const unsigned grid = hu::grid_for((n_bases + RUN - 1) / RUN);  // (one thread per run: every word of per_window is written)
-    if (k >= 32) abundance_kernel<true><<<grid, hu::EB, 0, st>>>(a, store.bad, n_bases, n, d_counts, ix->weight, d_minmax, d_per_window);
-    else abundance_kernel<false><<<grid, hu::EB, 0, st>>>(a, store.bad, n_bases, n, d_counts, ix->weight, d_minmax, d_per_window);
+    p.start();
+    HIP_CHECK(hipMemsetAsync(d_minmax, 0xFF, n * 4, p.st));
+    HIP_CHECK(hipMemsetAsync(d_minmax + n, 0, n * 4, p.st));
+    // (one thread per run: every word of per_window is written)
+    if (p.wide) abundance_kernel<true><<<p.run_grid(), hu::EB, 0, p.st>>>(p.a, p.store.bad, n_bases, n, p.d_counts, ix->weight, d_minmax, d_per_window);
+    else abundance_kernel<false><<<p.run_grid(), hu::EB, 0, p.st>>>(p.a, p.store.bad, n_bases, n, p.d_counts, ix->weight, d_minmax, d_per_window);
     HIP_CHECK(hipGetLastError());
-    ev.mark(1, st);
-    HIP_CHECK(hipStreamSynchronize(st));
+    p.ev.mark(1, p.st);
+    HIP_CHECK(hipStreamSynchronize(p.st));
     const auto t0 = std::chrono::steady_clock::now();
-    HIP_CHECK(hipMemcpyAsync(valid, d_counts, n * 8, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipMemcpyAsync(found, d_counts + n, n * 8, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipMemcpyAsync(sum, d_counts + 2 * n, n * 8, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipMemcpyAsync(min, d_minmax, n * 4, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipMemcpyAsync(max, d_minmax + n, n * 4, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    if (per_window) hu::download_sliced(per_window, d_per_window, n_bases * 4, st, ix->device_id);
+    p.download_counts(valid, found);
+    HIP_CHECK(hipMemcpyAsync(sum, p.d_counts + 2 * n, n * 8, hipMemcpyDeviceToHost, p.st));
+    HIP_CHECK(hipMemcpyAsync(min, d_minmax, n * 4, hipMemcpyDeviceToHost, p.st));
+    HIP_CHECK(hipMemcpyAsync(max, d_minmax + n, n * 4, hipMemcpyDeviceToHost, p.st));
+    HIP_CHECK(hipStreamSynchronize(p.st));
+    if (per_window) hu::download_sliced(per_window, d_per_window, n_bases * 4, p.st, p.device_id);
     for (uint64_t r = 0; r < n; r++)
         if (!found[r]) min[r] = 0;  // (nothing lowered the all-ones word)
     if (times) {
-        times->upload_ms = store.upload_ms;
-        times->pack_ms = store.pack_ms;
-        times->probe_ms = ev.ms(0, 1);
+        p.booked(&times->upload_ms, &times->pack_ms, &times->probe_ms);
         times->download_ms = ms_since(t0);
     }
-    hu::device_free(d_counts);
     hu::device_free(d_minmax);
     hu::device_free(d_per_window);
 }
@@ -671,55 +690,36 @@ void device_kmer_index_abundance(const KmerIndex *ix, const char *seq, const uin
 void device_kmer_index_colors(const KmerIndex *ix, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid,
                               uint64_t *found, uint32_t *per_color, uint64_t *per_window, KmerColorTimes *times) {
     if (!ix->color) MTG_DIE("mtg_kmer_index_colors: the index keeps no colours (build it with mtg_kmer_index_build_annotated)");
-    const uint64_t k = ix->info.k, C = ix->n_colors;
-    (void)check_offsets("mtg_kmer_index_colors", seq, off, n, k);
-    if (n && (!kmers || !valid || !found || !per_color)) MTG_DIE("mtg_kmer_index_colors: null argument");
-    const uint64_t n_bases = off[n];
-    if (n_bases >= POS_LIMIT) MTG_DIE("mtg_kmer_index_colors: %llu bases; the limit is 2^40 - 2", (unsigned long long)n_bases);
-    for (uint64_t r = 0; r < n; r++) {
-        const uint64_t len = off[r + 1] - off[r];
-        kmers[r] = len >= k ? len - k + 1 : 0;
+    const uint64_t C = ix->n_colors;
+    const uint64_t n_bases = probe_windows("mtg_kmer_index_colors", ix->info.k, seq, off, n, kmers, valid, found, n && !per_color);
+    for (uint64_t r = 0; r < n; r++)
         if (kmers[r] >> 32) MTG_DIE("mtg_kmer_index_colors: record %llu has %llu windows; the per-colour counters are 32-bit",
                                     (unsigned long long)r, (unsigned long long)kmers[r]);
-        valid[r] = found[r] = 0;
-    }
     std::fill(per_color, per_color + n * C, 0u);
     if (times) times->upload_ms = times->pack_ms = times->probe_ms = times->download_ms = 0;
     if (n_bases == 0) return;  // nothing to look at
-    HIP_CHECK(hipSetDevice(ix->device_id));
-    hipStream_t st = nullptr;
-    MaskedSeqStore store(seq, off, n, st, ix->device_id);
-    unsigned long long *d_counts = nullptr, *d_per_window = nullptr;  // d_counts: valid, found
+    Probe<> p(ix, seq, off, n, 2);
+    unsigned long long *d_per_window = nullptr;
     uint32_t *d_per_color = nullptr;
-    hu::device_malloc(&d_counts, 2 * n * 8);
     hu::device_malloc(&d_per_color, n * C * 4);
     if (per_window) hu::device_malloc(&d_per_window, n_bases * 8);
-    PhaseEvents<2> ev;
-    ev.mark(0, st);
-    HIP_CHECK(hipMemsetAsync(d_counts, 0, 2 * n * 8, st));
-    HIP_CHECK(hipMemsetAsync(d_per_color, 0, n * C * 4, st));
-    IndexArgs a{};
-    a.packed = store.packed; a.off = store.off; a.index_packed = ix->packed; a.table = ix->table; a.slots = ix->info.slots;
-    kw::window_args_set_k(a, k);
-    const unsigned grid = hu::grid_for((n_bases + RUN - 1) / RUN);  // (one thread per run: every word of per_window is written)
-    if (k >= 32) color_query_kernel<true><<<grid, hu::EB, 0, st>>>(a, store.bad, n_bases, n, d_counts, ix->color, (uint32_t)C, d_per_color, d_per_window);
-    else color_query_kernel<false><<<grid, hu::EB, 0, st>>>(a, store.bad, n_bases, n, d_counts, ix->color, (uint32_t)C, d_per_color, d_per_window);
+    p.start();
+    HIP_CHECK(hipMemsetAsync(d_per_color, 0, n * C * 4, p.st));
+    // (one thread per run: every word of per_window is written)
+    if (p.wide) color_query_kernel<true><<<p.run_grid(), hu::EB, 0, p.st>>>(p.a, p.store.bad, n_bases, n, p.d_counts, ix->color, (uint32_t)C, d_per_color, d_per_window);
+    else color_query_kernel<false><<<p.run_grid(), hu::EB, 0, p.st>>>(p.a, p.store.bad, n_bases, n, p.d_counts, ix->color, (uint32_t)C, d_per_color, d_per_window);
     HIP_CHECK(hipGetLastError());
-    ev.mark(1, st);
-    HIP_CHECK(hipStreamSynchronize(st));
+    p.ev.mark(1, p.st);
+    HIP_CHECK(hipStreamSynchronize(p.st));
     const auto t0 = std::chrono::steady_clock::now();
-    HIP_CHECK(hipMemcpyAsync(valid, d_counts, n * 8, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipMemcpyAsync(found, d_counts + n, n * 8, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    hu::download_sliced(per_color, d_per_color, n * C * 4, st, ix->device_id);
-    if (per_window) hu::download_sliced(per_window, d_per_window, n_bases * 8, st, ix->device_id);
+    p.download_counts(valid, found);
+    HIP_CHECK(hipStreamSynchronize(p.st));
+    hu::download_sliced(per_color, d_per_color, n * C * 4, p.st, p.device_id);
+    if (per_window) hu::download_sliced(per_window, d_per_window, n_bases * 8, p.st, p.device_id);
     if (times) {
-        times->upload_ms = store.upload_ms;
-        times->pack_ms = store.pack_ms;
-        times->probe_ms = ev.ms(0, 1);
+        p.booked(&times->upload_ms, &times->pack_ms, &times->probe_ms);
         times->download_ms = ms_since(t0);
     }
-    hu::device_free(d_counts);
     hu::device_free(d_per_color);
     hu::device_free(d_per_window);
 }
@@ -728,42 +728,26 @@ void device_kmer_index_locate(const KmerIndex *ix, const char *seq, const uint64
                               uint64_t *found, KmerRuns *runs, KmerLocateTimes *times) {
     if (!ix->locating) MTG_DIE("mtg_kmer_index_locate: the index keeps no positions (build it with mtg_kmer_index_build_locating)");
     const uint64_t k = ix->info.k;
-    (void)check_offsets("mtg_kmer_index_locate", seq, off, n, k);
-    if (!runs || (n && (!kmers || !valid || !found))) MTG_DIE("mtg_kmer_index_locate: null argument");
-    const uint64_t n_bases = off[n];
-    if (n_bases >= POS_LIMIT) MTG_DIE("mtg_kmer_index_locate: %llu bases; the limit is 2^40 - 2", (unsigned long long)n_bases);
-    for (uint64_t r = 0; r < n; r++) {
-        const uint64_t len = off[r + 1] - off[r];
-        kmers[r] = len >= k ? len - k + 1 : 0;
-        valid[r] = found[r] = 0;
-    }
+    const uint64_t n_bases = probe_windows("mtg_kmer_index_locate", k, seq, off, n, kmers, valid, found, !runs);
     *runs = KmerRuns();
     if (times) *times = KmerLocateTimes();
     if (n_bases == 0) return;  // nothing to look at
-    HIP_CHECK(hipSetDevice(ix->device_id));
-    hipStream_t st = nullptr;
-    MaskedSeqStore store(seq, off, n, st, ix->device_id);
-    unsigned long long *d_counts = nullptr, *d_hit = nullptr, *d_rank = nullptr, *d_sums = nullptr;  // d_sums: the scan's block sums, then its total
+    Probe<3> p(ix, seq, off, n, 2);
+    hipStream_t st = p.st;
+    unsigned long long *d_hit = nullptr, *d_rank = nullptr, *d_sums = nullptr;  // d_sums: the scan's block sums, then its total
     uint32_t *d_starts = nullptr;
     const uint64_t n_sums = hu::scan_blocks(n_bases) + 1;
-    hu::device_malloc(&d_counts, 2 * n * 8);
     hu::device_malloc(&d_hit, n_bases * 8);
     hu::device_malloc(&d_starts, n_bases * 4);
     hu::device_malloc(&d_rank, n_bases * 8);
     hu::device_malloc(&d_sums, (n_sums + 1) * 8);
-    PhaseEvents<3> ev;
-    ev.mark(0, st);
-    HIP_CHECK(hipMemsetAsync(d_counts, 0, 2 * n * 8, st));
+    p.start();
     HIP_CHECK(hipMemsetAsync(d_hit, 0xFF, n_bases * 8, st));
-    IndexArgs a{};
-    a.packed = store.packed; a.off = store.off; a.index_packed = ix->packed; a.table = ix->table; a.slots = ix->info.slots;
-    kw::window_args_set_k(a, k);
-    const unsigned grid = hu::grid_for((n_bases + RUN - 1) / RUN);
-    if (k >= 32) locate_kernel<true><<<grid, hu::EB, 0, st>>>(a, store.bad, n_bases, n, d_counts, ix->where, d_hit);
-    else locate_kernel<false><<<grid, hu::EB, 0, st>>>(a, store.bad, n_bases, n, d_counts, ix->where, d_hit);
+    if (p.wide) locate_kernel<true><<<p.run_grid(), hu::EB, 0, st>>>(p.a, p.store.bad, n_bases, n, p.d_counts, ix->where, d_hit);
+    else locate_kernel<false><<<p.run_grid(), hu::EB, 0, st>>>(p.a, p.store.bad, n_bases, n, p.d_counts, ix->where, d_hit);
     HIP_CHECK(hipGetLastError());
-    ev.mark(1, st);
-    RunArgs ra{d_hit, store.off, ix->off, n_bases, n, ix->info.records, k};
+    p.ev.mark(1, st);
+    RunArgs ra{d_hit, p.store.off, ix->off, n_bases, n, ix->info.records, k};
     const unsigned base_grid = hu::grid_for(n_bases);
     run_flag_kernel<<<base_grid, hu::EB, 0, st>>>(ra, d_starts);
     HIP_CHECK(hipGetLastError());
@@ -780,32 +764,23 @@ void device_kmer_index_locate(const KmerIndex *ix, const char *seq, const uint64
         run_emit_kernel<<<hu::grid_for(n_runs), hu::EB, 0, st>>>(ra, n_runs, d_ends, d_ends + n_runs, d_out, d_strand);
         HIP_CHECK(hipGetLastError());
     }
-    ev.mark(2, st);
-    HIP_CHECK(hipMemcpyAsync(valid, d_counts, n * 8, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipMemcpyAsync(found, d_counts + n, n * 8, hipMemcpyDeviceToHost, st));
+    p.ev.mark(2, st);
+    p.download_counts(valid, found);
     HIP_CHECK(hipStreamSynchronize(st));
     if (n_runs) {
         std::vector<uint64_t> *fields[5] = {&runs->q_record, &runs->q_start, &runs->kmers, &runs->t_record, &runs->t_start};
         for (int f = 0; f < 5; f++) {
             fields[f]->resize(n_runs);
-            hu::download_sliced(fields[f]->data(), d_out + f * n_runs, n_runs * 8, st, ix->device_id);
+            hu::download_sliced(fields[f]->data(), d_out + f * n_runs, n_runs * 8, st, p.device_id);
         }
         runs->strand.resize(n_runs);
-        hu::download_sliced(runs->strand.data(), d_out + 5 * n_runs, n_runs, st, ix->device_id);
+        hu::download_sliced(runs->strand.data(), d_out + 5 * n_runs, n_runs, st, p.device_id);
     }
     if (times) {
-        times->upload_ms = store.upload_ms;
-        times->pack_ms = store.pack_ms;
-        times->probe_ms = ev.ms(0, 1);
-        times->runs_ms = ev.ms(1, 2);
+        p.booked(&times->upload_ms, &times->pack_ms, &times->probe_ms);
+        times->runs_ms = p.ev.ms(1, 2);
     }
-    hu::device_free(d_counts);
-    hu::device_free(d_hit);
-    hu::device_free(d_starts);
-    hu::device_free(d_rank);
-    hu::device_free(d_sums);
-    hu::device_free(d_ends);
-    hu::device_free(d_out);
+    for (const void *d : std::initializer_list<const void *>{d_hit, d_starts, d_rank, d_sums, d_ends, d_out}) hu::device_free(d);
 }
 
 }  // namespace mtg

@@ -1,7 +1,7 @@
 """The unitig compaction on the GPU (`--seq-in`, mtg_compact_unitigs): bytes, offsets and statistics of the device
 against the restatement of the contract (compact_ref.py) on random haplotypes for narrow and wide k and on the special shapes; a
 long unitig (the pointer jumping must not walk); invariance under record order and strand; determinism; the product path through
-the CLI; and the graph at size against the tree's torch compaction."""
+the CLI; the graph at size against the tree's torch compaction; and every rung of the ladder over every input form giving one answer."""
 import subprocess
 import sys
 from pathlib import Path
@@ -213,3 +213,53 @@ def test_at_size(product_lib):
     print(f"torch compaction: {ua.n_unitigs} unitigs, {int(ua.off[-1])} characters")
     assert (c.unitigs, c.unitig_characters) == (ua.n_unitigs, int(ua.off[-1]))
     assert len(ua.kmers) == c.distinct_kmers
+
+
+@pytest.mark.parametrize("k", [4, 31, 32, 33, 34])
+def test_every_rung_and_input_form_give_one_answer(product_lib, tmp_path, k):
+    """compact_unitigs, _counted (without and with kmer_counts), _colored and _colored_classes(split=False), each over a list of str,
+    (array, offsets) and a UnitigStore, are one computation at min_abundance = 1: the same store and Compaction fifteen times -- the
+    restatement's --, the same Abundance, counts, masks and classes wherever a rung returns them."""
+    import dataclasses
+
+    from matchtigs_amd import api
+
+    a, b, c = ("".join("ACGT"[x] for x in np.random.default_rng(10 * k + i).integers(0, 4, n)) for i, n in enumerate((100, 230, 300)))
+    seqs = [a, b, "ACG", a, c[:150] + b[40:140]]  # a repeated: abundances differ; "ACG" is shorter than every k
+    colors = [i % 3 for i in range(len(seqs))]
+    (tmp_path / "in.fa").write_text("".join(f">r{i}\n{s}\n" for i, s in enumerate(seqs)))
+    as_store = api.read_sequences(str(tmp_path / "in.fa"))
+    assert as_store.sequences() == seqs
+    forms = (seqs, (np.frombuffer("".join(seqs).encode(), np.uint8), np.cumsum([0] + [len(s) for s in seqs]).astype(np.uint64)), as_store)
+    rungs = (lambda x: api.compact_unitigs(x, k),
+             lambda x: api.compact_unitigs_counted(x, k, 1),
+             lambda x: api.compact_unitigs_counted(x, k, 1, kmer_counts=True),
+             lambda x: api.compact_unitigs_colored(x, k, colors, 3),
+             lambda x: api.compact_unitigs_colored_classes(x, k, colors, 3, split=False))
+    results = [rung(form) for rung in rungs for form in forms]
+    assert len(results) == 15
+
+    unitigs, stats, _ = R.compact(seqs, k)
+    assert results[0][0].sequences() == unitigs and dataclasses.asdict(results[0][1]) == stats
+    for r in results:
+        assert r[0].sequences() == unitigs and r[1] == results[0][1]
+    counted = [r[2] for r in results if len(r) >= 3]
+    assert len(counted) == 12 and counted[0].distinct_kept == stats["distinct_kmers"] and counted[0].max_abundance >= 2
+    for ab in counted:
+        assert (ab.distinct_all, ab.distinct_kept, ab.max_abundance, ab.kept_occurrences) == (
+            counted[0].distinct_all, counted[0].distinct_kept, counted[0].max_abundance, counted[0].kept_occurrences)
+        assert np.array_equal(ab.spectrum, counted[0].spectrum) and np.array_equal(ab.unitig_sums, counted[0].unitig_sums)
+    assert all(ab.kmer_counts is None for ab in counted[:3])
+    per_kmer = [ab.kmer_counts for ab in counted[3:]]
+    assert len(per_kmer[0]) == stats["distinct_kmers"] and all(np.array_equal(x, per_kmer[0]) for x in per_kmer)
+    colored = [r[3] for r in results if len(r) >= 4]
+    assert len(colored) == 6 and len(colored[0].kmer_colors) == stats["distinct_kmers"]
+    for col in colored:
+        assert col.n_colors == 3 and np.array_equal(col.kmer_colors, colored[0].kmer_colors)
+        assert np.array_equal(col.per_color, colored[0].per_color) and np.array_equal(col.shared, colored[0].shared)
+        assert np.array_equal(col.occupancy, colored[0].occupancy)
+    classed = [r for r in results if len(r) == 5]
+    assert len(classed) == 3
+    for r in classed:
+        assert np.array_equal(r[4].masks[r[4].kmer_class], r[3].kmer_colors)
+        assert all(np.array_equal(getattr(r[4], f), getattr(classed[0][4], f)) for f in ("masks", "kmers", "runs", "first", "kmer_class"))
