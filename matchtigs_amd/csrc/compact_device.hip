@@ -25,7 +25,7 @@
 //   rank      pointer jumping over (jump, rank) pairs held in one 64-bit word, updated in place: a pair always says "jump is the
 //             rank-th predecessor", so any interleaving of the threads keeps it true, and the final state (jump = the walk's head,
 //             rank = the distance from it) is unique. A round at least doubles every open distance: ceil(log2(longest walk)) + 1
-//             rounds. What still moves after ceil(log2(2 N)) + 1 rounds lies on a closed walk; those elements are listed, the
+//             rounds. What still moves after ceil(log2(2 N)) + 2 rounds lies on a closed walk; those elements are listed, the
 //             minimum oriented id of each cycle is found by doubling windows (ping-pong buffers), the cycle is cut in front of that
 //             element and ranked like a chain. No kernel walks a chain sequentially.
 //   emit      per walk the minimum oriented id (atomicMin at the head, one per wave where a wave lies on one walk) and the length
