@@ -739,6 +739,46 @@ void mtg_color_classes_free(mtg_color_classes *classes);
 void mtg_last_color_class_times(double out[5]);
 /* {the classes the counts kernel keeps in LDS, its largest grid, its block}: what an input must exceed to reach the kernel's other paths. */
 void mtg_color_class_limits(uint64_t out[3]);
+/* TIP CLIPPING and ISOLATED UNITIGS. mtg_compact_unitigs_cleaned is mtg_compact_unitigs_colored_classes over a k-mer set
+ * T that starts as S_m and shrinks in rounds. With the oriented edges of G(T), an OPEN walk W = e_1 .. e_n of the contract over T
+ * has two ends: its head node (the suffix of e_n) and the head node of its mirror walk (the reverse complement of the prefix of
+ * e_1). For an end with head node v: beyond = |out(v)|, beside = |into(v)| - 1; at a self-mirror node beyond = beside = |out(v)| - 1
+ * (our own mirror leaves v). The end is FREE iff beyond = beside = 0, ANCHORED iff beside >= 1, THROUGH otherwise. W is a TIP iff
+ * n < tip_kmers, one end is free and the other anchored; ISOLATED iff n < isolated_kmers and both ends are free. Closed walks are
+ * never removed. A ROUND decides all walks of T on one snapshot and removes the k-mers of every tip and isolated walk; rounds repeat
+ * on the unitigs of the new T until one removes nothing or `rounds` have run. The result is the contract of the lower rungs over the
+ * final T -- creators, readings, abundances and masks still taken over ALL windows. With split = 1 the decisions are taken on the
+ * unsplit unitigs of T; only the final pass splits.
+ * *stats, *sums, *kmer_counts, *kmer_colors, *color_stats and *classes describe the final store; *abundance keeps its meaning
+ * (distinct_kept = |S_m|, kept_occurrences over S_m), so the sum of *sums is kept_occurrences - removed_occurrences.
+ * Null out-pointers select a lower rung: classes (then split must be 0); kmer_colors and color_stats (then record_colors is not read);
+ * kmer_counts; abundance and sums (then min_abundance must be 1 and removed_occurrences is 0). params == NULL or cleaning == NULL, or
+ * both lengths 0, cleans nothing: the call then runs the kernels of the rung it selects and returns that rung's bytes. rounds outside
+ * 1 .. 64 aborts. Exact integers that depend on the input and the parameters alone. */
+typedef struct mtg_cleaning_params {
+    uint64_t tip_kmers;      /* a tip has fewer k-mers than this; 0 = no tip clipping */
+    uint64_t isolated_kmers; /* an isolated unitig has fewer k-mers than this; 0 = keep them */
+    uint64_t rounds;         /* 1 .. 64 */
+} mtg_cleaning_params;
+typedef struct mtg_cleaning {
+    uint64_t rounds_run;           /* the decision rounds that ran, the one that removed nothing included */
+    uint64_t tips, tip_kmers;      /* walks removed as tips over all rounds, and their k-mers */
+    uint64_t isolated, isolated_kmers;
+    uint64_t removed_occurrences;  /* the sum of the removed k-mers' abundances */
+} mtg_cleaning;
+void mtg_compact_unitigs_cleaned(const char *data, const uint64_t *offsets, uint64_t n, uint64_t k, uint64_t min_abundance,
+                                 const uint8_t *record_colors, uint64_t n_colors, int split, const mtg_cleaning_params *params, int device_id,
+                                 mtg_unitigs **out, mtg_compaction *stats, mtg_abundance *abundance, mtg_abundance_sums **sums,
+                                 mtg_kmer_counts **kmer_counts, mtg_kmer_colors **kmer_colors, mtg_color_stats *color_stats,
+                                 mtg_color_classes **classes, mtg_cleaning *cleaning);
+void mtg_compact_unitigs_cleaned_store(const mtg_unitigs *in, uint64_t k, uint64_t min_abundance, const uint8_t *record_colors,
+                                       uint64_t n_colors, int split, const mtg_cleaning_params *params, int device_id, mtg_unitigs **out,
+                                       mtg_compaction *stats, mtg_abundance *abundance, mtg_abundance_sums **sums,
+                                       mtg_kmer_counts **kmer_counts, mtg_kmer_colors **kmer_colors, mtg_color_stats *color_stats,
+                                       mtg_color_classes **classes, mtg_cleaning *cleaning);
+/* Of the last compaction on this thread: {ms of the decision and removal kernels over all rounds (HIP events), the rounds run}.
+ * mtg_last_compact_times' nodes and rank phases include every round's. */
+void mtg_last_clean_times(double out[2]);
 /* mtg_read_sequences without an alphabet rule: every byte of a sequence line is kept as it is (`N`, IUPAC codes, lower case), for
  * the queries of a k-mer index. *names_out = the record names as a second store with the same accessors: the header text behind `>`
  * up to the first white space. */

@@ -33,6 +33,10 @@ shares, `--unitig-colors-out` the colours along every unitig as runs `count:hexm
 `--monochromatic-unitigs` cuts the unitigs wherever the set of files changes, so that every k-mer of a unitig is carried by the same
 files; `--color-classes-out` writes the distinct sets of files (the colour classes, numbered in the order the unitigs show them) with
 their k-mers and runs, and `--unitig-color-classes-out` the classes along every unitig as runs `count:class`.
+`--clip-tips L` (with `--seq-in`; not in the reference) removes the tips -- dead-end unitigs of fewer than L k-mers that hang off a fork,
+what a sequencing error near a read end leaves behind even above `--min-abundance` -- and `--remove-isolated L` the unitigs of fewer
+than L k-mers that touch nothing, both inside the GPU compaction and before the unitigs are formed for good; `--clean-rounds R`
+repeats that up to R times on the unitigs the round before left. Every output sees the cleaned unitigs.
 """
 from __future__ import annotations
 
@@ -126,6 +130,13 @@ def main(argv=None) -> int:
     ap.add_argument("--unitig-color-classes-out", metavar="PATH",
                     help="with --seq-in: per record of --unitigs-fa-out a line of runs count:class over its k-mers, left to right; the "
                          "classes are those of --color-classes-out (.gz => gzip)")
+    ap.add_argument("--clip-tips", type=int, metavar="L",
+                    help="with --seq-in: remove the dead-end unitigs of fewer than L k-mers that hang off a fork (L >= 2; the "
+                         "conventional value is k; not in the reference)")
+    ap.add_argument("--remove-isolated", type=int, metavar="L",
+                    help="with --seq-in: remove the unitigs of fewer than L k-mers with two dead ends (L >= 1)")
+    ap.add_argument("--clean-rounds", type=int, metavar="R",
+                    help="with --clip-tips / --remove-isolated: at most R rounds (1..64, default 1), each on the unitigs the one before left")
     args = ap.parse_args(argv)
 
     classed = bool(args.monochromatic_unitigs or args.color_classes_out or args.unitig_color_classes_out)
@@ -163,9 +174,18 @@ def main(argv=None) -> int:
                         ("--unitig-abundance-out", args.unitig_abundance_out), ("--unitig-kmer-abundance-out", args.unitig_kmer_abundance_out),
                         ("--color-matrix-out", args.color_matrix_out), ("--unitig-colors-out", args.unitig_colors_out),
                         ("--monochromatic-unitigs", args.monochromatic_unitigs or None), ("--color-classes-out", args.color_classes_out),
-                        ("--unitig-color-classes-out", args.unitig_color_classes_out)):
+                        ("--unitig-color-classes-out", args.unitig_color_classes_out), ("--clip-tips", args.clip_tips),
+                        ("--remove-isolated", args.remove_isolated), ("--clean-rounds", args.clean_rounds)):
         if value is not None and args.seq_in is None:
             ap.error(f"{flag} needs --seq-in")
+    if args.clip_tips is not None and args.clip_tips < 2:
+        ap.error("--clip-tips must be >= 2")
+    if args.remove_isolated is not None and args.remove_isolated < 1:
+        ap.error("--remove-isolated must be >= 1")
+    if args.clean_rounds is not None and args.clip_tips is None and args.remove_isolated is None:
+        ap.error("--clean-rounds needs --clip-tips or --remove-isolated")
+    if args.clean_rounds is not None and not 1 <= args.clean_rounds <= 64:
+        ap.error("--clean-rounds must be in 1..64")
     if args.min_abundance is not None and args.min_abundance < 1:
         ap.error("--min-abundance must be >= 1")
     for flag, value in (("--min-base-quality", args.min_base_quality), ("--query-min-base-quality", args.query_min_base_quality)):
@@ -217,6 +237,7 @@ def _read_seq_in(api, args, fastq, record_colors=None):
 
 def _run(api, args, fastq) -> int:
     t0 = time.perf_counter()
+    cleaning = None
     if args.bcalm_in is not None:
         graph, store = api.read_bcalm2(args.bcalm_in, args.k)
     elif args.seq_in is not None:  # sequences -> unitigs (GPU compaction) -> graph (the --fa-in join on the same store)
@@ -224,14 +245,19 @@ def _run(api, args, fastq) -> int:
         colored = bool(args.color_matrix_out or args.unitig_colors_out or args.query_colors_out or classed)  # 
         record_colors = [] if colored else None
         seqs, pieces_cut = _read_seq_in(api, args, fastq, record_colors)
-        abundance = colors = None
+        abundance = colors = cleaning = None
+        cleaned = args.clip_tips is not None or args.remove_isolated is not None  # 
         per_kmer = bool(args.query_abundance_out or args.unitig_kmer_abundance_out)  # 
         counted = not (args.min_abundance is None and not (args.kmer_spectrum_out or args.unitig_abundance_out or per_kmer))
-        if not counted and not colored:
+        if not counted and not colored and not cleaned:
             store, compaction = api.compact_unitigs(seqs, args.k, args.device)
         else:  # the counted compaction; an output flag alone counts without filtering
             min_abundance = args.min_abundance or 1
-            if classed:  # (the coloured call plus the class dictionary, over unitigs cut at the colour changes if asked for)
+            if cleaned:  # (whichever of the calls below it would have been, with the rounds in front of the final pass)
+                store, compaction, abundance, colors, classes, cleaning = api.compact_unitigs_cleaned(
+                    seqs, args.k, args.clip_tips or 0, args.remove_isolated or 0, args.clean_rounds or 1, min_abundance,
+                    record_colors if colored else None, len(args.seq_in) if colored else 0, bool(args.monochromatic_unitigs), per_kmer, args.device)
+            elif classed:  # (the coloured call plus the class dictionary, over unitigs cut at the colour changes if asked for)
                 store, compaction, abundance, colors, classes = api.compact_unitigs_colored_classes(
                     seqs, args.k, record_colors, len(args.seq_in), min_abundance, args.monochromatic_unitigs, args.device)
             elif colored:  # (the counted call that hands out the counts, plus the colours)
@@ -245,6 +271,9 @@ def _run(api, args, fastq) -> int:
                 _write_spectrum(args, abundance)
             if abundance.distinct_kept == 0:
                 print(f"no k-mer reaches --min-abundance {min_abundance} ({abundance.describe()})", file=sys.stderr)
+                return 1
+            if len(store) == 0:
+                print(f"nothing is left after cleaning ({cleaning.describe()}; {abundance.describe()})", file=sys.stderr)
                 return 1
             if args.unitig_abundance_out:
                 _write_unitig_abundance(args, store, abundance)
@@ -268,13 +297,15 @@ def _run(api, args, fastq) -> int:
         loaded += f" (compacted from {compaction.describe()}; "
         loaded += f"cut into {compaction.unitigs} monochromatic unitigs; " if args.monochromatic_unitigs else ""
         loaded += f"{abundance.describe()}; " if abundance is not None and counted else ""
+        loaded += f"{cleaning.describe()}; " if cleaning is not None else ""
         loaded += f"{pieces_cut} non-ACGT runs cut)"
     print(loaded, file=sys.stderr)
     # what the tigs are verified against: the input as given -- on the --seq-in route the sequences, so that the check covers the compaction
     truth = seqs if args.seq_in is not None else store
     filtered = args.seq_in is not None and abundance is not None and min_abundance > 1
-    if filtered:  # the tigs spell S_m, not the input's set: they are held to the unitigs, and the unitigs to the input (below)
-        truth = store
+    if filtered or cleaning is not None:  # the tigs spell S_m less what the cleaning took, not the input's set: they are held to the
+        truth = store                     # unitigs, and the unitigs to the input (below)
+    cleaned_away = cleaning.removed_kmers if cleaning is not None else 0
 
     def report(what: str, tigs, cmp) -> bool:
         """The verification line of one tig set; names the first missing and the first foreign k-mer when there is one."""
@@ -289,13 +320,19 @@ def _run(api, args, fastq) -> int:
         return cmp.equal
 
     all_equal = True
-    if filtered and (args.verify or args.verify_fa):
-        # by the k-mer set comparison, a kernel the compaction does not share: no foreign k-mer survived, and exactly the dropped are gone
+    if (filtered or cleaning is not None) and (args.verify or args.verify_fa):
+        # by the k-mer set comparison, a kernel the compaction does not share: no foreign k-mer survived, and exactly the dropped and
+        # the cleaned are gone
         cmp = api.compare_kmer_sets(seqs, store, args.k, args.device)
-        ok = cmp.only_in_b == 0 and cmp.only_in_a == abundance.dropped
-        print(f"Verifying abundance filter: {cmp.distinct_b} of the input's {cmp.distinct_a} distinct k-mers are in the unitigs, "
-              f"{cmp.only_in_a} are not ({abundance.dropped} dropped by the filter), {cmp.only_in_b} foreign: "
-              f"{'as counted' if ok else 'MISMATCH'}", file=sys.stderr)
+        ok = cmp.only_in_b == 0 and cmp.only_in_a == abundance.dropped + cleaned_away
+        if filtered:
+            print(f"Verifying abundance filter: {cmp.distinct_b} of the input's {cmp.distinct_a} distinct k-mers are in the unitigs, "
+                  f"{cmp.only_in_a - cleaned_away} are not ({abundance.dropped} dropped by the filter), {cmp.only_in_b} foreign: "
+                  f"{'as counted' if ok else 'MISMATCH'}", file=sys.stderr)
+        if cleaning is not None:
+            print(f"Verifying cleaning: {cmp.distinct_b} of the input's {cmp.distinct_a} distinct k-mers are in the unitigs, "
+                  f"{cmp.only_in_a} are not ({abundance.dropped} dropped by the filter, {cleaning.tip_kmers} in tips, "
+                  f"{cleaning.isolated_kmers} in isolated unitigs), {cmp.only_in_b} foreign: {'as counted' if ok else 'MISMATCH'}", file=sys.stderr)
         all_equal &= ok
     for path in args.verify_fa or ():
         tigs = api.read_sequences(path)

@@ -103,6 +103,21 @@ class MtgAbundance(C.Structure):
         ("spectrum", C.c_uint64 * 256)]
 
 
+class MtgCleaningParams(C.Structure):
+    """mtg_cleaning_params (include/mtg_engine.h)."""
+
+    _fields_ = [(n, C.c_uint64) for n in ("tip_kmers", "isolated_kmers", "rounds")]
+
+
+class MtgCleaning(C.Structure):
+    """mtg_cleaning (include/mtg_engine.h)."""
+
+    _fields_ = [(n, C.c_uint64) for n in ("rounds_run", "tips", "tip_kmers", "isolated", "isolated_kmers", "removed_occurrences")]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class MtgColorStats(C.Structure):
     """mtg_color_stats (include/mtg_engine.h)."""
 
@@ -305,6 +320,11 @@ def load():
                                                        P(vp), P(vp), P(vp), P(MtgColorStats), P(vp)]),
         "mtg_compact_unitigs_colored_classes_store": (None, [vp, u64, u64, vp, u64, C.c_int, C.c_int, P(vp), P(MtgCompaction), P(MtgAbundance),
                                                              P(vp), P(vp), P(vp), P(MtgColorStats), P(vp)]),
+        "mtg_compact_unitigs_cleaned": (None, [vp, vp, u64, u64, u64, vp, u64, C.c_int, P(MtgCleaningParams), C.c_int, P(vp), P(MtgCompaction),
+                                               P(MtgAbundance), P(vp), P(vp), P(vp), P(MtgColorStats), P(vp), P(MtgCleaning)]),
+        "mtg_compact_unitigs_cleaned_store": (None, [vp, u64, u64, vp, u64, C.c_int, P(MtgCleaningParams), C.c_int, P(vp), P(MtgCompaction),
+                                                     P(MtgAbundance), P(vp), P(vp), P(vp), P(MtgColorStats), P(vp), P(MtgCleaning)]),
+        "mtg_last_clean_times": (None, [P(C.c_double)]),
         "mtg_color_classes_build": (None, [vp, u64, vp, u64, C.c_int, P(vp)]),
         "mtg_color_classes_count": (u64, [vp]),
         "mtg_color_classes_masks": (vp, [vp]),

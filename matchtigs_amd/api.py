@@ -1083,7 +1083,69 @@ def compact_unitigs_colored_classes(seqs_or_store, k: int, record_colors, n_colo
     if not isinstance(split, (bool, np.bool_)):
         raise ValueError(f"split must be True or False, not {split!r}")
     rc = _record_colors(record_colors, n_colors, _record_count(seqs_or_store))
-    return _compact(_CLASSES, seqs_or_store, k, device_id, min_abundance, rc, int(n_colors), split)
+    return _compact(_CLASSES, seqs_or_store, k, device_id, min_abundance, rc, int(n_colors), split)[:5]
+
+
+@dataclass(frozen=True)
+class Cleaning:
+    """mtg_cleaning (include/mtg_engine.h): what the rounds of a cleaned compaction removed, in exact integers. A tip is
+    an open unitig of fewer than clip_tips k-mers with one free end and one end that shares its side of a fork; an isolated unitig
+    has fewer than remove_isolated k-mers and two free ends. rounds_run counts the round that removed nothing too."""
+
+    rounds_run: int
+    tips: int
+    tip_kmers: int
+    isolated: int
+    isolated_kmers: int
+    removed_occurrences: int
+
+    @property
+    def removed_kmers(self) -> int:
+        return self.tip_kmers + self.isolated_kmers
+
+    def describe(self) -> str:
+        return (f"{self.tips} tips of {self.tip_kmers} k-mers and {self.isolated} isolated unitigs of {self.isolated_kmers} k-mers "
+                f"removed in {self.rounds_run} rounds")
+
+
+MAX_CLEAN_ROUNDS = 64
+
+
+def compact_unitigs_cleaned(seqs_or_store, k: int, clip_tips: int = 0, remove_isolated: int = 0, rounds: int = 1, min_abundance: int = 1,
+                            record_colors=None, n_colors: int = 0, split: bool = False, kmer_counts: bool = False, device_id: int = 0):
+    """The counted, coloured or classed compaction with tips clipped and isolated unitigs dropped before the final pass
+    (mtg_compact_unitigs_cleaned) -> (UnitigStore, Compaction, Abundance, Colors | None, ColorClasses | None, Cleaning).
+    clip_tips = L removes the open unitigs of fewer than L k-mers that dead-end on one side and share their side of a fork on the other
+    (0: off; the conventional value is k); remove_isolated = L those with two dead ends; at most `rounds` rounds, each on the unitigs
+    the one before left. record_colors / n_colors as for compact_unitigs_colored_classes (None: no colours, the fourth and fifth
+    entries are None); split needs colours and is decided on the unsplit unitigs. Compaction, unitig_sums, kmer_counts, kmer_colors
+    and the classes describe the final store; Abundance's scalars keep their meaning (distinct_kept = the k-mers that reach
+    min_abundance), so unitig_sums.sum() == kept_occurrences - Cleaning.removed_occurrences. With both lengths 0 the result is the
+    uncleaned call's."""
+    for name, v, lo, hi in (("clip_tips", clip_tips, 0, 2 ** 64 - 1), ("remove_isolated", remove_isolated, 0, 2 ** 64 - 1),
+                            ("rounds", rounds, 1, MAX_CLEAN_ROUNDS)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+            raise ValueError(f"{name} must be an integer in {lo}..{hi}, not {v!r}")
+    if min_abundance < 1:
+        raise ValueError("min_abundance must be >= 1")
+    if not isinstance(split, (bool, np.bool_)):
+        raise ValueError(f"split must be True or False, not {split!r}")
+    if record_colors is None:
+        if split:
+            raise ValueError("split needs record_colors")
+        return _compact(_COUNTED_KMERS if kmer_counts else _COUNTED, seqs_or_store, k, device_id, min_abundance,
+                        cleaning=(int(clip_tips), int(remove_isolated), int(rounds)))
+    rc = _record_colors(record_colors, n_colors, _record_count(seqs_or_store))
+    return _compact(_CLASSES, seqs_or_store, k, device_id, min_abundance, rc, int(n_colors), split,
+                    cleaning=(int(clip_tips), int(remove_isolated), int(rounds)))
+
+
+def last_clean_times() -> dict:
+    """Of the last compaction on this thread: the ms of the decision and removal kernels over all rounds (HIP events) and the rounds
+    run. last_compact_times' nodes_ms and rank_ms include every round's."""
+    out = (C.c_double * 2)()
+    _lib.load().mtg_last_clean_times(out)
+    return {"clean_ms": float(out[0]), "rounds_run": int(out[1])}
 
 
 # The rungs of the compaction ladder and the C symbol each reaches (+ "_store" for a UnitigStore). The argument list of a rung is
@@ -1094,30 +1156,40 @@ _COMPACT_SYMBOLS = ("mtg_compact_unitigs", "mtg_compact_unitigs_counted", "mtg_c
 
 
 def _compact(rung: int, seqs_or_store, k: int, device_id: int, min_abundance: int = 1, record_colors=None, n_colors: int = 0,
-             split: bool = False):
-    """The one body of compact_unitigs* -> (UnitigStore, Compaction, Abundance, Colors, ColorClasses), None above the rung. The
-    arguments are the callers' to check."""
+             split: bool = False, cleaning=None):
+    """The one body of compact_unitigs* -> (UnitigStore, Compaction, Abundance, Colors, ColorClasses, Cleaning), None above the rung.
+    cleaning: None, or (clip_tips, remove_isolated, rounds) -- the call then goes through mtg_compact_unitigs_cleaned, which takes
+    the arguments of every rung and null out-pointers above the one asked for. The arguments are the callers' to check."""
     L = _lib.load()
     out, sums, counts, masks, classes = (C.c_void_p() for _ in range(5))
     stats, ab, cs = _lib.MtgCompaction(), _lib.MtgAbundance(), _lib.MtgColorStats()
-    ins, outs = [k], [C.byref(out), C.byref(stats)]
-    if rung >= _COUNTED:
-        ins += [min_abundance]
-        outs += [C.byref(ab), C.byref(sums)]
-    if rung >= _COUNTED_KMERS:
-        outs += [C.byref(counts)]
-    if rung >= _COLORED:
-        ins += [_ptr(record_colors), n_colors]
-        outs += [C.byref(masks), C.byref(cs)]
-    if rung >= _CLASSES:
-        ins += [int(bool(split))]
-        outs += [C.byref(classes)]
-    ins += [device_id]
+    if cleaning is None:
+        symbol = _COMPACT_SYMBOLS[rung]
+        ins, outs = [k], [C.byref(out), C.byref(stats)]
+        if rung >= _COUNTED:
+            ins += [min_abundance]
+            outs += [C.byref(ab), C.byref(sums)]
+        if rung >= _COUNTED_KMERS:
+            outs += [C.byref(counts)]
+        if rung >= _COLORED:
+            ins += [_ptr(record_colors), n_colors]
+            outs += [C.byref(masks), C.byref(cs)]
+        if rung >= _CLASSES:
+            ins += [int(bool(split))]
+            outs += [C.byref(classes)]
+        ins += [device_id]
+    else:
+        symbol = "mtg_compact_unitigs_cleaned"
+        params, cleaned = _lib.MtgCleaningParams(*cleaning), _lib.MtgCleaning()
+        ins = [k, min_abundance, _ptr(record_colors) if rung >= _COLORED else None, n_colors, int(bool(split)), C.byref(params), device_id]
+        outs = [C.byref(out), C.byref(stats), C.byref(ab), C.byref(sums), C.byref(counts) if rung >= _COUNTED_KMERS else None,
+                C.byref(masks) if rung >= _COLORED else None, C.byref(cs) if rung >= _COLORED else None,
+                C.byref(classes) if rung >= _CLASSES else None, C.byref(cleaned)]
     if isinstance(seqs_or_store, UnitigStore):
-        getattr(L, _COMPACT_SYMBOLS[rung] + "_store")(seqs_or_store.handle, *ins, *outs)
+        getattr(L, symbol + "_store")(seqs_or_store.handle, *ins, *outs)
     else:
         d, o, n, keep = _sequence_arrays(seqs_or_store)
-        getattr(L, _COMPACT_SYMBOLS[rung])(d, o, n, *ins, *outs)
+        getattr(L, symbol)(d, o, n, *ins, *outs)
         del keep
     abundance = colors = cc = None
     try:  # (a handle the rung does not reach is still null: nothing to take, and freeing it is a no-op)
@@ -1137,7 +1209,8 @@ def _compact(rung: int, seqs_or_store, k: int, device_id: int, min_abundance: in
         L.mtg_kmer_counts_free(counts)
         L.mtg_kmer_colors_free(masks)
         L.mtg_color_classes_free(classes)
-    return UnitigStore(out.value), Compaction(**stats.as_dict()), abundance, colors, cc
+    return (UnitigStore(out.value), Compaction(**stats.as_dict()), abundance, colors, cc,
+            Cleaning(**cleaned.as_dict()) if cleaning is not None else None)
 
 
 def last_color_class_times() -> dict:

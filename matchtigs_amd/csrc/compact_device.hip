@@ -65,8 +65,24 @@
 // which keeps a successor only where both k-mers have one mask, so that every unitig is monochromatic; rank, emit, sums, counts and
 // ordered masks follow from succ unchanged. Memory added after emit: 12 N + 48 per run + 32 per class.
 //
+// Cleaned calls (mtg_compact_unitigs_cleaned): tips and isolated unitigs leave the k-mer set T (at first S_m) in rounds
+// before the final pass. A round is nodes, succ<false> (decisions are taken on unsplit unitigs) and rank over the N k-mers of T, then
+// clean_decide_kernel: the thread of every oriented k-mer without a successor -- the last edge of an open walk; cut cycles have none
+// -- reads the walk's length from its rank, looks up the node classes of the walk's two ends (find_node<false>; the node table
+// stays alive through rank for this), derives free / anchored / through from the two "none / one / several" words, and writes the
+// verdict at the walk's first element; the mirror walk's thread derives the same verdict for its own first element, so every word
+// has one writer. clean_keep_kernel turns verdicts into a keep flag per k-mer, the scan of the flags gives the new dense ids (creator
+// order is kept: "smallest id" stays "smallest creator"), clean_move_kernel carries kpos, kcount and kcolor over, and the next pass
+// runs over N' <= N. The counters of a round are reduced per block; a block issues at most one global atomic per counter. The
+// rounds end when one removes nothing (its succ and ranks are then the final ones, unless the unitigs are to be split: succ<true>
+// and rank run once more on the same node table) or when the last allowed round has removed something (then one more pass runs
+// over the survivors). emit and everything behind it see the final set only. With no length given the call runs the kernels of
+// its rung and nothing else. Memory added per round: the node table with its words (64 N) lives on beside the pairs (16 N) instead
+// of being freed in front of rank; 2 N verdict bytes, 4 N keep flags; then, with table, succ and pairs freed, 4 N new ids and the
+// second copy of kpos / kcount / kcolor (8 + 4 + 8 B per survivor).
+//
 // All of these enter through device_compact_unitigs(CompactRequest) (device.hpp): one rung of the ladder per pointer of the request --
-// Counted, Colored, Classed --, null where the call does not climb that far.
+// Counted, Colored, Classed --, null where the call does not climb that far; Cleaned stands beside the ladder and goes with any rung.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -390,6 +406,104 @@ __global__ __launch_bounds__(hu::EB) void walk_kernel(const unsigned long long *
         atomicMin(&wmin[h], (uint32_t)o);
     }
 }
+// ---- tip clipping and isolated unitigs (cleaned calls) ----
+// counters of one round: [0] tips, [1] isolated walks, [2] tip k-mers, [3] isolated k-mers, [4] removed occurrences
+constexpr int CLEAN_COUNTERS = 5;
+constexpr uint8_t VERDICT_TIP = 1, VERDICT_ISOLATED = 2;
+enum EndState : int { END_FREE = 0, END_ANCHORED = 1, END_THROUGH = 2 };
+
+// 0, 1 or 2 (= two or more) incident edges
+__device__ __forceinline__ int incident_count(uint32_t word) { return word == NONE32 ? 0 : (word == MULTI32 ? 2 : 1); }
+
+// The state of the end behind oriented k-mer o, i.e. of o's head node v: the suffix of the reading as read (o even) or the reverse
+// complement of its prefix (o odd). The slot's words belong to the canonical orientation c of v's class: out(v) is out_e for v = c
+// and (mirrored) in_e for v = rc(c); the prefix as read is rc(v), which turns the roles once more. At a self-mirror node an
+// incident k-mer is recorded once, under in_e where its reading ends in v and under out_e where it starts there, and each stands
+// for one edge that leaves v: |out(v)| is the sum of both words.
+__device__ __forceinline__ int end_state(const NodeArgs &a, uint32_t o, unsigned int *err) {
+    kw::ClassKey key;
+    const uint64_t s = find_node<false>(a, a.kpos[o >> 1] + ((o & 1u) ? 0 : 1), key, err);
+    const int oc = incident_count(a.out_e[s]), ic = incident_count(a.in_e[s]);
+    if (key.pal) return oc + ic <= 1 ? END_FREE : END_ANCHORED;  // beyond = beside = |out(v)| - 1
+    const bool turned = key.flip != (bool)(o & 1u);
+    const int beyond = turned ? ic : oc, into = turned ? oc : ic;
+    return into >= 2 ? END_ANCHORED : (beyond == 0 ? END_FREE : END_THROUGH);
+}
+
+// sums[c] += the block's total of v[c], c < n: per wave by shuffles, per block through LDS, then at most one global atomic per counter
+template <int n>
+__device__ __forceinline__ void block_add(unsigned long long (&v)[n], unsigned long long *sums) {
+    __shared__ unsigned long long part[n][hu::EB / 64];
+    const int lane = threadIdx.x & (warpSize - 1), wave = threadIdx.x / warpSize;
+#pragma unroll
+    for (int c = 0; c < n; c++) {
+        for (int d = warpSize / 2; d > 0; d /= 2) v[c] += __shfl_down(v[c], d);
+        if (lane == 0) part[c][wave] = v[c];
+    }
+    __syncthreads();
+    if (threadIdx.x < n) {
+        unsigned long long t = 0;
+        for (int w = 0; w < hu::EB / 64; w++) t += part[threadIdx.x][w];
+        if (t) atomicAdd(&sums[threadIdx.x], t);
+    }
+}
+
+// One thread per oriented k-mer that ends an open walk (succ == none; the last element of a cut cycle has its head as successor and
+// never gets here). The walk e_1 .. e_n has n = rank + 1 k-mers and e_1 = jump; its two ends are the head node of e_n and the head
+// node of e_1's mirror. The verdict goes to verdict[e_1]. The thread at the end of the mirror walk sees the same two states in the
+// other order, so it writes the same verdict to its own first element: no word has two writers, and a walk is counted by the one of
+// the two threads with the smaller id (a walk is never its own mirror: the two ids differ).
+__global__ __launch_bounds__(hu::EB) void clean_decide_kernel(NodeArgs a, const unsigned long long *pairs, uint64_t n, uint64_t tip_kmers,
+                                                               uint64_t isolated_kmers, uint8_t *verdict, unsigned long long *counters,
+                                                               unsigned int *err) {
+    const uint64_t o = hu::gid();
+    unsigned long long c[2] = {0, 0};  // tips, isolated walks
+    if (o < n && a.succ[o] == NONE32) {
+        const uint64_t pr = pairs[o];
+        const uint32_t first = (uint32_t)pr == NONE32 ? (uint32_t)o : (uint32_t)pr;
+        const uint64_t len = (pr >> 32) + 1;
+        if ((len < tip_kmers || len < isolated_kmers) && a.succ[first ^ 1u] == NONE32) {  // (the second clause: e_1 has no predecessor)
+            const int here = end_state(a, (uint32_t)o, err), there = end_state(a, first ^ 1u, err);
+            uint8_t v = 0;
+            if (len < tip_kmers && here + there == END_FREE + END_ANCHORED) v = VERDICT_TIP;  // (0 + 1: no other pair of states sums to 1)
+            if (len < isolated_kmers && here == END_FREE && there == END_FREE) v = VERDICT_ISOLATED;
+            if (v) {
+                verdict[first] = v;
+                if ((uint32_t)o < (first ^ 1u)) c[v - 1] = 1;
+            }
+        }
+    }
+    block_add<2>(c, counters);
+}
+// keep[i] = 0 where the walk of k-mer i has a verdict (read at the first element of the reading's walk: the mirror walk holds the
+// same); the removed k-mers and their abundances are counted on the way (kcount: null in a call that does not count)
+__global__ __launch_bounds__(hu::EB) void clean_keep_kernel(const unsigned long long *pairs, const uint8_t *verdict, const uint32_t *kcount, uint64_t N,
+                                                             uint32_t *keep, unsigned long long *counters) {
+    const uint64_t i = hu::gid();
+    unsigned long long c[3] = {0, 0, 0};  // tip k-mers, isolated k-mers, removed occurrences
+    if (i < N) {
+        const uint32_t j = (uint32_t)pairs[2 * i];
+        const uint8_t v = verdict[j == NONE32 ? 2 * i : j];
+        keep[i] = v == 0;
+        if (v) {
+            c[v - 1] = 1;
+            c[2] = kcount ? kcount[i] : 0;
+        }
+    }
+    block_add<3>(c, counters + 2);
+}
+// the kept k-mers move to their new ids (new_id: the exclusive scan of keep -- creator order is kept)
+__global__ __launch_bounds__(hu::EB) void clean_move_kernel(const uint32_t *keep, const uint32_t *new_id, uint64_t N, const unsigned long long *kpos,
+                                                             const uint32_t *kcount, const unsigned long long *kcolor, unsigned long long *kpos_to,
+                                                             uint32_t *kcount_to, unsigned long long *kcolor_to) {
+    const uint64_t i = hu::gid();
+    if (i >= N || !keep[i]) return;
+    const uint32_t to = new_id[i];
+    kpos_to[to] = kpos[i];
+    if (kcount) kcount_to[to] = kcount[i];
+    if (kcolor) kcolor_to[to] = kcolor[i];
+}
+
 // heads of emitted walks (the minimum is even: the walk holds the reading of its leader) leave their length at the leader's id
 // stats: [0] closed walks, [1] k-mers of the longest unitig
 __global__ __launch_bounds__(hu::EB) void leader_kernel(const unsigned long long *pairs, const uint32_t *succ, uint64_t n, const uint32_t *wmin,
@@ -688,7 +802,7 @@ void color_classes(const unsigned long long *d_ordered, const unsigned long long
 // counted == nullptr: the plain compaction
 // colored != nullptr: counted too
 UnitigStore *compact(const char *data, const uint64_t *off, uint64_t n_rec, uint64_t k, int device_id, mtg_compaction *stats_out, CompactTimes *times,
-                     const Counted *counted, const Colored *colored = nullptr, const Classed *classed = nullptr) {
+                     const Counted *counted, const Colored *colored = nullptr, const Classed *classed = nullptr, const Cleaned *cleaned = nullptr) {
     if (!off || (n_rec && off[n_rec] && !data)) MTG_DIE("mtg_compact_unitigs: null argument");
     if (k < 2) MTG_DIE("mtg_compact_unitigs: k must be >= 2");
     if (k >= (1ull << 31)) MTG_DIE("mtg_compact_unitigs: k too large");
@@ -730,11 +844,20 @@ UnitigStore *compact(const char *data, const uint64_t *off, uint64_t n_rec, uint
         *classed->out = ColorClasses{};
         *classed->times = ColorClassTimes{};
     }
+    if (cleaned && (cleaned->params.rounds < 1 || cleaned->params.rounds > 64))
+        MTG_DIE("mtg_compact_unitigs_cleaned: %llu rounds; 1 .. 64 are served", (unsigned long long)cleaned->params.rounds);
+    const bool cleaning = cleaned && (cleaned->params.tip_kmers || cleaned->params.isolated_kmers);
+    mtg_cleaning clean{};
+    double clean_ms = 0;
     auto finish = [&]() {
         t.total_ms = ms_since(t_total);
         if (stats_out) *stats_out = r;
         if (counted && counted->abundance) *counted->abundance = ab;
         if (times) *times = t;
+        if (cleaned) {
+            *cleaned->out = clean;
+            *cleaned->clean_ms = clean_ms;
+        }
         return store;
     };
     if (n_bases == 0) return finish();
@@ -755,7 +878,7 @@ UnitigStore *compact(const char *data, const uint64_t *off, uint64_t n_rec, uint
     t.pack_ms = seq.pack_ms;
     auto free_all = [&](std::initializer_list<const void *> ps) { for (const void *p : ps) hu::device_free(p); };
     if (r.windows == 0) return finish();  // nothing is as long as k
-    PhaseEvents<6> ev;
+    PhaseEvents<5> ev;
     ev.mark(0, st);
 
     // ---- insert: the creator of every k-mer class ----
@@ -821,7 +944,7 @@ UnitigStore *compact(const char *data, const uint64_t *off, uint64_t n_rec, uint
     }
     HIP_CHECK(hipGetLastError());
     small.read(st, stage);
-    const uint64_t N = r.distinct_kmers = small.h[2], n_or = 2 * N;
+    uint64_t N = r.distinct_kmers = small.h[2], n_or = 2 * N;  // (a cleaned call: they shrink with the rounds)
     if (N > MAX_KMERS) MTG_DIE("mtg_compact_unitigs: %llu distinct k-mers; oriented k-mer ids are 32-bit", (unsigned long long)N);
     if (counted) ab.distinct_kept = N;
     if (N == 0) {  // (counted calls only: no k-mer reaches the threshold)
@@ -848,31 +971,23 @@ UnitigStore *compact(const char *data, const uint64_t *off, uint64_t n_rec, uint
     ev.mark(2, st);
     free_all({ka.table, d_id_of_pos, d_bsum32, d_count, d_rec_colors, d_colors});
 
-    // ---- the (k-1)-mer classes and succ ----
+    // ---- the (k-1)-mer classes, succ and the ranks: once, or in a cleaned call once per round and once more over the final set ----
     NodeArgs na{};
-    na.packed = d_packed; na.kpos = d_kpos; na.N = N; na.L = k - 1;
-    na.slots = std::max<uint64_t>(8, 4 * N);  // at most 2 N classes
-    hu::device_malloc(&na.table, na.slots * 8);
-    hu::device_malloc(&na.out_e, na.slots * 4);
-    hu::device_malloc(&na.in_e, na.slots * 4);
-    hu::device_malloc(&na.succ, n_or * 4);
-    HIP_CHECK(hipMemsetAsync(na.table, 0xFF, na.slots * 8, st));
-    HIP_CHECK(hipMemsetAsync(na.out_e, 0xFF, na.slots * 4, st));
-    HIP_CHECK(hipMemsetAsync(na.in_e, 0xFF, na.slots * 4, st));
-    node_insert_kernel<<<hu::grid_for(N), hu::EB, 0, st>>>(na, d_err);
-    if (classed && classed->split) succ_kernel<true><<<hu::grid_for(N), hu::EB, 0, st>>>(na, d_err, d_kcolor);
-    else succ_kernel<false><<<hu::grid_for(N), hu::EB, 0, st>>>(na, d_err, nullptr);
-    HIP_CHECK(hipGetLastError());
-    ev.mark(3, st);
-    free_all({na.table, na.out_e, na.in_e});
-    small.read(st, stage);
-
-    // ---- ranks by pointer jumping ----
+    na.packed = d_packed; na.L = k - 1;
     unsigned long long *d_pairs = nullptr;
-    hu::device_malloc(&d_pairs, n_or * 8);
-    rank_init_kernel<<<hu::grid_for(n_or), hu::EB, 0, st>>>(na.succ, n_or, d_pairs);
-    HIP_CHECK(hipGetLastError());
-    int rounds = 0;
+    int rounds = 0, rankings = 0;
+    double nodes_ms = 0, rank_ms = 0;
+    const bool split = classed && classed->split;
+    auto run_succ = [&](bool cut_at_colours) {
+        if (cut_at_colours) succ_kernel<true><<<hu::grid_for(N), hu::EB, 0, st>>>(na, d_err, d_kcolor);
+        else succ_kernel<false><<<hu::grid_for(N), hu::EB, 0, st>>>(na, d_err, nullptr);
+        HIP_CHECK(hipGetLastError());
+    };
+    auto free_nodes = [&]() {
+        free_all({na.table, na.out_e, na.in_e});
+        na.table = nullptr;
+        na.out_e = na.in_e = nullptr;
+    };
     auto jump_rounds = [&](uint64_t n, const uint32_t *list, int max_rounds) {  // true: settled
         for (int i = 0; i < max_rounds; i++) {
             HIP_CHECK(hipMemsetAsync(d_changed, 0, 4, st));
@@ -884,10 +999,16 @@ UnitigStore *compact(const char *data, const uint64_t *off, uint64_t n_rec, uint
         }
         return false;
     };
-    if (!jump_rounds(n_or, nullptr, log2_ceil(n_or) + 2)) {  // closed walks
-        uint32_t *d_list = nullptr;
+    auto run_rank = [&]() {  // ranks by pointer jumping over na.succ
+        const bool again = rankings++ > 0;
+        if (!d_pairs) hu::device_malloc(&d_pairs, n_or * 8);
+        rank_init_kernel<<<hu::grid_for(n_or), hu::EB, 0, st>>>(na.succ, n_or, d_pairs);
+        HIP_CHECK(hipGetLastError());
+        if (jump_rounds(n_or, nullptr, log2_ceil(n_or) + 2)) return;
+        uint32_t *d_list = nullptr;  // closed walks
         unsigned long long *d_buf = nullptr;
         hu::device_malloc(&d_list, n_or * 4);
+        if (again) HIP_CHECK(hipMemsetAsync(small.d + 4, 0, 8, st));  // (an earlier ranking has counted its own)
         cycle_list_kernel<<<hu::grid_for(n_or), hu::EB, 0, st>>>(d_pairs, na.succ, n_or, d_list, small.d + 4);
         HIP_CHECK(hipGetLastError());
         small.read(st, stage);
@@ -904,8 +1025,120 @@ UnitigStore *compact(const char *data, const uint64_t *off, uint64_t n_rec, uint
         HIP_CHECK(hipGetLastError());
         if (!jump_rounds(C, d_list, log2_ceil(C) + 2)) MTG_DIE("unitig compaction: internal error (a cut cycle does not settle)");
         free_all({d_list, d_buf});
+    };
+    for (bool final_pass = !cleaning;;) {
+        PhaseEvents<3> pe;
+        pe.mark(0, st);
+        na.kpos = d_kpos; na.N = N;
+        na.slots = std::max<uint64_t>(8, 4 * N);  // at most 2 N classes
+        hu::device_malloc(&na.table, na.slots * 8);
+        hu::device_malloc(&na.out_e, na.slots * 4);
+        hu::device_malloc(&na.in_e, na.slots * 4);
+        hu::device_malloc(&na.succ, n_or * 4);
+        HIP_CHECK(hipMemsetAsync(na.table, 0xFF, na.slots * 8, st));
+        HIP_CHECK(hipMemsetAsync(na.out_e, 0xFF, na.slots * 4, st));
+        HIP_CHECK(hipMemsetAsync(na.in_e, 0xFF, na.slots * 4, st));
+        node_insert_kernel<<<hu::grid_for(N), hu::EB, 0, st>>>(na, d_err);
+        run_succ(split && final_pass);  // (a round decides on the unsplit unitigs)
+        pe.mark(1, st);
+        if (final_pass) free_nodes();  // (a round's decision probes the table once more)
+        small.read(st, stage);
+        run_rank();
+        pe.mark(2, st);
+        nodes_ms += pe.ms(0, 1);
+        rank_ms += pe.ms(1, 2);
+        if (final_pass) break;
+
+        // ---- one round: verdicts per walk end, keep flags per k-mer, the survivors' new ids ----
+        PhaseEvents<4> ce;
+        uint8_t *d_verdict = nullptr;
+        uint32_t *d_keep = nullptr, *d_new_id = nullptr, *d_bsum_keep = nullptr;
+        unsigned long long *d_counters = nullptr;
+        unsigned long long h_counters[CLEAN_COUNTERS] = {};
+        hu::device_malloc(&d_verdict, n_or);
+        hu::device_malloc(&d_keep, N * 4);
+        hu::device_malloc(&d_counters, sizeof h_counters);
+        HIP_CHECK(hipMemsetAsync(d_verdict, 0, n_or, st));
+        HIP_CHECK(hipMemsetAsync(d_counters, 0, sizeof h_counters, st));
+        ce.mark(0, st);
+        clean_decide_kernel<<<hu::grid_for(n_or), hu::EB, 0, st>>>(na, d_pairs, n_or, cleaned->params.tip_kmers, cleaned->params.isolated_kmers, d_verdict,
+                                                                  d_counters, d_err);
+        clean_keep_kernel<<<hu::grid_for(N), hu::EB, 0, st>>>(d_pairs, d_verdict, d_kcount, N, d_keep, d_counters);
+        HIP_CHECK(hipGetLastError());
+        ce.mark(1, st);
+        HIP_CHECK(hipMemcpyAsync(h_counters, d_counters, sizeof h_counters, hipMemcpyDeviceToHost, st));
+        small.read(st, stage);
+        clean_ms += ce.ms(0, 1);
+        free_all({d_verdict, d_counters});
+        clean.rounds_run++;
+        clean.tips += h_counters[0];
+        clean.isolated += h_counters[1];
+        clean.tip_kmers += h_counters[2];
+        clean.isolated_kmers += h_counters[3];
+        clean.removed_occurrences += h_counters[4];
+        const uint64_t removed = h_counters[2] + h_counters[3];
+        if (removed > N) MTG_DIE("unitig compaction: internal error (%llu of %llu k-mers removed)", (unsigned long long)removed, (unsigned long long)N);
+        if (removed == 0) {  // the set is final: so are succ and the ranks, unless the unitigs are to be split
+            hu::device_free(d_keep);
+            if (split) {
+                PhaseEvents<3> fe;
+                fe.mark(0, st);
+                run_succ(true);
+                fe.mark(1, st);
+                free_nodes();
+                run_rank();
+                fe.mark(2, st);
+                nodes_ms += fe.ms(0, 1);
+                rank_ms += fe.ms(1, 2);
+            } else {
+                free_nodes();
+            }
+            break;
+        }
+        free_nodes();
+        free_all({na.succ, d_pairs});
+        na.succ = nullptr;
+        d_pairs = nullptr;
+        const uint64_t N_left = N - removed;
+        if (N_left) {
+            unsigned long long *d_kpos_to = nullptr, *d_kcolor_to = nullptr;
+            uint32_t *d_kcount_to = nullptr;
+            hu::device_malloc(&d_new_id, N * 4);
+            hu::device_malloc(&d_bsum_keep, (hu::scan_blocks(N) + 2) * 4);
+            hu::device_malloc(&d_kpos_to, N_left * 8);
+            if (d_kcount) hu::device_malloc(&d_kcount_to, N_left * 4);
+            if (d_kcolor) hu::device_malloc(&d_kcolor_to, N_left * 8);
+            uint32_t *d_n_left = d_bsum_keep + hu::scan_blocks(N) + 1;
+            uint32_t n_left = 0;
+            ce.mark(2, st);
+            hu::scan_u32<uint32_t>(st, d_keep, N, d_new_id, d_bsum_keep, d_n_left);
+            clean_move_kernel<<<hu::grid_for(N), hu::EB, 0, st>>>(d_keep, d_new_id, N, d_kpos, d_kcount, d_kcolor, d_kpos_to, d_kcount_to, d_kcolor_to);
+            HIP_CHECK(hipGetLastError());
+            ce.mark(3, st);
+            HIP_CHECK(hipMemcpyAsync(&n_left, d_n_left, 4, hipMemcpyDeviceToHost, st));
+            HIP_CHECK(hipStreamSynchronize(st));
+            clean_ms += ce.ms(2, 3);
+            if (n_left != N_left) MTG_DIE("unitig compaction: internal error (%llu k-mers kept, %llu counted)", (unsigned long long)n_left, (unsigned long long)N_left);
+            free_all({d_kpos, d_kcount, d_kcolor, d_new_id, d_bsum_keep});
+            d_kpos = d_kpos_to;
+            d_kcount = d_kcount_to;
+            d_kcolor = d_kcolor_to;
+        }
+        hu::device_free(d_keep);
+        N = r.distinct_kmers = N_left;
+        n_or = 2 * N;
+        if (N == 0) {  // everything was a tip or isolated
+            free_all({d_kpos, d_kcount, d_kcolor});
+            t.insert_ms = ev.ms(0, 1);
+            t.ids_ms = ev.ms(1, 2);
+            t.nodes_ms = nodes_ms;
+            t.rank_ms = rank_ms;
+            t.rounds = rounds;
+            return finish();
+        }
+        final_pass = clean.rounds_run == cleaned->params.rounds;
     }
-    ev.mark(4, st);
+    ev.mark(3, st);
 
     // ---- emit ----
     uint32_t *d_wmin = nullptr, *d_wlen = nullptr, *d_lead_flag = nullptr, *d_lead_chars = nullptr;
@@ -976,7 +1209,7 @@ UnitigStore *compact(const char *data, const uint64_t *off, uint64_t n_rec, uint
         HIP_CHECK(hipGetLastError());
         *colored->stats_ms = ev_stats.ms(0, 1);
     }
-    ev.mark(5, st);
+    ev.mark(4, st);
     HIP_CHECK(hipStreamSynchronize(st));
     if (classed) color_classes(d_ordered_colors, d_out_off, N, r.unitigs, k, classed->split, st, small, device_id, classed->out, classed->times);
 
@@ -1009,9 +1242,9 @@ UnitigStore *compact(const char *data, const uint64_t *off, uint64_t n_rec, uint
     t.download_ms = ms_since(t0);
     t.insert_ms = ev.ms(0, 1);
     t.ids_ms = ev.ms(1, 2);
-    t.nodes_ms = ev.ms(2, 3);
-    t.rank_ms = ev.ms(3, 4);
-    t.emit_ms = ev.ms(4, 5);
+    t.nodes_ms = nodes_ms;
+    t.rank_ms = rank_ms;
+    t.emit_ms = ev.ms(3, 4);
     t.rounds = rounds;
     free_all({d_kpos, na.succ, d_pairs, d_wmin, d_wlen, d_lead_flag, d_lead_chars, d_char_off, d_bsum32, d_bsum64, d_out, d_out_off, d_kcount, d_sums, d_ordered, d_kcolor,
               d_ordered_colors, d_color_stats});
@@ -1025,7 +1258,7 @@ UnitigStore *compact(const char *data, const uint64_t *off, uint64_t n_rec, uint
     // pair in the emit kernels, wmin / wlen; per leader flag, length and offset; and the output characters and offsets.
     t.bytes = n_bases + seq.n_words * 4 + r.windows * 8 + seq.n_words * 4 + slots * 8 * 3 + n_bases * 4 * 3 + N * 4 +
               N * (8 * 3 + 2 * 4 * ((k + 15) / 16 + 1) + 2 * (8 + 4) * 2 + 8) + n_or * 8 * (uint64_t)std::max(rounds, 1) +
-              n_or * (4 + 8 + 8 + 8 + 4) + N * (4 * 3 + 4 * 2 + 8 * 2) + n_chars + r.unitigs * 8;
+              n_or * (4 + 8 + 8 + 8 + 4) + N * (4 * 3 + 4 * 2 + 8 * 2) + n_chars + r.unitigs * 8;  // (of a cleaned call: the final pass alone)
     return finish();
 }
 
@@ -1038,7 +1271,8 @@ UnitigStore *device_compact_unitigs(const CompactRequest &rq) {
     if ((c && !c->sums) || (col && (!c || !c->kmer_counts || !col->kmer_colors || !col->stats || !col->stats_ms)) ||
         (cl && (!col || !cl->out || !cl->times)))
         MTG_DIE("%s: null argument", rq.who);
-    return compact(rq.data, rq.off, rq.n_rec, rq.k, rq.device_id, rq.stats_out, rq.times, c, col, cl);
+    if (rq.cleaned && (!rq.cleaned->out || !rq.cleaned->clean_ms)) MTG_DIE("%s: null argument", rq.who);
+    return compact(rq.data, rq.off, rq.n_rec, rq.k, rq.device_id, rq.stats_out, rq.times, c, col, cl, rq.cleaned);
 }
 
 void device_color_classes(const uint64_t *kmer_colors, uint64_t n, const uint64_t *unitig_kmers, uint64_t n_unitigs, int device_id, ColorClasses *out,

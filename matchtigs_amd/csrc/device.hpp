@@ -231,6 +231,14 @@ struct Classed {
     ColorClasses *out;
     ColorClassTimes *times;
 };
+// What a cleaned call adds: tip clipping and the removal of isolated unitigs in rounds before the final pass. It
+// needs no rung below it; removed_occurrences is 0 unless the call is counted. clean_ms: HIP-event time of the decision and removal
+// kernels over all rounds.
+struct Cleaned {
+    mtg_cleaning_params params;
+    mtg_cleaning *out;
+    double *clean_ms;
+};
 // One compaction. who: the public entry point that was called, for the messages. Each rung of the ladder is one pointer, null where
 // the call does not climb that far; a rung needs the ones below it.
 struct CompactRequest {
@@ -244,6 +252,7 @@ struct CompactRequest {
     const Counted *counted;
     const Colored *colored;
     const Classed *classed;
+    const Cleaned *cleaned = nullptr;
 };
 UnitigStore *device_compact_unitigs(const CompactRequest &rq);
 // ... of masks and unitig lengths handed in (kmer_colors: n masks in window order, none 0; unitig_kmers: n_unitigs lengths that sum to n)

@@ -794,6 +794,7 @@ void mtg_read_sequences_named(const char *path, mtg_unitigs **seqs_out, mtg_unit
 // ---- unitig compaction on the GPU (compact_device.hip) ----
 static thread_local CompactTimes g_last_compact;
 static thread_local ColorClassTimes g_last_color_class;
+static thread_local double g_last_clean[2];  // ms of the decision and removal kernels, rounds run
 struct mtg_abundance_sums { std::vector<uint64_t> v; };
 struct mtg_kmer_counts { std::vector<uint32_t> v; };
 struct mtg_kmer_colors { std::vector<uint64_t> v; };
@@ -810,6 +811,7 @@ struct CompactIn {
     const uint8_t *record_colors = nullptr;  // from COLORED on
     uint64_t n_colors = 0;
     int split = 0;                           // CLASSES
+    const mtg_cleaning_params *cleaning = nullptr;  // mtg_compact_unitigs_cleaned, at any rung
 };
 struct CompactOut {
     mtg_unitigs **out;
@@ -820,6 +822,7 @@ struct CompactOut {
     mtg_kmer_colors **kmer_colors = nullptr;  // from COLORED on
     mtg_color_stats *color_stats = nullptr;
     mtg_color_classes **classes = nullptr;    // CLASSES
+    mtg_cleaning *cleaning = nullptr;         // mtg_compact_unitigs_cleaned
 };
 // what all mtg_compact_unitigs* share: the argument checks, the handles and their way to the out-pointers (who: the entry point)
 static void compact_call(const char *who, CompactRung rung, const CompactIn &in, const CompactOut &o) {
@@ -835,8 +838,13 @@ static void compact_call(const char *who, CompactRung rung, const CompactIn &in,
     const Counted counted{in.min_abundance, o.abundance, s ? &s->v : nullptr, c ? &c->v : nullptr};
     const Colored colored{in.record_colors, in.n_colors, m ? &m->v : nullptr, o.color_stats, &g_last_kmer_color.stats_ms};
     const Classed classed{in.split == 1, cl ? &cl->c : nullptr, &g_last_color_class};
+    mtg_cleaning none{};
+    const bool clean = in.cleaning && o.cleaning;
+    const Cleaned cleaned{clean ? *in.cleaning : mtg_cleaning_params{0, 0, 1}, clean ? o.cleaning : &none, &g_last_clean[0]};
     *o.out = new mtg_unitigs{device_compact_unitigs({who, in.data, in.offsets, in.n, in.k, in.device_id, o.stats, &g_last_compact, s ? &counted : nullptr,
-                                                     m ? &colored : nullptr, cl ? &classed : nullptr})};
+                                                     m ? &colored : nullptr, cl ? &classed : nullptr, &cleaned})};
+    g_last_clean[1] = (double)cleaned.out->rounds_run;
+    if (o.cleaning && !clean) *o.cleaning = none;
     if (s) *o.sums = s;
     if (c) *o.kmer_counts = c;
     if (m) *o.kmer_colors = m;
@@ -901,6 +909,32 @@ void mtg_compact_unitigs_colored_classes_store(const mtg_unitigs *in, uint64_t k
     if (!in) MTG_DIE("mtg_compact_unitigs_colored_classes_store: null argument");
     mtg_compact_unitigs_colored_classes(in->s->data.data(), in->s->off.data(), in->s->off.size() - 1, k, min_abundance, record_colors, n_colors, split,
                                         device_id, out, stats, abundance, sums, kmer_counts, kmer_colors, color_stats, classes);
+}
+// The rung is the highest one whose out-pointers are all there; a rung's inputs are read only where it is reached.
+void mtg_compact_unitigs_cleaned(const char *data, const uint64_t *offsets, uint64_t n, uint64_t k, uint64_t min_abundance,
+                                 const uint8_t *record_colors, uint64_t n_colors, int split, const mtg_cleaning_params *params, int device_id,
+                                 mtg_unitigs **out, mtg_compaction *stats, mtg_abundance *abundance, mtg_abundance_sums **sums,
+                                 mtg_kmer_counts **kmer_counts, mtg_kmer_colors **kmer_colors, mtg_color_stats *color_stats,
+                                 mtg_color_classes **classes, mtg_cleaning *cleaning) {
+    const char *const who = "mtg_compact_unitigs_cleaned";
+    const CompactRung rung = !sums ? PLAIN : !kmer_counts ? COUNTED : (!kmer_colors || !color_stats) ? COUNTED_KMERS : !classes ? COLORED : CLASSES;
+    if (rung < COUNTED && min_abundance != 1) MTG_DIE("%s: min_abundance %llu needs the sums' out-pointer", who, (unsigned long long)min_abundance);
+    if (rung < CLASSES && split != 0) MTG_DIE("%s: split needs the classes' out-pointer", who);
+    compact_call(who, rung, {data, offsets, n, k, device_id, min_abundance, record_colors, n_colors, split, params},
+                 {out, stats, abundance, sums, kmer_counts, kmer_colors, color_stats, classes, cleaning});
+}
+void mtg_compact_unitigs_cleaned_store(const mtg_unitigs *in, uint64_t k, uint64_t min_abundance, const uint8_t *record_colors,
+                                       uint64_t n_colors, int split, const mtg_cleaning_params *params, int device_id, mtg_unitigs **out,
+                                       mtg_compaction *stats, mtg_abundance *abundance, mtg_abundance_sums **sums,
+                                       mtg_kmer_counts **kmer_counts, mtg_kmer_colors **kmer_colors, mtg_color_stats *color_stats,
+                                       mtg_color_classes **classes, mtg_cleaning *cleaning) {
+    if (!in) MTG_DIE("mtg_compact_unitigs_cleaned_store: null argument");
+    mtg_compact_unitigs_cleaned(in->s->data.data(), in->s->off.data(), in->s->off.size() - 1, k, min_abundance, record_colors, n_colors, split, params,
+                                device_id, out, stats, abundance, sums, kmer_counts, kmer_colors, color_stats, classes, cleaning);
+}
+void mtg_last_clean_times(double out[2]) {
+    out[0] = g_last_clean[0];
+    out[1] = g_last_clean[1];
 }
 // the vector behind one of the handles above (who: the entry point, for the message)
 extern "C++" {
