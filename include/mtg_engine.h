@@ -438,7 +438,10 @@ uint64_t mtg_flatten_clib(const mtg_graph *g, const mtg_walks *tigs, int64_t *ti
 /* Tig spelling (replaces write_walks_fasta, bin.rs:466-606): walks (edge ids into the mutated graph,
  * limits[i] = exclusive end of walk i) -> FASTA text. unitig_seqs = concatenated ASCII sequences, unitig u occupies
  * [seq_offsets[u], seq_offsets[u+1]). Header ">{i+1}"; overlaps k-1 after a unitig edge, k-1-weight after a dummy
- * edge; backwards edges are reverse-complemented. Returns the byte count; *fasta_out is malloc'd (mtg_free). */
+ * edge; backwards edges are reverse-complemented. Returns the byte count; *fasta_out is malloc'd (mtg_free).
+ * Aborts with a message where the reference panics: an empty walk, a walk whose first edge is a dummy, a dummy edge heavier than
+ * k-1 in front of a unitig edge, an overlap longer than the unitig (the same checks, before any GPU call, in the _gfa and _device
+ * forms below). */
 uint64_t mtg_write_walks_fasta(const mtg_graph *g, uint64_t n_walks, const uint64_t *limits, const uint32_t *edges,
                                uint64_t k, const char *unitig_seqs, const uint64_t *seq_offsets, char **fasta_out);
 

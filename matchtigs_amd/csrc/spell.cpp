@@ -38,10 +38,38 @@ static inline unsigned decimal_digits(uint64_t v) {
     return d;
 }
 
+// The per-walk input checks of both spellers (this file and spell_device.hip), made before anything is written or any GPU call:
+// where the reference panics -- walk.first().unwrap() on an empty walk (bin.rs:487), a dummy first edge (:489), k - 1 - weight
+// below zero (:536), an overlap longer than the unitig (:541, :572) -- the library dies with a message.
+void check_walks_spellable(const HostGraph &g, uint64_t n_walks, const uint64_t *limits, const uint32_t *edges, uint64_t k,
+                           const uint64_t *seq_off) {
+    const uint64_t n_orig = g.n_original_edges;
+    uint64_t begin = 0;
+    for (uint64_t i = 0; i < n_walks; i++) {
+        const uint64_t end = limits[i];
+        if (end <= begin) MTG_DIE("empty walk %llu", (unsigned long long)i);
+        uint32_t prev = edges[begin];
+        if (prev >= n_orig) MTG_DIE("walk %llu starts with a dummy edge (bin.rs:489)", (unsigned long long)i);
+        for (uint64_t j = begin + 1; j < end; j++) {
+            const uint32_t cur = edges[j];
+            if (cur >= n_orig) { prev = cur; continue; }
+            if (prev >= n_orig && g.weight(prev) > k - 1)
+                MTG_DIE("dummy edge %llu of weight %llu: longer than k - 1 = %llu (bin.rs:536)", (unsigned long long)prev,
+                        (unsigned long long)g.weight(prev), (unsigned long long)(k - 1));
+            const uint64_t offset = prev < n_orig ? k - 1 : k - 1 - g.weight(prev);
+            const uint64_t sl = seq_off[g.unitig(cur) + 1] - seq_off[g.unitig(cur)];
+            if (offset > sl) MTG_DIE("overlap %llu longer than unitig %llu", (unsigned long long)offset, (unsigned long long)g.unitig(cur));
+            prev = cur;
+        }
+        begin = end;
+    }
+}
+
 // Returns the number of bytes; *out_buf is malloc'd (caller frees with mtg_free).
 uint64_t write_walks_text(const HostGraph &g, uint64_t n_walks, const uint64_t *limits, const uint32_t *edges, uint64_t k,
                           const char *seqs, const uint64_t *seq_off, bool gfa, const char *gfa_header, char **out_buf) {
     if (k < 1) MTG_DIE("k must be >= 1");
+    check_walks_spellable(g, n_walks, limits, edges, k, seq_off);
     std::string head;  // bin.rs:688-693
     if (gfa) head = (gfa_header ? std::string(gfa_header) : "H\tKL:Z:" + std::to_string(k)) + "\n";
     const uint64_t prefix_len = gfa ? 2 : 1, after_number = 1;  // "S\t" / ">", then the number, then "\t" / "\n"
@@ -53,18 +81,14 @@ uint64_t write_walks_text(const HostGraph &g, uint64_t n_walks, const uint64_t *
     uint64_t begin = 0;
     for (uint64_t i = 0; i < n_walks; i++) {
         const uint64_t end = limits[i];
-        if (end <= begin) MTG_DIE("empty walk %llu", (unsigned long long)i);
         uint64_t len = prefix_len + decimal_digits(i + 1) + after_number;
         uint32_t prev = edges[begin];
-        if (prev >= n_orig) MTG_DIE("walk %llu starts with a dummy edge (bin.rs:489)", (unsigned long long)i);
         len += seq_len(prev);
         for (uint64_t j = begin + 1; j < end; j++) {
             const uint32_t cur = edges[j];
             if (cur >= n_orig) { prev = cur; continue; }
             const uint64_t offset = prev < n_orig ? k - 1 : k - 1 - g.weight(prev);
-            const uint64_t sl = seq_len(cur);
-            if (offset > sl) MTG_DIE("overlap %llu longer than unitig %llu", (unsigned long long)offset, (unsigned long long)g.unitig(cur));
-            len += sl - offset;
+            len += seq_len(cur) - offset;
             prev = cur;
         }
         len += 1;  // "\n"

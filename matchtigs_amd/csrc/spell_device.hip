@@ -221,6 +221,8 @@ uint64_t device_write_walks_text(const HostGraph &g, uint64_t n_walks, const uin
     if (resident && resident->device != device_id) resident = nullptr;
     if (resident) n_walks = resident->n_tigs;
     if (k < 1) MTG_DIE("k must be >= 1");
+    // the host speller's input checks, before the first HIP call (resident tigs are the engine's own: mark_starts32_kernel checks those)
+    if (!resident) check_walks_spellable(g, n_walks, limits, edges, k, seq_off);
     if (device_count() <= device_id) MTG_DIE("no HIP device %d for the GPU tig spelling", device_id);
     if (n_walks >= 0xFFFFFFFEull) MTG_DIE("too many walks for the device spelling");
     HIP_CHECK(hipSetDevice(device_id));
@@ -228,12 +230,6 @@ uint64_t device_write_walks_text(const HostGraph &g, uint64_t n_walks, const uin
     if (gfa) head = (gfa_header ? std::string(gfa_header) : "H\tKL:Z:" + std::to_string(k)) + "\n";
     const uint64_t P = resident ? resident->n_edges : (n_walks ? limits[n_walks - 1] : 0);
     const uint64_t n_orig = g.n_original_edges, n_dummy = g.edge_count() - n_orig, U = n_orig / 2;
-    uint64_t begin = 0;
-    for (uint64_t i = 0; i < n_walks && !resident; i++) {  // the same input checks as the host path
-        if (limits[i] <= begin) MTG_DIE("empty walk %llu", (unsigned long long)i);
-        if (edges[begin] >= n_orig) MTG_DIE("walk %llu starts with a dummy edge (bin.rs:489)", (unsigned long long)i);
-        begin = limits[i];
-    }
     hipStream_t st = nullptr;
     SeqStore seq("unitig sequences", seqs, seq_off, U, st, device_id);
     char *d_out = nullptr;
