@@ -782,6 +782,44 @@ void mtg_compact_unitigs_cleaned_store(const mtg_unitigs *in, uint64_t k, uint64
 /* Of the last compaction on this thread: {ms of the decision and removal kernels over all rounds (HIP events), the rounds run}.
  * mtg_last_compact_times' nodes and rank phases include every round's. */
 void mtg_last_clean_times(double out[2]);
+/* BUBBLE POPPING. mtg_compact_unitigs_simplified is mtg_compact_unitigs_cleaned whose rounds also pop the weaker arms
+ * of simple bubbles. Over the current set T, an OPEN walk W = e_1 .. e_n has the tail node u (the prefix of e_1 as read) and the head
+ * node v (the suffix of e_n); its mirror runs from rc(v) to rc(u) and is the same arm. W is a CANDIDATE ARM iff n < max_arm_kmers,
+ * neither u nor v is its own reverse complement, u != v and u != rc(v). The candidate arms with one (u, v) are a BUNDLE. Arm a is
+ * BETTER than arm b iff sum_a n_b > sum_b n_a (sum: the abundances of the arm's k-mers), on equality the one with the smaller
+ * min(creator of e_1's k-mer, creator of e_n's k-mer). Every arm a other than the bundle's best B is POPPED iff
+ * sum_B n_a >= min_ratio sum_a n_B (exact integers; the right side is taken in 128 bits). A longer walk between u and v is in no
+ * bundle, closed walks are never touched, and an arm is never a tip or isolated: a round decides all three on one snapshot and
+ * removes their k-mers together; rounds repeat until one removes nothing or params->rounds have run.
+ * The arguments and the rungs are those of mtg_compact_unitigs_cleaned; everything returned describes the final store, so the sum
+ * of *sums is kept_occurrences - cleaning->removed_occurrences - bubbles->removed_occurrences. bubble_params == NULL, bubbles == NULL or
+ * max_arm_kmers 0 pops nothing: the call then runs the kernels of the cleaned call and nothing else. With max_arm_kmers > 0 the call
+ * must be counted (abundance and sums given) and params and cleaning must be given (params carries the rounds; both of its lengths
+ * may be 0), else it aborts; so does min_ratio outside 1 .. 255. */
+typedef struct mtg_bubble_params {
+    uint64_t max_arm_kmers; /* an arm has fewer k-mers than this; 0 = no popping */
+    uint64_t min_ratio;     /* 1 .. 255: the best arm's mean abundance is at least this many times the popped arm's */
+} mtg_bubble_params;
+typedef struct mtg_bubbles {
+    uint64_t arms;                /* arms popped over all rounds */
+    uint64_t arm_kmers;           /* their k-mers */
+    uint64_t removed_occurrences; /* the sum of those k-mers' abundances */
+} mtg_bubbles;
+void mtg_compact_unitigs_simplified(const char *data, const uint64_t *offsets, uint64_t n, uint64_t k, uint64_t min_abundance,
+                                    const uint8_t *record_colors, uint64_t n_colors, int split, const mtg_cleaning_params *params,
+                                    const mtg_bubble_params *bubble_params, int device_id, mtg_unitigs **out, mtg_compaction *stats,
+                                    mtg_abundance *abundance, mtg_abundance_sums **sums, mtg_kmer_counts **kmer_counts,
+                                    mtg_kmer_colors **kmer_colors, mtg_color_stats *color_stats, mtg_color_classes **classes,
+                                    mtg_cleaning *cleaning, mtg_bubbles *bubbles);
+void mtg_compact_unitigs_simplified_store(const mtg_unitigs *in, uint64_t k, uint64_t min_abundance, const uint8_t *record_colors,
+                                          uint64_t n_colors, int split, const mtg_cleaning_params *params,
+                                          const mtg_bubble_params *bubble_params, int device_id, mtg_unitigs **out, mtg_compaction *stats,
+                                          mtg_abundance *abundance, mtg_abundance_sums **sums, mtg_kmer_counts **kmer_counts,
+                                          mtg_kmer_colors **kmer_colors, mtg_color_stats *color_stats, mtg_color_classes **classes,
+                                          mtg_cleaning *cleaning, mtg_bubbles *bubbles);
+/* Of the last compaction on this thread: {ms of the list, sums, choose and verdict kernels over all rounds (HIP events; 0 where
+ * nothing was to be popped)}. mtg_last_clean_times leaves them out. */
+void mtg_last_bubble_times(double out[1]);
 /* mtg_read_sequences without an alphabet rule: every byte of a sequence line is kept as it is (`N`, IUPAC codes, lower case), for
  * the queries of a k-mer index. *names_out = the record names as a second store with the same accessors: the header text behind `>`
  * up to the first white space. */

@@ -37,6 +37,10 @@ their k-mers and runs, and `--unitig-color-classes-out` the classes along every 
 what a sequencing error near a read end leaves behind even above `--min-abundance` -- and `--remove-isolated L` the unitigs of fewer
 than L k-mers that touch nothing, both inside the GPU compaction and before the unitigs are formed for good; `--clean-rounds R`
 repeats that up to R times on the unitigs the round before left. Every output sees the cleaned unitigs.
+`--pop-bubbles L` (with `--seq-in`) pops simple bubbles in the same rounds: of the unitigs of fewer than L k-mers that join the same
+two nodes -- what a sequencing error in the middle of a read seen twice, or a heterozygous SNP, leaves -- the one with the largest
+mean abundance stays; a SNP's arms have k k-mers, so L = k + 1 is the least that pops them and 2 k the usual value. `--bubble-ratio R`
+pops an arm only if the best has at least R times its mean abundance, which keeps variation between samples.
 """
 from __future__ import annotations
 
@@ -136,7 +140,13 @@ def main(argv=None) -> int:
     ap.add_argument("--remove-isolated", type=int, metavar="L",
                     help="with --seq-in: remove the unitigs of fewer than L k-mers with two dead ends (L >= 1)")
     ap.add_argument("--clean-rounds", type=int, metavar="R",
-                    help="with --clip-tips / --remove-isolated: at most R rounds (1..64, default 1), each on the unitigs the one before left")
+                    help="with --clip-tips / --remove-isolated / --pop-bubbles: at most R rounds (1..64, default 1), each on the unitigs the "
+                         "one before left")
+    ap.add_argument("--pop-bubbles", type=int, metavar="L",
+                    help="with --seq-in: of the unitigs of fewer than L k-mers between the same two nodes keep the one with the largest mean "
+                         "abundance (L >= 2; k + 1 is the least that pops a SNP, 2 k the usual value; not in the reference)")
+    ap.add_argument("--bubble-ratio", type=int, metavar="R",
+                    help="with --pop-bubbles: pop an arm only if the best arm has at least R times its mean abundance (1..255, default 1)")
     args = ap.parse_args(argv)
 
     classed = bool(args.monochromatic_unitigs or args.color_classes_out or args.unitig_color_classes_out)
@@ -175,14 +185,21 @@ def main(argv=None) -> int:
                         ("--color-matrix-out", args.color_matrix_out), ("--unitig-colors-out", args.unitig_colors_out),
                         ("--monochromatic-unitigs", args.monochromatic_unitigs or None), ("--color-classes-out", args.color_classes_out),
                         ("--unitig-color-classes-out", args.unitig_color_classes_out), ("--clip-tips", args.clip_tips),
-                        ("--remove-isolated", args.remove_isolated), ("--clean-rounds", args.clean_rounds)):
+                        ("--remove-isolated", args.remove_isolated), ("--clean-rounds", args.clean_rounds),
+                        ("--pop-bubbles", args.pop_bubbles), ("--bubble-ratio", args.bubble_ratio)):
         if value is not None and args.seq_in is None:
             ap.error(f"{flag} needs --seq-in")
     if args.clip_tips is not None and args.clip_tips < 2:
         ap.error("--clip-tips must be >= 2")
     if args.remove_isolated is not None and args.remove_isolated < 1:
         ap.error("--remove-isolated must be >= 1")
-    if args.clean_rounds is not None and args.clip_tips is None and args.remove_isolated is None:
+    if args.pop_bubbles is not None and args.pop_bubbles < 2:
+        ap.error("--pop-bubbles must be >= 2")
+    if args.bubble_ratio is not None and args.pop_bubbles is None:
+        ap.error("--bubble-ratio needs --pop-bubbles")
+    if args.bubble_ratio is not None and not 1 <= args.bubble_ratio <= 255:
+        ap.error("--bubble-ratio must be in 1..255")
+    if args.clean_rounds is not None and args.clip_tips is None and args.remove_isolated is None and args.pop_bubbles is None:
         ap.error("--clean-rounds needs --clip-tips or --remove-isolated")
     if args.clean_rounds is not None and not 1 <= args.clean_rounds <= 64:
         ap.error("--clean-rounds must be in 1..64")
@@ -237,7 +254,7 @@ def _read_seq_in(api, args, fastq, record_colors=None):
 
 def _run(api, args, fastq) -> int:
     t0 = time.perf_counter()
-    cleaning = None
+    cleaning = bubbles = None
     if args.bcalm_in is not None:
         graph, store = api.read_bcalm2(args.bcalm_in, args.k)
     elif args.seq_in is not None:  # sequences -> unitigs (GPU compaction) -> graph (the --fa-in join on the same store)
@@ -246,14 +263,20 @@ def _run(api, args, fastq) -> int:
         record_colors = [] if colored else None
         seqs, pieces_cut = _read_seq_in(api, args, fastq, record_colors)
         abundance = colors = cleaning = None
-        cleaned = args.clip_tips is not None or args.remove_isolated is not None  # 
+        popping = args.pop_bubbles is not None  # 
+        cleaned = args.clip_tips is not None or args.remove_isolated is not None or popping  # 
         per_kmer = bool(args.query_abundance_out or args.unitig_kmer_abundance_out)  # 
         counted = not (args.min_abundance is None and not (args.kmer_spectrum_out or args.unitig_abundance_out or per_kmer))
         if not counted and not colored and not cleaned:
             store, compaction = api.compact_unitigs(seqs, args.k, args.device)
         else:  # the counted compaction; an output flag alone counts without filtering
             min_abundance = args.min_abundance or 1
-            if cleaned:  # (whichever of the calls below it would have been, with the rounds in front of the final pass)
+            if popping:  # (the cleaned call whose rounds pop bubbles too)
+                store, compaction, abundance, colors, classes, cleaning, bubbles = api.compact_unitigs_simplified(
+                    seqs, args.k, args.pop_bubbles, args.bubble_ratio or 1, args.clip_tips or 0, args.remove_isolated or 0, args.clean_rounds or 1,
+                    min_abundance, record_colors if colored else None, len(args.seq_in) if colored else 0, bool(args.monochromatic_unitigs),
+                    per_kmer, args.device)
+            elif cleaned:  # (whichever of the calls below it would have been, with the rounds in front of the final pass)
                 store, compaction, abundance, colors, classes, cleaning = api.compact_unitigs_cleaned(
                     seqs, args.k, args.clip_tips or 0, args.remove_isolated or 0, args.clean_rounds or 1, min_abundance,
                     record_colors if colored else None, len(args.seq_in) if colored else 0, bool(args.monochromatic_unitigs), per_kmer, args.device)
@@ -273,7 +296,8 @@ def _run(api, args, fastq) -> int:
                 print(f"no k-mer reaches --min-abundance {min_abundance} ({abundance.describe()})", file=sys.stderr)
                 return 1
             if len(store) == 0:
-                print(f"nothing is left after cleaning ({cleaning.describe()}; {abundance.describe()})", file=sys.stderr)
+                print(f"nothing is left after cleaning ({cleaning.describe()}; {bubbles.describe() + '; ' if bubbles is not None else ''}"
+                      f"{abundance.describe()})", file=sys.stderr)
                 return 1
             if args.unitig_abundance_out:
                 _write_unitig_abundance(args, store, abundance)
@@ -298,6 +322,7 @@ def _run(api, args, fastq) -> int:
         loaded += f"cut into {compaction.unitigs} monochromatic unitigs; " if args.monochromatic_unitigs else ""
         loaded += f"{abundance.describe()}; " if abundance is not None and counted else ""
         loaded += f"{cleaning.describe()}; " if cleaning is not None else ""
+        loaded += f"{bubbles.describe()}; " if bubbles is not None else ""
         loaded += f"{pieces_cut} non-ACGT runs cut)"
     print(loaded, file=sys.stderr)
     # what the tigs are verified against: the input as given -- on the --seq-in route the sequences, so that the check covers the compaction
@@ -305,7 +330,7 @@ def _run(api, args, fastq) -> int:
     filtered = args.seq_in is not None and abundance is not None and min_abundance > 1
     if filtered or cleaning is not None:  # the tigs spell S_m less what the cleaning took, not the input's set: they are held to the
         truth = store                     # unitigs, and the unitigs to the input (below)
-    cleaned_away = cleaning.removed_kmers if cleaning is not None else 0
+    cleaned_away = (cleaning.removed_kmers if cleaning is not None else 0) + (bubbles.arm_kmers if bubbles is not None else 0)
 
     def report(what: str, tigs, cmp) -> bool:
         """The verification line of one tig set; names the first missing and the first foreign k-mer when there is one."""
@@ -332,7 +357,8 @@ def _run(api, args, fastq) -> int:
         if cleaning is not None:
             print(f"Verifying cleaning: {cmp.distinct_b} of the input's {cmp.distinct_a} distinct k-mers are in the unitigs, "
                   f"{cmp.only_in_a} are not ({abundance.dropped} dropped by the filter, {cleaning.tip_kmers} in tips, "
-                  f"{cleaning.isolated_kmers} in isolated unitigs), {cmp.only_in_b} foreign: {'as counted' if ok else 'MISMATCH'}", file=sys.stderr)
+                  f"{cleaning.isolated_kmers} in isolated unitigs{f', {bubbles.arm_kmers} in bubble arms' if bubbles is not None else ''}), "
+                  f"{cmp.only_in_b} foreign: {'as counted' if ok else 'MISMATCH'}", file=sys.stderr)
         all_equal &= ok
     for path in args.verify_fa or ():
         tigs = api.read_sequences(path)

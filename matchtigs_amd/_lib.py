@@ -118,6 +118,21 @@ class MtgCleaning(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class MtgBubbleParams(C.Structure):
+    """mtg_bubble_params (include/mtg_engine.h)."""
+
+    _fields_ = [(n, C.c_uint64) for n in ("max_arm_kmers", "min_ratio")]
+
+
+class MtgBubbles(C.Structure):
+    """mtg_bubbles (include/mtg_engine.h)."""
+
+    _fields_ = [(n, C.c_uint64) for n in ("arms", "arm_kmers", "removed_occurrences")]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class MtgColorStats(C.Structure):
     """mtg_color_stats (include/mtg_engine.h)."""
 
@@ -325,6 +340,13 @@ def load():
         "mtg_compact_unitigs_cleaned_store": (None, [vp, u64, u64, vp, u64, C.c_int, P(MtgCleaningParams), C.c_int, P(vp), P(MtgCompaction),
                                                      P(MtgAbundance), P(vp), P(vp), P(vp), P(MtgColorStats), P(vp), P(MtgCleaning)]),
         "mtg_last_clean_times": (None, [P(C.c_double)]),
+        "mtg_compact_unitigs_simplified": (None, [vp, vp, u64, u64, u64, vp, u64, C.c_int, P(MtgCleaningParams), P(MtgBubbleParams), C.c_int, P(vp),
+                                                  P(MtgCompaction), P(MtgAbundance), P(vp), P(vp), P(vp), P(MtgColorStats), P(vp), P(MtgCleaning),
+                                                  P(MtgBubbles)]),
+        "mtg_compact_unitigs_simplified_store": (None, [vp, u64, u64, vp, u64, C.c_int, P(MtgCleaningParams), P(MtgBubbleParams), C.c_int, P(vp),
+                                                        P(MtgCompaction), P(MtgAbundance), P(vp), P(vp), P(vp), P(MtgColorStats), P(vp),
+                                                        P(MtgCleaning), P(MtgBubbles)]),
+        "mtg_last_bubble_times": (None, [P(C.c_double)]),
         "mtg_color_classes_build": (None, [vp, u64, vp, u64, C.c_int, P(vp)]),
         "mtg_color_classes_count": (u64, [vp]),
         "mtg_color_classes_masks": (vp, [vp]),

@@ -1134,10 +1134,10 @@ def compact_unitigs_cleaned(seqs_or_store, k: int, clip_tips: int = 0, remove_is
         if split:
             raise ValueError("split needs record_colors")
         return _compact(_COUNTED_KMERS if kmer_counts else _COUNTED, seqs_or_store, k, device_id, min_abundance,
-                        cleaning=(int(clip_tips), int(remove_isolated), int(rounds)))
+                        cleaning=(int(clip_tips), int(remove_isolated), int(rounds)))[:6]
     rc = _record_colors(record_colors, n_colors, _record_count(seqs_or_store))
     return _compact(_CLASSES, seqs_or_store, k, device_id, min_abundance, rc, int(n_colors), split,
-                    cleaning=(int(clip_tips), int(remove_isolated), int(rounds)))
+                    cleaning=(int(clip_tips), int(remove_isolated), int(rounds)))[:6]
 
 
 def last_clean_times() -> dict:
@@ -1148,6 +1148,60 @@ def last_clean_times() -> dict:
     return {"clean_ms": float(out[0]), "rounds_run": int(out[1])}
 
 
+@dataclass(frozen=True)
+class Bubbles:
+    """mtg_bubbles (include/mtg_engine.h): what the rounds of a simplified compaction popped, in exact integers. An arm
+    is an open unitig of fewer than pop_bubbles k-mers between two nodes that another such unitig joins too; of the arms between
+    one pair of nodes the one with the largest mean abundance stays (ties: the earliest creator at an end), and another goes iff
+    the best has at least bubble_ratio times its mean abundance."""
+
+    arms: int
+    arm_kmers: int
+    removed_occurrences: int
+
+    def describe(self) -> str:
+        return f"{self.arms} bubble arms of {self.arm_kmers} k-mers popped"
+
+
+MAX_BUBBLE_RATIO = 255
+
+
+def compact_unitigs_simplified(seqs_or_store, k: int, pop_bubbles: int = 0, bubble_ratio: int = 1, clip_tips: int = 0, remove_isolated: int = 0,
+                               rounds: int = 1, min_abundance: int = 1, record_colors=None, n_colors: int = 0, split: bool = False,
+                               kmer_counts: bool = False, device_id: int = 0):
+    """compact_unitigs_cleaned whose rounds also pop the weaker arms of simple bubbles (mtg_compact_unitigs_simplified) ->
+    (UnitigStore, Compaction, Abundance, Colors | None, ColorClasses | None, Cleaning, Bubbles). pop_bubbles = L looks at the open
+    unitigs of fewer than L k-mers (0: off; a SNP's arms have k k-mers, so k + 1 is the least L that pops them and 2 k the usual
+    value); bubble_ratio = R pops an arm only if the best arm between the same two nodes has at least R times its mean abundance
+    (1: every arm but the best goes). Tips, isolated unitigs and arms of a round are decided on one snapshot and leave together.
+    Everything describes the final store: unitig_sums.sum() == kept_occurrences - Cleaning.removed_occurrences -
+    Bubbles.removed_occurrences. With pop_bubbles = 0 the first six entries are compact_unitigs_cleaned's."""
+    for name, v, lo, hi in (("pop_bubbles", pop_bubbles, 0, 2 ** 64 - 1), ("bubble_ratio", bubble_ratio, 1, MAX_BUBBLE_RATIO),
+                            ("clip_tips", clip_tips, 0, 2 ** 64 - 1), ("remove_isolated", remove_isolated, 0, 2 ** 64 - 1),
+                            ("rounds", rounds, 1, MAX_CLEAN_ROUNDS)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+            raise ValueError(f"{name} must be an integer in {lo}..{hi}, not {v!r}")
+    if min_abundance < 1:
+        raise ValueError("min_abundance must be >= 1")
+    if not isinstance(split, (bool, np.bool_)):
+        raise ValueError(f"split must be True or False, not {split!r}")
+    cleaning, bubbles = (int(clip_tips), int(remove_isolated), int(rounds)), (int(pop_bubbles), int(bubble_ratio))
+    if record_colors is None:
+        if split:
+            raise ValueError("split needs record_colors")
+        return _compact(_COUNTED_KMERS if kmer_counts else _COUNTED, seqs_or_store, k, device_id, min_abundance, cleaning=cleaning, bubbles=bubbles)
+    rc = _record_colors(record_colors, n_colors, _record_count(seqs_or_store))
+    return _compact(_CLASSES, seqs_or_store, k, device_id, min_abundance, rc, int(n_colors), split, cleaning=cleaning, bubbles=bubbles)
+
+
+def last_bubble_times() -> dict:
+    """Of the last compaction on this thread: the ms of the bubble kernels (list, sums, choose, verdict) over all rounds, by HIP
+    events; 0.0 where nothing was to be popped. last_clean_times leaves them out."""
+    out = (C.c_double * 1)()
+    _lib.load().mtg_last_bubble_times(out)
+    return {"bubble_ms": float(out[0])}
+
+
 # The rungs of the compaction ladder and the C symbol each reaches (+ "_store" for a UnitigStore). The argument list of a rung is
 # the one below it plus its own (_compact): a new rung is one row here and one `if` there.
 _PLAIN, _COUNTED, _COUNTED_KMERS, _COLORED, _CLASSES = range(5)
@@ -1156,10 +1210,11 @@ _COMPACT_SYMBOLS = ("mtg_compact_unitigs", "mtg_compact_unitigs_counted", "mtg_c
 
 
 def _compact(rung: int, seqs_or_store, k: int, device_id: int, min_abundance: int = 1, record_colors=None, n_colors: int = 0,
-             split: bool = False, cleaning=None):
-    """The one body of compact_unitigs* -> (UnitigStore, Compaction, Abundance, Colors, ColorClasses, Cleaning), None above the rung.
-    cleaning: None, or (clip_tips, remove_isolated, rounds) -- the call then goes through mtg_compact_unitigs_cleaned, which takes
-    the arguments of every rung and null out-pointers above the one asked for. The arguments are the callers' to check."""
+             split: bool = False, cleaning=None, bubbles=None):
+    """The one body of compact_unitigs* -> (UnitigStore, Compaction, Abundance, Colors, ColorClasses, Cleaning, Bubbles), None above the
+    rung. cleaning: None, or (clip_tips, remove_isolated, rounds) -- the call then goes through mtg_compact_unitigs_cleaned, which takes
+    the arguments of every rung and null out-pointers above the one asked for; bubbles: None, or (pop_bubbles, bubble_ratio) beside
+    a cleaning -- then through mtg_compact_unitigs_simplified. The arguments are the callers' to check."""
     L = _lib.load()
     out, sums, counts, masks, classes = (C.c_void_p() for _ in range(5))
     stats, ab, cs = _lib.MtgCompaction(), _lib.MtgAbundance(), _lib.MtgColorStats()
@@ -1179,12 +1234,18 @@ def _compact(rung: int, seqs_or_store, k: int, device_id: int, min_abundance: in
             outs += [C.byref(classes)]
         ins += [device_id]
     else:
-        symbol = "mtg_compact_unitigs_cleaned"
+        symbol = "mtg_compact_unitigs_cleaned" if bubbles is None else "mtg_compact_unitigs_simplified"
         params, cleaned = _lib.MtgCleaningParams(*cleaning), _lib.MtgCleaning()
-        ins = [k, min_abundance, _ptr(record_colors) if rung >= _COLORED else None, n_colors, int(bool(split)), C.byref(params), device_id]
+        ins = [k, min_abundance, _ptr(record_colors) if rung >= _COLORED else None, n_colors, int(bool(split)), C.byref(params)]
+        if bubbles is not None:
+            bubble_params, popped = _lib.MtgBubbleParams(*bubbles), _lib.MtgBubbles()
+            ins += [C.byref(bubble_params)]
+        ins += [device_id]
         outs = [C.byref(out), C.byref(stats), C.byref(ab), C.byref(sums), C.byref(counts) if rung >= _COUNTED_KMERS else None,
                 C.byref(masks) if rung >= _COLORED else None, C.byref(cs) if rung >= _COLORED else None,
                 C.byref(classes) if rung >= _CLASSES else None, C.byref(cleaned)]
+        if bubbles is not None:
+            outs += [C.byref(popped)]
     if isinstance(seqs_or_store, UnitigStore):
         getattr(L, symbol + "_store")(seqs_or_store.handle, *ins, *outs)
     else:
@@ -1210,7 +1271,7 @@ def _compact(rung: int, seqs_or_store, k: int, device_id: int, min_abundance: in
         L.mtg_kmer_colors_free(masks)
         L.mtg_color_classes_free(classes)
     return (UnitigStore(out.value), Compaction(**stats.as_dict()), abundance, colors, cc,
-            Cleaning(**cleaned.as_dict()) if cleaning is not None else None)
+            Cleaning(**cleaned.as_dict()) if cleaning is not None else None, Bubbles(**popped.as_dict()) if bubbles is not None else None)
 
 
 def last_color_class_times() -> dict:

@@ -81,8 +81,25 @@
 // of being freed in front of rank; 2 N verdict bytes, 4 N keep flags; then, with table, succ and pairs freed, 4 N new ids and the
 // second copy of kpos / kcount / kcolor (8 + 4 + 8 B per survivor).
 //
+// Simplified calls (mtg_compact_unitigs_simplified): a round also pops the weaker arms of simple bubbles, between
+// clean_decide_kernel and clean_keep_kernel and on the same snapshot. An arm is an open walk of fewer than L_bub k-mers from its tail
+// node u to its head node v (no self-mirror end, u != v, u != rc(v)); the arms with one (u, v) form a bundle, the mirror counting
+// once; the best arm has the largest mean abundance (sum_a n_b > sum_b n_a), then the smallest end k-mer id; another arm a goes iff
+// sum_B n_a >= R sum_a n_B. bubble_flag_kernel: the threads of clean_decide_kernel's entry condition whose walk is short flag the smaller
+// of the walk pair's two first elements; the scan numbers the M list slots. bubble_list_kernel: two find_node<false> probes per short
+// walk end give the oriented node ids (2 slot + orientation: 34 bits each, so a key is two 64-bit words), and the thread with the
+// smaller of the two mirror keys fills the slot. bubble_counts_kernel: every k-mer of an arm writes its count at the arm's offset (the
+// scan of the lengths) + its rank -- no thread walks an arm --, a 64-bit scan and bubble_sums_kernel give the sums by differences.
+// bubble_choose_kernel: open addressing over 2 M 32-bit table slots, a CAS loop that replaces a key's arm only by a better one, so the
+// table ends at the maxima. bubble_verdict_kernel: every arm that is not its key's best and passes the ratio test (right side in 128
+// bits) writes VERDICT_BUBBLE at its own first element and its mirror's, and counts itself once. clean_keep_kernel<true> counts arm
+// k-mers and occurrences apart. With max_arm_kmers 0 none of this runs and clean_keep_kernel<false> is the cleaned call's kernel.
+// Memory added while a round pops: 8 N (flags / list slots per oriented k-mer), 44 B per list slot (36 entry + 8 table), 12 B per
+// k-mer of a candidate arm (4 ordered count + 8 prefix); all freed before the keep flags are scanned.
+//
 // All of these enter through device_compact_unitigs(CompactRequest) (device.hpp): one rung of the ladder per pointer of the request --
-// Counted, Colored, Classed --, null where the call does not climb that far; Cleaned stands beside the ladder and goes with any rung.
+// Counted, Colored, Classed --, null where the call does not climb that far; Cleaned stands beside the ladder and goes with any rung,
+// Bubbled beside a Cleaned and a Counted.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -407,9 +424,10 @@ __global__ __launch_bounds__(hu::EB) void walk_kernel(const unsigned long long *
     }
 }
 // ---- tip clipping and isolated unitigs (cleaned calls) ----
-// counters of one round: [0] tips, [1] isolated walks, [2] tip k-mers, [3] isolated k-mers, [4] removed occurrences
-constexpr int CLEAN_COUNTERS = 5;
-constexpr uint8_t VERDICT_TIP = 1, VERDICT_ISOLATED = 2;
+// counters of one round: [0] tips, [1] isolated walks, [2] tip k-mers, [3] isolated k-mers, [4] removed occurrences; of a round that
+// pops bubbles also [5] arm k-mers, [6] their occurrences, [7] popped arms
+constexpr int CLEAN_COUNTERS = 8;
+constexpr uint8_t VERDICT_TIP = 1, VERDICT_ISOLATED = 2, VERDICT_BUBBLE = 3;
 enum EndState : int { END_FREE = 0, END_ANCHORED = 1, END_THROUGH = 2 };
 
 // 0, 1 or 2 (= two or more) incident edges
@@ -475,22 +493,184 @@ __global__ __launch_bounds__(hu::EB) void clean_decide_kernel(NodeArgs a, const 
     }
     block_add<2>(c, counters);
 }
+
+// ---- bubble popping (simplified calls) ----
+// A short open walk W = e_1 .. e_n (n < L_bub) from its tail node u (the prefix of e_1 as read) to its head node v (the suffix of
+// e_n) is a candidate ARM unless u or v is self-mirror, u = v or u = rc(v); the arms with one (u, v) form a BUNDLE, an arm and its
+// mirror (from rc(v) to rc(u)) counting once. An ORIENTED NODE ID is 2 * (the class's slot in the node table) + (the node is the
+// reverse complement of the class's canonical form): rc(x) has id(x) ^ 1, and the exclusions read "u or v self-mirror, or one slot".
+// Slots reach 2^33, so the two ids of a key do not fit one 64-bit word: a key is kept as two words (tail, head), the table of the
+// choose step holds 32-bit LIST SLOTS and compares the keys behind them.
+// The list of a round has one slot per short open walk, the walk and its mirror counting once: bubble_flag_kernel flags the
+// smaller of the two walks' first elements (e_1 and mirror(e_n)), the scan of the flags numbers the slots (M of them), and of the
+// two threads at the walks' ends the one whose key (tail, head) is the lexicographically smaller of (u, v) and (rc(v), rc(u)) fills
+// the slot -- the keys are equal only in the excluded hairpin case. An excluded walk leaves its slot a hole (n = 0).
+struct ArmArgs {
+    unsigned long long *tail, *head;  // [M] oriented node ids
+    uint32_t *first, *last;           // [M] e_1 and e_n of the walk whose thread made the entry
+    uint32_t *n;                      // [M] the arm's k-mers; 0: a hole
+    uint32_t *off;                    // [M] the exclusive scan of n: the arm's place among the K k-mers of all arms
+    uint32_t *sum;                    // [M] the sum of the arm's abundances (below 2^32: fewer than 2^32 windows)
+    uint32_t *table;                  // [slots] a list slot of the best arm seen of a key, or none
+    uint64_t M, slots;
+};
+
+// the end element o of an open walk shorter than max_arm: its first element, else none
+__device__ __forceinline__ uint32_t short_walk_first(const uint32_t *succ, const unsigned long long *pairs, uint64_t o, uint64_t max_arm, uint64_t *len) {
+    if (succ[o] != NONE32) return NONE32;
+    const uint64_t pr = pairs[o];
+    const uint32_t first = (uint32_t)pr == NONE32 ? (uint32_t)o : (uint32_t)pr;
+    *len = (pr >> 32) + 1;
+    return *len < max_arm && succ[first ^ 1u] == NONE32 ? first : NONE32;
+}
+// flag[min(e_1, mirror(e_n))] = 1 per short open walk; written by the one of the two end threads whose e_1 is the smaller (a walk is
+// never its own mirror: the two differ)
+__global__ __launch_bounds__(hu::EB) void bubble_flag_kernel(const uint32_t *succ, const unsigned long long *pairs, uint64_t n, uint64_t max_arm, uint32_t *flag) {
+    const uint64_t o = hu::gid();
+    if (o >= n) return;
+    uint64_t len;
+    const uint32_t first = short_walk_first(succ, pairs, o, max_arm, &len);
+    if (first != NONE32 && first < ((uint32_t)o ^ 1u)) flag[first] = 1u;
+}
+// slot_of: the exclusive scan of the flags. The two probes give the ids; the thread with the smaller key fills the slot.
+__global__ __launch_bounds__(hu::EB) void bubble_list_kernel(NodeArgs a, const unsigned long long *pairs, uint64_t n, uint64_t max_arm, const uint32_t *slot_of,
+                                                              ArmArgs b, unsigned int *err) {
+    const uint64_t o = hu::gid();
+    if (o >= n) return;
+    uint64_t len;
+    const uint32_t first = short_walk_first(a.succ, pairs, o, max_arm, &len);
+    if (first == NONE32) return;
+    kw::ClassKey key;
+    // v: the suffix of the reading (o even) or the reverse complement of its prefix; u: the prefix of e_1's reading or rc(its suffix)
+    const uint64_t sv = find_node<false>(a, a.kpos[o >> 1] + ((o & 1u) ? 0 : 1), key, err);
+    const bool pal_v = key.pal;
+    const uint64_t head = 2 * sv + (uint64_t)(key.flip != (bool)(o & 1u));
+    const uint64_t su = find_node<false>(a, a.kpos[first >> 1] + ((first & 1u) ? 1 : 0), key, err);
+    const uint64_t tail = 2 * su + (uint64_t)(key.flip != (bool)(first & 1u));
+    if (pal_v || key.pal || su == sv) return;  // a self-mirror end; u = v (a loop at one node); u = rc(v) (a hairpin)
+    if (tail > (head ^ 1ull)) return;          // the mirror key (rc(v), rc(u)) is the smaller: its thread makes the entry
+    const uint32_t mf = (uint32_t)o ^ 1u;      // (the first elements cannot be equal: tail = head ^ 1 means one slot)
+    const uint32_t e = slot_of[first < mf ? first : mf];
+    if (e >= b.M) return;  // (never: that element was flagged)
+    b.tail[e] = tail;
+    b.head[e] = head;
+    b.first[e] = first;
+    b.last[e] = (uint32_t)o;
+    b.n[e] = (uint32_t)len;
+}
+// Every k-mer of an arm writes its abundance at off[arm] + its rank on the entry's walk: no thread walks a chain. The k-mer's two
+// orientations lie on the walk and its mirror at ranks r and n - 1 - r, so n = rank(2 i) + rank(2 i + 1) + 1 without a lookup, and
+// only the k-mers of short walks look for a list slot: the one flagged at the smaller of their two heads.
+__global__ __launch_bounds__(hu::EB) void bubble_counts_kernel(const unsigned long long *pairs, const uint32_t *kcount, uint64_t N, uint64_t max_arm,
+                                                                const uint32_t *slot_of, ArmArgs b, uint32_t *ordered) {
+    const uint64_t i = hu::gid();
+    if (i >= N) return;
+    const uint64_t p0 = pairs[2 * i], p1 = pairs[2 * i + 1];
+    if ((p0 >> 32) + (p1 >> 32) + 1 >= max_arm) return;
+    const uint32_t h0 = (uint32_t)p0 == NONE32 ? (uint32_t)(2 * i) : (uint32_t)p0, h1 = (uint32_t)p1 == NONE32 ? (uint32_t)(2 * i + 1) : (uint32_t)p1;
+    const uint32_t at = h0 < h1 ? h0 : h1, e = slot_of[at];
+    if (e >= b.M || b.n[e] == 0) return;  // (a closed walk's ranks may look short: its heads hold no slot) / a hole
+    const uint32_t f = b.first[e], mf = b.last[e] ^ 1u;
+    if ((f < mf ? f : mf) != at) return;  // the slot flagged at `at` and no earlier one
+    const uint32_t rank = (uint32_t)((h0 == f ? p0 : p1) >> 32);
+    if (rank < b.n[e]) ordered[b.off[e] + rank] = kcount[i];  // (always: the guard keeps the write inside the arm's range)
+}
+// prefix: the exclusive scan of `ordered` to 64 bits, *total its end
+__global__ __launch_bounds__(hu::EB) void bubble_sums_kernel(ArmArgs b, const unsigned long long *prefix, const unsigned long long *total, uint64_t K) {
+    const uint64_t e = hu::gid();
+    if (e >= b.M || b.n[e] == 0) return;
+    const uint64_t lo = b.off[e], hi = lo + b.n[e];
+    b.sum[e] = (uint32_t)((hi < K ? prefix[hi] : *total) - prefix[lo]);
+}
+
+__device__ __forceinline__ uint64_t arm_hash(uint64_t tail, uint64_t head) { return kw::mix64(kw::mix64(tail) + head); }
+// The order inside a bundle: the larger mean abundance (sum_x n_y > sum_y n_x, below 2^63: exact in 64 bits), then the smaller of
+// the two end k-mers' ids (ids are in creator order; arms of one bundle share no k-mer, so the order is total; both are the same on
+// either strand).
+__device__ __forceinline__ bool arm_better(const ArmArgs &b, uint32_t x, uint32_t y) {
+    const uint64_t l = (uint64_t)b.sum[x] * b.n[y], r = (uint64_t)b.sum[y] * b.n[x];
+    if (l != r) return l > r;
+    const uint32_t tx = b.first[x] < b.last[x] ? b.first[x] : b.last[x], ty = b.first[y] < b.last[y] ? b.first[y] : b.last[y];
+    return (tx >> 1) < (ty >> 1);
+}
+// Open addressing over 2 M table slots, linear probing from the key's hash. An empty slot is claimed by CAS; a claimed slot keeps its
+// key for good (it is only ever replaced by a better arm of the same key), so every key owns one slot, and the CAS loop replaces
+// the slot's arm only by a better one: the final state is the bundle's maximum in any interleaving.
+__global__ __launch_bounds__(hu::EB) void bubble_choose_kernel(ArmArgs b, unsigned int *err) {
+    const uint64_t g = hu::gid();
+    if (g >= b.M || b.n[g] == 0) return;
+    const uint32_t e = (uint32_t)g;
+    const uint64_t tail = b.tail[e], head = b.head[e];
+    uint64_t s = __umul64hi(arm_hash(tail, head), b.slots);
+    for (uint64_t probe = 0; probe < b.slots; probe++) {
+        uint32_t cur = __hip_atomic_load(&b.table[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (cur == NONE32) {
+            cur = atomicCAS(&b.table[s], NONE32, e);
+            if (cur == NONE32) return;
+        }
+        if (b.tail[cur] == tail && b.head[cur] == head) {
+            while (arm_better(b, e, cur)) {
+                const uint32_t prev = atomicCAS(&b.table[s], cur, e);
+                if (prev == cur) return;
+                cur = prev;
+            }
+            return;
+        }
+        if (++s == b.slots) s = 0;
+    }
+    atomicOr(err, 32u);  // (2 table slots per arm: never full)
+}
+// Every arm that is not its bundle's best B and has sum_B n_a >= R sum_a n_B is popped: the verdict goes to the first elements of
+// its walk and of the mirror walk, the arm is counted once. R sum_a < 2^40 and n_B < 2^31: the right side is taken in 128 bits.
+__global__ __launch_bounds__(hu::EB) void bubble_verdict_kernel(ArmArgs b, uint64_t ratio, uint8_t *verdict, unsigned long long *arms, unsigned int *err) {
+    const uint64_t g = hu::gid();
+    unsigned long long c[1] = {0};
+    if (g < b.M && b.n[g] != 0) {
+        const uint32_t e = (uint32_t)g;
+        const uint64_t tail = b.tail[e], head = b.head[e];
+        uint64_t s = __umul64hi(arm_hash(tail, head), b.slots);
+        uint32_t best = NONE32;
+        for (uint64_t probe = 0; probe < b.slots && best == NONE32; probe++) {
+            const uint32_t cur = b.table[s];
+            if (cur == NONE32) break;
+            if (b.tail[cur] == tail && b.head[cur] == head) best = cur;
+            if (++s == b.slots) s = 0;
+        }
+        if (best == NONE32) {
+            atomicOr(err, 32u);  // (every arm's key was put in)
+        } else if (best != e) {
+            const uint64_t left = (uint64_t)b.sum[best] * b.n[e], m = ratio * b.sum[e];
+            if (__umul64hi(m, (uint64_t)b.n[best]) == 0 && left >= m * b.n[best]) {
+                verdict[b.first[e]] = VERDICT_BUBBLE;
+                verdict[b.last[e] ^ 1u] = VERDICT_BUBBLE;
+                c[0] = 1;
+            }
+        }
+    }
+    block_add<1>(c, arms);
+}
+
 // keep[i] = 0 where the walk of k-mer i has a verdict (read at the first element of the reading's walk: the mirror walk holds the
-// same); the removed k-mers and their abundances are counted on the way (kcount: null in a call that does not count)
+// same); the removed k-mers and their abundances are counted on the way (kcount: null in a call that does not count). POP: popped
+// arms' k-mers and occurrences go to counters of their own.
+template <bool POP>
 __global__ __launch_bounds__(hu::EB) void clean_keep_kernel(const unsigned long long *pairs, const uint8_t *verdict, const uint32_t *kcount, uint64_t N,
                                                              uint32_t *keep, unsigned long long *counters) {
     const uint64_t i = hu::gid();
-    unsigned long long c[3] = {0, 0, 0};  // tip k-mers, isolated k-mers, removed occurrences
+    unsigned long long c[POP ? 5 : 3] = {};  // tip k-mers, isolated k-mers, their occurrences [, arm k-mers, their occurrences]
     if (i < N) {
         const uint32_t j = (uint32_t)pairs[2 * i];
         const uint8_t v = verdict[j == NONE32 ? 2 * i : j];
         keep[i] = v == 0;
-        if (v) {
+        if (POP && v == VERDICT_BUBBLE) {
+            c[POP ? 3 : 0] = 1;
+            c[POP ? 4 : 0] = kcount[i];
+        } else if (v) {
             c[v - 1] = 1;
             c[2] = kcount ? kcount[i] : 0;
         }
     }
-    block_add<3>(c, counters + 2);
+    block_add<POP ? 5 : 3>(c, counters + 2);
 }
 // the kept k-mers move to their new ids (new_id: the exclusive scan of keep -- creator order is kept)
 __global__ __launch_bounds__(hu::EB) void clean_move_kernel(const uint32_t *keep, const uint32_t *new_id, uint64_t N, const unsigned long long *kpos,
@@ -799,10 +979,64 @@ void color_classes(const unsigned long long *d_ordered, const unsigned long long
         hu::device_free(p);
 }
 
+// The bubble verdicts of one round over the N k-mers behind `na` (node table, succ) and `pairs`: list, sums, choose, verdict.
+// verdict: [2 N], written only where an arm is popped; *arms += the popped arms. Leaves the stream idle.
+void pop_bubbles(const NodeArgs &na, const unsigned long long *d_pairs, const uint32_t *d_kcount, const mtg_bubble_params &p, uint8_t *d_verdict,
+                 unsigned long long *d_arms, unsigned int *d_err, hipStream_t st) {
+    const uint64_t N = na.N, n_or = 2 * N;
+    uint32_t *d_slot_of = nullptr, *d_bsum = nullptr;
+    hu::device_malloc(&d_slot_of, n_or * 4);
+    hu::device_malloc(&d_bsum, (hu::scan_blocks(n_or) + 2) * 4);
+    uint32_t *d_total = d_bsum + hu::scan_blocks(n_or) + 1;
+    HIP_CHECK(hipMemsetAsync(d_slot_of, 0, n_or * 4, st));
+    bubble_flag_kernel<<<hu::grid_for(n_or), hu::EB, 0, st>>>(na.succ, d_pairs, n_or, p.max_arm_kmers, d_slot_of);
+    hu::scan_u32<uint32_t>(st, d_slot_of, n_or, d_slot_of, d_bsum, d_total);
+    uint32_t M = 0, K = 0;
+    HIP_CHECK(hipMemcpyAsync(&M, d_total, 4, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    ArmArgs b{};
+    b.M = M;
+    if (M) {
+        hu::device_malloc(&b.tail, (uint64_t)M * 8);
+        hu::device_malloc(&b.head, (uint64_t)M * 8);
+        hu::device_malloc(&b.first, (uint64_t)M * 4);
+        hu::device_malloc(&b.last, (uint64_t)M * 4);
+        hu::device_malloc(&b.n, (uint64_t)M * 4);
+        hu::device_malloc(&b.off, (uint64_t)M * 4);
+        HIP_CHECK(hipMemsetAsync(b.n, 0, (uint64_t)M * 4, st));
+        bubble_list_kernel<<<hu::grid_for(n_or), hu::EB, 0, st>>>(na, d_pairs, n_or, p.max_arm_kmers, d_slot_of, b, d_err);
+        hu::scan_u32<uint32_t>(st, b.n, M, b.off, d_bsum, d_total);  // (M <= N: the block sums fit; K <= N < 2^31)
+        HIP_CHECK(hipMemcpyAsync(&K, d_total, 4, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+    }
+    if (K) {
+        uint32_t *d_ordered = nullptr;
+        unsigned long long *d_prefix = nullptr, *d_bsum64 = nullptr;
+        b.slots = std::max<uint64_t>(8, 2 * (uint64_t)M);
+        hu::device_malloc(&d_ordered, (uint64_t)K * 4);
+        hu::device_malloc(&d_prefix, (uint64_t)K * 8);
+        hu::device_malloc(&d_bsum64, (hu::scan_blocks(K) + 2) * 8);
+        hu::device_malloc(&b.sum, (uint64_t)M * 4);
+        hu::device_malloc(&b.table, b.slots * 4);
+        unsigned long long *d_sum_total = d_bsum64 + hu::scan_blocks(K) + 1;
+        HIP_CHECK(hipMemsetAsync(d_ordered, 0, (uint64_t)K * 4, st));
+        HIP_CHECK(hipMemsetAsync(b.table, 0xFF, b.slots * 4, st));
+        bubble_counts_kernel<<<hu::grid_for(N), hu::EB, 0, st>>>(d_pairs, d_kcount, N, p.max_arm_kmers, d_slot_of, b, d_ordered);
+        hu::scan_u32<unsigned long long>(st, d_ordered, K, d_prefix, d_bsum64, d_sum_total);
+        bubble_sums_kernel<<<hu::grid_for(M), hu::EB, 0, st>>>(b, d_prefix, d_sum_total, K);
+        bubble_choose_kernel<<<hu::grid_for(M), hu::EB, 0, st>>>(b, d_err);
+        bubble_verdict_kernel<<<hu::grid_for(M), hu::EB, 0, st>>>(b, p.min_ratio, d_verdict, d_arms, d_err);
+        HIP_CHECK(hipGetLastError());
+        for (const void *q : std::initializer_list<const void *>{d_ordered, d_prefix, d_bsum64, b.sum, b.table}) hu::device_free(q);
+    }
+    HIP_CHECK(hipGetLastError());
+    for (const void *q : std::initializer_list<const void *>{d_slot_of, d_bsum, b.tail, b.head, b.first, b.last, b.n, b.off}) hu::device_free(q);
+}
+
 // counted == nullptr: the plain compaction
 // colored != nullptr: counted too
 UnitigStore *compact(const char *data, const uint64_t *off, uint64_t n_rec, uint64_t k, int device_id, mtg_compaction *stats_out, CompactTimes *times,
-                     const Counted *counted, const Colored *colored = nullptr, const Classed *classed = nullptr, const Cleaned *cleaned = nullptr) {
+                     const Counted *counted, const Colored *colored = nullptr, const Classed *classed = nullptr, const Cleaned *cleaned = nullptr, const Bubbled *bubbles = nullptr) {
     if (!off || (n_rec && off[n_rec] && !data)) MTG_DIE("mtg_compact_unitigs: null argument");
     if (k < 2) MTG_DIE("mtg_compact_unitigs: k must be >= 2");
     if (k >= (1ull << 31)) MTG_DIE("mtg_compact_unitigs: k too large");
@@ -846,9 +1080,17 @@ UnitigStore *compact(const char *data, const uint64_t *off, uint64_t n_rec, uint
     }
     if (cleaned && (cleaned->params.rounds < 1 || cleaned->params.rounds > 64))
         MTG_DIE("mtg_compact_unitigs_cleaned: %llu rounds; 1 .. 64 are served", (unsigned long long)cleaned->params.rounds);
-    const bool cleaning = cleaned && (cleaned->params.tip_kmers || cleaned->params.isolated_kmers);
+    const bool popping = bubbles && bubbles->params.max_arm_kmers;
+    if (popping) {
+        if (!cleaned) MTG_DIE("mtg_compact_unitigs_simplified: null argument");
+        if (!counted) MTG_DIE("mtg_compact_unitigs_simplified: popping bubbles compares abundances and needs the abundance and sums out-pointers");
+        if (bubbles->params.min_ratio < 1 || bubbles->params.min_ratio > 255)
+            MTG_DIE("mtg_compact_unitigs_simplified: min_ratio %llu; 1 .. 255 are served", (unsigned long long)bubbles->params.min_ratio);
+    }
+    const bool cleaning = (cleaned && (cleaned->params.tip_kmers || cleaned->params.isolated_kmers)) || popping;
     mtg_cleaning clean{};
-    double clean_ms = 0;
+    mtg_bubbles popped{};
+    double clean_ms = 0, bubble_ms = 0;
     auto finish = [&]() {
         t.total_ms = ms_since(t_total);
         if (stats_out) *stats_out = r;
@@ -857,6 +1099,10 @@ UnitigStore *compact(const char *data, const uint64_t *off, uint64_t n_rec, uint
         if (cleaned) {
             *cleaned->out = clean;
             *cleaned->clean_ms = clean_ms;
+        }
+        if (bubbles) {
+            *bubbles->out = popped;
+            *bubbles->bubble_ms = bubble_ms;
         }
         return store;
     };
@@ -1063,12 +1309,23 @@ UnitigStore *compact(const char *data, const uint64_t *off, uint64_t n_rec, uint
         ce.mark(0, st);
         clean_decide_kernel<<<hu::grid_for(n_or), hu::EB, 0, st>>>(na, d_pairs, n_or, cleaned->params.tip_kmers, cleaned->params.isolated_kmers, d_verdict,
                                                                   d_counters, d_err);
-        clean_keep_kernel<<<hu::grid_for(N), hu::EB, 0, st>>>(d_pairs, d_verdict, d_kcount, N, d_keep, d_counters);
+        double round_bubble_ms = 0;
+        if (popping) {  // (the same snapshot: tips and arms are disjoint, both of an arm's ends are anchored)
+            PhaseEvents<2> be;
+            be.mark(0, st);
+            pop_bubbles(na, d_pairs, d_kcount, bubbles->params, d_verdict, d_counters + 7, d_err, st);
+            be.mark(1, st);
+            clean_keep_kernel<true><<<hu::grid_for(N), hu::EB, 0, st>>>(d_pairs, d_verdict, d_kcount, N, d_keep, d_counters);
+            round_bubble_ms = be.ms(0, 1);
+        } else {
+            clean_keep_kernel<false><<<hu::grid_for(N), hu::EB, 0, st>>>(d_pairs, d_verdict, d_kcount, N, d_keep, d_counters);
+        }
         HIP_CHECK(hipGetLastError());
         ce.mark(1, st);
         HIP_CHECK(hipMemcpyAsync(h_counters, d_counters, sizeof h_counters, hipMemcpyDeviceToHost, st));
         small.read(st, stage);
-        clean_ms += ce.ms(0, 1);
+        clean_ms += ce.ms(0, 1) - round_bubble_ms;  // (nested marks on one stream)
+        bubble_ms += round_bubble_ms;
         free_all({d_verdict, d_counters});
         clean.rounds_run++;
         clean.tips += h_counters[0];
@@ -1076,7 +1333,10 @@ UnitigStore *compact(const char *data, const uint64_t *off, uint64_t n_rec, uint
         clean.tip_kmers += h_counters[2];
         clean.isolated_kmers += h_counters[3];
         clean.removed_occurrences += h_counters[4];
-        const uint64_t removed = h_counters[2] + h_counters[3];
+        popped.arm_kmers += h_counters[5];
+        popped.removed_occurrences += h_counters[6];
+        popped.arms += h_counters[7];
+        const uint64_t removed = h_counters[2] + h_counters[3] + h_counters[5];
         if (removed > N) MTG_DIE("unitig compaction: internal error (%llu of %llu k-mers removed)", (unsigned long long)removed, (unsigned long long)N);
         if (removed == 0) {  // the set is final: so are succ and the ranks, unless the unitigs are to be split
             hu::device_free(d_keep);
@@ -1127,7 +1387,7 @@ UnitigStore *compact(const char *data, const uint64_t *off, uint64_t n_rec, uint
         hu::device_free(d_keep);
         N = r.distinct_kmers = N_left;
         n_or = 2 * N;
-        if (N == 0) {  // everything was a tip or isolated
+        if (N == 0) {  // everything was a tip or isolated (an arm's best stays: popping alone never gets here)
             free_all({d_kpos, d_kcount, d_kcolor});
             t.insert_ms = ev.ms(0, 1);
             t.ids_ms = ev.ms(1, 2);
@@ -1272,7 +1532,8 @@ UnitigStore *device_compact_unitigs(const CompactRequest &rq) {
         (cl && (!col || !cl->out || !cl->times)))
         MTG_DIE("%s: null argument", rq.who);
     if (rq.cleaned && (!rq.cleaned->out || !rq.cleaned->clean_ms)) MTG_DIE("%s: null argument", rq.who);
-    return compact(rq.data, rq.off, rq.n_rec, rq.k, rq.device_id, rq.stats_out, rq.times, c, col, cl, rq.cleaned);
+    if (rq.bubbles && (!rq.bubbles->out || !rq.bubbles->bubble_ms)) MTG_DIE("%s: null argument", rq.who);
+    return compact(rq.data, rq.off, rq.n_rec, rq.k, rq.device_id, rq.stats_out, rq.times, c, col, cl, rq.cleaned, rq.bubbles);
 }
 
 void device_color_classes(const uint64_t *kmer_colors, uint64_t n, const uint64_t *unitig_kmers, uint64_t n_unitigs, int device_id, ColorClasses *out,

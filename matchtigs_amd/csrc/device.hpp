@@ -239,6 +239,14 @@ struct Cleaned {
     mtg_cleaning *out;
     double *clean_ms;
 };
+// What a simplified call adds to a cleaned one: the rounds also pop the weaker arms of simple bubbles. It goes with a
+// Cleaned (whose params carry the rounds) and, where max_arm_kmers > 0, with a Counted. bubble_ms: HIP-event time of the list, sums,
+// choose and verdict kernels over all rounds, which clean_ms leaves out.
+struct Bubbled {
+    mtg_bubble_params params;
+    mtg_bubbles *out;
+    double *bubble_ms;
+};
 // One compaction. who: the public entry point that was called, for the messages. Each rung of the ladder is one pointer, null where
 // the call does not climb that far; a rung needs the ones below it.
 struct CompactRequest {
@@ -253,6 +261,7 @@ struct CompactRequest {
     const Colored *colored;
     const Classed *classed;
     const Cleaned *cleaned = nullptr;
+    const Bubbled *bubbles = nullptr;
 };
 UnitigStore *device_compact_unitigs(const CompactRequest &rq);
 // ... of masks and unitig lengths handed in (kmer_colors: n masks in window order, none 0; unitig_kmers: n_unitigs lengths that sum to n)

@@ -795,6 +795,7 @@ void mtg_read_sequences_named(const char *path, mtg_unitigs **seqs_out, mtg_unit
 static thread_local CompactTimes g_last_compact;
 static thread_local ColorClassTimes g_last_color_class;
 static thread_local double g_last_clean[2];  // ms of the decision and removal kernels, rounds run
+static thread_local double g_last_bubble;    // ms of the bubble kernels over all rounds
 struct mtg_abundance_sums { std::vector<uint64_t> v; };
 struct mtg_kmer_counts { std::vector<uint32_t> v; };
 struct mtg_kmer_colors { std::vector<uint64_t> v; };
@@ -812,6 +813,7 @@ struct CompactIn {
     uint64_t n_colors = 0;
     int split = 0;                           // CLASSES
     const mtg_cleaning_params *cleaning = nullptr;  // mtg_compact_unitigs_cleaned, at any rung
+    const mtg_bubble_params *bubbles = nullptr;     // mtg_compact_unitigs_simplified, from COUNTED on
 };
 struct CompactOut {
     mtg_unitigs **out;
@@ -823,6 +825,7 @@ struct CompactOut {
     mtg_color_stats *color_stats = nullptr;
     mtg_color_classes **classes = nullptr;    // CLASSES
     mtg_cleaning *cleaning = nullptr;         // mtg_compact_unitigs_cleaned
+    mtg_bubbles *bubbles = nullptr;           // mtg_compact_unitigs_simplified
 };
 // what all mtg_compact_unitigs* share: the argument checks, the handles and their way to the out-pointers (who: the entry point)
 static void compact_call(const char *who, CompactRung rung, const CompactIn &in, const CompactOut &o) {
@@ -841,10 +844,16 @@ static void compact_call(const char *who, CompactRung rung, const CompactIn &in,
     mtg_cleaning none{};
     const bool clean = in.cleaning && o.cleaning;
     const Cleaned cleaned{clean ? *in.cleaning : mtg_cleaning_params{0, 0, 1}, clean ? o.cleaning : &none, &g_last_clean[0]};
+    mtg_bubbles none_popped{};
+    const bool pop = in.bubbles && o.bubbles && in.bubbles->max_arm_kmers;
+    if (pop && !clean) MTG_DIE("%s: popping bubbles needs the cleaning parameters (they carry the rounds) and the cleaning out-pointer", who);
+    if (pop && rung < COUNTED) MTG_DIE("%s: popping bubbles compares abundances and needs the abundance and sums out-pointers", who);
+    const Bubbled bubbled{pop ? *in.bubbles : mtg_bubble_params{0, 1}, pop ? o.bubbles : &none_popped, &g_last_bubble};
     *o.out = new mtg_unitigs{device_compact_unitigs({who, in.data, in.offsets, in.n, in.k, in.device_id, o.stats, &g_last_compact, s ? &counted : nullptr,
-                                                     m ? &colored : nullptr, cl ? &classed : nullptr, &cleaned})};
+                                                     m ? &colored : nullptr, cl ? &classed : nullptr, &cleaned, &bubbled})};
     g_last_clean[1] = (double)cleaned.out->rounds_run;
     if (o.cleaning && !clean) *o.cleaning = none;
+    if (o.bubbles && !pop) *o.bubbles = none_popped;
     if (s) *o.sums = s;
     if (c) *o.kmer_counts = c;
     if (m) *o.kmer_colors = m;
@@ -936,6 +945,33 @@ void mtg_last_clean_times(double out[2]) {
     out[0] = g_last_clean[0];
     out[1] = g_last_clean[1];
 }
+void mtg_compact_unitigs_simplified(const char *data, const uint64_t *offsets, uint64_t n, uint64_t k, uint64_t min_abundance,
+                                    const uint8_t *record_colors, uint64_t n_colors, int split, const mtg_cleaning_params *params,
+                                    const mtg_bubble_params *bubble_params, int device_id, mtg_unitigs **out, mtg_compaction *stats,
+                                    mtg_abundance *abundance, mtg_abundance_sums **sums, mtg_kmer_counts **kmer_counts,
+                                    mtg_kmer_colors **kmer_colors, mtg_color_stats *color_stats, mtg_color_classes **classes,
+                                    mtg_cleaning *cleaning, mtg_bubbles *bubbles) {
+    const char *const who = "mtg_compact_unitigs_simplified";
+    const CompactRung rung = !sums ? PLAIN : !kmer_counts ? COUNTED : (!kmer_colors || !color_stats) ? COUNTED_KMERS : !classes ? COLORED : CLASSES;
+    if (rung < COUNTED && min_abundance != 1) MTG_DIE("%s: min_abundance %llu needs the sums' out-pointer", who, (unsigned long long)min_abundance);
+    if (rung < CLASSES && split != 0) MTG_DIE("%s: split needs the classes' out-pointer", who);
+    if (rung >= COUNTED && bubble_params && bubbles && bubble_params->max_arm_kmers && !abundance)
+        MTG_DIE("%s: popping bubbles compares abundances and needs the abundance and sums out-pointers", who);
+    compact_call(who, rung, {data, offsets, n, k, device_id, min_abundance, record_colors, n_colors, split, params, bubble_params},
+                 {out, stats, abundance, sums, kmer_counts, kmer_colors, color_stats, classes, cleaning, bubbles});
+}
+void mtg_compact_unitigs_simplified_store(const mtg_unitigs *in, uint64_t k, uint64_t min_abundance, const uint8_t *record_colors,
+                                          uint64_t n_colors, int split, const mtg_cleaning_params *params,
+                                          const mtg_bubble_params *bubble_params, int device_id, mtg_unitigs **out, mtg_compaction *stats,
+                                          mtg_abundance *abundance, mtg_abundance_sums **sums, mtg_kmer_counts **kmer_counts,
+                                          mtg_kmer_colors **kmer_colors, mtg_color_stats *color_stats, mtg_color_classes **classes,
+                                          mtg_cleaning *cleaning, mtg_bubbles *bubbles) {
+    if (!in) MTG_DIE("mtg_compact_unitigs_simplified_store: null argument");
+    mtg_compact_unitigs_simplified(in->s->data.data(), in->s->off.data(), in->s->off.size() - 1, k, min_abundance, record_colors, n_colors, split, params,
+                                   bubble_params, device_id, out, stats, abundance, sums, kmer_counts, kmer_colors, color_stats, classes, cleaning,
+                                   bubbles);
+}
+void mtg_last_bubble_times(double out[1]) { out[0] = g_last_bubble; }
 // the vector behind one of the handles above (who: the entry point, for the message)
 extern "C++" {
 template <class Handle>
