@@ -99,7 +99,11 @@
 //
 // All of these enter through device_compact_unitigs(CompactRequest) (device.hpp): one rung of the ladder per pointer of the request --
 // Counted, Colored, Classed --, null where the call does not climb that far; Cleaned stands beside the ladder and goes with any rung,
-// Bubbled beside a Cleaned and a Counted.
+// Bubbled beside a Cleaned and a Counted. On the host a call is check_request (no device call), then run() over a Work (the store, the
+// current k-mer set, its node table, succ, pairs) through one function per stage -- insert, ids, pass (build_nodes, succ, rank with
+// rank_closed_walks), clean_rounds (clean_round, move_survivors), emit, sums_and_colors, download --, then finish(), the one way
+// out. Every device array belongs to a hu::DeviceArray and goes back where its owner's scope ends; every scan's block sums and
+// total belong to a hu::ScanScratch, which checks that a scan fits it.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -762,7 +766,7 @@ constexpr int CLASS_LDS = 2048;   // classes 0 .. CLASS_LDS - 1 are counted in L
 constexpr int CLASS_GRID = 512;   // the counts kernel's largest grid
 constexpr int CLASS_PEEL = 2;     // classes combined across the wave before the lanes left add on their own
 
-__device__ __forceinline__ uint64_t mix64(uint64_t x) {
+__device__ __forceinline__ uint64_t mask_hash(uint64_t x) {
     x ^= x >> 33; x *= 0xFF51AFD7ED558CCDull;
     x ^= x >> 33; x *= 0xC4CEB9FE1A85EC53ull;
     return x ^ (x >> 33);
@@ -786,7 +790,7 @@ __global__ __launch_bounds__(hu::EB) void class_insert_kernel(const unsigned lon
     const uint64_t r = hu::gid();
     if (r >= R) return;
     const unsigned long long mask = ordered[run_start[r]];
-    uint64_t s = mix64(mask) % slots;
+    uint64_t s = mask_hash(mask) % slots;
     for (uint64_t probe = 0; probe < slots; probe++, s = s + 1 == slots ? 0 : s + 1) {
         unsigned long long cur = load64(&keys[s]);
         if (cur == 0) {
@@ -886,97 +890,80 @@ int log2_ceil(uint64_t n) {
 
 // The class dictionary of a store's masks in window order (ordered: [N], out_off: the unitigs' character offsets). Device memory, all
 // from the arena: 8 B per k-mer (head, run number) and 4 B more for kmer_class; per run R 4 (start) + 4 (slot) + 4 (class) + 4 (flag,
-// scanned in place) + 2 x (8 + 4 + 4) (the table: key, smallest run, class per slot); per class 32 B.
+// scanned in place) + 2 x (8 + 4 + 4) (the table: key, smallest run, class per slot); per class 32 B. All of it goes back at the end.
 void color_classes(const unsigned long long *d_ordered, const unsigned long long *d_out_off, uint64_t N, uint64_t n_unitigs, uint64_t k, bool split,
                    hipStream_t st, ScalarBlock &small, int device_id, ColorClasses *out, ColorClassTimes *times) {
     const char *const stage = "colour classes";
     PhaseEvents<5> ev;
     ev.mark(0, st);
     // ---- run heads ----
-    uint32_t *d_head = nullptr, *d_run_of = nullptr, *d_bsum = nullptr, *d_run_start = nullptr;
-    hu::device_malloc(&d_head, N * 4);
-    hu::device_malloc(&d_run_of, N * 4);
-    hu::device_malloc(&d_bsum, (hu::scan_blocks(N) + 2) * 4);
-    uint32_t *d_total = d_bsum + hu::scan_blocks(N) + 1;
-    HIP_CHECK(hipMemsetAsync(d_head, 0, N * 4, st));
-    unitig_heads_kernel<<<hu::grid_for(n_unitigs), hu::EB, 0, st>>>(d_out_off, n_unitigs, k, d_head);
-    run_heads_kernel<<<hu::grid_for(N), hu::EB, 0, st>>>(d_ordered, N, d_head);
-    hu::scan_u32<uint32_t>(st, d_head, N, d_run_of, d_bsum, d_total);
+    hu::DeviceArray<uint32_t> head(N), run_of(N);
+    hu::ScanScratch<uint32_t> scan(N);
+    HIP_CHECK(hipMemsetAsync(head, 0, N * 4, st));
+    unitig_heads_kernel<<<hu::grid_for(n_unitigs), hu::EB, 0, st>>>(d_out_off, n_unitigs, k, head);
+    run_heads_kernel<<<hu::grid_for(N), hu::EB, 0, st>>>(d_ordered, N, head);
+    scan.scan(st, head, N, run_of);
     uint32_t n_runs = 0;
-    HIP_CHECK(hipMemcpyAsync(&n_runs, d_total, 4, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(&n_runs, scan.total(), 4, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
     const uint64_t R = n_runs;
     if (R < n_unitigs || R > N || (split && R != n_unitigs))
         MTG_DIE("colour classes: internal error (%llu runs in %llu unitigs of %llu k-mers%s)", (unsigned long long)R, (unsigned long long)n_unitigs,
                 (unsigned long long)N, split ? ", split" : "");
-    hu::device_malloc(&d_run_start, (R + 1) * 4);
-    run_starts_kernel<<<hu::grid_for(N), hu::EB, 0, st>>>(d_head, d_run_of, N, R, d_run_start);
+    hu::DeviceArray<uint32_t> run_start(R + 1);
+    run_starts_kernel<<<hu::grid_for(N), hu::EB, 0, st>>>(head, run_of, N, R, run_start);
     HIP_CHECK(hipGetLastError());
     ev.mark(1, st);
     // ---- the class table: one insertion per run ----
     const uint64_t slots = std::max<uint64_t>(8, 2 * R);
-    unsigned long long *d_keys = nullptr;
-    uint32_t *d_min_run = nullptr, *d_run_slot = nullptr;
-    hu::device_malloc(&d_keys, slots * 8);
-    hu::device_malloc(&d_min_run, slots * 4);
-    hu::device_malloc(&d_run_slot, R * 4);
-    HIP_CHECK(hipMemsetAsync(d_keys, 0, slots * 8, st));
-    HIP_CHECK(hipMemsetAsync(d_min_run, 0xFF, slots * 4, st));
-    class_insert_kernel<<<hu::grid_for(R), hu::EB, 0, st>>>(d_ordered, d_run_start, R, d_keys, d_min_run, slots, d_run_slot, small.err());
+    hu::DeviceArray<unsigned long long> keys(slots);
+    hu::DeviceArray<uint32_t> min_run(slots), run_slot(R);
+    HIP_CHECK(hipMemsetAsync(keys, 0, slots * 8, st));
+    HIP_CHECK(hipMemsetAsync(min_run, 0xFF, slots * 4, st));
+    class_insert_kernel<<<hu::grid_for(R), hu::EB, 0, st>>>(d_ordered, run_start, R, keys, min_run, slots, run_slot, small.err());
     HIP_CHECK(hipGetLastError());
     ev.mark(2, st);
     // ---- class ids in first-appearance order ----
-    uint32_t *d_flag = nullptr, *d_bsum_r = nullptr, *d_slot_class = nullptr;
-    hu::device_malloc(&d_flag, R * 4);
-    hu::device_malloc(&d_bsum_r, (hu::scan_blocks(R) + 2) * 4);
-    hu::device_malloc(&d_slot_class, slots * 4);
-    uint32_t *d_n_classes = d_bsum_r + hu::scan_blocks(R) + 1;
-    HIP_CHECK(hipMemsetAsync(d_flag, 0, R * 4, st));
-    class_flag_kernel<<<hu::grid_for(slots), hu::EB, 0, st>>>(d_keys, d_min_run, slots, d_flag);
-    hu::scan_u32<uint32_t>(st, d_flag, R, d_flag, d_bsum_r, d_n_classes);
+    hu::DeviceArray<uint32_t> flag(R);
+    hu::ScanScratch<uint32_t> scan_runs(R);
+    hu::DeviceArray<uint32_t> slot_class(slots);
+    HIP_CHECK(hipMemsetAsync(flag, 0, R * 4, st));
+    class_flag_kernel<<<hu::grid_for(slots), hu::EB, 0, st>>>(keys, min_run, slots, flag);
+    scan_runs.scan(st, flag, R, flag);
     uint32_t n_classes32 = 0;
-    HIP_CHECK(hipMemcpyAsync(&n_classes32, d_n_classes, 4, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(&n_classes32, scan_runs.total(), 4, hipMemcpyDeviceToHost, st));
     small.read(st, stage);
     const uint64_t n_classes = n_classes32;
     if (n_classes == 0 || n_classes > R) MTG_DIE("colour classes: internal error (%llu classes in %llu runs)", (unsigned long long)n_classes, (unsigned long long)R);
-    unsigned long long *d_masks = nullptr, *d_first = nullptr, *d_sums = nullptr;
-    hu::device_malloc(&d_masks, n_classes * 8);
-    hu::device_malloc(&d_first, n_classes * 8);
-    hu::device_malloc(&d_sums, 2 * n_classes * 8);
-    HIP_CHECK(hipMemsetAsync(d_sums, 0, 2 * n_classes * 8, st));
-    class_ids_kernel<<<hu::grid_for(slots), hu::EB, 0, st>>>(d_keys, d_min_run, slots, d_flag, d_run_start, d_slot_class, d_masks, d_first);
+    hu::DeviceArray<unsigned long long> masks(n_classes), first(n_classes), sums(2 * n_classes);
+    HIP_CHECK(hipMemsetAsync(sums, 0, 2 * n_classes * 8, st));
+    class_ids_kernel<<<hu::grid_for(slots), hu::EB, 0, st>>>(keys, min_run, slots, flag, run_start, slot_class, masks, first);
     HIP_CHECK(hipGetLastError());
     ev.mark(3, st);
     // ---- counts per class, and the class of every window ----
-    uint32_t *d_run_class = nullptr, *d_kmer_class = nullptr;
-    hu::device_malloc(&d_run_class, R * 4);
-    hu::device_malloc(&d_kmer_class, N * 4);
-    class_counts_kernel<<<(unsigned)std::min<uint64_t>(hu::grid_for(R), CLASS_GRID), hu::EB, 0, st>>>(d_run_start, d_run_slot, d_slot_class, R, n_classes,
-                                                                                                      d_run_class, d_sums);
-    window_class_kernel<<<hu::grid_for(N), hu::EB, 0, st>>>(d_head, d_run_of, d_run_class, N, d_kmer_class);
+    hu::DeviceArray<uint32_t> run_class(R), kmer_class(N);
+    class_counts_kernel<<<(unsigned)std::min<uint64_t>(hu::grid_for(R), CLASS_GRID), hu::EB, 0, st>>>(run_start, run_slot, slot_class, R, n_classes, run_class, sums);
+    window_class_kernel<<<hu::grid_for(N), hu::EB, 0, st>>>(head, run_of, run_class, N, kmer_class);
     HIP_CHECK(hipGetLastError());
     ev.mark(4, st);
     HIP_CHECK(hipStreamSynchronize(st));
     const auto t0 = std::chrono::steady_clock::now();
-    std::vector<uint64_t> sums(2 * n_classes);
+    std::vector<uint64_t> h_sums(2 * n_classes);
     out->masks.resize(n_classes);
     out->first.resize(n_classes);
     out->kmer_class.resize(N);
-    hu::download_sliced(out->masks.data(), d_masks, n_classes * 8, st, device_id);
-    hu::download_sliced(out->first.data(), d_first, n_classes * 8, st, device_id);
-    hu::download_sliced(sums.data(), d_sums, 2 * n_classes * 8, st, device_id);
-    hu::download_sliced(out->kmer_class.data(), d_kmer_class, N * 4, st, device_id);
-    out->kmers.assign(sums.begin(), sums.begin() + n_classes);
-    out->runs.assign(sums.begin() + n_classes, sums.end());
+    hu::download_sliced(out->masks.data(), masks, n_classes * 8, st, device_id);
+    hu::download_sliced(out->first.data(), first, n_classes * 8, st, device_id);
+    hu::download_sliced(h_sums.data(), sums, 2 * n_classes * 8, st, device_id);
+    hu::download_sliced(out->kmer_class.data(), kmer_class, N * 4, st, device_id);
+    out->kmers.assign(h_sums.begin(), h_sums.begin() + n_classes);
+    out->runs.assign(h_sums.begin() + n_classes, h_sums.end());
     out->n_runs = R;
     times->download_ms = ms_since(t0);
     times->heads_ms = ev.ms(0, 1);
     times->table_ms = ev.ms(1, 2);
     times->ids_ms = ev.ms(2, 3);
     times->counts_ms = ev.ms(3, 4);
-    for (const void *p : std::initializer_list<const void *>{d_head, d_run_of, d_bsum, d_run_start, d_keys, d_min_run, d_run_slot, d_flag, d_bsum_r, d_slot_class,
-                                                             d_masks, d_first, d_sums, d_run_class, d_kmer_class})
-        hu::device_free(p);
 }
 
 // The bubble verdicts of one round over the N k-mers behind `na` (node table, succ) and `pairs`: list, sums, choose, verdict.
@@ -984,80 +971,94 @@ void color_classes(const unsigned long long *d_ordered, const unsigned long long
 void pop_bubbles(const NodeArgs &na, const unsigned long long *d_pairs, const uint32_t *d_kcount, const mtg_bubble_params &p, uint8_t *d_verdict,
                  unsigned long long *d_arms, unsigned int *d_err, hipStream_t st) {
     const uint64_t N = na.N, n_or = 2 * N;
-    uint32_t *d_slot_of = nullptr, *d_bsum = nullptr;
-    hu::device_malloc(&d_slot_of, n_or * 4);
-    hu::device_malloc(&d_bsum, (hu::scan_blocks(n_or) + 2) * 4);
-    uint32_t *d_total = d_bsum + hu::scan_blocks(n_or) + 1;
-    HIP_CHECK(hipMemsetAsync(d_slot_of, 0, n_or * 4, st));
-    bubble_flag_kernel<<<hu::grid_for(n_or), hu::EB, 0, st>>>(na.succ, d_pairs, n_or, p.max_arm_kmers, d_slot_of);
-    hu::scan_u32<uint32_t>(st, d_slot_of, n_or, d_slot_of, d_bsum, d_total);
+    hu::DeviceArray<uint32_t> slot_of(n_or);
+    hu::ScanScratch<uint32_t> scan(n_or);
+    HIP_CHECK(hipMemsetAsync(slot_of, 0, n_or * 4, st));
+    bubble_flag_kernel<<<hu::grid_for(n_or), hu::EB, 0, st>>>(na.succ, d_pairs, n_or, p.max_arm_kmers, slot_of);
+    scan.scan(st, slot_of, n_or, slot_of);
     uint32_t M = 0, K = 0;
-    HIP_CHECK(hipMemcpyAsync(&M, d_total, 4, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(&M, scan.total(), 4, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
     ArmArgs b{};
     b.M = M;
+    hu::DeviceArray<unsigned long long> tail, head;
+    hu::DeviceArray<uint32_t> first, last, n, off;
     if (M) {
-        hu::device_malloc(&b.tail, (uint64_t)M * 8);
-        hu::device_malloc(&b.head, (uint64_t)M * 8);
-        hu::device_malloc(&b.first, (uint64_t)M * 4);
-        hu::device_malloc(&b.last, (uint64_t)M * 4);
-        hu::device_malloc(&b.n, (uint64_t)M * 4);
-        hu::device_malloc(&b.off, (uint64_t)M * 4);
+        b.tail = tail.alloc(M);
+        b.head = head.alloc(M);
+        b.first = first.alloc(M);
+        b.last = last.alloc(M);
+        b.n = n.alloc(M);
+        b.off = off.alloc(M);
         HIP_CHECK(hipMemsetAsync(b.n, 0, (uint64_t)M * 4, st));
-        bubble_list_kernel<<<hu::grid_for(n_or), hu::EB, 0, st>>>(na, d_pairs, n_or, p.max_arm_kmers, d_slot_of, b, d_err);
-        hu::scan_u32<uint32_t>(st, b.n, M, b.off, d_bsum, d_total);  // (M <= N: the block sums fit; K <= N < 2^31)
-        HIP_CHECK(hipMemcpyAsync(&K, d_total, 4, hipMemcpyDeviceToHost, st));
+        bubble_list_kernel<<<hu::grid_for(n_or), hu::EB, 0, st>>>(na, d_pairs, n_or, p.max_arm_kmers, slot_of, b, d_err);
+        scan.scan(st, b.n, M, b.off);  // (M <= N, which the scratch checks; K <= N < 2^31)
+        HIP_CHECK(hipMemcpyAsync(&K, scan.total(), 4, hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipStreamSynchronize(st));
     }
     if (K) {
-        uint32_t *d_ordered = nullptr;
-        unsigned long long *d_prefix = nullptr, *d_bsum64 = nullptr;
         b.slots = std::max<uint64_t>(8, 2 * (uint64_t)M);
-        hu::device_malloc(&d_ordered, (uint64_t)K * 4);
-        hu::device_malloc(&d_prefix, (uint64_t)K * 8);
-        hu::device_malloc(&d_bsum64, (hu::scan_blocks(K) + 2) * 8);
-        hu::device_malloc(&b.sum, (uint64_t)M * 4);
-        hu::device_malloc(&b.table, b.slots * 4);
-        unsigned long long *d_sum_total = d_bsum64 + hu::scan_blocks(K) + 1;
-        HIP_CHECK(hipMemsetAsync(d_ordered, 0, (uint64_t)K * 4, st));
+        hu::DeviceArray<uint32_t> ordered(K);
+        hu::DeviceArray<unsigned long long> prefix(K);
+        hu::ScanScratch<unsigned long long> scan64(K);
+        hu::DeviceArray<uint32_t> sum(M), table(b.slots);
+        b.sum = sum;
+        b.table = table;
+        HIP_CHECK(hipMemsetAsync(ordered, 0, (uint64_t)K * 4, st));
         HIP_CHECK(hipMemsetAsync(b.table, 0xFF, b.slots * 4, st));
-        bubble_counts_kernel<<<hu::grid_for(N), hu::EB, 0, st>>>(d_pairs, d_kcount, N, p.max_arm_kmers, d_slot_of, b, d_ordered);
-        hu::scan_u32<unsigned long long>(st, d_ordered, K, d_prefix, d_bsum64, d_sum_total);
-        bubble_sums_kernel<<<hu::grid_for(M), hu::EB, 0, st>>>(b, d_prefix, d_sum_total, K);
+        bubble_counts_kernel<<<hu::grid_for(N), hu::EB, 0, st>>>(d_pairs, d_kcount, N, p.max_arm_kmers, slot_of, b, ordered);
+        scan64.scan(st, ordered, K, prefix);
+        bubble_sums_kernel<<<hu::grid_for(M), hu::EB, 0, st>>>(b, prefix, scan64.total(), K);
         bubble_choose_kernel<<<hu::grid_for(M), hu::EB, 0, st>>>(b, d_err);
         bubble_verdict_kernel<<<hu::grid_for(M), hu::EB, 0, st>>>(b, p.min_ratio, d_verdict, d_arms, d_err);
         HIP_CHECK(hipGetLastError());
-        for (const void *q : std::initializer_list<const void *>{d_ordered, d_prefix, d_bsum64, b.sum, b.table}) hu::device_free(q);
     }
     HIP_CHECK(hipGetLastError());
-    for (const void *q : std::initializer_list<const void *>{d_slot_of, d_bsum, b.tail, b.head, b.first, b.last, b.n, b.off}) hu::device_free(q);
 }
 
-// counted == nullptr: the plain compaction
-// colored != nullptr: counted too
-UnitigStore *compact(const char *data, const uint64_t *off, uint64_t n_rec, uint64_t k, int device_id, mtg_compaction *stats_out, CompactTimes *times,
-                     const Counted *counted, const Colored *colored = nullptr, const Classed *classed = nullptr, const Cleaned *cleaned = nullptr, const Bubbled *bubbles = nullptr) {
-    if (!off || (n_rec && off[n_rec] && !data)) MTG_DIE("mtg_compact_unitigs: null argument");
+// ---- the compaction: what a call was asked for and hands back (Call), its device state (Work), one function per stage in the
+// order of the header's list of kernels, and the driver (run) ----
+constexpr const char *STAGE = "unitig compaction";
+struct Call {
+    const CompactRequest &rq;
+    uint64_t m = 0;  // min_abundance of a counted call
+    bool popping = false, cleaning = false, split = false;
+    std::chrono::steady_clock::time_point t_total;
+    mtg_compaction r{};
+    CompactTimes t{};
+    mtg_abundance ab{};
+    mtg_cleaning clean{};
+    mtg_bubbles popped{};
+    double clean_ms = 0, bubble_ms = 0;
+    UnitigStore *store = nullptr;
+};
+
+// Stage 1, host only: the request's checks, the window count, the out-parameters emptied. No device call.
+void check_request(Call &c) {
+    const CompactRequest &q = c.rq;
+    const Counted *counted = q.counted;
+    const Colored *colored = q.colored;
+    const Cleaned *cleaned = q.cleaned;
+    const uint64_t n_rec = q.n_rec, k = q.k;
+    if (!q.off || (n_rec && q.off[n_rec] && !q.data)) MTG_DIE("mtg_compact_unitigs: null argument");
     if (k < 2) MTG_DIE("mtg_compact_unitigs: k must be >= 2");
     if (k >= (1ull << 31)) MTG_DIE("mtg_compact_unitigs: k too large");
-    if (off[0] != 0) MTG_DIE("mtg_compact_unitigs: offsets must start at 0");
-    const auto t_total = std::chrono::steady_clock::now();
-    mtg_compaction r{};
-    r.records = n_rec;
+    if (q.off[0] != 0) MTG_DIE("mtg_compact_unitigs: offsets must start at 0");
+    c.t_total = std::chrono::steady_clock::now();
+    c.r.records = n_rec;
     for (uint64_t u = 0; u < n_rec; u++) {
-        if (off[u + 1] < off[u]) MTG_DIE("mtg_compact_unitigs: offsets decrease at record %llu", (unsigned long long)u);
-        const uint64_t len = off[u + 1] - off[u];
-        if (len >= k) r.windows += len - k + 1;
+        if (q.off[u + 1] < q.off[u]) MTG_DIE("mtg_compact_unitigs: offsets decrease at record %llu", (unsigned long long)u);
+        const uint64_t len = q.off[u + 1] - q.off[u];
+        if (len >= k) c.r.windows += len - k + 1;
     }
-    const uint64_t n_bases = r.characters = off[n_rec];
-    CompactTimes t{};
-    UnitigStore *store = new UnitigStore();
-    store->off.push_back(0);
-    mtg_abundance ab{};
+    c.r.characters = q.off[n_rec];
+    c.store = new UnitigStore();
+    c.store->off.push_back(0);
     if (counted) {
         if (counted->m == 0) MTG_DIE("mtg_compact_unitigs_counted: min_abundance must be >= 1");
-        if (r.windows >= (1ull << 32)) MTG_DIE("mtg_compact_unitigs_counted: %llu windows; the abundance counters are 32-bit, the limit is 2^32 - 1",
-                                               (unsigned long long)r.windows);
+        if (c.r.windows >= (1ull << 32)) MTG_DIE("mtg_compact_unitigs_counted: %llu windows; the abundance counters are 32-bit, the limit is 2^32 - 1",
+                                                 (unsigned long long)c.r.windows);
+        c.m = counted->m;
         counted->sums->clear();
         if (counted->kmer_counts) counted->kmer_counts->clear();
     }
@@ -1074,422 +1075,432 @@ UnitigStore *compact(const char *data, const uint64_t *off, uint64_t n_rec, uint
         colored->stats->n_colors = colored->n_colors;
         *colored->stats_ms = 0;
     }
-    if (classed) {
-        *classed->out = ColorClasses{};
-        *classed->times = ColorClassTimes{};
+    if (q.classed) {
+        *q.classed->out = ColorClasses{};
+        *q.classed->times = ColorClassTimes{};
     }
     if (cleaned && (cleaned->params.rounds < 1 || cleaned->params.rounds > 64))
         MTG_DIE("mtg_compact_unitigs_cleaned: %llu rounds; 1 .. 64 are served", (unsigned long long)cleaned->params.rounds);
-    const bool popping = bubbles && bubbles->params.max_arm_kmers;
-    if (popping) {
+    c.popping = q.bubbles && q.bubbles->params.max_arm_kmers;
+    if (c.popping) {
         if (!cleaned) MTG_DIE("mtg_compact_unitigs_simplified: null argument");
         if (!counted) MTG_DIE("mtg_compact_unitigs_simplified: popping bubbles compares abundances and needs the abundance and sums out-pointers");
-        if (bubbles->params.min_ratio < 1 || bubbles->params.min_ratio > 255)
-            MTG_DIE("mtg_compact_unitigs_simplified: min_ratio %llu; 1 .. 255 are served", (unsigned long long)bubbles->params.min_ratio);
+        if (q.bubbles->params.min_ratio < 1 || q.bubbles->params.min_ratio > 255)
+            MTG_DIE("mtg_compact_unitigs_simplified: min_ratio %llu; 1 .. 255 are served", (unsigned long long)q.bubbles->params.min_ratio);
     }
-    const bool cleaning = (cleaned && (cleaned->params.tip_kmers || cleaned->params.isolated_kmers)) || popping;
-    mtg_cleaning clean{};
-    mtg_bubbles popped{};
-    double clean_ms = 0, bubble_ms = 0;
-    auto finish = [&]() {
-        t.total_ms = ms_since(t_total);
-        if (stats_out) *stats_out = r;
-        if (counted && counted->abundance) *counted->abundance = ab;
-        if (times) *times = t;
-        if (cleaned) {
-            *cleaned->out = clean;
-            *cleaned->clean_ms = clean_ms;
-        }
-        if (bubbles) {
-            *bubbles->out = popped;
-            *bubbles->bubble_ms = bubble_ms;
-        }
-        return store;
-    };
-    if (n_bases == 0) return finish();
-    if (n_bases >= POS_LIMIT) MTG_DIE("mtg_compact_unitigs: %llu bases; the limit is 2^40 - 2", (unsigned long long)n_bases);
-    if (device_id < 0 || device_count() <= device_id) MTG_DIE("no HIP device %d for the unitig compaction (there is no CPU path)", device_id);
-    HIP_CHECK(hipSetDevice(device_id));
-    device_arena_reset_peak(device_id);
-    hipStream_t st = nullptr;
-
-    // ---- upload and pack ----
-    SeqStore seq("sequences", data, off, n_rec, st, device_id);
-    const uint32_t *d_packed = seq.packed;
-    ScalarBlock &small = seq.small;  // [2] distinct k-mers, [3] changed, [4] cycle elements, [5] closed, [6] longest
-    const char *const stage = "unitig compaction";
-    unsigned int *d_err = small.err();
-    unsigned int *d_changed = reinterpret_cast<unsigned int *>(small.d + 3);
-    t.upload_ms = seq.upload_ms;
-    t.pack_ms = seq.pack_ms;
-    auto free_all = [&](std::initializer_list<const void *> ps) { for (const void *p : ps) hu::device_free(p); };
-    if (r.windows == 0) return finish();  // nothing is as long as k
-    PhaseEvents<5> ev;
-    ev.mark(0, st);
-
-    // ---- insert: the creator of every k-mer class ----
-    const uint64_t slots = std::max<uint64_t>(8, (2 * r.windows + 7) / 8 * 8);
+    c.cleaning = (cleaned && (cleaned->params.tip_kmers || cleaned->params.isolated_kmers)) || c.popping;
+    c.split = q.classed && q.classed->split;
+}
+// The one way out of a call, wherever its stages ended: the statistics, the times, the cleaning and the bubble results.
+UnitigStore *finish(Call &c) {
+    const CompactRequest &q = c.rq;
+    c.t.total_ms = ms_since(c.t_total);
+    if (q.stats_out) *q.stats_out = c.r;
+    if (q.counted && q.counted->abundance) *q.counted->abundance = c.ab;
+    if (q.times) *q.times = c.t;
+    if (q.cleaned) {
+        *q.cleaned->out = c.clean;
+        *q.cleaned->clean_ms = c.clean_ms;
+    }
+    if (q.bubbles) {
+        *q.bubbles->out = c.popped;
+        *q.bubbles->bubble_ms = c.bubble_ms;
+    }
+    return c.store;
+}
+// The (k-1)-mer classes of the current k-mer set: key, and per side the incident oriented k-mer (NodeArgs). Assigning an empty one frees it.
+struct NodeTable {
+    hu::DeviceArray<unsigned long long> table;
+    hu::DeviceArray<uint32_t> out_e, in_e;
+};
+// The device state of a call. Its constructor uploads and packs. The current k-mer set T has N k-mers (they shrink with the rounds of
+// a cleaned call): kpos, and kcount / kcolor where the call counts / colours; `nodes`, succ and the (jump, rank) pairs are those of T.
+struct Work {
+    Call &c;
+    hipStream_t st;
+    SeqStore seq;
+    ScalarBlock &small;  // [2] distinct k-mers, [3] changed, [4] cycle elements, [5] closed, [6] longest
+    PhaseEvents<5> ev;   // the marks around insert, ids, (nodes, rank and the rounds), emit
+    const uint64_t k, n_bases;
+    uint64_t slots = 0, N = 0;  // slots of the k-mer table
+    hu::DeviceArray<unsigned long long> kpos, kcolor;
+    hu::DeviceArray<uint32_t> kcount;
+    NodeTable nodes;
+    hu::DeviceArray<uint32_t> succ;
+    hu::DeviceArray<unsigned long long> pairs;
+    int rankings = 0;
+    Work(Call &call, hipStream_t stream)
+        : c(call), st(stream), seq("sequences", call.rq.data, call.rq.off, call.rq.n_rec, stream, call.rq.device_id), small(seq.small), k(call.rq.k),
+          n_bases(seq.n_bases) {}
+    uint64_t n_or() const { return 2 * N; }
+    unsigned int *err() const { return small.err(); }
+    NodeArgs node_args() const {
+        NodeArgs a{};
+        a.packed = seq.packed; a.kpos = kpos; a.table = nodes.table; a.out_e = nodes.out_e; a.in_e = nodes.in_e; a.succ = succ;
+        a.slots = std::max<uint64_t>(8, 4 * N);  // at most 2 N classes
+        a.N = N; a.L = k - 1;
+        return a;
+    }
+};
+// The k-mer table of insert and what the rungs keep per slot: alive until ids has numbered the creators.
+struct KmerTable {  // (members go back last to first: the table before the equally large masks, the order the arena's best fit has seen so far)
     KmerArgs ka{};
-    ka.packed = d_packed; ka.off = seq.off; ka.slots = slots;
-    kw::window_args_set_k(ka, k);
-    hu::device_malloc(&ka.table, slots * 8);
-    HIP_CHECK(hipMemsetAsync(ka.table, 0xFF, slots * 8, st));
-    uint32_t *d_count = nullptr, *d_kcount = nullptr;  // counted calls: [slots] abundance per slot, [N] per kept k-mer
-    if (counted) {
-        hu::device_malloc(&d_count, slots * 4);
-        HIP_CHECK(hipMemsetAsync(d_count, 0, slots * 4, st));
-    }
-    uint8_t *d_rec_colors = nullptr;
-    unsigned long long *d_colors = nullptr, *d_kcolor = nullptr;  // coloured calls: [slots] mask per slot, [N] per kept k-mer
-    if (colored) {
-        hu::device_malloc(&d_rec_colors, n_rec);
-        hu::device_malloc(&d_colors, slots * 8);
-        hu::upload_sliced(d_rec_colors, colored->record_colors, n_rec, st, device_id);
-        HIP_CHECK(hipMemsetAsync(d_colors, 0, slots * 8, st));
-    }
-    {
-        const unsigned grid = hu::grid_for((n_bases + RUN - 1) / RUN);
-        if (colored) {
-            if (k >= 32) insert_kernel<true, true, true><<<grid, hu::EB, 0, st>>>(ka, n_bases, n_rec, d_err, d_count, d_rec_colors, d_colors);
-            else insert_kernel<false, true, true><<<grid, hu::EB, 0, st>>>(ka, n_bases, n_rec, d_err, d_count, d_rec_colors, d_colors);
-        } else if (counted) {
-            if (k >= 32) insert_kernel<true, true, false><<<grid, hu::EB, 0, st>>>(ka, n_bases, n_rec, d_err, d_count, nullptr, nullptr);
-            else insert_kernel<false, true, false><<<grid, hu::EB, 0, st>>>(ka, n_bases, n_rec, d_err, d_count, nullptr, nullptr);
-        } else {
-            if (k >= 32) insert_kernel<true, false, false><<<grid, hu::EB, 0, st>>>(ka, n_bases, n_rec, d_err, nullptr, nullptr, nullptr);
-            else insert_kernel<false, false, false><<<grid, hu::EB, 0, st>>>(ka, n_bases, n_rec, d_err, nullptr, nullptr, nullptr);
-        }
-        HIP_CHECK(hipGetLastError());
-    }
-    ev.mark(1, st);
+    hu::DeviceArray<unsigned long long> colors;  // [slots] coloured calls: the mask
+    hu::DeviceArray<uint8_t> rec_colors;         // [n_rec] coloured calls
+    hu::DeviceArray<uint32_t> count;             // [slots] counted calls: the abundance
+    hu::DeviceArray<unsigned long long> table;   // [slots] = ka.table
+};
+// the instance of a kernel for the rung of the call (the arrays of a rung the call does not climb are null) and for k
+void launch_insert(const Work &w, const KmerTable &kt) {
+    const bool wide = w.k >= 32;
+    auto *kernel = kt.colors  ? (wide ? insert_kernel<true, true, true> : insert_kernel<false, true, true>)
+                   : kt.count ? (wide ? insert_kernel<true, true, false> : insert_kernel<false, true, false>)
+                              : (wide ? insert_kernel<true, false, false> : insert_kernel<false, false, false>);
+    kernel<<<hu::grid_for((w.n_bases + RUN - 1) / RUN), hu::EB, 0, w.st>>>(kt.ka, w.n_bases, w.c.rq.n_rec, w.err(), kt.count, kt.rec_colors, kt.colors);
+    HIP_CHECK(hipGetLastError());
+}
+void launch_mark(const Work &w, const KmerTable &kt, uint32_t *flag) {
+    auto *kernel = kt.count ? mark_kernel<true> : mark_kernel<false>;
+    kernel<<<(unsigned)std::min<uint64_t>(hu::grid_for(w.slots), 16384), hu::EB, 0, w.st>>>(kt.table, w.slots, flag, w.small.d + 2, kt.count, w.c.m);
+    HIP_CHECK(hipGetLastError());
+}
+void launch_kpos(const Work &w, const KmerTable &kt, const uint32_t *id_of_pos) {
+    auto *kernel = kpos_kernel<true, true>;
+    if (!kt.colors) kernel = kt.count ? kpos_kernel<true, false> : kpos_kernel<false, false>;
+    kernel<<<hu::grid_for(w.slots), hu::EB, 0, w.st>>>(kt.table, w.slots, id_of_pos, w.kpos, kt.count, w.c.m, w.kcount, kt.colors, w.kcolor);
+    HIP_CHECK(hipGetLastError());
+}
 
-    // ---- counted calls: the spectrum, before the filter ----
-    if (counted) {
-        unsigned long long *d_spec = nullptr;
+// Stage 2, insert: the creator of every k-mer class; a counted call also gets, from one sweep of the abundances per slot, the spectrum
+// before the filter (booked under ids_ms: mark 1 lies in front of it).
+KmerTable insert(Work &w) {
+    Call &c = w.c;
+    const uint64_t slots = w.slots = std::max<uint64_t>(8, (2 * c.r.windows + 7) / 8 * 8), n_rec = c.rq.n_rec;
+    KmerTable kt;
+    kt.ka.packed = w.seq.packed; kt.ka.off = w.seq.off; kt.ka.slots = slots;
+    kw::window_args_set_k(kt.ka, w.k);
+    kt.ka.table = kt.table.alloc(slots);
+    HIP_CHECK(hipMemsetAsync(kt.table, 0xFF, slots * 8, w.st));
+    if (c.rq.counted) {
+        kt.count.alloc(slots);
+        HIP_CHECK(hipMemsetAsync(kt.count, 0, slots * 4, w.st));
+    }
+    if (c.rq.colored) {
+        kt.rec_colors.alloc(n_rec);
+        kt.colors.alloc(slots);
+        hu::upload_sliced(kt.rec_colors, c.rq.colored->record_colors, n_rec, w.st, c.rq.device_id);
+        HIP_CHECK(hipMemsetAsync(kt.colors, 0, slots * 8, w.st));
+    }
+    launch_insert(w, kt);
+    w.ev.mark(1, w.st);
+    if (c.rq.counted) {
         std::vector<unsigned long long> h_spec(SPECTRUM_BINS + 2);
-        hu::device_malloc(&d_spec, h_spec.size() * 8);
-        HIP_CHECK(hipMemsetAsync(d_spec, 0, h_spec.size() * 8, st));
-        spectrum_kernel<<<(unsigned)std::min<uint64_t>(hu::grid_for(slots), 4096), hu::EB, 0, st>>>(d_count, slots, counted->m, d_spec);
+        hu::DeviceArray<unsigned long long> spec(h_spec.size());
+        HIP_CHECK(hipMemsetAsync(spec, 0, h_spec.size() * 8, w.st));
+        spectrum_kernel<<<(unsigned)std::min<uint64_t>(hu::grid_for(slots), 4096), hu::EB, 0, w.st>>>(kt.count, slots, c.m, spec);
         HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpyAsync(h_spec.data(), d_spec, h_spec.size() * 8, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipStreamSynchronize(st));
-        hu::device_free(d_spec);
-        for (int c = 0; c < SPECTRUM_BINS; c++) ab.distinct_all += ab.spectrum[c] = h_spec[c];
-        ab.max_abundance = h_spec[SPECTRUM_BINS];
-        ab.kept_occurrences = h_spec[SPECTRUM_BINS + 1];
+        HIP_CHECK(hipMemcpyAsync(h_spec.data(), spec, h_spec.size() * 8, hipMemcpyDeviceToHost, w.st));
+        HIP_CHECK(hipStreamSynchronize(w.st));
+        for (int b = 0; b < SPECTRUM_BINS; b++) c.ab.distinct_all += c.ab.spectrum[b] = h_spec[b];
+        c.ab.max_abundance = h_spec[SPECTRUM_BINS];
+        c.ab.kept_occurrences = h_spec[SPECTRUM_BINS + 1];
     }
+    return kt;
+}
 
-    // ---- ids in creator order ----
-    uint32_t *d_id_of_pos = nullptr;
-    hu::device_malloc(&d_id_of_pos, n_bases * 4);
-    HIP_CHECK(hipMemsetAsync(d_id_of_pos, 0, n_bases * 4, st));
-    {
-        const unsigned grid = (unsigned)std::min<uint64_t>(hu::grid_for(slots), 16384);
-        if (counted) mark_kernel<true><<<grid, hu::EB, 0, st>>>(ka.table, slots, d_id_of_pos, small.d + 2, d_count, counted->m);
-        else mark_kernel<false><<<grid, hu::EB, 0, st>>>(ka.table, slots, d_id_of_pos, small.d + 2, nullptr, 0);
-    }
-    HIP_CHECK(hipGetLastError());
-    small.read(st, stage);
-    uint64_t N = r.distinct_kmers = small.h[2], n_or = 2 * N;  // (a cleaned call: they shrink with the rounds)
+// Stage 3, ids: the creators flagged and scanned -> dense ids in creator order: N, kpos (kcount, kcolor). false: no k-mer is kept
+// (a counted call whose threshold none reaches). The flags and the scan's scratch go back here, the table with the caller's scope.
+bool ids(Work &w, const KmerTable &kt) {
+    Call &c = w.c;
+    hu::DeviceArray<uint32_t> id_of_pos(w.n_bases);
+    HIP_CHECK(hipMemsetAsync(id_of_pos, 0, w.n_bases * 4, w.st));
+    launch_mark(w, kt, id_of_pos);
+    w.small.read(w.st, STAGE);
+    c.t.insert_ms = w.ev.ms(0, 1);  // (over: the read has waited for the stream)
+    const uint64_t N = w.N = c.r.distinct_kmers = w.small.h[2];
     if (N > MAX_KMERS) MTG_DIE("mtg_compact_unitigs: %llu distinct k-mers; oriented k-mer ids are 32-bit", (unsigned long long)N);
-    if (counted) ab.distinct_kept = N;
-    if (N == 0) {  // (counted calls only: no k-mer reaches the threshold)
-        free_all({ka.table, d_id_of_pos, d_count, d_rec_colors, d_colors});
-        t.insert_ms = ev.ms(0, 1);
-        return finish();
+    if (c.rq.counted) c.ab.distinct_kept = N;
+    if (N == 0) return false;
+    hu::ScanScratch<uint32_t> scan(w.n_bases);
+    w.kpos.alloc(N);
+    scan.scan(w.st, id_of_pos, w.n_bases, id_of_pos);
+    if (c.rq.counted) w.kcount.alloc(N);
+    if (c.rq.colored) w.kcolor.alloc(N);
+    launch_kpos(w, kt, id_of_pos);
+    w.ev.mark(2, w.st);
+    return true;
+}
+
+// Stage 4, nodes: the table of T's (k-1)-mer classes with their incident words, and room for succ
+void build_nodes(Work &w) {
+    const uint64_t slots = std::max<uint64_t>(8, 4 * w.N);
+    w.nodes.table.alloc(slots);
+    w.nodes.out_e.alloc(slots);
+    w.nodes.in_e.alloc(slots);
+    w.succ.alloc(w.n_or());
+    HIP_CHECK(hipMemsetAsync(w.nodes.table, 0xFF, slots * 8, w.st));
+    HIP_CHECK(hipMemsetAsync(w.nodes.out_e, 0xFF, slots * 4, w.st));
+    HIP_CHECK(hipMemsetAsync(w.nodes.in_e, 0xFF, slots * 4, w.st));
+    node_insert_kernel<<<hu::grid_for(w.N), hu::EB, 0, w.st>>>(w.node_args(), w.err());
+}
+// at most max_rounds rounds of pointer jumping over all n elements or those of `list` -> true: settled
+bool jump_rounds(Work &w, uint64_t n, const uint32_t *list, int max_rounds) {
+    unsigned int *d_changed = reinterpret_cast<unsigned int *>(w.small.d + 3);
+    for (int i = 0; i < max_rounds; i++) {
+        HIP_CHECK(hipMemsetAsync(d_changed, 0, 4, w.st));
+        jump_kernel<<<hu::grid_for(n), hu::EB, 0, w.st>>>(w.pairs, n, list, d_changed);
+        HIP_CHECK(hipGetLastError());
+        w.c.t.rounds++;
+        w.small.read(w.st, STAGE);
+        if (!(w.small.h[3] & 0xFFFFFFFFull)) return true;
     }
-    uint32_t *d_bsum32 = nullptr;
-    unsigned long long *d_kpos = nullptr;
-    hu::device_malloc(&d_bsum32, (hu::scan_blocks(n_bases) + 2) * 4);
-    hu::device_malloc(&d_kpos, N * 8);
-    hu::scan_u32<uint32_t>(st, d_id_of_pos, n_bases, d_id_of_pos, d_bsum32, d_bsum32 + hu::scan_blocks(n_bases) + 1);
-    if (colored) {
-        hu::device_malloc(&d_kcount, N * 4);
-        hu::device_malloc(&d_kcolor, N * 8);
-        kpos_kernel<true, true><<<hu::grid_for(slots), hu::EB, 0, st>>>(ka.table, slots, d_id_of_pos, d_kpos, d_count, counted->m, d_kcount, d_colors, d_kcolor);
-    } else if (counted) {
-        hu::device_malloc(&d_kcount, N * 4);
-        kpos_kernel<true, false><<<hu::grid_for(slots), hu::EB, 0, st>>>(ka.table, slots, d_id_of_pos, d_kpos, d_count, counted->m, d_kcount, nullptr, nullptr);
+    return false;
+}
+// What still moves once every chain has settled lies on closed walks: list, minimum per cycle, cut in front of it, rank like chains.
+void rank_closed_walks(Work &w, bool again) {
+    const uint64_t n_or = w.n_or();
+    hu::DeviceArray<uint32_t> list(n_or);
+    if (again) HIP_CHECK(hipMemsetAsync(w.small.d + 4, 0, 8, w.st));  // (an earlier ranking has counted its own)
+    cycle_list_kernel<<<hu::grid_for(n_or), hu::EB, 0, w.st>>>(w.pairs, w.succ, n_or, list, w.small.d + 4);
+    HIP_CHECK(hipGetLastError());
+    w.small.read(w.st, STAGE);
+    const uint64_t C = w.small.h[4];
+    if (C == 0 || C > n_or) MTG_DIE("unitig compaction: internal error (%llu elements on closed walks)", (unsigned long long)C);
+    hu::DeviceArray<unsigned long long> buf(n_or);
+    cycle_min_init_kernel<<<hu::grid_for(C), hu::EB, 0, w.st>>>(w.succ, list, C, w.pairs);
+    unsigned long long *src = w.pairs, *dst = buf;
+    for (int i = 0, n = log2_ceil(C); i < n; i++, w.c.t.rounds++) {
+        cycle_min_kernel<<<hu::grid_for(C), hu::EB, 0, w.st>>>(src, dst, list, C);
+        std::swap(src, dst);
+    }
+    cycle_cut_kernel<<<hu::grid_for(C), hu::EB, 0, w.st>>>(src, w.succ, list, C, w.pairs);
+    HIP_CHECK(hipGetLastError());
+    if (!jump_rounds(w, C, list, log2_ceil(C) + 2)) MTG_DIE("unitig compaction: internal error (a cut cycle does not settle)");
+}
+// Stage 5, rank: pointer jumping over succ
+void rank(Work &w) {
+    const bool again = w.rankings++ > 0;
+    if (!w.pairs) w.pairs.alloc(w.n_or());
+    rank_init_kernel<<<hu::grid_for(w.n_or()), hu::EB, 0, w.st>>>(w.succ, w.n_or(), w.pairs);
+    HIP_CHECK(hipGetLastError());
+    if (!jump_rounds(w, w.n_or(), nullptr, log2_ceil(w.n_or()) + 2)) rank_closed_walks(w, again);
+}
+// Stages 4 and 5 over T. ROUND: a cleaning round's pass -- unsplit, and the node table stays for the decision to probe; FINAL: the
+// pass emit reads; SPLIT_AGAIN: succ<true> and rank once more over the node table of a round that removed nothing.
+enum class Pass { ROUND, FINAL, SPLIT_AGAIN };
+void pass(Work &w, Pass kind) {
+    PhaseEvents<3> pe;
+    pe.mark(0, w.st);
+    if (kind != Pass::SPLIT_AGAIN) build_nodes(w);
+    if (w.c.split && kind != Pass::ROUND) succ_kernel<true><<<hu::grid_for(w.N), hu::EB, 0, w.st>>>(w.node_args(), w.err(), w.kcolor);
+    else succ_kernel<false><<<hu::grid_for(w.N), hu::EB, 0, w.st>>>(w.node_args(), w.err(), nullptr);
+    HIP_CHECK(hipGetLastError());
+    pe.mark(1, w.st);
+    if (kind != Pass::ROUND) w.nodes = NodeTable{};  // (it goes back in front of rank; a round's decision probes it once more)
+    if (kind != Pass::SPLIT_AGAIN) w.small.read(w.st, STAGE);
+    rank(w);
+    pe.mark(2, w.st);
+    w.c.t.nodes_ms += pe.ms(0, 1);
+    w.c.t.rank_ms += pe.ms(1, 2);
+}
+
+// Stage 6, one cleaning round on the snapshot of pass(ROUND): verdicts per walk end (tips and isolated walks, then the weaker arms
+// of bubbles), keep flags per k-mer (keep: [N], for the move). Books the round's counters and times -> the k-mers it removes.
+uint64_t clean_round(Work &w, hu::DeviceArray<uint32_t> &keep) {
+    Call &c = w.c;
+    const uint64_t N = w.N, n_or = w.n_or();
+    PhaseEvents<2> ce;
+    unsigned long long h[CLEAN_COUNTERS] = {};
+    hu::DeviceArray<uint8_t> verdict(n_or);
+    keep.alloc(N);
+    hu::DeviceArray<unsigned long long> counters(CLEAN_COUNTERS);
+    HIP_CHECK(hipMemsetAsync(verdict, 0, n_or, w.st));
+    HIP_CHECK(hipMemsetAsync(counters, 0, sizeof h, w.st));
+    ce.mark(0, w.st);
+    clean_decide_kernel<<<hu::grid_for(n_or), hu::EB, 0, w.st>>>(w.node_args(), w.pairs, n_or, c.rq.cleaned->params.tip_kmers, c.rq.cleaned->params.isolated_kmers,
+                                                                verdict, counters, w.err());
+    double round_bubble_ms = 0;
+    if (c.popping) {  // (the same snapshot: tips and arms are disjoint, both of an arm's ends are anchored)
+        PhaseEvents<2> be;
+        be.mark(0, w.st);
+        pop_bubbles(w.node_args(), w.pairs, w.kcount, c.rq.bubbles->params, verdict, counters + 7, w.err(), w.st);
+        be.mark(1, w.st);
+        clean_keep_kernel<true><<<hu::grid_for(N), hu::EB, 0, w.st>>>(w.pairs, verdict, w.kcount, N, keep, counters);
+        round_bubble_ms = be.ms(0, 1);
     } else {
-        kpos_kernel<false, false><<<hu::grid_for(slots), hu::EB, 0, st>>>(ka.table, slots, d_id_of_pos, d_kpos, nullptr, 0, nullptr, nullptr, nullptr);
+        clean_keep_kernel<false><<<hu::grid_for(N), hu::EB, 0, w.st>>>(w.pairs, verdict, w.kcount, N, keep, counters);
     }
     HIP_CHECK(hipGetLastError());
-    ev.mark(2, st);
-    free_all({ka.table, d_id_of_pos, d_bsum32, d_count, d_rec_colors, d_colors});
-
-    // ---- the (k-1)-mer classes, succ and the ranks: once, or in a cleaned call once per round and once more over the final set ----
-    NodeArgs na{};
-    na.packed = d_packed; na.L = k - 1;
-    unsigned long long *d_pairs = nullptr;
-    int rounds = 0, rankings = 0;
-    double nodes_ms = 0, rank_ms = 0;
-    const bool split = classed && classed->split;
-    auto run_succ = [&](bool cut_at_colours) {
-        if (cut_at_colours) succ_kernel<true><<<hu::grid_for(N), hu::EB, 0, st>>>(na, d_err, d_kcolor);
-        else succ_kernel<false><<<hu::grid_for(N), hu::EB, 0, st>>>(na, d_err, nullptr);
+    ce.mark(1, w.st);
+    HIP_CHECK(hipMemcpyAsync(h, counters, sizeof h, hipMemcpyDeviceToHost, w.st));
+    w.small.read(w.st, STAGE);
+    c.clean_ms += ce.ms(0, 1) - round_bubble_ms;  // (nested marks on one stream)
+    c.bubble_ms += round_bubble_ms;
+    c.clean.rounds_run++;
+    c.clean.tips += h[0];
+    c.clean.isolated += h[1];
+    c.clean.tip_kmers += h[2];
+    c.clean.isolated_kmers += h[3];
+    c.clean.removed_occurrences += h[4];
+    c.popped.arm_kmers += h[5];
+    c.popped.removed_occurrences += h[6];
+    c.popped.arms += h[7];
+    const uint64_t removed = h[2] + h[3] + h[5];
+    if (removed > N) MTG_DIE("unitig compaction: internal error (%llu of %llu k-mers removed)", (unsigned long long)removed, (unsigned long long)N);
+    return removed;
+}
+// Stage 7: the scan of the keep flags gives the survivors' new ids (creator order is kept); kpos, kcount and kcolor move there and T
+// shrinks. The node table, succ and the pairs of the old ids are gone by now.
+void move_survivors(Work &w, const uint32_t *keep, uint64_t removed) {
+    Call &c = w.c;
+    const uint64_t N = w.N, N_left = N - removed;
+    if (N_left) {
+        PhaseEvents<2> me;
+        hu::DeviceArray<uint32_t> new_id(N);
+        hu::ScanScratch<uint32_t> scan(N);
+        hu::DeviceArray<unsigned long long> kpos_to(N_left), kcolor_to;
+        hu::DeviceArray<uint32_t> kcount_to;
+        if (w.kcount) kcount_to.alloc(N_left);
+        if (w.kcolor) kcolor_to.alloc(N_left);
+        uint32_t n_left = 0;
+        me.mark(0, w.st);
+        scan.scan(w.st, keep, N, new_id);
+        clean_move_kernel<<<hu::grid_for(N), hu::EB, 0, w.st>>>(keep, new_id, N, w.kpos, w.kcount, w.kcolor, kpos_to, kcount_to, kcolor_to);
         HIP_CHECK(hipGetLastError());
-    };
-    auto free_nodes = [&]() {
-        free_all({na.table, na.out_e, na.in_e});
-        na.table = nullptr;
-        na.out_e = na.in_e = nullptr;
-    };
-    auto jump_rounds = [&](uint64_t n, const uint32_t *list, int max_rounds) {  // true: settled
-        for (int i = 0; i < max_rounds; i++) {
-            HIP_CHECK(hipMemsetAsync(d_changed, 0, 4, st));
-            jump_kernel<<<hu::grid_for(n), hu::EB, 0, st>>>(d_pairs, n, list, d_changed);
-            HIP_CHECK(hipGetLastError());
-            rounds++;
-            small.read(st, stage);
-            if (!(small.h[3] & 0xFFFFFFFFull)) return true;
-        }
-        return false;
-    };
-    auto run_rank = [&]() {  // ranks by pointer jumping over na.succ
-        const bool again = rankings++ > 0;
-        if (!d_pairs) hu::device_malloc(&d_pairs, n_or * 8);
-        rank_init_kernel<<<hu::grid_for(n_or), hu::EB, 0, st>>>(na.succ, n_or, d_pairs);
-        HIP_CHECK(hipGetLastError());
-        if (jump_rounds(n_or, nullptr, log2_ceil(n_or) + 2)) return;
-        uint32_t *d_list = nullptr;  // closed walks
-        unsigned long long *d_buf = nullptr;
-        hu::device_malloc(&d_list, n_or * 4);
-        if (again) HIP_CHECK(hipMemsetAsync(small.d + 4, 0, 8, st));  // (an earlier ranking has counted its own)
-        cycle_list_kernel<<<hu::grid_for(n_or), hu::EB, 0, st>>>(d_pairs, na.succ, n_or, d_list, small.d + 4);
-        HIP_CHECK(hipGetLastError());
-        small.read(st, stage);
-        const uint64_t C = small.h[4];
-        if (C == 0 || C > n_or) MTG_DIE("unitig compaction: internal error (%llu elements on closed walks)", (unsigned long long)C);
-        hu::device_malloc(&d_buf, n_or * 8);
-        cycle_min_init_kernel<<<hu::grid_for(C), hu::EB, 0, st>>>(na.succ, d_list, C, d_pairs);
-        unsigned long long *src = d_pairs, *dst = d_buf;
-        for (int i = 0, n = log2_ceil(C); i < n; i++, rounds++) {
-            cycle_min_kernel<<<hu::grid_for(C), hu::EB, 0, st>>>(src, dst, d_list, C);
-            std::swap(src, dst);
-        }
-        cycle_cut_kernel<<<hu::grid_for(C), hu::EB, 0, st>>>(src, na.succ, d_list, C, d_pairs);
-        HIP_CHECK(hipGetLastError());
-        if (!jump_rounds(C, d_list, log2_ceil(C) + 2)) MTG_DIE("unitig compaction: internal error (a cut cycle does not settle)");
-        free_all({d_list, d_buf});
-    };
-    for (bool final_pass = !cleaning;;) {
-        PhaseEvents<3> pe;
-        pe.mark(0, st);
-        na.kpos = d_kpos; na.N = N;
-        na.slots = std::max<uint64_t>(8, 4 * N);  // at most 2 N classes
-        hu::device_malloc(&na.table, na.slots * 8);
-        hu::device_malloc(&na.out_e, na.slots * 4);
-        hu::device_malloc(&na.in_e, na.slots * 4);
-        hu::device_malloc(&na.succ, n_or * 4);
-        HIP_CHECK(hipMemsetAsync(na.table, 0xFF, na.slots * 8, st));
-        HIP_CHECK(hipMemsetAsync(na.out_e, 0xFF, na.slots * 4, st));
-        HIP_CHECK(hipMemsetAsync(na.in_e, 0xFF, na.slots * 4, st));
-        node_insert_kernel<<<hu::grid_for(N), hu::EB, 0, st>>>(na, d_err);
-        run_succ(split && final_pass);  // (a round decides on the unsplit unitigs)
-        pe.mark(1, st);
-        if (final_pass) free_nodes();  // (a round's decision probes the table once more)
-        small.read(st, stage);
-        run_rank();
-        pe.mark(2, st);
-        nodes_ms += pe.ms(0, 1);
-        rank_ms += pe.ms(1, 2);
-        if (final_pass) break;
-
-        // ---- one round: verdicts per walk end, keep flags per k-mer, the survivors' new ids ----
-        PhaseEvents<4> ce;
-        uint8_t *d_verdict = nullptr;
-        uint32_t *d_keep = nullptr, *d_new_id = nullptr, *d_bsum_keep = nullptr;
-        unsigned long long *d_counters = nullptr;
-        unsigned long long h_counters[CLEAN_COUNTERS] = {};
-        hu::device_malloc(&d_verdict, n_or);
-        hu::device_malloc(&d_keep, N * 4);
-        hu::device_malloc(&d_counters, sizeof h_counters);
-        HIP_CHECK(hipMemsetAsync(d_verdict, 0, n_or, st));
-        HIP_CHECK(hipMemsetAsync(d_counters, 0, sizeof h_counters, st));
-        ce.mark(0, st);
-        clean_decide_kernel<<<hu::grid_for(n_or), hu::EB, 0, st>>>(na, d_pairs, n_or, cleaned->params.tip_kmers, cleaned->params.isolated_kmers, d_verdict,
-                                                                  d_counters, d_err);
-        double round_bubble_ms = 0;
-        if (popping) {  // (the same snapshot: tips and arms are disjoint, both of an arm's ends are anchored)
-            PhaseEvents<2> be;
-            be.mark(0, st);
-            pop_bubbles(na, d_pairs, d_kcount, bubbles->params, d_verdict, d_counters + 7, d_err, st);
-            be.mark(1, st);
-            clean_keep_kernel<true><<<hu::grid_for(N), hu::EB, 0, st>>>(d_pairs, d_verdict, d_kcount, N, d_keep, d_counters);
-            round_bubble_ms = be.ms(0, 1);
-        } else {
-            clean_keep_kernel<false><<<hu::grid_for(N), hu::EB, 0, st>>>(d_pairs, d_verdict, d_kcount, N, d_keep, d_counters);
-        }
-        HIP_CHECK(hipGetLastError());
-        ce.mark(1, st);
-        HIP_CHECK(hipMemcpyAsync(h_counters, d_counters, sizeof h_counters, hipMemcpyDeviceToHost, st));
-        small.read(st, stage);
-        clean_ms += ce.ms(0, 1) - round_bubble_ms;  // (nested marks on one stream)
-        bubble_ms += round_bubble_ms;
-        free_all({d_verdict, d_counters});
-        clean.rounds_run++;
-        clean.tips += h_counters[0];
-        clean.isolated += h_counters[1];
-        clean.tip_kmers += h_counters[2];
-        clean.isolated_kmers += h_counters[3];
-        clean.removed_occurrences += h_counters[4];
-        popped.arm_kmers += h_counters[5];
-        popped.removed_occurrences += h_counters[6];
-        popped.arms += h_counters[7];
-        const uint64_t removed = h_counters[2] + h_counters[3] + h_counters[5];
-        if (removed > N) MTG_DIE("unitig compaction: internal error (%llu of %llu k-mers removed)", (unsigned long long)removed, (unsigned long long)N);
-        if (removed == 0) {  // the set is final: so are succ and the ranks, unless the unitigs are to be split
-            hu::device_free(d_keep);
-            if (split) {
-                PhaseEvents<3> fe;
-                fe.mark(0, st);
-                run_succ(true);
-                fe.mark(1, st);
-                free_nodes();
-                run_rank();
-                fe.mark(2, st);
-                nodes_ms += fe.ms(0, 1);
-                rank_ms += fe.ms(1, 2);
-            } else {
-                free_nodes();
-            }
-            break;
-        }
-        free_nodes();
-        free_all({na.succ, d_pairs});
-        na.succ = nullptr;
-        d_pairs = nullptr;
-        const uint64_t N_left = N - removed;
-        if (N_left) {
-            unsigned long long *d_kpos_to = nullptr, *d_kcolor_to = nullptr;
-            uint32_t *d_kcount_to = nullptr;
-            hu::device_malloc(&d_new_id, N * 4);
-            hu::device_malloc(&d_bsum_keep, (hu::scan_blocks(N) + 2) * 4);
-            hu::device_malloc(&d_kpos_to, N_left * 8);
-            if (d_kcount) hu::device_malloc(&d_kcount_to, N_left * 4);
-            if (d_kcolor) hu::device_malloc(&d_kcolor_to, N_left * 8);
-            uint32_t *d_n_left = d_bsum_keep + hu::scan_blocks(N) + 1;
-            uint32_t n_left = 0;
-            ce.mark(2, st);
-            hu::scan_u32<uint32_t>(st, d_keep, N, d_new_id, d_bsum_keep, d_n_left);
-            clean_move_kernel<<<hu::grid_for(N), hu::EB, 0, st>>>(d_keep, d_new_id, N, d_kpos, d_kcount, d_kcolor, d_kpos_to, d_kcount_to, d_kcolor_to);
-            HIP_CHECK(hipGetLastError());
-            ce.mark(3, st);
-            HIP_CHECK(hipMemcpyAsync(&n_left, d_n_left, 4, hipMemcpyDeviceToHost, st));
-            HIP_CHECK(hipStreamSynchronize(st));
-            clean_ms += ce.ms(2, 3);
-            if (n_left != N_left) MTG_DIE("unitig compaction: internal error (%llu k-mers kept, %llu counted)", (unsigned long long)n_left, (unsigned long long)N_left);
-            free_all({d_kpos, d_kcount, d_kcolor, d_new_id, d_bsum_keep});
-            d_kpos = d_kpos_to;
-            d_kcount = d_kcount_to;
-            d_kcolor = d_kcolor_to;
-        }
-        hu::device_free(d_keep);
-        N = r.distinct_kmers = N_left;
-        n_or = 2 * N;
-        if (N == 0) {  // everything was a tip or isolated (an arm's best stays: popping alone never gets here)
-            free_all({d_kpos, d_kcount, d_kcolor});
-            t.insert_ms = ev.ms(0, 1);
-            t.ids_ms = ev.ms(1, 2);
-            t.nodes_ms = nodes_ms;
-            t.rank_ms = rank_ms;
-            t.rounds = rounds;
-            return finish();
-        }
-        final_pass = clean.rounds_run == cleaned->params.rounds;
+        me.mark(1, w.st);
+        HIP_CHECK(hipMemcpyAsync(&n_left, scan.total(), 4, hipMemcpyDeviceToHost, w.st));
+        HIP_CHECK(hipStreamSynchronize(w.st));
+        c.clean_ms += me.ms(0, 1);
+        if (n_left != N_left) MTG_DIE("unitig compaction: internal error (%llu k-mers kept, %llu counted)", (unsigned long long)n_left, (unsigned long long)N_left);
+        w.kpos = std::move(kpos_to);
+        w.kcount = std::move(kcount_to);
+        w.kcolor = std::move(kcolor_to);
     }
-    ev.mark(3, st);
-
-    // ---- emit ----
-    uint32_t *d_wmin = nullptr, *d_wlen = nullptr, *d_lead_flag = nullptr, *d_lead_chars = nullptr;
-    uint64_t *d_char_off = nullptr, *d_bsum64 = nullptr;
-    hu::device_malloc(&d_wmin, n_or * 4);
-    hu::device_malloc(&d_wlen, n_or * 4);
-    hu::device_malloc(&d_lead_flag, N * 4);
-    hu::device_malloc(&d_lead_chars, N * 4);
-    hu::device_malloc(&d_char_off, N * 8);
-    hu::device_malloc(&d_bsum32, (hu::scan_blocks(N) + 2) * 4);
-    hu::device_malloc(&d_bsum64, (hu::scan_blocks(N) + 2) * 8);
-    HIP_CHECK(hipMemsetAsync(d_wmin, 0xFF, n_or * 4, st));
-    HIP_CHECK(hipMemsetAsync(d_wlen, 0, n_or * 4, st));
-    HIP_CHECK(hipMemsetAsync(d_lead_flag, 0, N * 4, st));
-    HIP_CHECK(hipMemsetAsync(d_lead_chars, 0, N * 4, st));
-    walk_kernel<<<hu::grid_for(n_or), hu::EB, 0, st>>>(d_pairs, na.succ, n_or, d_wmin, d_wlen);
-    leader_kernel<<<hu::grid_for(n_or), hu::EB, 0, st>>>(d_pairs, na.succ, n_or, d_wmin, d_wlen, (uint32_t)k, d_lead_flag, d_lead_chars, small.d + 5);
-    uint32_t *d_n_unitigs = d_bsum32 + hu::scan_blocks(N) + 1;
-    uint64_t *d_n_chars = d_bsum64 + hu::scan_blocks(N) + 1;
-    hu::scan_u32<uint32_t>(st, d_lead_flag, N, d_lead_flag, d_bsum32, d_n_unitigs);
-    hu::scan_u32<uint64_t>(st, d_lead_chars, N, d_char_off, d_bsum64, d_n_chars);
-    uint32_t n_unitigs = 0;
+    w.N = c.r.distinct_kmers = N_left;
+}
+// The rounds of a cleaned call and how they end.
+enum class Rounds {
+    SETTLED,      // a round removed nothing: its succ and ranks are the final ones (after the extra pass where the unitigs are to be split)
+    USED_UP,      // the last allowed round removed something: one more pass over the survivors follows
+    NOTHING_LEFT  // everything was a tip or isolated (an arm's best stays: popping alone never gets here)
+};
+Rounds clean_rounds(Work &w) {
+    for (;;) {
+        pass(w, Pass::ROUND);
+        hu::DeviceArray<uint32_t> keep;
+        const uint64_t removed = clean_round(w, keep);
+        if (removed == 0) {
+            keep.release();
+            if (w.c.split) pass(w, Pass::SPLIT_AGAIN);
+            else w.nodes = NodeTable{};
+            return Rounds::SETTLED;
+        }
+        w.nodes = NodeTable{};
+        w.succ.release();
+        w.pairs.release();
+        move_survivors(w, keep, removed);
+        if (w.N == 0) return Rounds::NOTHING_LEFT;
+        if (w.c.clean.rounds_run == w.c.rq.cleaned->params.rounds) return Rounds::USED_UP;
+    }
+}
+// The device arrays of the output: those of emit, the sums of a counted call, the ordered masks and statistics of a coloured one.
+// They stay until the downloads are done.
+struct Output {
+    hu::DeviceArray<uint32_t> wmin, wlen, lead_flag, lead_chars;  // [2 N] per head, [N] per leader (lead_flag: scanned in place to the unitig number)
+    hu::DeviceArray<uint64_t> char_off;                           // [N]
+    hu::ScanScratch<uint32_t> scan32;                             // its total: the unitigs
+    hu::ScanScratch<uint64_t> scan64;                             // its total: the characters, then the occurrences
+    hu::DeviceArray<char> chars;
+    hu::DeviceArray<unsigned long long> off, sums, ordered_colors, color_stats;
+    hu::DeviceArray<uint32_t> ordered;  // counted calls: the abundances in unitig order
     uint64_t n_chars = 0;
-    HIP_CHECK(hipMemcpyAsync(&n_unitigs, d_n_unitigs, 4, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipMemcpyAsync(&n_chars, d_n_chars, 8, hipMemcpyDeviceToHost, st));
-    small.read(st, stage);
+    explicit Output(uint64_t N) : wmin(2 * N), wlen(2 * N), lead_flag(N), lead_chars(N), char_off(N), scan32(N), scan64(N) {}
+};
+// Stage 8, emit: walk, leader, the two scans, offsets, spell
+Output emit(Work &w) {
+    mtg_compaction &r = w.c.r;
+    const uint64_t N = w.N, n_or = w.n_or(), k = w.k;
+    Output o(N);
+    HIP_CHECK(hipMemsetAsync(o.wmin, 0xFF, n_or * 4, w.st));
+    HIP_CHECK(hipMemsetAsync(o.wlen, 0, n_or * 4, w.st));
+    HIP_CHECK(hipMemsetAsync(o.lead_flag, 0, N * 4, w.st));
+    HIP_CHECK(hipMemsetAsync(o.lead_chars, 0, N * 4, w.st));
+    walk_kernel<<<hu::grid_for(n_or), hu::EB, 0, w.st>>>(w.pairs, w.succ, n_or, o.wmin, o.wlen);
+    leader_kernel<<<hu::grid_for(n_or), hu::EB, 0, w.st>>>(w.pairs, w.succ, n_or, o.wmin, o.wlen, (uint32_t)k, o.lead_flag, o.lead_chars, w.small.d + 5);
+    o.scan32.scan(w.st, o.lead_flag, N, o.lead_flag);
+    o.scan64.scan(w.st, o.lead_chars, N, o.char_off);
+    uint32_t n_unitigs = 0;
+    HIP_CHECK(hipMemcpyAsync(&n_unitigs, o.scan32.total(), 4, hipMemcpyDeviceToHost, w.st));
+    HIP_CHECK(hipMemcpyAsync(&o.n_chars, o.scan64.total(), 8, hipMemcpyDeviceToHost, w.st));
+    w.small.read(w.st, STAGE);
     r.unitigs = n_unitigs;
-    r.unitig_characters = n_chars;
-    r.closed_walks = small.h[5];
-    r.longest_unitig_kmers = small.h[6];
-    if (n_chars != N + (k - 1) * r.unitigs) MTG_DIE("unitig compaction: internal error (%llu characters for %llu k-mers in %llu unitigs)",
-                                                    (unsigned long long)n_chars, (unsigned long long)N, (unsigned long long)r.unitigs);
-    char *d_out = nullptr;
-    unsigned long long *d_out_off = nullptr;
-    hu::device_malloc(&d_out, n_chars);
-    hu::device_malloc(&d_out_off, (r.unitigs + 1) * 8);
-    offsets_kernel<<<hu::grid_for(N), hu::EB, 0, st>>>(d_lead_chars, d_lead_flag, d_char_off, N, d_out_off);
-    spell_kernel<<<hu::grid_for(n_or), hu::EB, 0, st>>>(d_packed, d_kpos, d_pairs, d_wmin, d_char_off, n_or, k, d_out);
+    r.unitig_characters = o.n_chars;
+    r.closed_walks = w.small.h[5];
+    r.longest_unitig_kmers = w.small.h[6];
+    if (o.n_chars != N + (k - 1) * r.unitigs) MTG_DIE("unitig compaction: internal error (%llu characters for %llu k-mers in %llu unitigs)",
+                                                      (unsigned long long)o.n_chars, (unsigned long long)N, (unsigned long long)r.unitigs);
+    o.chars.alloc(o.n_chars);
+    o.off.alloc(r.unitigs + 1);
+    offsets_kernel<<<hu::grid_for(N), hu::EB, 0, w.st>>>(o.lead_chars, o.lead_flag, o.char_off, N, o.off);
+    spell_kernel<<<hu::grid_for(n_or), hu::EB, 0, w.st>>>(w.seq.packed, w.kpos, w.pairs, o.wmin, o.char_off, n_or, k, o.chars);
     HIP_CHECK(hipGetLastError());
-    unsigned long long *d_sums = nullptr;
-    uint32_t *d_ordered = nullptr;
-    if (counted) {  // the abundances in unitig order, their 64-bit prefix sums, differences at the unitig boundaries
-        uint64_t *d_prefix = nullptr;
-        hu::device_malloc(&d_ordered, N * 4);
-        hu::device_malloc(&d_prefix, N * 8);
-        hu::device_malloc(&d_sums, r.unitigs * 8);
-        order_counts_kernel<uint32_t><<<hu::grid_for(n_or), hu::EB, 0, st>>>(d_pairs, d_wmin, d_char_off, d_lead_flag, d_kcount, n_or, k, d_ordered);
-        hu::scan_u32<uint64_t>(st, d_ordered, N, d_prefix, d_bsum64, d_n_chars);  // (the block sums and the total's word are free again)
-        unitig_sums_kernel<<<hu::grid_for(r.unitigs), hu::EB, 0, st>>>(d_out_off, d_prefix, d_n_chars, r.unitigs, k, d_sums);
+    return o;
+}
+
+// Stage 9. Counted calls: the abundances in unitig order, their 64-bit prefix sums (emit's 64-bit scratch is free again, and N is
+// the same), differences at the unitig boundaries; `ordered` stays only where the call hands out the counts. Coloured calls: the
+// masks in unitig order, and the statistics over kcolor (any order serves).
+void sums_and_colors(Work &w, Output &o) {
+    const Counted *counted = w.c.rq.counted;
+    const Colored *colored = w.c.rq.colored;
+    const uint64_t N = w.N, n_or = w.n_or(), unitigs = w.c.r.unitigs;
+    if (counted) {
+        o.ordered.alloc(N);
+        hu::DeviceArray<uint64_t> prefix(N);
+        o.sums.alloc(unitigs);
+        order_counts_kernel<uint32_t><<<hu::grid_for(n_or), hu::EB, 0, w.st>>>(w.pairs, o.wmin, o.char_off, o.lead_flag, w.kcount, n_or, w.k, o.ordered);
+        o.scan64.scan(w.st, o.ordered, N, prefix);
+        unitig_sums_kernel<<<hu::grid_for(unitigs), hu::EB, 0, w.st>>>(o.off, prefix, o.scan64.total(), unitigs, w.k, o.sums);
         HIP_CHECK(hipGetLastError());
-        hu::device_free(d_prefix);
-        if (!counted->kmer_counts) {
-            hu::device_free(d_ordered);
-            d_ordered = nullptr;
-        }
+        if (!counted->kmer_counts) o.ordered.release();
     }
-    unsigned long long *d_ordered_colors = nullptr, *d_color_stats = nullptr;
-    if (colored) {  // the masks in unitig order, and the statistics over kcolor (any order serves)
+    if (colored) {
         PhaseEvents<2> ev_stats;
-        hu::device_malloc(&d_color_stats, COLOR_STATS_WORDS * 8);
-        hu::device_malloc(&d_ordered_colors, N * 8);
-        HIP_CHECK(hipMemsetAsync(d_color_stats, 0, COLOR_STATS_WORDS * 8, st));
-        order_counts_kernel<unsigned long long><<<hu::grid_for(n_or), hu::EB, 0, st>>>(d_pairs, d_wmin, d_char_off, d_lead_flag, d_kcolor, n_or, k,
-                                                                                         d_ordered_colors);
-        ev_stats.mark(0, st);
-        color_stats_kernel<<<(unsigned)std::min<uint64_t>(hu::grid_for(N), 512), hu::EB, 0, st>>>(d_kcolor, N, (int)colored->n_colors, d_color_stats);
-        ev_stats.mark(1, st);
+        o.color_stats.alloc(COLOR_STATS_WORDS);
+        o.ordered_colors.alloc(N);
+        HIP_CHECK(hipMemsetAsync(o.color_stats, 0, COLOR_STATS_WORDS * 8, w.st));
+        order_counts_kernel<unsigned long long><<<hu::grid_for(n_or), hu::EB, 0, w.st>>>(w.pairs, o.wmin, o.char_off, o.lead_flag, w.kcolor, n_or, w.k, o.ordered_colors);
+        ev_stats.mark(0, w.st);
+        color_stats_kernel<<<(unsigned)std::min<uint64_t>(hu::grid_for(N), 512), hu::EB, 0, w.st>>>(w.kcolor, N, (int)colored->n_colors, o.color_stats);
+        ev_stats.mark(1, w.st);
         HIP_CHECK(hipGetLastError());
         *colored->stats_ms = ev_stats.ms(0, 1);
     }
-    ev.mark(4, st);
-    HIP_CHECK(hipStreamSynchronize(st));
-    if (classed) color_classes(d_ordered_colors, d_out_off, N, r.unitigs, k, classed->split, st, small, device_id, classed->out, classed->times);
-
+}
+// Stage 10: the store, and what the rungs of the call hand out
+void download(Work &w, const Output &o) {
+    Call &c = w.c;
+    const Counted *counted = c.rq.counted;
+    const Colored *colored = c.rq.colored;
+    const uint64_t N = w.N, unitigs = c.r.unitigs;
+    const int device_id = c.rq.device_id;
     const auto t0 = std::chrono::steady_clock::now();
-    store->data.resize(n_chars);
-    store->off.resize(r.unitigs + 1);
-    hu::download_sliced(&store->data[0], d_out, n_chars, st, device_id);
-    hu::download_sliced(store->off.data(), d_out_off, r.unitigs * 8, st, device_id);
-    store->off[r.unitigs] = n_chars;
+    c.store->data.resize(o.n_chars);
+    c.store->off.resize(unitigs + 1);
+    hu::download_sliced(&c.store->data[0], o.chars, o.n_chars, w.st, device_id);
+    hu::download_sliced(c.store->off.data(), o.off, unitigs * 8, w.st, device_id);
+    c.store->off[unitigs] = o.n_chars;
     if (counted) {
-        counted->sums->resize(r.unitigs);
-        hu::download_sliced(counted->sums->data(), d_sums, r.unitigs * 8, st, device_id);
+        counted->sums->resize(unitigs);
+        hu::download_sliced(counted->sums->data(), o.sums, unitigs * 8, w.st, device_id);
         if (counted->kmer_counts) {  // (`ordered` itself: unitig order is the store's window order)
             counted->kmer_counts->resize(N);
-            hu::download_sliced(counted->kmer_counts->data(), d_ordered, N * 4, st, device_id);
+            hu::download_sliced(counted->kmer_counts->data(), o.ordered, N * 4, w.st, device_id);
         }
     }
     if (colored) {
         std::vector<unsigned long long> h(COLOR_STATS_WORDS);
-        hu::download_sliced(h.data(), d_color_stats, h.size() * 8, st, device_id);
+        hu::download_sliced(h.data(), o.color_stats, h.size() * 8, w.st, device_id);
         mtg_color_stats &cs = *colored->stats;
         for (int i = 0; i < MAX_COLORS; i++) {
             cs.per_color[i] = h[i * MAX_COLORS + i];
@@ -1497,43 +1508,70 @@ UnitigStore *compact(const char *data, const uint64_t *off, uint64_t n_rec, uint
         }
         for (int j = 0; j <= MAX_COLORS; j++) cs.occupancy[j] = h[COLOR_OCC + j];
         colored->kmer_colors->resize(N);
-        hu::download_sliced(colored->kmer_colors->data(), d_ordered_colors, N * 8, st, device_id);
+        hu::download_sliced(colored->kmer_colors->data(), o.ordered_colors, N * 8, w.st, device_id);
     }
-    t.download_ms = ms_since(t0);
-    t.insert_ms = ev.ms(0, 1);
-    t.ids_ms = ev.ms(1, 2);
-    t.nodes_ms = nodes_ms;
-    t.rank_ms = rank_ms;
-    t.emit_ms = ev.ms(3, 4);
-    t.rounds = rounds;
-    free_all({d_kpos, na.succ, d_pairs, d_wmin, d_wlen, d_lead_flag, d_lead_chars, d_char_off, d_bsum32, d_bsum64, d_out, d_out_off, d_kcount, d_sums, d_ordered, d_kcolor,
-              d_ordered_colors, d_color_stats});
+    c.t.download_ms = ms_since(t0);
+}
+
+// The stages of a call with bases, top to bottom. Every return leaves through finish(); what a stage booked by then is what the
+// call reports. Device arrays go back where their owner's scope ends: the k-mer table behind ids, everything else behind the downloads.
+void run(Call &c) {
+    const CompactRequest &q = c.rq;
+    if (c.r.characters >= POS_LIMIT) MTG_DIE("mtg_compact_unitigs: %llu bases; the limit is 2^40 - 2", (unsigned long long)c.r.characters);
+    if (q.device_id < 0 || device_count() <= q.device_id) MTG_DIE("no HIP device %d for the unitig compaction (there is no CPU path)", q.device_id);
+    HIP_CHECK(hipSetDevice(q.device_id));
+    device_arena_reset_peak(q.device_id);
+    Work w(c, nullptr);  // upload and pack
+    c.t.upload_ms = w.seq.upload_ms;
+    c.t.pack_ms = w.seq.pack_ms;
+    if (c.r.windows == 0) return;  // nothing is as long as k
+    w.ev.mark(0, w.st);
+    {
+        const KmerTable kt = insert(w);
+        if (!ids(w, kt)) return;
+    }
+    c.t.ids_ms = w.ev.ms(1, 2);
+    // nodes, succ and rank: once, or in a cleaned call once per round and, unless a round settled it, once more over the final set
+    const Rounds rounds = c.cleaning ? clean_rounds(w) : Rounds::USED_UP;
+    if (rounds == Rounds::NOTHING_LEFT) return;
+    if (rounds == Rounds::USED_UP) pass(w, Pass::FINAL);
+    w.ev.mark(3, w.st);
+    Output o = emit(w);
+    sums_and_colors(w, o);
+    w.ev.mark(4, w.st);
+    HIP_CHECK(hipStreamSynchronize(w.st));
+    if (q.classed) color_classes(o.ordered_colors, o.off, w.N, c.r.unitigs, w.k, q.classed->split, w.st, w.small, q.device_id, q.classed->out, q.classed->times);
+    download(w, o);
+    c.t.emit_ms = w.ev.ms(3, 4);
     uint64_t arena[4];
-    device_arena_stats(device_id, arena);
-    t.peak_arena_bytes = arena[2];
+    device_arena_stats(q.device_id, arena);
+    c.t.peak_arena_bytes = arena[2];
     // What the kernels must move at the least: ASCII read and packed store written; per window the packed bases once (2 bits) and one
     // slot; the table filled, then read twice (mark, kpos); per base the flag word written, scanned (read + written) and read per
     // creator; per distinct k-mer its creator written and read twice with 2 (k + 15) / 16 packed words each time, two node slots
     // and two incident words written and read, two succ words; per oriented k-mer one pair per round at the least (read), succ and the
     // pair in the emit kernels, wmin / wlen; per leader flag, length and offset; and the output characters and offsets.
-    t.bytes = n_bases + seq.n_words * 4 + r.windows * 8 + seq.n_words * 4 + slots * 8 * 3 + n_bases * 4 * 3 + N * 4 +
-              N * (8 * 3 + 2 * 4 * ((k + 15) / 16 + 1) + 2 * (8 + 4) * 2 + 8) + n_or * 8 * (uint64_t)std::max(rounds, 1) +
-              n_or * (4 + 8 + 8 + 8 + 4) + N * (4 * 3 + 4 * 2 + 8 * 2) + n_chars + r.unitigs * 8;  // (of a cleaned call: the final pass alone)
-    return finish();
+    const uint64_t n_bases = w.n_bases, N = w.N, n_or = w.n_or(), k = w.k;
+    c.t.bytes = n_bases + w.seq.n_words * 4 + c.r.windows * 8 + w.seq.n_words * 4 + w.slots * 8 * 3 + n_bases * 4 * 3 + N * 4 +
+                N * (8 * 3 + 2 * 4 * ((k + 15) / 16 + 1) + 2 * (8 + 4) * 2 + 8) + n_or * 8 * (uint64_t)std::max(c.t.rounds, 1) +
+                n_or * (4 + 8 + 8 + 8 + 4) + N * (4 * 3 + 4 * 2 + 8 * 2) + o.n_chars + c.r.unitigs * 8;  // (of a cleaned call: the final pass alone)
 }
 
 }  // namespace
 
 UnitigStore *device_compact_unitigs(const CompactRequest &rq) {
-    const Counted *c = rq.counted;
+    const Counted *cn = rq.counted;
     const Colored *col = rq.colored;
     const Classed *cl = rq.classed;
-    if ((c && !c->sums) || (col && (!c || !c->kmer_counts || !col->kmer_colors || !col->stats || !col->stats_ms)) ||
+    if ((cn && !cn->sums) || (col && (!cn || !cn->kmer_counts || !col->kmer_colors || !col->stats || !col->stats_ms)) ||
         (cl && (!col || !cl->out || !cl->times)))
         MTG_DIE("%s: null argument", rq.who);
     if (rq.cleaned && (!rq.cleaned->out || !rq.cleaned->clean_ms)) MTG_DIE("%s: null argument", rq.who);
     if (rq.bubbles && (!rq.bubbles->out || !rq.bubbles->bubble_ms)) MTG_DIE("%s: null argument", rq.who);
-    return compact(rq.data, rq.off, rq.n_rec, rq.k, rq.device_id, rq.stats_out, rq.times, c, col, cl, rq.cleaned, rq.bubbles);
+    Call c{rq};
+    check_request(c);
+    if (c.r.characters) run(c);
+    return finish(c);
 }
 
 void device_color_classes(const uint64_t *kmer_colors, uint64_t n, const uint64_t *unitig_kmers, uint64_t n_unitigs, int device_id, ColorClasses *out,
@@ -1556,14 +1594,10 @@ void device_color_classes(const uint64_t *kmer_colors, uint64_t n, const uint64_
     HIP_CHECK(hipSetDevice(device_id));
     hipStream_t st = nullptr;
     ScalarBlock small(st);
-    unsigned long long *d_masks = nullptr, *d_off = nullptr;
-    hu::device_malloc(&d_masks, n * 8);
-    hu::device_malloc(&d_off, (n_unitigs + 1) * 8);
+    hu::DeviceArray<unsigned long long> d_masks(n), d_off(n_unitigs + 1);
     hu::upload_sliced(d_masks, kmer_colors, n * 8, st, device_id);
     hu::upload_sliced(d_off, off.data(), (n_unitigs + 1) * 8, st, device_id);
     color_classes(d_masks, d_off, n, n_unitigs, 1, false, st, small, device_id, out, times);
-    hu::device_free(d_masks);
-    hu::device_free(d_off);
 }
 
 uint64_t device_color_class_limit(int which) { return which == 0 ? CLASS_LDS : which == 1 ? CLASS_GRID : hu::EB; }

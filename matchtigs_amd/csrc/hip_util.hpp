@@ -1,5 +1,5 @@
 // hip_util.hpp -- small device-side building blocks shared by the streaming HIP stages (finish_device.hip,
-// euler_device.hip, synth_device.hip): error check, stream-ordered buffers, a three-phase exclusive scan.
+// euler_device.hip, synth_device.hip): error check, stream-ordered buffers, owning arrays, a three-phase exclusive scan and its scratch.
 // Every kernel here is `static`: each translation unit that includes the header gets its own copy.
 #pragma once
 
@@ -410,6 +410,36 @@ inline void device_free_on(int device_id, const void *p) {
     device_arena(device_id).free(const_cast<void *>(p), false);
     (void)hipSetDevice(cur);
 }
+// n elements from device_malloc that go back through device_free (same meaning: the device is idle then) when the owner is
+// released, allocates again or leaves its scope. Move-only; kernels take the raw pointer.
+template <typename T>
+struct DeviceArray {
+    T *p = nullptr;
+    DeviceArray() = default;
+    explicit DeviceArray(uint64_t n) { alloc(n); }
+    DeviceArray(DeviceArray &&o) noexcept : p(o.p) { o.p = nullptr; }
+    DeviceArray &operator=(DeviceArray &&o) {
+        if (this != &o) { release(); p = o.p; o.p = nullptr; }
+        return *this;
+    }
+    ~DeviceArray() { release(); }
+    T *alloc(uint64_t n) { release(); device_malloc(&p, n * sizeof(T)); return p; }
+    void release() { device_free(p); p = nullptr; }
+    T *get() const { return p; }
+    operator T *() const { return p; }
+};
+// The scratch of scan_u32<T> for inputs of up to max_n elements: the block sums and, behind them, the total's word.
+template <typename T>
+struct ScanScratch {
+    uint64_t blocks;
+    DeviceArray<T> sums;  // [blocks + 1] block sums (scan_u32), [1] the total
+    explicit ScanScratch(uint64_t max_n) : blocks(scan_blocks(max_n)), sums(blocks + 2) {}
+    T *total() const { return sums.get() + blocks + 1; }  // the device word that holds the last scan's sum of all
+    void scan(hipStream_t st, const uint32_t *in, uint64_t n, T *out) {
+        if (scan_blocks(n) > blocks) MTG_DIE("internal error: a scan of %llu elements in scratch for %llu blocks", (unsigned long long)n, (unsigned long long)blocks);
+        scan_u32<T>(st, in, n, out, sums.get(), total());
+    }
+};
 
 // One stream per device for the finishing stages, created on first use.
 inline hipStream_t finish_stream(int device_id) {
