@@ -885,6 +885,29 @@ uint64_t mtg_write_walks_text_device(const mtg_graph *g, uint64_t n_walks, const
                                      char **text_out);
 double mtg_last_spell_kernel_ms(void); /* HIP-event time of the last spelling kernel on this thread */
 uint64_t mtg_last_spell_bytes(void);   /* HBM bytes it moved (text written + packed bases + per-position metadata) */
+/* ---- the unitig graph with its links, made on the GPU ------------------------------------------------------
+ * Unitig u (record u of the store) has two orientations: (u,+) is edge 2u, (u,-) is edge 2u + 1. Oriented unitig o links to o' iff
+ * from(edge o') == to(edge o); only the original edges count, so a tig computation that appended dummy edges changes nothing.
+ * mtg_unitig_links: *link_off gets 2U + 1 offsets, *link_to the target edge ids -- those of o are link_to[link_off[o] ..
+ * link_off[o + 1]), ascending. Both arrays are released with mtg_free. Returns the number of links. Aborts without a GPU. */
+uint64_t mtg_unitig_links(const mtg_graph *g, int device_id, uint64_t **link_off, uint32_t **link_to);
+/* The graph as text, written by one kernel on GPU `device_id`. gfa == 0: BCALM2/GGCAT FASTA, per unitig
+ * ">{u} LN:i:{len} KC:i:{KC} km:f:{km}" + " L:{+-}:{v}:{+-}" per link + "\n{sequence}\n" -- the links of (u,+) before those of
+ * (u,-), each ascending by target edge --; else GFA1: "H\tVN:Z:1.0\tKL:Z:{k}", then per unitig
+ * "S\t{u}\t{sequence}\tLN:i:{len}\tKC:i:{KC}\tkm:f:{km}" followed by its links "L\t{u}\t{+-}\t{v}\t{+-}\t{k-1}M".
+ * unitig_kc: the abundance sum of every unitig, or NULL for its number of k-mers; km = KC / k-mers with one decimal, rounded half up
+ * in integers. n_unitigs sequences of at least k bases each (ACGT, either case; written upper case), as many as the graph has
+ * unitigs. *text_out is released with mtg_free. Returns the bytes. Aborts without a GPU. */
+uint64_t mtg_write_unitig_graph_text(const mtg_graph *g, const char *unitig_seqs, const uint64_t *seq_offsets, uint64_t n_unitigs,
+                                     uint64_t k, const uint64_t *unitig_kc, int gfa, int device_id, char **text_out);
+/* The same text into a file; a ".gz" suffix selects gzip at compression_level 0-9. Returns the uncompressed byte count. */
+uint64_t mtg_write_unitig_graph_file(const mtg_graph *g, const char *unitig_seqs, const uint64_t *seq_offsets, uint64_t n_unitigs,
+                                     uint64_t k, const uint64_t *unitig_kc, int gfa, int device_id, const char *path,
+                                     int compression_level);
+/* Of the last of the three calls above on this thread: {upload (host clock, ms), link kernels, scans of the text, text kernel -- HIP
+ * events, ms --, download (host clock, ms), links, bytes of the text, bytes the text kernel must move at the least, peak of the
+ * device arena's live bytes}. */
+void mtg_last_unitig_graph_times(double out[9]);
 /* Duplication bitvectors (implementation/mod.rs:668-702): one line per tig with `weight` characters per edge, '1' for an
  * original edge and '0' for a dummy edge (k-mers that repeat ones spelled elsewhere). */
 uint64_t mtg_write_duplication_bitvector(const mtg_graph *g, uint64_t n_walks, const uint64_t *limits, const uint32_t *edges,

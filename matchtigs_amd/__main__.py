@@ -41,6 +41,10 @@ repeats that up to R times on the unitigs the round before left. 
 two nodes -- what a sequencing error in the middle of a read seen twice, or a heterozygous SNP, leaves -- the one with the largest
 mean abundance stays; a SNP's arms have k k-mers, so L = k + 1 is the least that pops them and 2 k the usual value. `--bubble-ratio R`
 pops an arm only if the best has at least R times its mean abundance, which keeps variation between samples.
+`--unitigs-bcalm-out` and `--unitigs-gfa-out` (any input; not in the reference) write the unitigs WITH their links, beside
+`--unitigs-fa-out` and before the tig algorithms: as BCALM2/GGCAT FASTA (`>id LN:i: KC:i: km:f: L:+:id:-`, what `--bcalm-in` reads) and
+as GFA1 (`S` and `L` lines with a k-1 overlap). The link lists and the whole text are made on the GPU; `KC` is the summed abundance of
+the unitig's k-mers where the compaction counted them, else their number.
 """
 from __future__ import annotations
 
@@ -67,6 +71,12 @@ def main(argv=None) -> int:
                     help="with fastq --query-fa files: a base whose Phred quality is below Q (0..93) is replaced by N")
     ap.add_argument("--unitigs-fa-out", help="write the input's unitigs as fasta (.gz => gzip): with --seq-in, the GPU compactor's output "
                                              "(not in the reference)")
+    ap.add_argument("--unitigs-bcalm-out", metavar="PATH",
+                    help="write the input's unitigs with their links as bcalm2/GGCAT fasta, `>id LN:i: KC:i: km:f: L:+:id:-` "
+                         "(.gz => gzip), the format --bcalm-in reads (not in the reference)")
+    ap.add_argument("--unitigs-gfa-out", metavar="PATH",
+                    help="write the input's unitigs with their links as GFA1: S lines with LN, KC and km tags, L lines with a k-1 "
+                         "overlap (.gz => gzip) (not in the reference)")
     ap.add_argument("-k", type=int, help="k-mer size used to build the de Bruijn graph (bin.rs:139-141)")
     ap.add_argument("-t", "--threads", type=int, default=1, help="accepted; results always equal the 1-thread order (bin.rs:148-149)")
     ap.add_argument("--greedytigs-fa-out", help="write greedy matchtigs as fasta (.gz => gzip) (bin.rs:107-109)")
@@ -209,7 +219,8 @@ def main(argv=None) -> int:
         if value is not None and not 0 <= value <= 93:
             ap.error(f"{flag} must be in 0..93")
     if not (args.color_classes_out or args.unitig_color_classes_out or args.color_matrix_out or args.unitig_colors_out or args.kmer_spectrum_out or args.unitig_abundance_out or args.unitig_kmer_abundance_out or args.query_fa or args.greedytigs_fa_out or args.eulertigs_fa_out or args.greedytigs_gfa_out or args.eulertigs_gfa_out
-            or args.greedytigs_duplication_bitvector_out or args.matchtigs_fa_out or args.matchtigs_gfa_out or args.verify_fa or args.unitigs_fa_out):
+            or args.greedytigs_duplication_bitvector_out or args.matchtigs_fa_out or args.matchtigs_gfa_out or args.verify_fa or args.unitigs_fa_out
+            or args.unitigs_bcalm_out or args.unitigs_gfa_out):
         ap.error("nothing to do: give --greedytigs-fa-out / --greedytigs-gfa-out and/or --eulertigs-fa-out / --eulertigs-gfa-out")
 
     from . import api
@@ -367,6 +378,15 @@ def _run(api, args, fastq) -> int:
         r = api.compute_tigs_to_fasta_file(graph, store, 1, args.k, args.unitigs_fa_out, args.compression_level, args.device)
         graph.reset()
         print(f"Writing unitigs took {r['write_s']:.1f}s ({r['tigs']} unitigs, {r['fasta_bytes']} fasta bytes)", file=sys.stderr)
+    if args.unitigs_bcalm_out or args.unitigs_gfa_out:  # the same unitigs with their links
+        t1 = time.perf_counter()
+        kc = abundance.unitig_sums if args.seq_in is not None and abundance is not None else None
+        for path, gfa in ((args.unitigs_bcalm_out, False), (args.unitigs_gfa_out, True)):
+            if path:
+                r = api.write_unitig_graph(graph, store, args.k, path, gfa, kc, args.compression_level, args.device)
+                print(f"Writing unitig graph took {time.perf_counter() - t1:.1f}s ({r['unitigs']} unitigs, {r['links']} links, "
+                      f"{r['bytes']} bytes)", file=sys.stderr)
+                t1 = time.perf_counter()
     for name, alg, out, gfa, dup in (("matchtigs", 4, args.matchtigs_fa_out, args.matchtigs_gfa_out,
                                       args.matchtigs_duplication_bitvector_out),
                                      ("eulertigs", 3, args.eulertigs_fa_out, args.eulertigs_gfa_out, None),

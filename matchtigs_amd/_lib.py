@@ -381,6 +381,10 @@ def load():
         "mtg_write_walks_text_device": (u64, [vp, u64, vp, vp, u64, C.c_char_p, vp, C.c_int, C.c_char_p, C.c_int, P(vp)]),
         "mtg_last_spell_kernel_ms": (C.c_double, []),
         "mtg_last_spell_bytes": (u64, []),
+        "mtg_unitig_links": (u64, [vp, C.c_int, P(vp), P(vp)]),
+        "mtg_write_unitig_graph_text": (u64, [vp, vp, vp, u64, u64, vp, C.c_int, C.c_int, P(vp)]),
+        "mtg_write_unitig_graph_file": (u64, [vp, vp, vp, u64, u64, vp, C.c_int, C.c_int, C.c_char_p, C.c_int]),
+        "mtg_last_unitig_graph_times": (None, [P(C.c_double)]),
         "mtg_write_duplication_bitvector": (u64, [vp, u64, vp, vp, P(vp)]),
         "mtg_write_tigs_duplication_bitvector_file": (u64, [vp, vp, C.c_char_p]),
         "mtg_write_walks_gfa": (u64, [vp, u64, vp, vp, u64, C.c_char_p, vp, C.c_char_p, P(vp)]),

@@ -1856,6 +1856,59 @@ def write_walks_text_device(graph: Bigraph, tigs, unitigs, k: int, gfa: bool = F
     return data
 
 
+def unitig_links(graph: Bigraph, device_id: int = 0):
+    """The links of the unitig graph, made on the GPU (mtg_unitig_links) -> (link_off, link_to). Oriented unitig o --
+    (u,+) is 2u, (u,-) is 2u + 1, the edge ids of every graph -- links to the edges link_to[link_off[o]:link_off[o + 1]], ascending:
+    o' is among them iff from(edge o') == to(edge o). link_off: uint64[2U + 1], link_to: uint32[links]. Only the original edges
+    count, so dummy edges a tig computation left in the graph change nothing."""
+    L = _lib.load()
+    off, to = C.c_void_p(), C.c_void_p()
+    n = int(L.mtg_unitig_links(graph.handle, device_id, C.byref(off), C.byref(to)))
+    n_off = graph.original_edge_count() + 1
+    link_off = np.ctypeslib.as_array(C.cast(off, C.POINTER(C.c_uint64)), shape=(n_off,)).copy()
+    link_to = np.ctypeslib.as_array(C.cast(to, C.POINTER(C.c_uint32)), shape=(n,)).copy() if n else np.zeros(0, np.uint32)
+    L.mtg_free(off)
+    L.mtg_free(to)
+    return link_off, link_to
+
+
+def write_unitig_graph(graph: Bigraph, store, k: int, path: Optional[str] = None, gfa: bool = False, kc=None,
+                       compression_level: int = 6, device_id: int = 0):
+    """The unitigs with their links as BCALM2/GGCAT FASTA (`>u LN:i: KC:i: km:f: L:+:v:-`) or, with gfa, as GFA1 (`S` and `L`
+    lines), the whole text made on the GPU (mtg_write_unitig_graph_text / _file). store: the unitigs of `graph` as a
+    UnitigStore, a list of str, or (uint8 array, offsets). kc: the abundance sum of every unitig (Abundance.unitig_sums), or None for
+    its number of k-mers. Without a path the bytes are returned; with one the file is written (`.gz`: gzip at compression_level) and
+    {"unitigs", "links", "bytes"} returned."""
+    L = _lib.load()
+    data, off, n, keep = _sequence_arrays(store)
+    if kc is not None:
+        kc = np.ascontiguousarray(kc, dtype=np.uint64)
+        if len(kc) != n:
+            raise ValueError(f"{len(kc)} abundance sums for {n} unitigs")
+    if path is None:
+        out = C.c_void_p()
+        nbytes = int(L.mtg_write_unitig_graph_text(graph.handle, data, off, n, k, _ptr(kc) if kc is not None and n else None,
+                                                   1 if gfa else 0, device_id, C.byref(out)))
+        text = C.string_at(out, nbytes)
+        L.mtg_free(out)
+        del keep
+        return text
+    nbytes = int(L.mtg_write_unitig_graph_file(graph.handle, data, off, n, k, _ptr(kc) if kc is not None and n else None,
+                                               1 if gfa else 0, device_id, str(path).encode(), compression_level))
+    del keep
+    return {"unitigs": n, "links": int(last_unitig_graph_times()["links"]), "bytes": nbytes}
+
+
+def last_unitig_graph_times() -> dict:
+    """Of the last unitig_links / write_unitig_graph on this thread: the uploads and the download by the host clock, the link kernels,
+    the scans of the text and the text kernel by HIP events (ms); the links, the bytes of the text, the bytes the text kernel must
+    move at the least and the peak of the device arena's live bytes."""
+    out = (C.c_double * 9)()
+    _lib.load().mtg_last_unitig_graph_times(out)
+    names = ("upload_ms", "link_ms", "text_prepare_ms", "text_ms", "download_ms", "links", "bytes", "text_min_bytes", "peak_arena_bytes")
+    return {name: (float(v) if name.endswith("_ms") else int(v)) for name, v in zip(names, out)}
+
+
 def last_spell_kernel() -> dict:
     L = _lib.load()
     return {"ms": float(L.mtg_last_spell_kernel_ms()), "bytes": int(L.mtg_last_spell_bytes())}

@@ -112,6 +112,19 @@ HostGraph *device_synth_g_csr(uint64_t n_binodes, uint64_t n_self_mirrors, uint6
 uint64_t device_write_walks_text(const HostGraph &g, uint64_t n_walks, const uint64_t *limits, const uint32_t *edges, uint64_t k,
                                  const char *seqs, const uint64_t *seq_off, bool gfa, const char *gfa_header, int device_id,
                                  char **out_buf, double *kernel_ms_out, uint64_t *bytes_out, const struct ResidentTigs *resident = nullptr);
+// unitig_links_device.hip: the unitig graph with its links (the file's header and DESIGN.md 26 state the contract). times: host wall
+// clock of the uploads and the download, HIP-event time of the link kernels, of the text's scans and of the text kernel, the links,
+// the bytes of the text, what the text kernel must move at the least, the arena's peak of live bytes.
+struct UnitigGraphTimes {
+    double upload_ms = 0, link_ms = 0, text_prepare_ms = 0, text_ms = 0, download_ms = 0;
+    uint64_t links = 0, bytes = 0, text_min_bytes = 0, peak_arena_bytes = 0;
+};
+// link_off[2U + 1] and link_to[links] of the original edges, malloc'd (the caller frees); returns the links
+uint64_t device_unitig_links(const HostGraph &g, int device_id, uint64_t **link_off_out, uint32_t **link_to_out, UnitigGraphTimes *times);
+// the BCALM2 FASTA (gfa == false) or GFA1 text of the n_unitigs records with their links; kc: null, or the abundance sum of every
+// unitig. Returns the bytes; *out_buf is malloc'd (the caller frees)
+uint64_t device_write_unitig_graph_text(const HostGraph &g, const char *seqs, const uint64_t *seq_off, uint64_t n_unitigs, uint64_t k,
+                                        const uint64_t *kc, bool gfa, int device_id, char **out_buf, UnitigGraphTimes *times);
 // fasta_in_device.hip: the plain unitig FASTA route -- graph of the (k-1)-mer overlaps of the unitig ends, joined on the GPU
 // (records: data[off[u], off[u + 1]), off[0] = 0). times: host wall clock of upload / download / graph build, HIP-event time of the
 // join kernels, and the bytes those kernels must move at the least.

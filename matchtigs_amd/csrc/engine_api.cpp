@@ -588,6 +588,33 @@ uint64_t mtg_write_walks_text_device(const mtg_graph *g, uint64_t n_walks, const
 double mtg_last_spell_kernel_ms(void) { return g_last_spell_kernel_ms; }
 uint64_t mtg_last_spell_bytes(void) { return g_last_spell_bytes; }
 
+// ---- the unitig graph with its links (unitig_links_device.hip) ----
+static thread_local UnitigGraphTimes g_last_unitig_graph;
+uint64_t mtg_unitig_links(const mtg_graph *g, int device_id, uint64_t **link_off, uint32_t **link_to) {
+    if (!g || !link_off || !link_to) MTG_DIE("mtg_unitig_links: null argument");
+    return device_unitig_links(g->g, device_id, link_off, link_to, &g_last_unitig_graph);
+}
+uint64_t mtg_write_unitig_graph_text(const mtg_graph *g, const char *unitig_seqs, const uint64_t *seq_offsets, uint64_t n_unitigs, uint64_t k,
+                                     const uint64_t *unitig_kc, int gfa, int device_id, char **text_out) {
+    if (!g || !text_out || !seq_offsets || (n_unitigs && !unitig_seqs)) MTG_DIE("mtg_write_unitig_graph_text: null argument");
+    return device_write_unitig_graph_text(g->g, unitig_seqs, seq_offsets, n_unitigs, k, unitig_kc, gfa != 0, device_id, text_out,
+                                          &g_last_unitig_graph);
+}
+uint64_t mtg_write_unitig_graph_file(const mtg_graph *g, const char *unitig_seqs, const uint64_t *seq_offsets, uint64_t n_unitigs, uint64_t k,
+                                     const uint64_t *unitig_kc, int gfa, int device_id, const char *path, int compression_level) {
+    if (!path) MTG_DIE("mtg_write_unitig_graph_file: null argument");
+    char *buf = nullptr;
+    const uint64_t n = mtg_write_unitig_graph_text(g, unitig_seqs, seq_offsets, n_unitigs, k, unitig_kc, gfa, device_id, &buf);
+    write_file(path, buf, n, compression_level);
+    std::free(buf);
+    return n;
+}
+void mtg_last_unitig_graph_times(double out[9]) {
+    const UnitigGraphTimes &t = g_last_unitig_graph;
+    out[0] = t.upload_ms; out[1] = t.link_ms; out[2] = t.text_prepare_ms; out[3] = t.text_ms; out[4] = t.download_ms;
+    out[5] = (double)t.links; out[6] = (double)t.bytes; out[7] = (double)t.text_min_bytes; out[8] = (double)t.peak_arena_bytes;
+}
+
 uint64_t mtg_write_duplication_bitvector(const mtg_graph *g, uint64_t n_walks, const uint64_t *limits, const uint32_t *edges,
                                          char **text_out) {
     if (!g || !text_out || (n_walks && (!limits || !edges))) MTG_DIE("mtg_write_duplication_bitvector: null argument");
