@@ -375,27 +375,21 @@ static void build_lower_bounds(Device *d, hipStream_t st) {
     const uint64_t V = d->V;
     if (!V || d->w8) return;
     const unsigned vb = (unsigned)((V + 255) / 256);
-    uint32_t *d_D = nullptr;
-    uint8_t *d_lb8 = nullptr;
-    uint16_t *d_lbx = nullptr;
-    hu::device_malloc(&d_D, V * 4);
-    hu::device_malloc(&d_lb8, V);
-    hu::device_malloc(&d_lbx, V * 2);
+    hu::DeviceArray<uint32_t> d_D(V);
+    hu::DeviceArray<uint8_t> d_lb8(V);
+    hu::DeviceArray<uint16_t> d_lbx(V);
     HIP_CHECK(hipEventRecord(d->ev0, st));
     hipLaunchKernelGGL(lb_init_kernel, dim3(vb), dim3(256), 0, st, d->d_odeg, d->d_mirror, V, d_D);
     for (uint32_t r = 0; r < d->K1; r++)
         hipLaunchKernelGGL(lb_round_kernel, dim3(vb), dim3(256), 0, st, d->d_recs, d->d_ext_col, d->d_ext_w, V, r, d->K1, d_D);
     hipLaunchKernelGGL(lb_mirror_kernel, dim3(vb), dim3(256), 0, st, d->d_mirror, d_D, V, d_lb8);
     hipLaunchKernelGGL(build_lbx_kernel, dim3(vb), dim3(256), 0, st, V, d->d_recs, d->d_ext_col, d->d_ext_w, d_lb8, d->K1, d_lbx, d->d_odeg);
-    hipLaunchKernelGGL(build_children_kernel<true>, dim3(vb), dim3(256), 0, st, V, d->d_recs, (const uint16_t *)d_lbx);
+    hipLaunchKernelGGL(build_children_kernel<true>, dim3(vb), dim3(256), 0, st, V, d->d_recs, (const uint16_t *)d_lbx.get());
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipEventRecord(d->ev1, st));
     HIP_CHECK(hipStreamSynchronize(st));
     d->lower_bounds_ms = elapsed_ms(d);
     d->w8 = true;
-    hu::device_free(d_D);
-    hu::device_free(d_lb8);
-    hu::device_free(d_lbx);
 }
 // ... for a device graph that was built without them (a caller that turns out to iterate): the searchable-source list of the
 // classification changes with the reach flags, so a classification that was there is repeated.
@@ -469,31 +463,28 @@ Device *device_create(const HostGraph &g, uint64_t k, int device_id, bool lower_
     // One chunk of the device's arena for the whole call unless an earlier call (or the reservation the graph's construction started
     // on a helper thread, device_reserve_async) left one: every allocation below and in the stages that follow is a range of it.
     const size_t call_bytes = device_call_bytes_estimate(V, E, k);
-    uint32_t *d_from = nullptr, *d_fill = nullptr, *d_need = nullptr, *d_row0 = nullptr, *d_adj0 = nullptr;
-    uint16_t *d_w = nullptr;
-    unsigned long long *d_ext_off = nullptr;
     // the long-lived arrays first (they collect at the front of the chunk), the build's scratch after them
-    hu::device_malloc(&d->d_recs, std::max<uint64_t>(V, 1) * sizeof(NodeBlock), call_bytes);
-    hu::device_malloc(&d->d_odeg, std::max<uint64_t>(V, 1) * 4);
-    hu::device_malloc(&d->d_mirror, std::max<uint64_t>(V, 1) * 4);
+    hu::device_malloc(&d->d_recs.p, std::max<uint64_t>(V, 1) * sizeof(NodeBlock), call_bytes);  // (the one allocation with a grow hint)
+    d->d_odeg.alloc(std::max<uint64_t>(V, 1));
+    d->d_mirror.alloc(std::max<uint64_t>(V, 1));
     // (class bytes, multiplicities, out-node list: taken by the first classification, once the build's scratch arrays are back)
     d->n_cls_blocks = (V + CLS_NODES - 1) / CLS_NODES;
-    hu::device_malloc(&d->d_block_counts, std::max<uint64_t>(d->n_cls_blocks, 1) * 2 * 4);  // source counts | positive multiplicities per block
-    hu::device_malloc(&d->d_act_blocks, std::max<uint64_t>(d->n_cls_blocks, 1) * 4);
-    hu::device_malloc(&d->d_act_total, 8);
-    hu::device_malloc(&d->d_counters, C_COUNT * sizeof(unsigned long long));
-    hu::device_malloc(&d_from, std::max<uint64_t>(E, 1) * 4);
+    d->d_block_counts.alloc(std::max<uint64_t>(d->n_cls_blocks, 1) * 2);  // source counts | positive multiplicities per block
+    d->d_act_blocks.alloc(std::max<uint64_t>(d->n_cls_blocks, 1));
+    d->d_act_total.alloc(1);
+    d->d_counters.alloc(C_COUNT);
+    hu::DeviceArray<uint32_t> d_from(std::max<uint64_t>(E, 1)), d_row0, d_adj0;
     // the buckets of the original darts by from-node (row0[V + 1], adj0[E]: what the finishing stages keep with the graph) fall out
     // of build_nodes_kernel's sort; kept while they are small next to the stand-ins of BASELINE configs[4] (finish_device.hip)
     const bool want_buckets = E && (V + 1 + E) * 4 <= (8ull << 30) && !g.device_cache && !(hu::finish_tuning().flags.load() & hu::FT_NO_EDGE_CACHE);
     if (want_buckets) {
-        hu::device_malloc(&d_row0, (V + 1) * 4);
-        hu::device_malloc(&d_adj0, E * 4);
+        d_row0.alloc(V + 1);
+        d_adj0.alloc(E);
     }
-    hu::device_malloc(&d_w, std::max<uint64_t>(U, 1) * 2);
-    hu::device_malloc(&d_fill, std::max<uint64_t>(E, 1) * 4);  // rank of every edge among the out-edges of its from-node (arrival order of the counting pass)
-    hu::device_malloc(&d_need, std::max<uint64_t>(V, 1) * 4);
-    hu::device_malloc(&d_ext_off, std::max<uint64_t>(V, 1) * 8);
+    hu::DeviceArray<uint16_t> d_w(std::max<uint64_t>(U, 1));
+    hu::DeviceArray<uint32_t> d_fill(std::max<uint64_t>(E, 1));  // rank of every edge among the out-edges of its from-node (arrival order of the counting pass)
+    hu::DeviceArray<uint32_t> d_need(std::max<uint64_t>(V, 1));
+    hu::DeviceArray<unsigned long long> d_ext_off(std::max<uint64_t>(V, 1));
     HIP_CHECK(hipHostMalloc(&d->h_counters, C_COUNT * sizeof(unsigned long long)));
     HIP_CHECK(hipEventCreate(&d->ev0));
     HIP_CHECK(hipEventCreate(&d->ev1));
@@ -508,7 +499,7 @@ Device *device_create(const HostGraph &g, uint64_t k, int device_id, bool lower_
     dl.lap("upload of from");
     const unsigned eb = (unsigned)((E + 255) / 256), vb = (unsigned)((V + 255) / 256);
     uint64_t ext_total = 0;
-    uint32_t *d_bs = nullptr;
+    hu::DeviceArray<uint32_t> d_bs;
     hipStream_t bs = nullptr;
     HIP_CHECK(hipStreamCreateWithFlags(&bs, hipStreamNonBlocking));
     HIP_CHECK(hipMemsetAsync(d->d_odeg, 0, std::max<uint64_t>(V, 1) * 4, bs));
@@ -516,9 +507,9 @@ Device *device_create(const HostGraph &g, uint64_t k, int device_id, bool lower_
         if (E) hipLaunchKernelGGL(build_count_kernel, dim3(eb), dim3(256), 0, bs, d_from, E, d->d_odeg, d_fill);
         hipLaunchKernelGGL(build_ext_need_kernel, dim3(vb), dim3(256), 0, bs, d->d_odeg, V, d_need);
         HIP_CHECK(hipGetLastError());
-        scan_u32(d, bs, d->replay, d_need, V, d_ext_off, &d->d_counters[C_OVF_LIST]);
+        scan_u32(bs, d->replay, d_need, V, d_ext_off, &d->d_counters[C_OVF_LIST]);  // (borrows the replay's scan scratch: its first allocation)
         if (want_buckets) {  // row0 = exclusive scan of the out-degrees
-            hu::device_malloc(&d_bs, (hu::scan_blocks(V) + 2) * 4);
+            d_bs.alloc(hu::scan_blocks(V) + 2);
             hu::scan_u32<uint32_t>(bs, d->d_odeg, V, d_row0, d_bs, d_row0 + V);
         }
     }
@@ -526,15 +517,15 @@ Device *device_create(const HostGraph &g, uint64_t k, int device_id, bool lower_
     if (V) hu::upload_sliced(d->d_mirror, g.mirror.data(), V * 4, st, device_id);  // (both calls return when the data is there)
     if (V) {
         read_counters(d, bs);
-        if (d_bs) hu::device_free(d_bs);
+        d_bs.release();
         ext_total = d->h_counters[C_OVF_LIST];
     }
     HIP_CHECK(hipStreamSynchronize(bs));
     HIP_CHECK(hipStreamDestroy(bs));
     dl.lap("count + scans beside the uploads of weights and mirror");
     d->ext_n = ext_total;
-    hu::device_malloc(&d->d_ext_col, std::max<uint64_t>(ext_total, 1) * 4);
-    hu::device_malloc(&d->d_ext_w, std::max<uint64_t>(ext_total, 1) * 2);
+    d->d_ext_col.alloc(std::max<uint64_t>(ext_total, 1));
+    d->d_ext_w.alloc(std::max<uint64_t>(ext_total, 1));
     if (V) {
         if (E) hipLaunchKernelGGL(build_fill_kernel, dim3(eb), dim3(256), 0, st, d_from, E, d->d_odeg, d_ext_off, d_fill, d->d_recs, d->d_ext_col);
         hipLaunchKernelGGL(build_nodes_kernel, dim3(vb), dim3(256), 0, st, V, d->d_odeg, d->d_mirror, d_ext_off, d_from, d_w, d->d_recs,
@@ -546,13 +537,12 @@ Device *device_create(const HostGraph &g, uint64_t k, int device_id, bool lower_
     }
     dl.lap("build kernels (+ lower bounds)");
     // the finishing stages on this GPU start from the same arrays: from, mirror and the buckets stay with the graph
-    uint32_t *d_mirror_copy = nullptr;
-    hu::device_malloc(&d_mirror_copy, std::max<uint64_t>(V, 1) * 4);
+    hu::DeviceArray<uint32_t> d_mirror_copy(std::max<uint64_t>(V, 1));
     if (V) HIP_CHECK(hipMemcpyAsync(d_mirror_copy, d->d_mirror, V * 4, hipMemcpyDeviceToDevice, st));
     HIP_CHECK(hipStreamSynchronize(st));
-    hu::edge_cache_put(g, device_id, d_from, d_mirror_copy);
-    if (want_buckets) hu::edge_cache_set_buckets(g, device_id, d_row0, d_adj0);
-    for (void *p : {(void *)d_w, (void *)d_fill, (void *)d_need, (void *)d_ext_off}) hu::device_free(p);
+    hu::edge_cache_put(g, device_id, d_from.take(), d_mirror_copy.take());
+    if (want_buckets) hu::edge_cache_set_buckets(g, device_id, d_row0.take(), d_adj0.take());
+    d_w.release(); d_fill.release(); d_need.release(); d_ext_off.release();
     d->graph_bytes = V * sizeof(NodeBlock) + ext_total * 6 + V * 13;
     dl.lap("edge cache + frees");
     return d;
@@ -577,25 +567,7 @@ void device_reserve_step_work(Device *d) {
 
 void device_free(Device *d) {
     if (!d) return;
-    (void)hipSetDevice(d->dev);
-    void *bufs[] = {d->d_recs, d->d_odeg, d->d_cls, d->d_ext_col, d->d_ext_w, d->d_mult, d->d_mirror, d->d_out_nodes, d->d_block_counts, d->d_counters,
-                    d->d_act_index, d->d_act_node, d->d_act_blocks, d->d_act_total};
-    for (void *b : bufs) hu::device_free(b);
-    for (int i = 0; i < 2; i++) hu::device_free(d->d_ovf[i]);
-    hu::device_free(d->d_fix);
-    hu::device_free(d->d_fix_dense);
-    hu::device_free(d->d_fix_val);
-    hu::device_free(d->d_fix_dense_val);
-    ReplayWork &w = d->replay;
-    void *rb[] = {w.state, w.resv[0], w.resv[1], w.touch, w.src_mirror, w.dense, w.claims, w.pending[0], w.pending[1], w.spill,
-                  w.final_off, w.block_sums, w.ctl, w.out};
-    for (void *b : rb) hu::device_free(b);
-    (void)hipHostFree(w.h_ctl);
-    (void)hipHostFree(w.h_out);
-    (void)hipHostFree(d->h_counters);
-    (void)hipEventDestroy(d->ev0);
-    (void)hipEventDestroy(d->ev1);
-    for (auto e : d->ev_r) (void)hipEventDestroy(e);
+    (void)hipSetDevice(d->dev);  // (a Device may die on a thread whose current device is another one)
     delete d;
 }
 

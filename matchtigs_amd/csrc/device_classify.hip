@@ -135,9 +135,9 @@ uint64_t device_classify(Device *d, void *stream) {
     HIP_CHECK(hipSetDevice(d->dev));
     d->n_sources = 0;
     if (!d->d_cls) {
-        hu::device_malloc(&d->d_cls, std::max<uint64_t>(d->V, 1));
-        hu::device_malloc(&d->d_mult, std::max<uint64_t>(d->V, 1) * 4);
-        hu::device_malloc(&d->d_out_nodes, std::max<uint64_t>(d->V, 1) * 4);
+        d->d_cls.alloc(std::max<uint64_t>(d->V, 1));
+        d->d_mult.alloc(std::max<uint64_t>(d->V, 1));
+        d->d_out_nodes.alloc(std::max<uint64_t>(d->V, 1));
     }
     if (d->V) {
         static const bool dbg = std::getenv("MTG_DEBUG") != nullptr;
@@ -158,9 +158,9 @@ uint64_t device_classify(Device *d, void *stream) {
         d->total_demand = d->h_counters[C_DEMAND];
         const uint64_t act_need = d->w8 ? d->n_sources : 0;  // (without the 8:8 format no source carries the flag: the lists stay empty)
         if (d->act_cap < act_need || !d->d_act_index) {
-            for (void *p : {(void *)d->d_act_index, (void *)d->d_act_node}) if (p) hu::device_free(p);
-            hu::device_malloc(&d->d_act_index, std::max<uint64_t>(act_need, 1) * 4);
-            hu::device_malloc(&d->d_act_node, std::max<uint64_t>(act_need, 1) * 4);
+            d->d_act_index.release(); d->d_act_node.release();
+            d->d_act_index.alloc(std::max<uint64_t>(act_need, 1));
+            d->d_act_node.alloc(std::max<uint64_t>(act_need, 1));
             d->act_cap = act_need;
         }
         hipLaunchKernelGGL(compact_sources_kernel, dim3((unsigned)d->n_cls_blocks), dim3(CLS_BLOCK), 0, st, d->d_cls,
@@ -179,13 +179,11 @@ void device_classify_download(Device *d, void *stream, uint32_t *out_nodes, int3
         HIP_CHECK(hipMemcpyAsync(out_nodes, d->d_out_nodes, d->n_sources * 4, hipMemcpyDeviceToHost, st));
     if (mult && d->V) HIP_CHECK(hipMemcpyAsync(mult, d->d_mult, d->V * 4, hipMemcpyDeviceToHost, st));
     if (live && d->V) {
-        uint8_t *d_live = nullptr;
-        hu::device_malloc(&d_live, d->V);
+        hu::DeviceArray<uint8_t> d_live(d->V);
         hipLaunchKernelGGL(export_live_kernel, dim3((unsigned)((d->V + 255) / 256)), dim3(256), 0, st, d->d_cls, (uint32_t)d->V, d_live);
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipMemcpyAsync(live, d_live, d->V, hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipStreamSynchronize(st));
-        hu::device_free(d_live);
     }
     HIP_CHECK(hipStreamSynchronize(st));
 }

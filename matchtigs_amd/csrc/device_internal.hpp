@@ -132,18 +132,19 @@ struct Touch;  // replay_kernels.inc
 struct Dense;
 struct ReplayWork {
     uint64_t cap_v = 0, cap_s = 0, cap_spill = 0, cap_blocks = 0, cap_out = 0;
-    unsigned long long *state = nullptr;      // [V] working node states {mirror, multiplicity, live}
-    unsigned long long *resv[2] = {nullptr, nullptr};
+    hu::DeviceArray<unsigned long long> state;  // [V] working node states {mirror, multiplicity, live}
+    hu::DeviceArray<unsigned long long> resv[2];
     uint32_t tag_base = 0xFFFFFFFFu;          // reservation tags used so far (the arrays are never cleared between calls)
-    Touch *touch = nullptr;
-    uint32_t *src_mirror = nullptr;
-    Dense *dense = nullptr;                   // the sources that have candidates (replay_kernels.inc)
+    hu::DeviceArray<Touch> touch;             // (incomplete here: only alloc(), in device_replay.hip, needs the size)
+    hu::DeviceArray<uint32_t> src_mirror;
+    hu::DeviceArray<Dense> dense;             // the sources that have candidates (replay_kernels.inc)
     uint64_t cap_dense = 0;
-    unsigned long long *claims = nullptr;
-    uint32_t *pending[2] = {nullptr, nullptr}, *spill = nullptr;
-    unsigned long long *final_off = nullptr, *block_sums = nullptr;
-    unsigned long long *ctl = nullptr, *h_ctl = nullptr;  // control block (device / pinned host copy)
-    mtg_pair *out = nullptr;
+    hu::DeviceArray<unsigned long long> claims;
+    hu::DeviceArray<uint32_t> pending[2], spill;
+    hu::DeviceArray<unsigned long long> final_off, block_sums;
+    hu::DeviceArray<unsigned long long> ctl;  // control block ...
+    unsigned long long *h_ctl = nullptr;      // ... and its pinned host copy
+    hu::DeviceArray<mtg_pair> out;
     mtg_pair *h_out = nullptr;                // pinned staging of the pair download (pageable D2H runs at a few GB/s)
     uint64_t cap_h_out = 0;
     unsigned grid = 0, grid_small = 0;        // co-resident workgroups of the cooperative launch (workgroups of 1024 / of 256)
@@ -157,30 +158,30 @@ struct Device {
     uint64_t E0 = 0;  // original edges of the graph the device copy was built from
     double lower_bounds_ms = 0.0;  // GPU time of the lower-bound precompute (0 without)
     bool single_use = false;  // the caller searches once (mtg_compute_tigs_cfg): what only the search needs goes back before the claim replay takes its arrays
-    NodeBlock *d_recs = nullptr;              // [V] family blocks
-    uint32_t *d_odeg = nullptr;               // [V] out-degree (classification)
-    uint8_t *d_cls = nullptr;                 // [V] class byte of the last classification (F_TARGET | F_SOURCE | F_SELF_MIRROR)
-    uint32_t *d_ext_col = nullptr;
-    uint16_t *d_ext_w = nullptr;
+    hu::DeviceArray<NodeBlock> d_recs;        // [V] family blocks
+    hu::DeviceArray<uint32_t> d_odeg;         // [V] out-degree (classification)
+    hu::DeviceArray<uint8_t> d_cls;           // [V] class byte of the last classification (F_TARGET | F_SOURCE | F_SELF_MIRROR)
+    hu::DeviceArray<uint32_t> d_ext_col;
+    hu::DeviceArray<uint16_t> d_ext_w;
     uint64_t ext_n = 0;
-    int32_t *d_mult = nullptr;
-    uint32_t *d_out_nodes = nullptr;
-    uint32_t *d_block_counts = nullptr;
+    hu::DeviceArray<int32_t> d_mult;
+    hu::DeviceArray<uint32_t> d_out_nodes;
+    hu::DeviceArray<uint32_t> d_block_counts;
     uint64_t n_cls_blocks = 0;
     uint64_t n_sources = 0;
     uint64_t total_demand = 0;  // sum of the positive multiplicities (classification)
     bool classified = false;
-    unsigned long long *d_counters = nullptr;
+    hu::DeviceArray<unsigned long long> d_counters;
     unsigned long long *h_counters = nullptr;  // pinned
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     hipEvent_t ev_r[4] = {nullptr, nullptr, nullptr, nullptr};  // claim replay: start, before / after the rounds kernel, end of the GPU work
     double last_replay_kernel_ms = 0.0, last_replay_gpu_ms = 0.0;
     double last_wall_s[3] = {0, 0, 0};  // host wall clock of the last device_pairs[_multi]: SSSP stage (+ gather), claim replay, pair download
     double last_kernel_ms = 0.0;  // sum of the SSSP level kernels' HIP-event durations of the last call
-    uint32_t *d_mirror = nullptr;             // [V] mirror node (claim replay)
-    uint32_t *d_ovf[2] = {nullptr, nullptr};  // ping-pong overflow source lists
-    unsigned long long *d_fix_val = nullptr, *d_fix_dense_val = nullptr;  // ... and the lists' places beside the entries
-    uint32_t *d_fix = nullptr, *d_fix_dense = nullptr;  // enumeration level: work list of its post-pass (chunked, as written / dense, by length class)
+    hu::DeviceArray<uint32_t> d_mirror;       // [V] mirror node (claim replay)
+    hu::DeviceArray<uint32_t> d_ovf[2];       // ping-pong overflow source lists
+    hu::DeviceArray<unsigned long long> d_fix_val, d_fix_dense_val;  // ... and the lists' places beside the entries
+    hu::DeviceArray<uint32_t> d_fix, d_fix_dense;  // enumeration level: work list of its post-pass (chunked, as written / dense, by length class)
     uint64_t ovf_cap = 0;
     int last_n_levels = 0;           // per-level record of the last call: kernel ms and sources handed to the level
     double last_level_ms[8] = {0};
@@ -192,8 +193,8 @@ struct Device {
     bool w8 = false;                 // blocks in the 8:8 format with lower bounds (k <= 255)
     // the sources that can reach an in-node (8:8 format), in order, written by the classification (cap: act_cap sources); per-block
     // counts of them (d_act_blocks, n_cls_blocks words) and their number (d_act_total, on the device)
-    uint32_t *d_act_index = nullptr, *d_act_node = nullptr, *d_act_blocks = nullptr;
-    unsigned long long *d_act_total = nullptr;
+    hu::DeviceArray<uint32_t> d_act_index, d_act_node, d_act_blocks;
+    hu::DeviceArray<unsigned long long> d_act_total;
     uint64_t act_cap = 0;
     uint64_t last_active_sources = 0;
     int n_cu = 256;
@@ -206,6 +207,15 @@ struct Device {
     int last_replay_rounds = 0;
     uint64_t last_n_pairs = 0;        // pairs of the last claim replay; they stay in replay.out until the next one (or device_take_pairs)
     uint64_t last_replay_visits = 0;  // sum over the rounds of the pending-list lengths (first RC_TRACE_ROUNDS rounds)
+    ~Device() {  // (device_free sets the device first; the arrays release themselves after this body)
+        (void)hipDeviceSynchronize();  // (as the first array's release does: the pinned blocks and the events are idle too)
+        (void)hipHostFree(replay.h_ctl);
+        (void)hipHostFree(replay.h_out);
+        (void)hipHostFree(h_counters);
+        (void)hipEventDestroy(ev0);
+        (void)hipEventDestroy(ev1);
+        for (auto e : ev_r) (void)hipEventDestroy(e);
+    }
 };
 
 // ---- shared between the translation units ----
@@ -213,7 +223,7 @@ void read_counters(Device *d, hipStream_t st);                      // device_ss
 float elapsed_ms(Device *d);                                        // ev0 .. ev1
 int run_levels(Device *d, hipStream_t st, int count_mode, uint64_t src_begin, uint64_t src_end, unsigned long long *d_pool, uint64_t pool_cap,
                unsigned long long *d_cand_start, uint32_t *d_cand_count, uint64_t *pool_needed, mtg_sssp_stats *stats);
-void scan_u32(Device *d, hipStream_t st, ReplayWork &w, const uint32_t *in, uint64_t n, unsigned long long *out, unsigned long long *d_total);  // device_replay.hip
+void scan_u32(hipStream_t st, ReplayWork &w, const uint32_t *in, uint64_t n, unsigned long long *out, unsigned long long *d_total);  // device_replay.hip
 void device_drop_search_arrays(Device *d);
 // one kernel's attributes per translation unit of the stage: asking for them loads the unit's code object (3-10 ms otherwise, inside its first launch)
 void device_warm_classify_unit(hipFuncAttributes *a);

@@ -9,12 +9,11 @@ namespace mtg {
 void device_set_single_use(Device *d) { d->single_use = true; }
 void device_drop_search_arrays(Device *d) {
     HIP_CHECK(hipDeviceSynchronize());
-    for (void **p : {(void **)&d->d_recs, (void **)&d->d_ext_col, (void **)&d->d_ext_w, (void **)&d->d_act_index, (void **)&d->d_act_node,
-                     (void **)&d->d_ovf[0], (void **)&d->d_ovf[1], (void **)&d->d_fix, (void **)&d->d_fix_dense, (void **)&d->d_fix_val, (void **)&d->d_fix_dense_val}) {
-        if (*p) hu::device_arena(d->dev).free(*p, false);
-        *p = nullptr;
-    }
-    d->ovf_cap = 0;
+    d->d_recs.release(); d->d_ext_col.release(); d->d_ext_w.release();
+    d->d_act_index.release(); d->d_act_node.release();  // (the classification takes them again: !d_act_index)
+    d->d_ovf[0].release(); d->d_ovf[1].release();
+    d->d_fix.release(); d->d_fix_dense.release(); d->d_fix_val.release(); d->d_fix_dense_val.release();
+    d->ovf_cap = 0;  // (run_levels grows the lists by this)
     d->act_cap = 0;
 }
 
@@ -29,27 +28,19 @@ uint64_t device_pairs(Device *d, void *stream, mtg_pair **pairs_out, int *rounds
         if (rounds_out) *rounds_out = 0;
         return 0;
     }
-    unsigned long long *d_start = nullptr, *d_pool = nullptr;
-    uint32_t *d_count = nullptr;
     const auto t_begin = std::chrono::steady_clock::now();
-    hu::device_malloc(&d_start, S * 8);
-    hu::device_malloc(&d_count, S * 4);
+    hu::DeviceArray<unsigned long long> d_start(S), d_pool;
+    hu::DeviceArray<uint32_t> d_count(S);
     uint64_t cap = std::max<uint64_t>(S * 2 + std::min<uint64_t>((S + 63) / 64, (uint64_t)d->n_cu * 8) * ENUM_POOL_CHUNK, 1024);  // keys + per-wave chunk slack
     for (;;) {
-        hu::device_malloc(&d_pool, cap * 8);
+        d_pool.alloc(cap);  // (a retry gives the pool that was too small back first)
         uint64_t needed = 0;
         if (run_levels(d, st, 0, 0, S, d_pool, cap, d_start, d_count, &needed, nullptr) == 0) break;
-        hu::device_free(d_pool);
-        d_pool = nullptr;
         cap = needed + needed / 8 + 1024;
     }
     if (d->single_use) device_drop_search_arrays(d);
     d->last_wall_s[0] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
-    const uint64_t n = device_replay(d, stream, S, (const uint64_t *)d_start, d_count, (const uint64_t *)d_pool, pairs_out, rounds_out);
-    hu::device_free(d_pool);
-    hu::device_free(d_start);
-    hu::device_free(d_count);
-    return n;
+    return device_replay(d, stream, S, (const uint64_t *)d_start.get(), d_count, (const uint64_t *)d_pool.get(), pairs_out, rounds_out);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -89,21 +80,17 @@ std::vector<uint64_t> device_partition_sources(Device *d, void *stream, int part
         for (int r = 1; r < parts; r++) cuts[(size_t)r] = S;
         return cuts;
     }
-    uint32_t *d_work = nullptr;
-    unsigned long long *d_prefix = nullptr, *d_cut = nullptr;
-    hu::device_malloc(&d_work, S * 4);
-    hu::device_malloc(&d_prefix, S * 8);
-    hu::device_malloc(&d_cut, (size_t)parts * 8);
+    hu::DeviceArray<uint32_t> d_work(S);
+    hu::DeviceArray<unsigned long long> d_prefix(S), d_cut((uint64_t)parts);
     HIP_CHECK(hipMemsetAsync(d_cut, 0, (size_t)parts * 8, st));
     hipLaunchKernelGGL(source_work_kernel, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, st, d->d_out_nodes, d->d_odeg, S, d_work);
-    scan_u32(d, st, d->replay, d_work, S, d_prefix, &d->d_counters[C_OVF_LIST]);
+    scan_u32(st, d->replay, d_work, S, d_prefix, &d->d_counters[C_OVF_LIST]);
     hipLaunchKernelGGL(work_cuts_kernel, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, st, d_prefix, d_work, S, &d->d_counters[C_OVF_LIST], parts, d_cut);
     HIP_CHECK(hipGetLastError());
     std::vector<unsigned long long> h((size_t)parts);
     HIP_CHECK(hipMemcpyAsync(h.data(), d_cut, (size_t)parts * 8, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
     for (int r = 1; r < parts; r++) cuts[(size_t)r] = std::max<uint64_t>(cuts[(size_t)r - 1], h[(size_t)r]);
-    hu::device_free(d_work); hu::device_free(d_prefix); hu::device_free(d_cut);
     return cuts;
 }
 
@@ -123,7 +110,7 @@ uint64_t device_pairs_multi(Device *const *devs, int n_dev, mtg_pair **pairs_out
     }
     const auto t_begin = std::chrono::steady_clock::now();
     const std::vector<uint64_t> cuts = device_partition_sources(d0, nullptr, n_dev);
-    struct Part { unsigned long long *start = nullptr, *pool = nullptr; uint32_t *count = nullptr; uint64_t used = 0; };
+    struct Part { hu::DeviceArray<unsigned long long> start, pool; hu::DeviceArray<uint32_t> count; uint64_t used = 0; };
     std::vector<Part> parts((size_t)n_dev);
     std::vector<std::thread> th;
     for (int i = 0; i < n_dev; i++) {
@@ -133,15 +120,13 @@ uint64_t device_pairs_multi(Device *const *devs, int n_dev, mtg_pair **pairs_out
             HIP_CHECK(hipSetDevice(d->dev));
             const uint64_t lo = cuts[(size_t)i], hi = cuts[(size_t)i + 1], n = hi - lo;
             if (!n) return;
-            hu::device_malloc(&p.start, n * 8);
-            hu::device_malloc(&p.count, n * 4);
+            p.start.alloc(n);
+            p.count.alloc(n);
             uint64_t cap = std::max<uint64_t>(n * 2 + std::min<uint64_t>((n + 63) / 64, (uint64_t)d->n_cu * 8) * ENUM_POOL_CHUNK, 1024);
             for (;;) {
-                hu::device_malloc(&p.pool, cap * 8);
+                p.pool.alloc(cap);
                 uint64_t needed = 0;
                 if (run_levels(d, nullptr, 0, lo, hi, p.pool, cap, p.start, p.count, &needed, nullptr) == 0) { p.used = needed; break; }
-                hu::device_free(p.pool);
-                p.pool = nullptr;
                 cap = needed + needed / 8 + 1024;
             }
         });
@@ -152,11 +137,9 @@ uint64_t device_pairs_multi(Device *const *devs, int n_dev, mtg_pair **pairs_out
     HIP_CHECK(hipSetDevice(d0->dev));
     uint64_t pool_total = 0;
     for (const Part &p : parts) pool_total += p.used;
-    unsigned long long *g_start = nullptr, *g_pool = nullptr;
-    uint32_t *g_count = nullptr;
-    hu::device_malloc(&g_start, S * 8);
-    hu::device_malloc(&g_count, S * 4);
-    hu::device_malloc(&g_pool, std::max<uint64_t>(pool_total, 1) * 8);
+    hu::DeviceArray<unsigned long long> g_start(S);
+    hu::DeviceArray<uint32_t> g_count(S);
+    hu::DeviceArray<unsigned long long> g_pool(std::max<uint64_t>(pool_total, 1));
     uint64_t off = 0;
     for (int i = 0; i < n_dev; i++) {
         const Part &p = parts[(size_t)i];
@@ -176,16 +159,14 @@ uint64_t device_pairs_multi(Device *const *devs, int n_dev, mtg_pair **pairs_out
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(nullptr));
     if (gather_ms_out) *gather_ms_out = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    for (int i = 0; i < n_dev; i++) {
+    for (int i = 0; i < n_dev; i++) {  // (each part on the device it was taken from)
         HIP_CHECK(hipSetDevice(devs[i]->dev));
-        if (parts[(size_t)i].start) { hu::device_free(parts[(size_t)i].start); hu::device_free(parts[(size_t)i].count); hu::device_free(parts[(size_t)i].pool); }
+        parts[(size_t)i].start.release(); parts[(size_t)i].count.release(); parts[(size_t)i].pool.release();
     }
     HIP_CHECK(hipSetDevice(d0->dev));
     if (d0->single_use) device_drop_search_arrays(d0);
     d0->last_wall_s[0] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
-    const uint64_t n = device_replay(d0, nullptr, S, (const uint64_t *)g_start, g_count, (const uint64_t *)g_pool, pairs_out, rounds_out);
-    hu::device_free(g_pool); hu::device_free(g_start); hu::device_free(g_count);
-    return n;
+    return device_replay(d0, nullptr, S, (const uint64_t *)g_start.get(), g_count, (const uint64_t *)g_pool.get(), pairs_out, rounds_out);
 }
 
 // convenience for tests: allocates device buffers, grows the pool on demand, downloads to host vectors
@@ -198,13 +179,11 @@ void device_candidates_to_host(Device *d, void *stream, std::vector<uint64_t> &c
     cand_count.assign(S, 0);
     pool.clear();
     if (!S) return;
-    unsigned long long *d_start = nullptr, *d_pool = nullptr;
-    uint32_t *d_count = nullptr;
-    hu::device_malloc(&d_start, S * 8);
-    hu::device_malloc(&d_count, S * 4);
+    hu::DeviceArray<unsigned long long> d_start(S), d_pool;
+    hu::DeviceArray<uint32_t> d_count(S);
     uint64_t cap = std::max<uint64_t>(S * 4, 1024);
     for (;;) {
-        hu::device_malloc(&d_pool, cap * 8);
+        d_pool.alloc(cap);
         uint64_t needed = 0;
         const int rc = run_levels(d, st, 0, 0, S, d_pool, cap, d_start, d_count, &needed, nullptr);
         if (rc == 0) {
@@ -212,16 +191,11 @@ void device_candidates_to_host(Device *d, void *stream, std::vector<uint64_t> &c
             if (needed) HIP_CHECK(hipMemcpyAsync(pool.data(), d_pool, needed * 8, hipMemcpyDeviceToHost, st));
             break;
         }
-        hu::device_free(d_pool);
-        d_pool = nullptr;
         cap = needed + needed / 8 + 1024;
     }
     HIP_CHECK(hipMemcpyAsync(cand_start.data(), d_start, S * 8, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipMemcpyAsync(cand_count.data(), d_count, S * 4, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
-    hu::device_free(d_pool);
-    hu::device_free(d_start);
-    hu::device_free(d_count);
 }
 
 

@@ -10,23 +10,22 @@ namespace mtg {
 // ------------------------------------------------------------------------------------------------
 // GPU claim replay (replay_kernels.inc): host driver
 // ------------------------------------------------------------------------------------------------
+static void grow_block_sums(ReplayWork &w, uint64_t nb) {
+    if (nb <= w.cap_blocks) return;
+    w.block_sums.alloc(nb);
+    w.cap_blocks = nb;
+}
 template <typename In>
 static void scan_values(hipStream_t st, ReplayWork &w, In in, uint64_t n, unsigned long long *out, unsigned long long *d_total) {
     const uint64_t nb = (n + SCAN_BLOCK - 1) / SCAN_BLOCK;
-    if (nb > w.cap_blocks) {
-        if (w.block_sums) hu::device_free(w.block_sums);
-        hu::device_malloc(&w.block_sums, nb * 8);
-        w.cap_blocks = nb;
-    }
+    grow_block_sums(w, nb);
     hipLaunchKernelGGL(scan_reduce_kernel<In>, dim3((unsigned)nb), dim3(SCAN_BLOCK), 0, st, in, n, w.block_sums);
     hipLaunchKernelGGL(scan_block_sums_kernel, dim3(1), dim3(SCAN_BLOCK), 0, st, w.block_sums, nb, d_total);
     hipLaunchKernelGGL(scan_apply_kernel<In>, dim3((unsigned)nb), dim3(SCAN_BLOCK), 0, st, in, n, w.block_sums, out);
     HIP_CHECK(hipGetLastError());
 }
-void scan_u32(Device *d, hipStream_t st, ReplayWork &w, const uint32_t *in, uint64_t n, unsigned long long *out,
-              unsigned long long *d_total) {
+void scan_u32(hipStream_t st, ReplayWork &w, const uint32_t *in, uint64_t n, unsigned long long *out, unsigned long long *d_total) {
     scan_values(st, w, ScanInU32{in}, n, out, d_total);
-    (void)d;
 }
 
 // Claims for ALL n_sources classified sources (candidate arrays indexed by absolute source index, device pointers).
@@ -58,39 +57,35 @@ uint64_t device_replay(Device *d, void *stream, uint64_t n_sources, const uint64
         return 0;
     }
     if (V > w.cap_v) {
-        if (w.state) hu::device_free(w.state);
-        for (int i = 0; i < 2; i++) if (w.resv[i]) { hu::device_free(w.resv[i]); w.resv[i] = nullptr; }
+        w.state.release(); w.resv[0].release(); w.resv[1].release();
 #if MTG_REPLAY_RECORDS
-        hu::device_malloc(&w.state, ((V + 1) / 2) * 64);  // one 64-byte record per pair of numeric neighbours: states + both reservation words
+        w.state.alloc(((V + 1) / 2) * 8);  // one 64-byte record per pair of numeric neighbours: states + both reservation words
 #else
-        hu::device_malloc(&w.state, (V + 2) * 8);  // (states are read in aligned pairs: the last pair may reach one word beyond V)
-        hu::device_malloc(&w.resv[0], V * 8);
-        hu::device_malloc(&w.resv[1], V * 8);
+        w.state.alloc(V + 2);  // (states are read in aligned pairs: the last pair may reach one word beyond V)
+        w.resv[0].alloc(V);
+        w.resv[1].alloc(V);
 #endif
         w.cap_v = V;
         w.tag_base = 0xFFFFFFFFu;  // forces the clear below
     }
     if (S > w.cap_s) {
-        if (w.touch) {
-            hu::device_free(w.touch); hu::device_free(w.src_mirror); hu::device_free(w.claims);
-            hu::device_free(w.pending[0]); hu::device_free(w.pending[1]); hu::device_free(w.final_off);
-        }
-        hu::device_malloc(&w.touch, S * sizeof(Touch));
-        hu::device_malloc(&w.src_mirror, S * 4);
-        hu::device_malloc(&w.claims, S * 8);
-        hu::device_malloc(&w.pending[0], S * 4);
-        hu::device_malloc(&w.pending[1], S * 4);
-        hu::device_malloc(&w.final_off, S * 8);
+        w.touch.release(); w.src_mirror.release(); w.claims.release();
+        w.pending[0].release(); w.pending[1].release(); w.final_off.release();
+        w.touch.alloc(S);
+        w.src_mirror.alloc(S);
+        w.claims.alloc(S);
+        w.pending[0].alloc(S);
+        w.pending[1].alloc(S);
+        w.final_off.alloc(S);
         w.cap_s = S;
     }
     const uint64_t spill_need = std::max<uint64_t>(d->total_demand, 1);  // a source emits at most its demand (classification)
     if (spill_need > w.cap_spill) {
-        if (w.spill) hu::device_free(w.spill);
-        hu::device_malloc(&w.spill, spill_need * 4);
+        w.spill.alloc(spill_need);
         w.cap_spill = spill_need;
     }
     if (!w.ctl) {
-        hu::device_malloc(&w.ctl, RC_COUNT * 8);
+        w.ctl.alloc(RC_COUNT);
         HIP_CHECK(hipHostMalloc(&w.h_ctl, RC_COUNT * 8));
     }
     // reservation tags decrease with every round of every call, so the two reservation arrays are never cleared; only when
@@ -124,11 +119,7 @@ uint64_t device_replay(Device *d, void *stream, uint64_t n_sources, const uint64
     {
         static_assert(DENSE_BLOCK == SCAN_BLOCK, "the dense fill uses the scan's block offsets");
         const uint64_t nb = (S + SCAN_BLOCK - 1) / SCAN_BLOCK;
-        if (nb > w.cap_blocks) {
-            if (w.block_sums) hu::device_free(w.block_sums);
-            hu::device_malloc(&w.block_sums, nb * 8);
-            w.cap_blocks = nb;
-        }
+        grow_block_sums(w, nb);
         unsigned long long *total = &d->d_counters[C_OVF_LIST];
         hipLaunchKernelGGL(scan_reduce_kernel<ScanInHasCand>, dim3((unsigned)nb), dim3(SCAN_BLOCK), 0, st, ScanInHasCand{d_cand_count}, S, w.block_sums);
         hipLaunchKernelGGL(scan_block_sums_kernel, dim3(1), dim3(SCAN_BLOCK), 0, st, w.block_sums, nb, total);
@@ -136,8 +127,7 @@ uint64_t device_replay(Device *d, void *stream, uint64_t n_sources, const uint64
         read_counters(d, st);
         n_dense = d->h_counters[C_OVF_LIST];
         if (n_dense > w.cap_dense) {
-            if (w.dense) hu::device_free(w.dense);
-            hu::device_malloc(&w.dense, n_dense * sizeof(Dense));
+            w.dense.alloc(n_dense);
             w.cap_dense = n_dense;
         }
         hipLaunchKernelGGL(replay_dense_fill_kernel, dim3((unsigned)nb), dim3(DENSE_BLOCK), 0, st, d->d_out_nodes, d_cand_count,
@@ -281,8 +271,7 @@ uint64_t device_replay(Device *d, void *stream, uint64_t n_sources, const uint64
     rt.lap("tail + scan");
     d->last_n_pairs = n_pairs;
     if (n_pairs > w.cap_out || !w.out) {
-        if (w.out) hu::device_free(w.out);
-        hu::device_malloc(&w.out, std::max<uint64_t>(n_pairs, 1) * sizeof(mtg_pair));
+        w.out.alloc(std::max<uint64_t>(n_pairs, 1));
         w.cap_out = std::max<uint64_t>(n_pairs, 1);
     }
     if (n_pairs) {
@@ -382,11 +371,9 @@ const mtg_pair *device_resident_pairs(const Device *d, uint64_t *n_out) {
 // the same, handed over: the caller owns the device array now (device_free_array) -- lets the device graph go before the finish starts
 mtg_pair *device_take_pairs(Device *d, uint64_t *n_out) {
     if (n_out) *n_out = d->last_n_pairs;
-    mtg_pair *p = d->replay.out;
-    d->replay.out = nullptr;
     d->replay.cap_out = 0;
     d->last_n_pairs = 0;
-    return p;
+    return d->replay.out.take();
 }
 void device_free_array(int device_id, void *p) {
     hu::device_free_on(device_id, p);

@@ -1305,7 +1305,7 @@ static void launch_level(Device *d, hipStream_t st, const LevelCfg &cfg, bool co
     HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, cfg.block, 0));
     if (occ < 1) occ = 1;
     uint64_t grid = (uint64_t)d->n_cu * (uint64_t)occ;
-    unsigned long long *ws = nullptr;
+    hu::DeviceArray<unsigned long long> ws;
     uint64_t ws_stride = 0;
     if (cfg.global_ws) {
         grid = std::min<uint64_t>(grid, 64);
@@ -1313,7 +1313,7 @@ static void launch_level(Device *d, hipStream_t st, const LevelCfg &cfg, bool co
         // table[H] u64 | stage[SCAP] u64 | log[QCAP] u32 | stage_src[SCAP] u16
         ws_stride = H + (uint64_t)cfg.scap + ((uint64_t)cfg.qcap + 1) / 2 + ((uint64_t)cfg.scap + 3) / 4;
         grid = std::min<uint64_t>(grid, n_batches);
-        hu::device_malloc(&ws, grid * ws_stride * 8);
+        ws.alloc(grid * ws_stride);
     }
     grid = std::max<uint64_t>(1, std::min<uint64_t>(grid, n_batches));
     args.ws = ws;
@@ -1324,7 +1324,7 @@ static void launch_level(Device *d, hipStream_t st, const LevelCfg &cfg, bool co
     HIP_CHECK(hipEventRecord(d->ev1, st));
     if (ws) {
         HIP_CHECK(hipStreamSynchronize(st));
-        hu::device_free(ws);
+        ws.release();
     }
 }
 
@@ -1379,14 +1379,8 @@ static void run_dense_level(Device *d, hipStream_t st, const SsspArgs &a, const 
     HIP_CHECK(hipMemcpyAsync(list.data(), d_list, n_src * 4, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
     std::sort(list.begin(), list.end());
-    uint32_t *d_dist = nullptr, *d_stamp = nullptr, *d_front[2] = {nullptr, nullptr};
-    unsigned long long *d_keys = nullptr, *d_n = nullptr;
-    hu::device_malloc(&d_dist, V * 4);
-    hu::device_malloc(&d_stamp, V * 4);
-    hu::device_malloc(&d_front[0], V * 4);
-    hu::device_malloc(&d_front[1], V * 4);
-    hu::device_malloc(&d_keys, V * 8);
-    hu::device_malloc(&d_n, 16);
+    hu::DeviceArray<uint32_t> d_dist(V), d_stamp(V), d_front[2] = {hu::DeviceArray<uint32_t>(V), hu::DeviceArray<uint32_t>(V)};
+    hu::DeviceArray<unsigned long long> d_keys(V), d_n(2);
     std::vector<unsigned long long> keys;
     std::vector<uint32_t> sources(1);
     for (const uint32_t idx : list) {
@@ -1430,7 +1424,6 @@ static void run_dense_level(Device *d, hipStream_t st, const SsspArgs &a, const 
     }
     HIP_CHECK(hipMemcpyAsync(&d->d_counters[C_POOL], &d->h_counters[C_POOL], 8, hipMemcpyHostToDevice, st));
     HIP_CHECK(hipStreamSynchronize(st));
-    for (void *p : {(void *)d_dist, (void *)d_stamp, (void *)d_front[0], (void *)d_front[1], (void *)d_keys, (void *)d_n}) hu::device_free(p);
 }
 
 void read_counters(Device *d, hipStream_t st) {
@@ -1460,21 +1453,13 @@ int run_levels(Device *d, hipStream_t st, int count_mode, uint64_t src_begin, ui
     a.prune = (prune_count || !count) && enum_prunes(d) ? 1u : 0u;
     if (prune_count && !enum_prunes(d)) MTG_DIE("mtg_sssp_count_visited: this device graph / plan does not prune (k > 255 or plan + 4)");
     if (d->ovf_cap < n) {  // two overflow lists of up to n source indices each + the post-pass work list
-        for (int i = 0; i < 2; i++) {
-            if (d->d_ovf[i]) hu::device_free(d->d_ovf[i]);
-            hu::device_malloc(&d->d_ovf[i], std::max<uint64_t>(n, 1) * sizeof(uint32_t));
-        }
-        if (d->d_fix) hu::device_free(d->d_fix);
-
+        for (auto &l : d->d_ovf) l.alloc(std::max<uint64_t>(n, 1));  // (array by array: alloc() gives the old range back first)
         // (a wave abandons a work-list chunk with fewer than 64 free slots: < 1/7 of every chunk incl. its tag) + three open chunks per wave
         const uint64_t fix_slots = std::max<uint64_t>(n, 1) * 5 / 4 + (uint64_t)d->n_cu * 32 * 3 * ENUM_FIX_CHUNK;
-        hu::device_malloc(&d->d_fix, fix_slots * sizeof(uint32_t));
-        if (d->d_fix_dense) hu::device_free(d->d_fix_dense);
-        hu::device_malloc(&d->d_fix_dense, std::max<uint64_t>(n, 1) * sizeof(uint32_t));
-        if (d->d_fix_val) hu::device_free(d->d_fix_val);
-        hu::device_malloc(&d->d_fix_val, fix_slots * sizeof(unsigned long long));
-        if (d->d_fix_dense_val) hu::device_free(d->d_fix_dense_val);
-        hu::device_malloc(&d->d_fix_dense_val, std::max<uint64_t>(n, 1) * sizeof(unsigned long long));
+        d->d_fix.alloc(fix_slots);
+        d->d_fix_dense.alloc(std::max<uint64_t>(n, 1));
+        d->d_fix_val.alloc(fix_slots);
+        d->d_fix_dense_val.alloc(std::max<uint64_t>(n, 1));
         d->ovf_cap = n;
     }
     a.ovf_list = d->d_ovf[0];
@@ -1626,15 +1611,11 @@ int device_sssp(Device *d, void *stream, uint64_t src_begin, uint64_t src_end, u
 void device_sssp_count(Device *d, void *stream, uint64_t src_begin, uint64_t src_end, mtg_sssp_stats *stats) {
     HIP_CHECK(hipSetDevice(d->dev));
     const uint64_t n = src_end - src_begin;
-    unsigned long long *d_start = nullptr;
-    uint32_t *d_count = nullptr;
-    hu::device_malloc(&d_start, std::max<uint64_t>(n, 1) * 8);
-    hu::device_malloc(&d_count, std::max<uint64_t>(n, 1) * 4);
+    hu::DeviceArray<unsigned long long> d_start(std::max<uint64_t>(n, 1));
+    hu::DeviceArray<uint32_t> d_count(std::max<uint64_t>(n, 1));
     const double keep_ms = d->last_kernel_ms;
     run_levels(d, (hipStream_t)stream, 1, src_begin, src_end, nullptr, 0, d_start, d_count, nullptr, stats);
     d->last_kernel_ms = keep_ms;
-    hu::device_free(d_start);
-    hu::device_free(d_count);
 }
 
 // the same counters for the search the default plan really runs: only the sources that can reach an in-node, successors pruned by
@@ -1642,16 +1623,12 @@ void device_sssp_count(Device *d, void *stream, uint64_t src_begin, uint64_t src
 void device_sssp_count_visited(Device *d, void *stream, uint64_t src_begin, uint64_t src_end, mtg_sssp_stats *stats) {
     HIP_CHECK(hipSetDevice(d->dev));
     const uint64_t n = src_end - src_begin;
-    unsigned long long *d_start = nullptr;
-    uint32_t *d_count = nullptr;
-    hu::device_malloc(&d_start, std::max<uint64_t>(n, 1) * 8);
-    hu::device_malloc(&d_count, std::max<uint64_t>(n, 1) * 4);
+    hu::DeviceArray<unsigned long long> d_start(std::max<uint64_t>(n, 1));
+    hu::DeviceArray<uint32_t> d_count(std::max<uint64_t>(n, 1));
     const double keep_ms = d->last_kernel_ms;
     run_levels(d, (hipStream_t)stream, 3, src_begin, src_end, nullptr, 0, d_start, d_count, nullptr, stats);
     if (stats) stats->sources = d->h_counters[C_ACTIVE];
     d->last_kernel_ms = keep_ms;
-    hu::device_free(d_start);
-    hu::device_free(d_count);
 }
 bool device_prunes(const Device *d) { return enum_prunes(d); }
 uint64_t device_last_active_sources(const Device *d) { return d->last_active_sources; }
@@ -1660,14 +1637,11 @@ uint64_t device_last_active_sources(const Device *d) { return d->last_active_sou
 void device_performance_data(Device *d, void *stream, mtg_dijkstra_performance_data *out) {
     HIP_CHECK(hipSetDevice(d->dev));
     const uint64_t n = d->n_sources;
-    unsigned long long *d_start = nullptr;
-    uint32_t *d_count = nullptr;
-    hu::device_malloc(&d_start, std::max<uint64_t>(n, 1) * 8);
-    hu::device_malloc(&d_count, std::max<uint64_t>(n, 1) * 4);
+    hu::DeviceArray<unsigned long long> d_start(std::max<uint64_t>(n, 1));
+    hu::DeviceArray<uint32_t> d_count(std::max<uint64_t>(n, 1));
     mtg_sssp_stats st{};
     run_levels(d, (hipStream_t)stream, 2, 0, n, nullptr, 0, d_start, d_count, nullptr, &st);
-    hu::device_free(d_start);
-    hu::device_free(d_count);
+    d_start.release(); d_count.release();
     out->dijkstras = n;
     out->iterations = st.settled_nodes;
     out->heap_pushes = d->h_counters[C_PUSHES];

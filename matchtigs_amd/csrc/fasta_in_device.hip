@@ -163,36 +163,30 @@ HostGraph *device_graph_from_sequences(const char *data, const uint64_t *off, ui
     ev.mark(0, st);
     JoinArgs a{};
     a.packed = store.packed; a.off = store.off; a.n_occ = n_occ; a.L = (uint32_t)(k - 1); a.slots = slots;
-    hu::device_malloc(&a.hash, n_occ * 8);
-    hu::device_malloc(&a.flags, n_occ);
-    hu::device_malloc(&a.table, slots * 8);
+    hu::DeviceArray<unsigned long long> d_hash(n_occ);
+    hu::DeviceArray<uint8_t> d_flags(n_occ);
+    hu::DeviceArray<unsigned long long> d_table(slots);
+    a.hash = d_hash; a.flags = d_flags; a.table = d_table;
     HIP_CHECK(hipMemsetAsync(a.table, 0xFF, slots * 8, st));
-    uint32_t *d_creator = nullptr, *d_count = nullptr;
-    hu::device_malloc(&d_creator, n_occ * 4);
-    hu::device_malloc(&d_count, n_occ * 4);
+    hu::DeviceArray<uint32_t> d_creator(n_occ), d_count(n_occ);
     extract_kernel<<<hu::grid_for(n_occ), hu::EB, 0, st>>>(a);
     insert_kernel<<<hu::grid_for(n_occ), hu::EB, 0, st>>>(a, store.small.err());
     lookup_kernel<<<hu::grid_for(n_occ), hu::EB, 0, st>>>(a, d_creator, d_count, store.small.err());
     HIP_CHECK(hipGetLastError());
-    hu::device_free(a.table);
-    hu::device_free(a.hash);
+    d_table.release();  // (before the next group is taken)
+    d_hash.release();
     a.table = nullptr;
     a.hash = nullptr;  // (not read after the lookup)
-    uint64_t *d_first = nullptr, *d_bsum = nullptr;
-    hu::device_malloc(&d_first, n_occ * 8);
-    hu::device_malloc(&d_bsum, (hu::scan_blocks(n_occ) + 2) * 8);
-    hu::scan_u32<uint64_t>(st, d_count, n_occ, d_first, d_bsum, d_bsum + hu::scan_blocks(n_occ) + 1);
-    uint32_t *d_mirror = nullptr, *d_from = nullptr, *d_to = nullptr;
-    uint64_t *d_weight = nullptr;
-    hu::device_malloc(&d_mirror, max_ids * 4);
-    hu::device_malloc(&d_from, n_occ * 4);
-    hu::device_malloc(&d_to, n_occ * 4);
-    hu::device_malloc(&d_weight, n_occ * 8);
+    hu::DeviceArray<uint64_t> d_first(n_occ);
+    hu::ScanScratch<uint64_t> scan(n_occ);
+    scan.scan(st, d_count, n_occ, d_first);
+    hu::DeviceArray<uint32_t> d_mirror(max_ids), d_from(n_occ), d_to(n_occ);
+    hu::DeviceArray<uint64_t> d_weight(n_occ);
     edges_kernel<<<hu::grid_for(U), hu::EB, 0, st>>>(a, d_creator, d_first, d_mirror, d_from, d_to, d_weight);
     HIP_CHECK(hipGetLastError());
     ev.mark(1, st);
     unsigned long long n_nodes = 0;
-    HIP_CHECK(hipMemcpyAsync(&n_nodes, d_bsum + hu::scan_blocks(n_occ) + 1, 8, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(&n_nodes, scan.total(), 8, hipMemcpyDeviceToHost, st));
     store.small.read(st, "plain-FASTA join");
     t.kernel_ms = store.pack_ms + ev.ms(0, 1);
     if (n_nodes > max_ids || n_nodes >= NONE) MTG_DIE("%llu nodes; node ids are 32-bit", n_nodes);
@@ -206,9 +200,8 @@ HostGraph *device_graph_from_sequences(const char *data, const uint64_t *off, ui
     HIP_CHECK(hipMemcpyAsync(weight.data(), d_weight, n_occ * 8, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
     t.download_ms = ms_since(t0);
-    for (void *p : {(void *)a.flags, (void *)d_creator, (void *)d_count, (void *)d_first, (void *)d_bsum, (void *)d_mirror, (void *)d_from,
-                    (void *)d_to, (void *)d_weight})
-        hu::device_free(p);
+    d_flags.release(); d_creator.release(); d_count.release(); d_first.release(); scan.sums.release();  // (before the host builds the graph)
+    d_mirror.release(); d_from.release(); d_to.release(); d_weight.release();
 
     t0 = std::chrono::steady_clock::now();
     HostGraph *g = graph_from_edges(n_nodes, mirror.data(), n_occ, from.data(), to.data(), weight.data());

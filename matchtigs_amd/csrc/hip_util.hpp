@@ -425,6 +425,7 @@ struct DeviceArray {
     ~DeviceArray() { release(); }
     T *alloc(uint64_t n) { release(); device_malloc(&p, n * sizeof(T)); return p; }
     void release() { device_free(p); p = nullptr; }
+    T *take() { T *q = p; p = nullptr; return q; }  // hands the range over: whoever gets the pointer frees it
     T *get() const { return p; }
     operator T *() const { return p; }
 };

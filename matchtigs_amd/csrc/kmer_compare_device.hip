@@ -174,8 +174,7 @@ void device_compare_kmer_sets(const char *seq_a, const uint64_t *off_a, uint64_t
     t.pack_ms = store.pack_ms;
     PhaseEvents<4> ev;
     ev.mark(0, st);
-    unsigned long long *d_table = nullptr;
-    hu::device_malloc(&d_table, slots * 8);
+    hu::DeviceArray<unsigned long long> d_table(slots);
 
     CompareArgs a{};
     a.packed = store.packed; a.off = store.off; a.table = d_table; a.slots = slots; a.k = k;
@@ -215,7 +214,7 @@ void device_compare_kmer_sets(const char *seq_a, const uint64_t *off_a, uint64_t
     t.insert_a_ms = ev.ms(0, 1);  // (with the table's fill)
     t.insert_b_ms = ev.ms(1, 2);
     t.count_ms = ev.ms(2, 3);     // (with the witness passes, if any)
-    hu::device_free(d_table);
+    d_table.release();
     for (int s = 0; s < 2; s++) {
         const unsigned long long w = small.h[5 + s];
         if ((s ? r.only_in_b : r.only_in_a) == 0) continue;

@@ -416,13 +416,13 @@ uint64_t check_offsets(const char *fn, const char *data, const uint64_t *off, ui
 struct KmerIndex {
     mtg_kmer_index_info info{};
     int device_id = 0;
-    uint32_t *packed = nullptr;           // k >= 32, or locating
-    unsigned long long *table = nullptr;  // [info.slots]
+    hu::DeviceArray<uint32_t> packed;            // k >= 32, or locating
+    hu::DeviceArray<unsigned long long> table;   // [info.slots]
     bool locating = false;
-    unsigned long long *where = nullptr;  // locating: [info.slots] the smallest window start of the slot's class
-    unsigned long long *off = nullptr;    // locating: [info.records + 1]
-    uint32_t *weight = nullptr;           // weighted: [info.slots] the weight of the slot's class
-    unsigned long long *color = nullptr;  // coloured: [info.slots] the colour mask of the slot's class
+    hu::DeviceArray<unsigned long long> where;   // locating: [info.slots] the smallest window start of the slot's class
+    hu::DeviceArray<unsigned long long> off;     // locating: [info.records + 1]
+    hu::DeviceArray<uint32_t> weight;            // weighted: [info.slots] the weight of the slot's class
+    hu::DeviceArray<unsigned long long> color;   // coloured: [info.slots] the colour mask of the slot's class
     uint64_t n_colors = 0;                // coloured: 1 .. 64
 };
 
@@ -458,17 +458,16 @@ struct Probe {
     const int device_id;
     hipStream_t st = nullptr;
     MaskedSeqStore store;
-    unsigned long long *d_counts = nullptr;
+    hu::DeviceArray<unsigned long long> d_counts;
     IndexArgs a{};
     PhaseEvents<EVENTS> ev;
 
     Probe(const KmerIndex *ix, const char *seq, const uint64_t *off, uint64_t n, uint64_t words)
         : n(n), words(words), wide(ix->info.k >= 32), device_id(on_device(ix->device_id)), store(seq, off, n, st, device_id) {
-        hu::device_malloc(&d_counts, words * n * 8);
+        d_counts.alloc(words * n);
         a.packed = store.packed; a.off = store.off; a.index_packed = ix->packed; a.table = ix->table; a.slots = ix->info.slots;
         kw::window_args_set_k(a, ix->info.k);
     }
-    ~Probe() { hu::device_free(d_counts); }
     unsigned run_grid() const { return hu::grid_for((store.n_bases + RUN - 1) / RUN); }  // one thread per run of window starts
     void start() {
         ev.mark(0, st);
@@ -522,12 +521,12 @@ KmerIndex *device_kmer_index_build(const char *seq, const uint64_t *off, uint64_
     SeqStore store("indexed sequences", seq, off, n, st, device_id);
     PhaseEvents<2> ev;
     ev.mark(0, st);
-    hu::device_malloc(&ix->table, info.slots * 8);
+    ix->table.alloc(info.slots);
     HIP_CHECK(hipMemsetAsync(ix->table, 0xFF, info.slots * 8, st));
     ix->locating = locating;
     const bool positions = locating || weights || colors;  // the insert notes the smallest window start of every class
     if (positions) {
-        hu::device_malloc(&ix->where, info.slots * 8);
+        ix->where.alloc(info.slots);
         HIP_CHECK(hipMemsetAsync(ix->where, 0xFF, info.slots * 8, st));
     }
     if (info.occurrences) {
@@ -547,34 +546,31 @@ KmerIndex *device_kmer_index_build(const char *seq, const uint64_t *off, uint64_
         HIP_CHECK(hipGetLastError());
     }
     if (weights || colors) {  // (also for an index without windows: its zeroed table is still probed)
-        if (weights) hu::device_malloc(&ix->weight, info.slots * 4);
+        if (weights) ix->weight.alloc(info.slots);
         if (colors) {
-            hu::device_malloc(&ix->color, info.slots * 8);
+            ix->color.alloc(info.slots);
             ix->n_colors = colors->n_colors;
         }
         if (info.occurrences) {
             std::vector<unsigned long long> win_off(n + 1, 0);
             for (uint64_t r = 0; r < n; r++) win_off[r + 1] = win_off[r] + (off[r + 1] - off[r] >= k ? off[r + 1] - off[r] - k + 1 : 0);
-            unsigned long long *d_win_off = nullptr, *d_colors = nullptr;
-            uint32_t *d_weights = nullptr;
-            hu::device_malloc(&d_win_off, (n + 1) * 8);
+            hu::DeviceArray<unsigned long long> d_win_off(n + 1), d_colors;
+            hu::DeviceArray<uint32_t> d_weights;
             hu::upload_sliced(d_win_off, win_off.data(), (n + 1) * 8, st, device_id);
             if (weights) {
-                hu::device_malloc(&d_weights, weights->n * 4);
+                d_weights.alloc(weights->n);
                 hu::upload_sliced(d_weights, weights->w, weights->n * 4, st, device_id);
                 weight_gather_kernel<<<hu::grid_for(info.slots), hu::EB, 0, st>>>(ix->table, ix->where, store.off, n, d_win_off, d_weights, weights->n,
                                                                                  info.slots, ix->weight, store.small.err());
             }
             if (colors) {
-                hu::device_malloc(&d_colors, colors->n * 8);
+                d_colors.alloc(colors->n);
                 hu::upload_sliced(d_colors, colors->c, colors->n * 8, st, device_id);
                 color_gather_kernel<<<hu::grid_for(info.slots), hu::EB, 0, st>>>(ix->table, ix->where, store.off, n, d_win_off, d_colors, colors->n,
                                                                                 info.slots, ix->color, store.small.err());
             }
             HIP_CHECK(hipGetLastError());
-            hu::device_free(d_win_off);  // (synchronises: the gathers are done)
-            hu::device_free(d_weights);
-            hu::device_free(d_colors);
+            // (the three uploads go back here, which synchronises: the gathers are done)
         } else {
             if (weights) HIP_CHECK(hipMemsetAsync(ix->weight, 0, info.slots * 4, st));
             if (colors) HIP_CHECK(hipMemsetAsync(ix->color, 0, info.slots * 8, st));
@@ -596,9 +592,8 @@ KmerIndex *device_kmer_index_build(const char *seq, const uint64_t *off, uint64_
     if (locating) {
         ix->off = store.take_off();
         info.device_bytes += info.slots * 8 + (n + 1) * 8;
-    } else if (ix->where) {  // weighted or coloured only: the positions have done their work
-        hu::device_free(ix->where);
-        ix->where = nullptr;
+    } else {
+        ix->where.release();  // weighted or coloured only: the positions have done their work
     }
     if (weights) info.device_bytes += info.slots * 4;
     if (colors) info.device_bytes += info.slots * 8;
@@ -606,20 +601,18 @@ KmerIndex *device_kmer_index_build(const char *seq, const uint64_t *off, uint64_
 }
 
 bool device_kmer_index_is_locating(const KmerIndex *ix) { return ix->locating; }
-bool device_kmer_index_is_weighted(const KmerIndex *ix) { return ix->weight != nullptr; }
+bool device_kmer_index_is_weighted(const KmerIndex *ix) { return ix->weight.get() != nullptr; }
 uint64_t device_kmer_index_n_colors(const KmerIndex *ix) { return ix->color ? ix->n_colors : 0; }
 
 void device_kmer_index_info(const KmerIndex *ix, mtg_kmer_index_info *out) { *out = ix->info; }
 
 void device_kmer_index_free(KmerIndex *ix) {
     if (!ix) return;
-    hu::device_free_on(ix->device_id, ix->packed);
-    hu::device_free_on(ix->device_id, ix->table);
-    hu::device_free_on(ix->device_id, ix->where);
-    hu::device_free_on(ix->device_id, ix->off);
-    hu::device_free_on(ix->device_id, ix->weight);
-    hu::device_free_on(ix->device_id, ix->color);
+    int cur = 0;  // (an index may die on a thread whose current device is another one)
+    (void)hipGetDevice(&cur);
+    (void)hipSetDevice(ix->device_id);
     delete ix;
+    (void)hipSetDevice(cur);
 }
 
 void device_kmer_index_query(const KmerIndex *ix, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid,
@@ -629,10 +622,10 @@ void device_kmer_index_query(const KmerIndex *ix, const char *seq, const uint64_
     if (times) times->query_upload_ms = times->query_pack_ms = times->query_probe_ms = 0;
     if (n_bases == 0) return;  // nothing to look at
     Probe<> p(ix, seq, off, n, 2);
-    unsigned long long *d_bits = nullptr;  // valid_bits, then present_bits (those asked for)
+    hu::DeviceArray<unsigned long long> d_bits;  // valid_bits, then present_bits (those asked for)
     const int n_arrays = (valid_bits != nullptr) + (present_bits != nullptr);
-    if (n_arrays) hu::device_malloc(&d_bits, n_arrays * bit_words * 8);
-    unsigned long long *d_valid_bits = valid_bits ? d_bits : nullptr;
+    if (n_arrays) d_bits.alloc(n_arrays * bit_words);
+    unsigned long long *d_valid_bits = valid_bits ? d_bits.get() : nullptr;
     unsigned long long *d_present_bits = present_bits ? d_bits + (valid_bits ? bit_words : 0) : nullptr;
     p.start();
     const unsigned grid = hu::grid_for(bit_words);  // (one thread per word: every word of the bit arrays is written)
@@ -645,7 +638,6 @@ void device_kmer_index_query(const KmerIndex *ix, const char *seq, const uint64_
     if (present_bits) HIP_CHECK(hipMemcpyAsync(present_bits, d_present_bits, bit_words * 8, hipMemcpyDeviceToHost, p.st));
     HIP_CHECK(hipStreamSynchronize(p.st));
     if (times) p.booked(&times->query_upload_ms, &times->query_pack_ms, &times->query_probe_ms);  // (the build fields stay)
-    hu::device_free(d_bits);
 }
 
 void device_kmer_index_abundance(const KmerIndex *ix, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid,
@@ -658,9 +650,8 @@ void device_kmer_index_abundance(const KmerIndex *ix, const char *seq, const uin
     if (times) *times = KmerAbundanceTimes();
     if (n_bases == 0) return;  // nothing to look at
     Probe<> p(ix, seq, off, n, 3);  // valid, found, sum
-    uint32_t *d_minmax = nullptr, *d_per_window = nullptr;
-    hu::device_malloc(&d_minmax, 2 * n * 4);
-    if (per_window) hu::device_malloc(&d_per_window, n_bases * 4);
+    hu::DeviceArray<uint32_t> d_minmax(2 * n), d_per_window;
+    if (per_window) d_per_window.alloc(n_bases);
     p.start();
     HIP_CHECK(hipMemsetAsync(d_minmax, 0xFF, n * 4, p.st));
     HIP_CHECK(hipMemsetAsync(d_minmax + n, 0, n * 4, p.st));
@@ -683,8 +674,6 @@ void device_kmer_index_abundance(const KmerIndex *ix, const char *seq, const uin
         p.booked(&times->upload_ms, &times->pack_ms, &times->probe_ms);
         times->download_ms = ms_since(t0);
     }
-    hu::device_free(d_minmax);
-    hu::device_free(d_per_window);
 }
 
 void device_kmer_index_colors(const KmerIndex *ix, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid,
@@ -699,10 +688,9 @@ void device_kmer_index_colors(const KmerIndex *ix, const char *seq, const uint64
     if (times) times->upload_ms = times->pack_ms = times->probe_ms = times->download_ms = 0;
     if (n_bases == 0) return;  // nothing to look at
     Probe<> p(ix, seq, off, n, 2);
-    unsigned long long *d_per_window = nullptr;
-    uint32_t *d_per_color = nullptr;
-    hu::device_malloc(&d_per_color, n * C * 4);
-    if (per_window) hu::device_malloc(&d_per_window, n_bases * 8);
+    hu::DeviceArray<uint32_t> d_per_color(n * C);
+    hu::DeviceArray<unsigned long long> d_per_window;
+    if (per_window) d_per_window.alloc(n_bases);
     p.start();
     HIP_CHECK(hipMemsetAsync(d_per_color, 0, n * C * 4, p.st));
     // (one thread per run: every word of per_window is written)
@@ -720,8 +708,6 @@ void device_kmer_index_colors(const KmerIndex *ix, const char *seq, const uint64
         p.booked(&times->upload_ms, &times->pack_ms, &times->probe_ms);
         times->download_ms = ms_since(t0);
     }
-    hu::device_free(d_per_color);
-    hu::device_free(d_per_window);
 }
 
 void device_kmer_index_locate(const KmerIndex *ix, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid,
@@ -734,13 +720,10 @@ void device_kmer_index_locate(const KmerIndex *ix, const char *seq, const uint64
     if (n_bases == 0) return;  // nothing to look at
     Probe<3> p(ix, seq, off, n, 2);
     hipStream_t st = p.st;
-    unsigned long long *d_hit = nullptr, *d_rank = nullptr, *d_sums = nullptr;  // d_sums: the scan's block sums, then its total
-    uint32_t *d_starts = nullptr;
-    const uint64_t n_sums = hu::scan_blocks(n_bases) + 1;
-    hu::device_malloc(&d_hit, n_bases * 8);
-    hu::device_malloc(&d_starts, n_bases * 4);
-    hu::device_malloc(&d_rank, n_bases * 8);
-    hu::device_malloc(&d_sums, (n_sums + 1) * 8);
+    hu::DeviceArray<unsigned long long> d_hit(n_bases);
+    hu::DeviceArray<uint32_t> d_starts(n_bases);
+    hu::DeviceArray<unsigned long long> d_rank(n_bases);
+    hu::ScanScratch<unsigned long long> scan(n_bases);
     p.start();
     HIP_CHECK(hipMemsetAsync(d_hit, 0xFF, n_bases * 8, st));
     if (p.wide) locate_kernel<true><<<p.run_grid(), hu::EB, 0, st>>>(p.a, p.store.bad, n_bases, n, p.d_counts, ix->where, d_hit);
@@ -751,15 +734,17 @@ void device_kmer_index_locate(const KmerIndex *ix, const char *seq, const uint64
     const unsigned base_grid = hu::grid_for(n_bases);
     run_flag_kernel<<<base_grid, hu::EB, 0, st>>>(ra, d_starts);
     HIP_CHECK(hipGetLastError());
-    hu::scan_u32<unsigned long long>(st, d_starts, n_bases, d_rank, d_sums, d_sums + n_sums);
+    scan.scan(st, d_starts, n_bases, d_rank);
     uint64_t n_runs = 0;
-    HIP_CHECK(hipMemcpyAsync(&n_runs, d_sums + n_sums, 8, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(&n_runs, scan.total(), 8, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
-    unsigned long long *d_ends = nullptr, *d_out = nullptr;  // d_ends: first then last position of every run; d_out: five fields, then the strands
+    hu::DeviceArray<unsigned long long> d_ends;  // first then last position of every run
+    hu::DeviceArray<unsigned char> d_out_bytes;  // five 64-bit fields per run, then the strands
+    unsigned long long *d_out = nullptr;
     if (n_runs) {
-        hu::device_malloc(&d_ends, 2 * n_runs * 8);
-        hu::device_malloc(&d_out, 5 * n_runs * 8 + n_runs);
-        unsigned char *d_strand = reinterpret_cast<unsigned char *>(d_out + 5 * n_runs);
+        d_ends.alloc(2 * n_runs);
+        d_out = reinterpret_cast<unsigned long long *>(d_out_bytes.alloc(5 * n_runs * 8 + n_runs));
+        unsigned char *d_strand = d_out_bytes + 5 * n_runs * 8;
         run_mark_kernel<<<base_grid, hu::EB, 0, st>>>(ra, d_starts, d_rank, n_runs, d_ends, d_ends + n_runs);
         run_emit_kernel<<<hu::grid_for(n_runs), hu::EB, 0, st>>>(ra, n_runs, d_ends, d_ends + n_runs, d_out, d_strand);
         HIP_CHECK(hipGetLastError());
@@ -780,7 +765,6 @@ void device_kmer_index_locate(const KmerIndex *ix, const char *seq, const uint64
         p.booked(&times->upload_ms, &times->pack_ms, &times->probe_ms);
         times->runs_ms = p.ev.ms(1, 2);
     }
-    for (const void *d : std::initializer_list<const void *>{d_hit, d_starts, d_rank, d_sums, d_ends, d_out}) hu::device_free(d);
 }
 
 }  // namespace mtg

@@ -85,15 +85,12 @@ struct PhaseEvents {
 // ACGT (all ones: none; pack_kernel), [1] error bits of the class-table kernels (low 32 bits; zero: none), [2..7] the stage's own,
 // zeroed. read() brings all eight to h[] and dies on an error bit.
 struct ScalarBlock {
-    unsigned long long *d = nullptr;
+    hu::DeviceArray<unsigned long long> d;
     unsigned long long h[8] = {};
-    explicit ScalarBlock(hipStream_t st) {
-        hu::device_malloc(&d, sizeof h);
+    explicit ScalarBlock(hipStream_t st) : d(8) {
         HIP_CHECK(hipMemsetAsync(d, 0, sizeof h, st));
         HIP_CHECK(hipMemsetAsync(d, 0xFF, 8, st));
     }
-    ~ScalarBlock() { hu::device_free(d); }
-    ScalarBlock(const ScalarBlock &) = delete;
     unsigned int *err() const { return reinterpret_cast<unsigned int *>(d + 1); }
     void read(hipStream_t st, const char *stage) {
         HIP_CHECK(hipMemcpyAsync(h, d, sizeof h, hipMemcpyDeviceToHost, st));
@@ -105,10 +102,10 @@ struct ScalarBlock {
 // The packed store of `n_rec` records on the device: bases [off[r], off[r + 1]) are record r, off[0] = 0. The constructor uploads the
 // ASCII (`ascii`, followed by the last `tail_bases` bases from `tail` if given) and the offsets, packs, frees the ASCII and dies with
 // "`what`: character at offset ..." if a character is outside ACGT. On return the stream is idle, `packed` (padded as the invariant at
-// the top says) and `off` are ready, and `small` is the stage's scalar block. The destructor frees all three.
+// the top says) and `off` are ready, and `small` is the stage's scalar block. All three are owners.
 struct SeqStore {
-    uint32_t *packed = nullptr;
-    unsigned long long *off = nullptr;  // [n_rec + 1]
+    hu::DeviceArray<uint32_t> packed;
+    hu::DeviceArray<unsigned long long> off;  // [n_rec + 1]
     ScalarBlock small;
     uint64_t n_bases, n_words;
     double upload_ms = 0.0, pack_ms = 0.0;
@@ -117,10 +114,9 @@ struct SeqStore {
              const char *tail = nullptr, uint64_t tail_bases = 0)
         : small(st), n_bases(h_off[n_rec]), n_words((h_off[n_rec] + 15) / 16) {
         const auto t0 = std::chrono::steady_clock::now();
-        char *d_ascii = nullptr;
-        hu::device_malloc(&d_ascii, n_bases ? n_bases : 1);
-        hu::device_malloc(&packed, (n_words + 2) * 4);
-        hu::device_malloc(&off, (n_rec + 1) * 8);
+        hu::DeviceArray<char> d_ascii(n_bases ? n_bases : 1);
+        packed.alloc(n_words + 2);
+        off.alloc(n_rec + 1);
         HIP_CHECK(hipMemsetAsync(packed + n_words, 0, 8, st));
         hu::upload_sliced(off, h_off, (n_rec + 1) * 8, st, device_id);
         hu::upload_sliced(d_ascii, ascii, n_bases - tail_bases, st, device_id);
@@ -131,37 +127,23 @@ struct SeqStore {
         if (n_words) pack_kernel<<<hu::grid_for(n_words), hu::EB, 0, st>>>(d_ascii, n_bases, packed, small.d);
         HIP_CHECK(hipGetLastError());
         ev.mark(1, st);
-        hu::device_free(d_ascii);  // (synchronises: the pack is done)
+        d_ascii.release();  // (synchronises: the pack is done)
         HIP_CHECK(hipMemcpyAsync(small.h, small.d, 8, hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipStreamSynchronize(st));
         if (small.h[0] != ~0ull) MTG_DIE("%s: character at offset %llu is not in the DNA alphabet (ACGT)", what, small.h[0]);
         pack_ms = ev.ms(0, 1);
     }
-    ~SeqStore() {
-        hu::device_free(packed);
-        hu::device_free(off);
-    }
-    SeqStore(const SeqStore &) = delete;
-    // the packed bases leave the store: the caller frees them (hu::device_free)
-    uint32_t *take_packed() {
-        uint32_t *p = packed;
-        packed = nullptr;
-        return p;
-    }
-    // ... and so do the offsets
-    unsigned long long *take_off() {
-        unsigned long long *p = off;
-        off = nullptr;
-        return p;
-    }
+    // the packed bases and the offsets may leave the store with their ranges (the k-mer index keeps them)
+    hu::DeviceArray<uint32_t> take_packed() { return std::move(packed); }
+    hu::DeviceArray<unsigned long long> take_off() { return std::move(off); }
 };
 
 // SeqStore for records of arbitrary bytes: nothing aborts. A character outside ACGT is packed as A and has its bit set in `bad`
 // (bit b & 63 of word b >> 6 for base b; every bit from n_bases on is 0, and one zeroed word lies behind the last).
 struct MaskedSeqStore {
-    uint32_t *packed = nullptr;
-    unsigned long long *off = nullptr;  // [n_rec + 1]
-    unsigned long long *bad = nullptr;  // [(n_bases + 63) / 64 + 1]
+    hu::DeviceArray<uint32_t> packed;
+    hu::DeviceArray<unsigned long long> off;  // [n_rec + 1]
+    hu::DeviceArray<unsigned long long> bad;  // [(n_bases + 63) / 64 + 1]
     uint64_t n_bases, n_words;
     double upload_ms = 0.0, pack_ms = 0.0;
 
@@ -169,11 +151,10 @@ struct MaskedSeqStore {
         : n_bases(h_off[n_rec]), n_words((h_off[n_rec] + 15) / 16) {
         const auto t0 = std::chrono::steady_clock::now();
         const uint64_t bad_bytes = ((n_bases + 63) / 64 + 1) * 8;
-        char *d_ascii = nullptr;
-        hu::device_malloc(&d_ascii, n_bases ? n_bases : 1);
-        hu::device_malloc(&packed, (n_words + 2) * 4);
-        hu::device_malloc(&bad, bad_bytes);
-        hu::device_malloc(&off, (n_rec + 1) * 8);
+        hu::DeviceArray<char> d_ascii(n_bases ? n_bases : 1);
+        packed.alloc(n_words + 2);
+        bad.alloc(bad_bytes / 8);
+        off.alloc(n_rec + 1);
         HIP_CHECK(hipMemsetAsync(packed + n_words, 0, 8, st));
         HIP_CHECK(hipMemsetAsync(bad, 0, bad_bytes, st));
         hu::upload_sliced(off, h_off, (n_rec + 1) * 8, st, device_id);
@@ -181,18 +162,12 @@ struct MaskedSeqStore {
         upload_ms = ms_since(t0);
         PhaseEvents<2> ev;
         ev.mark(0, st);
-        if (n_words) pack_masked_kernel<<<hu::grid_for(n_words), hu::EB, 0, st>>>(d_ascii, n_bases, packed, reinterpret_cast<unsigned short *>(bad));
+        if (n_words) pack_masked_kernel<<<hu::grid_for(n_words), hu::EB, 0, st>>>(d_ascii, n_bases, packed, reinterpret_cast<unsigned short *>(bad.get()));
         HIP_CHECK(hipGetLastError());
         ev.mark(1, st);
-        hu::device_free(d_ascii);  // (synchronises: the pack is done)
+        d_ascii.release();  // (synchronises: the pack is done)
         pack_ms = ev.ms(0, 1);
     }
-    ~MaskedSeqStore() {
-        hu::device_free(packed);
-        hu::device_free(bad);
-        hu::device_free(off);
-    }
-    MaskedSeqStore(const MaskedSeqStore &) = delete;
 };
 
 }  // namespace mtg

@@ -232,28 +232,22 @@ uint64_t device_write_walks_text(const HostGraph &g, uint64_t n_walks, const uin
     const uint64_t n_orig = g.n_original_edges, n_dummy = g.edge_count() - n_orig, U = n_orig / 2;
     hipStream_t st = nullptr;
     SeqStore seq("unitig sequences", seqs, seq_off, U, st, device_id);
-    char *d_out = nullptr;
-    uint32_t *d_edges = nullptr, *d_ws = nullptr, *d_unitig = nullptr, *d_dw = nullptr, *d_lo = nullptr, *d_hi = nullptr;
-    uint8_t *d_fwd = nullptr;
-    unsigned long long *d_limits = nullptr, *d_start = nullptr, *d_bsum = nullptr, *d_tot = nullptr;
-    hu::device_malloc(&d_tot, 8);
+    hu::DeviceArray<unsigned long long> d_tot(1);
     // per-edge tables the positions index (u32 / u8 instead of the host graph's 64-bit fields)
     PodVec<uint32_t> h_dw(std::max<uint64_t>(n_dummy / 2, 1));
     for (uint64_t i = 0; i < n_dummy / 2; i++) h_dw[i] = (uint32_t)std::min<uint64_t>(g.w_biedge[n_orig / 2 + i], 0xFFFFFFFFull);
-    hu::device_malloc(&d_dw, std::max<uint64_t>(n_dummy / 2, 1) * 4);
+    hu::DeviceArray<uint32_t> d_dw(std::max<uint64_t>(n_dummy / 2, 1)), d_edges;
+    hu::DeviceArray<unsigned long long> d_limits;
     if (!resident) {
-        hu::device_malloc(&d_edges, std::max<uint64_t>(P, 1) * 4);
-        hu::device_malloc(&d_limits, std::max<uint64_t>(n_walks, 1) * 8);
+        d_edges.alloc(std::max<uint64_t>(P, 1));
+        d_limits.alloc(std::max<uint64_t>(n_walks, 1));
     }
-    unsigned long long *d_err = nullptr;
-    hu::device_malloc(&d_err, 16);
+    hu::DeviceArray<unsigned long long> d_err(2);
     HIP_CHECK(hipMemsetAsync(d_err, 0xFF, 16, st));
-    hu::device_malloc(&d_ws, (P + 1) * 4);
-    hu::device_malloc(&d_lo, (P + 1) * 4);
-    hu::device_malloc(&d_hi, (P + 1) * 4);
-    hu::device_malloc(&d_start, (P + 2) * 8);
+    hu::DeviceArray<uint32_t> d_ws(P + 1), d_lo(P + 1), d_hi(P + 1);
+    hu::DeviceArray<unsigned long long> d_start(P + 2);
     const uint64_t nb = (P + 1 + 1023) / 1024;
-    hu::device_malloc(&d_bsum, nb * 8);
+    hu::DeviceArray<unsigned long long> d_bsum(nb);
     if (n_dummy) HIP_CHECK(hipMemcpyAsync(d_dw, h_dw.data(), n_dummy / 2 * 4, hipMemcpyHostToDevice, st));
     HIP_CHECK(hipMemsetAsync(d_ws, 0, (P + 1) * 4, st));
     if (resident) {
@@ -265,7 +259,7 @@ uint64_t device_write_walks_text(const HostGraph &g, uint64_t n_walks, const uin
         hipLaunchKernelGGL(mark_starts_kernel, dim3((unsigned)((n_walks + 1 + 255) / 256)), dim3(256), 0, st, d_limits, n_walks, P, d_ws);
     }
     SpellArgs a{};
-    a.edges = resident ? resident->d_edges : d_edges; a.walk_start = d_ws; a.dummy_w = d_dw; a.seq_off = seq.off; a.packed = seq.packed;
+    a.edges = resident ? resident->d_edges : d_edges.get(); a.walk_start = d_ws; a.dummy_w = d_dw; a.seq_off = seq.off; a.packed = seq.packed;
     a.n_pos = P; a.n_orig = n_orig; a.k = (uint32_t)k; a.rec_prefix = gfa ? 2 : 1; a.sep = gfa ? '\t' : '\n'; a.head_bytes = head.size();
     hipLaunchKernelGGL(extent_kernel, dim3((unsigned)((P + 1 + 255) / 256)), dim3(256), 0, st, a, d_lo, d_hi);
     hipLaunchKernelGGL(scan64_reduce_kernel, dim3((unsigned)nb), dim3(1024), 0, st, d_lo, d_hi, P + 1, d_bsum);
@@ -276,15 +270,16 @@ uint64_t device_write_walks_text(const HostGraph &g, uint64_t n_walks, const uin
     HIP_CHECK(hipMemcpyAsync(&h_tot, d_tot, 8, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipMemcpyAsync(h_err, d_err, 16, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
-    hu::device_free(d_err);
+    d_err.release();
     if (h_err[0] != ~0ull && h_err[0] < h_err[1]) MTG_DIE("empty walk %llu", h_err[0]);  // (the first offending walk, as the host loop reports it)
     if (h_err[1] != ~0ull) MTG_DIE("walk %llu starts with a dummy edge (bin.rs:489)", h_err[1]);
     const uint64_t total = n_walks ? h_tot : head.size();
     char *out = static_cast<char *>(std::malloc(total + 1));
     if (!out) MTG_DIE("out of memory (%llu bytes)", (unsigned long long)total);
     double ms = 0.0;
+    hu::DeviceArray<char> d_out;
     if (n_walks) {
-        hu::device_malloc(&d_out, total);
+        d_out.alloc(total);
         hipEvent_t e0, e1;
         HIP_CHECK(hipEventCreate(&e0));
         HIP_CHECK(hipEventCreate(&e1));
@@ -304,9 +299,6 @@ uint64_t device_write_walks_text(const HostGraph &g, uint64_t n_walks, const uin
     out[total] = '\0';
     if (kernel_ms_out) *kernel_ms_out = ms;
     if (bytes_out) *bytes_out = total + seq.n_bases / 4 + (P + 1) * (8 + 4 + 4);
-    for (void *p : {(void *)d_out, (void *)d_edges, (void *)d_ws, (void *)d_unitig, (void *)d_dw, (void *)d_lo, (void *)d_hi,
-                    (void *)d_fwd, (void *)d_limits, (void *)d_start, (void *)d_bsum, (void *)d_tot})
-        hu::device_free(p);
     *out_buf = out;
     return total;
 }
