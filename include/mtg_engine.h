@@ -861,6 +861,8 @@ void mtg_last_fastq_times(double out[6]);
 uint64_t mtg_unitigs_count(const mtg_unitigs *u);
 const char *mtg_unitigs_data(const mtg_unitigs *u);        /* concatenated ASCII sequences */
 const uint64_t *mtg_unitigs_offsets(const mtg_unitigs *u); /* count + 1 offsets into data */
+/* A new store of the records i of `u` with keep[i] != 0 (count bytes), in their order; host only. Free with mtg_unitigs_free. */
+void mtg_unitigs_select(const mtg_unitigs *u, const uint8_t *keep, mtg_unitigs **out);
 void mtg_unitigs_free(mtg_unitigs *u);
 /* Spells `tigs` (mtg_write_walks_fasta) into a file; a ".gz" suffix selects gzip at compression_level 0-9
  * (bin.rs:203, :442-446; pass 6 for the reference's default). Returns the uncompressed byte count. */
@@ -908,6 +910,34 @@ uint64_t mtg_write_unitig_graph_file(const mtg_graph *g, const char *unitig_seqs
  * events, ms --, download (host clock, ms), links, bytes of the text, bytes the text kernel must move at the least, peak of the
  * device arena's live bytes}. */
 void mtg_last_unitig_graph_times(double out[9]);
+/* ---- the connected components of the unitig graph, on the GPU ------------------------------------------------
+ * Unitigs u and v are adjacent iff some orientation of the one links to some orientation of the other by the rule of
+ * mtg_unitig_links (from(edge o') == to(edge o), original edges only); a component is a class of the closure of that: connectivity
+ * over LINKS, not over shared nodes. Components are numbered 0 .. C - 1 by their smallest unitig, ascending. One entry per
+ * component: its smallest unitig, its unitigs, the sums of unitig_kmers and of unitig_kc over them, its link entries (those of
+ * mtg_unitig_links whose source orientation lies in it), its orientations without a link, and its orientations whose number of links
+ * is not 1 -- none: every orientation has exactly one way on and the component is a closed ring. */
+typedef struct mtg_component_arrays {
+    uint32_t *first_unitig;
+    uint32_t *unitigs;
+    uint64_t *kmers;
+    uint64_t *abundance;
+    uint64_t *links;
+    uint32_t *dead_ends;
+    uint32_t *irregular;
+} mtg_component_arrays;
+/* unitig_kmers: the number of k-mers of every unitig (U values); unitig_kc: their abundance sums, or NULL for the number of k-mers.
+ * *component_of gets U component numbers; it and the seven arrays of *components are released with mtg_free. Fewer than 2^31
+ * unitigs. Returns C. The link lists are not built. Aborts without a GPU. */
+uint64_t mtg_unitig_components(const mtg_graph *g, const uint64_t *unitig_kmers, const uint64_t *unitig_kc, int device_id,
+                               uint32_t **component_of, mtg_component_arrays *components);
+/* Of the last mtg_unitig_components on this thread: {upload (host clock, ms), label kernels, statistics kernel -- HIP events, ms --,
+ * download (host clock, ms), components, unitigs, peak of the device arena's live bytes, and the parts of the label kernels' time:
+ * rep / degree, the unions, flatten + scan + numbers}. The union-find's retries are not counted. */
+void mtg_last_unitig_components_times(double out[10]);
+/* Measurement switch: 0 sends every unitig's statistics to its component's counters by itself; the default (1) aggregates the lanes
+ * of a wave that share a component first. The results are the same. */
+void mtg_set_unitig_components_aggregation(int on);
 /* Duplication bitvectors (implementation/mod.rs:668-702): one line per tig with `weight` characters per edge, '1' for an
  * original edge and '0' for a dummy edge (k-mers that repeat ones spelled elsewhere). */
 uint64_t mtg_write_duplication_bitvector(const mtg_graph *g, uint64_t n_walks, const uint64_t *limits, const uint32_t *edges,

@@ -45,6 +45,12 @@ pops an arm only if the best has at least R times its mean abundance, which keep
 `--unitigs-fa-out` and before the tig algorithms: as BCALM2/GGCAT FASTA (`>id LN:i: KC:i: km:f: L:+:id:-`, what `--bcalm-in` reads) and
 as GFA1 (`S` and `L` lines with a k-1 overlap). The link lists and the whole text are made on the GPU; `KC` is the summed abundance of
 the unitig's k-mers where the compaction counted them, else their number.
+`--components-out` and `--unitig-components-out` (any input; not in the reference) describe how that graph falls apart: one TSV row
+per connected component over the links -- unitigs, k-mers, bases, abundance, links, dead ends, whether it is a closed ring -- and
+the component of every unitig, line i for record i of `--unitigs-fa-out`; the labels and the sums are made on the GPU without the
+link lists. `--min-component-kmers N` (`--seq-in`, `--fa-in`) removes every component of fewer than N k-mers -- the clusters of two
+or three short unitigs that are neither tip nor isolated nor bubble -- once, before `--verify` and every output; links exist only
+inside a component, so what stays is still maximal and nothing is compacted again.
 """
 from __future__ import annotations
 
@@ -77,6 +83,14 @@ def main(argv=None) -> int:
     ap.add_argument("--unitigs-gfa-out", metavar="PATH",
                     help="write the input's unitigs with their links as GFA1: S lines with LN, KC and km tags, L lines with a k-1 "
                          "overlap (.gz => gzip) (not in the reference)")
+    ap.add_argument("--components-out", metavar="PATH",
+                    help="write one TSV row per connected component of the unitig graph over its links: component, first_unitig, "
+                         "unitigs, kmers, bases, abundance, mean, links, dead_ends, circular (.gz => gzip) (not in the reference)")
+    ap.add_argument("--unitig-components-out", metavar="PATH",
+                    help="write the component of every unitig, line i for record i of --unitigs-fa-out (.gz => gzip) (not in the reference)")
+    ap.add_argument("--min-component-kmers", type=int, metavar="N",
+                    help="with --seq-in or --fa-in: remove the connected components of fewer than N k-mers before --verify and every "
+                         "output (not in the reference)")
     ap.add_argument("-k", type=int, help="k-mer size used to build the de Bruijn graph (bin.rs:139-141)")
     ap.add_argument("-t", "--threads", type=int, default=1, help="accepted; results always equal the 1-thread order (bin.rs:148-149)")
     ap.add_argument("--greedytigs-fa-out", help="write greedy matchtigs as fasta (.gz => gzip) (bin.rs:107-109)")
@@ -215,12 +229,22 @@ def main(argv=None) -> int:
         ap.error("--clean-rounds must be in 1..64")
     if args.min_abundance is not None and args.min_abundance < 1:
         ap.error("--min-abundance must be >= 1")
+    if args.min_component_kmers is not None:
+        if args.min_component_kmers < 1:
+            ap.error("--min-component-kmers must be >= 1")
+        if args.bcalm_in is not None:
+            ap.error("--min-component-kmers needs --seq-in or --fa-in")
+        for flag, value in (("--color-matrix-out", args.color_matrix_out), ("--unitig-colors-out", args.unitig_colors_out),
+                            ("--query-colors-out", args.query_colors_out), ("--monochromatic-unitigs", args.monochromatic_unitigs or None),
+                            ("--color-classes-out", args.color_classes_out), ("--unitig-color-classes-out", args.unitig_color_classes_out)):
+            if value is not None:
+                ap.error(f"--min-component-kmers cannot be combined with {flag}")
     for flag, value in (("--min-base-quality", args.min_base_quality), ("--query-min-base-quality", args.query_min_base_quality)):
         if value is not None and not 0 <= value <= 93:
             ap.error(f"{flag} must be in 0..93")
     if not (args.color_classes_out or args.unitig_color_classes_out or args.color_matrix_out or args.unitig_colors_out or args.kmer_spectrum_out or args.unitig_abundance_out or args.unitig_kmer_abundance_out or args.query_fa or args.greedytigs_fa_out or args.eulertigs_fa_out or args.greedytigs_gfa_out or args.eulertigs_gfa_out
             or args.greedytigs_duplication_bitvector_out or args.matchtigs_fa_out or args.matchtigs_gfa_out or args.verify_fa or args.unitigs_fa_out
-            or args.unitigs_bcalm_out or args.unitigs_gfa_out):
+            or args.unitigs_bcalm_out or args.unitigs_gfa_out or args.components_out or args.unitig_components_out):
         ap.error("nothing to do: give --greedytigs-fa-out / --greedytigs-gfa-out and/or --eulertigs-fa-out / --eulertigs-gfa-out")
 
     from . import api
@@ -265,7 +289,8 @@ def _read_seq_in(api, args, fastq, record_colors=None):
 
 def _run(api, args, fastq) -> int:
     t0 = time.perf_counter()
-    cleaning = bubbles = None
+    cleaning = bubbles = abundance = None
+    component_filter = args.min_component_kmers is not None  # 
     if args.bcalm_in is not None:
         graph, store = api.read_bcalm2(args.bcalm_in, args.k)
     elif args.seq_in is not None:  # sequences -> unitigs (GPU compaction) -> graph (the --fa-in join on the same store)
@@ -310,9 +335,9 @@ def _run(api, args, fastq) -> int:
                 print(f"nothing is left after cleaning ({cleaning.describe()}; {bubbles.describe() + '; ' if bubbles is not None else ''}"
                       f"{abundance.describe()})", file=sys.stderr)
                 return 1
-            if args.unitig_abundance_out:
+            if args.unitig_abundance_out and not component_filter:  # (with the component filter: after it, below)
                 _write_unitig_abundance(args, store, abundance)
-            if args.unitig_kmer_abundance_out:
+            if args.unitig_kmer_abundance_out and not component_filter:
                 _write_unitig_kmer_abundance(args, store, abundance)
             if args.color_matrix_out:
                 _write_color_matrix(args, colors)
@@ -336,10 +361,37 @@ def _run(api, args, fastq) -> int:
         loaded += f"{bubbles.describe()}; " if bubbles is not None else ""
         loaded += f"{pieces_cut} non-ACGT runs cut)"
     print(loaded, file=sys.stderr)
+    component_kmers = 0  # the k-mers the component filter removed
+    if component_filter:  # once, in front of everything that reads the unitigs; links exist only inside a component, so what stays is maximal
+        import dataclasses
+
+        import numpy as np
+
+        given = store  # (what --fa-in's unitigs are verified against)
+        store, keep, before = api.select_components(graph, given, args.k, args.min_component_kmers,
+                                                    abundance.unitig_sums if abundance is not None else None, args.device)
+        small = before.kmers < np.uint64(args.min_component_kmers)
+        component_kmers = int(before.kmers[small].sum())
+        print(f"Component filter: {int(small.sum())} of {len(before)} components have fewer than {args.min_component_kmers} k-mers: "
+              f"{int(before.unitigs[small].sum())} unitigs, {component_kmers} k-mers removed, {len(store)} unitigs left "
+              f"({before.describe()})", file=sys.stderr)
+        if len(store) == 0:
+            print(f"nothing is left after the component filter (--min-component-kmers {args.min_component_kmers}; {before.describe()})",
+                  file=sys.stderr)
+            return 1
+        if abundance is not None:  # the abundances of the kept unitigs, for the outputs, KC and the weighted queries
+            kmers = (np.diff(given.arrays()[1]) - np.uint64(args.k - 1)).astype(np.int64)
+            abundance = dataclasses.replace(abundance, unitig_sums=abundance.unitig_sums[keep], kmer_counts=(
+                None if abundance.kmer_counts is None else abundance.kmer_counts[np.repeat(keep, kmers)]))
+        graph = api.Bigraph.from_sequences(store.arrays(), args.k, args.device)
+        if args.unitig_abundance_out:
+            _write_unitig_abundance(args, store, abundance)
+        if args.unitig_kmer_abundance_out:
+            _write_unitig_kmer_abundance(args, store, abundance)
     # what the tigs are verified against: the input as given -- on the --seq-in route the sequences, so that the check covers the compaction
     truth = seqs if args.seq_in is not None else store
     filtered = args.seq_in is not None and abundance is not None and min_abundance > 1
-    if filtered or cleaning is not None:  # the tigs spell S_m less what the cleaning took, not the input's set: they are held to the
+    if filtered or cleaning is not None or component_filter:  # the tigs spell S_m less what the cleaning took, not the input's set: they are held to the
         truth = store                     # unitigs, and the unitigs to the input (below)
     cleaned_away = (cleaning.removed_kmers if cleaning is not None else 0) + (bubbles.arm_kmers if bubbles is not None else 0)
 
@@ -356,20 +408,26 @@ def _run(api, args, fastq) -> int:
         return cmp.equal
 
     all_equal = True
-    if (filtered or cleaning is not None) and (args.verify or args.verify_fa):
-        # by the k-mer set comparison, a kernel the compaction does not share: no foreign k-mer survived, and exactly the dropped and
-        # the cleaned are gone
-        cmp = api.compare_kmer_sets(seqs, store, args.k, args.device)
-        ok = cmp.only_in_b == 0 and cmp.only_in_a == abundance.dropped + cleaned_away
+    if (filtered or cleaning is not None or component_filter) and (args.verify or args.verify_fa):
+        # by the k-mer set comparison, a kernel the compaction does not share: no foreign k-mer survived, and exactly the dropped, the
+        # cleaned and those of the removed components are gone
+        cmp = api.compare_kmer_sets(seqs if args.seq_in is not None else given, store, args.k, args.device)
+        dropped = abundance.dropped if abundance is not None else 0
+        ok = cmp.only_in_b == 0 and cmp.only_in_a == dropped + cleaned_away + component_kmers
         if filtered:
             print(f"Verifying abundance filter: {cmp.distinct_b} of the input's {cmp.distinct_a} distinct k-mers are in the unitigs, "
-                  f"{cmp.only_in_a - cleaned_away} are not ({abundance.dropped} dropped by the filter), {cmp.only_in_b} foreign: "
+                  f"{cmp.only_in_a - cleaned_away - component_kmers} are not ({abundance.dropped} dropped by the filter), {cmp.only_in_b} foreign: "
                   f"{'as counted' if ok else 'MISMATCH'}", file=sys.stderr)
         if cleaning is not None:
             print(f"Verifying cleaning: {cmp.distinct_b} of the input's {cmp.distinct_a} distinct k-mers are in the unitigs, "
-                  f"{cmp.only_in_a} are not ({abundance.dropped} dropped by the filter, {cleaning.tip_kmers} in tips, "
+                  f"{cmp.only_in_a - component_kmers} are not ({abundance.dropped} dropped by the filter, {cleaning.tip_kmers} in tips, "
                   f"{cleaning.isolated_kmers} in isolated unitigs{f', {bubbles.arm_kmers} in bubble arms' if bubbles is not None else ''}), "
                   f"{cmp.only_in_b} foreign: {'as counted' if ok else 'MISMATCH'}", file=sys.stderr)
+        if component_filter:
+            print(f"Verifying component filter: {cmp.distinct_b} of the input's {cmp.distinct_a} distinct k-mers are in the unitigs, "
+                  f"{cmp.only_in_a} are not ({dropped} dropped by the abundance filter, {cleaned_away} cleaned away, {component_kmers} in "
+                  f"components of fewer than {args.min_component_kmers} k-mers), {cmp.only_in_b} foreign: "
+                  f"{'as counted' if ok else 'MISMATCH'}", file=sys.stderr)
         all_equal &= ok
     for path in args.verify_fa or ():
         tigs = api.read_sequences(path)
@@ -387,6 +445,16 @@ def _run(api, args, fastq) -> int:
                 print(f"Writing unitig graph took {time.perf_counter() - t1:.1f}s ({r['unitigs']} unitigs, {r['links']} links, "
                       f"{r['bytes']} bytes)", file=sys.stderr)
                 t1 = time.perf_counter()
+    if args.components_out or args.unitig_components_out:  # how the graph as written falls apart
+        t1 = time.perf_counter()
+        comps = api.unitig_components(graph, store, args.k, abundance.unitig_sums if args.seq_in is not None and abundance is not None else None,
+                                      args.device)
+        if args.components_out:
+            _write_components(args, comps)
+        if args.unitig_components_out:
+            with _open_text(args, args.unitig_components_out) as f:
+                f.write("".join(f"{c}\n" for c in comps.component_of.tolist()))
+        print(f"Writing components took {time.perf_counter() - t1:.1f}s ({comps.describe()})", file=sys.stderr)
     for name, alg, out, gfa, dup in (("matchtigs", 4, args.matchtigs_fa_out, args.matchtigs_gfa_out,
                                       args.matchtigs_duplication_bitvector_out),
                                      ("eulertigs", 3, args.eulertigs_fa_out, args.eulertigs_gfa_out, None),
@@ -417,6 +485,18 @@ def _open_text(args, path):
     import gzip
 
     return gzip.open(path, "wt", compresslevel=args.compression_level) if path.endswith(".gz") else open(path, "w")
+
+
+def _write_components(args, comps) -> None:
+    """`--components-out`: one row per component, in order; mean = abundance / kmers with one decimal, rounded half up in integers,
+    as the `km` of the unitig graph output."""
+    with _open_text(args, args.components_out) as f:
+        f.write("component\tfirst_unitig\tunitigs\tkmers\tbases\tabundance\tmean\tlinks\tdead_ends\tcircular\n")
+        for c, (first, n, m, a, links, dead, irregular) in enumerate(zip(
+                comps.first_unitig.tolist(), comps.unitigs.tolist(), comps.kmers.tolist(), comps.abundance.tolist(), comps.links.tolist(),
+                comps.dead_ends.tolist(), comps.irregular.tolist())):
+            t = (10 * a + m // 2) // m
+            f.write(f"{c}\t{first}\t{n}\t{m}\t{m + (args.k - 1) * n}\t{a}\t{t // 10}.{t % 10}\t{links}\t{dead}\t{1 if irregular == 0 else 0}\n")
 
 
 def _write_spectrum(args, abundance) -> None:

@@ -158,6 +158,12 @@ class MtgKmerIndexInfo(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class MtgComponentArrays(C.Structure):
+    """mtg_component_arrays (include/mtg_engine.h): one array per field, one entry per component; each goes back through mtg_free."""
+
+    _fields_ = [(n, C.c_void_p) for n in ("first_unitig", "unitigs", "kmers", "abundance", "links", "dead_ends", "irregular")]
+
+
 class MtgDijkstraPerformanceData(C.Structure):
     _fields_ = [
         ("dijkstras", C.c_uint64),
@@ -385,6 +391,10 @@ def load():
         "mtg_write_unitig_graph_text": (u64, [vp, vp, vp, u64, u64, vp, C.c_int, C.c_int, P(vp)]),
         "mtg_write_unitig_graph_file": (u64, [vp, vp, vp, u64, u64, vp, C.c_int, C.c_int, C.c_char_p, C.c_int]),
         "mtg_last_unitig_graph_times": (None, [P(C.c_double)]),
+        "mtg_unitig_components": (u64, [vp, vp, vp, C.c_int, P(vp), P(MtgComponentArrays)]),
+        "mtg_last_unitig_components_times": (None, [P(C.c_double)]),
+        "mtg_set_unitig_components_aggregation": (None, [C.c_int]),
+        "mtg_unitigs_select": (None, [vp, vp, P(vp)]),
         "mtg_write_duplication_bitvector": (u64, [vp, u64, vp, vp, P(vp)]),
         "mtg_write_tigs_duplication_bitvector_file": (u64, [vp, vp, C.c_char_p]),
         "mtg_write_walks_gfa": (u64, [vp, u64, vp, vp, u64, C.c_char_p, vp, C.c_char_p, P(vp)]),

@@ -1909,6 +1909,118 @@ def last_unitig_graph_times() -> dict:
     return {name: (float(v) if name.endswith("_ms") else int(v)) for name, v in zip(names, out)}
 
 
+@dataclass(frozen=True, eq=False)
+class Components:
+    """The connected components of a unitig graph over its links (mtg_unitig_components), in exact integers.
+    component_of[u]: the component of unitig u; components are numbered by their smallest unitig, ascending. Per component:
+    first_unitig, unitigs, kmers, abundance (the sum of the caller's per-unitig sums, or of the k-mers), links (the link entries whose
+    source orientation lies in it), dead_ends (orientations without a link), irregular (orientations whose number of links is not 1)."""
+
+    component_of: np.ndarray  # uint32[unitigs]
+    first_unitig: np.ndarray  # uint32[components]
+    unitigs: np.ndarray       # uint32[components]
+    kmers: np.ndarray         # uint64[components]
+    abundance: np.ndarray     # uint64[components]
+    links: np.ndarray         # uint64[components]
+    dead_ends: np.ndarray     # uint32[components]
+    irregular: np.ndarray     # uint32[components]
+
+    def __len__(self) -> int:
+        return len(self.first_unitig)
+
+    @property
+    def circular(self) -> np.ndarray:
+        """bool[components]: every orientation has exactly one link, so the component is a closed ring of unitigs."""
+        return self.irregular == 0
+
+    def describe(self) -> str:
+        if len(self) == 0:
+            return "0 components"
+        big = int(np.argmax(self.kmers))  # (ties: the first)
+        total = int(self.kmers.sum())
+        share = 100.0 * int(self.kmers[big]) / total if total else 0.0
+        return (f"{len(self)} components, largest {int(self.unitigs[big])} unitigs / {int(self.kmers[big])} k-mers ({share:.1f} % of the k-mers), "
+                f"{int((self.unitigs == 1).sum())} of one unitig, {int(self.circular.sum())} circular")
+
+
+def _unitig_kmers(store, k: int) -> np.ndarray:
+    """The number of k-mers of every record of a UnitigStore, a list of str or (uint8 array, offsets)."""
+    if isinstance(store, UnitigStore):
+        lengths = np.diff(store.arrays()[1])
+    elif isinstance(store, tuple):
+        lengths = np.diff(np.asarray(store[1], np.uint64))
+    else:
+        lengths = np.array([len(s) for s in store], np.uint64)
+    if len(lengths) and int(lengths.min()) < k:
+        raise ValueError(f"a unitig is shorter than k = {k}")
+    return (lengths.astype(np.uint64) - np.uint64(k - 1)).astype(np.uint64)
+
+
+def unitig_components(graph: Bigraph, store_or_kmers, k: Optional[int] = None, kc=None, device_id: int = 0) -> Components:
+    """The connected components of the unitig graph over its links, labelled and measured on the GPU (mtg_unitig_components,
+    DESIGN.md 27). store_or_kmers: with k, the unitigs of `graph` as a UnitigStore, a list of str or (uint8 array, offsets); without
+    k, the number of k-mers of every unitig as a plain array (graphs built from links, without sequences). kc: the abundance sum of
+    every unitig (Abundance.unitig_sums), or None for its number of k-mers. Only the original edges count, so dummy edges a tig
+    computation left in the graph change nothing."""
+    L = _lib.load()
+    U = graph.original_edge_count() // 2
+    kmers = np.ascontiguousarray(store_or_kmers, dtype=np.uint64) if k is None else _unitig_kmers(store_or_kmers, k)
+    if kmers.ndim != 1 or len(kmers) != U:
+        raise ValueError(f"{len(kmers)} k-mer counts for a graph of {U} unitigs")
+    if kc is not None:
+        kc = np.ascontiguousarray(kc, dtype=np.uint64)
+        if len(kc) != U:
+            raise ValueError(f"{len(kc)} abundance sums for {U} unitigs")
+    of, arrays = C.c_void_p(), _lib.MtgComponentArrays()
+    n = int(L.mtg_unitig_components(graph.handle, _ptr(kmers) if U else None, _ptr(kc) if kc is not None and U else None, device_id,
+                                    C.byref(of), C.byref(arrays)))
+
+    def take(p, ctype, dtype, count):
+        a = np.ctypeslib.as_array(C.cast(p, C.POINTER(ctype)), shape=(count,)).copy() if count else np.zeros(0, dtype)
+        L.mtg_free(p)
+        return a
+
+    component_of = take(of, C.c_uint32, np.uint32, U)
+    fields = {name: take(getattr(arrays, name), C.c_uint64 if name in ("kmers", "abundance", "links") else C.c_uint32,
+                         np.uint64 if name in ("kmers", "abundance", "links") else np.uint32, n) for name, _ in arrays._fields_}
+    return Components(component_of=component_of, **fields)
+
+
+def select_components(graph: Bigraph, store, k: int, min_kmers: int, kc=None, device_id: int = 0):
+    """The unitigs of the components that have at least min_kmers k-mers -> (store of the kept records in their order, keep (bool per
+    unitig), Components of the graph as it was). A UnitigStore gives a UnitigStore (mtg_unitigs_select); a list of str gives a list,
+    (uint8 array, offsets) gives such a pair. Links exist only inside a component, so the kept unitigs stay maximal, and the
+    components of the graph of the kept store (Bigraph.from_sequences) are the kept ones, renumbered in their order."""
+    if min_kmers < 1:
+        raise ValueError("min_kmers must be >= 1")
+    comps = unitig_components(graph, store, k, kc, device_id)
+    keep = (comps.kmers >= np.uint64(min_kmers))[comps.component_of] if len(comps) else np.zeros(0, bool)
+    if isinstance(store, UnitigStore):
+        out = C.c_void_p()
+        flags = np.ascontiguousarray(keep, dtype=np.uint8)
+        _lib.load().mtg_unitigs_select(store.handle, _ptr(flags) if len(flags) else None, C.byref(out))
+        kept = UnitigStore(out.value)
+    elif isinstance(store, tuple):
+        data, off = np.asarray(store[0], np.uint8), np.asarray(store[1], np.uint64)
+        lengths = np.diff(off)
+        new_off = np.zeros(int(keep.sum()) + 1, np.uint64)
+        new_off[1:] = np.cumsum(lengths[keep])
+        kept = (data[np.repeat(keep, lengths.astype(np.int64))], new_off)
+    else:
+        kept = [s for s, f in zip(store, keep.tolist()) if f]
+    return kept, keep, comps
+
+
+def last_unitig_components_times() -> dict:
+    """Of the last unitig_components / select_components on this thread: the uploads and the download by the host clock, the label
+    kernels and the statistics kernel by HIP events (ms); the components, the unitigs and the peak of the device arena's live bytes;
+    and the parts of label_ms: rep / degree, the unions, flatten + scan + numbers."""
+    out = (C.c_double * 10)()
+    _lib.load().mtg_last_unitig_components_times(out)
+    names = ("upload_ms", "label_ms", "stats_ms", "download_ms", "components", "unitigs", "peak_arena_bytes", "rep_ms", "union_ms", "flatten_ms")
+    return {name: (float(v) if name.endswith("_ms") else int(v)) for name, v in zip(names, out)}
+
+
 def last_spell_kernel() -> dict:
     L = _lib.load()
     return {"ms": float(L.mtg_last_spell_kernel_ms()), "bytes": int(L.mtg_last_spell_bytes())}

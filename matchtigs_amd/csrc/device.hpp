@@ -125,6 +125,23 @@ uint64_t device_unitig_links(const HostGraph &g, int device_id, uint64_t **link_
 // unitig. Returns the bytes; *out_buf is malloc'd (the caller frees)
 uint64_t device_write_unitig_graph_text(const HostGraph &g, const char *seqs, const uint64_t *seq_off, uint64_t n_unitigs, uint64_t k,
                                         const uint64_t *kc, bool gfa, int device_id, char **out_buf, UnitigGraphTimes *times);
+// unitig_components_device.hip: the connected components of the unitig graph over its links (the file's header and DESIGN.md 27
+// state the contract). The arrays of UnitigComponentArrays have one entry per component and are malloc'd (the caller frees).
+struct UnitigComponentArrays {
+    uint32_t *first_unitig = nullptr, *unitigs = nullptr;
+    uint64_t *kmers = nullptr, *abundance = nullptr, *links = nullptr;
+    uint32_t *dead_ends = nullptr, *irregular = nullptr;
+};
+// host wall clock of the uploads and the download, HIP-event time of the label kernels and of the statistics kernel, the components,
+// the unitigs, the arena's peak of live bytes; and the label kernels' parts: rep / degree, the unions, flatten + scan + numbers
+struct UnitigComponentsTimes {
+    double upload_ms = 0, label_ms = 0, stats_ms = 0, download_ms = 0, rep_ms = 0, union_ms = 0, flatten_ms = 0;
+    uint64_t components = 0, unitigs = 0, peak_arena_bytes = 0;
+};
+// kmers[U], kc[U] or null (then the abundance is the k-mers); aggregate: per-wave aggregation of the statistics' atomics (the
+// default; off only to measure it). *component_of_out[U] is malloc'd. Returns the components.
+uint64_t device_unitig_components(const HostGraph &g, const uint64_t *unitig_kmers, const uint64_t *unitig_kc, int device_id, bool aggregate,
+                                  uint32_t **component_of_out, UnitigComponentArrays *out, UnitigComponentsTimes *times);
 // fasta_in_device.hip: the plain unitig FASTA route -- graph of the (k-1)-mer overlaps of the unitig ends, joined on the GPU
 // (records: data[off[u], off[u + 1]), off[0] = 0). times: host wall clock of upload / download / graph build, HIP-event time of the
 // join kernels, and the bytes those kernels must move at the least.

@@ -8,6 +8,7 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cerrno>
 #include <chrono>
 #include <cstdarg>
@@ -615,6 +616,28 @@ void mtg_last_unitig_graph_times(double out[9]) {
     out[5] = (double)t.links; out[6] = (double)t.bytes; out[7] = (double)t.text_min_bytes; out[8] = (double)t.peak_arena_bytes;
 }
 
+// ---- the connected components of the unitig graph (unitig_components_device.hip) ----
+static thread_local UnitigComponentsTimes g_last_unitig_components;
+static std::atomic<int> g_unitig_components_aggregation{1};
+void mtg_set_unitig_components_aggregation(int on) { g_unitig_components_aggregation.store(on ? 1 : 0); }
+uint64_t mtg_unitig_components(const mtg_graph *g, const uint64_t *unitig_kmers, const uint64_t *unitig_kc, int device_id,
+                               uint32_t **component_of, mtg_component_arrays *components) {
+    if (!g || !component_of || !components) MTG_DIE("mtg_unitig_components: null argument");
+    UnitigComponentArrays a;
+    const uint64_t n = device_unitig_components(g->g, unitig_kmers, unitig_kc, device_id, g_unitig_components_aggregation.load() != 0, component_of,
+                                                &a, &g_last_unitig_components);
+    components->first_unitig = a.first_unitig; components->unitigs = a.unitigs; components->kmers = a.kmers;
+    components->abundance = a.abundance; components->links = a.links; components->dead_ends = a.dead_ends;
+    components->irregular = a.irregular;
+    return n;
+}
+void mtg_last_unitig_components_times(double out[10]) {
+    const UnitigComponentsTimes &t = g_last_unitig_components;
+    out[0] = t.upload_ms; out[1] = t.label_ms; out[2] = t.stats_ms; out[3] = t.download_ms;
+    out[4] = (double)t.components; out[5] = (double)t.unitigs; out[6] = (double)t.peak_arena_bytes;
+    out[7] = t.rep_ms; out[8] = t.union_ms; out[9] = t.flatten_ms;
+}
+
 uint64_t mtg_write_duplication_bitvector(const mtg_graph *g, uint64_t n_walks, const uint64_t *limits, const uint32_t *edges,
                                          char **text_out) {
     if (!g || !text_out || (n_walks && (!limits || !edges))) MTG_DIE("mtg_write_duplication_bitvector: null argument");
@@ -1088,6 +1111,24 @@ void mtg_last_fastq_times(double out[6]) {
 uint64_t mtg_unitigs_count(const mtg_unitigs *u) { return u->s->off.size() - 1; }
 const char *mtg_unitigs_data(const mtg_unitigs *u) { return u->s->data.data(); }
 const uint64_t *mtg_unitigs_offsets(const mtg_unitigs *u) { return u->s->off.data(); }
+void mtg_unitigs_select(const mtg_unitigs *u, const uint8_t *keep, mtg_unitigs **out) {
+    if (!u || !out || (mtg_unitigs_count(u) && !keep)) MTG_DIE("mtg_unitigs_select: null argument");
+    const UnitigStore &in = *u->s;
+    const uint64_t n = in.off.size() - 1;
+    uint64_t records = 0, bytes = 0;
+    for (uint64_t i = 0; i < n; i++)
+        if (keep[i]) { records++; bytes += in.off[i + 1] - in.off[i]; }
+    UnitigStore *st = new UnitigStore();
+    st->data.reserve(bytes);
+    st->off.reserve(records + 1);
+    st->off.push_back(0);
+    for (uint64_t i = 0; i < n; i++)
+        if (keep[i]) {
+            st->data.append(in.data, in.off[i], in.off[i + 1] - in.off[i]);
+            st->off.push_back(st->data.size());
+        }
+    *out = new mtg_unitigs{st};
+}
 void mtg_unitigs_free(mtg_unitigs *u) {
     if (!u) return;
     delete u->s;
