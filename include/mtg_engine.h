@@ -591,6 +591,33 @@ void mtg_kmer_index_free(mtg_kmer_index *ix);
 /* Of the last index build and the last query on this thread, in ms: {build: upload (host clock), pack, insert (with the table's fill
  * and the count); query: upload (host clock), pack, probe} -- HIP events around the kernels. */
 void mtg_last_kmer_query_times(double out[6]);
+/* The same question asked of a SPARSE index (tig_index_device.hip; there is no CPU path): instead of a table slot per
+ * window it keeps the 2-bit packed bases, the record offsets and one 8-byte word per minimizer anchor -- about 2 / (k - m + 2) of the
+ * windows --, so its size follows the cumulative length of the indexed sequences: tigs index smaller than unitigs. m is the
+ * minimizer length, 1 <= m <= min(k, 31); m = 0 means min(19, ceil(2 k / 3)). A directory bucket with more than bucket_limit anchors
+ * (low-complexity minimizers) is heavy: its windows go into a class table of 16 B per window instead; bucket_limit = 0 means 64, and
+ * 65536 is the most. Membership is decided by a compare of packed bases: exact, like the table index. The index holds device
+ * memory (info.device_bytes) until mtg_tig_index_free; mtg_release_device_memory leaves it intact. Limits: those of mtg_kmer_index. */
+typedef struct mtg_tig_index mtg_tig_index;
+typedef struct mtg_tig_index_info {
+    uint64_t k, m, records, characters, occurrences;    /* as mtg_kmer_index_info; m as used */
+    uint64_t anchors, buckets, bucket_limit;            /* anchors kept, directory buckets (a power of two), the limit as used */
+    uint64_t heavy_buckets, heavy_windows, table_slots; /* the skew path: buckets over the limit, windows in the table, its slots */
+    uint64_t device_bytes;                              /* everything the index keeps on the device */
+} mtg_tig_index_info;
+mtg_tig_index *mtg_tig_index_build(const char *seq, const uint64_t *off, uint64_t n, uint64_t k, uint64_t m, uint64_t bucket_limit,
+                                   int device_id);
+mtg_tig_index *mtg_tig_index_build_store(const mtg_unitigs *store, uint64_t k, uint64_t m, uint64_t bucket_limit, int device_id);
+void mtg_tig_index_get_info(const mtg_tig_index *ix, mtg_tig_index_info *out);
+/* mtg_kmer_index_query's contract, word for word: the same outputs for the same indexed set and query. */
+void mtg_tig_index_query(const mtg_tig_index *ix, const char *seq, const uint64_t *off, uint64_t n,
+                         uint64_t *kmers, uint64_t *valid, uint64_t *found, /* [n] each */
+                         uint64_t *present_bits, uint64_t *valid_bits);     /* nullable */
+void mtg_tig_index_free(mtg_tig_index *ix);
+/* Of the last tig index build and the last query of one on this thread, in ms: {build: upload (host clock), pack, anchors (mark,
+ * count, compact), directory (histogram, scan, scatter, sort), heavy table (count, insert); query: upload (host clock), pack, probe}
+ * -- HIP events around the kernels. */
+void mtg_last_tig_index_times(double out[8]);
 /* WHERE the k-mers of a query are in the indexed sequences. A LOCATING index is built by the two functions below;
  * beside the table it keeps the smallest position of every class, the packed bases (for every k) and the record offsets, all counted
  * in info.device_bytes. mtg_kmer_index_query answers on it exactly as on a plain index. */

@@ -14,6 +14,9 @@ contigs, `N` and all -- are in the input's k-mer set: per record the windows, th
 and with `--query-presence-out` one `1` / `0` / `-` character per window; the set is indexed once on the GPU.
 `--query-locate-out` adds where those k-mers are: one TSV row per maximal run of consecutive query k-mers that lie one after the
 other in an input record, on either strand, with both half-open base intervals.
+`--query-index minimizer` answers `--query-out` / `--query-presence-out` from a sparse minimizer index -- the packed bases plus one word
+per minimizer anchor (`--query-minimizer-length M`) instead of a table slot per k-mer --, and `--query-index-over greedytigs` /
+`eulertigs` indexes the tigs this run wrote instead of the input: the same answers from an index the size of the tigs.
 `--min-abundance N` (with `--seq-in`; not in the reference) keeps only the k-mers that at least N windows of the input show, on either
 strand -- sequencing reads, where a k-mer seen once is mostly an error -- before the unitigs are formed (DESIGN.md 19);
 `--kmer-spectrum-out` writes how many distinct k-mers have each abundance, `--unitig-abundance-out` the summed and mean abundance
@@ -122,6 +125,14 @@ def main(argv=None) -> int:
                     help="TSV (.gz => gzip) with one row per maximal collinear run of found k-mers: record, qstart, qend, strand, target "
                          "(0-based input record), tstart, tend, kmers; a repeated k-mer is placed at its first occurrence; "
                          "needs --query-fa and --query-out")
+    ap.add_argument("--query-index", choices=("table", "minimizer"),
+                    help="the index --query-fa asks: table (default; a slot per k-mer) or minimizer (the packed bases plus one word per "
+                         "minimizer anchor: a fraction of the memory, the same answers; serves --query-out and --query-presence-out)")
+    ap.add_argument("--query-minimizer-length", type=int, metavar="M",
+                    help="with --query-index minimizer: the minimizer length, 1 .. min(k, 31) (default min(19, ceil(2k/3)))")
+    ap.add_argument("--query-index-over", choices=("input", "greedytigs", "eulertigs"),
+                    help="the sequences --query-fa indexes: the input (default) or the tigs this run wrote, read back from "
+                         "--greedytigs-fa-out / --eulertigs-fa-out; they spell the same k-mer set")
     ap.add_argument("--min-abundance", type=int, metavar="N",
                     help="with --seq-in: compact only the k-mers seen in at least N windows of the input, both strands counted "
                          "(N >= 1; not in the reference)")
@@ -204,6 +215,26 @@ def main(argv=None) -> int:
         ap.error("--query-abundance-profile-out needs --query-abundance-out")
     if args.query_colors_out and not (args.seq_in and args.query_fa and args.query_out):
         ap.error("--query-colors-out needs --seq-in, --query-fa and --query-out")
+    for flag, value in (("--query-index", args.query_index), ("--query-minimizer-length", args.query_minimizer_length),
+                        ("--query-index-over", args.query_index_over)):
+        if value is not None and not args.query_fa:
+            ap.error(f"{flag} needs --query-fa")
+    if args.query_minimizer_length is not None:
+        if args.query_index != "minimizer":
+            ap.error("--query-minimizer-length needs --query-index minimizer")
+        if not 1 <= args.query_minimizer_length <= min(args.k, 31):
+            ap.error(f"--query-minimizer-length must be in 1..{min(args.k, 31)} (1 .. min(k, 31))")
+    for over, out in (("greedytigs", args.greedytigs_fa_out), ("eulertigs", args.eulertigs_fa_out)):
+        if args.query_index_over == over and not out:
+            ap.error(f"--query-index-over {over} needs --{over}-fa-out")
+    for flag, value in (("--query-locate-out", args.query_locate_out), ("--query-abundance-profile-out", args.query_abundance_profile_out),
+                        ("--query-abundance-out", args.query_abundance_out), ("--query-colors-out", args.query_colors_out)):
+        if value is None:
+            continue
+        if args.query_index == "minimizer":  # (a slot per class is what carries positions, weights and colours)
+            ap.error(f"{flag} cannot be combined with --query-index minimizer: it needs the table index")
+        if args.query_index_over not in (None, "input"):
+            ap.error(f"{flag} cannot be combined with --query-index-over {args.query_index_over}: it needs the index over the input")
     for flag, value in (("--min-abundance", args.min_abundance), ("--kmer-spectrum-out", args.kmer_spectrum_out),
                         ("--unitig-abundance-out", args.unitig_abundance_out), ("--unitig-kmer-abundance-out", args.unitig_kmer_abundance_out),
                         ("--color-matrix-out", args.color_matrix_out), ("--unitig-colors-out", args.unitig_colors_out),
@@ -690,13 +721,27 @@ def _query(api, args, store, kmer_counts=None, fastq=(), colors=None) -> None:
         return gzip.open(path, "w" + mode, compresslevel=args.compression_level) if path.endswith(".gz") else open(path, "w" + mode)
 
     with contextlib.ExitStack() as stack:
-        if colors is not None:  # (the masks, and the counts too when abundances are asked for)
+        sparse = args.query_index == "minimizer"
+        over = args.query_index_over or "input"
+        if sparse or over != "input":  # (the same k-mer set, asked of another index or spelled by the tigs)
+            indexed = store if over == "input" else api.read_sequences(args.greedytigs_fa_out if over == "greedytigs" else args.eulertigs_fa_out)
+            if sparse:
+                index = stack.enter_context(api.TigIndex(indexed, args.k, args.query_minimizer_length, args.device))
+            else:
+                index = stack.enter_context(api.KmerIndex(indexed, args.k, args.device))
+        elif colors is not None:  # (the masks, and the counts too when abundances are asked for)
             index = stack.enter_context(api.KmerIndex(store, args.k, args.device, locate=bool(args.query_locate_out), weights=kmer_counts,
                                                       colors=colors.kmer_colors, n_colors=colors.n_colors))
         elif kmer_counts is None:
             index = stack.enter_context(api.KmerIndex(store, args.k, args.device, locate=bool(args.query_locate_out)))
         else:
             index = stack.enter_context(api.KmerIndex(store, args.k, args.device, locate=bool(args.query_locate_out), weights=kmer_counts))
+        if args.query_index is not None or args.query_index_over is not None:
+            i = index.info
+            line = i.describe() if sparse else (
+                f"table index: {i.characters} bases in {i.records} records, 0 anchors, 0 heavy buckets with 0 windows, {i.device_bytes} "
+                f"device bytes, {i.device_bytes / i.occurrences if i.occurrences else 0.0:.2f} bytes per k-mer window")
+            print(f"Indexing the {'input' if over == 'input' else over}: {line}", file=sys.stderr)
         tsv = stack.enter_context(writer(args.query_out, "t"))
         presence = stack.enter_context(writer(args.query_presence_out, "b")) if args.query_presence_out else None
         located = stack.enter_context(writer(args.query_locate_out, "t")) if args.query_locate_out else None

@@ -158,6 +158,16 @@ class MtgKmerIndexInfo(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class MtgTigIndexInfo(C.Structure):
+    """mtg_tig_index_info (include/mtg_engine.h)."""
+
+    _fields_ = [(n, C.c_uint64) for n in ("k", "m", "records", "characters", "occurrences", "anchors", "buckets", "bucket_limit",
+                                          "heavy_buckets", "heavy_windows", "table_slots", "device_bytes")]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class MtgComponentArrays(C.Structure):
     """mtg_component_arrays (include/mtg_engine.h): one array per field, one entry per component; each goes back through mtg_free."""
 
@@ -320,6 +330,12 @@ def load():
         "mtg_kmer_index_query": (None, [vp, vp, vp, u64, vp, vp, vp, vp, vp]),
         "mtg_kmer_index_free": (None, [vp]),
         "mtg_last_kmer_query_times": (None, [P(C.c_double)]),
+        "mtg_tig_index_build": (vp, [vp, vp, u64, u64, u64, u64, C.c_int]),
+        "mtg_tig_index_build_store": (vp, [vp, u64, u64, u64, C.c_int]),
+        "mtg_tig_index_get_info": (None, [vp, P(MtgTigIndexInfo)]),
+        "mtg_tig_index_query": (None, [vp, vp, vp, u64, vp, vp, vp, vp, vp]),
+        "mtg_tig_index_free": (None, [vp]),
+        "mtg_last_tig_index_times": (None, [P(C.c_double)]),
         "mtg_kmer_index_build_locating": (vp, [vp, vp, u64, u64, C.c_int]),
         "mtg_kmer_index_build_locating_store": (vp, [vp, u64, C.c_int]),
         "mtg_kmer_index_is_locating": (C.c_int, [vp]),

@@ -1720,6 +1720,102 @@ class KmerIndex:
         return KmerColorResult(self.info.k, off, kmers, valid, found, per_color, pw)
 
 
+def default_minimizer_length(k: int) -> int:
+    """The minimizer length a TigIndex takes when none is given: min(19, ceil(2 k / 3)) -- 19 at k = 31."""
+    return min(19, (2 * k + 2) // 3)
+
+
+@dataclass(frozen=True)
+class TigIndexInfo:
+    """mtg_tig_index_info (include/mtg_engine.h)."""
+
+    k: int
+    m: int
+    records: int
+    characters: int
+    occurrences: int
+    anchors: int
+    buckets: int
+    bucket_limit: int
+    heavy_buckets: int
+    heavy_windows: int
+    table_slots: int
+    device_bytes: int
+
+    @property
+    def bytes_per_kmer(self) -> float:
+        """Device bytes per k-mer window of the indexed sequences; 0.0 for an index without windows."""
+        return self.device_bytes / self.occurrences if self.occurrences else 0.0
+
+    def describe(self) -> str:
+        return (f"minimizer index (m = {self.m}): {self.characters} bases in {self.records} records, {self.anchors} anchors in "
+                f"{self.buckets} buckets, {self.heavy_buckets} heavy buckets with {self.heavy_windows} windows, {self.device_bytes} device "
+                f"bytes, {self.bytes_per_kmer:.2f} bytes per k-mer window")
+
+
+class TigIndex:
+    """The canonical k-mers of a sequence set as a sparse index on GPU `device_id` (mtg_tig_index_*): the 2-bit packed
+    bases plus one word per minimizer anchor instead of KmerIndex's table slot per window, so its size follows the cumulative length
+    of the sequences -- tigs index smaller than unitigs. query() answers exactly as KmerIndex.query does. seqs_or_store: UnitigStore,
+    list of str, or (uint8 array, offsets); ACGT of either case only. m: the minimizer length, 1 .. min(k, 31) (None:
+    default_minimizer_length(k)). bucket_limit: a directory bucket with more anchors sends its windows to a class table (None: 64).
+    The index holds device memory until close() (or its collection); release_device_memory leaves it intact."""
+
+    def __init__(self, seqs_or_store, k: int, m: Optional[int] = None, device_id: int = 0, bucket_limit: Optional[int] = None):
+        self._h = None
+        if m is not None and not 1 <= m <= min(k, 31):
+            raise ValueError(f"m must be in 1..min(k, 31), not {m!r}")
+        if bucket_limit is not None and not 1 <= bucket_limit <= 65536:
+            raise ValueError(f"bucket_limit must be in 1..65536, not {bucket_limit!r}")
+        self._L = _lib.load()
+        if isinstance(seqs_or_store, UnitigStore):
+            self._h = self._L.mtg_tig_index_build_store(seqs_or_store.handle, k, m or 0, bucket_limit or 0, device_id)
+        else:
+            d, o, n, keep = _sequence_arrays(seqs_or_store)
+            self._h = self._L.mtg_tig_index_build(d, o, n, k, m or 0, bucket_limit or 0, device_id)
+            del keep
+        out = _lib.MtgTigIndexInfo()
+        self._L.mtg_tig_index_get_info(self._h, C.byref(out))
+        self.info = TigIndexInfo(**out.as_dict())
+
+    def close(self) -> None:
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            self._L.mtg_tig_index_free(h)
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def query(self, seqs_or_store, bits: bool = False) -> KmerQueryResult:
+        """KmerIndex.query's answer: per record of seqs_or_store (ANY bytes) windows, valid windows, windows found in the index;
+        bits: also the two bit arrays that presence() reads."""
+        if not self._h:
+            raise ValueError("the index is closed")
+        d, o, n, keep = _sequence_arrays(seqs_or_store)
+        off = np.ctypeslib.as_array(C.cast(o, C.POINTER(C.c_uint64)), shape=(n + 1,)).copy()
+        kmers, valid, found = (np.zeros(n, np.uint64) for _ in range(3))
+        words = (int(off[n]) + 63) // 64
+        vb, pb = (np.zeros(words, np.uint64), np.zeros(words, np.uint64)) if bits else (None, None)
+        self._L.mtg_tig_index_query(self._h, d, o, n, _ptr(kmers), _ptr(valid), _ptr(found), _ptr(pb) if bits else None,
+                                    _ptr(vb) if bits else None)
+        del keep
+        return KmerQueryResult(self.info.k, off, kmers, valid, found, vb, pb)
+
+
+def last_tig_index_times() -> dict:
+    """Phases of the last TigIndex build and the last query of one on this thread, in ms (HIP events around the kernels; uploads by
+    the host clock)."""
+    out = (C.c_double * 8)()
+    _lib.load().mtg_last_tig_index_times(out)
+    return dict(zip(("build_upload_ms", "build_pack_ms", "build_anchors_ms", "build_directory_ms", "build_heavy_ms", "query_upload_ms",
+                     "query_pack_ms", "query_probe_ms"), list(out)))
+
+
 def last_kmer_color_times() -> dict:
     """In ms: stats = the colour statistics kernel of the last compact_unitigs_colored on this thread (HIP events); the phases of the
     last KmerIndex.color_hits (HIP events around the kernels; upload and download by the host clock)."""

@@ -217,6 +217,21 @@ struct KmerColorTimes {
 };
 void device_kmer_index_colors(const KmerIndex *ix, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid,
                               uint64_t *found, uint32_t *per_color, uint64_t *per_window, KmerColorTimes *times);
+// tig_index_device.hip: the sparse minimizer index over a sequence set (the file's header and DESIGN.md 28 state the contract): the
+// packed bases plus one word per anchor, asked what device_kmer_index_query is asked. m = 0: tig_index_default_m(k); bucket_limit
+// = 0: 64. times: host wall clock of the uploads, HIP-event time of the kernels; a build sets the first five, a query the last three.
+struct TigIndexTimes {
+    double build_upload_ms = 0, build_pack_ms = 0, build_anchors_ms = 0, build_directory_ms = 0, build_heavy_ms = 0, query_upload_ms = 0,
+           query_pack_ms = 0, query_probe_ms = 0;
+};
+struct TigIndex;
+uint64_t tig_index_default_m(uint64_t k);  // min(19, ceil(2 k / 3))
+TigIndex *device_tig_index_build(const char *seq, const uint64_t *off, uint64_t n, uint64_t k, uint64_t m, uint64_t bucket_limit, int device_id,
+                                 TigIndexTimes *times);
+void device_tig_index_info(const TigIndex *ix, mtg_tig_index_info *out);
+void device_tig_index_query(const TigIndex *ix, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid,
+                            uint64_t *found, uint64_t *present_bits, uint64_t *valid_bits, TigIndexTimes *times);
+void device_tig_index_free(TigIndex *ix);
 // compact_device.hip: the maximal unitigs of the k-mer set of arbitrary sequences (the file's header and DESIGN.md 16 state the
 // contract), as an ordinary sequence store. times: host wall clock of upload, download and the whole call, HIP-event time of the
 // kernel phases, the pointer-jumping rounds, the bytes the kernels must move at the least, the arena's peak of live bytes.

@@ -835,6 +835,36 @@ void mtg_last_kmer_query_times(double out[6]) {
     out[0] = t.build_upload_ms; out[1] = t.build_pack_ms; out[2] = t.build_insert_ms;
     out[3] = t.query_upload_ms; out[4] = t.query_pack_ms; out[5] = t.query_probe_ms;
 }
+// ---- the sparse minimizer index (tig_index_device.hip) ----
+struct mtg_tig_index { TigIndex *ix; };
+static thread_local TigIndexTimes g_last_tig_index;
+mtg_tig_index *mtg_tig_index_build(const char *seq, const uint64_t *off, uint64_t n, uint64_t k, uint64_t m, uint64_t bucket_limit, int device_id) {
+    return new mtg_tig_index{device_tig_index_build(seq, off, n, k, m, bucket_limit, device_id, &g_last_tig_index)};
+}
+mtg_tig_index *mtg_tig_index_build_store(const mtg_unitigs *store, uint64_t k, uint64_t m, uint64_t bucket_limit, int device_id) {
+    if (!store) MTG_DIE("mtg_tig_index_build_store: null argument");
+    const UnitigStore &s = *store->s;
+    return mtg_tig_index_build(s.data.data(), s.off.data(), s.off.size() - 1, k, m, bucket_limit, device_id);
+}
+void mtg_tig_index_get_info(const mtg_tig_index *ix, mtg_tig_index_info *out) {
+    if (!ix || !out) MTG_DIE("mtg_tig_index_get_info: null argument");
+    device_tig_index_info(ix->ix, out);
+}
+void mtg_tig_index_query(const mtg_tig_index *ix, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid,
+                         uint64_t *found, uint64_t *present_bits, uint64_t *valid_bits) {
+    if (!ix) MTG_DIE("mtg_tig_index_query: null argument");
+    device_tig_index_query(ix->ix, seq, off, n, kmers, valid, found, present_bits, valid_bits, &g_last_tig_index);
+}
+void mtg_tig_index_free(mtg_tig_index *ix) {
+    if (!ix) return;
+    device_tig_index_free(ix->ix);
+    delete ix;
+}
+void mtg_last_tig_index_times(double out[8]) {
+    const TigIndexTimes &t = g_last_tig_index;
+    out[0] = t.build_upload_ms; out[1] = t.build_pack_ms; out[2] = t.build_anchors_ms; out[3] = t.build_directory_ms; out[4] = t.build_heavy_ms;
+    out[5] = t.query_upload_ms; out[6] = t.query_pack_ms; out[7] = t.query_probe_ms;
+}
 void mtg_read_sequences_named(const char *path, mtg_unitigs **seqs_out, mtg_unitigs **names_out) {
     if (!path || !seqs_out || !names_out) MTG_DIE("mtg_read_sequences_named: null argument");
     UnitigStore *names = nullptr;

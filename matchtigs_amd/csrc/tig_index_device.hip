@@ -1,0 +1,520 @@
+// tig_index_device.hip -- a k-mer dictionary the size of the tigs: the sparse minimizer index (mtg_tig_index_*)
+//
+// The contract is the k-mer index's (kmer_query_device.hip): the INDEX is a sequence set, its k-mers the windows of length k inside
+// one record, taken by their class {x, rc(x)}; a QUERY is n records of arbitrary bytes and gets kmers / valid / found per record and
+// the two bit arrays, word for word what mtg_kmer_index_query gives. What differs is what the index keeps: not a table slot per
+// window but the 2-bit packed bases themselves plus one 8-byte word per ANCHOR, about 2 / (k - m + 2) of the windows.
+//
+// Definitions. 1 <= m <= min(k, 31), w = k - m + 1. The m-mer at a text position has the class key hash = kw::mix64(canonical 2-bit
+// code), a bijection of the class. The MINIMIZER of a window is the class with the smallest hash among its w m-mers; its ANCHOR is
+// the global position of the LEFTMOST m-mer of that class in the window, in the forward text. The index keeps the packed bases, the
+// record offsets, entries[] = kw::tagged_pos(hash, anchor) of every position that is the anchor of at least one window, grouped by
+// the top b bits of the hash and ascending by position inside a group, and dir[2^b + 1], where each group starts (2^b = the least
+// power of two at or above the anchors, 8 at the least).
+//
+// Heavy buckets. A bucket of more than bucket_limit anchors (low-complexity minimizers: poly-A marks every position) is HEAVY: bit
+// 63 of its dir word. Its anchors are dropped, and every window whose minimizer hashes into it goes into an ordinary class table
+// (kw::find_slot, 2 slots per such window, the slot forms of kmer_query_device.hip) instead. Which path a k-mer takes is a function
+// of its minimizer's bucket, the same for x and rc(x), in the build and in the query.
+//
+// Build:
+//   pack       SeqStore
+//   anchors    anchor_mark_kernel: a thread owns kw::RUN window starts, rolls the m-mer codes (MinimizerWalk: the minimum is kept
+//              while its leftmost occurrence stays in the window, else the w candidates are rescanned) and ORs the anchor's bit
+//              into a bitmap of one bit per base -- a union of bits: order independent, no duplicates at run or record borders;
+//              popcount per word, hu::scan_u32, anchor_compact_kernel: the positions, ascending
+//   directory  bucket_hist_kernel, bucket_light_kernel (heavy buckets count 0), hu::scan_u32, bucket_scatter_kernel (the order inside
+//              a bucket is that of the atomics), bucket_sort_kernel (ascending by position: the bytes no longer depend on that order;
+//              then the heavy bit)
+//   heavy      heavy_kernel<.., false> counts the windows of the heavy buckets, heavy_kernel<.., true> inserts them
+// Query: MaskedSeqStore, then tig_query_kernel: query_kernel's walk (64 window starts per thread, one plain store per bit-array word,
+// clear_from, one atomicAdd per (thread, record) and counter) with the lookup of tig_contains.
+//
+// Exactness. A hit is declared only after kw::same_class has compared the query's k bases with k index bases that lie inside ONE
+// record, or after the heavy table's exact `same`: never a false positive, and a tag or hash collision costs a compare. No false
+// negative: let the class of the query window x be the index window y at c. Both have the same set of m-mer classes, hence the same
+// minimizer v and the same bucket; if that is heavy both sides use the table. Else, if y == x, the leftmost m-mer of v in y is at
+// the offset j1 of the leftmost one in x, so the build marked p = c + j1 and the candidate p - j1 is c. If y == rc(x), offset j of y
+// is offset w - 1 - j of x, the leftmost in y is the RIGHTMOST in x (offset jL), the build marked p = c + (w - 1 - jL), and the second
+// candidate is c. Light anchors are all kept, so p is in the bucket.
+//
+// Limits: those of the k-mer index (fewer than 2^40 - 1 bases, k < 2^32), m <= 31, bucket_limit <= 65536 (a bucket is sorted by one
+// thread). Device memory: 0.25 B per base, 8 B per record, 8 B per anchor, 8 B per bucket (at most 16 B per anchor), 16 B per heavy
+// window. There is no host path.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "device.hpp"
+#include "hip_util.hpp"
+#include "kmer_window_device.hpp"
+#include "pack_device.hpp"
+
+namespace mtg {
+
+namespace {
+
+using kw::EMPTY_SLOT;
+using kw::POS_LIMIT;
+using kw::RUN;
+using kw::Window;
+
+constexpr unsigned long long HEAVY = 1ull << 63;  // in a dir word
+constexpr uint64_t TAG_MASK = 0x3FFFFFull;        // kw::tagged_pos keeps these bits of a hash
+
+// what the m-mer walk needs beside the packed bases
+struct MinArgs {
+    uint64_t m, w;  // w = k - m + 1 m-mers per window
+    uint64_t top;   // 2 (m - 1), where a base enters the reverse-complement code
+    uint64_t mask;  // the 2 m low bits
+};
+
+// the minimizer of a window: the smallest m-mer hash, the global positions of the leftmost and the rightmost m-mer of that class
+struct Minimizer {
+    uint64_t hash, first, last;
+};
+
+// The minimizers of windows taken in ascending order. at(q) rolls one m-mer in if q follows the window before and the leftmost
+// occurrence of the minimum is still inside, else it reads the window's k bases again. Either way the result is a function of the
+// window alone: min, leftmost and rightmost are kept exactly (a new m-mer below the minimum replaces all three, one equal to it moves
+// `last`, and `last` >= `first` never leaves before `first` does).
+struct MinimizerWalk {
+    const uint32_t *packed;
+    const MinArgs &a;
+    kw::BaseReader rd;  // at the base behind the last m-mer read
+    uint64_t fwd = 0, rc = 0, next_q = ~0ull;
+    Minimizer cur{0, 0, 0};
+
+    __device__ __forceinline__ MinimizerWalk(const uint32_t *p, const MinArgs &args) : packed(p), a(args), rd(p, 0) {}
+    __device__ __forceinline__ uint64_t step() {  // one base in; the hash of the m-mer that ends with it
+        const uint64_t c = rd.next();
+        fwd = ((fwd << 2) | c) & a.mask;
+        rc = (rc >> 2) | ((3 - c) << a.top);
+        return kw::mix64(fwd < rc ? fwd : rc);
+    }
+    __device__ __forceinline__ void take(uint64_t h, uint64_t pos) {
+        if (h < cur.hash) cur = Minimizer{h, pos, pos};
+        else if (h == cur.hash) cur.last = pos;
+    }
+    __device__ __forceinline__ const Minimizer &at(uint64_t q) {
+        if (q == next_q && cur.first >= q) {
+            take(step(), q + a.w - 1);
+        } else {
+            rd = kw::BaseReader(packed, q);
+            fwd = rc = 0;
+            for (uint64_t i = 0; i + 1 < a.m; i++) (void)step();
+            cur = Minimizer{step(), q, q};
+            for (uint64_t j = 1; j < a.w; j++) take(step(), q + j);
+        }
+        next_q = q + 1;
+        return cur;
+    }
+};
+
+struct TigArgs : kw::WindowArgs {  // packed / off: the sequences that are walked (build: the index's, query: the query's)
+    MinArgs mn;
+    const uint32_t *index_packed;
+    const unsigned long long *index_off;  // [index_rec + 1]
+    uint64_t index_rec;
+    const unsigned long long *dir;      // [2^b + 1]; bit 63: heavy
+    const unsigned long long *entries;  // [anchors]
+    uint32_t shift;                     // 64 - b: a hash's bucket is hash >> shift
+    unsigned long long *table;          // [slots] the windows of the heavy buckets; slots == 0: there are none
+    uint64_t slots;
+};
+
+// ---- build: anchors ----
+// bitmap: one bit per base, zeroed; bit p & 31 of word p >> 5 is set iff p is the anchor of a window
+template <bool WIDE>
+__global__ __launch_bounds__(hu::EB) void anchor_mark_kernel(TigArgs a, uint64_t n_bases, uint64_t n_rec, uint32_t *bitmap) {
+    const uint64_t p0 = hu::gid() * RUN;
+    if (p0 >= n_bases) return;
+    MinimizerWalk walk(a.packed, a.mn);
+    uint64_t marked = ~0ull;  // (consecutive windows mostly share their anchor)
+    kw::for_each_window<WIDE>(a, p0, p0 + RUN < n_bases ? p0 + RUN : n_bases, 0, n_rec, [&](uint64_t q, uint64_t, const Window &) {
+        const uint64_t p = walk.at(q).first;
+        if (p != marked) atomicOr(&bitmap[p >> 5], 1u << (p & 31));
+        marked = p;
+    });
+}
+__global__ __launch_bounds__(hu::EB) void anchor_count_kernel(const uint32_t *bitmap, uint64_t n_words, uint32_t *count) {
+    const uint64_t w = hu::gid();
+    if (w < n_words) count[w] = (uint32_t)__popc(bitmap[w]);
+}
+// pos[rank[w] ..] = the set bits of word w: all anchors, ascending
+__global__ __launch_bounds__(hu::EB) void anchor_compact_kernel(const uint32_t *bitmap, uint64_t n_words, const unsigned long long *rank,
+                                                                uint64_t n_anchors, unsigned long long *pos) {
+    const uint64_t w = hu::gid();
+    if (w >= n_words) return;
+    uint64_t i = rank[w];
+    for (uint32_t v = bitmap[w]; v && i < n_anchors; v &= v - 1) pos[i++] = w * 32 + (uint64_t)__builtin_ctz(v);
+}
+
+// ---- build: directory ----
+__global__ __launch_bounds__(hu::EB) void bucket_hist_kernel(const uint32_t *packed, const unsigned long long *pos, uint64_t n_anchors, uint64_t m,
+                                                             uint32_t shift, uint32_t *hist) {
+    const uint64_t i = hu::gid();
+    if (i < n_anchors) atomicAdd(&hist[kw::class_key(packed, pos[i], m).hash >> shift], 1u);
+}
+// light[b] = the anchors bucket b keeps: none if it is heavy; *n_heavy += heavy buckets
+__global__ __launch_bounds__(hu::EB) void bucket_light_kernel(const uint32_t *hist, uint64_t buckets, uint64_t limit, uint32_t *light,
+                                                              unsigned long long *n_heavy) {
+    const uint64_t b = hu::gid();
+    if (b >= buckets) return;
+    const bool heavy = hist[b] > limit;
+    light[b] = heavy ? 0u : hist[b];
+    if (heavy) atomicAdd(n_heavy, 1ull);
+}
+// cursor: [buckets], zeroed; afterwards the anchors each bucket keeps
+__global__ __launch_bounds__(hu::EB) void bucket_scatter_kernel(const uint32_t *packed, const unsigned long long *pos, uint64_t n_anchors, uint64_t m,
+                                                                uint32_t shift, const uint32_t *hist, uint64_t limit, const unsigned long long *dir,
+                                                                uint32_t *cursor, uint64_t n_entries, unsigned long long *entries) {
+    const uint64_t i = hu::gid();
+    if (i >= n_anchors) return;
+    const uint64_t p = pos[i], h = kw::class_key(packed, p, m).hash, b = h >> shift;
+    if (hist[b] > limit) return;
+    const uint64_t at = dir[b] + atomicAdd(&cursor[b], 1u);
+    if (at < n_entries) entries[at] = kw::tagged_pos(h, p);  // (the scan counted exactly these: always)
+}
+// one thread per bucket: its entries ascending by position (at most `limit` of them, mostly one or two), then the heavy bit
+__global__ __launch_bounds__(hu::EB) void bucket_sort_kernel(const uint32_t *hist, const uint32_t *kept, uint64_t buckets, uint64_t limit,
+                                                             unsigned long long *dir, unsigned long long *entries) {
+    const uint64_t b = hu::gid();
+    if (b >= buckets) return;
+    unsigned long long *e = entries + dir[b];
+    const uint32_t n = kept[b];
+    for (uint32_t i = 1; i < n; i++) {
+        const unsigned long long x = e[i];
+        uint32_t j = i;
+        for (; j > 0 && (e[j - 1] & POS_LIMIT) > (x & POS_LIMIT); j--) e[j] = e[j - 1];
+        e[j] = x;
+    }
+    if (hist[b] > limit) dir[b] |= HEAVY;
+}
+
+// ---- the heavy table ----
+// the slot of w's class; w is a window of a.packed (CLAIM: taken with w.ident if the class has none)
+template <bool WIDE, bool CLAIM>
+__device__ __forceinline__ kw::Found heavy_find(const TigArgs &a, const Window &w) {
+    return kw::find_slot<CLAIM>(a.table, a.slots, w.hash, w.ident, [&](unsigned long long cur) {
+        if (!WIDE) return cur == w.ident;
+        if ((cur >> 40) != (w.ident >> 40)) return false;
+        if (CLAIM) return kw::same_class(a.packed, w.ident & POS_LIMIT, cur & POS_LIMIT, a.k);
+        return kw::same_class(a.packed, w.ident & POS_LIMIT, a.index_packed, cur & POS_LIMIT, a.k);
+    });
+}
+// the windows whose minimizer's bucket is heavy: counted into *count, or (INSERT) put into the table
+template <bool WIDE, bool INSERT>
+__global__ __launch_bounds__(hu::EB) void heavy_kernel(TigArgs a, uint64_t n_bases, uint64_t n_rec, unsigned long long *count, unsigned int *err) {
+    const uint64_t p0 = hu::gid() * RUN;
+    if (p0 >= n_bases) return;
+    MinimizerWalk walk(a.packed, a.mn);
+    uint32_t n = 0;
+    kw::for_each_window<WIDE>(a, p0, p0 + RUN < n_bases ? p0 + RUN : n_bases, 0, n_rec, [&](uint64_t q, uint64_t, const Window &w) {
+        if (!(a.dir[walk.at(q).hash >> a.shift] & HEAVY)) return;
+        if (!INSERT) n++;
+        else if (heavy_find<WIDE, true>(a, w).slot == a.slots) atomicOr(err, 1u);  // (2 slots per window: never full)
+    });
+    if (!INSERT && n) atomicAdd(count, (unsigned long long)n);
+}
+
+// ---- query ----
+// the last record that starts at or before x (n_rec >= 1)
+__device__ __forceinline__ uint64_t record_of(const unsigned long long *off, uint64_t n_rec, uint64_t x) {
+    uint64_t lo = 0, hi = n_rec;
+    while (hi - lo > 1) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (off[mid] <= x) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// The window at q of a.packed (w: what it is to a table, mz: its minimizer) is a k-mer of the index: the header's lookup rule.
+// [lo, hi): the index record of the last anchor looked at (empty before the first). Neighbouring windows mostly hit the same record,
+// and the bounds of the record that holds p are a function of p, so keeping them only saves the binary search.
+template <bool WIDE>
+__device__ __forceinline__ bool tig_contains(const TigArgs &a, uint64_t q, const Window &w, const Minimizer &mz, uint64_t &lo, uint64_t &hi) {
+    const uint64_t b = mz.hash >> a.shift;
+    const unsigned long long d = a.dir[b];
+    if (d & HEAVY) return heavy_find<WIDE, false>(a, w).slot != a.slots;
+    const uint64_t end = a.dir[b + 1] & ~HEAVY, tag = mz.hash & TAG_MASK;
+    const uint64_t j_fwd = mz.first - q;                  // x lies forward in the text: the anchor is its leftmost occurrence
+    const uint64_t j_rev = a.mn.w - 1 - (mz.last - q);    // rc(x) does: the anchor is x's rightmost one, seen from the other end
+    for (uint64_t i = d; i < end; i++) {
+        const unsigned long long e = a.entries[i];
+        if ((e >> 40) != tag) continue;
+        const uint64_t p = e & POS_LIMIT;
+        if (p < lo || p >= hi) {  // a candidate counts only inside the record of p
+            const uint64_t r = record_of(a.index_off, a.index_rec, p);
+            lo = a.index_off[r];
+            hi = a.index_off[r + 1];
+        }
+        if (p >= lo + j_fwd && p - j_fwd + a.k <= hi && kw::same_class(a.packed, q, a.index_packed, p - j_fwd, a.k)) return true;
+        if (j_rev != j_fwd && p >= lo + j_rev && p - j_rev + a.k <= hi && kw::same_class(a.packed, q, a.index_packed, p - j_rev, a.k)) return true;
+    }
+    return false;
+}
+
+// one past the last base of [lo, hi) whose bit is set in `bad`; lo if there is none
+__device__ __forceinline__ uint64_t past_last_bad(const unsigned long long *bad, uint64_t lo, uint64_t hi) {
+    if (hi <= lo) return lo;
+    uint64_t w = (hi - 1) >> 6;
+    const uint64_t w_lo = lo >> 6;
+    unsigned long long m = bad[w] & (~0ull >> (63 - ((hi - 1) & 63)));
+    for (;;) {
+        if (w == w_lo) m &= ~0ull << (lo & 63);
+        if (m) return (w << 6) + 64 - (uint64_t)__clzll((long long)m);
+        if (w == w_lo) return lo;
+        m = bad[--w];
+    }
+}
+
+// query_kernel's contract and layout (kmer_query_device.hip). counts: [2 n_rec], valid then found; valid_bits / present_bits:
+// [(n_bases + 63) / 64] or null. The minimizer walk is asked for valid windows only: after an invalid stretch it reads afresh.
+template <bool WIDE>
+__global__ __launch_bounds__(hu::EB) void tig_query_kernel(TigArgs a, const unsigned long long *bad, uint64_t n_bases, uint64_t n_rec,
+                                                           unsigned long long *counts, unsigned long long *valid_bits,
+                                                           unsigned long long *present_bits) {
+    const uint64_t gid = hu::gid(), p0 = gid * RUN;
+    if (p0 >= n_bases) return;
+    unsigned long long vbits = 0, pbits = 0;
+    uint64_t rec = ~0ull, next_q = ~0ull, clear_from = 0;
+    uint64_t idx_lo = 1, idx_hi = 0;    // tig_contains' index record: none yet
+    uint32_t n_valid = 0, n_found = 0;  // (of the current record; at most RUN)
+    MinimizerWalk walk(a.packed, a.mn);
+    auto flush = [&]() {
+        if (n_valid) atomicAdd(&counts[rec], (unsigned long long)n_valid);
+        if (n_found) atomicAdd(&counts[n_rec + rec], (unsigned long long)n_found);
+        n_valid = n_found = 0;
+    };
+    kw::for_each_window<WIDE>(a, p0, p0 + RUN < n_bases ? p0 + RUN : n_bases, 0, n_rec, [&](uint64_t q, uint64_t r, const Window &w) {
+        const uint64_t last = q + a.k - 1;  // the window's last base
+        if (r != rec) {
+            flush();
+            rec = r;
+        }
+        if (q != next_q) clear_from = past_last_bad(bad, q, last);  // the walk jumped: what it knew lies behind q
+        next_q = q + 1;
+        if ((bad[last >> 6] >> (last & 63)) & 1) clear_from = last + 1;
+        if (clear_from > q) return;  // a bad base inside the window
+        const unsigned long long bit = 1ull << (q - p0);
+        n_valid++;
+        vbits |= bit;
+        if (tig_contains<WIDE>(a, q, w, walk.at(q), idx_lo, idx_hi)) {
+            n_found++;
+            pbits |= bit;
+        }
+    });
+    flush();
+    if (valid_bits) valid_bits[gid] = vbits;
+    if (present_bits) present_bits[gid] = pbits;
+}
+
+// offsets of one set: start at 0, do not decrease; returns its windows
+uint64_t check_offsets(const char *fn, const char *data, const uint64_t *off, uint64_t n, uint64_t k) {
+    if (!off || (n && off[n] && !data)) MTG_DIE("%s: null argument", fn);
+    if (off[0] != 0) MTG_DIE("%s: offsets must start at 0", fn);
+    uint64_t occ = 0;
+    for (uint64_t u = 0; u < n; u++) {
+        if (off[u + 1] < off[u]) MTG_DIE("%s: offsets decrease at record %llu", fn, (unsigned long long)u);
+        const uint64_t len = off[u + 1] - off[u];
+        if (len >= k) occ += len - k + 1;
+    }
+    return occ;
+}
+
+}  // namespace
+
+struct TigIndex {
+    mtg_tig_index_info info{};
+    int device_id = 0;
+    uint32_t shift = 61;
+    hu::DeviceArray<uint32_t> packed;
+    hu::DeviceArray<unsigned long long> off;      // [info.records + 1]
+    hu::DeviceArray<unsigned long long> dir;      // [info.buckets + 1]
+    hu::DeviceArray<unsigned long long> entries;  // [info.anchors]
+    hu::DeviceArray<unsigned long long> table;    // [info.table_slots]
+};
+
+uint64_t tig_index_default_m(uint64_t k) { return std::min<uint64_t>(19, (2 * k + 2) / 3); }
+
+TigIndex *device_tig_index_build(const char *seq, const uint64_t *off, uint64_t n, uint64_t k, uint64_t m, uint64_t bucket_limit, int device_id,
+                                 TigIndexTimes *times) {
+    const char *fn = "mtg_tig_index_build";
+    if (k < 1) MTG_DIE("%s: k must be >= 1", fn);
+    if (k > 0xFFFFFFFFull) MTG_DIE("%s: k too large", fn);
+    if (m == 0) m = tig_index_default_m(k);
+    if (m > k || m > 31) MTG_DIE("%s: the minimizer length %llu is outside 1 .. min(k, 31)", fn, (unsigned long long)m);
+    if (bucket_limit == 0) bucket_limit = 64;
+    if (bucket_limit > 65536) MTG_DIE("%s: bucket_limit %llu; the limit is 65536", fn, (unsigned long long)bucket_limit);
+    TigIndex *ix = new TigIndex();
+    mtg_tig_index_info &info = ix->info;
+    info.k = k;
+    info.m = m;
+    info.bucket_limit = bucket_limit;
+    info.records = n;
+    info.occurrences = check_offsets(fn, seq, off, n, k);
+    info.characters = off[n];
+    if (info.characters >= POS_LIMIT) MTG_DIE("%s: %llu bases; the limit is 2^40 - 2", fn, (unsigned long long)info.characters);
+    if (device_id < 0 || device_count() <= device_id) MTG_DIE("no HIP device %d for the tig index (there is no CPU path)", device_id);
+    HIP_CHECK(hipSetDevice(device_id));
+    ix->device_id = device_id;
+    hipStream_t st = nullptr;
+    const bool wide = k >= 32;
+
+    SeqStore store("indexed sequences", seq, off, n, st, device_id);
+    PhaseEvents<4> ev;
+    ev.mark(0, st);
+    TigArgs a{};
+    a.packed = a.index_packed = store.packed; a.off = a.index_off = store.off; a.index_rec = n;
+    a.mn = MinArgs{m, k - m + 1, 2 * (m - 1), (1ull << (2 * m)) - 1};
+    kw::window_args_set_k(a, k);
+    const unsigned run_grid = hu::grid_for((store.n_bases + RUN - 1) / RUN);
+
+    // anchors: every position that is the anchor of a window, ascending
+    uint64_t all_anchors = 0;
+    hu::DeviceArray<unsigned long long> pos;
+    if (info.occurrences) {
+        const uint64_t bit_words = (store.n_bases + 31) / 32;
+        hu::DeviceArray<uint32_t> bitmap(bit_words), count(bit_words);
+        hu::DeviceArray<unsigned long long> rank(bit_words);
+        hu::ScanScratch<unsigned long long> scan(bit_words);
+        HIP_CHECK(hipMemsetAsync(bitmap, 0, bit_words * 4, st));
+        if (wide) anchor_mark_kernel<true><<<run_grid, hu::EB, 0, st>>>(a, store.n_bases, n, bitmap);
+        else anchor_mark_kernel<false><<<run_grid, hu::EB, 0, st>>>(a, store.n_bases, n, bitmap);
+        anchor_count_kernel<<<hu::grid_for(bit_words), hu::EB, 0, st>>>(bitmap, bit_words, count);
+        HIP_CHECK(hipGetLastError());
+        scan.scan(st, count, bit_words, rank);
+        HIP_CHECK(hipMemcpyAsync(&all_anchors, scan.total(), 8, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        pos.alloc(all_anchors);  // (a window has an anchor: at least one)
+        anchor_compact_kernel<<<hu::grid_for(bit_words), hu::EB, 0, st>>>(bitmap, bit_words, rank, all_anchors, pos);
+        HIP_CHECK(hipGetLastError());
+    }
+    ev.mark(1, st);
+
+    // directory: the anchors of the light buckets, grouped by bucket, ascending inside one
+    uint32_t bits = 3;
+    while ((1ull << bits) < all_anchors) bits++;
+    const uint64_t buckets = 1ull << bits;
+    ix->shift = a.shift = 64 - bits;
+    info.buckets = buckets;
+    ix->dir.alloc(buckets + 1);
+    {
+        hu::DeviceArray<uint32_t> hist(buckets), light(buckets);
+        hu::ScanScratch<unsigned long long> scan(buckets);
+        HIP_CHECK(hipMemsetAsync(hist, 0, buckets * 4, st));
+        if (all_anchors) bucket_hist_kernel<<<hu::grid_for(all_anchors), hu::EB, 0, st>>>(store.packed, pos, all_anchors, m, a.shift, hist);
+        bucket_light_kernel<<<hu::grid_for(buckets), hu::EB, 0, st>>>(hist, buckets, bucket_limit, light, store.small.d + 2);
+        HIP_CHECK(hipGetLastError());
+        scan.scan(st, light, buckets, ix->dir.get());
+        HIP_CHECK(hipMemcpyAsync(ix->dir + buckets, scan.total(), 8, hipMemcpyDeviceToDevice, st));
+        HIP_CHECK(hipMemcpyAsync(&info.anchors, scan.total(), 8, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        ix->entries.alloc(std::max<uint64_t>(info.anchors, 1));
+        HIP_CHECK(hipMemsetAsync(light, 0, buckets * 4, st));  // (now the scatter's cursors)
+        if (all_anchors)
+            bucket_scatter_kernel<<<hu::grid_for(all_anchors), hu::EB, 0, st>>>(store.packed, pos, all_anchors, m, a.shift, hist, bucket_limit, ix->dir,
+                                                                               light, info.anchors, ix->entries);
+        bucket_sort_kernel<<<hu::grid_for(buckets), hu::EB, 0, st>>>(hist, light, buckets, bucket_limit, ix->dir, ix->entries);
+        HIP_CHECK(hipGetLastError());
+        ev.mark(2, st);
+        store.small.read(st, "tig index");
+        info.heavy_buckets = store.small.h[2];
+    }
+    pos.release();
+    a.dir = ix->dir;
+    a.entries = ix->entries;
+
+    // the heavy table: every window whose minimizer's bucket is heavy
+    if (info.heavy_buckets) {
+        if (wide) heavy_kernel<true, false><<<run_grid, hu::EB, 0, st>>>(a, store.n_bases, n, store.small.d + 3, store.small.err());
+        else heavy_kernel<false, false><<<run_grid, hu::EB, 0, st>>>(a, store.n_bases, n, store.small.d + 3, store.small.err());
+        HIP_CHECK(hipGetLastError());
+        store.small.read(st, "tig index");
+        info.heavy_windows = store.small.h[3];
+        info.table_slots = std::max<uint64_t>(8, (2 * info.heavy_windows + 7) / 8 * 8);
+        a.table = ix->table.alloc(info.table_slots);
+        a.slots = info.table_slots;
+        HIP_CHECK(hipMemsetAsync(ix->table, 0xFF, info.table_slots * 8, st));
+        if (wide) heavy_kernel<true, true><<<run_grid, hu::EB, 0, st>>>(a, store.n_bases, n, nullptr, store.small.err());
+        else heavy_kernel<false, true><<<run_grid, hu::EB, 0, st>>>(a, store.n_bases, n, nullptr, store.small.err());
+        HIP_CHECK(hipGetLastError());
+    }
+    ev.mark(3, st);
+    store.small.read(st, "tig index");
+    if (times) {
+        times->build_upload_ms = store.upload_ms;
+        times->build_pack_ms = store.pack_ms;
+        times->build_anchors_ms = ev.ms(0, 1);
+        times->build_directory_ms = ev.ms(1, 2);
+        times->build_heavy_ms = ev.ms(2, 3);
+    }
+    ix->packed = store.take_packed();
+    ix->off = store.take_off();
+    info.device_bytes = (store.n_words + 2) * 4 + (n + 1) * 8 + (buckets + 1) * 8 + std::max<uint64_t>(info.anchors, 1) * 8 + info.table_slots * 8;
+    return ix;
+}
+
+void device_tig_index_info(const TigIndex *ix, mtg_tig_index_info *out) { *out = ix->info; }
+
+void device_tig_index_free(TigIndex *ix) {
+    if (!ix) return;
+    int cur = 0;  // (an index may die on a thread whose current device is another one)
+    (void)hipGetDevice(&cur);
+    (void)hipSetDevice(ix->device_id);
+    delete ix;
+    (void)hipSetDevice(cur);
+}
+
+void device_tig_index_query(const TigIndex *ix, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid,
+                            uint64_t *found, uint64_t *present_bits, uint64_t *valid_bits, TigIndexTimes *times) {
+    const char *fn = "mtg_tig_index_query";
+    const uint64_t k = ix->info.k;
+    (void)check_offsets(fn, seq, off, n, k);
+    if (n && (!kmers || !valid || !found)) MTG_DIE("%s: null argument", fn);
+    if (off[n] >= POS_LIMIT) MTG_DIE("%s: %llu bases; the limit is 2^40 - 2", fn, (unsigned long long)off[n]);
+    for (uint64_t r = 0; r < n; r++) {
+        const uint64_t len = off[r + 1] - off[r];
+        kmers[r] = len >= k ? len - k + 1 : 0;
+        valid[r] = found[r] = 0;
+    }
+    const uint64_t n_bases = off[n], bit_words = (n_bases + 63) / 64;
+    if (times) times->query_upload_ms = times->query_pack_ms = times->query_probe_ms = 0;
+    if (n_bases == 0) return;  // nothing to look at
+    HIP_CHECK(hipSetDevice(ix->device_id));
+    hipStream_t st = nullptr;
+    MaskedSeqStore store(seq, off, n, st, ix->device_id);
+    hu::DeviceArray<unsigned long long> d_counts(2 * n), d_bits;  // valid_bits, then present_bits (those asked for)
+    const int n_arrays = (valid_bits != nullptr) + (present_bits != nullptr);
+    if (n_arrays) d_bits.alloc(n_arrays * bit_words);
+    unsigned long long *d_valid_bits = valid_bits ? d_bits.get() : nullptr;
+    unsigned long long *d_present_bits = present_bits ? d_bits + (valid_bits ? bit_words : 0) : nullptr;
+    TigArgs a{};
+    a.packed = store.packed; a.off = store.off;
+    a.index_packed = ix->packed; a.index_off = ix->off; a.index_rec = ix->info.records;
+    a.dir = ix->dir; a.entries = ix->entries; a.shift = ix->shift; a.table = ix->table; a.slots = ix->info.table_slots;
+    a.mn = MinArgs{ix->info.m, k - ix->info.m + 1, 2 * (ix->info.m - 1), (1ull << (2 * ix->info.m)) - 1};
+    kw::window_args_set_k(a, k);
+    PhaseEvents<2> ev;
+    ev.mark(0, st);
+    HIP_CHECK(hipMemsetAsync(d_counts, 0, 2 * n * 8, st));
+    const unsigned grid = hu::grid_for(bit_words);  // (one thread per word: every word of the bit arrays is written)
+    if (k >= 32) tig_query_kernel<true><<<grid, hu::EB, 0, st>>>(a, store.bad, n_bases, n, d_counts, d_valid_bits, d_present_bits);
+    else tig_query_kernel<false><<<grid, hu::EB, 0, st>>>(a, store.bad, n_bases, n, d_counts, d_valid_bits, d_present_bits);
+    HIP_CHECK(hipGetLastError());
+    ev.mark(1, st);
+    HIP_CHECK(hipMemcpyAsync(valid, d_counts, n * 8, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(found, d_counts + n, n * 8, hipMemcpyDeviceToHost, st));
+    if (valid_bits) HIP_CHECK(hipMemcpyAsync(valid_bits, d_valid_bits, bit_words * 8, hipMemcpyDeviceToHost, st));
+    if (present_bits) HIP_CHECK(hipMemcpyAsync(present_bits, d_present_bits, bit_words * 8, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    if (times) {
+        times->query_upload_ms = store.upload_ms;
+        times->query_pack_ms = store.pack_ms;
+        times->query_probe_ms = ev.ms(0, 1);
+    }
+}
+
+}  // namespace mtg
