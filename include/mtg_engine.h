@@ -727,6 +727,41 @@ void mtg_kmer_index_colors(const mtg_kmer_index *ix, const char *seq, const uint
 /* In ms: {the colour statistics kernel of the last mtg_compact_unitigs_colored on this thread (HIP events); of the last
  * mtg_kmer_index_colors: upload (host clock), pack, probe -- HIP events around the kernels --, download (host clock)}. */
 void mtg_last_kmer_color_times(double out[5]);
+/* HOW OFTEN OTHER SEQUENCES SEE the indexed k-mers: the opposite question to the probes above. A TALLY belongs to one
+ * index -- plain, locating, weighted or coloured --, which must outlive it and which it never changes. It holds one unsigned 64-bit
+ * counter per table slot, all 0 at creation: 8 B per slot = 16 B per indexed window, taken from the device arena on the index's
+ * device (mtg_kmer_tally_device_bytes = 8 * info.slots) and given back by mtg_kmer_tally_free; mtg_release_device_memory leaves it
+ * intact. Several tallies on one index are independent.
+ * add: the query of mtg_kmer_index_query (n records of ARBITRARY bytes, the same validity rules; kmers / valid / found as there) and,
+ * for every valid window whose canonical k-mer is in the index, tally[class] += 1: repeats inside a record count, both strands fold
+ * onto one counter, invalid and absent windows add nothing. Any number of calls accumulate; one call has fewer than 2^40 - 1 bases,
+ * as a query, so a 64-bit counter does not overflow and nothing saturates.
+ * coverage: ANY sequences may be asked (the indexed ones say how deep the reads cover them); kmers / valid / found as in the query,
+ * and for record r over its found windows: covered[r] = those whose class has a tally > 0, sum[r] = the sum of tally(class), max[r] =
+ * the largest such tally; all three 0 when found[r] = 0. A k-mer that occurs in several asked windows contributes its class's tally
+ * to each of them. per_window (may be NULL; off[n] entries, one per global base position): [p] = the tally of the class of the
+ * window that starts at p if that window is valid and found, else 0 -- the positions of mtg_kmer_index_abundance's per_window.
+ * reset: every counter 0 again. Exact integers, a function of the index, the sequences added since creation or the last reset, and
+ * the sequences asked; integer atomic sums make them independent of launch geometry and arrival order. A null argument or bad
+ * offsets abort with the function's name; an empty query returns at once. */
+typedef struct mtg_kmer_tally mtg_kmer_tally;
+mtg_kmer_tally *mtg_kmer_tally_create(const mtg_kmer_index *ix); /* the index must outlive the tally */
+uint64_t mtg_kmer_tally_device_bytes(const mtg_kmer_tally *t);   /* 8 * info.slots */
+void mtg_kmer_tally_add(mtg_kmer_tally *t, const char *seq, const uint64_t *off, uint64_t n,
+                        uint64_t *kmers, uint64_t *valid, uint64_t *found); /* [n] each */
+void mtg_kmer_tally_coverage(const mtg_kmer_tally *t, const char *seq, const uint64_t *off, uint64_t n,
+                             uint64_t *kmers, uint64_t *valid, uint64_t *found,       /* [n] each */
+                             uint64_t *covered, uint64_t *sum, uint64_t *max,         /* [n] each */
+                             uint64_t *per_window);                                   /* nullable, [off[n]] */
+/* The same over a store as mtg_read_sequences / mtg_compact_unitigs hand it out: n = mtg_unitigs_count(store). */
+void mtg_kmer_tally_add_store(mtg_kmer_tally *t, const mtg_unitigs *store, uint64_t *kmers, uint64_t *valid, uint64_t *found);
+void mtg_kmer_tally_coverage_store(const mtg_kmer_tally *t, const mtg_unitigs *store, uint64_t *kmers, uint64_t *valid, uint64_t *found,
+                                   uint64_t *covered, uint64_t *sum, uint64_t *max, uint64_t *per_window);
+void mtg_kmer_tally_reset(mtg_kmer_tally *t);
+void mtg_kmer_tally_free(mtg_kmer_tally *t); /* NULL is fine; any current device */
+/* Of the last mtg_kmer_tally_add or mtg_kmer_tally_coverage on this thread, in ms: {upload (host clock), pack, probe -- HIP events
+ * around the kernel --, download (host clock)}. */
+void mtg_last_kmer_tally_times(double out[4]);
 /* MONOCHROMATIC UNITIGS and COLOUR CLASSES. mtg_compact_unitigs_colored_classes is mtg_compact_unitigs_colored plus
  * *classes, the dictionary of the output store's masks. Number the windows of *out i = 0 .. N - 1 in window order (the indexing of
  * *kmer_colors). A RUN is a maximal stretch of consecutive windows of ONE unitig with equal masks. The classes are the distinct masks,

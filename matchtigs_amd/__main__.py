@@ -54,6 +54,12 @@ the component of every unitig, line i for record i of `--unitigs-fa-out`; the la
 link lists. `--min-component-kmers N` (`--seq-in`, `--fa-in`) removes every component of fewer than N k-mers -- the clusters of two
 or three short unitigs that are neither tip nor isolated nor bubble -- once, before `--verify` and every output; links exist only
 inside a component, so what stays is still maximal and nothing is compacted again.
+`--count-fa` with `--count-out` (any input; not in the reference) asks the opposite of `--query-fa`: how much of the input's k-mer set
+did OTHER reads see? Every `--count-fa` file is a sample (FASTA or FASTQ, `.gz` or not, told apart by the content); its k-mers are
+counted on the k-mers of the unitigs -- as written, after cleaning, splitting and the component filter -- on the GPU, either strand,
+repeats included, and `--count-out` gets one row per unitig with, per sample, the k-mers of the unitig the sample saw at all and the sum
+of their counts: a unitig x sample depth matrix of exact integers. `--count-min-base-quality Q` masks the bases of FASTQ count files
+whose Phred quality is below Q.
 """
 from __future__ import annotations
 
@@ -182,6 +188,14 @@ def main(argv=None) -> int:
                          "abundance (L >= 2; k + 1 is the least that pops a SNP, 2 k the usual value; not in the reference)")
     ap.add_argument("--bubble-ratio", type=int, metavar="R",
                     help="with --pop-bubbles: pop an arm only if the best arm has at least R times its mean abundance (1..255, default 1)")
+    ap.add_argument("--count-fa", action="append", metavar="PATH",
+                    help="reads of one sample (fasta or fastq, optionally .gz; any characters) whose k-mers are counted on the k-mers of "
+                         "the input's unitigs on the GPU; repeatable, one sample per file; needs --count-out (not in the reference)")
+    ap.add_argument("--count-out", metavar="PATH",
+                    help="TSV (.gz => gzip) with one row per record of --unitigs-fa-out (0-based): unitig, kmers, then per --count-fa "
+                         "file <file>:covered (its k-mers the file saw) and <file>:sum (the sum of their counts)")
+    ap.add_argument("--count-min-base-quality", type=int, metavar="Q",
+                    help="with fastq --count-fa files: a base whose Phred quality is below Q (0..93) is replaced by N")
     args = ap.parse_args(argv)
 
     classed = bool(args.monochromatic_unitigs or args.color_classes_out or args.unitig_color_classes_out)
@@ -215,6 +229,10 @@ def main(argv=None) -> int:
         ap.error("--query-abundance-profile-out needs --query-abundance-out")
     if args.query_colors_out and not (args.seq_in and args.query_fa and args.query_out):
         ap.error("--query-colors-out needs --seq-in, --query-fa and --query-out")
+    if bool(args.count_fa) != bool(args.count_out):
+        ap.error("--count-fa needs --count-out" if args.count_fa else "--count-out needs --count-fa")
+    if args.count_min_base_quality is not None and not args.count_fa:
+        ap.error("--count-min-base-quality needs --count-fa")
     for flag, value in (("--query-index", args.query_index), ("--query-minimizer-length", args.query_minimizer_length),
                         ("--query-index-over", args.query_index_over)):
         if value is not None and not args.query_fa:
@@ -270,10 +288,11 @@ def main(argv=None) -> int:
                             ("--color-classes-out", args.color_classes_out), ("--unitig-color-classes-out", args.unitig_color_classes_out)):
             if value is not None:
                 ap.error(f"--min-component-kmers cannot be combined with {flag}")
-    for flag, value in (("--min-base-quality", args.min_base_quality), ("--query-min-base-quality", args.query_min_base_quality)):
+    for flag, value in (("--min-base-quality", args.min_base_quality), ("--query-min-base-quality", args.query_min_base_quality),
+                        ("--count-min-base-quality", args.count_min_base_quality)):
         if value is not None and not 0 <= value <= 93:
             ap.error(f"{flag} must be in 0..93")
-    if not (args.color_classes_out or args.unitig_color_classes_out or args.color_matrix_out or args.unitig_colors_out or args.kmer_spectrum_out or args.unitig_abundance_out or args.unitig_kmer_abundance_out or args.query_fa or args.greedytigs_fa_out or args.eulertigs_fa_out or args.greedytigs_gfa_out or args.eulertigs_gfa_out
+    if not (args.color_classes_out or args.unitig_color_classes_out or args.color_matrix_out or args.unitig_colors_out or args.kmer_spectrum_out or args.unitig_abundance_out or args.unitig_kmer_abundance_out or args.query_fa or args.count_fa or args.greedytigs_fa_out or args.eulertigs_fa_out or args.greedytigs_gfa_out or args.eulertigs_gfa_out
             or args.greedytigs_duplication_bitvector_out or args.matchtigs_fa_out or args.matchtigs_gfa_out or args.verify_fa or args.unitigs_fa_out
             or args.unitigs_bcalm_out or args.unitigs_gfa_out or args.components_out or args.unitig_components_out):
         ap.error("nothing to do: give --greedytigs-fa-out / --greedytigs-gfa-out and/or --eulertigs-fa-out / --eulertigs-gfa-out")
@@ -281,11 +300,13 @@ def main(argv=None) -> int:
     from . import api
 
     # FASTQ is told from FASTA by the content; the quality flags need a file they can apply to
-    fastq = {path for path in (args.seq_in or []) + (args.query_fa or []) if api.sequence_file_format(path) == 2}
-    if args.min_base_quality is not None and not fastq:
+    fastq = {path for path in (args.seq_in or []) + (args.query_fa or []) + (args.count_fa or []) if api.sequence_file_format(path) == 2}
+    if args.min_base_quality is not None and not fastq.intersection((args.seq_in or []) + (args.query_fa or [])):
         ap.error("--min-base-quality needs a fastq file among --seq-in / --query-fa")
     if args.query_min_base_quality is not None and not fastq.intersection(args.query_fa or []):
         ap.error("--query-min-base-quality needs a fastq file among --query-fa")
+    if args.count_min_base_quality is not None and not fastq.intersection(args.count_fa):
+        ap.error("--count-min-base-quality needs a fastq file among --count-fa")
     try:
         return _run(api, args, fastq)
     except api.FastqFormatError as e:  # an error of the input: the message names file, record, line and reason
@@ -506,9 +527,12 @@ def _run(api, args, fastq) -> int:
               f"({r['tigs']} tigs, {r['fasta_bytes']} fasta bytes)", file=sys.stderr)
         if args.verify:
             all_equal &= report(f"{name} ({out or 'spelled in memory'})", r["verify_tigs"], r["verify"])
+    table_index = None  # the plain-enough table index over the unitig store, if the queries built one: the count reuses it
     if args.query_fa:
-        _query(api, args, store, abundance.kmer_counts if args.query_abundance_out else None, fastq,
-               colors if args.query_colors_out else None)
+        table_index = _query(api, args, store, abundance.kmer_counts if args.query_abundance_out else None, fastq,
+                             colors if args.query_colors_out else None, keep_index=bool(args.count_fa))
+    if args.count_fa:
+        _count(api, args, store, fastq, table_index)
     return 0 if all_equal else 1
 
 
@@ -707,11 +731,12 @@ def _write_color_matrix(args, colors) -> None:
     print(line, file=sys.stderr)
 
 
-def _query(api, args, store, kmer_counts=None, fastq=(), colors=None) -> None:
+def _query(api, args, store, kmer_counts=None, fastq=(), colors=None, keep_index=False):
     """`--query-fa`: the input's k-mer set (the unitig store) indexed once; one TSV row and one presence line per query record, and
     with `--query-locate-out` one row per run of located k-mers. kmer_counts (`--query-abundance-out`): the index is weighted with
     them, and one more TSV row, and with `--query-abundance-profile-out` one line of integers, per query record. colors
-    (`--query-colors-out`): the index carries their masks, and one more TSV row per query record."""
+    (`--query-colors-out`): the index carries their masks, and one more TSV row per query record. keep_index: a table index over
+    `store` is handed back open instead of closed (`--count-fa` counts on it); None if the queries asked another kind of index."""
     import contextlib
     import gzip
 
@@ -723,6 +748,8 @@ def _query(api, args, store, kmer_counts=None, fastq=(), colors=None) -> None:
     with contextlib.ExitStack() as stack:
         sparse = args.query_index == "minimizer"
         over = args.query_index_over or "input"
+        kept = keep_index and not sparse and over == "input"
+        hold = (lambda ix: ix) if kept else stack.enter_context  # (a kept index is closed by the caller)
         if sparse or over != "input":  # (the same k-mer set, asked of another index or spelled by the tigs)
             indexed = store if over == "input" else api.read_sequences(args.greedytigs_fa_out if over == "greedytigs" else args.eulertigs_fa_out)
             if sparse:
@@ -730,12 +757,12 @@ def _query(api, args, store, kmer_counts=None, fastq=(), colors=None) -> None:
             else:
                 index = stack.enter_context(api.KmerIndex(indexed, args.k, args.device))
         elif colors is not None:  # (the masks, and the counts too when abundances are asked for)
-            index = stack.enter_context(api.KmerIndex(store, args.k, args.device, locate=bool(args.query_locate_out), weights=kmer_counts,
-                                                      colors=colors.kmer_colors, n_colors=colors.n_colors))
+            index = hold(api.KmerIndex(store, args.k, args.device, locate=bool(args.query_locate_out), weights=kmer_counts,
+                                       colors=colors.kmer_colors, n_colors=colors.n_colors))
         elif kmer_counts is None:
-            index = stack.enter_context(api.KmerIndex(store, args.k, args.device, locate=bool(args.query_locate_out)))
+            index = hold(api.KmerIndex(store, args.k, args.device, locate=bool(args.query_locate_out)))
         else:
-            index = stack.enter_context(api.KmerIndex(store, args.k, args.device, locate=bool(args.query_locate_out), weights=kmer_counts))
+            index = hold(api.KmerIndex(store, args.k, args.device, locate=bool(args.query_locate_out), weights=kmer_counts))
         if args.query_index is not None or args.query_index_over is not None:
             i = index.info
             line = i.describe() if sparse else (
@@ -786,6 +813,41 @@ def _query(api, args, store, kmer_counts=None, fastq=(), colors=None) -> None:
             valid, found = int(r.valid.sum()), int(r.found.sum())
             print(f"Querying {path}: {len(names)} records, {int(r.kmers.sum())} k-mers, {valid} valid, {found} found "
                   f"({100.0 * found / valid if valid else 0.0:.2f} %) in {time.perf_counter() - t0:.1f} s", file=sys.stderr)
+        return index if kept else None
+
+
+def _count(api, args, store, fastq=(), index=None) -> None:
+    """`--count-fa`: every file is a sample whose k-mers are counted on the k-mers of the unitig store. One table
+    index over the store -- `index`, the one the queries left open, else a plain one built here -- and one tally serve all samples in
+    turn: add the sample, read the coverage of the store's own records, keep two columns, reset. `--count-out`: one row per record
+    of the store, per sample the k-mers it saw at all and the sum of their counts."""
+    import numpy as np
+
+    with (index if index is not None else api.KmerIndex(store, args.k, args.device)) as index, api.KmerTally(index) as tally:
+        columns, kmers = [], None
+        for path in args.count_fa:
+            t0 = time.perf_counter()
+            if path in fastq:
+                seqs, _, _ = api.read_fastq(path, args.count_min_base_quality or 0, args.device, named=True)  # (masked bases are N)
+            else:
+                seqs, _ = api.read_sequences_named(path)  # (any characters, as the queries)
+            r = tally.add(seqs)
+            cov = tally.coverage(store)
+            tally.reset()
+            if not (np.array_equal(cov.valid, cov.kmers) and np.array_equal(cov.found, cov.kmers)):  # the store is what is indexed
+                bad = int(np.flatnonzero((cov.valid != cov.kmers) | (cov.found != cov.kmers))[0])
+                raise SystemExit(f"--count-fa {path}: unitig {bad} has {int(cov.kmers[bad])} k-mers, of which the index finds "
+                                 f"{int(cov.found[bad])} ({int(cov.valid[bad])} valid): the index does not hold the unitigs")
+            kmers = cov.kmers
+            columns += [cov.covered, cov.sum]
+            valid, found, total = int(r.valid.sum()), int(r.found.sum()), int(kmers.sum())
+            print(f"Counting {path}: {len(r.kmers)} records, {int(r.kmers.sum())} k-mers, {valid} valid, {found} found "
+                  f"({100.0 * found / valid if valid else 0.0:.2f} %), {int(np.count_nonzero(cov.covered))} of {len(kmers)} unitigs covered, "
+                  f"mean depth {int(cov.sum.sum()) / total if total else 0.0:.3f} in {time.perf_counter() - t0:.1f} s", file=sys.stderr)
+        with _open_text(args, args.count_out) as f:
+            f.write("\t".join(["unitig", "kmers"] + [f"{path}:{what}" for path in args.count_fa for what in ("covered", "sum")]) + "\n")
+            rows = np.stack([np.arange(len(kmers), dtype=np.uint64), kmers] + columns, axis=1).tolist() if len(kmers) else []
+            f.writelines("\t".join(map(str, row)) + "\n" for row in rows)
 
 
 def _write_query_abundance(index, seqs, names, weighed, profile, valid_bits) -> None:

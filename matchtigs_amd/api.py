@@ -1720,6 +1720,104 @@ class KmerIndex:
         return KmerColorResult(self.info.k, off, kmers, valid, found, per_color, pw)
 
 
+@dataclass(frozen=True, eq=False)
+class KmerCoverageResult:
+    """What KmerTally.coverage found, per asked record (numpy uint64 arrays): kmers / valid / found as KmerIndex.query gives them,
+    and over the found windows of the record covered = those whose k-mer was added at least once, sum = the sum of the tallies of
+    their k-mers, max = the largest such tally -- all 0 where nothing was found. With per_window=True also per_window (one entry per
+    global base position of the asked sequences): the tally of the k-mer of the window that starts there if it is valid and found,
+    else 0."""
+
+    k: int
+    offsets: np.ndarray
+    kmers: np.ndarray
+    valid: np.ndarray
+    found: np.ndarray
+    covered: np.ndarray
+    sum: np.ndarray
+    max: np.ndarray
+    per_window: Optional[np.ndarray] = None
+
+
+class KmerTally:
+    """How often other sequences see the k-mers of a KmerIndex (mtg_kmer_tally_*): one 64-bit counter per k-mer of the
+    index, zero at first, on the index's GPU (device_bytes, until close() or collection). add(reads) counts every valid window of
+    the reads whose k-mer is in the index, on either strand, repeats included; any number of adds accumulate. coverage(sequences)
+    reads the counters back along any sequences -- the indexed ones give their depth in the reads. The index may be plain, locating,
+    weighted or coloured and is never changed; the tally keeps a reference to it, and several tallies on one index are independent."""
+
+    def __init__(self, index: KmerIndex):
+        self._h = None
+        if not isinstance(index, KmerIndex):
+            raise TypeError("KmerTally counts on a KmerIndex")
+        if not index._h:
+            raise ValueError("the index is closed")
+        self.index = index
+        self._L = index._L
+        self._h = self._L.mtg_kmer_tally_create(index._h)
+        self.device_bytes = int(self._L.mtg_kmer_tally_device_bytes(self._h))
+
+    def close(self) -> None:
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            self._L.mtg_kmer_tally_free(h)
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _open(self) -> None:
+        """The tally open and its index open, else ValueError: before the library is asked."""
+        if not self._h:
+            raise ValueError("the tally is closed")
+        if not self.index._h:
+            raise ValueError("the index is closed")
+
+    def add(self, seqs_or_store) -> KmerQueryResult:
+        """Count the k-mers of seqs_or_store (UnitigStore, list of str, or (uint8 array, offsets); ANY bytes) that the index holds
+        -> what KmerIndex.query says of them."""
+        self._open()
+        d, o, n, keep, off, kmers, valid, found = self.index._probe_inputs(seqs_or_store)
+        if isinstance(seqs_or_store, UnitigStore):
+            self._L.mtg_kmer_tally_add_store(self._h, seqs_or_store.handle, _ptr(kmers), _ptr(valid), _ptr(found))
+        else:
+            self._L.mtg_kmer_tally_add(self._h, d, o, n, _ptr(kmers), _ptr(valid), _ptr(found))
+        del keep
+        return KmerQueryResult(self.index.info.k, off, kmers, valid, found)
+
+    def coverage(self, seqs_or_store, per_window: bool = False) -> KmerCoverageResult:
+        """KmerIndex.query's counts per record of seqs_or_store plus, over its found windows, how many were added at least once, the
+        sum and the largest of their tallies (KmerCoverageResult); per_window: also the tally at every window start."""
+        self._open()
+        d, o, n, keep, off, kmers, valid, found = self.index._probe_inputs(seqs_or_store)
+        covered, total, hi = (np.zeros(n, np.uint64) for _ in range(3))
+        pw = np.zeros(int(off[n]), np.uint64) if per_window else None
+        outs = (_ptr(kmers), _ptr(valid), _ptr(found), _ptr(covered), _ptr(total), _ptr(hi), _ptr(pw) if per_window else None)
+        if isinstance(seqs_or_store, UnitigStore):
+            self._L.mtg_kmer_tally_coverage_store(self._h, seqs_or_store.handle, *outs)
+        else:
+            self._L.mtg_kmer_tally_coverage(self._h, d, o, n, *outs)
+        del keep
+        return KmerCoverageResult(self.index.info.k, off, kmers, valid, found, covered, total, hi, pw)
+
+    def reset(self) -> None:
+        """Every counter zero again."""
+        self._open()
+        self._L.mtg_kmer_tally_reset(self._h)
+
+
+def last_kmer_tally_times() -> dict:
+    """Phases of the last KmerTally.add or KmerTally.coverage on this thread, in ms (HIP events around the kernels; upload and
+    download by the host clock)."""
+    out = (C.c_double * 4)()
+    _lib.load().mtg_last_kmer_tally_times(out)
+    return dict(zip(("upload_ms", "pack_ms", "probe_ms", "download_ms"), list(out)))
+
+
 def default_minimizer_length(k: int) -> int:
     """The minimizer length a TigIndex takes when none is given: min(19, ceil(2 k / 3)) -- 19 at k = 31."""
     return min(19, (2 * k + 2) // 3)

@@ -217,6 +217,22 @@ struct KmerColorTimes {
 };
 void device_kmer_index_colors(const KmerIndex *ix, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid,
                               uint64_t *found, uint32_t *per_color, uint64_t *per_window, KmerColorTimes *times);
+// A tally over one index: one 64-bit counter per table slot, zero at creation, from the device arena of the index's
+// device until device_kmer_tally_free; the index must outlive it and is not changed. add: the query plus, per found window, one
+// more on the counter of its class. coverage: the query plus, per record over its found windows, those whose class has a count > 0,
+// the sum of the counts and the largest; per_window, if given ([off[n]]): the count at every found window's global start, 0 elsewhere.
+struct KmerTally;
+struct KmerTallyTimes {
+    double upload_ms = 0, pack_ms = 0, probe_ms = 0, download_ms = 0;
+};
+KmerTally *device_kmer_tally_create(const KmerIndex *ix);
+uint64_t device_kmer_tally_device_bytes(const KmerTally *t);
+void device_kmer_tally_add(KmerTally *t, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid, uint64_t *found,
+                           KmerTallyTimes *times);
+void device_kmer_tally_coverage(const KmerTally *t, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid,
+                                uint64_t *found, uint64_t *covered, uint64_t *sum, uint64_t *max, uint64_t *per_window, KmerTallyTimes *times);
+void device_kmer_tally_reset(KmerTally *t);
+void device_kmer_tally_free(KmerTally *t);
 // tig_index_device.hip: the sparse minimizer index over a sequence set (the file's header and DESIGN.md 28 state the contract): the
 // packed bases plus one word per anchor, asked what device_kmer_index_query is asked. m = 0: tig_index_default_m(k); bucket_limit
 // = 0: 64. times: host wall clock of the uploads, HIP-event time of the kernels; a build sets the first five, a query the last three.

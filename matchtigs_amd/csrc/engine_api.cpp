@@ -830,6 +830,51 @@ void mtg_last_kmer_color_times(double out[5]) {
     const KmerColorTimes &t = g_last_kmer_color;
     out[0] = t.stats_ms; out[1] = t.upload_ms; out[2] = t.pack_ms; out[3] = t.probe_ms; out[4] = t.download_ms;
 }
+// ---- ... and how often other sequences see them ----
+struct mtg_kmer_tally { KmerTally *t; };
+static thread_local KmerTallyTimes g_last_kmer_tally;
+mtg_kmer_tally *mtg_kmer_tally_create(const mtg_kmer_index *ix) {
+    if (!ix) MTG_DIE("mtg_kmer_tally_create: null argument");
+    return new mtg_kmer_tally{device_kmer_tally_create(ix->ix)};
+}
+uint64_t mtg_kmer_tally_device_bytes(const mtg_kmer_tally *t) {
+    if (!t) MTG_DIE("mtg_kmer_tally_device_bytes: null argument");
+    return device_kmer_tally_device_bytes(t->t);
+}
+void mtg_kmer_tally_add(mtg_kmer_tally *t, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid,
+                        uint64_t *found) {
+    if (!t) MTG_DIE("mtg_kmer_tally_add: null argument");
+    device_kmer_tally_add(t->t, seq, off, n, kmers, valid, found, &g_last_kmer_tally);
+}
+void mtg_kmer_tally_add_store(mtg_kmer_tally *t, const mtg_unitigs *store, uint64_t *kmers, uint64_t *valid, uint64_t *found) {
+    if (!t || !store) MTG_DIE("mtg_kmer_tally_add_store: null argument");
+    const UnitigStore &s = *store->s;
+    mtg_kmer_tally_add(t, s.data.data(), s.off.data(), s.off.size() - 1, kmers, valid, found);
+}
+void mtg_kmer_tally_coverage(const mtg_kmer_tally *t, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid,
+                             uint64_t *found, uint64_t *covered, uint64_t *sum, uint64_t *max, uint64_t *per_window) {
+    if (!t) MTG_DIE("mtg_kmer_tally_coverage: null argument");
+    device_kmer_tally_coverage(t->t, seq, off, n, kmers, valid, found, covered, sum, max, per_window, &g_last_kmer_tally);
+}
+void mtg_kmer_tally_coverage_store(const mtg_kmer_tally *t, const mtg_unitigs *store, uint64_t *kmers, uint64_t *valid, uint64_t *found,
+                                   uint64_t *covered, uint64_t *sum, uint64_t *max, uint64_t *per_window) {
+    if (!t || !store) MTG_DIE("mtg_kmer_tally_coverage_store: null argument");
+    const UnitigStore &s = *store->s;
+    mtg_kmer_tally_coverage(t, s.data.data(), s.off.data(), s.off.size() - 1, kmers, valid, found, covered, sum, max, per_window);
+}
+void mtg_kmer_tally_reset(mtg_kmer_tally *t) {
+    if (!t) MTG_DIE("mtg_kmer_tally_reset: null argument");
+    device_kmer_tally_reset(t->t);
+}
+void mtg_kmer_tally_free(mtg_kmer_tally *t) {
+    if (!t) return;
+    device_kmer_tally_free(t->t);
+    delete t;
+}
+void mtg_last_kmer_tally_times(double out[4]) {
+    const KmerTallyTimes &t = g_last_kmer_tally;
+    out[0] = t.upload_ms; out[1] = t.pack_ms; out[2] = t.probe_ms; out[3] = t.download_ms;
+}
 void mtg_last_kmer_query_times(double out[6]) {
     const KmerQueryTimes &t = g_last_kmer_query;
     out[0] = t.build_upload_ms; out[1] = t.build_pack_ms; out[2] = t.build_insert_ms;

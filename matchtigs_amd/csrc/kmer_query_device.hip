@@ -68,6 +68,18 @@
 //             --, and a change of either, or the end of the walk, flushes it: one atomicAdd(per_color[r C + c], run) per set bit c.
 //             Worst case: masks that alternate from window to window cost popcount(mask) atomics per window.
 // A call takes 4 C B per record and, with per_window, 8 B per query base beside the query's store.
+//
+// Tally (any index, mtg_kmer_tally_*). The opposite question: how often did these reads see each k-mer of the set? A
+// tally is one 64-bit counter per slot of one index, 8 B per slot = 16 B per window, zero at creation; the index is not changed.
+//   add       tally_kernel: the query's walk (probe_run); per found window tally[slot] += 1. The thread keeps (slot, run length):
+//             a found window on the same slot only lengthens the run, a change of slot or the end of the walk flushes one 64-bit
+//             atomicAdd(&tally[slot], run) whose result is not read. A homopolymer costs one atomic per thread; distinct k-mers
+//             one random 8-byte atomic per found window
+//   coverage  coverage_kernel: abundance_kernel reading tally[slot] for weight[slot]; per (thread, record) covered / sum / max in
+//             registers, out by two atomicAdds and one 64-bit atomicMax when the record changes. per_window as there, 64-bit
+// Integer sums and maxima: nothing depends on the launch geometry or on the order the atomics land in. A call is limited like a
+// query (fewer than 2^40 - 1 bases), so a counter cannot overflow. Coverage takes 8 + 8 + 8 B per record and, with per_window,
+// 8 B per base beside the query's store.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -398,6 +410,70 @@ __global__ __launch_bounds__(hu::EB) void color_query_kernel(IndexArgs a, const 
         for (const uint64_t end = p0 + RUN < n_bases ? p0 + RUN : n_bases; next_p < end; next_p++) per_window[next_p] = 0;
 }
 
+// ---- tally ----
+// query_kernel's walk; per found window tally[slot of its class] += 1 (tally: [slots], 64-bit). The thread keeps (slot, run length):
+// a found window on the slot of the found window before it only lengthens the run -- absent and invalid windows and a change of
+// record in between do not break it, only sums leave --, and a change of slot, or the end of the walk, flushes it: one
+// atomicAdd(&tally[slot], run) whose result nobody reads. Worst case: classes that alternate from window to window, one atomic each.
+template <bool WIDE>
+__global__ __launch_bounds__(hu::EB) void tally_kernel(IndexArgs a, const unsigned long long *bad, uint64_t n_bases, uint64_t n_rec,
+                                                       unsigned long long *counts, unsigned long long *tally) {
+    const uint64_t p0 = hu::gid() * RUN;
+    if (p0 >= n_bases) return;
+    unsigned long long vbits = 0, pbits = 0;
+    uint64_t cur = 0;  // the slot of the run (a slot is < a.slots: the walk calls hit only with one it found)
+    uint32_t run = 0;  // found windows on `cur` since the last flush (at most RUN)
+    probe_run<WIDE>(a, bad, p0, n_bases, n_rec, counts, vbits, pbits, [&](uint64_t, uint64_t, uint64_t slot) {
+        if (slot != cur) {
+            if (run) atomicAdd(&tally[cur], (unsigned long long)run);
+            cur = slot;
+            run = 0;
+        }
+        run++;
+    });
+    if (run) atomicAdd(&tally[cur], (unsigned long long)run);
+}
+
+// abundance_kernel with tally[slot] in place of weight[slot]. counts: [5 n_rec] valid, found, then the found windows whose class
+// has a tally > 0, the sum of the tallies and the largest tally (all 0 before); per_window: [n_bases] or null.
+template <bool WIDE>
+__global__ __launch_bounds__(hu::EB) void coverage_kernel(IndexArgs a, const unsigned long long *bad, uint64_t n_bases, uint64_t n_rec,
+                                                          unsigned long long *counts, const unsigned long long *tally,
+                                                          unsigned long long *per_window) {
+    const uint64_t p0 = hu::gid() * RUN;
+    if (p0 >= n_bases) return;
+    unsigned long long vbits = 0, pbits = 0;
+    uint64_t rec = 0, sum = 0, hi = 0, next_p = p0;  // next_p: the first position of the run that per_window has not been told yet
+    uint32_t covered = 0, hits = 0;                  // (of the record `rec`; at most RUN hits)
+    auto flush = [&]() {
+        if (!hits) return;
+        if (covered) {  // (else the sum and the largest are 0 too)
+            atomicAdd(&counts[2 * n_rec + rec], (unsigned long long)covered);
+            atomicAdd(&counts[3 * n_rec + rec], (unsigned long long)sum);
+            atomicMax(&counts[4 * n_rec + rec], (unsigned long long)hi);
+        }
+        sum = 0; hi = 0; covered = 0; hits = 0;
+    };
+    probe_run<WIDE>(a, bad, p0, n_bases, n_rec, counts, vbits, pbits, [&](uint64_t q, uint64_t r, uint64_t slot) {
+        if (r != rec) {
+            flush();
+            rec = r;
+        }
+        const uint64_t t = tally[slot];
+        covered += t != 0;
+        sum += t;
+        hi = t > hi ? t : hi;
+        hits++;
+        if (per_window) {
+            for (; next_p < q; next_p++) per_window[next_p] = 0;
+            per_window[next_p++] = t;
+        }
+    });
+    flush();
+    if (per_window)
+        for (const uint64_t end = p0 + RUN < n_bases ? p0 + RUN : n_bases; next_p < end; next_p++) per_window[next_p] = 0;
+}
+
 // offsets of one set: start at 0, do not decrease; returns its windows
 uint64_t check_offsets(const char *fn, const char *data, const uint64_t *off, uint64_t n, uint64_t k) {
     if (!off || (n && off[n] && !data)) MTG_DIE("%s: null argument", fn);
@@ -703,6 +779,93 @@ void device_kmer_index_colors(const KmerIndex *ix, const char *seq, const uint64
     p.download_counts(valid, found);
     HIP_CHECK(hipStreamSynchronize(p.st));
     hu::download_sliced(per_color, d_per_color, n * C * 4, p.st, p.device_id);
+    if (per_window) hu::download_sliced(per_window, d_per_window, n_bases * 8, p.st, p.device_id);
+    if (times) {
+        p.booked(&times->upload_ms, &times->pack_ms, &times->probe_ms);
+        times->download_ms = ms_since(t0);
+    }
+}
+
+// ---- tally ----
+struct KmerTally {
+    const KmerIndex *ix;  // (the caller keeps it alive for add and coverage; reset and free do without it)
+    int device_id;
+    uint64_t slots;
+    hu::DeviceArray<unsigned long long> count;  // [slots] the windows added on the slot's class
+};
+
+KmerTally *device_kmer_tally_create(const KmerIndex *ix) {
+    on_device(ix->device_id);
+    KmerTally *t = new KmerTally{ix, ix->device_id, ix->info.slots, {}};
+    t->count.alloc(t->slots);
+    device_kmer_tally_reset(t);
+    return t;
+}
+
+uint64_t device_kmer_tally_device_bytes(const KmerTally *t) { return t->slots * 8; }
+
+void device_kmer_tally_reset(KmerTally *t) {
+    on_device(t->device_id);
+    HIP_CHECK(hipMemsetAsync(t->count, 0, t->slots * 8, nullptr));
+    HIP_CHECK(hipStreamSynchronize(nullptr));
+}
+
+void device_kmer_tally_free(KmerTally *t) {
+    if (!t) return;
+    int cur = 0;  // (as an index: it may die on a thread whose current device is another one)
+    (void)hipGetDevice(&cur);
+    (void)hipSetDevice(t->device_id);
+    delete t;
+    (void)hipSetDevice(cur);
+}
+
+void device_kmer_tally_add(KmerTally *t, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid, uint64_t *found,
+                           KmerTallyTimes *times) {
+    const KmerIndex *ix = t->ix;
+    const uint64_t n_bases = probe_windows("mtg_kmer_tally_add", ix->info.k, seq, off, n, kmers, valid, found, false);
+    if (times) *times = KmerTallyTimes();
+    if (n_bases == 0) return;  // nothing to look at
+    Probe<> p(ix, seq, off, n, 2);
+    p.start();
+    if (p.wide) tally_kernel<true><<<p.run_grid(), hu::EB, 0, p.st>>>(p.a, p.store.bad, n_bases, n, p.d_counts, t->count);
+    else tally_kernel<false><<<p.run_grid(), hu::EB, 0, p.st>>>(p.a, p.store.bad, n_bases, n, p.d_counts, t->count);
+    HIP_CHECK(hipGetLastError());
+    p.ev.mark(1, p.st);
+    HIP_CHECK(hipStreamSynchronize(p.st));
+    const auto t0 = std::chrono::steady_clock::now();
+    p.download_counts(valid, found);
+    HIP_CHECK(hipStreamSynchronize(p.st));
+    if (times) {
+        p.booked(&times->upload_ms, &times->pack_ms, &times->probe_ms);
+        times->download_ms = ms_since(t0);
+    }
+}
+
+void device_kmer_tally_coverage(const KmerTally *t, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid,
+                                uint64_t *found, uint64_t *covered, uint64_t *sum, uint64_t *max, uint64_t *per_window, KmerTallyTimes *times) {
+    const KmerIndex *ix = t->ix;
+    const uint64_t n_bases = probe_windows("mtg_kmer_tally_coverage", ix->info.k, seq, off, n, kmers, valid, found, n && (!covered || !sum || !max));
+    std::fill(covered, covered + n, 0ull);
+    std::fill(sum, sum + n, 0ull);
+    std::fill(max, max + n, 0ull);
+    if (times) *times = KmerTallyTimes();
+    if (n_bases == 0) return;  // nothing to look at
+    Probe<> p(ix, seq, off, n, 5);  // valid, found, covered, sum, max
+    hu::DeviceArray<unsigned long long> d_per_window;
+    if (per_window) d_per_window.alloc(n_bases);
+    p.start();
+    // (one thread per run: every word of per_window is written)
+    if (p.wide) coverage_kernel<true><<<p.run_grid(), hu::EB, 0, p.st>>>(p.a, p.store.bad, n_bases, n, p.d_counts, t->count, d_per_window);
+    else coverage_kernel<false><<<p.run_grid(), hu::EB, 0, p.st>>>(p.a, p.store.bad, n_bases, n, p.d_counts, t->count, d_per_window);
+    HIP_CHECK(hipGetLastError());
+    p.ev.mark(1, p.st);
+    HIP_CHECK(hipStreamSynchronize(p.st));
+    const auto t0 = std::chrono::steady_clock::now();
+    p.download_counts(valid, found);
+    HIP_CHECK(hipStreamSynchronize(p.st));
+    hu::download_sliced(covered, p.d_counts + 2 * n, n * 8, p.st, p.device_id);
+    hu::download_sliced(sum, p.d_counts + 3 * n, n * 8, p.st, p.device_id);
+    hu::download_sliced(max, p.d_counts + 4 * n, n * 8, p.st, p.device_id);
     if (per_window) hu::download_sliced(per_window, d_per_window, n_bases * 8, p.st, p.device_id);
     if (times) {
         p.booked(&times->upload_ms, &times->pack_ms, &times->probe_ms);
