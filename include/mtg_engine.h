@@ -646,6 +646,22 @@ void mtg_kmer_runs_free(mtg_kmer_runs *runs);
 /* Of the last mtg_kmer_index_locate on this thread, in ms: {upload (host clock), pack, probe (with the fill of the hit array), runs
  * (flag, scan, emit)} -- HIP events around the kernels. */
 void mtg_last_kmer_locate_times(double out[4]);
+/* The same answer from the SPARSE index. A LOCATING tig index is built by the two functions below; beside what a
+ * plain one keeps it holds the smallest position of every class of its heavy buckets, 8 B per table slot, counted in
+ * info.device_bytes -- nothing more where no bucket is heavy. mtg_tig_index_query answers on it exactly as on a plain index.
+ * mtg_tig_index_locate is mtg_kmer_index_locate's contract, word for word, "the index" being the sequences the tig index was built
+ * from: for the same sequences, query and k the counts and the runs are field for field those of a locating mtg_kmer_index, for every
+ * m and bucket_limit. It dies if the index is not locating (build it with mtg_tig_index_build_locating). */
+mtg_tig_index *mtg_tig_index_build_locating(const char *seq, const uint64_t *off, uint64_t n, uint64_t k, uint64_t m,
+                                            uint64_t bucket_limit, int device_id);
+mtg_tig_index *mtg_tig_index_build_locating_store(const mtg_unitigs *store, uint64_t k, uint64_t m, uint64_t bucket_limit, int device_id);
+int mtg_tig_index_is_locating(const mtg_tig_index *ix);
+void mtg_tig_index_locate(const mtg_tig_index *ix, const char *seq, const uint64_t *off, uint64_t n,
+                          uint64_t *kmers, uint64_t *valid, uint64_t *found, /* [n] each */
+                          mtg_kmer_runs **out);                              /* mtg_kmer_runs_count / _arrays / _free */
+/* Of the last mtg_tig_index_locate on this thread, in ms: {upload (host clock), pack, probe (with the fill of the hit array), runs
+ * (flag, scan, emit)} -- HIP events around the kernels. */
+void mtg_last_tig_locate_times(double out[4]);
 /* HOW HEAVY the k-mers of a query are. A WEIGHTED index is built by the two functions below from the sequences and
  * one uint32 per window of them, in window order: a record shorter than k has no window, and the window at global position q of
  * record r has the ordinal (windows of the records before r) + (q - off[r]). n_weights must equal info.occurrences, else the call

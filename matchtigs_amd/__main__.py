@@ -17,6 +17,8 @@ other in an input record, on either strand, with both half-open base intervals (
 `--query-index minimizer` answers `--query-out` / `--query-presence-out` from a sparse minimizer index -- the packed bases plus one word
 per minimizer anchor (`--query-minimizer-length M`) instead of a table slot per k-mer --, and `--query-index-over greedytigs` /
 `eulertigs` indexes the tigs this run wrote instead of the input: the same answers from an index the size of the tigs.
+`--query-index-locate-out` (with `--query-index minimizer`) writes `--query-locate-out`'s rows from that sparse index, at the coordinates
+of whatever it indexes -- the input's records, or the records of the tig FASTA this run wrote.
 `--min-abundance N` (with `--seq-in`; not in the reference) keeps only the k-mers that at least N windows of the input show, on either
 strand -- sequencing reads, where a k-mer seen once is mostly an error -- before the unitigs are formed (DESIGN.md 19);
 `--kmer-spectrum-out` writes how many distinct k-mers have each abundance, `--unitig-abundance-out` the summed and mean abundance
@@ -134,6 +136,10 @@ def main(argv=None) -> int:
     ap.add_argument("--query-index", choices=("table", "minimizer"),
                     help="the index --query-fa asks: table (default; a slot per k-mer) or minimizer (the packed bases plus one word per "
                          "minimizer anchor: a fraction of the memory, the same answers; serves --query-out and --query-presence-out)")
+    ap.add_argument("--query-index-locate-out", metavar="PATH",
+                    help="with --query-index minimizer: --query-locate-out's TSV (.gz => gzip) from the sparse index; target is the 0-based "
+                         "record of what --query-index-over names (the input, or the tig FASTA this run wrote); needs --query-fa and "
+                         "--query-out")
     ap.add_argument("--query-minimizer-length", type=int, metavar="M",
                     help="with --query-index minimizer: the minimizer length, 1 .. min(k, 31) (default min(19, ceil(2k/3)))")
     ap.add_argument("--query-index-over", choices=("input", "greedytigs", "eulertigs"),
@@ -219,6 +225,13 @@ def main(argv=None) -> int:
         ap.error("--matchtigs-duplication-bitvector-out needs --matchtigs-fa-out or --matchtigs-gfa-out (bin.rs:955-957)")
     if args.query_locate_out and not (args.query_fa and args.query_out):
         ap.error("--query-locate-out needs --query-fa and --query-out")
+    if args.query_index_locate_out:
+        if not args.query_fa:
+            ap.error("--query-index-locate-out needs --query-fa")
+        if not args.query_out:
+            ap.error("--query-index-locate-out needs --query-out")
+        if args.query_index != "minimizer":
+            ap.error("--query-index-locate-out needs --query-index minimizer (the table index writes --query-locate-out)")
     if bool(args.query_fa) != bool(args.query_out):
         ap.error("--query-fa needs --query-out" if args.query_fa else "--query-out needs --query-fa")
     if args.query_presence_out and not args.query_fa:
@@ -733,7 +746,7 @@ def _write_color_matrix(args, colors) -> None:
 
 def _query(api, args, store, kmer_counts=None, fastq=(), colors=None, keep_index=False):
     """`--query-fa`: the input's k-mer set (the unitig store) indexed once; one TSV row and one presence line per query record, and
-    with `--query-locate-out` one row per run of located k-mers. kmer_counts (`--query-abundance-out`): the index is weighted with
+    with `--query-locate-out` (the sparse index: `--query-index-locate-out`) one row per run of located k-mers. kmer_counts (`--query-abundance-out`): the index is weighted with
     them, and one more TSV row, and with `--query-abundance-profile-out` one line of integers, per query record. colors
     (`--query-colors-out`): the index carries their masks, and one more TSV row per query record. keep_index: a table index over
     `store` is handed back open instead of closed (`--count-fa` counts on it); None if the queries asked another kind of index."""
@@ -753,7 +766,8 @@ def _query(api, args, store, kmer_counts=None, fastq=(), colors=None, keep_index
         if sparse or over != "input":  # (the same k-mer set, asked of another index or spelled by the tigs)
             indexed = store if over == "input" else api.read_sequences(args.greedytigs_fa_out if over == "greedytigs" else args.eulertigs_fa_out)
             if sparse:
-                index = stack.enter_context(api.TigIndex(indexed, args.k, args.query_minimizer_length, args.device))
+                index = stack.enter_context(api.TigIndex(indexed, args.k, args.query_minimizer_length, args.device,
+                                                         locate=bool(args.query_index_locate_out)))
             else:
                 index = stack.enter_context(api.KmerIndex(indexed, args.k, args.device))
         elif colors is not None:  # (the masks, and the counts too when abundances are asked for)
@@ -771,7 +785,8 @@ def _query(api, args, store, kmer_counts=None, fastq=(), colors=None, keep_index
             print(f"Indexing the {'input' if over == 'input' else over}: {line}", file=sys.stderr)
         tsv = stack.enter_context(writer(args.query_out, "t"))
         presence = stack.enter_context(writer(args.query_presence_out, "b")) if args.query_presence_out else None
-        located = stack.enter_context(writer(args.query_locate_out, "t")) if args.query_locate_out else None
+        locate_out = args.query_locate_out or args.query_index_locate_out  # (never both: the first is refused with the sparse index)
+        located = stack.enter_context(writer(locate_out, "t")) if locate_out else None
         weighed = stack.enter_context(writer(args.query_abundance_out, "t")) if kmer_counts is not None else None
         profile = stack.enter_context(writer(args.query_abundance_profile_out, "b")) if args.query_abundance_profile_out else None
         coloured = stack.enter_context(writer(args.query_colors_out, "t")) if colors is not None else None

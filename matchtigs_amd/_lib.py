@@ -344,6 +344,11 @@ def load():
         "mtg_kmer_runs_arrays": (None, [vp, P(vp), P(vp), P(vp), P(vp), P(vp), P(vp)]),
         "mtg_kmer_runs_free": (None, [vp]),
         "mtg_last_kmer_locate_times": (None, [P(C.c_double)]),
+        "mtg_tig_index_build_locating": (vp, [vp, vp, u64, u64, u64, u64, C.c_int]),
+        "mtg_tig_index_build_locating_store": (vp, [vp, u64, u64, u64, C.c_int]),
+        "mtg_tig_index_is_locating": (C.c_int, [vp]),
+        "mtg_tig_index_locate": (None, [vp, vp, vp, u64, vp, vp, vp, P(vp)]),
+        "mtg_last_tig_locate_times": (None, [P(C.c_double)]),
         "mtg_kmer_index_build_weighted": (vp, [vp, vp, u64, u64, vp, u64, C.c_int, C.c_int]),
         "mtg_kmer_index_build_weighted_store": (vp, [vp, u64, vp, u64, C.c_int, C.c_int]),
         "mtg_kmer_index_is_weighted": (C.c_int, [vp]),

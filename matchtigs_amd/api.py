@@ -1587,6 +1587,22 @@ def _window_count(seqs_or_store, k: int) -> int:
     return int(np.maximum(lengths - (k - 1), 0).sum())
 
 
+def _take_runs(L, h) -> np.ndarray:
+    """The runs of a mtg_kmer_runs handle as a KMER_RUN_DTYPE array of its own; the handle is freed."""
+    try:
+        count = int(L.mtg_kmer_runs_count(h))
+        runs = np.zeros(count, KMER_RUN_DTYPE)
+        if count:
+            ptrs = [C.c_void_p() for _ in range(6)]
+            L.mtg_kmer_runs_arrays(h, *(C.byref(p) for p in ptrs))
+            for name, p in zip(("q_record", "q_start", "kmers", "strand", "t_record", "t_start"), ptrs):
+                ctype = C.c_uint8 if name == "strand" else C.c_uint64
+                runs[name] = np.ctypeslib.as_array(C.cast(p, C.POINTER(ctype)), shape=(count,))
+    finally:
+        L.mtg_kmer_runs_free(h)
+    return runs
+
+
 class KmerIndex:
     """The canonical k-mers of a sequence set, kept on GPU `device_id` and asked which k-mers of other sequences they hold
     (mtg_kmer_index_*). seqs_or_store: UnitigStore, list of str, or (uint8 array, offsets); ACGT of either case only.
@@ -1685,18 +1701,7 @@ class KmerIndex:
         h = C.c_void_p()
         self._L.mtg_kmer_index_locate(self._h, d, o, n, _ptr(kmers), _ptr(valid), _ptr(found), C.byref(h))
         del keep
-        try:
-            count = int(self._L.mtg_kmer_runs_count(h))
-            runs = np.zeros(count, KMER_RUN_DTYPE)
-            if count:
-                ptrs = [C.c_void_p() for _ in range(6)]
-                self._L.mtg_kmer_runs_arrays(h, *(C.byref(p) for p in ptrs))
-                for name, p in zip(("q_record", "q_start", "kmers", "strand", "t_record", "t_start"), ptrs):
-                    ctype = C.c_uint8 if name == "strand" else C.c_uint64
-                    runs[name] = np.ctypeslib.as_array(C.cast(p, C.POINTER(ctype)), shape=(count,))
-        finally:
-            self._L.mtg_kmer_runs_free(h)
-        return KmerLocateResult(self.info.k, off, kmers, valid, found, runs)
+        return KmerLocateResult(self.info.k, off, kmers, valid, found, _take_runs(self._L, h))
 
     def abundance(self, seqs_or_store, per_window: bool = False) -> KmerAbundanceResult:
         """query()'s counts per record plus the sum, the smallest and the largest weight over the record's found windows
@@ -1857,20 +1862,26 @@ class TigIndex:
     of the sequences -- tigs index smaller than unitigs. query() answers exactly as KmerIndex.query does. seqs_or_store: UnitigStore,
     list of str, or (uint8 array, offsets); ACGT of either case only. m: the minimizer length, 1 .. min(k, 31) (None:
     default_minimizer_length(k)). bucket_limit: a directory bucket with more anchors sends its windows to a class table (None: 64).
-    The index holds device memory until close() (or its collection); release_device_memory leaves it intact."""
+    The index holds device memory until close() (or its collection); release_device_memory leaves it intact. locate=True (DESIGN.md
+    30): a LOCATING index, which also answers locate() exactly as KmerIndex(locate=True).locate does, at the coordinates of
+    seqs_or_store; it keeps 8 B per slot of the heavy buckets' table more, nothing more where no bucket is heavy."""
 
-    def __init__(self, seqs_or_store, k: int, m: Optional[int] = None, device_id: int = 0, bucket_limit: Optional[int] = None):
+    def __init__(self, seqs_or_store, k: int, m: Optional[int] = None, device_id: int = 0, bucket_limit: Optional[int] = None,
+                 locate: bool = False):
         self._h = None
         if m is not None and not 1 <= m <= min(k, 31):
             raise ValueError(f"m must be in 1..min(k, 31), not {m!r}")
         if bucket_limit is not None and not 1 <= bucket_limit <= 65536:
             raise ValueError(f"bucket_limit must be in 1..65536, not {bucket_limit!r}")
         self._L = _lib.load()
+        self.locating = bool(locate)
         if isinstance(seqs_or_store, UnitigStore):
-            self._h = self._L.mtg_tig_index_build_store(seqs_or_store.handle, k, m or 0, bucket_limit or 0, device_id)
+            build = self._L.mtg_tig_index_build_locating_store if locate else self._L.mtg_tig_index_build_store
+            self._h = build(seqs_or_store.handle, k, m or 0, bucket_limit or 0, device_id)
         else:
             d, o, n, keep = _sequence_arrays(seqs_or_store)
-            self._h = self._L.mtg_tig_index_build(d, o, n, k, m or 0, bucket_limit or 0, device_id)
+            build = self._L.mtg_tig_index_build_locating if locate else self._L.mtg_tig_index_build
+            self._h = build(d, o, n, k, m or 0, bucket_limit or 0, device_id)
             del keep
         out = _lib.MtgTigIndexInfo()
         self._L.mtg_tig_index_get_info(self._h, C.byref(out))
@@ -1903,6 +1914,30 @@ class TigIndex:
                                     _ptr(vb) if bits else None)
         del keep
         return KmerQueryResult(self.info.k, off, kmers, valid, found, vb, pb)
+
+    def locate(self, seqs_or_store) -> KmerLocateResult:
+        """KmerIndex.locate's answer: query()'s counts per record plus where the found windows lie in the indexed sequences, folded
+        into maximal collinear runs (KmerLocateResult). A k-mer that occurs several times in the index is reported at its smallest
+        position only. Needs an index built with locate=True."""
+        if not self._h:
+            raise ValueError("the index is closed")
+        if not self.locating:
+            raise ValueError("locate() needs an index built with locate=True")
+        d, o, n, keep = _sequence_arrays(seqs_or_store)
+        off = np.ctypeslib.as_array(C.cast(o, C.POINTER(C.c_uint64)), shape=(n + 1,)).copy()
+        kmers, valid, found = (np.zeros(n, np.uint64) for _ in range(3))
+        h = C.c_void_p()
+        self._L.mtg_tig_index_locate(self._h, d, o, n, _ptr(kmers), _ptr(valid), _ptr(found), C.byref(h))
+        del keep
+        return KmerLocateResult(self.info.k, off, kmers, valid, found, _take_runs(self._L, h))
+
+
+def last_tig_locate_times() -> dict:
+    """Phases of the last TigIndex.locate on this thread, in ms (HIP events around the kernels; the upload by the host clock): probe =
+    the lookup of every window with its position and strand (with the fill of the hit array), runs = folding the hits into runs."""
+    out = (C.c_double * 4)()
+    _lib.load().mtg_last_tig_locate_times(out)
+    return dict(zip(("upload_ms", "pack_ms", "probe_ms", "runs_ms"), list(out)))
 
 
 def last_tig_index_times() -> dict:

@@ -243,8 +243,13 @@ struct TigIndexTimes {
 struct TigIndex;
 uint64_t tig_index_default_m(uint64_t k);  // min(19, ceil(2 k / 3))
 TigIndex *device_tig_index_build(const char *seq, const uint64_t *off, uint64_t n, uint64_t k, uint64_t m, uint64_t bucket_limit, int device_id,
-                                 TigIndexTimes *times);
+                                 TigIndexTimes *times, bool locating = false);
 void device_tig_index_info(const TigIndex *ix, mtg_tig_index_info *out);
+// locating: the index also keeps the smallest window start of every class of its heavy buckets (8 B per table slot) and
+// answers device_tig_index_locate: device_kmer_index_locate's contract and results, at the coordinates of the sequences it was built from.
+bool device_tig_index_is_locating(const TigIndex *ix);
+void device_tig_index_locate(const TigIndex *ix, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid,
+                             uint64_t *found, KmerRuns *runs, KmerLocateTimes *times);
 void device_tig_index_query(const TigIndex *ix, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid,
                             uint64_t *found, uint64_t *present_bits, uint64_t *valid_bits, TigIndexTimes *times);
 void device_tig_index_free(TigIndex *ix);

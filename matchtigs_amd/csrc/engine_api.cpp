@@ -900,6 +900,32 @@ void mtg_tig_index_query(const mtg_tig_index *ix, const char *seq, const uint64_
     if (!ix) MTG_DIE("mtg_tig_index_query: null argument");
     device_tig_index_query(ix->ix, seq, off, n, kmers, valid, found, present_bits, valid_bits, &g_last_tig_index);
 }
+// ---- ... that also says where its k-mers are ----
+static thread_local KmerLocateTimes g_last_tig_locate;
+mtg_tig_index *mtg_tig_index_build_locating(const char *seq, const uint64_t *off, uint64_t n, uint64_t k, uint64_t m, uint64_t bucket_limit,
+                                            int device_id) {
+    return new mtg_tig_index{device_tig_index_build(seq, off, n, k, m, bucket_limit, device_id, &g_last_tig_index, true)};
+}
+mtg_tig_index *mtg_tig_index_build_locating_store(const mtg_unitigs *store, uint64_t k, uint64_t m, uint64_t bucket_limit, int device_id) {
+    if (!store) MTG_DIE("mtg_tig_index_build_locating_store: null argument");
+    const UnitigStore &s = *store->s;
+    return mtg_tig_index_build_locating(s.data.data(), s.off.data(), s.off.size() - 1, k, m, bucket_limit, device_id);
+}
+int mtg_tig_index_is_locating(const mtg_tig_index *ix) {
+    if (!ix) MTG_DIE("mtg_tig_index_is_locating: null argument");
+    return device_tig_index_is_locating(ix->ix) ? 1 : 0;
+}
+void mtg_tig_index_locate(const mtg_tig_index *ix, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid,
+                          uint64_t *found, mtg_kmer_runs **out) {
+    if (!ix || !out) MTG_DIE("mtg_tig_index_locate: null argument");
+    mtg_kmer_runs *runs = new mtg_kmer_runs();
+    device_tig_index_locate(ix->ix, seq, off, n, kmers, valid, found, &runs->r, &g_last_tig_locate);
+    *out = runs;
+}
+void mtg_last_tig_locate_times(double out[4]) {
+    const KmerLocateTimes &t = g_last_tig_locate;
+    out[0] = t.upload_ms; out[1] = t.pack_ms; out[2] = t.probe_ms; out[3] = t.runs_ms;
+}
 void mtg_tig_index_free(mtg_tig_index *ix) {
     if (!ix) return;
     device_tig_index_free(ix->ix);

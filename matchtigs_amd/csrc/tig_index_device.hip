@@ -30,6 +30,13 @@
 // Query: MaskedSeqStore, then tig_query_kernel: query_kernel's walk (64 window starts per thread, one plain store per bit-array word,
 // clear_from, one atomicAdd per (thread, record) and counter) with the lookup of tig_contains.
 //
+// Locate (a LOCATING index only, mtg_tig_index_build_locating): device_kmer_index_locate's contract and results at the
+// coordinates of the indexed sequences. Such an index also keeps heavy_where[table slots], the smallest window start of every class
+// of the heavy table (atomicMin behind the inserting heavy_kernel's find_slot); nothing more where no bucket is heavy. tig_locate_kernel
+// is tig_query_kernel's walk without the bit arrays; per found window hit[q] = (t << 1) | strand, t = tig_where -- the MINIMUM over all
+// candidates of the bucket that pass, or heavy_where[slot] -- and strand from one forward compare at t. From the hits to the runs:
+// kmer_runs_device.hpp, shared with the table index.
+//
 // Exactness. A hit is declared only after kw::same_class has compared the query's k bases with k index bases that lie inside ONE
 // record, or after the heavy table's exact `same`: never a false positive, and a tag or hash collision costs a compare. No false
 // negative: let the class of the query window x be the index window y at c. Both have the same set of m-mer classes, hence the same
@@ -47,6 +54,7 @@
 
 #include "device.hpp"
 #include "hip_util.hpp"
+#include "kmer_runs_device.hpp"
 #include "kmer_window_device.hpp"
 #include "pack_device.hpp"
 
@@ -54,6 +62,8 @@ namespace mtg {
 
 namespace {
 
+using kr::NO_HIT;
+using kr::record_of;
 using kw::EMPTY_SLOT;
 using kw::POS_LIMIT;
 using kw::RUN;
@@ -203,9 +213,13 @@ __device__ __forceinline__ kw::Found heavy_find(const TigArgs &a, const Window &
         return kw::same_class(a.packed, w.ident & POS_LIMIT, a.index_packed, cur & POS_LIMIT, a.k);
     });
 }
-// the windows whose minimizer's bucket is heavy: counted into *count, or (INSERT) put into the table
-template <bool WIDE, bool INSERT>
-__global__ __launch_bounds__(hu::EB) void heavy_kernel(TigArgs a, uint64_t n_bases, uint64_t n_rec, unsigned long long *count, unsigned int *err) {
+// the windows whose minimizer's bucket is heavy: counted into *count, or (INSERT) put into the table. LOCATE (a locating index; where
+// is not read otherwise): where is [a.slots], all ones before; where[slot of the class] = the smallest window start of the class -- a
+// claimed slot keeps its class, and the minimum over the occurrences of a class does not depend on the order they arrive in
+// (index_insert_kernel's argument). A template parameter, so that the plain build's kernel stays the one it was.
+template <bool WIDE, bool INSERT, bool LOCATE = false>
+__global__ __launch_bounds__(hu::EB) void heavy_kernel(TigArgs a, uint64_t n_bases, uint64_t n_rec, unsigned long long *count, unsigned int *err,
+                                                       unsigned long long *where) {
     const uint64_t p0 = hu::gid() * RUN;
     if (p0 >= n_bases) return;
     MinimizerWalk walk(a.packed, a.mn);
@@ -213,23 +227,16 @@ __global__ __launch_bounds__(hu::EB) void heavy_kernel(TigArgs a, uint64_t n_bas
     kw::for_each_window<WIDE>(a, p0, p0 + RUN < n_bases ? p0 + RUN : n_bases, 0, n_rec, [&](uint64_t q, uint64_t, const Window &w) {
         if (!(a.dir[walk.at(q).hash >> a.shift] & HEAVY)) return;
         if (!INSERT) n++;
-        else if (heavy_find<WIDE, true>(a, w).slot == a.slots) atomicOr(err, 1u);  // (2 slots per window: never full)
+        else {
+            const uint64_t slot = heavy_find<WIDE, true>(a, w).slot;
+            if (slot == a.slots) atomicOr(err, 1u);  // (2 slots per window: never full)
+            else if (LOCATE) atomicMin(&where[slot], (unsigned long long)q);
+        }
     });
     if (!INSERT && n) atomicAdd(count, (unsigned long long)n);
 }
 
 // ---- query ----
-// the last record that starts at or before x (n_rec >= 1)
-__device__ __forceinline__ uint64_t record_of(const unsigned long long *off, uint64_t n_rec, uint64_t x) {
-    uint64_t lo = 0, hi = n_rec;
-    while (hi - lo > 1) {
-        const uint64_t mid = lo + (hi - lo) / 2;
-        if (off[mid] <= x) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-
 // The window at q of a.packed (w: what it is to a table, mz: its minimizer) is a k-mer of the index: the header's lookup rule.
 // [lo, hi): the index record of the last anchor looked at (empty before the first). Neighbouring windows mostly hit the same record,
 // and the bounds of the record that holds p are a function of p, so keeping them only saves the binary search.
@@ -254,6 +261,44 @@ __device__ __forceinline__ bool tig_contains(const TigArgs &a, uint64_t q, const
         if (j_rev != j_fwd && p >= lo + j_rev && p - j_rev + a.k <= hi && kw::same_class(a.packed, q, a.index_packed, p - j_rev, a.k)) return true;
     }
     return false;
+}
+
+// tig_contains that says where: the smallest start of an index window, inside one record, of the class of the window
+// at q; NO_HIT if there is none. Heavy bucket: heavy_where[slot]. Light bucket: every occurrence of the class has its anchor among
+// the bucket's entries, so the candidates that pass the record bound and kw::same_class ARE the occurrences, and the answer is the
+// minimum over all of them -- not the first that passes: entries ascend by anchor p, but the two candidates p - j_fwd and p - j_rev
+// differ in their offsets, and an occurrence on the other strand can lie earlier in the text while its anchor lies later. A
+// candidate at or above the best so far is not compared, and once a best t is known an entry with p - max(j_fwd, j_rev) >= t ends
+// the scan: its candidates and those of every later entry are at or above t.
+template <bool WIDE>
+__device__ __forceinline__ uint64_t tig_where(const TigArgs &a, const unsigned long long *heavy_where, uint64_t q, const Window &w,
+                                              const Minimizer &mz, uint64_t &lo, uint64_t &hi) {
+    const uint64_t b = mz.hash >> a.shift;
+    const unsigned long long d = a.dir[b];
+    if (d & HEAVY) {
+        const uint64_t slot = heavy_find<WIDE, false>(a, w).slot;
+        return slot != a.slots ? heavy_where[slot] : NO_HIT;
+    }
+    const uint64_t end = a.dir[b + 1] & ~HEAVY, tag = mz.hash & TAG_MASK;
+    const uint64_t j_fwd = mz.first - q, j_rev = a.mn.w - 1 - (mz.last - q), j_max = j_fwd > j_rev ? j_fwd : j_rev;
+    uint64_t best = NO_HIT;
+    for (uint64_t i = d; i < end; i++) {
+        const unsigned long long e = a.entries[i];
+        const uint64_t p = e & POS_LIMIT;
+        if (best != NO_HIT && p >= best + j_max) break;
+        if ((e >> 40) != tag) continue;
+        if (p < lo || p >= hi) {  // a candidate counts only inside the record of p
+            const uint64_t r = record_of(a.index_off, a.index_rec, p);
+            lo = a.index_off[r];
+            hi = a.index_off[r + 1];
+        }
+        if (p >= lo + j_fwd && p - j_fwd < best && p - j_fwd + a.k <= hi && kw::same_class(a.packed, q, a.index_packed, p - j_fwd, a.k))
+            best = p - j_fwd;
+        if (j_rev != j_fwd && p >= lo + j_rev && p - j_rev < best && p - j_rev + a.k <= hi &&
+            kw::same_class(a.packed, q, a.index_packed, p - j_rev, a.k))
+            best = p - j_rev;
+    }
+    return best;
 }
 
 // one past the last base of [lo, hi) whose bit is set in `bad`; lo if there is none
@@ -311,6 +356,43 @@ __global__ __launch_bounds__(hu::EB) void tig_query_kernel(TigArgs a, const unsi
     if (present_bits) present_bits[gid] = pbits;
 }
 
+// tig_query_kernel's walk without the bit arrays; per found window at q: hit[q] = (t << 1) | strand, t = tig_where,
+// strand 0 iff the query's bases equal the index's at t one by one (kr::same_forward). hit: [n_bases], NO_HIT before; a thread is the
+// only writer of its RUN positions. heavy_where: [a.slots] (null if no bucket is heavy: never read then).
+template <bool WIDE>
+__global__ __launch_bounds__(hu::EB) void tig_locate_kernel(TigArgs a, const unsigned long long *bad, uint64_t n_bases, uint64_t n_rec,
+                                                            unsigned long long *counts, const unsigned long long *heavy_where,
+                                                            unsigned long long *hit) {
+    const uint64_t p0 = hu::gid() * RUN;
+    if (p0 >= n_bases) return;
+    uint64_t rec = ~0ull, next_q = ~0ull, clear_from = 0;
+    uint64_t idx_lo = 1, idx_hi = 0;    // tig_where's index record: none yet
+    uint32_t n_valid = 0, n_found = 0;  // (of the current record; at most RUN)
+    MinimizerWalk walk(a.packed, a.mn);
+    auto flush = [&]() {
+        if (n_valid) atomicAdd(&counts[rec], (unsigned long long)n_valid);
+        if (n_found) atomicAdd(&counts[n_rec + rec], (unsigned long long)n_found);
+        n_valid = n_found = 0;
+    };
+    kw::for_each_window<WIDE>(a, p0, p0 + RUN < n_bases ? p0 + RUN : n_bases, 0, n_rec, [&](uint64_t q, uint64_t r, const Window &w) {
+        const uint64_t last = q + a.k - 1;  // the window's last base
+        if (r != rec) {
+            flush();
+            rec = r;
+        }
+        if (q != next_q) clear_from = past_last_bad(bad, q, last);  // the walk jumped: what it knew lies behind q
+        next_q = q + 1;
+        if ((bad[last >> 6] >> (last & 63)) & 1) clear_from = last + 1;
+        if (clear_from > q) return;  // a bad base inside the window
+        n_valid++;
+        const uint64_t t = tig_where<WIDE>(a, heavy_where, q, w, walk.at(q), idx_lo, idx_hi);
+        if (t == NO_HIT) return;
+        n_found++;
+        hit[q] = (t << 1) | (kr::same_forward(a.packed, q, a.index_packed, t, a.k) ? 0ull : 1ull);
+    });
+    flush();
+}
+
 // offsets of one set: start at 0, do not decrease; returns its windows
 uint64_t check_offsets(const char *fn, const char *data, const uint64_t *off, uint64_t n, uint64_t k) {
     if (!off || (n && off[n] && !data)) MTG_DIE("%s: null argument", fn);
@@ -335,13 +417,15 @@ struct TigIndex {
     hu::DeviceArray<unsigned long long> dir;      // [info.buckets + 1]
     hu::DeviceArray<unsigned long long> entries;  // [info.anchors]
     hu::DeviceArray<unsigned long long> table;    // [info.table_slots]
+    bool locating = false;
+    hu::DeviceArray<unsigned long long> heavy_where;  // locating, and a bucket is heavy: [info.table_slots] the smallest window start of the slot's class
 };
 
 uint64_t tig_index_default_m(uint64_t k) { return std::min<uint64_t>(19, (2 * k + 2) / 3); }
 
 TigIndex *device_tig_index_build(const char *seq, const uint64_t *off, uint64_t n, uint64_t k, uint64_t m, uint64_t bucket_limit, int device_id,
-                                 TigIndexTimes *times) {
-    const char *fn = "mtg_tig_index_build";
+                                 TigIndexTimes *times, bool locating) {
+    const char *fn = locating ? "mtg_tig_index_build_locating" : "mtg_tig_index_build";
     if (k < 1) MTG_DIE("%s: k must be >= 1", fn);
     if (k > 0xFFFFFFFFull) MTG_DIE("%s: k too large", fn);
     if (m == 0) m = tig_index_default_m(k);
@@ -360,6 +444,7 @@ TigIndex *device_tig_index_build(const char *seq, const uint64_t *off, uint64_t 
     if (device_id < 0 || device_count() <= device_id) MTG_DIE("no HIP device %d for the tig index (there is no CPU path)", device_id);
     HIP_CHECK(hipSetDevice(device_id));
     ix->device_id = device_id;
+    ix->locating = locating;
     hipStream_t st = nullptr;
     const bool wide = k >= 32;
 
@@ -429,8 +514,8 @@ TigIndex *device_tig_index_build(const char *seq, const uint64_t *off, uint64_t 
 
     // the heavy table: every window whose minimizer's bucket is heavy
     if (info.heavy_buckets) {
-        if (wide) heavy_kernel<true, false><<<run_grid, hu::EB, 0, st>>>(a, store.n_bases, n, store.small.d + 3, store.small.err());
-        else heavy_kernel<false, false><<<run_grid, hu::EB, 0, st>>>(a, store.n_bases, n, store.small.d + 3, store.small.err());
+        if (wide) heavy_kernel<true, false><<<run_grid, hu::EB, 0, st>>>(a, store.n_bases, n, store.small.d + 3, store.small.err(), nullptr);
+        else heavy_kernel<false, false><<<run_grid, hu::EB, 0, st>>>(a, store.n_bases, n, store.small.d + 3, store.small.err(), nullptr);
         HIP_CHECK(hipGetLastError());
         store.small.read(st, "tig index");
         info.heavy_windows = store.small.h[3];
@@ -438,8 +523,17 @@ TigIndex *device_tig_index_build(const char *seq, const uint64_t *off, uint64_t 
         a.table = ix->table.alloc(info.table_slots);
         a.slots = info.table_slots;
         HIP_CHECK(hipMemsetAsync(ix->table, 0xFF, info.table_slots * 8, st));
-        if (wide) heavy_kernel<true, true><<<run_grid, hu::EB, 0, st>>>(a, store.n_bases, n, nullptr, store.small.err());
-        else heavy_kernel<false, true><<<run_grid, hu::EB, 0, st>>>(a, store.n_bases, n, nullptr, store.small.err());
+        if (locating) {
+            ix->heavy_where.alloc(info.table_slots);
+            HIP_CHECK(hipMemsetAsync(ix->heavy_where, 0xFF, info.table_slots * 8, st));
+        }
+        if (locating) {
+            if (wide) heavy_kernel<true, true, true><<<run_grid, hu::EB, 0, st>>>(a, store.n_bases, n, nullptr, store.small.err(), ix->heavy_where);
+            else heavy_kernel<false, true, true><<<run_grid, hu::EB, 0, st>>>(a, store.n_bases, n, nullptr, store.small.err(), ix->heavy_where);
+        } else {
+            if (wide) heavy_kernel<true, true><<<run_grid, hu::EB, 0, st>>>(a, store.n_bases, n, nullptr, store.small.err(), nullptr);
+            else heavy_kernel<false, true><<<run_grid, hu::EB, 0, st>>>(a, store.n_bases, n, nullptr, store.small.err(), nullptr);
+        }
         HIP_CHECK(hipGetLastError());
     }
     ev.mark(3, st);
@@ -454,10 +548,12 @@ TigIndex *device_tig_index_build(const char *seq, const uint64_t *off, uint64_t 
     ix->packed = store.take_packed();
     ix->off = store.take_off();
     info.device_bytes = (store.n_words + 2) * 4 + (n + 1) * 8 + (buckets + 1) * 8 + std::max<uint64_t>(info.anchors, 1) * 8 + info.table_slots * 8;
+    if (locating) info.device_bytes += info.table_slots * 8;  // heavy_where
     return ix;
 }
 
 void device_tig_index_info(const TigIndex *ix, mtg_tig_index_info *out) { *out = ix->info; }
+bool device_tig_index_is_locating(const TigIndex *ix) { return ix->locating; }
 
 void device_tig_index_free(TigIndex *ix) {
     if (!ix) return;
@@ -514,6 +610,56 @@ void device_tig_index_query(const TigIndex *ix, const char *seq, const uint64_t 
         times->query_upload_ms = store.upload_ms;
         times->query_pack_ms = store.pack_ms;
         times->query_probe_ms = ev.ms(0, 1);
+    }
+}
+
+void device_tig_index_locate(const TigIndex *ix, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid,
+                             uint64_t *found, KmerRuns *runs, KmerLocateTimes *times) {
+    const char *fn = "mtg_tig_index_locate";
+    if (!ix->locating) MTG_DIE("%s: the index keeps no positions of its heavy buckets (build it with mtg_tig_index_build_locating)", fn);
+    const uint64_t k = ix->info.k;
+    (void)check_offsets(fn, seq, off, n, k);
+    if (!runs || (n && (!kmers || !valid || !found))) MTG_DIE("%s: null argument", fn);
+    if (off[n] >= POS_LIMIT) MTG_DIE("%s: %llu bases; the limit is 2^40 - 2", fn, (unsigned long long)off[n]);
+    for (uint64_t r = 0; r < n; r++) {
+        const uint64_t len = off[r + 1] - off[r];
+        kmers[r] = len >= k ? len - k + 1 : 0;
+        valid[r] = found[r] = 0;
+    }
+    *runs = KmerRuns();
+    if (times) *times = KmerLocateTimes();
+    const uint64_t n_bases = off[n];
+    if (n_bases == 0) return;  // nothing to look at
+    HIP_CHECK(hipSetDevice(ix->device_id));
+    hipStream_t st = nullptr;
+    MaskedSeqStore store(seq, off, n, st, ix->device_id);
+    hu::DeviceArray<unsigned long long> d_counts(2 * n), d_hit(n_bases);
+    TigArgs a{};
+    a.packed = store.packed; a.off = store.off;
+    a.index_packed = ix->packed; a.index_off = ix->off; a.index_rec = ix->info.records;
+    a.dir = ix->dir; a.entries = ix->entries; a.shift = ix->shift; a.table = ix->table; a.slots = ix->info.table_slots;
+    a.mn = MinArgs{ix->info.m, k - ix->info.m + 1, 2 * (ix->info.m - 1), (1ull << (2 * ix->info.m)) - 1};
+    kw::window_args_set_k(a, k);
+    PhaseEvents<3> ev;
+    ev.mark(0, st);
+    HIP_CHECK(hipMemsetAsync(d_counts, 0, 2 * n * 8, st));
+    HIP_CHECK(hipMemsetAsync(d_hit, 0xFF, n_bases * 8, st));
+    const unsigned grid = hu::grid_for((n_bases + RUN - 1) / RUN);
+    if (k >= 32) tig_locate_kernel<true><<<grid, hu::EB, 0, st>>>(a, store.bad, n_bases, n, d_counts, ix->heavy_where.get(), d_hit);
+    else tig_locate_kernel<false><<<grid, hu::EB, 0, st>>>(a, store.bad, n_bases, n, d_counts, ix->heavy_where.get(), d_hit);
+    HIP_CHECK(hipGetLastError());
+    ev.mark(1, st);
+    const kr::RunArgs ra{d_hit, store.off, ix->off, n_bases, n, ix->info.records, k};
+    kr::runs_from_hits(ra, st, ix->device_id, runs, [&](hipStream_t) {
+        ev.mark(2, st);
+        HIP_CHECK(hipMemcpyAsync(valid, d_counts, n * 8, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(found, d_counts + n, n * 8, hipMemcpyDeviceToHost, st));
+    });
+    if (times) {
+        times->upload_ms = store.upload_ms;
+        times->pack_ms = store.pack_ms;
+        times->probe_ms = ev.ms(0, 1);
+        times->runs_ms = ev.ms(1, 2);
     }
 }
 
