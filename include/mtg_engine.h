@@ -743,6 +743,52 @@ void mtg_kmer_index_colors(const mtg_kmer_index *ix, const char *seq, const uint
 /* In ms: {the colour statistics kernel of the last mtg_compact_unitigs_colored on this thread (HIP events); of the last
  * mtg_kmer_index_colors: upload (host clock), pack, probe -- HIP events around the kernels --, download (host clock)}. */
 void mtg_last_kmer_color_times(double out[5]);
+/* The same two answers from the SPARSE index: payloads hung off text positions instead of table slots. weights and
+ * colors are exactly what mtg_kmer_index_build_annotated takes (either may be NULL; both NULL gives a plain locating index): one
+ * entry per window of the sequences, in window order; the counts must equal info.occurrences, 1 <= n_colors <= 64 and no mask may
+ * have a bit from n_colors on, else the call aborts. The index is built in the locating form (mtg_tig_index_is_locating = 1,
+ * mtg_tig_index_locate works) and keeps, beside it, the windows before every record (8 B per record) and each payload in one of
+ * two layouts: DENSE, one element per window of `width` bytes (weights: the narrowest of 1, 2, 4 that holds the largest weight;
+ * masks: the narrowest of 1, 2, 4, 8 that holds n_colors bits), width * windows bytes; or RUNS, the maximal runs of equal
+ * consecutive entries, (8 + 4) * runs bytes for weights and (8 + 8) * runs for masks. layout = 0: each payload takes the smaller,
+ * dense on a tie; 1: dense; 2: runs; anything else aborts. All of it is counted in info.device_bytes.
+ * mtg_tig_index_abundance / mtg_tig_index_colors are mtg_kmer_index_abundance's / mtg_kmer_index_colors' contracts, word for word:
+ * for the same sequences, payloads, query and k every output equals that of an annotated mtg_kmer_index, for every m, bucket_limit
+ * and layout -- the payload of a k-mer is that of the smallest window start of its class. They abort on an index without that
+ * payload. */
+mtg_tig_index *mtg_tig_index_build_annotated(const char *seq, const uint64_t *off, uint64_t n, uint64_t k, uint64_t m, uint64_t bucket_limit,
+                                             const uint32_t *weights, uint64_t n_weights, const uint64_t *colors, uint64_t n_color_words,
+                                             uint64_t n_colors, int layout, int device_id);
+mtg_tig_index *mtg_tig_index_build_annotated_store(const mtg_unitigs *store, uint64_t k, uint64_t m, uint64_t bucket_limit,
+                                                   const uint32_t *weights, uint64_t n_weights, const uint64_t *colors,
+                                                   uint64_t n_color_words, uint64_t n_colors, int layout, int device_id);
+int mtg_tig_index_is_weighted(const mtg_tig_index *ix);
+int mtg_tig_index_is_colored(const mtg_tig_index *ix);
+typedef struct mtg_tig_payload {
+    uint64_t layout;       /* 0: the index has no such payload; 1: dense; 2: runs */
+    uint64_t width;        /* bytes per element of the dense layout (reported for runs too: what dense would take) */
+    uint64_t windows;      /* entries given = info.occurrences */
+    uint64_t runs;         /* maximal runs of equal consecutive entries (counted for either layout) */
+    uint64_t device_bytes; /* dense: width * windows; runs: (8 + 4 or 8) * runs */
+} mtg_tig_payload;
+typedef struct mtg_tig_payload_info {
+    mtg_tig_payload weights, colors;
+    uint64_t n_colors;         /* 0: not coloured */
+    uint64_t win_offset_bytes; /* 8 * (records + 1) if there is a payload, else 0 */
+} mtg_tig_payload_info;
+void mtg_tig_index_get_payload_info(const mtg_tig_index *ix, mtg_tig_payload_info *out);
+void mtg_tig_index_abundance(const mtg_tig_index *ix, const char *seq, const uint64_t *off, uint64_t n,
+                             uint64_t *kmers, uint64_t *valid, uint64_t *found, /* [n] each */
+                             uint64_t *sum, uint32_t *min, uint32_t *max,       /* [n] each */
+                             uint32_t *per_window);                             /* nullable, [off[n]] */
+void mtg_tig_index_colors(const mtg_tig_index *ix, const char *seq, const uint64_t *off, uint64_t n,
+                          uint64_t *kmers, uint64_t *valid, uint64_t *found, /* [n] each */
+                          uint32_t *per_color,                               /* [n * n_colors] */
+                          uint64_t *per_window);                             /* nullable, [off[n]] */
+/* On this thread, in ms: of the last mtg_tig_index_build_annotated, the weights' {upload (host clock), reduce, flag + scan, compact or
+ * narrow} then the colours' same four (0 where there is no such payload); of the last mtg_tig_index_abundance or _colors: {upload
+ * (host clock), pack, probe (tig_locate_kernel with the fill of the hit array), gather} -- HIP events around the kernels. */
+void mtg_last_tig_payload_times(double out[12]);
 /* HOW OFTEN OTHER SEQUENCES SEE the indexed k-mers: the opposite question to the probes above. A TALLY belongs to one
  * index -- plain, locating, weighted or coloured --, which must outlive it and which it never changes. It holds one unsigned 64-bit
  * counter per table slot, all 0 at creation: 8 B per slot = 16 B per indexed window, taken from the device arena on the index's

@@ -19,6 +19,9 @@ per minimizer anchor (`--query-minimizer-length M`) instead of a table slot per 
 `eulertigs` indexes the tigs this run wrote instead of the input: the same answers from an index the size of the tigs.
 `--query-index-locate-out` (with `--query-index minimizer`) writes `--query-locate-out`'s rows from that sparse index, at the coordinates
 of whatever it indexes -- the input's records, or the records of the tig FASTA this run wrote.
+`--query-index-abundance-out` (with `--query-index-abundance-profile-out`) and `--query-index-colors-out` write `--query-abundance-out`'s,
+`--query-abundance-profile-out`'s and `--query-colors-out`'s files from that sparse index, byte for byte, whatever it indexes: the
+weights and masks hang off the positions of its text, one per window, dense or as runs of equal values.
 `--min-abundance N` (with `--seq-in`; not in the reference) keeps only the k-mers that at least N windows of the input show, on either
 strand -- sequencing reads, where a k-mer seen once is mostly an error -- before the unitigs are formed (DESIGN.md 19);
 `--kmer-spectrum-out` writes how many distinct k-mers have each abundance, `--unitig-abundance-out` the summed and mean abundance
@@ -140,6 +143,14 @@ def main(argv=None) -> int:
                     help="with --query-index minimizer: --query-locate-out's TSV (.gz => gzip) from the sparse index; target is the 0-based "
                          "record of what --query-index-over names (the input, or the tig FASTA this run wrote); needs --query-fa and "
                          "--query-out")
+    ap.add_argument("--query-index-abundance-out", metavar="PATH",
+                    help="with --query-index minimizer and --seq-in: --query-abundance-out's TSV (.gz => gzip) from the sparse index, over "
+                         "whatever --query-index-over names; needs --query-fa and --query-out")
+    ap.add_argument("--query-index-abundance-profile-out", metavar="PATH",
+                    help="with --query-index-abundance-out: --query-abundance-profile-out's lines (.gz => gzip) from the sparse index")
+    ap.add_argument("--query-index-colors-out", metavar="PATH",
+                    help="with --query-index minimizer and --seq-in: --query-colors-out's TSV (.gz => gzip) from the sparse index, over "
+                         "whatever --query-index-over names; needs --query-fa and --query-out")
     ap.add_argument("--query-minimizer-length", type=int, metavar="M",
                     help="with --query-index minimizer: the minimizer length, 1 .. min(k, 31) (default min(19, ceil(2k/3)))")
     ap.add_argument("--query-index-over", choices=("input", "greedytigs", "eulertigs"),
@@ -205,7 +216,7 @@ def main(argv=None) -> int:
     args = ap.parse_args(argv)
 
     classed = bool(args.monochromatic_unitigs or args.color_classes_out or args.unitig_color_classes_out)
-    colored = bool(args.color_matrix_out or args.unitig_colors_out or args.query_colors_out or classed)
+    colored = bool(args.color_matrix_out or args.unitig_colors_out or args.query_colors_out or args.query_index_colors_out or classed)
     if colored and args.seq_in is not None and len(args.seq_in) > MAX_COLORS:
         ap.error(f"{len(args.seq_in)} --seq-in files: at most {MAX_COLORS} files can be told apart as colours")
 
@@ -232,6 +243,20 @@ def main(argv=None) -> int:
             ap.error("--query-index-locate-out needs --query-out")
         if args.query_index != "minimizer":
             ap.error("--query-index-locate-out needs --query-index minimizer (the table index writes --query-locate-out)")
+    if args.query_index_abundance_profile_out and not args.query_index_abundance_out:
+        ap.error("--query-index-abundance-profile-out needs --query-index-abundance-out")
+    for flag, value, table_flag in (("--query-index-abundance-out", args.query_index_abundance_out, "--query-abundance-out"),
+                                    ("--query-index-colors-out", args.query_index_colors_out, "--query-colors-out")):
+        if not value:
+            continue
+        if not args.seq_in:
+            ap.error(f"{flag} needs --seq-in")
+        if not args.query_fa:
+            ap.error(f"{flag} needs --query-fa")
+        if not args.query_out:
+            ap.error(f"{flag} needs --query-out")
+        if args.query_index != "minimizer":
+            ap.error(f"{flag} needs --query-index minimizer (the table index writes {table_flag})")
     if bool(args.query_fa) != bool(args.query_out):
         ap.error("--query-fa needs --query-out" if args.query_fa else "--query-out needs --query-fa")
     if args.query_presence_out and not args.query_fa:
@@ -297,8 +322,8 @@ def main(argv=None) -> int:
         if args.bcalm_in is not None:
             ap.error("--min-component-kmers needs --seq-in or --fa-in")
         for flag, value in (("--color-matrix-out", args.color_matrix_out), ("--unitig-colors-out", args.unitig_colors_out),
-                            ("--query-colors-out", args.query_colors_out), ("--monochromatic-unitigs", args.monochromatic_unitigs or None),
-                            ("--color-classes-out", args.color_classes_out), ("--unitig-color-classes-out", args.unitig_color_classes_out)):
+                            ("--query-colors-out", args.query_colors_out), ("--query-index-colors-out", args.query_index_colors_out),
+                            ("--monochromatic-unitigs", args.monochromatic_unitigs or None), ("--color-classes-out", args.color_classes_out), ("--unitig-color-classes-out", args.unitig_color_classes_out)):
             if value is not None:
                 ap.error(f"--min-component-kmers cannot be combined with {flag}")
     for flag, value in (("--min-base-quality", args.min_base_quality), ("--query-min-base-quality", args.query_min_base_quality),
@@ -360,13 +385,13 @@ def _run(api, args, fastq) -> int:
         graph, store = api.read_bcalm2(args.bcalm_in, args.k)
     elif args.seq_in is not None:  # sequences -> unitigs (GPU compaction) -> graph (the --fa-in join on the same store)
         classed = bool(args.monochromatic_unitigs or args.color_classes_out or args.unitig_color_classes_out)  # 
-        colored = bool(args.color_matrix_out or args.unitig_colors_out or args.query_colors_out or classed)  # 
+        colored = bool(args.color_matrix_out or args.unitig_colors_out or args.query_colors_out or args.query_index_colors_out or classed)  # 
         record_colors = [] if colored else None
         seqs, pieces_cut = _read_seq_in(api, args, fastq, record_colors)
         abundance = colors = cleaning = None
         popping = args.pop_bubbles is not None  # 
         cleaned = args.clip_tips is not None or args.remove_isolated is not None or popping  # 
-        per_kmer = bool(args.query_abundance_out or args.unitig_kmer_abundance_out)  # 
+        per_kmer = bool(args.query_abundance_out or args.query_index_abundance_out or args.unitig_kmer_abundance_out)  # 
         counted = not (args.min_abundance is None and not (args.kmer_spectrum_out or args.unitig_abundance_out or per_kmer))
         if not counted and not colored and not cleaned:
             store, compaction = api.compact_unitigs(seqs, args.k, args.device)
@@ -542,8 +567,8 @@ def _run(api, args, fastq) -> int:
             all_equal &= report(f"{name} ({out or 'spelled in memory'})", r["verify_tigs"], r["verify"])
     table_index = None  # the plain-enough table index over the unitig store, if the queries built one: the count reuses it
     if args.query_fa:
-        table_index = _query(api, args, store, abundance.kmer_counts if args.query_abundance_out else None, fastq,
-                             colors if args.query_colors_out else None, keep_index=bool(args.count_fa))
+        table_index = _query(api, args, store, abundance.kmer_counts if args.query_abundance_out or args.query_index_abundance_out else None, fastq,
+                             colors if args.query_colors_out or args.query_index_colors_out else None, keep_index=bool(args.count_fa))
     if args.count_fa:
         _count(api, args, store, fastq, table_index)
     return 0 if all_equal else 1
@@ -744,12 +769,47 @@ def _write_color_matrix(args, colors) -> None:
     print(line, file=sys.stderr)
 
 
+def _tig_payloads(api, args, store, tigs, kmer_counts, colors, what):
+    """The per-window weights and masks of a tig file: a k-mer's abundance and mask are functions of the k-mer, so a
+    transient annotated table index over the unitig store is asked for every window of `tigs` (a UnitigStore), in slices of about
+    2^24 bases, and the answers are cut to window order. The table is closed on return: the build peak of this route is the
+    table's. Dies if a window of a tig is not a k-mer of the unitigs."""
+    import numpy as np
+
+    data, off = tigs.arrays()
+    off = np.asarray(off).astype(np.int64)
+    weights, masks = [], []
+    with api.KmerIndex(store, args.k, args.device, weights=kmer_counts, colors=None if colors is None else colors.kmer_colors,
+                       n_colors=None if colors is None else colors.n_colors) as table:
+        at = 0
+        while at < len(off) - 1:
+            end = max(at + 1, int(np.searchsorted(off, int(off[at]) + (1 << 24), side="right")) - 1)
+            piece = (np.ascontiguousarray(data[off[at]:off[end]]), (off[at:end + 1] - off[at]).astype(np.uint64))
+            answers = ([table.abundance(piece, per_window=True)] if kmer_counts is not None else []) + (
+                [table.color_hits(piece, per_window=True)] if colors is not None else [])
+            r = answers[0]
+            if not (np.array_equal(r.valid, r.kmers) and np.array_equal(r.found, r.kmers)):  # the tigs spell the unitigs' k-mers
+                bad = int(np.flatnonzero((r.valid != r.kmers) | (r.found != r.kmers))[0])
+                raise SystemExit(f"--query-index-over {what}: tig {at + bad} has {int(r.kmers[bad])} k-mers, of which the index over the "
+                                 f"unitigs finds {int(r.found[bad])} ({int(r.valid[bad])} valid): the tigs do not spell the unitigs' k-mers")
+            n = r.kmers.astype(np.int64)
+            rec = np.repeat(np.arange(at, end), n)
+            pos = (off[rec] - off[at]) + (np.arange(len(rec)) - np.repeat(np.cumsum(n) - n, n))  # the start of every window, in the piece
+            for out, answer in zip(([weights] if kmer_counts is not None else []) + ([masks] if colors is not None else []), answers):
+                out.append(answer.per_window[pos])
+            at = end
+    return (np.concatenate(weights) if weights else np.zeros(0, np.uint32) if kmer_counts is not None else None,
+            np.concatenate(masks) if masks else np.zeros(0, np.uint64) if colors is not None else None)
+
+
 def _query(api, args, store, kmer_counts=None, fastq=(), colors=None, keep_index=False):
     """`--query-fa`: the input's k-mer set (the unitig store) indexed once; one TSV row and one presence line per query record, and
     with `--query-locate-out` (the sparse index: `--query-index-locate-out`) one row per run of located k-mers. kmer_counts (`--query-abundance-out`): the index is weighted with
     them, and one more TSV row, and with `--query-abundance-profile-out` one line of integers, per query record. colors
     (`--query-colors-out`): the index carries their masks, and one more TSV row per query record. keep_index: a table index over
-    `store` is handed back open instead of closed (`--count-fa` counts on it); None if the queries asked another kind of index."""
+    `store` is handed back open instead of closed (`--count-fa` counts on it); None if the queries asked another kind of index.
+    With the sparse index (`--query-index-abundance-out`, `--query-index-colors-out`) the same two payloads hang off the
+    positions of whatever it indexes, and the same rows are written."""
     import contextlib
     import gzip
 
@@ -765,7 +825,12 @@ def _query(api, args, store, kmer_counts=None, fastq=(), colors=None, keep_index
         hold = (lambda ix: ix) if kept else stack.enter_context  # (a kept index is closed by the caller)
         if sparse or over != "input":  # (the same k-mer set, asked of another index or spelled by the tigs)
             indexed = store if over == "input" else api.read_sequences(args.greedytigs_fa_out if over == "greedytigs" else args.eulertigs_fa_out)
-            if sparse:
+            if sparse and (kmer_counts is not None or colors is not None):  # (payloads by position)
+                weights, masks = (kmer_counts, None if colors is None else colors.kmer_colors) if over == "input" else _tig_payloads(
+                    api, args, store, indexed, kmer_counts, colors, over)
+                index = stack.enter_context(api.TigIndex.annotated(indexed, args.k, args.query_minimizer_length, args.device, weights=weights,
+                                                                   colors=masks, n_colors=None if colors is None else colors.n_colors))
+            elif sparse:
                 index = stack.enter_context(api.TigIndex(indexed, args.k, args.query_minimizer_length, args.device,
                                                          locate=bool(args.query_index_locate_out)))
             else:
@@ -783,13 +848,20 @@ def _query(api, args, store, kmer_counts=None, fastq=(), colors=None, keep_index
                 f"table index: {i.characters} bases in {i.records} records, 0 anchors, 0 heavy buckets with 0 windows, {i.device_bytes} "
                 f"device bytes, {i.device_bytes / i.occurrences if i.occurrences else 0.0:.2f} bytes per k-mer window")
             print(f"Indexing the {'input' if over == 'input' else over}: {line}", file=sys.stderr)
+            for what, p in (getattr(index, "payload_info", None) or {}).items():
+                print(f"  {what} by position: {p['layout']}, {p['width']} B wide, {p['runs']} runs over {p['windows']} windows, "
+                      f"{p['device_bytes']} device bytes", file=sys.stderr)
         tsv = stack.enter_context(writer(args.query_out, "t"))
         presence = stack.enter_context(writer(args.query_presence_out, "b")) if args.query_presence_out else None
         locate_out = args.query_locate_out or args.query_index_locate_out  # (never both: the first is refused with the sparse index)
         located = stack.enter_context(writer(locate_out, "t")) if locate_out else None
-        weighed = stack.enter_context(writer(args.query_abundance_out, "t")) if kmer_counts is not None else None
-        profile = stack.enter_context(writer(args.query_abundance_profile_out, "b")) if args.query_abundance_profile_out else None
-        coloured = stack.enter_context(writer(args.query_colors_out, "t")) if colors is not None else None
+        # (the table's flag or the sparse index's, never both: the first is refused with the sparse index, the second without it)
+        abundance_out = args.query_abundance_out or args.query_index_abundance_out
+        profile_out = args.query_abundance_profile_out or args.query_index_abundance_profile_out
+        colors_out = args.query_colors_out or args.query_index_colors_out
+        weighed = stack.enter_context(writer(abundance_out, "t")) if kmer_counts is not None else None
+        profile = stack.enter_context(writer(profile_out, "b")) if profile_out else None
+        coloured = stack.enter_context(writer(colors_out, "t")) if colors is not None else None
         if coloured is not None:
             coloured.write("\t".join(["record", "kmers", "valid", "found"] + args.seq_in) + "\n")
         tsv.write("record\tlength\tkmers\tvalid\tfound\n")

@@ -168,6 +168,21 @@ class MtgTigIndexInfo(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class MtgTigPayload(C.Structure):
+    """mtg_tig_payload (include/mtg_engine.h): one payload of a tig index; layout 0: none, 1: dense, 2: runs."""
+
+    _fields_ = [(n, C.c_uint64) for n in ("layout", "width", "windows", "runs", "device_bytes")]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class MtgTigPayloadInfo(C.Structure):
+    """mtg_tig_payload_info (include/mtg_engine.h)."""
+
+    _fields_ = [("weights", MtgTigPayload), ("colors", MtgTigPayload), ("n_colors", C.c_uint64), ("win_offset_bytes", C.c_uint64)]
+
+
 class MtgComponentArrays(C.Structure):
     """mtg_component_arrays (include/mtg_engine.h): one array per field, one entry per component; each goes back through mtg_free."""
 
@@ -394,6 +409,14 @@ def load():
         "mtg_kmer_index_n_colors": (u64, [vp]),
         "mtg_kmer_index_colors": (None, [vp, vp, vp, u64, vp, vp, vp, vp, vp]),
         "mtg_last_kmer_color_times": (None, [P(C.c_double)]),
+        "mtg_tig_index_build_annotated": (vp, [vp, vp, u64, u64, u64, u64, vp, u64, vp, u64, u64, C.c_int, C.c_int]),
+        "mtg_tig_index_build_annotated_store": (vp, [vp, u64, u64, u64, vp, u64, vp, u64, u64, C.c_int, C.c_int]),
+        "mtg_tig_index_is_weighted": (C.c_int, [vp]),
+        "mtg_tig_index_is_colored": (C.c_int, [vp]),
+        "mtg_tig_index_get_payload_info": (None, [vp, P(MtgTigPayloadInfo)]),
+        "mtg_tig_index_abundance": (None, [vp, vp, vp, u64, vp, vp, vp, vp, vp, vp, vp]),
+        "mtg_tig_index_colors": (None, [vp, vp, vp, u64, vp, vp, vp, vp, vp]),
+        "mtg_last_tig_payload_times": (None, [P(C.c_double)]),
         "mtg_kmer_tally_create": (vp, [vp]),
         "mtg_kmer_tally_device_bytes": (u64, [vp]),
         "mtg_kmer_tally_add": (None, [vp, vp, vp, u64, vp, vp, vp]),

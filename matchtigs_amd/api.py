@@ -1603,6 +1603,31 @@ def _take_runs(L, h) -> np.ndarray:
     return runs
 
 
+def _payload_arrays(seqs_or_store, k: int, weights, colors, n_colors):
+    """The per-window payloads of an index as the library takes them (KmerIndex, TigIndex): weights as a uint32 array, colors as a
+    uint64 array, None for one not given; ValueError unless each holds one entry per window, n_colors is in 1..64 and no mask has
+    a bit beyond it."""
+    if colors is not None:
+        if isinstance(n_colors, bool) or not isinstance(n_colors, (int, np.integer)) or not 1 <= n_colors <= MAX_COLORS:
+            raise ValueError(f"n_colors must be in 1..{MAX_COLORS}, not {n_colors!r}")
+    elif n_colors is not None:
+        raise ValueError("n_colors needs colors")
+    c = w = None
+    if colors is not None or weights is not None:
+        windows = _window_count(seqs_or_store, k) if k >= 1 else -1
+    if colors is not None:
+        c = np.ascontiguousarray(colors, np.uint64)
+        if c.ndim != 1 or len(c) != windows:
+            raise ValueError(f"colors must hold one entry per window: {c.shape} for {windows} windows")
+        if n_colors < MAX_COLORS and len(c) and int(c.max()) >> int(n_colors):
+            raise ValueError(f"a mask has a colour beyond the {n_colors} given")
+    if weights is not None:
+        w = np.ascontiguousarray(weights, np.uint32)
+        if w.ndim != 1 or len(w) != windows:
+            raise ValueError(f"weights must hold one entry per window: {w.shape} for {windows} windows")
+    return w, c
+
+
 class KmerIndex:
     """The canonical k-mers of a sequence set, kept on GPU `device_id` and asked which k-mers of other sequences they hold
     (mtg_kmer_index_*). seqs_or_store: UnitigStore, list of str, or (uint8 array, offsets); ACGT of either case only.
@@ -1621,24 +1646,7 @@ class KmerIndex:
         self.weighted = weights is not None
         self.colored = colors is not None
         self.n_colors = 0
-        if self.colored:
-            if isinstance(n_colors, bool) or not isinstance(n_colors, (int, np.integer)) or not 1 <= n_colors <= MAX_COLORS:
-                raise ValueError(f"n_colors must be in 1..{MAX_COLORS}, not {n_colors!r}")
-        elif n_colors is not None:
-            raise ValueError("n_colors needs colors")
-        c = w = None
-        if self.colored or self.weighted:
-            windows = _window_count(seqs_or_store, k) if k >= 1 else -1
-        if self.colored:
-            c = np.ascontiguousarray(colors, np.uint64)
-            if c.ndim != 1 or len(c) != windows:
-                raise ValueError(f"colors must hold one entry per window: {c.shape} for {windows} windows")
-            if n_colors < MAX_COLORS and len(c) and int(c.max()) >> int(n_colors):
-                raise ValueError(f"a mask has a colour beyond the {n_colors} given")
-        if self.weighted:
-            w = np.ascontiguousarray(weights, np.uint32)
-            if w.ndim != 1 or len(w) != windows:
-                raise ValueError(f"weights must hold one entry per window: {w.shape} for {windows} windows")
+        w, c = _payload_arrays(seqs_or_store, k, weights, colors, n_colors)
         # one symbol (+ "_store" for a UnitigStore) and what it takes behind k, per kind of index
         if self.colored:
             build, payload = "mtg_kmer_index_build_annotated", (_ptr(w), len(w) if self.weighted else 0, _ptr(c), len(c), int(n_colors),
@@ -1864,28 +1872,70 @@ class TigIndex:
     default_minimizer_length(k)). bucket_limit: a directory bucket with more anchors sends its windows to a class table (None: 64).
     The index holds device memory until close() (or its collection); release_device_memory leaves it intact. locate=True (DESIGN.md
     30): a LOCATING index, which also answers locate() exactly as KmerIndex(locate=True).locate does, at the coordinates of
-    seqs_or_store; it keeps 8 B per slot of the heavy buckets' table more, nothing more where no bucket is heavy."""
+    seqs_or_store; it keeps 8 B per slot of the heavy buckets' table more, nothing more where no bucket is heavy.
+    TigIndex.annotated(..., weights=, colors=, n_colors=, payload_layout=): weights / colors with n_colors are
+    exactly what KmerIndex takes, one entry per window in window order; the index is then locating and also answers abundance() /
+    color_hits() exactly as the annotated KmerIndex does -- the payload of a k-mer is that of its first occurrence. Each payload is
+    kept per window of the text, dense or as runs of equal entries, whichever is smaller (a tie is dense; payload_layout "dense" or
+    "runs" forces one): see payload_info ({"weights": {...}, "colors": {...}}, each with layout, width, windows, runs,
+    device_bytes; {} on an index without payloads)."""
+
+    _LAYOUTS = {None: 0, "dense": 1, "runs": 2}
 
     def __init__(self, seqs_or_store, k: int, m: Optional[int] = None, device_id: int = 0, bucket_limit: Optional[int] = None,
                  locate: bool = False):
+        self._build(seqs_or_store, k, m, device_id, bucket_limit, locate)
+
+    @classmethod
+    def annotated(cls, seqs_or_store, k: int, m: Optional[int] = None, device_id: int = 0, bucket_limit: Optional[int] = None,
+                  weights=None, colors=None, n_colors=None, payload_layout: Optional[str] = None) -> "TigIndex":
+        """A locating index with weights, colours, both or neither (see the class). The ValueErrors are KmerIndex's, raised before
+        the library is asked."""
+        ix = cls.__new__(cls)
+        ix._build(seqs_or_store, k, m, device_id, bucket_limit, True, weights, colors, n_colors, payload_layout)
+        return ix
+
+    def _build(self, seqs_or_store, k, m, device_id, bucket_limit, locate, weights=None, colors=None, n_colors=None, payload_layout=None):
         self._h = None
+        self.weighted = weights is not None
+        self.colored = colors is not None
+        self.n_colors = 0
+        self.payload_info = {}
         if m is not None and not 1 <= m <= min(k, 31):
             raise ValueError(f"m must be in 1..min(k, 31), not {m!r}")
         if bucket_limit is not None and not 1 <= bucket_limit <= 65536:
             raise ValueError(f"bucket_limit must be in 1..65536, not {bucket_limit!r}")
+        if payload_layout not in self._LAYOUTS:
+            raise ValueError(f"payload_layout must be None, 'dense' or 'runs', not {payload_layout!r}")
+        if payload_layout is not None and not (self.weighted or self.colored):
+            raise ValueError("payload_layout needs weights or colors")
+        w, c = _payload_arrays(seqs_or_store, k, weights, colors, n_colors)
         self._L = _lib.load()
-        self.locating = bool(locate)
+        annotated = self.weighted or self.colored
+        self.locating = bool(locate) or annotated
+        if annotated:
+            build = "mtg_tig_index_build_annotated"
+            payload = (_ptr(w) if self.weighted else None, len(w) if self.weighted else 0, _ptr(c) if self.colored else None,
+                       len(c) if self.colored else 0, int(n_colors) if self.colored else 0, self._LAYOUTS[payload_layout], device_id)
+        else:
+            build, payload = "mtg_tig_index_build_locating" if locate else "mtg_tig_index_build", (device_id,)
         if isinstance(seqs_or_store, UnitigStore):
-            build = self._L.mtg_tig_index_build_locating_store if locate else self._L.mtg_tig_index_build_store
-            self._h = build(seqs_or_store.handle, k, m or 0, bucket_limit or 0, device_id)
+            self._h = getattr(self._L, build + "_store")(seqs_or_store.handle, k, m or 0, bucket_limit or 0, *payload)
         else:
             d, o, n, keep = _sequence_arrays(seqs_or_store)
-            build = self._L.mtg_tig_index_build_locating if locate else self._L.mtg_tig_index_build
-            self._h = build(d, o, n, k, m or 0, bucket_limit or 0, device_id)
+            self._h = getattr(self._L, build)(d, o, n, k, m or 0, bucket_limit or 0, *payload)
             del keep
         out = _lib.MtgTigIndexInfo()
         self._L.mtg_tig_index_get_info(self._h, C.byref(out))
         self.info = TigIndexInfo(**out.as_dict())
+        if annotated:
+            pi = _lib.MtgTigPayloadInfo()
+            self._L.mtg_tig_index_get_payload_info(self._h, C.byref(pi))
+            names = {1: "dense", 2: "runs"}
+            for key, one in (("weights", pi.weights), ("colors", pi.colors)):
+                if one.layout:
+                    self.payload_info[key] = dict(one.as_dict(), layout=names[int(one.layout)])
+            self.n_colors = int(pi.n_colors)
 
     def close(self) -> None:
         h, self._h = getattr(self, "_h", None), None
@@ -1930,6 +1980,40 @@ class TigIndex:
         self._L.mtg_tig_index_locate(self._h, d, o, n, _ptr(kmers), _ptr(valid), _ptr(found), C.byref(h))
         del keep
         return KmerLocateResult(self.info.k, off, kmers, valid, found, _take_runs(self._L, h))
+
+    _probe_inputs = KmerIndex._probe_inputs  # (the same checks in the same order: closed first, then the missing payload)
+
+    def abundance(self, seqs_or_store, per_window: bool = False) -> KmerAbundanceResult:
+        """KmerIndex.abundance's answer: query()'s counts per record plus the sum, the smallest and the largest weight
+        over the record's found windows; per_window: also the weight at every window start. Needs an index built with weights."""
+        d, o, n, keep, off, kmers, valid, found = self._probe_inputs(seqs_or_store, self.weighted, "abundance() needs an index built with weights")
+        total, lo, hi = np.zeros(n, np.uint64), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        pw = np.zeros(int(off[n]), np.uint32) if per_window else None
+        self._L.mtg_tig_index_abundance(self._h, d, o, n, _ptr(kmers), _ptr(valid), _ptr(found), _ptr(total), _ptr(lo), _ptr(hi),
+                                        _ptr(pw) if per_window else None)
+        del keep
+        return KmerAbundanceResult(self.info.k, off, kmers, valid, found, total, lo, hi, pw)
+
+    def color_hits(self, seqs_or_store, per_window: bool = False) -> KmerColorResult:
+        """KmerIndex.color_hits' answer: query()'s counts per record plus, per record and colour, the found windows
+        whose k-mer that colour carries; per_window: also the mask at every window start. Needs an index built with colors."""
+        d, o, n, keep, off, kmers, valid, found = self._probe_inputs(seqs_or_store, self.colored, "color_hits() needs an index built with colors")
+        per_color = np.zeros((n, self.n_colors), np.uint32)
+        pw = np.zeros(int(off[n]), np.uint64) if per_window else None
+        self._L.mtg_tig_index_colors(self._h, d, o, n, _ptr(kmers), _ptr(valid), _ptr(found), _ptr(per_color), _ptr(pw) if per_window else None)
+        del keep
+        return KmerColorResult(self.info.k, off, kmers, valid, found, per_color, pw)
+
+
+def last_tig_payload_times() -> dict:
+    """Phases on this thread, in ms (HIP events around the kernels; uploads by the host clock): of the last annotated TigIndex build,
+    per payload the upload, the max-reduction, flag + scan and the compaction or the narrowing copy; of the last TigIndex.abundance
+    or .color_hits the upload, the pack, the probe (the locate pass with the fill of the hit array) and the gather."""
+    out = (C.c_double * 12)()
+    _lib.load().mtg_last_tig_payload_times(out)
+    phases = ("upload_ms", "reduce_ms", "flag_scan_ms", "store_ms")
+    return {"weights": dict(zip(phases, out[0:4])), "colors": dict(zip(phases, out[4:8])),
+            **dict(zip(("upload_ms", "pack_ms", "probe_ms", "gather_ms"), out[8:12]))}
 
 
 def last_tig_locate_times() -> dict:

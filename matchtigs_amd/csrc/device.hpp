@@ -243,7 +243,7 @@ struct TigIndexTimes {
 struct TigIndex;
 uint64_t tig_index_default_m(uint64_t k);  // min(19, ceil(2 k / 3))
 TigIndex *device_tig_index_build(const char *seq, const uint64_t *off, uint64_t n, uint64_t k, uint64_t m, uint64_t bucket_limit, int device_id,
-                                 TigIndexTimes *times, bool locating = false);
+                                 TigIndexTimes *times, bool locating = false, const char *fn = nullptr);
 void device_tig_index_info(const TigIndex *ix, mtg_tig_index_info *out);
 // locating: the index also keeps the smallest window start of every class of its heavy buckets (8 B per table slot) and
 // answers device_tig_index_locate: device_kmer_index_locate's contract and results, at the coordinates of the sequences it was built from.
@@ -252,6 +252,22 @@ void device_tig_index_locate(const TigIndex *ix, const char *seq, const uint64_t
                              uint64_t *found, KmerRuns *runs, KmerLocateTimes *times);
 void device_tig_index_query(const TigIndex *ix, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid,
                             uint64_t *found, uint64_t *present_bits, uint64_t *valid_bits, TigIndexTimes *times);
+// payloads by position (tig_payload_device.hpp): a locating index that also keeps one weight and / or one colour mask
+// per window of its sequences (KmerWeights / KmerColors as device_kmer_index_build takes them; layout 0: each payload takes the
+// smaller of dense and runs, 1: dense, 2: runs) and answers device_kmer_index_abundance's / _colors' contracts with their results.
+// times: build {upload, reduce, flag + scan, compact or narrow} per payload; call {upload, pack, probe, gather}.
+struct TigPayloadTimes {
+    double weights_ms[4] = {0, 0, 0, 0}, colors_ms[4] = {0, 0, 0, 0};
+    double upload_ms = 0, pack_ms = 0, probe_ms = 0, gather_ms = 0;
+};
+TigIndex *device_tig_index_build_annotated(const char *seq, const uint64_t *off, uint64_t n, uint64_t k, uint64_t m, uint64_t bucket_limit,
+                                           const KmerWeights *weights, const KmerColors *colors, int layout, int device_id, TigIndexTimes *times,
+                                           TigPayloadTimes *payload_times);
+void device_tig_index_payload_info(const TigIndex *ix, mtg_tig_payload_info *out);
+void device_tig_index_abundance(const TigIndex *ix, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid,
+                                uint64_t *found, uint64_t *sum, uint32_t *min, uint32_t *max, uint32_t *per_window, TigPayloadTimes *times);
+void device_tig_index_colors(const TigIndex *ix, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid,
+                             uint64_t *found, uint32_t *per_color, uint64_t *per_window, TigPayloadTimes *times);
 void device_tig_index_free(TigIndex *ix);
 // compact_device.hip: the maximal unitigs of the k-mer set of arbitrary sequences (the file's header and DESIGN.md 16 state the
 // contract), as an ordinary sequence store. times: host wall clock of upload, download and the whole call, HIP-event time of the

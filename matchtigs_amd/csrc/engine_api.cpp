@@ -926,6 +926,60 @@ void mtg_last_tig_locate_times(double out[4]) {
     const KmerLocateTimes &t = g_last_tig_locate;
     out[0] = t.upload_ms; out[1] = t.pack_ms; out[2] = t.probe_ms; out[3] = t.runs_ms;
 }
+// ---- ... and how heavy they are and which inputs carry them: payloads by position ----
+static thread_local TigPayloadTimes g_last_tig_payload;
+mtg_tig_index *mtg_tig_index_build_annotated(const char *seq, const uint64_t *off, uint64_t n, uint64_t k, uint64_t m, uint64_t bucket_limit,
+                                             const uint32_t *weights, uint64_t n_weights, const uint64_t *colors, uint64_t n_color_words,
+                                             uint64_t n_colors, int layout, int device_id) {
+    if (!weights && n_weights) MTG_DIE("mtg_tig_index_build_annotated: %llu weights but no array", (unsigned long long)n_weights);
+    if (!colors && n_color_words) MTG_DIE("mtg_tig_index_build_annotated: %llu colour words but no array", (unsigned long long)n_color_words);
+    const KmerWeights w{weights, n_weights};
+    const KmerColors c{colors, n_color_words, n_colors};
+    return new mtg_tig_index{device_tig_index_build_annotated(seq, off, n, k, m, bucket_limit, weights ? &w : nullptr, colors ? &c : nullptr, layout,
+                                                              device_id, &g_last_tig_index, &g_last_tig_payload)};
+}
+mtg_tig_index *mtg_tig_index_build_annotated_store(const mtg_unitigs *store, uint64_t k, uint64_t m, uint64_t bucket_limit,
+                                                   const uint32_t *weights, uint64_t n_weights, const uint64_t *colors,
+                                                   uint64_t n_color_words, uint64_t n_colors, int layout, int device_id) {
+    if (!store) MTG_DIE("mtg_tig_index_build_annotated_store: null argument");
+    const UnitigStore &s = *store->s;
+    return mtg_tig_index_build_annotated(s.data.data(), s.off.data(), s.off.size() - 1, k, m, bucket_limit, weights, n_weights, colors,
+                                         n_color_words, n_colors, layout, device_id);
+}
+void mtg_tig_index_get_payload_info(const mtg_tig_index *ix, mtg_tig_payload_info *out) {
+    if (!ix || !out) MTG_DIE("mtg_tig_index_get_payload_info: null argument");
+    device_tig_index_payload_info(ix->ix, out);
+}
+int mtg_tig_index_is_weighted(const mtg_tig_index *ix) {
+    if (!ix) MTG_DIE("mtg_tig_index_is_weighted: null argument");
+    mtg_tig_payload_info info;
+    device_tig_index_payload_info(ix->ix, &info);
+    return info.weights.layout ? 1 : 0;
+}
+int mtg_tig_index_is_colored(const mtg_tig_index *ix) {
+    if (!ix) MTG_DIE("mtg_tig_index_is_colored: null argument");
+    mtg_tig_payload_info info;
+    device_tig_index_payload_info(ix->ix, &info);
+    return info.colors.layout ? 1 : 0;
+}
+void mtg_tig_index_abundance(const mtg_tig_index *ix, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid,
+                             uint64_t *found, uint64_t *sum, uint32_t *min, uint32_t *max, uint32_t *per_window) {
+    if (!ix) MTG_DIE("mtg_tig_index_abundance: null argument");
+    device_tig_index_abundance(ix->ix, seq, off, n, kmers, valid, found, sum, min, max, per_window, &g_last_tig_payload);
+}
+void mtg_tig_index_colors(const mtg_tig_index *ix, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid,
+                          uint64_t *found, uint32_t *per_color, uint64_t *per_window) {
+    if (!ix) MTG_DIE("mtg_tig_index_colors: null argument");
+    device_tig_index_colors(ix->ix, seq, off, n, kmers, valid, found, per_color, per_window, &g_last_tig_payload);
+}
+void mtg_last_tig_payload_times(double out[12]) {
+    const TigPayloadTimes &t = g_last_tig_payload;
+    for (int i = 0; i < 4; i++) {
+        out[i] = t.weights_ms[i];
+        out[4 + i] = t.colors_ms[i];
+    }
+    out[8] = t.upload_ms; out[9] = t.pack_ms; out[10] = t.probe_ms; out[11] = t.gather_ms;
+}
 void mtg_tig_index_free(mtg_tig_index *ix) {
     if (!ix) return;
     device_tig_index_free(ix->ix);

@@ -37,6 +37,10 @@
 // candidates of the bucket that pass, or heavy_where[slot] -- and strand from one forward compare at t. From the hits to the runs:
 // kmer_runs_device.hpp, shared with the table index.
 //
+// Payloads (mtg_tig_index_build_annotated): a locating index that also keeps win_off[records + 1] and one weight and / or
+// one colour mask per window of the text, dense or as runs (tig_payload_device.hpp). t above is the position whose payload the table
+// index keeps for the class, so abundance and colours are two passes: tig_locate_kernel, unchanged, then a gather over hit[].
+//
 // Exactness. A hit is declared only after kw::same_class has compared the query's k bases with k index bases that lie inside ONE
 // record, or after the heavy table's exact `same`: never a false positive, and a tag or hash collision costs a compare. No false
 // negative: let the class of the query window x be the index window y at c. Both have the same set of m-mer classes, hence the same
@@ -57,6 +61,7 @@
 #include "kmer_runs_device.hpp"
 #include "kmer_window_device.hpp"
 #include "pack_device.hpp"
+#include "tig_payload_device.hpp"
 
 namespace mtg {
 
@@ -419,13 +424,18 @@ struct TigIndex {
     hu::DeviceArray<unsigned long long> table;    // [info.table_slots]
     bool locating = false;
     hu::DeviceArray<unsigned long long> heavy_where;  // locating, and a bucket is heavy: [info.table_slots] the smallest window start of the slot's class
+    // payloads by position: none unless built annotated
+    hu::DeviceArray<unsigned long long> win_off;  // [info.records + 1] the windows of the records before
+    tp::Payload<uint32_t> weights;
+    tp::Payload<unsigned long long> colors;
+    uint64_t n_colors = 0;
 };
 
 uint64_t tig_index_default_m(uint64_t k) { return std::min<uint64_t>(19, (2 * k + 2) / 3); }
 
 TigIndex *device_tig_index_build(const char *seq, const uint64_t *off, uint64_t n, uint64_t k, uint64_t m, uint64_t bucket_limit, int device_id,
-                                 TigIndexTimes *times, bool locating) {
-    const char *fn = locating ? "mtg_tig_index_build_locating" : "mtg_tig_index_build";
+                                 TigIndexTimes *times, bool locating, const char *fn) {
+    if (!fn) fn = locating ? "mtg_tig_index_build_locating" : "mtg_tig_index_build";
     if (k < 1) MTG_DIE("%s: k must be >= 1", fn);
     if (k > 0xFFFFFFFFull) MTG_DIE("%s: k too large", fn);
     if (m == 0) m = tig_index_default_m(k);
@@ -613,54 +623,227 @@ void device_tig_index_query(const TigIndex *ix, const char *seq, const uint64_t 
     }
 }
 
-void device_tig_index_locate(const TigIndex *ix, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid,
-                             uint64_t *found, KmerRuns *runs, KmerLocateTimes *times) {
-    const char *fn = "mtg_tig_index_locate";
-    if (!ix->locating) MTG_DIE("%s: the index keeps no positions of its heavy buckets (build it with mtg_tig_index_build_locating)", fn);
+namespace {
+
+// What the calls on a locating index share (locate, abundance, colors): the checks of the query, kmers[] filled, valid[] and found[]
+// zeroed; returns the query's bases (missing: an out-pointer of the caller's own is null). All on the host.
+uint64_t locate_windows(const char *fn, const TigIndex *ix, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid,
+                        uint64_t *found, bool missing) {
     const uint64_t k = ix->info.k;
     (void)check_offsets(fn, seq, off, n, k);
-    if (!runs || (n && (!kmers || !valid || !found))) MTG_DIE("%s: null argument", fn);
+    if (missing || (n && (!kmers || !valid || !found))) MTG_DIE("%s: null argument", fn);
     if (off[n] >= POS_LIMIT) MTG_DIE("%s: %llu bases; the limit is 2^40 - 2", fn, (unsigned long long)off[n]);
     for (uint64_t r = 0; r < n; r++) {
         const uint64_t len = off[r + 1] - off[r];
         kmers[r] = len >= k ? len - k + 1 : 0;
         valid[r] = found[r] = 0;
     }
-    *runs = KmerRuns();
-    if (times) *times = KmerLocateTimes();
-    const uint64_t n_bases = off[n];
-    if (n_bases == 0) return;  // nothing to look at
-    HIP_CHECK(hipSetDevice(ix->device_id));
+    return off[n];
+}
+
+int on_device(int device_id) {
+    HIP_CHECK(hipSetDevice(device_id));
+    return device_id;
+}
+
+// ... and the first pass of a query that has bases: the query on the index's device and tig_locate_kernel between the marks 0 and 1
+// of ev; d_counts: [2 n] valid then found, d_hit: [n_bases]. The caller queues its second pass and marks 2.
+struct LocateProbe {
+    const uint64_t n;
+    const int device_id;
     hipStream_t st = nullptr;
-    MaskedSeqStore store(seq, off, n, st, ix->device_id);
-    hu::DeviceArray<unsigned long long> d_counts(2 * n), d_hit(n_bases);
-    TigArgs a{};
-    a.packed = store.packed; a.off = store.off;
-    a.index_packed = ix->packed; a.index_off = ix->off; a.index_rec = ix->info.records;
-    a.dir = ix->dir; a.entries = ix->entries; a.shift = ix->shift; a.table = ix->table; a.slots = ix->info.table_slots;
-    a.mn = MinArgs{ix->info.m, k - ix->info.m + 1, 2 * (ix->info.m - 1), (1ull << (2 * ix->info.m)) - 1};
-    kw::window_args_set_k(a, k);
+    MaskedSeqStore store;
+    hu::DeviceArray<unsigned long long> d_counts, d_hit;
     PhaseEvents<3> ev;
-    ev.mark(0, st);
-    HIP_CHECK(hipMemsetAsync(d_counts, 0, 2 * n * 8, st));
-    HIP_CHECK(hipMemsetAsync(d_hit, 0xFF, n_bases * 8, st));
-    const unsigned grid = hu::grid_for((n_bases + RUN - 1) / RUN);
-    if (k >= 32) tig_locate_kernel<true><<<grid, hu::EB, 0, st>>>(a, store.bad, n_bases, n, d_counts, ix->heavy_where.get(), d_hit);
-    else tig_locate_kernel<false><<<grid, hu::EB, 0, st>>>(a, store.bad, n_bases, n, d_counts, ix->heavy_where.get(), d_hit);
-    HIP_CHECK(hipGetLastError());
-    ev.mark(1, st);
-    const kr::RunArgs ra{d_hit, store.off, ix->off, n_bases, n, ix->info.records, k};
-    kr::runs_from_hits(ra, st, ix->device_id, runs, [&](hipStream_t) {
-        ev.mark(2, st);
+
+    LocateProbe(const TigIndex *ix, const char *seq, const uint64_t *off, uint64_t n)
+        : n(n), device_id(on_device(ix->device_id)), store(seq, off, n, st, device_id), d_counts(2 * n), d_hit(store.n_bases) {
+        const uint64_t k = ix->info.k, n_bases = store.n_bases;
+        TigArgs a{};
+        a.packed = store.packed; a.off = store.off;
+        a.index_packed = ix->packed; a.index_off = ix->off; a.index_rec = ix->info.records;
+        a.dir = ix->dir; a.entries = ix->entries; a.shift = ix->shift; a.table = ix->table; a.slots = ix->info.table_slots;
+        a.mn = MinArgs{ix->info.m, k - ix->info.m + 1, 2 * (ix->info.m - 1), (1ull << (2 * ix->info.m)) - 1};
+        kw::window_args_set_k(a, k);
+        ev.mark(0, st);
+        HIP_CHECK(hipMemsetAsync(d_counts, 0, 2 * n * 8, st));
+        HIP_CHECK(hipMemsetAsync(d_hit, 0xFF, n_bases * 8, st));
+        const unsigned grid = hu::grid_for((n_bases + RUN - 1) / RUN);
+        if (k >= 32) tig_locate_kernel<true><<<grid, hu::EB, 0, st>>>(a, store.bad, n_bases, n, d_counts, ix->heavy_where.get(), d_hit);
+        else tig_locate_kernel<false><<<grid, hu::EB, 0, st>>>(a, store.bad, n_bases, n, d_counts, ix->heavy_where.get(), d_hit);
+        HIP_CHECK(hipGetLastError());
+        ev.mark(1, st);
+    }
+    void download_counts(uint64_t *valid, uint64_t *found) {
         HIP_CHECK(hipMemcpyAsync(valid, d_counts, n * 8, hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipMemcpyAsync(found, d_counts + n, n * 8, hipMemcpyDeviceToHost, st));
+    }
+    tp::GatherArgs gather_args(const TigIndex *ix, unsigned int *err) const {
+        return tp::GatherArgs{d_hit, store.off, ix->off, ix->win_off, store.n_bases, n, ix->info.records, err};
+    }
+    void booked(TigPayloadTimes *t) {
+        t->upload_ms = store.upload_ms;
+        t->pack_ms = store.pack_ms;
+        t->probe_ms = ev.ms(0, 1);
+        t->gather_ms = ev.ms(1, 2);
+    }
+};
+
+}  // namespace
+
+void device_tig_index_locate(const TigIndex *ix, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid,
+                             uint64_t *found, KmerRuns *runs, KmerLocateTimes *times) {
+    const char *fn = "mtg_tig_index_locate";
+    if (!ix->locating) MTG_DIE("%s: the index keeps no positions of its heavy buckets (build it with mtg_tig_index_build_locating)", fn);
+    const uint64_t n_bases = locate_windows(fn, ix, seq, off, n, kmers, valid, found, !runs);
+    *runs = KmerRuns();
+    if (times) *times = KmerLocateTimes();
+    if (n_bases == 0) return;  // nothing to look at
+    LocateProbe p(ix, seq, off, n);
+    const kr::RunArgs ra{p.d_hit, p.store.off, ix->off, n_bases, n, ix->info.records, ix->info.k};
+    kr::runs_from_hits(ra, p.st, ix->device_id, runs, [&](hipStream_t) {
+        p.ev.mark(2, p.st);
+        p.download_counts(valid, found);
     });
     if (times) {
-        times->upload_ms = store.upload_ms;
-        times->pack_ms = store.pack_ms;
-        times->probe_ms = ev.ms(0, 1);
-        times->runs_ms = ev.ms(1, 2);
+        times->upload_ms = p.store.upload_ms;
+        times->pack_ms = p.store.pack_ms;
+        times->probe_ms = p.ev.ms(0, 1);
+        times->runs_ms = p.ev.ms(1, 2);
     }
+}
+
+// ---- payloads by position ----
+TigIndex *device_tig_index_build_annotated(const char *seq, const uint64_t *off, uint64_t n, uint64_t k, uint64_t m, uint64_t bucket_limit,
+                                           const KmerWeights *weights, const KmerColors *colors, int layout, int device_id, TigIndexTimes *times,
+                                           TigPayloadTimes *payload_times) {
+    const char *fn = "mtg_tig_index_build_annotated";
+    if (k < 1) MTG_DIE("%s: k must be >= 1", fn);
+    if (layout < 0 || layout > 2) MTG_DIE("%s: layout %d; 0 (auto), 1 (dense) and 2 (runs) are served", fn, layout);
+    const uint64_t windows = check_offsets(fn, seq, off, n, k);
+    if (weights && weights->n != windows) MTG_DIE("%s: %llu weights for %llu windows", fn, (unsigned long long)weights->n, (unsigned long long)windows);
+    if (weights && weights->n && !weights->w) MTG_DIE("%s: null argument", fn);
+    if (colors && (colors->n_colors < 1 || colors->n_colors > 64)) MTG_DIE("%s: %llu colours; 1 .. 64 are served", fn, (unsigned long long)colors->n_colors);
+    if (colors && colors->n != windows) MTG_DIE("%s: %llu colour words for %llu windows", fn, (unsigned long long)colors->n, (unsigned long long)windows);
+    if (colors && colors->n && !colors->c) MTG_DIE("%s: null argument", fn);
+    if (colors && colors->n_colors < 64)  // (the gather adds into per_color[r C + c] for every set bit c)
+        for (uint64_t i = 0; i < colors->n; i++)
+            if (colors->c[i] >> colors->n_colors)
+                MTG_DIE("%s: the mask of window %llu has a bit at or beyond n_colors = %llu", fn, (unsigned long long)i, (unsigned long long)colors->n_colors);
+    TigIndex *ix = device_tig_index_build(seq, off, n, k, m, bucket_limit, device_id, times, true, fn);
+    if (payload_times) *payload_times = TigPayloadTimes();
+    if (!weights && !colors) return ix;
+    hipStream_t st = nullptr;
+    {
+        std::vector<unsigned long long> win_off(n + 1, 0);
+        for (uint64_t r = 0; r < n; r++) win_off[r + 1] = win_off[r] + (off[r + 1] - off[r] >= k ? off[r + 1] - off[r] - k + 1 : 0);
+        ix->win_off.alloc(n + 1);
+        hu::upload_sliced(ix->win_off, win_off.data(), (n + 1) * 8, st, device_id);
+        HIP_CHECK(hipStreamSynchronize(st));  // (win_off leaves its scope)
+    }
+    ix->info.device_bytes += (n + 1) * 8;
+    tp::PayloadBuildTimes t;
+    if (weights) {
+        tp::payload_build(ix->weights, weights->w, windows, 0, (uint32_t)layout, st, device_id, &t);
+        ix->info.device_bytes += ix->weights.info.device_bytes;
+        if (payload_times) { double *o = payload_times->weights_ms; o[0] = t.upload_ms; o[1] = t.reduce_ms; o[2] = t.flag_scan_ms; o[3] = t.store_ms; }
+    }
+    if (colors) {
+        tp::payload_build(ix->colors, reinterpret_cast<const unsigned long long *>(colors->c), windows, colors->n_colors, (uint32_t)layout, st, device_id, &t);
+        ix->n_colors = colors->n_colors;
+        ix->info.device_bytes += ix->colors.info.device_bytes;
+        if (payload_times) { double *o = payload_times->colors_ms; o[0] = t.upload_ms; o[1] = t.reduce_ms; o[2] = t.flag_scan_ms; o[3] = t.store_ms; }
+    }
+    return ix;
+}
+
+void device_tig_index_payload_info(const TigIndex *ix, mtg_tig_payload_info *out) {
+    *out = mtg_tig_payload_info{};
+    out->weights = ix->weights.info;
+    out->colors = ix->colors.info;
+    out->n_colors = ix->colors.present() ? ix->n_colors : 0;
+    out->win_offset_bytes = ix->win_off ? (ix->info.records + 1) * 8 : 0;
+}
+
+namespace {
+// the gather's error word, zeroed on st; check() after the stream was waited for
+struct GatherErr {
+    hu::DeviceArray<unsigned int> d;
+    unsigned int h = 0;
+    explicit GatherErr(hipStream_t st) : d(1) { HIP_CHECK(hipMemsetAsync(d, 0, 4, st)); }
+    void fetch(hipStream_t st) { HIP_CHECK(hipMemcpyAsync(&h, d, 4, hipMemcpyDeviceToHost, st)); }
+    void check(const char *fn) const {
+        if (h) MTG_DIE("%s: internal error %u (a located window outside the payload)", fn, h);
+    }
+};
+}  // namespace
+
+void device_tig_index_abundance(const TigIndex *ix, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid,
+                                uint64_t *found, uint64_t *sum, uint32_t *min, uint32_t *max, uint32_t *per_window, TigPayloadTimes *times) {
+    const char *fn = "mtg_tig_index_abundance";
+    if (!ix->weights.present()) MTG_DIE("%s: the index keeps no weights (build it with mtg_tig_index_build_annotated)", fn);
+    const uint64_t n_bases = locate_windows(fn, ix, seq, off, n, kmers, valid, found, n && (!sum || !min || !max));
+    std::fill(sum, sum + n, 0ull);
+    std::fill(min, min + n, 0u);
+    std::fill(max, max + n, 0u);
+    if (times) times->upload_ms = times->pack_ms = times->probe_ms = times->gather_ms = 0;
+    if (n_bases == 0) return;  // nothing to look at
+    LocateProbe p(ix, seq, off, n);
+    hu::DeviceArray<unsigned long long> d_sum(n);
+    hu::DeviceArray<uint32_t> d_minmax(2 * n), d_per_window;
+    if (per_window) d_per_window.alloc(n_bases);
+    GatherErr err(p.st);
+    HIP_CHECK(hipMemsetAsync(d_sum, 0, n * 8, p.st));
+    HIP_CHECK(hipMemsetAsync(d_minmax, 0xFF, n * 4, p.st));
+    HIP_CHECK(hipMemsetAsync(d_minmax + n, 0, n * 4, p.st));
+    // (one thread per run of positions: every word of per_window is written)
+    tp::abundance_gather_kernel<<<hu::grid_for((n_bases + RUN - 1) / RUN), hu::EB, 0, p.st>>>(p.gather_args(ix, err.d), ix->weights.view(), d_sum, d_minmax,
+                                                                                             d_per_window);
+    HIP_CHECK(hipGetLastError());
+    p.ev.mark(2, p.st);
+    p.download_counts(valid, found);
+    err.fetch(p.st);
+    HIP_CHECK(hipMemcpyAsync(sum, d_sum, n * 8, hipMemcpyDeviceToHost, p.st));
+    HIP_CHECK(hipMemcpyAsync(min, d_minmax, n * 4, hipMemcpyDeviceToHost, p.st));
+    HIP_CHECK(hipMemcpyAsync(max, d_minmax + n, n * 4, hipMemcpyDeviceToHost, p.st));
+    HIP_CHECK(hipStreamSynchronize(p.st));
+    err.check(fn);
+    if (per_window) hu::download_sliced(per_window, d_per_window, n_bases * 4, p.st, p.device_id);
+    for (uint64_t r = 0; r < n; r++)
+        if (!found[r]) min[r] = 0;  // (nothing lowered the all-ones word)
+    if (times) p.booked(times);
+}
+
+void device_tig_index_colors(const TigIndex *ix, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid,
+                             uint64_t *found, uint32_t *per_color, uint64_t *per_window, TigPayloadTimes *times) {
+    const char *fn = "mtg_tig_index_colors";
+    if (!ix->colors.present()) MTG_DIE("%s: the index keeps no colours (build it with mtg_tig_index_build_annotated)", fn);
+    const uint64_t C = ix->n_colors;
+    const uint64_t n_bases = locate_windows(fn, ix, seq, off, n, kmers, valid, found, n && !per_color);
+    for (uint64_t r = 0; r < n; r++)
+        if (kmers[r] >> 32) MTG_DIE("%s: record %llu has %llu windows; the per-colour counters are 32-bit", fn, (unsigned long long)r,
+                                    (unsigned long long)kmers[r]);
+    std::fill(per_color, per_color + n * C, 0u);
+    if (times) times->upload_ms = times->pack_ms = times->probe_ms = times->gather_ms = 0;
+    if (n_bases == 0) return;  // nothing to look at
+    LocateProbe p(ix, seq, off, n);
+    hu::DeviceArray<uint32_t> d_per_color(n * C);
+    hu::DeviceArray<unsigned long long> d_per_window;
+    if (per_window) d_per_window.alloc(n_bases);
+    GatherErr err(p.st);
+    HIP_CHECK(hipMemsetAsync(d_per_color, 0, n * C * 4, p.st));
+    // (one thread per run of positions: every word of per_window is written)
+    tp::color_gather_kernel<<<hu::grid_for((n_bases + RUN - 1) / RUN), hu::EB, 0, p.st>>>(p.gather_args(ix, err.d), ix->colors.view(), (uint32_t)C, d_per_color,
+                                                                                         d_per_window);
+    HIP_CHECK(hipGetLastError());
+    p.ev.mark(2, p.st);
+    p.download_counts(valid, found);
+    err.fetch(p.st);
+    HIP_CHECK(hipStreamSynchronize(p.st));
+    err.check(fn);
+    hu::download_sliced(per_color, d_per_color, n * C * 4, p.st, p.device_id);
+    if (per_window) hu::download_sliced(per_window, d_per_window, n_bases * 8, p.st, p.device_id);
+    if (times) p.booked(times);
 }
 
 }  // namespace mtg
