@@ -824,6 +824,39 @@ void mtg_kmer_tally_free(mtg_kmer_tally *t); /* NULL is fine; any current device
 /* Of the last mtg_kmer_tally_add or mtg_kmer_tally_coverage on this thread, in ms: {upload (host clock), pack, probe -- HIP events
  * around the kernel --, download (host clock)}. */
 void mtg_last_kmer_tally_times(double out[4]);
+/* The same tally on the SPARSE index: counters hung off text positions instead of table slots. A TIG TALLY belongs to
+ * one LOCATING mtg_tig_index (mtg_tig_index_build_locating* or mtg_tig_index_build_annotated*; mtg_tig_tally_create aborts on any
+ * other and names mtg_tig_index_build_locating), which must outlive it and which it never changes. It holds one unsigned 64-bit
+ * counter per WINDOW ORDINAL of the indexed text (the windows of record 0 from left to right, then record 1's; W = info.occurrences
+ * = mtg_tig_tally_windows), all 0 at creation, and the windows before every record (8 B per record + 8) unless the index keeps them
+ * already (an annotated index with a payload): mtg_tig_tally_device_bytes = 8 W, plus 8 (records + 1) iff the tally owns those.
+ * From the arena on the index's device until mtg_tig_tally_free; mtg_release_device_memory leaves it intact. Several tallies on one
+ * index are independent.
+ * add / coverage / reset are mtg_kmer_tally_add's / _coverage's / _reset's contracts, word for word: for the same indexed sequences,
+ * k, adds and asked sequences every output equals that of a mtg_kmer_tally on a mtg_kmer_index, for every m and bucket_limit. The
+ * counter of a class is the one at the ordinal of the smallest window start of the class in the text (what mtg_tig_index_locate
+ * reports): mtg_tig_tally_counters copies the W counters out in window order, where a window that is not the first occurrence of its
+ * class holds 0 and the sum of all equals the sum of found[] over the adds since creation or the last reset.
+ * A null argument or bad offsets abort with the function's name; a query without bases returns at once. */
+typedef struct mtg_tig_tally mtg_tig_tally;
+mtg_tig_tally *mtg_tig_tally_create(const mtg_tig_index *ix); /* the index must outlive the tally */
+uint64_t mtg_tig_tally_device_bytes(const mtg_tig_tally *t);
+uint64_t mtg_tig_tally_windows(const mtg_tig_tally *t); /* W */
+void mtg_tig_tally_add(mtg_tig_tally *t, const char *seq, const uint64_t *off, uint64_t n,
+                       uint64_t *kmers, uint64_t *valid, uint64_t *found); /* [n] each */
+void mtg_tig_tally_coverage(const mtg_tig_tally *t, const char *seq, const uint64_t *off, uint64_t n,
+                            uint64_t *kmers, uint64_t *valid, uint64_t *found,       /* [n] each */
+                            uint64_t *covered, uint64_t *sum, uint64_t *max,         /* [n] each */
+                            uint64_t *per_window);                                   /* nullable, [off[n]] */
+void mtg_tig_tally_add_store(mtg_tig_tally *t, const mtg_unitigs *store, uint64_t *kmers, uint64_t *valid, uint64_t *found);
+void mtg_tig_tally_coverage_store(const mtg_tig_tally *t, const mtg_unitigs *store, uint64_t *kmers, uint64_t *valid, uint64_t *found,
+                                  uint64_t *covered, uint64_t *sum, uint64_t *max, uint64_t *per_window);
+void mtg_tig_tally_counters(const mtg_tig_tally *t, uint64_t *out); /* [W] */
+void mtg_tig_tally_reset(mtg_tig_tally *t);
+void mtg_tig_tally_free(mtg_tig_tally *t); /* NULL is fine; any current device */
+/* Of the last mtg_tig_tally_add or mtg_tig_tally_coverage on this thread, in ms: {upload (host clock), pack, probe (tig_locate_kernel
+ * with the fill of the hit array), the add or the gather -- HIP events around the kernels --, download (host clock)}. */
+void mtg_last_tig_tally_times(double out[5]);
 /* MONOCHROMATIC UNITIGS and COLOUR CLASSES. mtg_compact_unitigs_colored_classes is mtg_compact_unitigs_colored plus
  * *classes, the dictionary of the output store's masks. Number the windows of *out i = 0 .. N - 1 in window order (the indexing of
  * *kmer_colors). A RUN is a maximal stretch of consecutive windows of ONE unitig with equal masks. The classes are the distinct masks,

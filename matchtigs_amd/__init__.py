@@ -15,8 +15,10 @@ from .api import (  # noqa: F401
     NodeWeightArrayType,
     PerformanceDataType,
     TigAlgorithm,
+    TigTally,
     clib_compute_tigs,
     last_phase_seconds,
+    last_tig_tally_times,
 )
 
 __all__ = [n for n in dir() if not n.startswith("_")]

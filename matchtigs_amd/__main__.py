@@ -65,6 +65,9 @@ counted on the k-mers of the unitigs -- as written, after cleaning, splitting an
 repeats included, and `--count-out` gets one row per unitig with, per sample, the k-mers of the unitig the sample saw at all and the sum
 of their counts: a unitig x sample depth matrix of exact integers. `--count-min-base-quality Q` masks the bases of FASTQ count files
 whose Phred quality is below Q.
+`--count-index minimizer` counts on the sparse minimizer index instead of the table (`--count-minimizer-length M`), with one counter per
+window of the indexed text, and `--count-index-over greedytigs` / `eulertigs` indexes the tigs this run wrote: `--count-out` is byte for
+byte the table route's. Queries that asked the same sparse index hand it over.
 """
 from __future__ import annotations
 
@@ -213,6 +216,14 @@ def main(argv=None) -> int:
                          "file <file>:covered (its k-mers the file saw) and <file>:sum (the sum of their counts)")
     ap.add_argument("--count-min-base-quality", type=int, metavar="Q",
                     help="with fastq --count-fa files: a base whose Phred quality is below Q (0..93) is replaced by N")
+    ap.add_argument("--count-index", choices=("table", "minimizer"),
+                    help="the index --count-fa counts on: table (default; a slot and a counter per k-mer) or minimizer (the sparse index "
+                         "with a counter per window of its text: a fraction of the memory, the same --count-out)")
+    ap.add_argument("--count-minimizer-length", type=int, metavar="M",
+                    help="with --count-index minimizer: the minimizer length, 1 .. min(k, 31) (default min(19, ceil(2k/3)))")
+    ap.add_argument("--count-index-over", choices=("input", "greedytigs", "eulertigs"),
+                    help="with --count-index minimizer: the sequences --count-fa indexes: the input (default) or the tigs this run wrote, "
+                         "read back from --greedytigs-fa-out / --eulertigs-fa-out; --count-out keeps one row per unitig")
     args = ap.parse_args(argv)
 
     classed = bool(args.monochromatic_unitigs or args.color_classes_out or args.unitig_color_classes_out)
@@ -271,6 +282,16 @@ def main(argv=None) -> int:
         ap.error("--count-fa needs --count-out" if args.count_fa else "--count-out needs --count-fa")
     if args.count_min_base_quality is not None and not args.count_fa:
         ap.error("--count-min-base-quality needs --count-fa")
+    if args.count_index is not None and not args.count_fa:
+        ap.error("--count-index needs --count-fa")
+    for flag, value in (("--count-minimizer-length", args.count_minimizer_length), ("--count-index-over", args.count_index_over)):
+        if value is not None and args.count_index != "minimizer":
+            ap.error(f"{flag} needs --count-index minimizer")
+    if args.count_minimizer_length is not None and not 1 <= args.count_minimizer_length <= min(args.k, 31):
+        ap.error(f"--count-minimizer-length must be in 1..{min(args.k, 31)} (1 .. min(k, 31), as --query-minimizer-length)")
+    for over, out in (("greedytigs", args.greedytigs_fa_out), ("eulertigs", args.eulertigs_fa_out)):
+        if args.count_index_over == over and not out:
+            ap.error(f"--count-index-over {over} needs --{over}-fa-out")
     for flag, value in (("--query-index", args.query_index), ("--query-minimizer-length", args.query_minimizer_length),
                         ("--query-index-over", args.query_index_over)):
         if value is not None and not args.query_fa:
@@ -565,12 +586,19 @@ def _run(api, args, fastq) -> int:
               f"({r['tigs']} tigs, {r['fasta_bytes']} fasta bytes)", file=sys.stderr)
         if args.verify:
             all_equal &= report(f"{name} ({out or 'spelled in memory'})", r["verify_tigs"], r["verify"])
-    table_index = None  # the plain-enough table index over the unitig store, if the queries built one: the count reuses it
+    # the queries' index, left open, if it is the one the count asks for: the plain-enough table index over the unitig store, or
+    #  the sparse index over the same sequences with the same minimizer length, then built locating
+    shared_index = None
+    count_sparse = args.count_index == "minimizer"
+    share_sparse = bool(count_sparse and args.query_fa and args.query_index == "minimizer"
+                        and (args.query_index_over or "input") == (args.count_index_over or "input")
+                        and args.count_minimizer_length in (None, args.query_minimizer_length or api.default_minimizer_length(args.k)))
     if args.query_fa:
-        table_index = _query(api, args, store, abundance.kmer_counts if args.query_abundance_out or args.query_index_abundance_out else None, fastq,
-                             colors if args.query_colors_out or args.query_index_colors_out else None, keep_index=bool(args.count_fa))
+        shared_index = _query(api, args, store, abundance.kmer_counts if args.query_abundance_out or args.query_index_abundance_out else None, fastq,
+                              colors if args.query_colors_out or args.query_index_colors_out else None,
+                              keep_index=bool(args.count_fa) and not count_sparse, keep_sparse=share_sparse)
     if args.count_fa:
-        _count(api, args, store, fastq, table_index)
+        _count(api, args, store, fastq, shared_index)
     return 0 if all_equal else 1
 
 
@@ -802,12 +830,22 @@ def _tig_payloads(api, args, store, tigs, kmer_counts, colors, what):
             np.concatenate(masks) if masks else np.zeros(0, np.uint64) if colors is not None else None)
 
 
-def _query(api, args, store, kmer_counts=None, fastq=(), colors=None, keep_index=False):
+def _describe_index(index, sparse) -> str:
+    """What the `Indexing the ...` lines say of an index: the sparse one's own words, the table in the same terms."""
+    i = index.info
+    if sparse:
+        return i.describe()
+    return (f"table index: {i.characters} bases in {i.records} records, 0 anchors, 0 heavy buckets with 0 windows, {i.device_bytes} "
+            f"device bytes, {i.device_bytes / i.occurrences if i.occurrences else 0.0:.2f} bytes per k-mer window")
+
+
+def _query(api, args, store, kmer_counts=None, fastq=(), colors=None, keep_index=False, keep_sparse=False):
     """`--query-fa`: the input's k-mer set (the unitig store) indexed once; one TSV row and one presence line per query record, and
     with `--query-locate-out` (the sparse index: `--query-index-locate-out`) one row per run of located k-mers. kmer_counts (`--query-abundance-out`): the index is weighted with
     them, and one more TSV row, and with `--query-abundance-profile-out` one line of integers, per query record. colors
     (`--query-colors-out`): the index carries their masks, and one more TSV row per query record. keep_index: a table index over
     `store` is handed back open instead of closed (`--count-fa` counts on it); None if the queries asked another kind of index.
+    keep_sparse (`--count-index minimizer` on what the queries index): the sparse index is built locating and handed back open.
     With the sparse index (`--query-index-abundance-out`, `--query-index-colors-out`) the same two payloads hang off the
     positions of whatever it indexes, and the same rows are written."""
     import contextlib
@@ -821,18 +859,18 @@ def _query(api, args, store, kmer_counts=None, fastq=(), colors=None, keep_index
     with contextlib.ExitStack() as stack:
         sparse = args.query_index == "minimizer"
         over = args.query_index_over or "input"
-        kept = keep_index and not sparse and over == "input"
+        kept = (keep_index and not sparse and over == "input") or (keep_sparse and sparse)
         hold = (lambda ix: ix) if kept else stack.enter_context  # (a kept index is closed by the caller)
         if sparse or over != "input":  # (the same k-mer set, asked of another index or spelled by the tigs)
             indexed = store if over == "input" else api.read_sequences(args.greedytigs_fa_out if over == "greedytigs" else args.eulertigs_fa_out)
             if sparse and (kmer_counts is not None or colors is not None):  # (payloads by position)
                 weights, masks = (kmer_counts, None if colors is None else colors.kmer_colors) if over == "input" else _tig_payloads(
                     api, args, store, indexed, kmer_counts, colors, over)
-                index = stack.enter_context(api.TigIndex.annotated(indexed, args.k, args.query_minimizer_length, args.device, weights=weights,
-                                                                   colors=masks, n_colors=None if colors is None else colors.n_colors))
+                index = hold(api.TigIndex.annotated(indexed, args.k, args.query_minimizer_length, args.device, weights=weights,
+                                                    colors=masks, n_colors=None if colors is None else colors.n_colors))
             elif sparse:
-                index = stack.enter_context(api.TigIndex(indexed, args.k, args.query_minimizer_length, args.device,
-                                                         locate=bool(args.query_index_locate_out)))
+                index = hold(api.TigIndex(indexed, args.k, args.query_minimizer_length, args.device,
+                                          locate=bool(args.query_index_locate_out) or keep_sparse))
             else:
                 index = stack.enter_context(api.KmerIndex(indexed, args.k, args.device))
         elif colors is not None:  # (the masks, and the counts too when abundances are asked for)
@@ -843,11 +881,7 @@ def _query(api, args, store, kmer_counts=None, fastq=(), colors=None, keep_index
         else:
             index = hold(api.KmerIndex(store, args.k, args.device, locate=bool(args.query_locate_out), weights=kmer_counts))
         if args.query_index is not None or args.query_index_over is not None:
-            i = index.info
-            line = i.describe() if sparse else (
-                f"table index: {i.characters} bases in {i.records} records, 0 anchors, 0 heavy buckets with 0 windows, {i.device_bytes} "
-                f"device bytes, {i.device_bytes / i.occurrences if i.occurrences else 0.0:.2f} bytes per k-mer window")
-            print(f"Indexing the {'input' if over == 'input' else over}: {line}", file=sys.stderr)
+            print(f"Indexing the {over}: {_describe_index(index, sparse)}", file=sys.stderr)
             for what, p in (getattr(index, "payload_info", None) or {}).items():
                 print(f"  {what} by position: {p['layout']}, {p['width']} B wide, {p['runs']} runs over {p['windows']} windows, "
                       f"{p['device_bytes']} device bytes", file=sys.stderr)
@@ -907,10 +941,25 @@ def _count(api, args, store, fastq=(), index=None) -> None:
     """`--count-fa`: every file is a sample whose k-mers are counted on the k-mers of the unitig store. One table
     index over the store -- `index`, the one the queries left open, else a plain one built here -- and one tally serve all samples in
     turn: add the sample, read the coverage of the store's own records, keep two columns, reset. `--count-out`: one row per record
-    of the store, per sample the k-mers it saw at all and the sum of their counts."""
+    of the store, per sample the k-mers it saw at all and the sum of their counts.
+    With `--count-index minimizer` the index is a locating sparse one over what `--count-index-over` names -- the
+    queries' own if they left it open -- and the tally one counter per window of that text; the coverage is still asked of the store."""
+    import contextlib
+
     import numpy as np
 
-    with (index if index is not None else api.KmerIndex(store, args.k, args.device)) as index, api.KmerTally(index) as tally:
+    with contextlib.ExitStack() as stack:
+        sparse, over, built = args.count_index == "minimizer", args.count_index_over or "input", index is None
+        if built and sparse:
+            indexed = store if over == "input" else api.read_sequences(args.greedytigs_fa_out if over == "greedytigs" else args.eulertigs_fa_out)
+            index = api.TigIndex(indexed, args.k, args.count_minimizer_length, args.device, locate=True)
+        elif built:
+            index = api.KmerIndex(store, args.k, args.device)
+        stack.enter_context(index)
+        tally = stack.enter_context(api.TigTally(index) if sparse else api.KmerTally(index))
+        if built and args.count_index is not None:
+            print(f"Indexing the {over} for the count: {_describe_index(index, sparse)}; the tally: {tally.device_bytes} device bytes",
+                  file=sys.stderr)
         columns, kmers = [], None
         for path in args.count_fa:
             t0 = time.perf_counter()

@@ -426,6 +426,17 @@ def load():
         "mtg_kmer_tally_reset": (None, [vp]),
         "mtg_kmer_tally_free": (None, [vp]),
         "mtg_last_kmer_tally_times": (None, [P(C.c_double)]),
+        "mtg_tig_tally_create": (vp, [vp]),
+        "mtg_tig_tally_device_bytes": (u64, [vp]),
+        "mtg_tig_tally_windows": (u64, [vp]),
+        "mtg_tig_tally_add": (None, [vp, vp, vp, u64, vp, vp, vp]),
+        "mtg_tig_tally_add_store": (None, [vp, vp, vp, vp, vp]),
+        "mtg_tig_tally_coverage": (None, [vp, vp, vp, u64, vp, vp, vp, vp, vp, vp, vp]),
+        "mtg_tig_tally_coverage_store": (None, [vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "mtg_tig_tally_counters": (None, [vp, vp]),
+        "mtg_tig_tally_reset": (None, [vp]),
+        "mtg_tig_tally_free": (None, [vp]),
+        "mtg_last_tig_tally_times": (None, [P(C.c_double)]),
         "mtg_read_sequences_named": (None, [C.c_char_p, P(vp), P(vp)]),
         "mtg_read_fastq_split": (C.c_int, [C.c_char_p, u64, C.c_int, P(vp), P(MtgFastqStats), C.c_char_p, u64]),
         "mtg_read_fastq_named": (C.c_int, [C.c_char_p, u64, C.c_int, P(vp), P(vp), P(MtgFastqStats), C.c_char_p, u64]),

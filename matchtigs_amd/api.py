@@ -2016,6 +2016,97 @@ def last_tig_payload_times() -> dict:
             **dict(zip(("upload_ms", "pack_ms", "probe_ms", "gather_ms"), out[8:12]))}
 
 
+class TigTally:
+    """KmerTally on the sparse index (mtg_tig_tally_*): how often other sequences see the k-mers of a LOCATING TigIndex
+    (locate=True or TigIndex.annotated). One 64-bit counter per window of the indexed text (`windows` of them, 8 B each; device_bytes
+    also counts the windows-before-every-record array where the index keeps none), zero at first, on the index's GPU until close()
+    or collection. add / coverage / reset answer exactly as KmerTally's do on a KmerIndex over the same sequences: a k-mer is counted
+    at the window where its class occurs first in the text, so counters() -- the counters in window order -- holds 0 at every later
+    occurrence and sums to the found windows added. The index is never changed; the tally keeps a reference to it, and several
+    tallies on one index are independent."""
+
+    def __init__(self, index: "TigIndex"):
+        self._h = None
+        if not isinstance(index, TigIndex):
+            raise TypeError("TigTally counts on a TigIndex")
+        if not index._h:
+            raise ValueError("the index is closed")
+        if not index.locating:
+            raise ValueError("TigTally needs an index built with locate=True")
+        self.index = index
+        self._L = index._L
+        self._h = self._L.mtg_tig_tally_create(index._h)
+        self.device_bytes = int(self._L.mtg_tig_tally_device_bytes(self._h))
+        self.windows = int(self._L.mtg_tig_tally_windows(self._h))
+
+    def close(self) -> None:
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            self._L.mtg_tig_tally_free(h)
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _open(self) -> None:
+        """The tally open and its index open, else ValueError: before the library is asked."""
+        if not self._h:
+            raise ValueError("the tally is closed")
+        if not self.index._h:
+            raise ValueError("the index is closed")
+
+    def add(self, seqs_or_store) -> KmerQueryResult:
+        """Count the k-mers of seqs_or_store (UnitigStore, list of str, or (uint8 array, offsets); ANY bytes) that the index holds
+        -> what TigIndex.query says of them."""
+        self._open()
+        d, o, n, keep, off, kmers, valid, found = self.index._probe_inputs(seqs_or_store)
+        if isinstance(seqs_or_store, UnitigStore):
+            self._L.mtg_tig_tally_add_store(self._h, seqs_or_store.handle, _ptr(kmers), _ptr(valid), _ptr(found))
+        else:
+            self._L.mtg_tig_tally_add(self._h, d, o, n, _ptr(kmers), _ptr(valid), _ptr(found))
+        del keep
+        return KmerQueryResult(self.index.info.k, off, kmers, valid, found)
+
+    def coverage(self, seqs_or_store, per_window: bool = False) -> KmerCoverageResult:
+        """KmerTally.coverage's answer: query()'s counts per record of seqs_or_store plus, over its found windows, how many were
+        added at least once, the sum and the largest of their tallies; per_window: also the tally at every window start."""
+        self._open()
+        d, o, n, keep, off, kmers, valid, found = self.index._probe_inputs(seqs_or_store)
+        covered, total, hi = (np.zeros(n, np.uint64) for _ in range(3))
+        pw = np.zeros(int(off[n]), np.uint64) if per_window else None
+        outs = (_ptr(kmers), _ptr(valid), _ptr(found), _ptr(covered), _ptr(total), _ptr(hi), _ptr(pw) if per_window else None)
+        if isinstance(seqs_or_store, UnitigStore):
+            self._L.mtg_tig_tally_coverage_store(self._h, seqs_or_store.handle, *outs)
+        else:
+            self._L.mtg_tig_tally_coverage(self._h, d, o, n, *outs)
+        del keep
+        return KmerCoverageResult(self.index.info.k, off, kmers, valid, found, covered, total, hi, pw)
+
+    def counters(self) -> np.ndarray:
+        """The counters in window order of the indexed sequences (uint64, `windows` of them)."""
+        self._open()
+        out = np.zeros(self.windows, np.uint64)
+        self._L.mtg_tig_tally_counters(self._h, _ptr(out))
+        return out
+
+    def reset(self) -> None:
+        """Every counter zero again."""
+        self._open()
+        self._L.mtg_tig_tally_reset(self._h)
+
+
+def last_tig_tally_times() -> dict:
+    """Phases of the last TigTally.add or TigTally.coverage on this thread, in ms (HIP events around the kernels; upload and download
+    by the host clock): probe = the locate pass with the fill of the hit array, pass2 = the add or the gather over the hits."""
+    out = (C.c_double * 5)()
+    _lib.load().mtg_last_tig_tally_times(out)
+    return dict(zip(("upload_ms", "pack_ms", "probe_ms", "pass2_ms", "download_ms"), list(out)))
+
+
 def last_tig_locate_times() -> dict:
     """Phases of the last TigIndex.locate on this thread, in ms (HIP events around the kernels; the upload by the host clock): probe =
     the lookup of every window with its position and strand (with the fill of the hit array), runs = folding the hits into runs."""

@@ -269,6 +269,24 @@ void device_tig_index_abundance(const TigIndex *ix, const char *seq, const uint6
 void device_tig_index_colors(const TigIndex *ix, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid,
                              uint64_t *found, uint32_t *per_color, uint64_t *per_window, TigPayloadTimes *times);
 void device_tig_index_free(TigIndex *ix);
+// A tally over one locating sparse index (tig_tally_device.hpp): device_kmer_tally_*'s contracts and results with one
+// 64-bit counter per window ordinal of the indexed text (plus win_off[records + 1] where the index keeps none), counted at the first
+// occurrence of a window's class. counters: the W counters in window order. times: host wall clock of the upload and the download,
+// HIP-event time of the kernels; pass2: the add or the gather.
+struct TigTally;
+struct TigTallyTimes {
+    double upload_ms = 0, pack_ms = 0, probe_ms = 0, pass2_ms = 0, download_ms = 0;
+};
+TigTally *device_tig_tally_create(const TigIndex *ix);
+uint64_t device_tig_tally_device_bytes(const TigTally *t);
+uint64_t device_tig_tally_windows(const TigTally *t);
+void device_tig_tally_add(TigTally *t, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid, uint64_t *found,
+                          TigTallyTimes *times);
+void device_tig_tally_coverage(const TigTally *t, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid,
+                               uint64_t *found, uint64_t *covered, uint64_t *sum, uint64_t *max, uint64_t *per_window, TigTallyTimes *times);
+void device_tig_tally_counters(const TigTally *t, uint64_t *out);
+void device_tig_tally_reset(TigTally *t);
+void device_tig_tally_free(TigTally *t);
 // compact_device.hip: the maximal unitigs of the k-mer set of arbitrary sequences (the file's header and DESIGN.md 16 state the
 // contract), as an ordinary sequence store. times: host wall clock of upload, download and the whole call, HIP-event time of the
 // kernel phases, the pointer-jumping rounds, the bytes the kernels must move at the least, the arena's peak of live bytes.

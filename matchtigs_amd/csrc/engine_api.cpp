@@ -980,6 +980,58 @@ void mtg_last_tig_payload_times(double out[12]) {
     }
     out[8] = t.upload_ms; out[9] = t.pack_ms; out[10] = t.probe_ms; out[11] = t.gather_ms;
 }
+// ---- tallies by position on the sparse index (tig_tally_device.hpp) ----
+struct mtg_tig_tally { TigTally *t; };
+static thread_local TigTallyTimes g_last_tig_tally;
+mtg_tig_tally *mtg_tig_tally_create(const mtg_tig_index *ix) {
+    if (!ix) MTG_DIE("mtg_tig_tally_create: null argument");
+    return new mtg_tig_tally{device_tig_tally_create(ix->ix)};
+}
+uint64_t mtg_tig_tally_device_bytes(const mtg_tig_tally *t) {
+    if (!t) MTG_DIE("mtg_tig_tally_device_bytes: null argument");
+    return device_tig_tally_device_bytes(t->t);
+}
+uint64_t mtg_tig_tally_windows(const mtg_tig_tally *t) {
+    if (!t) MTG_DIE("mtg_tig_tally_windows: null argument");
+    return device_tig_tally_windows(t->t);
+}
+void mtg_tig_tally_add(mtg_tig_tally *t, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid, uint64_t *found) {
+    if (!t) MTG_DIE("mtg_tig_tally_add: null argument");
+    device_tig_tally_add(t->t, seq, off, n, kmers, valid, found, &g_last_tig_tally);
+}
+void mtg_tig_tally_add_store(mtg_tig_tally *t, const mtg_unitigs *store, uint64_t *kmers, uint64_t *valid, uint64_t *found) {
+    if (!t || !store) MTG_DIE("mtg_tig_tally_add_store: null argument");
+    const UnitigStore &s = *store->s;
+    mtg_tig_tally_add(t, s.data.data(), s.off.data(), s.off.size() - 1, kmers, valid, found);
+}
+void mtg_tig_tally_coverage(const mtg_tig_tally *t, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid,
+                            uint64_t *found, uint64_t *covered, uint64_t *sum, uint64_t *max, uint64_t *per_window) {
+    if (!t) MTG_DIE("mtg_tig_tally_coverage: null argument");
+    device_tig_tally_coverage(t->t, seq, off, n, kmers, valid, found, covered, sum, max, per_window, &g_last_tig_tally);
+}
+void mtg_tig_tally_coverage_store(const mtg_tig_tally *t, const mtg_unitigs *store, uint64_t *kmers, uint64_t *valid, uint64_t *found,
+                                  uint64_t *covered, uint64_t *sum, uint64_t *max, uint64_t *per_window) {
+    if (!t || !store) MTG_DIE("mtg_tig_tally_coverage_store: null argument");
+    const UnitigStore &s = *store->s;
+    mtg_tig_tally_coverage(t, s.data.data(), s.off.data(), s.off.size() - 1, kmers, valid, found, covered, sum, max, per_window);
+}
+void mtg_tig_tally_counters(const mtg_tig_tally *t, uint64_t *out) {
+    if (!t) MTG_DIE("mtg_tig_tally_counters: null argument");
+    device_tig_tally_counters(t->t, out);
+}
+void mtg_tig_tally_reset(mtg_tig_tally *t) {
+    if (!t) MTG_DIE("mtg_tig_tally_reset: null argument");
+    device_tig_tally_reset(t->t);
+}
+void mtg_tig_tally_free(mtg_tig_tally *t) {
+    if (!t) return;
+    device_tig_tally_free(t->t);
+    delete t;
+}
+void mtg_last_tig_tally_times(double out[5]) {
+    const TigTallyTimes &t = g_last_tig_tally;
+    out[0] = t.upload_ms; out[1] = t.pack_ms; out[2] = t.probe_ms; out[3] = t.pass2_ms; out[4] = t.download_ms;
+}
 void mtg_tig_index_free(mtg_tig_index *ix) {
     if (!ix) return;
     device_tig_index_free(ix->ix);

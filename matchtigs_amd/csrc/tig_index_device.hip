@@ -41,6 +41,10 @@
 // one colour mask per window of the text, dense or as runs (tig_payload_device.hpp). t above is the position whose payload the table
 // index keeps for the class, so abundance and colours are two passes: tig_locate_kernel, unchanged, then a gather over hit[].
 //
+// Tallies (any locating index, mtg_tig_tally_*): one 64-bit counter per window ordinal of the text, owned by a TigTally,
+// not by the index. The same two passes: tig_locate_kernel, then tig_tally_add_kernel or tig_coverage_gather_kernel
+// (tig_tally_device.hpp) over hit[]. t is the same for every window of a class, so the counter at its ordinal is the class's.
+//
 // Exactness. A hit is declared only after kw::same_class has compared the query's k bases with k index bases that lie inside ONE
 // record, or after the heavy table's exact `same`: never a false positive, and a tag or hash collision costs a compare. No false
 // negative: let the class of the query window x be the index window y at c. Both have the same set of m-mer classes, hence the same
@@ -62,6 +66,7 @@
 #include "kmer_window_device.hpp"
 #include "pack_device.hpp"
 #include "tig_payload_device.hpp"
+#include "tig_tally_device.hpp"
 
 namespace mtg {
 
@@ -844,6 +849,116 @@ void device_tig_index_colors(const TigIndex *ix, const char *seq, const uint64_t
     hu::download_sliced(per_color, d_per_color, n * C * 4, p.st, p.device_id);
     if (per_window) hu::download_sliced(per_window, d_per_window, n_bases * 8, p.st, p.device_id);
     if (times) p.booked(times);
+}
+
+// ---- tallies by position ----
+struct TigTally {
+    const TigIndex *ix;  // (the caller keeps it alive for add and coverage; the rest does without it)
+    int device_id;
+    uint64_t windows, records;
+    hu::DeviceArray<unsigned long long> count;    // [windows] the windows added on the class whose first occurrence this is
+    hu::DeviceArray<unsigned long long> win_off;  // [records + 1], unless the index keeps one
+    const unsigned long long *d_win_off() const { return win_off ? win_off.get() : ix->win_off.get(); }
+};
+
+TigTally *device_tig_tally_create(const TigIndex *ix) {
+    const char *fn = "mtg_tig_tally_create";
+    if (!ix->locating) MTG_DIE("%s: the index keeps no positions of its heavy buckets (build it with mtg_tig_index_build_locating)", fn);
+    on_device(ix->device_id);
+    hipStream_t st = nullptr;
+    const uint64_t n = ix->info.records, k = ix->info.k;
+    TigTally *t = new TigTally{ix, ix->device_id, ix->info.occurrences, n, {}, {}};
+    t->count.alloc(std::max<uint64_t>(t->windows, 1));  // (an index without windows: never read)
+    if (!ix->win_off) {  // the windows of the records before, from the index's own offsets
+        std::vector<unsigned long long> off(n + 1, 0), win_off(n + 1, 0);
+        hu::download_sliced(off.data(), ix->off.get(), (n + 1) * 8, st, ix->device_id);
+        for (uint64_t r = 0; r < n; r++) win_off[r + 1] = win_off[r] + (off[r + 1] - off[r] >= k ? off[r + 1] - off[r] - k + 1 : 0);
+        t->win_off.alloc(n + 1);
+        hu::upload_sliced(t->win_off, win_off.data(), (n + 1) * 8, st, ix->device_id);
+        HIP_CHECK(hipStreamSynchronize(st));  // (win_off leaves its scope)
+    }
+    device_tig_tally_reset(t);
+    return t;
+}
+
+uint64_t device_tig_tally_device_bytes(const TigTally *t) { return t->windows * 8 + (t->win_off ? (t->records + 1) * 8 : 0); }
+uint64_t device_tig_tally_windows(const TigTally *t) { return t->windows; }
+
+void device_tig_tally_reset(TigTally *t) {
+    on_device(t->device_id);
+    if (!t->windows) return;
+    HIP_CHECK(hipMemsetAsync(t->count, 0, t->windows * 8, nullptr));
+    HIP_CHECK(hipStreamSynchronize(nullptr));
+}
+
+void device_tig_tally_counters(const TigTally *t, uint64_t *out) {
+    if (t->windows && !out) MTG_DIE("mtg_tig_tally_counters: null argument");
+    on_device(t->device_id);
+    if (t->windows) hu::download_sliced(out, t->count.get(), t->windows * 8, nullptr, t->device_id);
+}
+
+void device_tig_tally_free(TigTally *t) {
+    if (!t) return;
+    int cur = 0;  // (as an index: it may die on a thread whose current device is another one)
+    (void)hipGetDevice(&cur);
+    (void)hipSetDevice(t->device_id);
+    delete t;
+    (void)hipSetDevice(cur);
+}
+
+void device_tig_tally_add(TigTally *t, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid, uint64_t *found,
+                          TigTallyTimes *times) {
+    const char *fn = "mtg_tig_tally_add";
+    const TigIndex *ix = t->ix;
+    const uint64_t n_bases = locate_windows(fn, ix, seq, off, n, kmers, valid, found, false);
+    if (times) *times = TigTallyTimes();
+    if (n_bases == 0) return;  // nothing to look at
+    LocateProbe p(ix, seq, off, n);
+    GatherErr err(p.st);
+    const tp::GatherArgs g{p.d_hit, p.store.off, ix->off, t->d_win_off(), n_bases, n, ix->info.records, err.d};
+    tt::tig_tally_add_kernel<<<hu::grid_for((n_bases + RUN - 1) / RUN), hu::EB, 0, p.st>>>(g, t->windows, t->count);
+    HIP_CHECK(hipGetLastError());
+    p.ev.mark(2, p.st);
+    HIP_CHECK(hipStreamSynchronize(p.st));
+    const auto t0 = std::chrono::steady_clock::now();
+    p.download_counts(valid, found);
+    err.fetch(p.st);
+    HIP_CHECK(hipStreamSynchronize(p.st));
+    err.check(fn);
+    if (times) *times = TigTallyTimes{p.store.upload_ms, p.store.pack_ms, p.ev.ms(0, 1), p.ev.ms(1, 2), ms_since(t0)};
+}
+
+void device_tig_tally_coverage(const TigTally *t, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid,
+                               uint64_t *found, uint64_t *covered, uint64_t *sum, uint64_t *max, uint64_t *per_window, TigTallyTimes *times) {
+    const char *fn = "mtg_tig_tally_coverage";
+    const TigIndex *ix = t->ix;
+    const uint64_t n_bases = locate_windows(fn, ix, seq, off, n, kmers, valid, found, n && (!covered || !sum || !max));
+    std::fill(covered, covered + n, 0ull);
+    std::fill(sum, sum + n, 0ull);
+    std::fill(max, max + n, 0ull);
+    if (times) *times = TigTallyTimes();
+    if (n_bases == 0) return;  // nothing to look at
+    LocateProbe p(ix, seq, off, n);
+    hu::DeviceArray<unsigned long long> d_out(3 * n), d_per_window;  // covered, sum, max
+    if (per_window) d_per_window.alloc(n_bases);
+    GatherErr err(p.st);
+    HIP_CHECK(hipMemsetAsync(d_out, 0, 3 * n * 8, p.st));
+    const tp::GatherArgs g{p.d_hit, p.store.off, ix->off, t->d_win_off(), n_bases, n, ix->info.records, err.d};
+    // (one thread per run of positions: every word of per_window is written)
+    tt::tig_coverage_gather_kernel<<<hu::grid_for((n_bases + RUN - 1) / RUN), hu::EB, 0, p.st>>>(g, t->windows, t->count, d_out, d_per_window);
+    HIP_CHECK(hipGetLastError());
+    p.ev.mark(2, p.st);
+    HIP_CHECK(hipStreamSynchronize(p.st));
+    const auto t0 = std::chrono::steady_clock::now();
+    p.download_counts(valid, found);
+    err.fetch(p.st);
+    HIP_CHECK(hipStreamSynchronize(p.st));
+    err.check(fn);
+    hu::download_sliced(covered, d_out.get(), n * 8, p.st, p.device_id);
+    hu::download_sliced(sum, d_out + n, n * 8, p.st, p.device_id);
+    hu::download_sliced(max, d_out + 2 * n, n * 8, p.st, p.device_id);
+    if (per_window) hu::download_sliced(per_window, d_per_window.get(), n_bases * 8, p.st, p.device_id);
+    if (times) *times = TigTallyTimes{p.store.upload_ms, p.store.pack_ms, p.ev.ms(0, 1), p.ev.ms(1, 2), ms_since(t0)};
 }
 
 }  // namespace mtg
