@@ -857,6 +857,45 @@ void mtg_tig_tally_free(mtg_tig_tally *t); /* NULL is fine; any current device *
 /* Of the last mtg_tig_tally_add or mtg_tig_tally_coverage on this thread, in ms: {upload (host clock), pack, probe (tig_locate_kernel
  * with the fill of the hit array), the add or the gather -- HIP events around the kernels --, download (host clock)}. */
 void mtg_last_tig_tally_times(double out[5]);
+/* PSEUDOALIGNMENT against the coloured k-mer set, with EQUIVALENCE CLASSES. A pseudoaligner belongs to one COLOURED
+ * index, a mtg_kmer_index (mtg_kmer_index_build_annotated* with colors) or a mtg_tig_index (mtg_tig_index_build_annotated* with
+ * colors), which must outlive it and which it never changes. C = n_colors, 1 <= C <= 64; mask(x) is what mtg_kmer_index_colors /
+ * mtg_tig_index_colors use: the mask of the class's first occurrence. Exact integers throughout:
+ *  - A FRAGMENT is one query record or, with mates, the pair (record r of the reads, record r of the mates); both sets have n records.
+ *  - kmers, valid and found of a fragment are mtg_kmer_index_query's columns summed over its one or two records (any byte is
+ *    tolerated, a non-ACGT byte costs the windows that cover it, case is folded).
+ *  - hits[c] = the found windows of the fragment whose class's mask has bit c: windows, not distinct k-mers -- per_color of
+ *    mtg_kmer_index_colors summed over the mates. A class with mask 0 is found and touches no colour.
+ *  - params: threshold_permille P in 1 .. 1000; over_valid 0: denom = found, else denom = valid; min_kmers >= 1. NULL params:
+ *    {1000, 0, 1}.
+ *  - Colour c is ASSIGNED iff denom >= min_kmers, hits[c] > 0 and hits[c] * 1000 >= P * denom, in 64-bit integers. masks[f] = the
+ *    bits of the assigned colours. P = 1000 over found: the intersection of the masks of the found windows, the classical
+ *    pseudoalignment; over valid it also requires that every valid window was found.
+ *  - The EQUIVALENCE CLASSES are the distinct non-zero masks since creation or the last reset; per class mask, fragments (how many
+ *    fragments have exactly that mask) and first (the smallest ordinal of such a fragment; ordinals run over every fragment aligned
+ *    since creation or reset, across calls). mtg_pseudoaligner_classes returns them ascending by first, in three arrays of the
+ *    caller's (mtg_free each; all NULL where there is none).
+ *  - totals: fragments, eligible (denom >= min_kmers), assigned (mask != 0), ambiguous (more than one bit), since creation or reset.
+ * The per-colour counters never leave the device; a call downloads 4 x 8 B per fragment and the call's classes. The aligner holds no
+ * device memory between calls. Aborts with the function's name: a null index, an index without colours, P outside 1 .. 1000,
+ * min_kmers = 0, exactly one of mate_seq / mate_off NULL (stores: a mates store with another record count), a fragment with 2^32
+ * windows or more, bad offsets. n = 0 returns at once. */
+typedef struct mtg_pseudoalign_params { uint64_t threshold_permille, over_valid, min_kmers; } mtg_pseudoalign_params;
+typedef struct mtg_pseudoaligner mtg_pseudoaligner;
+mtg_pseudoaligner *mtg_pseudoaligner_create(const mtg_kmer_index *ix, const mtg_pseudoalign_params *p);    /* the index outlives it */
+mtg_pseudoaligner *mtg_pseudoaligner_create_tig(const mtg_tig_index *ix, const mtg_pseudoalign_params *p); /* the index outlives it */
+void mtg_pseudoaligner_align(mtg_pseudoaligner *pa, const char *seq, const uint64_t *off, uint64_t n,
+                             const char *mate_seq, const uint64_t *mate_off,                       /* both NULL: single-end */
+                             uint64_t *kmers, uint64_t *valid, uint64_t *found, uint64_t *masks); /* [n] each */
+void mtg_pseudoaligner_align_store(mtg_pseudoaligner *pa, const mtg_unitigs *reads, const mtg_unitigs *mates, /* mates NULL: single-end */
+                                   uint64_t *kmers, uint64_t *valid, uint64_t *found, uint64_t *masks);
+uint64_t mtg_pseudoaligner_classes(const mtg_pseudoaligner *pa, uint64_t **mask, uint64_t **fragments, uint64_t **first);
+void mtg_pseudoaligner_totals(const mtg_pseudoaligner *pa, uint64_t out[4]); /* fragments, eligible, assigned, ambiguous */
+void mtg_pseudoaligner_reset(mtg_pseudoaligner *pa);
+void mtg_pseudoaligner_free(mtg_pseudoaligner *pa); /* NULL is fine */
+/* Of the last mtg_pseudoaligner_align* on this thread, in ms: {upload (host clock), pack, the colour probe(s), the mask kernel, the
+ * dictionary -- HIP events around the kernels --, download (host clock)}. */
+void mtg_last_pseudoalign_times(double out[6]);
 /* MONOCHROMATIC UNITIGS and COLOUR CLASSES. mtg_compact_unitigs_colored_classes is mtg_compact_unitigs_colored plus
  * *classes, the dictionary of the output store's masks. Number the windows of *out i = 0 .. N - 1 in window order (the indexing of
  * *kmer_colors). A RUN is a maximal stretch of consecutive windows of ONE unitig with equal masks. The classes are the distinct masks,

@@ -14,10 +14,12 @@ from .api import (  # noqa: F401
     MatchtigEdgeData,
     NodeWeightArrayType,
     PerformanceDataType,
+    Pseudoaligner,
     TigAlgorithm,
     TigTally,
     clib_compute_tigs,
     last_phase_seconds,
+    last_pseudoalign_times,
     last_tig_tally_times,
 )
 

@@ -68,6 +68,13 @@ whose Phred quality is below Q.
 `--count-index minimizer` counts on the sparse minimizer index instead of the table (`--count-minimizer-length M`), with one counter per
 window of the indexed text, and `--count-index-over greedytigs` / `eulertigs` indexes the tigs this run wrote: `--count-out` is byte for
 byte the table route's. Queries that asked the same sparse index hand it over.
+`--pseudoalign-fa` (with several `--seq-in` files as colours; not in the reference) pseudoaligns reads to the coloured k-mer set: every
+file is a sample, `--pseudoalign-mate-fa` its second mates, and per fragment the files whose k-mers cover at least
+`--pseudoalign-threshold` of its found (`--pseudoalign-over valid`: valid) k-mers are its colours -- at the default 1, the
+intersection of the colour sets of its found k-mers. `--pseudoalign-out` gets one row per fragment, `--pseudoalign-classes-out` the
+distinct colour sets of each sample with their fragments (the equivalence classes) and `--pseudoalign-summary-out` per colour the
+fragments assigned to it and to it alone. The per-colour counters never leave the GPU; `--pseudoalign-index minimizer` aligns on the
+sparse index with the same files, byte for byte.
 """
 from __future__ import annotations
 
@@ -224,10 +231,41 @@ def main(argv=None) -> int:
     ap.add_argument("--count-index-over", choices=("input", "greedytigs", "eulertigs"),
                     help="with --count-index minimizer: the sequences --count-fa indexes: the input (default) or the tigs this run wrote, "
                          "read back from --greedytigs-fa-out / --eulertigs-fa-out; --count-out keeps one row per unitig")
+    ap.add_argument("--pseudoalign-fa", action="append", metavar="PATH",
+                    help="reads of one sample (fasta or fastq, optionally .gz; any characters) that are pseudoaligned to the colours, the "
+                         "--seq-in files, on the GPU; repeatable, one sample per file; needs --seq-in and one of the three "
+                         "--pseudoalign-*-out (not in the reference)")
+    ap.add_argument("--pseudoalign-mate-fa", action="append", metavar="PATH",
+                    help="the second mates of the i-th --pseudoalign-fa file, record by record: a pair is one fragment; none, or as many "
+                         "as --pseudoalign-fa")
+    ap.add_argument("--pseudoalign-out", metavar="PATH",
+                    help="TSV (.gz => gzip) with one row per fragment of all samples: record (the first mate's name), kmers, valid, found, "
+                         "colors (the 0-based --seq-in files assigned, ascending, comma separated; - for none)")
+    ap.add_argument("--pseudoalign-classes-out", metavar="PATH",
+                    help="TSV (.gz => gzip) sample, class, mask, carriers, fragments: per sample its distinct colour sets, numbered from 0 "
+                         "by their first fragment; mask as in --color-classes-out")
+    ap.add_argument("--pseudoalign-summary-out", metavar="PATH",
+                    help="TSV (.gz => gzip) with one row per colour: color, then per sample <sample>:assigned and <sample>:unique; closing "
+                         "rows #fragments, #eligible, #assigned, #ambiguous: a sample's total under :assigned, - under :unique")
+    ap.add_argument("--pseudoalign-threshold", metavar="T",
+                    help="the share of a fragment's k-mers a colour must carry: a decimal in (0, 1] with at most three places (default 1)")
+    ap.add_argument("--pseudoalign-over", choices=("found", "valid"),
+                    help="the k-mers the threshold is a share of: those found in the set (default) or all valid ones")
+    ap.add_argument("--pseudoalign-min-kmers", type=int, metavar="N",
+                    help="a fragment with fewer than N such k-mers gets no colour (N >= 1, default 1)")
+    ap.add_argument("--pseudoalign-min-base-quality", type=int, metavar="Q",
+                    help="with fastq --pseudoalign-fa / --pseudoalign-mate-fa files: a base whose Phred quality is below Q (0..93) is "
+                         "replaced by N")
+    ap.add_argument("--pseudoalign-index", choices=("table", "minimizer"),
+                    help="the index the reads are aligned on: table (default) or minimizer (the sparse index with the masks by position: "
+                         "the same files)")
+    ap.add_argument("--pseudoalign-minimizer-length", type=int, metavar="M",
+                    help="with --pseudoalign-index minimizer: the minimizer length, 1 .. min(k, 31) (default min(19, ceil(2k/3)))")
     args = ap.parse_args(argv)
 
     classed = bool(args.monochromatic_unitigs or args.color_classes_out or args.unitig_color_classes_out)
-    colored = bool(args.color_matrix_out or args.unitig_colors_out or args.query_colors_out or args.query_index_colors_out or classed)
+    colored = bool(args.color_matrix_out or args.unitig_colors_out or args.query_colors_out or args.query_index_colors_out or classed
+                   or args.pseudoalign_fa)
     if colored and args.seq_in is not None and len(args.seq_in) > MAX_COLORS:
         ap.error(f"{len(args.seq_in)} --seq-in files: at most {MAX_COLORS} files can be told apart as colours")
 
@@ -289,6 +327,34 @@ def main(argv=None) -> int:
             ap.error(f"{flag} needs --count-index minimizer")
     if args.count_minimizer_length is not None and not 1 <= args.count_minimizer_length <= min(args.k, 31):
         ap.error(f"--count-minimizer-length must be in 1..{min(args.k, 31)} (1 .. min(k, 31), as --query-minimizer-length)")
+    args.pseudoalign_permille = None
+    if args.pseudoalign_fa:
+        if args.seq_in is None:
+            ap.error("--pseudoalign-fa needs --seq-in: the colours are the --seq-in files")
+        if not (args.pseudoalign_out or args.pseudoalign_classes_out or args.pseudoalign_summary_out):
+            ap.error("--pseudoalign-fa needs --pseudoalign-out, --pseudoalign-classes-out or --pseudoalign-summary-out")
+        if args.pseudoalign_mate_fa and len(args.pseudoalign_mate_fa) != len(args.pseudoalign_fa):
+            ap.error(f"{len(args.pseudoalign_mate_fa)} --pseudoalign-mate-fa files for {len(args.pseudoalign_fa)} --pseudoalign-fa files: "
+                     "give none, or one per --pseudoalign-fa")
+        args.pseudoalign_permille = _permille(args.pseudoalign_threshold if args.pseudoalign_threshold is not None else "1")
+        if args.pseudoalign_permille is None:
+            ap.error(f"--pseudoalign-threshold must be a decimal in (0, 1] with at most three places, not {args.pseudoalign_threshold!r}")
+        if args.pseudoalign_min_kmers is not None and args.pseudoalign_min_kmers < 1:
+            ap.error("--pseudoalign-min-kmers must be >= 1")
+        if args.pseudoalign_minimizer_length is not None:
+            if args.pseudoalign_index != "minimizer":
+                ap.error("--pseudoalign-minimizer-length needs --pseudoalign-index minimizer")
+            if not 1 <= args.pseudoalign_minimizer_length <= min(args.k, 31):
+                ap.error(f"--pseudoalign-minimizer-length must be in 1..{min(args.k, 31)} (1 .. min(k, 31), as --count-minimizer-length)")
+    else:
+        for flag, value in (("--pseudoalign-mate-fa", args.pseudoalign_mate_fa), ("--pseudoalign-out", args.pseudoalign_out),
+                            ("--pseudoalign-classes-out", args.pseudoalign_classes_out), ("--pseudoalign-summary-out", args.pseudoalign_summary_out),
+                            ("--pseudoalign-threshold", args.pseudoalign_threshold), ("--pseudoalign-over", args.pseudoalign_over),
+                            ("--pseudoalign-min-kmers", args.pseudoalign_min_kmers),
+                            ("--pseudoalign-min-base-quality", args.pseudoalign_min_base_quality), ("--pseudoalign-index", args.pseudoalign_index),
+                            ("--pseudoalign-minimizer-length", args.pseudoalign_minimizer_length)):
+            if value is not None:
+                ap.error(f"{flag} needs --pseudoalign-fa")
     for over, out in (("greedytigs", args.greedytigs_fa_out), ("eulertigs", args.eulertigs_fa_out)):
         if args.count_index_over == over and not out:
             ap.error(f"--count-index-over {over} needs --{over}-fa-out")
@@ -344,14 +410,16 @@ def main(argv=None) -> int:
             ap.error("--min-component-kmers needs --seq-in or --fa-in")
         for flag, value in (("--color-matrix-out", args.color_matrix_out), ("--unitig-colors-out", args.unitig_colors_out),
                             ("--query-colors-out", args.query_colors_out), ("--query-index-colors-out", args.query_index_colors_out),
-                            ("--monochromatic-unitigs", args.monochromatic_unitigs or None), ("--color-classes-out", args.color_classes_out), ("--unitig-color-classes-out", args.unitig_color_classes_out)):
+                            ("--monochromatic-unitigs", args.monochromatic_unitigs or None), ("--color-classes-out", args.color_classes_out), ("--unitig-color-classes-out", args.unitig_color_classes_out),
+                            ("--pseudoalign-fa", args.pseudoalign_fa)):
             if value is not None:
                 ap.error(f"--min-component-kmers cannot be combined with {flag}")
     for flag, value in (("--min-base-quality", args.min_base_quality), ("--query-min-base-quality", args.query_min_base_quality),
-                        ("--count-min-base-quality", args.count_min_base_quality)):
+                        ("--count-min-base-quality", args.count_min_base_quality),
+                        ("--pseudoalign-min-base-quality", args.pseudoalign_min_base_quality)):
         if value is not None and not 0 <= value <= 93:
             ap.error(f"{flag} must be in 0..93")
-    if not (args.color_classes_out or args.unitig_color_classes_out or args.color_matrix_out or args.unitig_colors_out or args.kmer_spectrum_out or args.unitig_abundance_out or args.unitig_kmer_abundance_out or args.query_fa or args.count_fa or args.greedytigs_fa_out or args.eulertigs_fa_out or args.greedytigs_gfa_out or args.eulertigs_gfa_out
+    if not (args.color_classes_out or args.unitig_color_classes_out or args.color_matrix_out or args.unitig_colors_out or args.kmer_spectrum_out or args.unitig_abundance_out or args.unitig_kmer_abundance_out or args.query_fa or args.count_fa or args.pseudoalign_fa or args.greedytigs_fa_out or args.eulertigs_fa_out or args.greedytigs_gfa_out or args.eulertigs_gfa_out
             or args.greedytigs_duplication_bitvector_out or args.matchtigs_fa_out or args.matchtigs_gfa_out or args.verify_fa or args.unitigs_fa_out
             or args.unitigs_bcalm_out or args.unitigs_gfa_out or args.components_out or args.unitig_components_out):
         ap.error("nothing to do: give --greedytigs-fa-out / --greedytigs-gfa-out and/or --eulertigs-fa-out / --eulertigs-gfa-out")
@@ -359,18 +427,35 @@ def main(argv=None) -> int:
     from . import api
 
     # FASTQ is told from FASTA by the content; the quality flags need a file they can apply to
-    fastq = {path for path in (args.seq_in or []) + (args.query_fa or []) + (args.count_fa or []) if api.sequence_file_format(path) == 2}
+    aligned = (args.pseudoalign_fa or []) + (args.pseudoalign_mate_fa or [])
+    fastq = {path for path in (args.seq_in or []) + (args.query_fa or []) + (args.count_fa or []) + aligned if api.sequence_file_format(path) == 2}
     if args.min_base_quality is not None and not fastq.intersection((args.seq_in or []) + (args.query_fa or [])):
         ap.error("--min-base-quality needs a fastq file among --seq-in / --query-fa")
     if args.query_min_base_quality is not None and not fastq.intersection(args.query_fa or []):
         ap.error("--query-min-base-quality needs a fastq file among --query-fa")
     if args.count_min_base_quality is not None and not fastq.intersection(args.count_fa):
         ap.error("--count-min-base-quality needs a fastq file among --count-fa")
+    if args.pseudoalign_min_base_quality is not None and not fastq.intersection(aligned):
+        ap.error("--pseudoalign-min-base-quality needs a fastq file among --pseudoalign-fa / --pseudoalign-mate-fa")
     try:
         return _run(api, args, fastq)
     except api.FastqFormatError as e:  # an error of the input: the message names file, record, line and reason
         print(e, file=sys.stderr)
         return 2
+
+
+def _permille(text: str):
+    """`--pseudoalign-threshold`: a decimal in (0, 1] with at most three places -> its thousandths, 1 .. 1000; None for anything else.
+    Never through a float."""
+    import decimal
+
+    try:
+        t = decimal.Decimal(text)
+    except decimal.InvalidOperation:
+        return None
+    if not t.is_finite() or not 0 < t <= 1 or t * 1000 != (t * 1000).to_integral_value():
+        return None
+    return int(t * 1000)
 
 
 def _read_seq_in(api, args, fastq, record_colors=None):
@@ -406,7 +491,8 @@ def _run(api, args, fastq) -> int:
         graph, store = api.read_bcalm2(args.bcalm_in, args.k)
     elif args.seq_in is not None:  # sequences -> unitigs (GPU compaction) -> graph (the --fa-in join on the same store)
         classed = bool(args.monochromatic_unitigs or args.color_classes_out or args.unitig_color_classes_out)  # 
-        colored = bool(args.color_matrix_out or args.unitig_colors_out or args.query_colors_out or args.query_index_colors_out or classed)  # 
+        colored = bool(args.color_matrix_out or args.unitig_colors_out or args.query_colors_out or args.query_index_colors_out or classed
+                       or args.pseudoalign_fa)  # 
         record_colors = [] if colored else None
         seqs, pieces_cut = _read_seq_in(api, args, fastq, record_colors)
         abundance = colors = cleaning = None
@@ -599,6 +685,10 @@ def _run(api, args, fastq) -> int:
                               keep_index=bool(args.count_fa) and not count_sparse, keep_sparse=share_sparse)
     if args.count_fa:
         _count(api, args, store, fastq, shared_index)
+    if args.pseudoalign_fa:
+        status = _pseudoalign(api, args, store, colors, fastq)
+        if status:
+            return status
     return 0 if all_equal else 1
 
 
@@ -984,6 +1074,77 @@ def _count(api, args, store, fastq=(), index=None) -> None:
             f.write("\t".join(["unitig", "kmers"] + [f"{path}:{what}" for path in args.count_fa for what in ("covered", "sum")]) + "\n")
             rows = np.stack([np.arange(len(kmers), dtype=np.uint64), kmers] + columns, axis=1).tolist() if len(kmers) else []
             f.writelines("\t".join(map(str, row)) + "\n" for row in rows)
+
+
+def _pseudoalign(api, args, store, colors, fastq=()) -> int:
+    """`--pseudoalign-fa`: every file is a sample whose reads are pseudoaligned to the colours of the unitig store's k-mers (DESIGN.md
+    33). One coloured index over the store -- the table, or with `--pseudoalign-index minimizer` the sparse index with the masks by
+    position -- and one aligner serve all samples in turn: align the sample (with its mates), keep the rows, the classes and the
+    per-colour sums, reset. Returns 2 where a sample and its mates differ in their number of records."""
+    import contextlib
+
+    import numpy as np
+
+    def read(path):
+        if path in fastq:
+            seqs, names, _ = api.read_fastq(path, args.pseudoalign_min_base_quality or 0, args.device, named=True)  # (masked bases are N)
+            return seqs, names
+        return api.read_sequences_named(path)  # (any characters, as the queries)
+
+    with contextlib.ExitStack() as stack:
+        sparse = args.pseudoalign_index == "minimizer"
+        if sparse:
+            index = api.TigIndex.annotated(store, args.k, args.pseudoalign_minimizer_length, args.device, colors=colors.kmer_colors,
+                                           n_colors=colors.n_colors)
+        else:
+            index = api.KmerIndex(store, args.k, args.device, colors=colors.kmer_colors, n_colors=colors.n_colors)
+        stack.enter_context(index)
+        aligner = stack.enter_context(api.Pseudoaligner(index, args.pseudoalign_permille, args.pseudoalign_over or "found",
+                                                        args.pseudoalign_min_kmers or 1))
+        print(f"Indexing the input for the pseudoalignment: {_describe_index(index, sparse)}; {colors.n_colors} colours, threshold "
+              f"{args.pseudoalign_permille}/1000 of the {aligner.over} k-mers, at least {aligner.min_kmers}", file=sys.stderr)
+        rows = stack.enter_context(_open_text(args, args.pseudoalign_out)) if args.pseudoalign_out else None
+        classes_out = stack.enter_context(_open_text(args, args.pseudoalign_classes_out)) if args.pseudoalign_classes_out else None
+        if rows is not None:
+            rows.write("record\tkmers\tvalid\tfound\tcolors\n")
+        if classes_out is not None:
+            classes_out.write("sample\tclass\tmask\tcarriers\tfragments\n")
+        columns, totals = [], []
+        for i, path in enumerate(args.pseudoalign_fa):
+            t0 = time.perf_counter()
+            seqs, names = read(path)
+            mates = None
+            if args.pseudoalign_mate_fa:
+                mates, mate_names = read(args.pseudoalign_mate_fa[i])
+                if len(mate_names) != len(names):
+                    print(f"--pseudoalign-fa {path} has {len(names)} records and --pseudoalign-mate-fa {args.pseudoalign_mate_fa[i]} has "
+                          f"{len(mate_names)}: mates pair record by record", file=sys.stderr)
+                    return 2
+            r = aligner.align(seqs, mates)
+            cl, tot = aligner.classes(), aligner.totals
+            columns += list(aligner.color_reads)
+            totals.append(tot)
+            aligner.reset()
+            if rows is not None:
+                masks = r.masks.tolist()
+                shown = {m: ",".join(str(c) for c in range(colors.n_colors) if (m >> c) & 1) or "-" for m in set(masks)}
+                rows.writelines(f"{name}\t{n}\t{v}\t{f}\t{shown[m]}\n" for name, n, v, f, m in zip(
+                    names, r.kmers.tolist(), r.valid.tolist(), r.found.tolist(), masks))
+            if classes_out is not None:
+                classes_out.writelines(f"{path}\t{c}\t{m:x}\t{b}\t{n}\n" for c, (m, b, n) in enumerate(zip(
+                    cl["mask"].tolist(), cl["carriers"].tolist(), cl["fragments"].tolist())))
+            largest = int(np.argmax(cl["fragments"])) if len(cl["mask"]) else -1
+            print(f"Pseudoaligning {path}{' with ' + args.pseudoalign_mate_fa[i] if mates is not None else ''}: {tot['fragments']} fragments, "
+                  f"{tot['eligible']} eligible, {tot['assigned']} assigned, {tot['ambiguous']} ambiguous, {len(cl['mask'])} classes, the largest "
+                  + (f"{int(cl['mask'][largest]):x} with {int(cl['fragments'][largest])} fragments" if largest >= 0 else "none")
+                  + f" in {time.perf_counter() - t0:.1f} s", file=sys.stderr)
+        if args.pseudoalign_summary_out:
+            with _open_text(args, args.pseudoalign_summary_out) as f:
+                f.write("\t".join(["color"] + [f"{path}:{what}" for path in args.pseudoalign_fa for what in ("assigned", "unique")]) + "\n")
+                f.writelines("\t".join([args.seq_in[c]] + [str(int(col[c])) for col in columns]) + "\n" for c in range(colors.n_colors))
+                for what in ("fragments", "eligible", "assigned", "ambiguous"):  # (one value per sample: under its first column)
+                    f.write("\t".join([f"#{what}"] + [x for tot in totals for x in (str(tot[what]), "-")]) + "\n")
+    return 0
 
 
 def _write_query_abundance(index, seqs, names, weighed, profile, valid_bits) -> None:

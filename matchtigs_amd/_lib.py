@@ -437,6 +437,15 @@ def load():
         "mtg_tig_tally_reset": (None, [vp]),
         "mtg_tig_tally_free": (None, [vp]),
         "mtg_last_tig_tally_times": (None, [P(C.c_double)]),
+        "mtg_pseudoaligner_create": (vp, [vp, vp]),
+        "mtg_pseudoaligner_create_tig": (vp, [vp, vp]),
+        "mtg_pseudoaligner_align": (None, [vp, vp, vp, u64, vp, vp, vp, vp, vp, vp]),
+        "mtg_pseudoaligner_align_store": (None, [vp, vp, vp, vp, vp, vp, vp]),
+        "mtg_pseudoaligner_classes": (u64, [vp, P(vp), P(vp), P(vp)]),
+        "mtg_pseudoaligner_totals": (None, [vp, P(u64)]),
+        "mtg_pseudoaligner_reset": (None, [vp]),
+        "mtg_pseudoaligner_free": (None, [vp]),
+        "mtg_last_pseudoalign_times": (None, [P(C.c_double)]),
         "mtg_read_sequences_named": (None, [C.c_char_p, P(vp), P(vp)]),
         "mtg_read_fastq_split": (C.c_int, [C.c_char_p, u64, C.c_int, P(vp), P(MtgFastqStats), C.c_char_p, u64]),
         "mtg_read_fastq_named": (C.c_int, [C.c_char_p, u64, C.c_int, P(vp), P(vp), P(MtgFastqStats), C.c_char_p, u64]),

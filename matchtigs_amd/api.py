@@ -2107,6 +2107,148 @@ def last_tig_tally_times() -> dict:
     return dict(zip(("upload_ms", "pack_ms", "probe_ms", "pass2_ms", "download_ms"), list(out)))
 
 
+@dataclass(frozen=True, eq=False)
+class PseudoalignResult:
+    """What Pseudoaligner.align found, per fragment (numpy uint64 arrays): kmers / valid / found as KmerIndex.query gives them, summed
+    over the fragment's one or two records, and masks: bit c set iff the rule assigns colour c to the fragment. offsets: those of the
+    reads (the first mates)."""
+
+    k: int
+    offsets: np.ndarray
+    kmers: np.ndarray
+    valid: np.ndarray
+    found: np.ndarray
+    masks: np.ndarray
+
+    def colors(self, i: int) -> list[int]:
+        """The colours of fragment i, ascending."""
+        m = int(self.masks[i])
+        return [c for c in range(MAX_COLORS) if (m >> c) & 1]
+
+
+class Pseudoaligner:
+    """Which colours is each read compatible with, and how many reads fall into each distinct colour set? (mtg_pseudoaligner_*,
+    DESIGN.md 33). index: a coloured KmerIndex or a coloured TigIndex (TigIndex.annotated(..., colors=...)), never changed; the
+    aligner keeps a reference to it, and several aligners on one index are independent. A fragment is one record, or with mates the
+    pair of record r of the reads and record r of the mates. Per fragment, hits[c] = its found windows whose k-mer carries colour c
+    (KmerIndex.color_hits' per_color, summed over the mates) and denom = its found windows (over="found") or its valid windows
+    (over="valid"); colour c is assigned iff denom >= min_kmers, hits[c] > 0 and hits[c] * 1000 >= threshold_permille * denom, in
+    integers. threshold_permille=1000 over found is the intersection of the found k-mers' colour sets. The per-colour counters stay
+    on the GPU: a call brings back four words per fragment and its distinct masks. The aligner holds no device memory between calls."""
+
+    def __init__(self, index, threshold_permille: int = 1000, over: str = "found", min_kmers: int = 1):
+        self._h = None
+        if not isinstance(index, (KmerIndex, TigIndex)):
+            raise TypeError("Pseudoaligner aligns on a KmerIndex or a TigIndex")
+        if not index._h:
+            raise ValueError("the index is closed")
+        if not index.colored:
+            raise ValueError("Pseudoaligner needs an index built with colors")
+        if isinstance(threshold_permille, bool) or not isinstance(threshold_permille, (int, np.integer)) or not 1 <= threshold_permille <= 1000:
+            raise ValueError(f"threshold_permille must be an integer in 1..1000, not {threshold_permille!r}")
+        if over not in ("found", "valid"):
+            raise ValueError(f"over must be 'found' or 'valid', not {over!r}")
+        if isinstance(min_kmers, bool) or not isinstance(min_kmers, (int, np.integer)) or not 1 <= min_kmers < 1 << 64:
+            raise ValueError(f"min_kmers must be an integer >= 1, not {min_kmers!r}")
+        self.index = index
+        self.n_colors = index.n_colors
+        self.threshold_permille, self.over, self.min_kmers = int(threshold_permille), over, int(min_kmers)
+        self._L = index._L
+        params = (C.c_uint64 * 3)(self.threshold_permille, int(over == "valid"), self.min_kmers)
+        create = self._L.mtg_pseudoaligner_create if isinstance(index, KmerIndex) else self._L.mtg_pseudoaligner_create_tig
+        self._h = create(index._h, C.cast(params, C.c_void_p))
+
+    def close(self) -> None:
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            self._L.mtg_pseudoaligner_free(h)
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _open(self) -> None:
+        """The aligner open and its index open, else ValueError: before the library is asked."""
+        if not self._h:
+            raise ValueError("the aligner is closed")
+        if not self.index._h:
+            raise ValueError("the index is closed")
+
+    def align(self, seqs_or_store, mates=None) -> PseudoalignResult:
+        """One fragment per record of seqs_or_store (UnitigStore, list of str, or (uint8 array, offsets); ANY bytes); mates: the
+        second mates in the same order, as many records. The fragments take the next ordinals of the aligner."""
+        self._open()
+        d, o, n, keep, off, kmers, valid, found = self.index._probe_inputs(seqs_or_store)
+        masks = np.zeros(n, np.uint64)
+        md = mo = keep_m = None
+        if mates is not None:
+            md, mo, mn, keep_m = _sequence_arrays(mates)
+            if mn != n:
+                raise ValueError(f"{n} reads and {mn} mates: the mates pair with the reads record by record")
+            if md is None:  # (mates without a base: the library tells the mates from the two pointers)
+                keep_m = (keep_m, np.zeros(1, np.uint8))
+                md = _ptr(keep_m[1])
+        outs = (_ptr(kmers), _ptr(valid), _ptr(found), _ptr(masks))
+        if isinstance(seqs_or_store, UnitigStore) and (mates is None or isinstance(mates, UnitigStore)):
+            self._L.mtg_pseudoaligner_align_store(self._h, seqs_or_store.handle, None if mates is None else mates.handle, *outs)
+        else:
+            self._L.mtg_pseudoaligner_align(self._h, d, o, n, md, mo, *outs)
+        del keep, keep_m
+        return PseudoalignResult(self.index.info.k, off, kmers, valid, found, masks)
+
+    def classes(self) -> dict:
+        """The equivalence classes since creation or reset(), ordered by their first fragment: {"mask", "carriers" (the colours in
+        the mask), "fragments" (the fragments with exactly that mask), "first" (the smallest ordinal of one)} as uint64 arrays."""
+        self._open()
+        ptrs = [C.c_void_p() for _ in range(3)]
+        n = int(self._L.mtg_pseudoaligner_classes(self._h, *(C.byref(p) for p in ptrs)))
+        mask, fragments, first = [_taken(n, p, np.uint64) for p in ptrs]
+        for p in ptrs:
+            self._L.mtg_free(p)
+        carriers = np.array([bin(int(m)).count("1") for m in mask], np.uint64)
+        return {"mask": mask, "carriers": carriers, "fragments": fragments, "first": first}
+
+    @property
+    def totals(self) -> dict:
+        """Since creation or reset(): fragments, eligible (denom >= min_kmers), assigned (a colour at least), ambiguous (two at least)."""
+        self._open()
+        out = (C.c_uint64 * 4)()
+        self._L.mtg_pseudoaligner_totals(self._h, out)
+        return dict(zip(("fragments", "eligible", "assigned", "ambiguous"), (int(x) for x in out)))
+
+    @property
+    def color_reads(self):
+        """(assigned[n_colors], unique[n_colors]): the fragments whose mask has the colour, and those whose mask is that colour alone."""
+        cl = self.classes()
+        assigned, unique = np.zeros(self.n_colors, np.uint64), np.zeros(self.n_colors, np.uint64)
+        for m, f in zip(cl["mask"], cl["fragments"]):
+            m = int(m)
+            for c in range(self.n_colors):
+                if (m >> c) & 1:
+                    assigned[c] += f
+                    if m == 1 << c:
+                        unique[c] += f
+        return assigned, unique
+
+    def reset(self) -> None:
+        """No class, every total zero, the next fragment has the ordinal 0."""
+        self._open()
+        self._L.mtg_pseudoaligner_reset(self._h)
+
+
+def last_pseudoalign_times() -> dict:
+    """Phases of the last Pseudoaligner.align on this thread, in ms (HIP events around the kernels; upload and download by the host
+    clock): probe = the colour probe of the reads and of the mates, mask = the counters to one mask per fragment, dictionary = the
+    distinct masks and their compaction."""
+    out = (C.c_double * 6)()
+    _lib.load().mtg_last_pseudoalign_times(out)
+    return dict(zip(("upload_ms", "pack_ms", "probe_ms", "mask_ms", "dictionary_ms", "download_ms"), list(out)))
+
+
 def last_tig_locate_times() -> dict:
     """Phases of the last TigIndex.locate on this thread, in ms (HIP events around the kernels; the upload by the host clock): probe =
     the lookup of every window with its position and strand (with the fill of the hit array), runs = folding the hits into runs."""

@@ -287,6 +287,27 @@ void device_tig_tally_coverage(const TigTally *t, const char *seq, const uint64_
 void device_tig_tally_counters(const TigTally *t, uint64_t *out);
 void device_tig_tally_reset(TigTally *t);
 void device_tig_tally_free(TigTally *t);
+// Pseudoalignment on a coloured index of either kind (pseudoalign_device.hpp; include/mtg_engine.h states the rule).
+// A fragment is record r of the reads or, with mates (both pointers given, the same n), the pair of record r of each: kmers, valid and
+// found are the query's columns summed over its records, masks[f] the colours the rule assigns. base: the ordinal of fragment 0.
+// *out: the call's equivalence classes in no particular order, its totals, and the phases -- host wall clock of the uploads and the
+// download, HIP-event time of the kernels (probe: every colour probe of the call).
+struct PseudoalignRule {
+    uint64_t permille, min_kmers;
+    uint32_t over_valid;  // the denominator: 0 found, 1 valid
+};
+struct PseudoalignCall {
+    std::vector<uint64_t> mask, fragments, first;
+    uint64_t eligible = 0, assigned = 0, ambiguous = 0;
+    double upload_ms = 0, pack_ms = 0, probe_ms = 0, mask_ms = 0, dictionary_ms = 0, download_ms = 0;
+};
+void device_kmer_index_pseudoalign(const KmerIndex *ix, const PseudoalignRule &rule, uint64_t base, const char *seq, const uint64_t *off, uint64_t n,
+                                   const char *mate_seq, const uint64_t *mate_off, uint64_t *kmers, uint64_t *valid, uint64_t *found, uint64_t *masks,
+                                   PseudoalignCall *out);
+uint64_t device_tig_index_n_colors(const TigIndex *ix);  // 0: not coloured
+void device_tig_index_pseudoalign(const TigIndex *ix, const PseudoalignRule &rule, uint64_t base, const char *seq, const uint64_t *off, uint64_t n,
+                                  const char *mate_seq, const uint64_t *mate_off, uint64_t *kmers, uint64_t *valid, uint64_t *found, uint64_t *masks,
+                                  PseudoalignCall *out);
 // compact_device.hip: the maximal unitigs of the k-mer set of arbitrary sequences (the file's header and DESIGN.md 16 state the
 // contract), as an ordinary sequence store. times: host wall clock of upload, download and the whole call, HIP-event time of the
 // kernel phases, the pointer-jumping rounds, the bytes the kernels must move at the least, the arena's peak of live bytes.

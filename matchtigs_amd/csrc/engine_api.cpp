@@ -1032,6 +1032,106 @@ void mtg_last_tig_tally_times(double out[5]) {
     const TigTallyTimes &t = g_last_tig_tally;
     out[0] = t.upload_ms; out[1] = t.pack_ms; out[2] = t.probe_ms; out[3] = t.pass2_ms; out[4] = t.download_ms;
 }
+// ---- pseudoalignment with equivalence classes on either coloured index (pseudoalign_device.hpp) ----
+// The aligner is host state only: the rule, the dictionary of the masks seen so far and the totals. A call's device work is transient.
+struct mtg_pseudoaligner {
+    const KmerIndex *table;  // one of the two
+    const TigIndex *sparse;
+    PseudoalignRule rule;
+    struct Class { uint64_t mask, fragments, first; };
+    std::vector<Class> classes;  // (in no particular order: mtg_pseudoaligner_classes sorts)
+    uint64_t totals[4] = {0, 0, 0, 0};
+};
+static thread_local PseudoalignCall g_last_pseudoalign;
+static mtg_pseudoaligner *pseudoaligner_new(const char *fn, const KmerIndex *table, const TigIndex *sparse, const mtg_pseudoalign_params *p) {
+    const mtg_pseudoalign_params q = p ? *p : mtg_pseudoalign_params{1000, 0, 1};
+    const uint64_t C = table ? device_kmer_index_n_colors(table) : device_tig_index_n_colors(sparse);
+    if (!C) MTG_DIE("%s: the index keeps no colours (build it with %s)", fn, table ? "mtg_kmer_index_build_annotated" : "mtg_tig_index_build_annotated");
+    if (q.threshold_permille < 1 || q.threshold_permille > 1000)
+        MTG_DIE("%s: threshold_permille %llu is outside 1 .. 1000", fn, (unsigned long long)q.threshold_permille);
+    if (q.min_kmers < 1) MTG_DIE("%s: min_kmers must be >= 1", fn);
+    return new mtg_pseudoaligner{table, sparse, PseudoalignRule{q.threshold_permille, q.min_kmers, q.over_valid ? 1u : 0u}, {}, {0, 0, 0, 0}};
+}
+mtg_pseudoaligner *mtg_pseudoaligner_create(const mtg_kmer_index *ix, const mtg_pseudoalign_params *p) {
+    if (!ix) MTG_DIE("mtg_pseudoaligner_create: null argument");
+    return pseudoaligner_new("mtg_pseudoaligner_create", ix->ix, nullptr, p);
+}
+mtg_pseudoaligner *mtg_pseudoaligner_create_tig(const mtg_tig_index *ix, const mtg_pseudoalign_params *p) {
+    if (!ix) MTG_DIE("mtg_pseudoaligner_create_tig: null argument");
+    return pseudoaligner_new("mtg_pseudoaligner_create_tig", nullptr, ix->ix, p);
+}
+void mtg_pseudoaligner_align(mtg_pseudoaligner *pa, const char *seq, const uint64_t *off, uint64_t n, const char *mate_seq, const uint64_t *mate_off,
+                             uint64_t *kmers, uint64_t *valid, uint64_t *found, uint64_t *masks) {
+    if (!pa) MTG_DIE("mtg_pseudoaligner_align: null argument");
+    if ((mate_seq == nullptr) != (mate_off == nullptr)) MTG_DIE("mtg_pseudoaligner_align: mate_seq and mate_off go together (both NULL: single-end)");
+    g_last_pseudoalign = PseudoalignCall();
+    if (n == 0) return;
+    PseudoalignCall &call = g_last_pseudoalign;
+    if (pa->table) device_kmer_index_pseudoalign(pa->table, pa->rule, pa->totals[0], seq, off, n, mate_seq, mate_off, kmers, valid, found, masks, &call);
+    else device_tig_index_pseudoalign(pa->sparse, pa->rule, pa->totals[0], seq, off, n, mate_seq, mate_off, kmers, valid, found, masks, &call);
+    // the call's classes into the aligner's (a few masks as a rule: a sorted copy of the keys, then a binary search per class)
+    std::vector<std::pair<uint64_t, size_t>> known(pa->classes.size());
+    for (size_t i = 0; i < known.size(); i++) known[i] = {pa->classes[i].mask, i};
+    std::sort(known.begin(), known.end());
+    for (size_t i = 0; i < call.mask.size(); i++) {
+        auto it = std::lower_bound(known.begin(), known.end(), std::make_pair(call.mask[i], (size_t)0));
+        if (it != known.end() && it->first == call.mask[i]) {
+            mtg_pseudoaligner::Class &c = pa->classes[it->second];
+            c.fragments += call.fragments[i];
+            c.first = std::min(c.first, call.first[i]);
+        } else {
+            pa->classes.push_back({call.mask[i], call.fragments[i], call.first[i]});  // (a call's masks are distinct)
+        }
+    }
+    pa->totals[0] += n;
+    pa->totals[1] += call.eligible;
+    pa->totals[2] += call.assigned;
+    pa->totals[3] += call.ambiguous;
+}
+void mtg_pseudoaligner_align_store(mtg_pseudoaligner *pa, const mtg_unitigs *reads, const mtg_unitigs *mates, uint64_t *kmers, uint64_t *valid,
+                                   uint64_t *found, uint64_t *masks) {
+    if (!pa || !reads) MTG_DIE("mtg_pseudoaligner_align_store: null argument");
+    const UnitigStore &s = *reads->s;
+    const uint64_t n = s.off.size() - 1;
+    if (mates && mates->s->off.size() - 1 != n)
+        MTG_DIE("mtg_pseudoaligner_align_store: %llu reads and %llu mates", (unsigned long long)n, (unsigned long long)(mates->s->off.size() - 1));
+    // (a store without bases may have no data pointer: the mates are told from the offsets)
+    static const char none = 0;
+    const char *mate_seq = mates ? (mates->s->data.data() ? mates->s->data.data() : &none) : nullptr;
+    mtg_pseudoaligner_align(pa, s.data.data(), s.off.data(), n, mate_seq, mates ? mates->s->off.data() : nullptr, kmers, valid, found, masks);
+}
+uint64_t mtg_pseudoaligner_classes(const mtg_pseudoaligner *pa, uint64_t **mask, uint64_t **fragments, uint64_t **first) {
+    if (!pa || !mask || !fragments || !first) MTG_DIE("mtg_pseudoaligner_classes: null argument");
+    std::vector<mtg_pseudoaligner::Class> sorted = pa->classes;
+    std::sort(sorted.begin(), sorted.end(), [](const mtg_pseudoaligner::Class &a, const mtg_pseudoaligner::Class &b) { return a.first < b.first; });
+    const size_t n = sorted.size();
+    *mask = *fragments = *first = nullptr;
+    if (!n) return 0;
+    *mask = (uint64_t *)std::malloc(n * 8);
+    *fragments = (uint64_t *)std::malloc(n * 8);
+    *first = (uint64_t *)std::malloc(n * 8);
+    if (!*mask || !*fragments || !*first) MTG_DIE("mtg_pseudoaligner_classes: out of memory");
+    for (size_t i = 0; i < n; i++) {
+        (*mask)[i] = sorted[i].mask;
+        (*fragments)[i] = sorted[i].fragments;
+        (*first)[i] = sorted[i].first;
+    }
+    return n;
+}
+void mtg_pseudoaligner_totals(const mtg_pseudoaligner *pa, uint64_t out[4]) {
+    if (!pa || !out) MTG_DIE("mtg_pseudoaligner_totals: null argument");
+    std::copy(pa->totals, pa->totals + 4, out);
+}
+void mtg_pseudoaligner_reset(mtg_pseudoaligner *pa) {
+    if (!pa) MTG_DIE("mtg_pseudoaligner_reset: null argument");
+    pa->classes.clear();
+    std::fill(pa->totals, pa->totals + 4, 0ull);
+}
+void mtg_pseudoaligner_free(mtg_pseudoaligner *pa) { delete pa; }
+void mtg_last_pseudoalign_times(double out[6]) {
+    const PseudoalignCall &t = g_last_pseudoalign;
+    out[0] = t.upload_ms; out[1] = t.pack_ms; out[2] = t.probe_ms; out[3] = t.mask_ms; out[4] = t.dictionary_ms; out[5] = t.download_ms;
+}
 void mtg_tig_index_free(mtg_tig_index *ix) {
     if (!ix) return;
     device_tig_index_free(ix->ix);

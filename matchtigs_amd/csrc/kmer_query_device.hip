@@ -81,6 +81,11 @@
 // Integer sums and maxima: nothing depends on the launch geometry or on the order the atomics land in. A call is limited like a
 // query (fewer than 2^40 - 1 bases), so a counter cannot overflow. Coverage takes 8 + 8 + 8 B per record and, with per_window,
 // 8 B per base beside the query's store.
+//
+// Pseudoalignment (a COLOURED index only, mtg_pseudoaligner_*). The colour call's counters stay on the device: the
+// unchanged color_query_kernel runs once for the reads and, with mates, once more for the mates into the same per_color and counts,
+// and pseudoalign_device.hpp turns every row into one mask and the masks into their dictionary. Only 4 x 8 B per fragment and the
+// classes come back. A call takes (4 C + 16) B per fragment beside one side's store, then at most 180 B per fragment for the masks and the dictionary.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -90,6 +95,7 @@
 #include "kmer_runs_device.hpp"
 #include "kmer_window_device.hpp"
 #include "pack_device.hpp"
+#include "pseudoalign_device.hpp"
 
 namespace mtg {
 
@@ -708,6 +714,59 @@ void device_kmer_index_colors(const KmerIndex *ix, const char *seq, const uint64
         p.booked(&times->upload_ms, &times->pack_ms, &times->probe_ms);
         times->download_ms = ms_since(t0);
     }
+}
+
+// ---- pseudoalignment ----
+// color_query_kernel, unchanged, once per side into one pair of arrays that stay on the device; pa::reduce does the rest.
+void device_kmer_index_pseudoalign(const KmerIndex *ix, const PseudoalignRule &rule, uint64_t base, const char *seq, const uint64_t *off, uint64_t n,
+                                   const char *mate_seq, const uint64_t *mate_off, uint64_t *kmers, uint64_t *valid, uint64_t *found, uint64_t *masks,
+                                   PseudoalignCall *out) {
+    const char *fn = "mtg_pseudoaligner_align";
+    if (!ix->color) MTG_DIE("%s: the index keeps no colours (build it with mtg_kmer_index_build_annotated)", fn);
+    const uint64_t C = ix->n_colors, k = ix->info.k;
+    const bool paired = mate_off != nullptr;
+    uint64_t side_bases[2] = {probe_windows(fn, k, seq, off, n, kmers, valid, found, n && !masks), 0};
+    if (paired) {
+        std::vector<uint64_t> mk(n), mv(n), mf(n);
+        side_bases[1] = probe_windows(fn, k, mate_seq, mate_off, n, mk.data(), mv.data(), mf.data(), false);
+        for (uint64_t r = 0; r < n; r++) kmers[r] += mk[r];
+    }
+    for (uint64_t r = 0; r < n; r++)
+        if (kmers[r] >> 32) MTG_DIE("%s: fragment %llu has %llu windows; the per-colour counters are 32-bit", fn, (unsigned long long)r,
+                                    (unsigned long long)kmers[r]);
+    std::fill(masks, masks + n, 0ull);
+    *out = PseudoalignCall();
+    if (side_bases[0] + side_bases[1] == 0) return;  // nothing to look at: no fragment is eligible
+    on_device(ix->device_id);
+    hipStream_t st = nullptr;
+    hu::DeviceArray<unsigned long long> d_counts(2 * n);
+    hu::DeviceArray<uint32_t> d_hits(n * C);
+    HIP_CHECK(hipMemsetAsync(d_counts, 0, 2 * n * 8, st));
+    HIP_CHECK(hipMemsetAsync(d_hits, 0, n * C * 4, st));
+    for (int side = 0; side < 2; side++) {
+        const uint64_t n_bases = side_bases[side];
+        if (!n_bases) continue;
+        MaskedSeqStore store(side ? mate_seq : seq, side ? mate_off : off, n, st, ix->device_id);
+        IndexArgs a{};
+        a.packed = store.packed; a.off = store.off; a.index_packed = ix->packed; a.table = ix->table; a.slots = ix->info.slots;
+        kw::window_args_set_k(a, k);
+        PhaseEvents<2> ev;
+        ev.mark(0, st);
+        const unsigned grid = hu::grid_for((n_bases + RUN - 1) / RUN);
+        if (k >= 32) color_query_kernel<true><<<grid, hu::EB, 0, st>>>(a, store.bad, n_bases, n, d_counts, ix->color, (uint32_t)C, d_hits, nullptr);
+        else color_query_kernel<false><<<grid, hu::EB, 0, st>>>(a, store.bad, n_bases, n, d_counts, ix->color, (uint32_t)C, d_hits, nullptr);
+        HIP_CHECK(hipGetLastError());
+        ev.mark(1, st);
+        out->upload_ms += store.upload_ms;
+        out->pack_ms += store.pack_ms;
+        out->probe_ms += ev.ms(0, 1);  // (waits: the side's store may go)
+    }
+    pa::reduce(fn, d_hits, d_counts, n, (uint32_t)C, rule, base, st, ix->device_id, masks, out);
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_CHECK(hipMemcpyAsync(valid, d_counts, n * 8, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(found, d_counts + n, n * 8, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    out->download_ms += ms_since(t0);
 }
 
 // ---- tally ----

@@ -45,6 +45,10 @@
 // not by the index. The same two passes: tig_locate_kernel, then tig_tally_add_kernel or tig_coverage_gather_kernel
 // (tig_tally_device.hpp) over hit[]. t is the same for every window of a class, so the counter at its ordinal is the class's.
 //
+// Pseudoalignment (a COLOURED index only, mtg_pseudoaligner_*): the colour call's two passes, unchanged, once for the
+// reads and, with mates, once more for the mates into per_color and counts arrays that stay on the device; pseudoalign_device.hpp
+// turns every row into one mask and the masks into their dictionary.
+//
 // Exactness. A hit is declared only after kw::same_class has compared the query's k bases with k index bases that lie inside ONE
 // record, or after the heavy table's exact `same`: never a false positive, and a tag or hash collision costs a compare. No false
 // negative: let the class of the query window x be the index window y at c. Both have the same set of m-mer classes, hence the same
@@ -65,6 +69,7 @@
 #include "kmer_runs_device.hpp"
 #include "kmer_window_device.hpp"
 #include "pack_device.hpp"
+#include "pseudoalign_device.hpp"
 #include "tig_payload_device.hpp"
 #include "tig_tally_device.hpp"
 
@@ -652,7 +657,8 @@ int on_device(int device_id) {
 }
 
 // ... and the first pass of a query that has bases: the query on the index's device and tig_locate_kernel between the marks 0 and 1
-// of ev; d_counts: [2 n] valid then found, d_hit: [n_bases]. The caller queues its second pass and marks 2.
+// of ev; d_counts: [2 n] valid then found, d_hit: [n_bases]. The caller queues its second pass and marks 2. into: the caller's own
+// [2 n] counters, which the pass adds to as they are, in place of d_counts.
 struct LocateProbe {
     const uint64_t n;
     const int device_id;
@@ -661,9 +667,10 @@ struct LocateProbe {
     hu::DeviceArray<unsigned long long> d_counts, d_hit;
     PhaseEvents<3> ev;
 
-    LocateProbe(const TigIndex *ix, const char *seq, const uint64_t *off, uint64_t n)
-        : n(n), device_id(on_device(ix->device_id)), store(seq, off, n, st, device_id), d_counts(2 * n), d_hit(store.n_bases) {
+    LocateProbe(const TigIndex *ix, const char *seq, const uint64_t *off, uint64_t n, unsigned long long *into = nullptr)
+        : n(n), device_id(on_device(ix->device_id)), store(seq, off, n, st, device_id), d_hit(store.n_bases) {
         const uint64_t k = ix->info.k, n_bases = store.n_bases;
+        unsigned long long *counts = into ? into : d_counts.alloc(2 * n);
         TigArgs a{};
         a.packed = store.packed; a.off = store.off;
         a.index_packed = ix->packed; a.index_off = ix->off; a.index_rec = ix->info.records;
@@ -671,11 +678,11 @@ struct LocateProbe {
         a.mn = MinArgs{ix->info.m, k - ix->info.m + 1, 2 * (ix->info.m - 1), (1ull << (2 * ix->info.m)) - 1};
         kw::window_args_set_k(a, k);
         ev.mark(0, st);
-        HIP_CHECK(hipMemsetAsync(d_counts, 0, 2 * n * 8, st));
+        if (!into) HIP_CHECK(hipMemsetAsync(counts, 0, 2 * n * 8, st));
         HIP_CHECK(hipMemsetAsync(d_hit, 0xFF, n_bases * 8, st));
         const unsigned grid = hu::grid_for((n_bases + RUN - 1) / RUN);
-        if (k >= 32) tig_locate_kernel<true><<<grid, hu::EB, 0, st>>>(a, store.bad, n_bases, n, d_counts, ix->heavy_where.get(), d_hit);
-        else tig_locate_kernel<false><<<grid, hu::EB, 0, st>>>(a, store.bad, n_bases, n, d_counts, ix->heavy_where.get(), d_hit);
+        if (k >= 32) tig_locate_kernel<true><<<grid, hu::EB, 0, st>>>(a, store.bad, n_bases, n, counts, ix->heavy_where.get(), d_hit);
+        else tig_locate_kernel<false><<<grid, hu::EB, 0, st>>>(a, store.bad, n_bases, n, counts, ix->heavy_where.get(), d_hit);
         HIP_CHECK(hipGetLastError());
         ev.mark(1, st);
     }
@@ -849,6 +856,60 @@ void device_tig_index_colors(const TigIndex *ix, const char *seq, const uint64_t
     hu::download_sliced(per_color, d_per_color, n * C * 4, p.st, p.device_id);
     if (per_window) hu::download_sliced(per_window, d_per_window, n_bases * 8, p.st, p.device_id);
     if (times) p.booked(times);
+}
+
+// ---- pseudoalignment ----
+uint64_t device_tig_index_n_colors(const TigIndex *ix) { return ix->colors.present() ? ix->n_colors : 0; }
+
+// tig_locate_kernel and tp::color_gather_kernel, unchanged, once per side into one pair of arrays that stay on the device; pa::reduce
+// does the rest.
+void device_tig_index_pseudoalign(const TigIndex *ix, const PseudoalignRule &rule, uint64_t base, const char *seq, const uint64_t *off, uint64_t n,
+                                  const char *mate_seq, const uint64_t *mate_off, uint64_t *kmers, uint64_t *valid, uint64_t *found, uint64_t *masks,
+                                  PseudoalignCall *out) {
+    const char *fn = "mtg_pseudoaligner_align";
+    if (!ix->colors.present()) MTG_DIE("%s: the index keeps no colours (build it with mtg_tig_index_build_annotated)", fn);
+    const uint64_t C = ix->n_colors;
+    const bool paired = mate_off != nullptr;
+    uint64_t side_bases[2] = {locate_windows(fn, ix, seq, off, n, kmers, valid, found, n && !masks), 0};
+    if (paired) {
+        std::vector<uint64_t> mk(n), mv(n), mf(n);
+        side_bases[1] = locate_windows(fn, ix, mate_seq, mate_off, n, mk.data(), mv.data(), mf.data(), false);
+        for (uint64_t r = 0; r < n; r++) kmers[r] += mk[r];
+    }
+    for (uint64_t r = 0; r < n; r++)
+        if (kmers[r] >> 32) MTG_DIE("%s: fragment %llu has %llu windows; the per-colour counters are 32-bit", fn, (unsigned long long)r,
+                                    (unsigned long long)kmers[r]);
+    std::fill(masks, masks + n, 0ull);
+    *out = PseudoalignCall();
+    if (side_bases[0] + side_bases[1] == 0) return;  // nothing to look at: no fragment is eligible
+    on_device(ix->device_id);
+    hipStream_t st = nullptr;
+    hu::DeviceArray<unsigned long long> d_counts(2 * n);
+    hu::DeviceArray<uint32_t> d_hits(n * C);
+    HIP_CHECK(hipMemsetAsync(d_counts, 0, 2 * n * 8, st));
+    HIP_CHECK(hipMemsetAsync(d_hits, 0, n * C * 4, st));
+    for (int side = 0; side < 2; side++) {
+        const uint64_t n_bases = side_bases[side];
+        if (!n_bases) continue;
+        LocateProbe p(ix, side ? mate_seq : seq, side ? mate_off : off, n, d_counts);
+        GatherErr err(p.st);
+        tp::color_gather_kernel<<<hu::grid_for((n_bases + RUN - 1) / RUN), hu::EB, 0, p.st>>>(p.gather_args(ix, err.d), ix->colors.view(), (uint32_t)C, d_hits,
+                                                                                             nullptr);
+        HIP_CHECK(hipGetLastError());
+        p.ev.mark(2, p.st);
+        err.fetch(p.st);
+        HIP_CHECK(hipStreamSynchronize(p.st));
+        err.check(fn);
+        out->upload_ms += p.store.upload_ms;
+        out->pack_ms += p.store.pack_ms;
+        out->probe_ms += p.ev.ms(0, 2);  // (the locate pass and the gather)
+    }
+    pa::reduce(fn, d_hits, d_counts, n, (uint32_t)C, rule, base, st, ix->device_id, masks, out);
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_CHECK(hipMemcpyAsync(valid, d_counts, n * 8, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(found, d_counts + n, n * 8, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    out->download_ms += ms_since(t0);
 }
 
 // ---- tallies by position ----
