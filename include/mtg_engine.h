@@ -896,6 +896,45 @@ void mtg_pseudoaligner_free(mtg_pseudoaligner *pa); /* NULL is fine */
 /* Of the last mtg_pseudoaligner_align* on this thread, in ms: {upload (host clock), pack, the colour probe(s), the mask kernel, the
  * dictionary -- HIP events around the kernels --, download (host clock)}. */
 void mtg_last_pseudoalign_times(double out[6]);
+/* READ CORRECTION against the indexed k-mer set: substitution errors of the query's records are put right where the
+ * set says how. Any mtg_kmer_index serves, for any k it takes, and is never changed. Exact integers throughout:
+ *  - The SOLID SET is the index's k-mer set: whatever cleaning or threshold formed the indexed sequences decides what is solid.
+ *  - A record x[0..n) has the windows i = 0 .. n - k. A base is GOOD iff it is one of ACGTacgt (case is folded, as in
+ *    mtg_kmer_index_query). A window is VALID iff all its k bases are good, and PRESENT iff it is valid and its class is in the set.
+ *    cover(p) = the valid windows i with max(0, p - k + 1) <= i <= min(p, n - k).
+ *  - params: min_solid W >= 1, rounds R in 1 .. 8. NULL params: {4, 2}.
+ *  - ONE ROUND; every decision is made against the round's input text, all substitutions are applied together afterwards:
+ *      1. p is a CANDIDATE iff x[p] is good, cover(p) is not empty and no window of cover(p) is present.
+ *      2. For a candidate and each of the three bases b != x[p] (compared as upper-case ACGT): S(p, b) = the number of windows of
+ *         cover(p) that are in the set when x[p] alone is replaced by b.
+ *      3. best = max over b of S(p, b), need = min(W, |cover(p)|). best < need: nothing happens. Two or more b attain best (and
+ *         best >= need): p is AMBIGUOUS and nothing happens. Otherwise x[p] is substituted by that b.
+ *  - Round r + 1 runs on round r's output. A substituted position is covered by a present window from then on and is never a
+ *    candidate again, provided no other substitution of the same round lies within k - 1 of it (two such are each scored against
+ *    the other's old base; a window that holds both may be solid with neither pair, and the position may be substituted again). A
+ *    round that substitutes nothing anywhere ends the rounds: every later one would be identical.
+ *  - Per record: kmers, valid, found = mtg_kmer_index_query's columns on the input; found_after = found on the final text;
+ *    candidates = the candidates of round 1; ambiguous = the ambiguous positions of round R; corrected = the positions substituted
+ *    over all rounds: those whose base in the final text is not the input's.
+ *  - Per call: the substitutions as *positions (index into the concatenated query data, ascending, each once) and *bases ('A', 'C',
+ *    'G' or 'T', the base of the final text; the caller keeps the case of the letter it replaces), *n_substitutions entries each,
+ *    malloc'd (mtg_free each; both NULL where there is none); round_corrected[r] = the substitutions made in round r + 1, 0 for
+ *    the rounds not run (their sum exceeds *n_substitutions only where a position was substituted twice).
+ * The bit arrays, the candidates and the text never leave the device; a call downloads 5 x 8 B per record and 9 B per substitution
+ * and holds no device memory afterwards. Aborts with the function's name: min_solid = 0, rounds outside 1 .. 8, a null argument, bad
+ * offsets, 2^40 - 1 bases or more. n = 0 returns at once. The cost of a candidate grows with k^2 for k >= 32. */
+typedef struct mtg_correct_params { uint32_t min_solid, rounds; } mtg_correct_params;
+void mtg_kmer_index_correct(const mtg_kmer_index *ix, const char *seq, const uint64_t *off, uint64_t n, const mtg_correct_params *params,
+                            uint64_t *kmers, uint64_t *valid, uint64_t *found, uint64_t *found_after, /* [n] each */
+                            uint64_t *candidates, uint64_t *ambiguous, uint64_t *corrected,           /* [n] each */
+                            uint64_t **positions, uint8_t **bases, uint64_t *n_substitutions, uint64_t round_corrected[8]);
+void mtg_kmer_index_correct_store(const mtg_kmer_index *ix, const mtg_unitigs *reads, const mtg_correct_params *params,
+                                  uint64_t *kmers, uint64_t *valid, uint64_t *found, uint64_t *found_after,
+                                  uint64_t *candidates, uint64_t *ambiguous, uint64_t *corrected,
+                                  uint64_t **positions, uint8_t **bases, uint64_t *n_substitutions, uint64_t round_corrected[8]);
+/* Of the last mtg_kmer_index_correct* on this thread, in ms: {upload (host clock), pack, the query passes, flag and compaction, the
+ * evaluation, apply -- HIP events around the kernels --, download (host clock), the whole call (host clock)}. */
+void mtg_last_kmer_correct_times(double out[8]);
 /* MONOCHROMATIC UNITIGS and COLOUR CLASSES. mtg_compact_unitigs_colored_classes is mtg_compact_unitigs_colored plus
  * *classes, the dictionary of the output store's masks. Number the windows of *out i = 0 .. N - 1 in window order (the indexing of
  * *kmer_colors). A RUN is a maximal stretch of consecutive windows of ONE unitig with equal masks. The classes are the distinct masks,

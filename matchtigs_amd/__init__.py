@@ -15,9 +15,11 @@ from .api import (  # noqa: F401
     NodeWeightArrayType,
     PerformanceDataType,
     Pseudoaligner,
+    ReadCorrector,
     TigAlgorithm,
     TigTally,
     clib_compute_tigs,
+    last_kmer_correct_times,
     last_phase_seconds,
     last_pseudoalign_times,
     last_tig_tally_times,

@@ -75,6 +75,10 @@ intersection of the colour sets of its found k-mers. `--pseudoalign-out` gets on
 distinct colour sets of each sample with their fragments (the equivalence classes) and `--pseudoalign-summary-out` per colour the
 fragments assigned to it and to it alone. The per-colour counters never leave the GPU; `--pseudoalign-index minimizer` aligns on the
 sparse index with the same files, byte for byte.
+`--correct-fa` (not in the reference) corrects the substitution errors of reads against the k-mers of the run's unitigs, after all
+cleaning: a base that no k-mer of the set covers is replaced by the one base that makes at least `--correct-min-solid` of its covering
+k-mers solid, in `--correct-rounds` rounds on the GPU. `--correct-out` is the file with exactly those bytes replaced -- headers, line
+wrapping, qualities and line ends as they were -- and `--correct-report-out` one row per read with its substitutions.
 """
 from __future__ import annotations
 
@@ -261,6 +265,19 @@ def main(argv=None) -> int:
                          "the same files)")
     ap.add_argument("--pseudoalign-minimizer-length", type=int, metavar="M",
                     help="with --pseudoalign-index minimizer: the minimizer length, 1 .. min(k, 31) (default min(19, ceil(2k/3)))")
+    ap.add_argument("--correct-fa", action="append", metavar="PATH",
+                    help="reads (fasta or fastq, optionally .gz; any characters) whose substitution errors are corrected on the GPU against "
+                         "the k-mers of the run's unitigs, after all cleaning; repeatable; needs --correct-out or --correct-report-out "
+                         "(not in the reference)")
+    ap.add_argument("--correct-out", action="append", metavar="PATH",
+                    help="the i-th --correct-fa file's text with exactly the substituted bytes replaced (.gz => gzip): none, or one per "
+                         "--correct-fa, in order")
+    ap.add_argument("--correct-report-out", metavar="PATH",
+                    help="TSV (.gz => gzip) with one row per read of all --correct-fa files: file, record, length, kmers, valid, found, "
+                         "found_after, candidates, ambiguous, corrected, corrections (pos:X>Y,... with 0-based positions, ascending; - for none)")
+    ap.add_argument("--correct-min-solid", type=int, metavar="W",
+                    help="a substitution must make at least min(W, the valid k-mers that cover the base) of them solid (W >= 1, default 4)")
+    ap.add_argument("--correct-rounds", type=int, metavar="R", help="rounds of correction, each on the text the one before left (1..8, default 2)")
     args = ap.parse_args(argv)
 
     classed = bool(args.monochromatic_unitigs or args.color_classes_out or args.unitig_color_classes_out)
@@ -355,6 +372,21 @@ def main(argv=None) -> int:
                             ("--pseudoalign-minimizer-length", args.pseudoalign_minimizer_length)):
             if value is not None:
                 ap.error(f"{flag} needs --pseudoalign-fa")
+    if args.correct_fa:
+        if not (args.correct_out or args.correct_report_out):
+            ap.error("--correct-fa needs --correct-out or --correct-report-out")
+        if args.correct_out and len(args.correct_out) != len(args.correct_fa):
+            ap.error(f"{len(args.correct_out)} --correct-out files for {len(args.correct_fa)} --correct-fa files: give none, or one per "
+                     "--correct-fa, in order")
+        if args.correct_min_solid is not None and not 1 <= args.correct_min_solid < 1 << 32:
+            ap.error("--correct-min-solid must be >= 1")
+        if args.correct_rounds is not None and not 1 <= args.correct_rounds <= 8:
+            ap.error("--correct-rounds must be in 1..8")
+    else:
+        for flag, value in (("--correct-out", args.correct_out), ("--correct-report-out", args.correct_report_out),
+                            ("--correct-min-solid", args.correct_min_solid), ("--correct-rounds", args.correct_rounds)):
+            if value is not None:
+                ap.error(f"{flag} needs --correct-fa")
     for over, out in (("greedytigs", args.greedytigs_fa_out), ("eulertigs", args.eulertigs_fa_out)):
         if args.count_index_over == over and not out:
             ap.error(f"--count-index-over {over} needs --{over}-fa-out")
@@ -419,7 +451,7 @@ def main(argv=None) -> int:
                         ("--pseudoalign-min-base-quality", args.pseudoalign_min_base_quality)):
         if value is not None and not 0 <= value <= 93:
             ap.error(f"{flag} must be in 0..93")
-    if not (args.color_classes_out or args.unitig_color_classes_out or args.color_matrix_out or args.unitig_colors_out or args.kmer_spectrum_out or args.unitig_abundance_out or args.unitig_kmer_abundance_out or args.query_fa or args.count_fa or args.pseudoalign_fa or args.greedytigs_fa_out or args.eulertigs_fa_out or args.greedytigs_gfa_out or args.eulertigs_gfa_out
+    if not (args.color_classes_out or args.unitig_color_classes_out or args.color_matrix_out or args.unitig_colors_out or args.kmer_spectrum_out or args.unitig_abundance_out or args.unitig_kmer_abundance_out or args.query_fa or args.count_fa or args.pseudoalign_fa or args.correct_fa or args.greedytigs_fa_out or args.eulertigs_fa_out or args.greedytigs_gfa_out or args.eulertigs_gfa_out
             or args.greedytigs_duplication_bitvector_out or args.matchtigs_fa_out or args.matchtigs_gfa_out or args.verify_fa or args.unitigs_fa_out
             or args.unitigs_bcalm_out or args.unitigs_gfa_out or args.components_out or args.unitig_components_out):
         ap.error("nothing to do: give --greedytigs-fa-out / --greedytigs-gfa-out and/or --eulertigs-fa-out / --eulertigs-gfa-out")
@@ -428,7 +460,8 @@ def main(argv=None) -> int:
 
     # FASTQ is told from FASTA by the content; the quality flags need a file they can apply to
     aligned = (args.pseudoalign_fa or []) + (args.pseudoalign_mate_fa or [])
-    fastq = {path for path in (args.seq_in or []) + (args.query_fa or []) + (args.count_fa or []) + aligned if api.sequence_file_format(path) == 2}
+    fastq = {path for path in (args.seq_in or []) + (args.query_fa or []) + (args.count_fa or []) + aligned + (args.correct_fa or [])
+             if api.sequence_file_format(path) == 2}
     if args.min_base_quality is not None and not fastq.intersection((args.seq_in or []) + (args.query_fa or [])):
         ap.error("--min-base-quality needs a fastq file among --seq-in / --query-fa")
     if args.query_min_base_quality is not None and not fastq.intersection(args.query_fa or []):
@@ -682,13 +715,16 @@ def _run(api, args, fastq) -> int:
     if args.query_fa:
         shared_index = _query(api, args, store, abundance.kmer_counts if args.query_abundance_out or args.query_index_abundance_out else None, fastq,
                               colors if args.query_colors_out or args.query_index_colors_out else None,
-                              keep_index=bool(args.count_fa) and not count_sparse, keep_sparse=share_sparse)
-    if args.count_fa:
-        _count(api, args, store, fastq, shared_index)
+                              keep_index=(bool(args.count_fa) and not count_sparse) or bool(args.correct_fa and not args.count_fa),
+                              keep_sparse=share_sparse)
+    if args.count_fa:  # (with --correct-fa a table index it counted on stays open for the correction)
+        shared_index = _count(api, args, store, fastq, shared_index, keep=bool(args.correct_fa))
     if args.pseudoalign_fa:
         status = _pseudoalign(api, args, store, colors, fastq)
         if status:
             return status
+    if args.correct_fa:
+        _correct(api, args, store, fastq, shared_index)
     return 0 if all_equal else 1
 
 
@@ -1027,13 +1063,14 @@ def _query(api, args, store, kmer_counts=None, fastq=(), colors=None, keep_index
         return index if kept else None
 
 
-def _count(api, args, store, fastq=(), index=None) -> None:
+def _count(api, args, store, fastq=(), index=None, keep=False):
     """`--count-fa`: every file is a sample whose k-mers are counted on the k-mers of the unitig store. One table
     index over the store -- `index`, the one the queries left open, else a plain one built here -- and one tally serve all samples in
     turn: add the sample, read the coverage of the store's own records, keep two columns, reset. `--count-out`: one row per record
     of the store, per sample the k-mers it saw at all and the sum of their counts.
     With `--count-index minimizer` the index is a locating sparse one over what `--count-index-over` names -- the
-    queries' own if they left it open -- and the tally one counter per window of that text; the coverage is still asked of the store."""
+    queries' own if they left it open -- and the tally one counter per window of that text; the coverage is still asked of the store.
+    keep (`--correct-fa` follows): a table index is handed back open instead of closed; None if the count took the sparse one."""
     import contextlib
 
     import numpy as np
@@ -1045,7 +1082,8 @@ def _count(api, args, store, fastq=(), index=None) -> None:
             index = api.TigIndex(indexed, args.k, args.count_minimizer_length, args.device, locate=True)
         elif built:
             index = api.KmerIndex(store, args.k, args.device)
-        stack.enter_context(index)
+        if sparse or not keep:
+            stack.enter_context(index)
         tally = stack.enter_context(api.TigTally(index) if sparse else api.KmerTally(index))
         if built and args.count_index is not None:
             print(f"Indexing the {over} for the count: {_describe_index(index, sparse)}; the tally: {tally.device_bytes} device bytes",
@@ -1074,6 +1112,7 @@ def _count(api, args, store, fastq=(), index=None) -> None:
             f.write("\t".join(["unitig", "kmers"] + [f"{path}:{what}" for path in args.count_fa for what in ("covered", "sum")]) + "\n")
             rows = np.stack([np.arange(len(kmers), dtype=np.uint64), kmers] + columns, axis=1).tolist() if len(kmers) else []
             f.writelines("\t".join(map(str, row)) + "\n" for row in rows)
+        return index if keep and not sparse else None
 
 
 def _pseudoalign(api, args, store, colors, fastq=()) -> int:
@@ -1145,6 +1184,97 @@ def _pseudoalign(api, args, store, colors, fastq=()) -> int:
                 for what in ("fragments", "eligible", "assigned", "ambiguous"):  # (one value per sample: under its first column)
                     f.write("\t".join([f"#{what}"] + [x for tot in totals for x in (str(tot[what]), "-")]) + "\n")
     return 0
+
+
+def _sequence_bytes(text, n_records, is_fastq):
+    """Where the bases of a FASTA / FASTQ text lie: the byte offset of every base, in the order the readers concatenate them (numpy
+    int64). FASTA: the content of every line that is neither empty nor a header, less the `\\r`s before its `\\n`. FASTQ: the content of
+    line 4 r + 1 of each of the n_records records, less one `\\r`. The readers' line rules, not a parser: the caller
+    holds the result against the reader's store."""
+    import numpy as np
+
+    a = np.frombuffer(text, np.uint8)
+    ends = np.flatnonzero(a == 10)
+    if len(a) and (not len(ends) or ends[-1] != len(a) - 1):
+        ends = np.append(ends, len(a))  # (a last line without its line end)
+    starts = np.concatenate(([0], ends[:-1] + 1)).astype(np.int64) if len(ends) else np.zeros(0, np.int64)
+    ends = ends.astype(np.int64)
+    if is_fastq:
+        starts, ends = starts[1:4 * n_records:4], ends[1:4 * n_records:4].copy()
+        cr = (ends > starts) & (a[np.maximum(ends - 1, 0)] == 13)
+        ends[cr] -= 1
+    else:
+        ends = ends.copy()
+        while True:
+            cr = (ends > starts) & (a[np.maximum(ends - 1, 0)] == 13)
+            if not cr.any():
+                break
+            ends[cr] -= 1
+        body = (ends > starts) & (a[np.minimum(starts, max(len(a) - 1, 0))] != ord(">"))
+        starts, ends = starts[body], ends[body]
+    lengths = ends - starts
+    total = int(lengths.sum())
+    if not total:
+        return np.zeros(0, np.int64)
+    first = np.cumsum(lengths) - lengths  # the ordinal of each line's first base
+    return np.arange(total, dtype=np.int64) + np.repeat(starts - first, lengths)
+
+
+def _correct(api, args, store, fastq=(), index=None) -> None:
+    """`--correct-fa`: every file's reads corrected against the k-mers of the unitig store. One table index over the
+    store -- `index`, the one the queries or the count left open, else a plain one built here -- and one corrector serve all files in
+    turn. `--correct-out`: the file's inflated text with exactly the substituted bytes replaced; the bases are found in the text by
+    the readers' line rules and held against the reader's store before a byte is written. `--correct-report-out`: one row per read."""
+    import contextlib
+    import gzip
+
+    import numpy as np
+
+    with contextlib.ExitStack() as stack:
+        if index is None:
+            index = api.KmerIndex(store, args.k, args.device)
+        stack.enter_context(index)
+        corrector = stack.enter_context(api.ReadCorrector(index, args.correct_min_solid or 4, args.correct_rounds or 2))
+        report = stack.enter_context(_open_text(args, args.correct_report_out)) if args.correct_report_out else None
+        if report is not None:
+            report.write("file\trecord\tlength\tkmers\tvalid\tfound\tfound_after\tcandidates\tambiguous\tcorrected\tcorrections\n")
+        for i, path in enumerate(args.correct_fa):
+            t0 = time.perf_counter()
+            if path in fastq:
+                seqs, names, _ = api.read_fastq(path, 0, args.device, named=True)
+            else:
+                seqs, names = api.read_sequences_named(path)
+            r = corrector.correct(seqs)
+            with open(path, "rb") as f:
+                text = f.read()
+            if text[:2] == b"\x1f\x8b":
+                text = gzip.decompress(text)
+            data = seqs.arrays()[0]
+            where = _sequence_bytes(text, len(names), path in fastq)
+            old = np.frombuffer(text, np.uint8)
+            if len(where) != len(data) or not np.array_equal(old[where], data):
+                raise SystemExit(f"--correct-fa {path}: the bases of the text are not the reader's ({len(where)} against {len(data)})")
+            at = where[r.positions.astype(np.int64)]
+            new = api.patched_bytes(old[at], r.bases)
+            if args.correct_out:
+                patched = old.copy()
+                patched[at] = new
+                out = args.correct_out[i]
+                with (gzip.open(out, "wb", compresslevel=args.compression_level) if out.endswith(".gz") else open(out, "wb")) as f:
+                    f.write(patched.tobytes())
+            if report is not None:
+                local = (r.positions - r.offsets[np.searchsorted(r.offsets, r.positions, side="right") - 1]).tolist()
+                shown = [f"{p}:{chr(a)}>{chr(b)}" for p, a, b in zip(local, old[at].tolist(), new.tolist())]
+                ends = np.cumsum(r.corrected.astype(np.int64)).tolist()
+                lengths = np.diff(r.offsets).tolist()
+                columns = [x.tolist() for x in (r.kmers, r.valid, r.found, r.found_after, r.candidates, r.ambiguous, r.corrected)]
+                report.writelines("\t".join([path, name, str(lengths[q])] + [str(c[q]) for c in columns]
+                                            + [",".join(shown[ends[q] - columns[6][q]:ends[q]]) or "-"]) + "\n" for q, name in enumerate(names))
+            per_round = [int(x) for x in r.round_corrected[:corrector.rounds]]
+            print(f"Correcting {path}: {len(names)} records, {int(r.candidates.sum())} candidates, {'+'.join(map(str, per_round))} = "
+                  f"{len(r.positions)} substitutions in {corrector.rounds} rounds, {int(r.ambiguous.sum())} ambiguous, k-mers found "
+                  f"{int(r.found.sum())} -> {int(r.found_after.sum())} of {int(r.valid.sum())} valid in {time.perf_counter() - t0:.1f} s",
+                  file=sys.stderr)
 
 
 def _write_query_abundance(index, seqs, names, weighed, profile, valid_bits) -> None:

@@ -446,6 +446,9 @@ def load():
         "mtg_pseudoaligner_reset": (None, [vp]),
         "mtg_pseudoaligner_free": (None, [vp]),
         "mtg_last_pseudoalign_times": (None, [P(C.c_double)]),
+        "mtg_kmer_index_correct": (None, [vp, vp, vp, u64, vp, vp, vp, vp, vp, vp, vp, vp, P(vp), P(vp), P(u64), P(u64)]),
+        "mtg_kmer_index_correct_store": (None, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, P(vp), P(vp), P(u64), P(u64)]),
+        "mtg_last_kmer_correct_times": (None, [P(C.c_double)]),
         "mtg_read_sequences_named": (None, [C.c_char_p, P(vp), P(vp)]),
         "mtg_read_fastq_split": (C.c_int, [C.c_char_p, u64, C.c_int, P(vp), P(MtgFastqStats), C.c_char_p, u64]),
         "mtg_read_fastq_named": (C.c_int, [C.c_char_p, u64, C.c_int, P(vp), P(vp), P(MtgFastqStats), C.c_char_p, u64]),

@@ -2249,6 +2249,118 @@ def last_pseudoalign_times() -> dict:
     return dict(zip(("upload_ms", "pack_ms", "probe_ms", "mask_ms", "dictionary_ms", "download_ms"), list(out)))
 
 
+@dataclass(frozen=True, eq=False)
+class CorrectionResult:
+    """What ReadCorrector.correct found. Per record (numpy uint64 arrays): kmers / valid / found as KmerIndex.query gives them on the
+    input, found_after = found on the corrected text, candidates = the positions of round 1 that no present window covers, ambiguous
+    = the positions of the last round with two equally good bases, corrected = the positions substituted. Per call: positions (uint64
+    indices into the concatenated records, ascending) and bases (uint8: the letters A C G T) of the substitutions, and
+    round_corrected[8], the substitutions made in each round."""
+
+    k: int
+    offsets: np.ndarray
+    kmers: np.ndarray
+    valid: np.ndarray
+    found: np.ndarray
+    found_after: np.ndarray
+    candidates: np.ndarray
+    ambiguous: np.ndarray
+    corrected: np.ndarray
+    positions: np.ndarray
+    bases: np.ndarray
+    round_corrected: np.ndarray
+
+    def record_of(self, i: int) -> int:
+        """The record that holds substitution i."""
+        return int(np.searchsorted(self.offsets, self.positions[i], side="right")) - 1
+
+    def apply(self, seqs) -> list:
+        """The records (a list of str, as they were given to correct) with the substitutions made; a replacement takes the case of
+        the letter it replaces."""
+        lengths = [len(s) for s in seqs]
+        if len(lengths) + 1 != len(self.offsets) or (np.cumsum([0] + lengths) != self.offsets).any():
+            raise ValueError("apply() takes the records that were corrected")
+        text = np.frombuffer("".join(seqs).encode("latin-1"), np.uint8).copy()
+        text[self.positions.astype(np.int64)] = patched_bytes(text[self.positions.astype(np.int64)], self.bases)
+        whole = text.tobytes().decode("latin-1")
+        return [whole[int(a):int(b)] for a, b in zip(self.offsets[:-1], self.offsets[1:])]
+
+
+def patched_bytes(old: np.ndarray, bases: np.ndarray) -> np.ndarray:
+    """The upper-case letters `bases` in the case of the letters `old` they replace (uint8 arrays of one length)."""
+    lower = (old >= ord("a")) & (old <= ord("z"))
+    return np.where(lower, bases | np.uint8(0x20), bases).astype(np.uint8)
+
+
+class ReadCorrector:
+    """Puts right the substitution errors of reads against the k-mers of a KmerIndex (mtg_kmer_index_correct). The
+    index's k-mer set is the solid set; the index is never changed, the corrector keeps a reference to it, and several correctors on
+    one index are independent. In each of `rounds` rounds (1..8) a base that no present window covers is a candidate; each of the
+    three other bases is tried, and the one that makes the most covering windows solid -- at least min(min_solid, the valid windows
+    that cover it), and more than either other base -- replaces it. All decisions of a round read the round's input. The search runs
+    on the GPU, one wave per candidate; only six words per record and the substitutions come back. The corrector holds no device
+    memory between calls."""
+
+    def __init__(self, index, min_solid: int = 4, rounds: int = 2):
+        self._open_flag = False
+        if isinstance(index, TigIndex):
+            raise TypeError("ReadCorrector corrects on a KmerIndex: the sparse minimizer index is not served")
+        if not isinstance(index, KmerIndex):
+            raise TypeError("ReadCorrector corrects on a KmerIndex")
+        if not index._h:
+            raise ValueError("the index is closed")
+        if isinstance(min_solid, bool) or not isinstance(min_solid, (int, np.integer)) or not 1 <= min_solid < 1 << 32:
+            raise ValueError(f"min_solid must be an integer >= 1, not {min_solid!r}")
+        if isinstance(rounds, bool) or not isinstance(rounds, (int, np.integer)) or not 1 <= rounds <= 8:
+            raise ValueError(f"rounds must be an integer in 1..8, not {rounds!r}")
+        self.index = index
+        self.min_solid, self.rounds = int(min_solid), int(rounds)
+        self._L = index._L
+        self._open_flag = True
+
+    def close(self) -> None:
+        self._open_flag = False
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def correct(self, seqs_or_store) -> CorrectionResult:
+        """seqs_or_store: UnitigStore, list of str, or (uint8 array, offsets); ANY bytes. The input is not changed: the result
+        names the substitutions, and CorrectionResult.apply makes them."""
+        if not getattr(self, "_open_flag", False):
+            raise ValueError("the corrector is closed")
+        d, o, n, keep, off, kmers, valid, found = self.index._probe_inputs(seqs_or_store)
+        found_after, candidates, ambiguous, corrected = (np.zeros(n, np.uint64) for _ in range(4))
+        params = (C.c_uint32 * 2)(self.min_solid, self.rounds)
+        positions, bases, count = C.c_void_p(), C.c_void_p(), C.c_uint64(0)
+        per_round = (C.c_uint64 * 8)()
+        outs = (_ptr(kmers), _ptr(valid), _ptr(found), _ptr(found_after), _ptr(candidates), _ptr(ambiguous), _ptr(corrected),
+                C.byref(positions), C.byref(bases), C.byref(count), per_round)
+        if isinstance(seqs_or_store, UnitigStore):
+            self._L.mtg_kmer_index_correct_store(self.index._h, seqs_or_store.handle, C.cast(params, C.c_void_p), *outs)
+        else:
+            self._L.mtg_kmer_index_correct(self.index._h, d, o, n, C.cast(params, C.c_void_p), *outs)
+        del keep
+        m = int(count.value)
+        pos, letters = _taken(m, positions, np.uint64), _taken(m, bases, np.uint8)
+        for p in (positions, bases):
+            self._L.mtg_free(p)
+        return CorrectionResult(self.index.info.k, off, kmers, valid, found, found_after, candidates, ambiguous, corrected, pos, letters,
+                                np.array(list(per_round), np.uint64))
+
+
+def last_kmer_correct_times() -> dict:
+    """Phases of the last ReadCorrector.correct on this thread, in ms (HIP events around the kernels; upload, download and total by
+    the host clock): query = every query pass, flag = the candidate bits and their compaction, evaluate = the search over the
+    substitutions, apply = the compaction of the accepted ones and the patch of the packed text."""
+    out = (C.c_double * 8)()
+    _lib.load().mtg_last_kmer_correct_times(out)
+    return dict(zip(("upload_ms", "pack_ms", "query_ms", "flag_ms", "evaluate_ms", "apply_ms", "download_ms", "total_ms"), list(out)))
+
+
 def last_tig_locate_times() -> dict:
     """Phases of the last TigIndex.locate on this thread, in ms (HIP events around the kernels; the upload by the host clock): probe =
     the lookup of every window with its position and strand (with the fill of the hit array), runs = folding the hits into runs."""

@@ -233,6 +233,21 @@ void device_kmer_tally_coverage(const KmerTally *t, const char *seq, const uint6
                                 uint64_t *found, uint64_t *covered, uint64_t *sum, uint64_t *max, uint64_t *per_window, KmerTallyTimes *times);
 void device_kmer_tally_reset(KmerTally *t);
 void device_kmer_tally_free(KmerTally *t);
+// Read correction against the index's k-mers (kmer_correct_device.hpp; include/mtg_engine.h states the rule). The query's
+// kmers / valid / found on the input, found_after on the corrected text, and per record the candidates of round 1, the ambiguous
+// positions of the last round and the positions substituted. *out: the substitutions by ascending global position (bases as the
+// letters ACGT), the counts per round, and the phases -- host wall clock of upload, download and the whole call, HIP-event time of
+// the kernels. The index is not changed and the call keeps no device memory.
+struct KmerCorrectCall {
+    std::vector<uint64_t> positions;
+    std::vector<uint8_t> bases;
+    uint64_t round_corrected[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    uint64_t candidates = 0;  // of round 1, over all records
+    double upload_ms = 0, pack_ms = 0, query_ms = 0, flag_ms = 0, evaluate_ms = 0, apply_ms = 0, download_ms = 0, total_ms = 0;
+};
+void device_kmer_index_correct(const KmerIndex *ix, uint32_t min_solid, uint32_t rounds, const char *seq, const uint64_t *off, uint64_t n,
+                               uint64_t *kmers, uint64_t *valid, uint64_t *found, uint64_t *found_after, uint64_t *candidates, uint64_t *ambiguous,
+                               uint64_t *corrected, KmerCorrectCall *out);
 // tig_index_device.hip: the sparse minimizer index over a sequence set (the file's header and DESIGN.md 28 state the contract): the
 // packed bases plus one word per anchor, asked what device_kmer_index_query is asked. m = 0: tig_index_default_m(k); bucket_limit
 // = 0: 64. times: host wall clock of the uploads, HIP-event time of the kernels; a build sets the first five, a query the last three.

@@ -1132,6 +1132,49 @@ void mtg_last_pseudoalign_times(double out[6]) {
     const PseudoalignCall &t = g_last_pseudoalign;
     out[0] = t.upload_ms; out[1] = t.pack_ms; out[2] = t.probe_ms; out[3] = t.mask_ms; out[4] = t.dictionary_ms; out[5] = t.download_ms;
 }
+// ---- read correction against the table index's k-mers (kmer_correct_device.hpp) ----
+static thread_local KmerCorrectCall g_last_kmer_correct;
+void mtg_kmer_index_correct(const mtg_kmer_index *ix, const char *seq, const uint64_t *off, uint64_t n, const mtg_correct_params *params,
+                            uint64_t *kmers, uint64_t *valid, uint64_t *found, uint64_t *found_after, uint64_t *candidates, uint64_t *ambiguous,
+                            uint64_t *corrected, uint64_t **positions, uint8_t **bases, uint64_t *n_substitutions, uint64_t round_corrected[8]) {
+    const mtg_correct_params q = params ? *params : mtg_correct_params{4, 2};
+    if (q.min_solid < 1) MTG_DIE("mtg_kmer_index_correct: min_solid must be >= 1");
+    if (q.rounds < 1 || q.rounds > 8) MTG_DIE("mtg_kmer_index_correct: rounds %u is outside 1 .. 8", q.rounds);
+    if (!ix || !positions || !bases || !n_substitutions || !round_corrected) MTG_DIE("mtg_kmer_index_correct: null argument");
+    g_last_kmer_correct = KmerCorrectCall();
+    *positions = nullptr;
+    *bases = nullptr;
+    *n_substitutions = 0;
+    std::fill(round_corrected, round_corrected + 8, 0ull);
+    if (n == 0) return;
+    KmerCorrectCall &call = g_last_kmer_correct;
+    device_kmer_index_correct(ix->ix, q.min_solid, q.rounds, seq, off, n, kmers, valid, found, found_after, candidates, ambiguous, corrected, &call);
+    std::copy(call.round_corrected, call.round_corrected + 8, round_corrected);
+    const size_t m = call.positions.size();
+    *n_substitutions = m;
+    if (m) {
+        *positions = (uint64_t *)std::malloc(m * 8);
+        *bases = (uint8_t *)std::malloc(m);
+        if (!*positions || !*bases) MTG_DIE("mtg_kmer_index_correct: out of memory");
+        std::copy(call.positions.begin(), call.positions.end(), *positions);
+        std::copy(call.bases.begin(), call.bases.end(), *bases);
+    }
+    call.positions = std::vector<uint64_t>();  // (the times stay for mtg_last_kmer_correct_times)
+    call.bases = std::vector<uint8_t>();
+}
+void mtg_kmer_index_correct_store(const mtg_kmer_index *ix, const mtg_unitigs *reads, const mtg_correct_params *params, uint64_t *kmers,
+                                  uint64_t *valid, uint64_t *found, uint64_t *found_after, uint64_t *candidates, uint64_t *ambiguous,
+                                  uint64_t *corrected, uint64_t **positions, uint8_t **bases, uint64_t *n_substitutions, uint64_t round_corrected[8]) {
+    if (!ix || !reads) MTG_DIE("mtg_kmer_index_correct_store: null argument");
+    const UnitigStore &s = *reads->s;
+    mtg_kmer_index_correct(ix, s.data.data(), s.off.data(), s.off.size() - 1, params, kmers, valid, found, found_after, candidates, ambiguous,
+                           corrected, positions, bases, n_substitutions, round_corrected);
+}
+void mtg_last_kmer_correct_times(double out[8]) {
+    const KmerCorrectCall &t = g_last_kmer_correct;
+    out[0] = t.upload_ms; out[1] = t.pack_ms; out[2] = t.query_ms; out[3] = t.flag_ms; out[4] = t.evaluate_ms; out[5] = t.apply_ms;
+    out[6] = t.download_ms; out[7] = t.total_ms;
+}
 void mtg_tig_index_free(mtg_tig_index *ix) {
     if (!ix) return;
     device_tig_index_free(ix->ix);

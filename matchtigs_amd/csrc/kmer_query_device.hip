@@ -86,12 +86,19 @@
 // unchanged color_query_kernel runs once for the reads and, with mates, once more for the mates into the same per_color and counts,
 // and pseudoalign_device.hpp turns every row into one mask and the masks into their dictionary. Only 4 x 8 B per fragment and the
 // classes come back. A call takes (4 C + 16) B per fragment beside one side's store, then at most 180 B per fragment for the masks and the dictionary.
+//
+// Correction (any index, mtg_kmer_index_correct). The way back: the unchanged query_kernel gives both bit arrays, and
+// kmer_correct_device.hpp flags the bases no present window covers, tries the three other bases of each on the table, one wave per
+// candidate, and XORs the accepted substitutions into the reads' packed store; the query pass then runs again, per round and once
+// more for found_after. Only five words per record and the substitutions come back. A call takes 0.25 B per base for the bit arrays,
+// 0.3 B per base for the candidate words and their ranks, 8 + 16 + 16 B per record and 21 B per candidate beside the query's store.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
 #include "device.hpp"
 #include "hip_util.hpp"
+#include "kmer_correct_device.hpp"
 #include "kmer_runs_device.hpp"
 #include "kmer_window_device.hpp"
 #include "pack_device.hpp"
@@ -767,6 +774,62 @@ void device_kmer_index_pseudoalign(const KmerIndex *ix, const PseudoalignRule &r
     HIP_CHECK(hipMemcpyAsync(found, d_counts + n, n * 8, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
     out->download_ms += ms_since(t0);
+}
+
+// ---- correction ----
+// query_kernel, unchanged, once on the input and once after every round that substituted; kc::rounds does the rest.
+void device_kmer_index_correct(const KmerIndex *ix, uint32_t min_solid, uint32_t rounds, const char *seq, const uint64_t *off, uint64_t n,
+                               uint64_t *kmers, uint64_t *valid, uint64_t *found, uint64_t *found_after, uint64_t *candidates, uint64_t *ambiguous,
+                               uint64_t *corrected, KmerCorrectCall *out) {
+    const auto t_call = std::chrono::steady_clock::now();
+    const char *fn = "mtg_kmer_index_correct";
+    const uint64_t n_bases = probe_windows(fn, ix->info.k, seq, off, n, kmers, valid, found, n && (!found_after || !candidates || !ambiguous || !corrected));
+    for (uint64_t *column : {found_after, candidates, ambiguous, corrected}) std::fill(column, column + n, 0ull);
+    *out = KmerCorrectCall();
+    if (n_bases == 0) return;  // nothing to look at
+    const uint64_t bit_words = (n_bases + 63) / 64;
+    Probe<> p(ix, seq, off, n, 2);
+    hipStream_t st = p.st;
+    hu::DeviceArray<unsigned long long> d_bits(2 * bit_words), d_rec(2 * n);  // valid then present; candidates, ambiguous
+    HIP_CHECK(hipMemsetAsync(d_rec, 0, 2 * n * 8, st));
+    auto query_pass = [&]() {
+        p.start();
+        const unsigned grid = hu::grid_for(bit_words);  // (one thread per word: every word of the bit arrays is written)
+        if (p.wide) query_kernel<true><<<grid, hu::EB, 0, st>>>(p.a, p.store.bad, n_bases, n, p.d_counts, d_bits, d_bits + bit_words);
+        else query_kernel<false><<<grid, hu::EB, 0, st>>>(p.a, p.store.bad, n_bases, n, p.d_counts, d_bits, d_bits + bit_words);
+        HIP_CHECK(hipGetLastError());
+        p.ev.mark(1, st);
+        out->query_ms += p.ev.ms(0, 1);  // (waits: the pass is done)
+    };
+    query_pass();
+    p.download_counts(valid, found);
+    HIP_CHECK(hipStreamSynchronize(st));  // (the next pass zeroes the counters)
+    kc::Args a{};
+    a.packed = p.store.packed; a.off = p.store.off; a.vbits = d_bits; a.pbits = d_bits + bit_words; a.index_packed = ix->packed;
+    a.table = ix->table; a.slots = ix->info.slots; a.n_bases = n_bases; a.n_rec = n; a.k = ix->info.k;
+    a.kmask = p.a.kmask; a.pow_k1 = p.a.pow_k1; a.inv_base = p.a.inv_base;
+    kc::rounds(a, p.store.packed.get(), p.wide, min_solid, rounds, st, p.device_id, d_rec.get(), query_pass, out);
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_CHECK(hipMemcpyAsync(found_after, p.d_counts + n, n * 8, hipMemcpyDeviceToHost, st));  // (of the last pass: the final text)
+    HIP_CHECK(hipMemcpyAsync(candidates, d_rec, n * 8, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(ambiguous, d_rec + n, n * 8, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    // the positions whose base is no longer the input's (a later round may have put a base back), and how many each record has
+    size_t kept = 0;
+    for (size_t i = 0, r = 0; i < out->positions.size(); i++) {
+        const uint64_t pos = out->positions[i];
+        if ((uint8_t)(seq[pos] & ~0x20) == out->bases[i]) continue;
+        while (off[r + 1] <= pos) r++;
+        corrected[r]++;
+        out->positions[kept] = pos;
+        out->bases[kept++] = out->bases[i];
+    }
+    out->positions.resize(kept);
+    out->bases.resize(kept);
+    out->download_ms += ms_since(t0);
+    out->upload_ms = p.store.upload_ms;
+    out->pack_ms = p.store.pack_ms;
+    out->total_ms = ms_since(t_call);
 }
 
 // ---- tally ----

@@ -97,6 +97,26 @@ __device__ inline bool same_class(const uint32_t *px, uint64_t p, const uint32_t
     }
     return true;
 }
+// ... where x is the window at p of px with its base j < k REPLACED: flip = old ^ new, XORed into the 16-base chunk that holds base j.
+// As exact as same_class: the same two passes over the same chunks.
+__device__ inline bool same_class_patched(const uint32_t *px, uint64_t p, uint64_t j, uint32_t flip, const uint32_t *py, uint64_t q, uint64_t k) {
+    const uint64_t ji = j & ~15ull;                    // the chunk of base j starts at base ji of x
+    const uint32_t patch = flip << (2 * (j & 15));
+    bool eq = true;
+    for (uint64_t i = 0; i < k && eq; i += 16) {
+        const uint32_t n = (uint32_t)(k - i < 16 ? k - i : 16), m = n == 16 ? ~0u : (1u << (2 * n)) - 1;
+        const uint32_t x = bases16(px, p + i) ^ (i == ji ? patch : 0u);
+        eq = ((x ^ bases16(py, q + i)) & m) == 0;
+    }
+    if (eq) return true;
+    for (uint64_t i = 0; i < k; i += 16) {  // x[i .. i + n) against the reverse complement of y[k - i - n .. k - i)
+        const uint32_t n = (uint32_t)(k - i < 16 ? k - i : 16), m = n == 16 ? ~0u : (1u << (2 * n)) - 1;
+        const uint32_t x = bases16(px, p + i) ^ (i == ji ? patch : 0u);
+        const uint32_t y = revcomp16(bases16(py, q + k - i - n) & m) >> (2 * (16 - n));
+        if ((x ^ y) & m) return false;
+    }
+    return true;
+}
 // ... both in one store
 __device__ inline bool same_class(const uint32_t *packed, uint64_t p, uint64_t q, uint64_t k) {
     return p == q || same_class(packed, p, packed, q, k);
