@@ -789,6 +789,33 @@ void mtg_tig_index_colors(const mtg_tig_index *ix, const char *seq, const uint64
  * narrow} then the colours' same four (0 where there is no such payload); of the last mtg_tig_index_abundance or _colors: {upload
  * (host clock), pack, probe (tig_locate_kernel with the fill of the hit array), gather} -- HIP events around the kernels. */
 void mtg_last_tig_payload_times(double out[12]);
+/* THE INDEX AS A FILE (conventional suffix .mtgx): a sparse index of any kind -- plain, locating, weighted, coloured --
+ * written once and reopened without its sequences. A file is little-endian: a fixed header (magic MTGTIGIX, format version 1, a
+ * byte-order mark, every field of mtg_tig_index_info but device_bytes, the payload infos, one table entry per section and the
+ * header's own digest), a length-prefixed metadata blob that the library stores and returns without reading it, and one section
+ * per device array of the index, 4096-aligned, whose bytes are the array as it lies on the device: a load is read -> upload, no
+ * rebuild, and info.device_bytes of the loaded index equals the builder's. A file is a function of the index and the blob alone.
+ * Every section carries a 64-bit digest computed ON THE GPU over the device array (save: before the download; load: after the upload).
+ * mtg_tig_index_save writes to path + ".tmp" and renames at the end; host memory is bounded by the pinned transfer slices, never by
+ * the index. 0, or 2 with the reason in err (an error of the output file).
+ * mtg_tig_index_load refuses a file that is damaged, truncated, of a later version, or whose arrays break an invariant the probes
+ * rely on: NULL, every allocation returned, and err = "<path>: [section <name>:] <check>: ..." (mtg_read_fastq_split's convention,
+ * not an abort). The order: header checks on the host before any device allocation (magic, version, byte order, header digest,
+ * every section inside the file's length, every count equal to what the info fields imply, k / m / bucket_limit / n_colors inside
+ * the build's limits), then every section's digest on the GPU, then the validation kernel. A loaded index is an index like any
+ * other: query, locate, abundance, colors, tallies and pseudoaligners take it unchanged.
+ * mtg_tig_index_meta: the blob of the file the index was loaded from, or of its last save; empty otherwise. The pointer lives as
+ * long as the index and until its next save.
+ * mtg_tig_index_file_info: the header checks alone, on the host -- no GPU is touched, it works on a machine without one. meta
+ * receives up to meta_cap bytes of the blob, *meta_len its full length. 0, or 2 with err.
+ * mtg_last_tig_index_file_times, on this thread, in ms: of the last save {digest kernels, download, write}, of the last load {read,
+ * upload, digest kernels, validation kernel}. */
+int mtg_tig_index_save(const mtg_tig_index *ix, const char *path, const char *meta_json, uint64_t meta_len, char *err, uint64_t err_len);
+mtg_tig_index *mtg_tig_index_load(const char *path, int device_id, char *err, uint64_t err_len);
+const char *mtg_tig_index_meta(const mtg_tig_index *ix, uint64_t *len);
+int mtg_tig_index_file_info(const char *path, mtg_tig_index_info *info, mtg_tig_payload_info *payload, int *locating, char *meta,
+                            uint64_t meta_cap, uint64_t *meta_len, char *err, uint64_t err_len);
+void mtg_last_tig_index_file_times(double out[7]);
 /* HOW OFTEN OTHER SEQUENCES SEE the indexed k-mers: the opposite question to the probes above. A TALLY belongs to one
  * index -- plain, locating, weighted or coloured --, which must outlive it and which it never changes. It holds one unsigned 64-bit
  * counter per table slot, all 0 at creation: 8 B per slot = 16 B per indexed window, taken from the device arena on the index's

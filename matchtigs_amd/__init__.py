@@ -11,6 +11,7 @@ from .api import (  # noqa: F401
     GreedytigAlgorithm,
     GreedytigAlgorithmConfiguration,
     HeapType,
+    IndexFileError,
     MatchtigEdgeData,
     NodeWeightArrayType,
     PerformanceDataType,
@@ -22,7 +23,9 @@ from .api import (  # noqa: F401
     last_kmer_correct_times,
     last_phase_seconds,
     last_pseudoalign_times,
+    last_tig_index_file_times,
     last_tig_tally_times,
+    tig_index_file_info,
 )
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -79,6 +79,11 @@ sparse index with the same files, byte for byte.
 cleaning: a base that no k-mer of the set covers is replaced by the one base that makes at least `--correct-min-solid` of its covering
 k-mers solid, in `--correct-rounds` rounds on the GPU. `--correct-out` is the file with exactly those bytes replaced -- headers, line
 wrapping, qualities and line ends as they were -- and `--correct-report-out` one row per read with its substitutions.
+`--index-out PATH` (not in the reference) saves a locating sparse minimizer index -- over the input or, with `--index-over`, over the
+tigs this run wrote; with `--index-weights` / `--index-colors` the abundances and the colours of the `--seq-in` files hang off it -- as
+one file, and `--index-in PATH` is a fifth kind of input: a run on such a file reads no sequences of the indexed set, compacts nothing
+and answers `--query-fa` and `--pseudoalign-fa` byte for byte as the building run did. `--index-info PATH` prints the file's header and
+metadata without a GPU.
 """
 from __future__ import annotations
 
@@ -278,11 +283,44 @@ def main(argv=None) -> int:
     ap.add_argument("--correct-min-solid", type=int, metavar="W",
                     help="a substitution must make at least min(W, the valid k-mers that cover the base) of them solid (W >= 1, default 4)")
     ap.add_argument("--correct-rounds", type=int, metavar="R", help="rounds of correction, each on the text the one before left (1..8, default 2)")
+    ap.add_argument("--index-out", metavar="PATH",
+                    help="after the tig outputs: build a locating sparse minimizer index and save it as one file (conventional suffix "
+                         ".mtgx) that --index-in reopens (not in the reference)")
+    ap.add_argument("--index-over", choices=("input", "greedytigs", "eulertigs"),
+                    help="with --index-out: the sequences it indexes: the input (default) or the tigs this run wrote, read back from "
+                         "--greedytigs-fa-out / --eulertigs-fa-out")
+    ap.add_argument("--index-minimizer-length", type=int, metavar="M",
+                    help="with --index-out: the minimizer length, 1 .. min(k, 31) (default min(19, ceil(2k/3)))")
+    ap.add_argument("--index-weights", action="store_true", help="with --index-out and --seq-in: the file also keeps the abundance of every k-mer")
+    ap.add_argument("--index-colors", action="store_true",
+                    help="with --index-out and --seq-in: the file also keeps which --seq-in files carry every k-mer (at most 64 files)")
+    ap.add_argument("--index-in", metavar="PATH",
+                    help="an index file written by --index-out, instead of sequences: serves --query-fa with --query-out, "
+                         "--query-presence-out, --query-index-locate-out, on a weighted file --query-index-abundance-out, on a coloured "
+                         "one --query-index-colors-out and --pseudoalign-fa; -k is the file's (not in the reference)")
+    ap.add_argument("--index-info", metavar="PATH",
+                    help="print the header fields and the metadata of an index file as key<TAB>value lines and exit; needs no other "
+                         "input and no GPU; exit 2 if the header is refused")
     args = ap.parse_args(argv)
+
+    if args.index_info is not None:
+        return _index_info(args.index_info)
+    if args.index_in is not None:
+        return _main_index_in(ap, args)
+    for flag, value in (("--index-over", args.index_over), ("--index-minimizer-length", args.index_minimizer_length),
+                        ("--index-weights", args.index_weights or None), ("--index-colors", args.index_colors or None)):
+        if value is not None and not args.index_out:
+            ap.error(f"{flag} needs --index-out")
+    for flag, value in (("--index-weights", args.index_weights), ("--index-colors", args.index_colors)):
+        if value and args.seq_in is None:
+            ap.error(f"{flag} needs --seq-in")
+    for over, out in (("greedytigs", args.greedytigs_fa_out), ("eulertigs", args.eulertigs_fa_out)):
+        if args.index_over == over and not out:
+            ap.error(f"--index-over {over} needs --{over}-fa-out")
 
     classed = bool(args.monochromatic_unitigs or args.color_classes_out or args.unitig_color_classes_out)
     colored = bool(args.color_matrix_out or args.unitig_colors_out or args.query_colors_out or args.query_index_colors_out or classed
-                   or args.pseudoalign_fa)
+                   or args.pseudoalign_fa or args.index_colors)
     if colored and args.seq_in is not None and len(args.seq_in) > MAX_COLORS:
         ap.error(f"{len(args.seq_in)} --seq-in files: at most {MAX_COLORS} files can be told apart as colours")
 
@@ -344,34 +382,7 @@ def main(argv=None) -> int:
             ap.error(f"{flag} needs --count-index minimizer")
     if args.count_minimizer_length is not None and not 1 <= args.count_minimizer_length <= min(args.k, 31):
         ap.error(f"--count-minimizer-length must be in 1..{min(args.k, 31)} (1 .. min(k, 31), as --query-minimizer-length)")
-    args.pseudoalign_permille = None
-    if args.pseudoalign_fa:
-        if args.seq_in is None:
-            ap.error("--pseudoalign-fa needs --seq-in: the colours are the --seq-in files")
-        if not (args.pseudoalign_out or args.pseudoalign_classes_out or args.pseudoalign_summary_out):
-            ap.error("--pseudoalign-fa needs --pseudoalign-out, --pseudoalign-classes-out or --pseudoalign-summary-out")
-        if args.pseudoalign_mate_fa and len(args.pseudoalign_mate_fa) != len(args.pseudoalign_fa):
-            ap.error(f"{len(args.pseudoalign_mate_fa)} --pseudoalign-mate-fa files for {len(args.pseudoalign_fa)} --pseudoalign-fa files: "
-                     "give none, or one per --pseudoalign-fa")
-        args.pseudoalign_permille = _permille(args.pseudoalign_threshold if args.pseudoalign_threshold is not None else "1")
-        if args.pseudoalign_permille is None:
-            ap.error(f"--pseudoalign-threshold must be a decimal in (0, 1] with at most three places, not {args.pseudoalign_threshold!r}")
-        if args.pseudoalign_min_kmers is not None and args.pseudoalign_min_kmers < 1:
-            ap.error("--pseudoalign-min-kmers must be >= 1")
-        if args.pseudoalign_minimizer_length is not None:
-            if args.pseudoalign_index != "minimizer":
-                ap.error("--pseudoalign-minimizer-length needs --pseudoalign-index minimizer")
-            if not 1 <= args.pseudoalign_minimizer_length <= min(args.k, 31):
-                ap.error(f"--pseudoalign-minimizer-length must be in 1..{min(args.k, 31)} (1 .. min(k, 31), as --count-minimizer-length)")
-    else:
-        for flag, value in (("--pseudoalign-mate-fa", args.pseudoalign_mate_fa), ("--pseudoalign-out", args.pseudoalign_out),
-                            ("--pseudoalign-classes-out", args.pseudoalign_classes_out), ("--pseudoalign-summary-out", args.pseudoalign_summary_out),
-                            ("--pseudoalign-threshold", args.pseudoalign_threshold), ("--pseudoalign-over", args.pseudoalign_over),
-                            ("--pseudoalign-min-kmers", args.pseudoalign_min_kmers),
-                            ("--pseudoalign-min-base-quality", args.pseudoalign_min_base_quality), ("--pseudoalign-index", args.pseudoalign_index),
-                            ("--pseudoalign-minimizer-length", args.pseudoalign_minimizer_length)):
-            if value is not None:
-                ap.error(f"{flag} needs --pseudoalign-fa")
+    _check_pseudoalign(ap, args)
     if args.correct_fa:
         if not (args.correct_out or args.correct_report_out):
             ap.error("--correct-fa needs --correct-out or --correct-report-out")
@@ -394,6 +405,10 @@ def main(argv=None) -> int:
                         ("--query-index-over", args.query_index_over)):
         if value is not None and not args.query_fa:
             ap.error(f"{flag} needs --query-fa")
+    if args.index_minimizer_length is not None and not 1 <= args.index_minimizer_length <= min(args.k, 31):
+        ap.error(f"--index-minimizer-length must be in 1..{min(args.k, 31)} (1 .. min(k, 31), as --query-minimizer-length)")
+    if args.min_component_kmers is not None and args.index_colors:
+        ap.error("--min-component-kmers cannot be combined with --index-colors")
     if args.query_minimizer_length is not None:
         if args.query_index != "minimizer":
             ap.error("--query-minimizer-length needs --query-index minimizer")
@@ -453,7 +468,7 @@ def main(argv=None) -> int:
             ap.error(f"{flag} must be in 0..93")
     if not (args.color_classes_out or args.unitig_color_classes_out or args.color_matrix_out or args.unitig_colors_out or args.kmer_spectrum_out or args.unitig_abundance_out or args.unitig_kmer_abundance_out or args.query_fa or args.count_fa or args.pseudoalign_fa or args.correct_fa or args.greedytigs_fa_out or args.eulertigs_fa_out or args.greedytigs_gfa_out or args.eulertigs_gfa_out
             or args.greedytigs_duplication_bitvector_out or args.matchtigs_fa_out or args.matchtigs_gfa_out or args.verify_fa or args.unitigs_fa_out
-            or args.unitigs_bcalm_out or args.unitigs_gfa_out or args.components_out or args.unitig_components_out):
+            or args.unitigs_bcalm_out or args.unitigs_gfa_out or args.components_out or args.unitig_components_out or args.index_out):
         ap.error("nothing to do: give --greedytigs-fa-out / --greedytigs-gfa-out and/or --eulertigs-fa-out / --eulertigs-gfa-out")
 
     from . import api
@@ -477,6 +492,38 @@ def main(argv=None) -> int:
         return 2
 
 
+def _check_pseudoalign(ap, args) -> None:
+    """The rules of the `--pseudoalign-*` flags among themselves; sets args.pseudoalign_permille."""
+    args.pseudoalign_permille = None
+    if args.pseudoalign_fa:
+        if args.seq_in is None and args.index_in is None:
+            ap.error("--pseudoalign-fa needs --seq-in: the colours are the --seq-in files")
+        if not (args.pseudoalign_out or args.pseudoalign_classes_out or args.pseudoalign_summary_out):
+            ap.error("--pseudoalign-fa needs --pseudoalign-out, --pseudoalign-classes-out or --pseudoalign-summary-out")
+        if args.pseudoalign_mate_fa and len(args.pseudoalign_mate_fa) != len(args.pseudoalign_fa):
+            ap.error(f"{len(args.pseudoalign_mate_fa)} --pseudoalign-mate-fa files for {len(args.pseudoalign_fa)} --pseudoalign-fa files: "
+                     "give none, or one per --pseudoalign-fa")
+        args.pseudoalign_permille = _permille(args.pseudoalign_threshold if args.pseudoalign_threshold is not None else "1")
+        if args.pseudoalign_permille is None:
+            ap.error(f"--pseudoalign-threshold must be a decimal in (0, 1] with at most three places, not {args.pseudoalign_threshold!r}")
+        if args.pseudoalign_min_kmers is not None and args.pseudoalign_min_kmers < 1:
+            ap.error("--pseudoalign-min-kmers must be >= 1")
+        if args.pseudoalign_minimizer_length is not None:
+            if args.pseudoalign_index != "minimizer":
+                ap.error("--pseudoalign-minimizer-length needs --pseudoalign-index minimizer")
+            if not 1 <= args.pseudoalign_minimizer_length <= min(args.k, 31):
+                ap.error(f"--pseudoalign-minimizer-length must be in 1..{min(args.k, 31)} (1 .. min(k, 31), as --count-minimizer-length)")
+    else:
+        for flag, value in (("--pseudoalign-mate-fa", args.pseudoalign_mate_fa), ("--pseudoalign-out", args.pseudoalign_out),
+                            ("--pseudoalign-classes-out", args.pseudoalign_classes_out), ("--pseudoalign-summary-out", args.pseudoalign_summary_out),
+                            ("--pseudoalign-threshold", args.pseudoalign_threshold), ("--pseudoalign-over", args.pseudoalign_over),
+                            ("--pseudoalign-min-kmers", args.pseudoalign_min_kmers),
+                            ("--pseudoalign-min-base-quality", args.pseudoalign_min_base_quality), ("--pseudoalign-index", args.pseudoalign_index),
+                            ("--pseudoalign-minimizer-length", args.pseudoalign_minimizer_length)):
+            if value is not None:
+                ap.error(f"{flag} needs --pseudoalign-fa")
+
+
 def _permille(text: str):
     """`--pseudoalign-threshold`: a decimal in (0, 1] with at most three places -> its thousandths, 1 .. 1000; None for anything else.
     Never through a float."""
@@ -489,6 +536,139 @@ def _permille(text: str):
     if not t.is_finite() or not 0 < t <= 1 or t * 1000 != (t * 1000).to_integral_value():
         return None
     return int(t * 1000)
+
+
+# what a run on an index file may be asked (`--index-in`): everything else needs sequences of the indexed set
+_INDEX_IN_SERVES = {"help", "index_in", "k", "threads", "device", "compression_level", "blossom5_command", "query_fa", "query_out",
+                    "query_presence_out", "query_index_locate_out", "query_min_base_quality", "query_index", "query_index_abundance_out",
+                    "query_index_abundance_profile_out", "query_index_colors_out", "pseudoalign_fa", "pseudoalign_mate_fa", "pseudoalign_out",
+                    "pseudoalign_classes_out", "pseudoalign_summary_out", "pseudoalign_threshold", "pseudoalign_over", "pseudoalign_min_kmers",
+                    "pseudoalign_min_base_quality", "pseudoalign_index"}
+
+
+def _index_info(path) -> int:
+    """`--index-info`: the header's fields and the metadata of an index file as `key\tvalue` lines; the header checks of a load on
+    the host, no GPU. 2 if the header is refused."""
+    import json
+
+    from . import api
+
+    try:
+        head = api.tig_index_file_info(path)
+    except api.IndexFileError as e:
+        print(e, file=sys.stderr)
+        return 2
+    import dataclasses
+
+    rows = [("file", path), ("file_bytes", head["file_bytes"]), ("format_version", 1)]
+    rows += list(dataclasses.asdict(head["info"]).items())
+    rows += [("locating", int(head["locating"])), ("weighted", int(head["weighted"])), ("colored", int(head["colored"])), ("n_colors", head["n_colors"]),
+             ("win_offset_bytes", head["win_offset_bytes"])]
+    for what, p in head["payload_info"].items():
+        rows += [(f"{what}.{key}", value) for key, value in p.items()]
+    rows += [(f"meta.{key}", value if isinstance(value, str) else json.dumps(value, ensure_ascii=False, sort_keys=True))
+             for key, value in sorted(head["meta"].items())]
+    sys.stdout.write("".join(f"{key}\t{value}\n" for key, value in rows))
+    return 0
+
+
+def _main_index_in(ap, args) -> int:
+    """`--index-in`: the checks that need no file first (argparse errors, before the GPU is touched), then the file's header on the
+    host, then the run. A refused file ends the run with status 2 and the library's message, as a malformed FASTQ does."""
+    for action in ap._actions:
+        value = getattr(args, action.dest, None)
+        if action.dest in _INDEX_IN_SERVES or value is None or value == action.default or not action.option_strings:
+            continue
+        flag = action.option_strings[-1]
+        if action.dest in ("bcalm_in", "gfa_in", "fa_in", "seq_in"):
+            ap.error(f"--index-in cannot be combined with {flag}: the index file is the input")
+        if action.dest in ("query_index_over", "query_minimizer_length", "pseudoalign_minimizer_length"):
+            ap.error(f"{flag} cannot be combined with --index-in: what is indexed and its minimizer length are the file's to say")
+        ap.error(f"{flag} cannot be combined with --index-in: it needs the sequences of the indexed set, and a run on an index file reads none")
+    if args.query_index == "table":
+        ap.error("--query-index table cannot be combined with --index-in: the file holds the minimizer index")
+    if args.pseudoalign_index == "table":
+        ap.error("--pseudoalign-index table cannot be combined with --index-in: the file holds the minimizer index")
+    if not (args.query_fa or args.pseudoalign_fa):
+        ap.error("nothing to do with --index-in: give --query-fa with --query-out and/or --pseudoalign-fa")
+    if bool(args.query_fa) != bool(args.query_out):
+        ap.error("--query-fa needs --query-out" if args.query_fa else "--query-out needs --query-fa")
+    for flag, value in (("--query-presence-out", args.query_presence_out), ("--query-index-locate-out", args.query_index_locate_out),
+                        ("--query-index-abundance-out", args.query_index_abundance_out), ("--query-index-colors-out", args.query_index_colors_out),
+                        ("--query-index", args.query_index), ("--query-min-base-quality", args.query_min_base_quality)):
+        if value is not None and not args.query_fa:
+            ap.error(f"{flag} needs --query-fa")
+    if args.query_index_abundance_profile_out and not args.query_index_abundance_out:
+        ap.error("--query-index-abundance-profile-out needs --query-index-abundance-out")
+    _check_pseudoalign(ap, args)
+    for flag, value in (("--query-min-base-quality", args.query_min_base_quality), ("--pseudoalign-min-base-quality", args.pseudoalign_min_base_quality)):
+        if value is not None and not 0 <= value <= 93:
+            ap.error(f"{flag} must be in 0..93")
+    if not 0 <= args.compression_level <= 9:
+        ap.error("compression level must be in 0..9")
+
+    from . import api
+
+    aligned = (args.pseudoalign_fa or []) + (args.pseudoalign_mate_fa or [])
+    fastq = {path for path in (args.query_fa or []) + aligned if api.sequence_file_format(path) == 2}
+    if args.query_min_base_quality is not None and not fastq.intersection(args.query_fa or []):
+        ap.error("--query-min-base-quality needs a fastq file among --query-fa")
+    if args.pseudoalign_min_base_quality is not None and not fastq.intersection(aligned):
+        ap.error("--pseudoalign-min-base-quality needs a fastq file among --pseudoalign-fa / --pseudoalign-mate-fa")
+    try:
+        head = api.tig_index_file_info(args.index_in)  # (on the host: what the file can serve is known before the GPU is touched)
+        if args.k is not None and args.k != head["info"].k:
+            print(f"--index-in {args.index_in}: the file was built with k = {head['info'].k}, not -k {args.k}", file=sys.stderr)
+            return 2
+        for flag, value, has, lacks in (("--query-index-locate-out", args.query_index_locate_out, head["locating"], "the positions of its heavy buckets"),
+                                        ("--query-index-abundance-out", args.query_index_abundance_out, head["weighted"], "weights (--index-weights)"),
+                                        ("--query-index-colors-out", args.query_index_colors_out, head["colored"], "colours (--index-colors)"),
+                                        ("--pseudoalign-fa", args.pseudoalign_fa, head["colored"], "colours (--index-colors)")):
+            if value and not has:
+                ap.error(f"{flag} cannot be served by --index-in {args.index_in}: the file keeps no {lacks}")
+        names = head["meta"].get("colors") or []
+        if head["colored"] and len(names) != head["n_colors"]:  # (a file of the library alone: its colours have no names)
+            names = [f"color{c}" for c in range(head["n_colors"])]
+        args.k, args.seq_in, args.query_index = head["info"].k, list(names), "minimizer"
+        t0 = time.perf_counter()
+        with api.TigIndex.load(args.index_in, args.device) as index:
+            print(f"Loaded the index of {args.index_in} ({head['file_bytes']} bytes, over the {head['meta'].get('indexed', 'sequences')}) in "
+                  f"{time.perf_counter() - t0:.1f}s: {index.info.describe()}", file=sys.stderr)
+            if args.query_fa:
+                _query(api, args, None, True if args.query_index_abundance_out else None, fastq, True if args.query_index_colors_out else None,
+                       loaded=index)
+            if args.pseudoalign_fa:
+                return _pseudoalign(api, args, None, None, fastq, loaded=index)
+        return 0
+    except (api.IndexFileError, api.FastqFormatError) as e:  # an error of the input: the message names the file and the reason
+        print(e, file=sys.stderr)
+        return 2
+
+
+def _index_out(api, args, store, kmer_counts, colors, cleaning, bubbles) -> None:
+    """`--index-out`: a locating sparse index over the unitig store or the tigs this run wrote, with the abundances and / or the
+    colours by position if asked for, saved as one file. The metadata says what was indexed, the colours' names (the
+    `--seq-in` paths as given, in order), `min_abundance` and the cleaning flags used."""
+    t0 = time.perf_counter()
+    over = args.index_over or "input"
+    indexed = store if over == "input" else api.read_sequences(args.greedytigs_fa_out if over == "greedytigs" else args.eulertigs_fa_out)
+    if kmer_counts is not None or colors is not None:
+        weights, masks = (kmer_counts, None if colors is None else colors.kmer_colors) if over == "input" else _tig_payloads(
+            api, args, store, indexed, kmer_counts, colors, over)
+        index = api.TigIndex.annotated(indexed, args.k, args.index_minimizer_length, args.device, weights=weights, colors=masks,
+                                       n_colors=None if colors is None else colors.n_colors)
+    else:
+        index = api.TigIndex(indexed, args.k, args.index_minimizer_length, args.device, locate=True)
+    cleaning_flags = {name: value for name, value in (("clip_tips", args.clip_tips), ("remove_isolated", args.remove_isolated),
+                                                      ("clean_rounds", args.clean_rounds), ("pop_bubbles", args.pop_bubbles),
+                                                      ("bubble_ratio", args.bubble_ratio), ("min_component_kmers", args.min_component_kmers),
+                                                      ("monochromatic_unitigs", args.monochromatic_unitigs or None)) if value is not None}
+    meta = {"indexed": over, "colors": list(args.seq_in) if colors is not None else [], "min_abundance": args.min_abundance or 1,
+            "cleaning": cleaning_flags}
+    with index:
+        n_bytes = index.save(args.index_out, meta)
+        print(f"Writing the index over the {over} to {args.index_out} took {time.perf_counter() - t0:.1f}s: {n_bytes} bytes; "
+              f"{index.info.describe()}", file=sys.stderr)
 
 
 def _read_seq_in(api, args, fastq, record_colors=None):
@@ -525,13 +705,14 @@ def _run(api, args, fastq) -> int:
     elif args.seq_in is not None:  # sequences -> unitigs (GPU compaction) -> graph (the --fa-in join on the same store)
         classed = bool(args.monochromatic_unitigs or args.color_classes_out or args.unitig_color_classes_out)  # 
         colored = bool(args.color_matrix_out or args.unitig_colors_out or args.query_colors_out or args.query_index_colors_out or classed
-                       or args.pseudoalign_fa)  # 
+                       or args.pseudoalign_fa or args.index_colors)  # 
         record_colors = [] if colored else None
         seqs, pieces_cut = _read_seq_in(api, args, fastq, record_colors)
         abundance = colors = cleaning = None
         popping = args.pop_bubbles is not None  # 
         cleaned = args.clip_tips is not None or args.remove_isolated is not None or popping  # 
-        per_kmer = bool(args.query_abundance_out or args.query_index_abundance_out or args.unitig_kmer_abundance_out)  # 
+        per_kmer = bool(args.query_abundance_out or args.query_index_abundance_out or args.unitig_kmer_abundance_out
+                        or args.index_weights)  # 
         counted = not (args.min_abundance is None and not (args.kmer_spectrum_out or args.unitig_abundance_out or per_kmer))
         if not counted and not colored and not cleaned:
             store, compaction = api.compact_unitigs(seqs, args.k, args.device)
@@ -705,6 +886,8 @@ def _run(api, args, fastq) -> int:
               f"({r['tigs']} tigs, {r['fasta_bytes']} fasta bytes)", file=sys.stderr)
         if args.verify:
             all_equal &= report(f"{name} ({out or 'spelled in memory'})", r["verify_tigs"], r["verify"])
+    if args.index_out:  # 
+        _index_out(api, args, store, abundance.kmer_counts if args.index_weights else None, colors if args.index_colors else None, cleaning, bubbles)
     # the queries' index, left open, if it is the one the count asks for: the plain-enough table index over the unitig store, or
     #  the sparse index over the same sequences with the same minimizer length, then built locating
     shared_index = None
@@ -965,7 +1148,7 @@ def _describe_index(index, sparse) -> str:
             f"device bytes, {i.device_bytes / i.occurrences if i.occurrences else 0.0:.2f} bytes per k-mer window")
 
 
-def _query(api, args, store, kmer_counts=None, fastq=(), colors=None, keep_index=False, keep_sparse=False):
+def _query(api, args, store, kmer_counts=None, fastq=(), colors=None, keep_index=False, keep_sparse=False, loaded=None):
     """`--query-fa`: the input's k-mer set (the unitig store) indexed once; one TSV row and one presence line per query record, and
     with `--query-locate-out` (the sparse index: `--query-index-locate-out`) one row per run of located k-mers. kmer_counts (`--query-abundance-out`): the index is weighted with
     them, and one more TSV row, and with `--query-abundance-profile-out` one line of integers, per query record. colors
@@ -973,7 +1156,8 @@ def _query(api, args, store, kmer_counts=None, fastq=(), colors=None, keep_index
     `store` is handed back open instead of closed (`--count-fa` counts on it); None if the queries asked another kind of index.
     keep_sparse (`--count-index minimizer` on what the queries index): the sparse index is built locating and handed back open.
     With the sparse index (`--query-index-abundance-out`, `--query-index-colors-out`) the same two payloads hang off the
-    positions of whatever it indexes, and the same rows are written."""
+    positions of whatever it indexes, and the same rows are written. loaded (`--index-in`): the sparse index of a file,
+    asked as it is and left open; kmer_counts / colors then only say, by not being None, that its weights / colours are asked."""
     import contextlib
     import gzip
 
@@ -987,7 +1171,9 @@ def _query(api, args, store, kmer_counts=None, fastq=(), colors=None, keep_index
         over = args.query_index_over or "input"
         kept = (keep_index and not sparse and over == "input") or (keep_sparse and sparse)
         hold = (lambda ix: ix) if kept else stack.enter_context  # (a kept index is closed by the caller)
-        if sparse or over != "input":  # (the same k-mer set, asked of another index or spelled by the tigs)
+        if loaded is not None:
+            index = loaded
+        elif sparse or over != "input":  # (the same k-mer set, asked of another index or spelled by the tigs)
             indexed = store if over == "input" else api.read_sequences(args.greedytigs_fa_out if over == "greedytigs" else args.eulertigs_fa_out)
             if sparse and (kmer_counts is not None or colors is not None):  # (payloads by position)
                 weights, masks = (kmer_counts, None if colors is None else colors.kmer_colors) if over == "input" else _tig_payloads(
@@ -1006,7 +1192,7 @@ def _query(api, args, store, kmer_counts=None, fastq=(), colors=None, keep_index
             index = hold(api.KmerIndex(store, args.k, args.device, locate=bool(args.query_locate_out)))
         else:
             index = hold(api.KmerIndex(store, args.k, args.device, locate=bool(args.query_locate_out), weights=kmer_counts))
-        if args.query_index is not None or args.query_index_over is not None:
+        if loaded is None and (args.query_index is not None or args.query_index_over is not None):
             print(f"Indexing the {over}: {_describe_index(index, sparse)}", file=sys.stderr)
             for what, p in (getattr(index, "payload_info", None) or {}).items():
                 print(f"  {what} by position: {p['layout']}, {p['width']} B wide, {p['runs']} runs over {p['windows']} windows, "
@@ -1115,11 +1301,12 @@ def _count(api, args, store, fastq=(), index=None, keep=False):
         return index if keep and not sparse else None
 
 
-def _pseudoalign(api, args, store, colors, fastq=()) -> int:
+def _pseudoalign(api, args, store, colors, fastq=(), loaded=None) -> int:
     """`--pseudoalign-fa`: every file is a sample whose reads are pseudoaligned to the colours of the unitig store's k-mers (DESIGN.md
     33). One coloured index over the store -- the table, or with `--pseudoalign-index minimizer` the sparse index with the masks by
     position -- and one aligner serve all samples in turn: align the sample (with its mates), keep the rows, the classes and the
-    per-colour sums, reset. Returns 2 where a sample and its mates differ in their number of records."""
+    per-colour sums, reset. Returns 2 where a sample and its mates differ in their number of records. loaded (`--index-in`, DESIGN.md
+    35): the coloured sparse index of a file, aligned on as it is and left open; the colours' names are args.seq_in."""
     import contextlib
 
     import numpy as np
@@ -1132,16 +1319,21 @@ def _pseudoalign(api, args, store, colors, fastq=()) -> int:
 
     with contextlib.ExitStack() as stack:
         sparse = args.pseudoalign_index == "minimizer"
-        if sparse:
+        n_colors = loaded.n_colors if loaded is not None else colors.n_colors
+        if loaded is not None:
+            index = loaded
+        elif sparse:
             index = api.TigIndex.annotated(store, args.k, args.pseudoalign_minimizer_length, args.device, colors=colors.kmer_colors,
                                            n_colors=colors.n_colors)
         else:
             index = api.KmerIndex(store, args.k, args.device, colors=colors.kmer_colors, n_colors=colors.n_colors)
-        stack.enter_context(index)
+        if loaded is None:
+            stack.enter_context(index)
         aligner = stack.enter_context(api.Pseudoaligner(index, args.pseudoalign_permille, args.pseudoalign_over or "found",
                                                         args.pseudoalign_min_kmers or 1))
-        print(f"Indexing the input for the pseudoalignment: {_describe_index(index, sparse)}; {colors.n_colors} colours, threshold "
-              f"{args.pseudoalign_permille}/1000 of the {aligner.over} k-mers, at least {aligner.min_kmers}", file=sys.stderr)
+        if loaded is None:
+            print(f"Indexing the input for the pseudoalignment: {_describe_index(index, sparse)}; {colors.n_colors} colours, threshold "
+                  f"{args.pseudoalign_permille}/1000 of the {aligner.over} k-mers, at least {aligner.min_kmers}", file=sys.stderr)
         rows = stack.enter_context(_open_text(args, args.pseudoalign_out)) if args.pseudoalign_out else None
         classes_out = stack.enter_context(_open_text(args, args.pseudoalign_classes_out)) if args.pseudoalign_classes_out else None
         if rows is not None:
@@ -1166,7 +1358,7 @@ def _pseudoalign(api, args, store, colors, fastq=()) -> int:
             aligner.reset()
             if rows is not None:
                 masks = r.masks.tolist()
-                shown = {m: ",".join(str(c) for c in range(colors.n_colors) if (m >> c) & 1) or "-" for m in set(masks)}
+                shown = {m: ",".join(str(c) for c in range(n_colors) if (m >> c) & 1) or "-" for m in set(masks)}
                 rows.writelines(f"{name}\t{n}\t{v}\t{f}\t{shown[m]}\n" for name, n, v, f, m in zip(
                     names, r.kmers.tolist(), r.valid.tolist(), r.found.tolist(), masks))
             if classes_out is not None:
@@ -1180,7 +1372,7 @@ def _pseudoalign(api, args, store, colors, fastq=()) -> int:
         if args.pseudoalign_summary_out:
             with _open_text(args, args.pseudoalign_summary_out) as f:
                 f.write("\t".join(["color"] + [f"{path}:{what}" for path in args.pseudoalign_fa for what in ("assigned", "unique")]) + "\n")
-                f.writelines("\t".join([args.seq_in[c]] + [str(int(col[c])) for col in columns]) + "\n" for c in range(colors.n_colors))
+                f.writelines("\t".join([args.seq_in[c]] + [str(int(col[c])) for col in columns]) + "\n" for c in range(n_colors))
                 for what in ("fragments", "eligible", "assigned", "ambiguous"):  # (one value per sample: under its first column)
                     f.write("\t".join([f"#{what}"] + [x for tot in totals for x in (str(tot[what]), "-")]) + "\n")
     return 0

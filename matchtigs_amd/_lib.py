@@ -416,6 +416,12 @@ def load():
         "mtg_tig_index_get_payload_info": (None, [vp, P(MtgTigPayloadInfo)]),
         "mtg_tig_index_abundance": (None, [vp, vp, vp, u64, vp, vp, vp, vp, vp, vp, vp]),
         "mtg_tig_index_colors": (None, [vp, vp, vp, u64, vp, vp, vp, vp, vp]),
+        "mtg_tig_index_save": (C.c_int, [vp, C.c_char_p, C.c_char_p, u64, C.c_char_p, u64]),
+        "mtg_tig_index_load": (vp, [C.c_char_p, C.c_int, C.c_char_p, u64]),
+        "mtg_tig_index_meta": (vp, [vp, P(u64)]),
+        "mtg_tig_index_file_info": (C.c_int, [C.c_char_p, P(MtgTigIndexInfo), P(MtgTigPayloadInfo), P(C.c_int), C.c_char_p, u64, P(u64),
+                                              C.c_char_p, u64]),
+        "mtg_last_tig_index_file_times": (None, [P(C.c_double)]),
         "mtg_last_tig_payload_times": (None, [P(C.c_double)]),
         "mtg_kmer_tally_create": (vp, [vp]),
         "mtg_kmer_tally_device_bytes": (u64, [vp]),

@@ -18,6 +18,8 @@ from __future__ import annotations
 
 import ctypes as C
 import enum
+import json
+import os
 from dataclasses import dataclass
 from typing import Iterable, Optional, Sequence
 
@@ -1864,6 +1866,58 @@ class TigIndexInfo:
                 f"bytes, {self.bytes_per_kmer:.2f} bytes per k-mer window")
 
 
+class IndexFileError(ValueError):
+    """An index file is refused (TigIndex.load, tig_index_file_info) or cannot be written (TigIndex.save): an error of the file,
+    the process goes on. The message names the path, the section where there is one, and the check."""
+
+
+def _payload_info_dict(pi) -> dict:
+    names = {1: "dense", 2: "runs"}
+    return {key: dict(one.as_dict(), layout=names[int(one.layout)]) for key, one in (("weights", pi.weights), ("colors", pi.colors)) if one.layout}
+
+
+def _meta_dict(blob: bytes, path) -> dict:
+    if not blob:
+        return {}
+    try:
+        meta = json.loads(blob.decode("utf-8"))
+    except ValueError as e:
+        raise IndexFileError(f"{path}: metadata: not a UTF-8 JSON object ({e})") from None
+    if not isinstance(meta, dict):
+        raise IndexFileError(f"{path}: metadata: not a JSON object")
+    return meta
+
+
+def tig_index_file_info(path) -> dict:
+    """What the header of an index file says (mtg_tig_index_file_info), after the header checks of a load and nothing
+    more -- on the host alone, no GPU is touched: {"info": TigIndexInfo, "locating", "weighted", "colored", "n_colors",
+    "payload_info", "win_offset_bytes", "meta": dict, "file_bytes"}. A refused header raises IndexFileError."""
+    L = _lib.load()
+    info, pi, locating, meta_len = _lib.MtgTigIndexInfo(), _lib.MtgTigPayloadInfo(), C.c_int(0), C.c_uint64(0)
+    err = C.create_string_buffer(4096)
+    blob = C.create_string_buffer(1)
+    for _ in range(2):  # (the second call has room for the whole blob)
+        if L.mtg_tig_index_file_info(str(path).encode(), C.byref(info), C.byref(pi), C.byref(locating), blob, len(blob), C.byref(meta_len),
+                                     err, len(err)) != 0:
+            raise IndexFileError(err.value.decode(errors="replace"))
+        if meta_len.value <= len(blob):
+            break
+        blob = C.create_string_buffer(int(meta_len.value))
+    return {"info": TigIndexInfo(**info.as_dict()), "locating": bool(locating.value), "weighted": bool(pi.weights.layout),
+            "colored": bool(pi.colors.layout), "n_colors": int(pi.n_colors), "payload_info": _payload_info_dict(pi),
+            "win_offset_bytes": int(pi.win_offset_bytes), "meta": _meta_dict(blob.raw[:int(meta_len.value)], path),
+            "file_bytes": os.path.getsize(path)}
+
+
+def last_tig_index_file_times() -> dict:
+    """Phases on this thread, in ms: of the last TigIndex.save the digest kernels (HIP events), the download and the write (host
+    clock); of the last TigIndex.load the read and the upload (host clock), the digest kernels and the validation kernel (HIP events)."""
+    out = (C.c_double * 7)()
+    _lib.load().mtg_last_tig_index_file_times(out)
+    return {"save": dict(zip(("digest_ms", "download_ms", "write_ms"), out[0:3])),
+            "load": dict(zip(("read_ms", "upload_ms", "digest_ms", "validate_ms"), out[3:7]))}
+
+
 class TigIndex:
     """The canonical k-mers of a sequence set as a sparse index on GPU `device_id` (mtg_tig_index_*): the 2-bit packed
     bases plus one word per minimizer anchor instead of KmerIndex's table slot per window, so its size follows the cumulative length
@@ -1878,7 +1932,9 @@ class TigIndex:
     color_hits() exactly as the annotated KmerIndex does -- the payload of a k-mer is that of its first occurrence. Each payload is
     kept per window of the text, dense or as runs of equal entries, whichever is smaller (a tie is dense; payload_layout "dense" or
     "runs" forces one): see payload_info ({"weights": {...}, "colors": {...}}, each with layout, width, windows, runs,
-    device_bytes; {} on an index without payloads)."""
+    device_bytes; {} on an index without payloads).
+    save(path, meta) / TigIndex.load(path): the index as a file and back, without its sequences; `meta` is the dict
+    given to the last save or read by load ({} otherwise)."""
 
     _LAYOUTS = {None: 0, "dense": 1, "runs": 2}
 
@@ -1901,6 +1957,7 @@ class TigIndex:
         self.colored = colors is not None
         self.n_colors = 0
         self.payload_info = {}
+        self.meta = {}
         if m is not None and not 1 <= m <= min(k, 31):
             raise ValueError(f"m must be in 1..min(k, 31), not {m!r}")
         if bucket_limit is not None and not 1 <= bucket_limit <= 65536:
@@ -1931,11 +1988,46 @@ class TigIndex:
         if annotated:
             pi = _lib.MtgTigPayloadInfo()
             self._L.mtg_tig_index_get_payload_info(self._h, C.byref(pi))
-            names = {1: "dense", 2: "runs"}
-            for key, one in (("weights", pi.weights), ("colors", pi.colors)):
-                if one.layout:
-                    self.payload_info[key] = dict(one.as_dict(), layout=names[int(one.layout)])
+            self.payload_info = _payload_info_dict(pi)
             self.n_colors = int(pi.n_colors)
+
+    def save(self, path, meta: Optional[dict] = None) -> int:
+        """Writes the index to `path` (mtg_tig_index_save; conventional suffix .mtgx) and returns the bytes written.
+        meta: a JSON-serialisable dict the file carries and load() returns; the library stores it without reading it. The file is a
+        function of the index and meta alone. A file that cannot be written raises IndexFileError."""
+        if not self._h:
+            raise ValueError("the index is closed")
+        blob = json.dumps(meta if meta is not None else {}, ensure_ascii=False, sort_keys=True, separators=(",", ":")).encode("utf-8")
+        err = C.create_string_buffer(4096)
+        if self._L.mtg_tig_index_save(self._h, str(path).encode(), blob, len(blob), err, len(err)) != 0:
+            raise IndexFileError(err.value.decode(errors="replace"))
+        self.meta = dict(meta) if meta is not None else {}
+        return os.path.getsize(path)
+
+    @classmethod
+    def load(cls, path, device_id: int = 0) -> "TigIndex":
+        """The index of a file written by save() (mtg_tig_index_load): read and uploaded, not rebuilt; info,
+        locating, weighted, colored, n_colors and payload_info as the builder filled them, plus meta. A file that is damaged,
+        truncated, of a later format version or whose arrays break an invariant of the probes raises IndexFileError naming the
+        path, the section and the check; nothing of it stays on the device."""
+        ix = cls.__new__(cls)
+        ix._h = None
+        ix._L = _lib.load()
+        err = C.create_string_buffer(4096)
+        ix._h = ix._L.mtg_tig_index_load(str(path).encode(), device_id, err, len(err))
+        if not ix._h:
+            raise IndexFileError(err.value.decode(errors="replace"))
+        out, pi, n = _lib.MtgTigIndexInfo(), _lib.MtgTigPayloadInfo(), C.c_uint64(0)
+        ix._L.mtg_tig_index_get_info(ix._h, C.byref(out))
+        ix._L.mtg_tig_index_get_payload_info(ix._h, C.byref(pi))
+        ix.info = TigIndexInfo(**out.as_dict())
+        ix.locating = bool(ix._L.mtg_tig_index_is_locating(ix._h))
+        ix.weighted, ix.colored = bool(pi.weights.layout), bool(pi.colors.layout)
+        ix.payload_info = _payload_info_dict(pi)
+        ix.n_colors = int(pi.n_colors)
+        p = ix._L.mtg_tig_index_meta(ix._h, C.byref(n))
+        ix.meta = _meta_dict(C.string_at(p, int(n.value)) if n.value else b"", path)
+        return ix
 
     def close(self) -> None:
         h, self._h = getattr(self, "_h", None), None

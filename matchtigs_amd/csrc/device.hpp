@@ -1,6 +1,7 @@
 // device.hpp -- interface of the HIP device stage (device_build.hip, device_classify.hip, device_sssp.hip, device_replay.hip, device_pairs.hip) towards the C-ABI layer.
 #pragma once
 
+#include <string>
 #include <thread>
 #include <cstdint>
 #include <vector>
@@ -284,6 +285,14 @@ void device_tig_index_abundance(const TigIndex *ix, const char *seq, const uint6
 void device_tig_index_colors(const TigIndex *ix, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid,
                              uint64_t *found, uint32_t *per_color, uint64_t *per_window, TigPayloadTimes *times);
 void device_tig_index_free(TigIndex *ix);
+// the index as a file (tig_index_file_device.hpp). save: false and err = why the file could not be written. load: null
+// and err = "<path>: <section>: <check>" for a file that is refused, with every allocation returned; meta: the file's metadata blob.
+// times: of a save {digest kernels, download, write}, of a load {read, upload, digest kernels, validation kernel}, in ms.
+struct TigIndexFileTimes {
+    double save_digest_ms = 0, save_download_ms = 0, save_write_ms = 0, load_read_ms = 0, load_upload_ms = 0, load_digest_ms = 0, load_validate_ms = 0;
+};
+bool device_tig_index_save(const TigIndex *ix, const char *path, const char *meta, uint64_t meta_len, TigIndexFileTimes *times, std::string &err);
+TigIndex *device_tig_index_load(const char *path, int device_id, std::string &meta, TigIndexFileTimes *times, std::string &err);
 // A tally over one locating sparse index (tig_tally_device.hpp): device_kmer_tally_*'s contracts and results with one
 // 64-bit counter per window ordinal of the indexed text (plus win_off[records + 1] where the index keeps none), counted at the first
 // occurrence of a window's class. counters: the W counters in window order. times: host wall clock of the upload and the download,

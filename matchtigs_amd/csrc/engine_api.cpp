@@ -881,7 +881,10 @@ void mtg_last_kmer_query_times(double out[6]) {
     out[3] = t.query_upload_ms; out[4] = t.query_pack_ms; out[5] = t.query_probe_ms;
 }
 // ---- the sparse minimizer index (tig_index_device.hip) ----
-struct mtg_tig_index { TigIndex *ix; };
+struct mtg_tig_index {
+    TigIndex *ix;
+    std::string meta{};  // the metadata blob of the file it was loaded from, or of its last save
+};
 static thread_local TigIndexTimes g_last_tig_index;
 mtg_tig_index *mtg_tig_index_build(const char *seq, const uint64_t *off, uint64_t n, uint64_t k, uint64_t m, uint64_t bucket_limit, int device_id) {
     return new mtg_tig_index{device_tig_index_build(seq, off, n, k, m, bucket_limit, device_id, &g_last_tig_index)};
@@ -1174,6 +1177,43 @@ void mtg_last_kmer_correct_times(double out[8]) {
     const KmerCorrectCall &t = g_last_kmer_correct;
     out[0] = t.upload_ms; out[1] = t.pack_ms; out[2] = t.query_ms; out[3] = t.flag_ms; out[4] = t.evaluate_ms; out[5] = t.apply_ms;
     out[6] = t.download_ms; out[7] = t.total_ms;
+}
+// ---- the index as a file ----
+static thread_local TigIndexFileTimes g_last_tig_index_file;
+static void put_message(const std::string &msg, char *err, uint64_t err_len) {
+    if (err && err_len) std::snprintf(err, err_len, "%s", msg.c_str());
+}
+int mtg_tig_index_save(const mtg_tig_index *ix, const char *path, const char *meta_json, uint64_t meta_len, char *err, uint64_t err_len) {
+    if (!ix || !path || (meta_len && !meta_json)) MTG_DIE("mtg_tig_index_save: null argument");
+    std::string why;
+    if (!device_tig_index_save(ix->ix, path, meta_json, meta_len, &g_last_tig_index_file, why)) {
+        put_message(why, err, err_len);
+        return 2;
+    }
+    const_cast<mtg_tig_index *>(ix)->meta.assign(meta_json ? meta_json : "", meta_len);
+    return 0;
+}
+mtg_tig_index *mtg_tig_index_load(const char *path, int device_id, char *err, uint64_t err_len) {
+    if (!path) MTG_DIE("mtg_tig_index_load: null argument");
+    std::string why, meta;
+    TigIndex *t = device_tig_index_load(path, device_id, meta, &g_last_tig_index_file, why);
+    if (!t) {
+        put_message(why, err, err_len);
+        return nullptr;
+    }
+    mtg_tig_index *ix = new mtg_tig_index{t};
+    ix->meta = std::move(meta);
+    return ix;
+}
+const char *mtg_tig_index_meta(const mtg_tig_index *ix, uint64_t *len) {
+    if (!ix) MTG_DIE("mtg_tig_index_meta: null argument");
+    if (len) *len = ix->meta.size();
+    return ix->meta.data();
+}
+void mtg_last_tig_index_file_times(double out[7]) {
+    const TigIndexFileTimes &t = g_last_tig_index_file;
+    out[0] = t.save_digest_ms; out[1] = t.save_download_ms; out[2] = t.save_write_ms;
+    out[3] = t.load_read_ms; out[4] = t.load_upload_ms; out[5] = t.load_digest_ms; out[6] = t.load_validate_ms;
 }
 void mtg_tig_index_free(mtg_tig_index *ix) {
     if (!ix) return;

@@ -49,6 +49,10 @@
 // reads and, with mates, once more for the mates into per_color and counts arrays that stay on the device; pseudoalign_device.hpp
 // turns every row into one mask and the masks into their dictionary.
 //
+// Files (mtg_tig_index_save / _load): the device arrays of the TigIndex struct below, as they are, behind a header;
+// tig_index_file_device.hpp, included at the end of this file, digests them on the device, and validates what a load has uploaded
+// against everything the probes here assume of the arrays. No kernel of this file knows where its index came from.
+//
 // Exactness. A hit is declared only after kw::same_class has compared the query's k bases with k index bases that lie inside ONE
 // record, or after the heavy table's exact `same`: never a false positive, and a tag or hash collision costs a compare. No false
 // negative: let the class of the query window x be the index window y at c. Both have the same set of m-mer classes, hence the same
@@ -1023,3 +1027,6 @@ void device_tig_tally_coverage(const TigTally *t, const char *seq, const uint64_
 }
 
 }  // namespace mtg
+
+// ---- the index as a file ----
+#include "tig_index_file_device.hpp"
