@@ -662,6 +662,48 @@ void mtg_tig_index_locate(const mtg_tig_index *ix, const char *seq, const uint64
 /* Of the last mtg_tig_index_locate on this thread, in ms: {upload (host clock), pack, probe (with the fill of the hit array), runs
  * (flag, scan, emit)} -- HIP events around the kernels. */
 void mtg_last_tig_locate_times(double out[4]);
+/* WHICH PATH through the indexed records a query takes: the runs of mtg_kmer_index_locate joined across record ends
+ * into walks. Let W(u) = len(u) - k + 1 be the windows of index record u. A run (q_record, q_start, n = kmers, strand, u = t_record,
+ * t = t_start) ENTERS AT THE HEAD of u iff t == 0 (+) or t + n == W(u) (-), and LEAVES AT THE TAIL iff t + n == W(u) (+) or t == 0
+ * (-). Run r + 1 CONTINUES run r iff both have the same q_record, q_start[r + 1] == q_start[r] + n[r], r leaves at the tail and
+ * r + 1 enters at the head: the query being contiguous there, the last k - 1 bases of step r, as oriented, are the first k - 1 of
+ * step r + 1, so over unitigs every walk is a path over the links of mtg_write_unitig_graph_text. Whatever is indexed, a walk is
+ * never wrong, only shorter: a k-mer that occurs more than once is located at its smallest position, which breaks runs and walks.
+ * A WALK is a maximal chain of continuing runs; its steps are the runs' (t_record, strand) in order (a ring record taken twice is
+ * two steps). Per walk, with K = the sum of n over its runs: q_record, q_start (of the first run), q_end = q_start + K + k - 1,
+ * kmers = K, steps, first_step (index of its first step in the step array), path_len = the sum of W(u) over its steps + k - 1,
+ * path_start = the offset of the walk's first base in its first step as oriented (t on +, W(u) - (t + n) on -), path_end =
+ * path_start + (q_end - q_start). Walks with K < min_kmers are dropped on the device (0 and 1 keep all); the kept walks come in
+ * ascending query position and their steps follow each other in the step array, (t_record << 1) | strand each. kmers / valid / found
+ * are those of mtg_kmer_index_query. Exact integers, a function of the inputs alone; mtg_tig_index_thread gives the same walks
+ * field for field, for every m and bucket_limit. Both die if the index is not locating. Fewer than 2^32 runs per call. */
+typedef struct mtg_kmer_walks mtg_kmer_walks;
+void mtg_kmer_index_thread(const mtg_kmer_index *ix, const char *seq, const uint64_t *off, uint64_t n, uint64_t min_kmers,
+                           uint64_t *kmers, uint64_t *valid, uint64_t *found, /* [n] each */
+                           mtg_kmer_walks **out);                             /* mtg_kmer_walks_free */
+void mtg_tig_index_thread(const mtg_tig_index *ix, const char *seq, const uint64_t *off, uint64_t n, uint64_t min_kmers,
+                          uint64_t *kmers, uint64_t *valid, uint64_t *found, /* [n] each */
+                          mtg_kmer_walks **out);                             /* mtg_kmer_walks_free */
+uint64_t mtg_kmer_walks_count(const mtg_kmer_walks *walks);
+uint64_t mtg_kmer_walks_steps_count(const mtg_kmer_walks *walks);
+/* fields[0 .. 9): q_record, q_start, q_end, kmers, steps, first_step, path_len, path_start, path_end -- count entries each; valid
+ * until mtg_kmer_walks_free */
+void mtg_kmer_walks_arrays(const mtg_kmer_walks *walks, const uint64_t *fields[9]);
+const uint64_t *mtg_kmer_walks_steps(const mtg_kmer_walks *walks); /* steps_count entries; valid until mtg_kmer_walks_free */
+void mtg_kmer_walks_free(mtg_kmer_walks *walks);                   /* NULL is fine */
+/* Of the last mtg_kmer_index_thread / mtg_tig_index_thread on this thread, in ms: {upload (host clock), pack, probe (with the fill of
+ * the hit array), runs (flag, scan, emit), walks (flag, scans, emit, compaction)} -- HIP events around the kernels. */
+void mtg_last_kmer_thread_times(double out[5]);
+void mtg_last_tig_thread_times(double out[5]);
+/* The walks as GAF text, one line per walk in the handle's order, written by the host's threads (the walks are on the host by
+ * then): query name, query_len[q_record], q_start, q_end, "+", the path (">" + name per + step, "<" + name per - step), path_len,
+ * path_start, path_end, matches and alignment length (both q_end - q_start), 255, "cg:Z:{q_end - q_start}=" and "km:i:{kmers}",
+ * tab-separated. Name i of a list is the bytes [off[i], off[i + 1]) of its text; segment_names == NULL names index record u by its
+ * decimal number, as the S lines of mtg_write_unitig_graph_text do. Dies on a walk or a step beyond the names given. *text_out is
+ * malloc'd and 0-terminated (mtg_free). Returns the bytes. */
+uint64_t mtg_kmer_walks_gaf(const mtg_kmer_walks *walks, uint64_t n_queries, const char *query_names, const uint64_t *query_name_off,
+                            const uint64_t *query_len, uint64_t n_segments, const char *segment_names,
+                            const uint64_t *segment_name_off, char **text_out);
 /* HOW HEAVY the k-mers of a query are. A WEIGHTED index is built by the two functions below from the sequences and
  * one uint32 per window of them, in window order: a record shorter than k has no window, and the window at global position q of
  * record r has the ordinal (windows of the records before r) + (q - off[r]). n_weights must equal info.occurrences, else the call

@@ -84,6 +84,13 @@ tigs this run wrote; with `--index-weights` / `--index-colors` the abundances an
 one file, and `--index-in PATH` is a fifth kind of input: a run on such a file reads no sequences of the indexed set, compacts nothing
 and answers `--query-fa` and `--pseudoalign-fa` byte for byte as the building run did. `--index-info PATH` prints the file's header and
 metadata without a GPU.
+`--thread-fa` (not in the reference) threads reads, genes or haplotypes through the unitig graph: over the unitigs every k-mer has one
+place, so the located runs of a record, joined wherever one ends at a unitig's end and the next starts at another's start, are the
+segments of its path. `--thread-gaf-out` gets one GAF line per maximal walk -- the `>`/`<` oriented `S` names of `--unitigs-gfa-out`,
+the path's length and the exact interval on it, a walk may start and end inside a segment -- and `--thread-report-out` one row per
+read; a read with an error k-mer the cleaning removed is broken exactly there. `--thread-min-kmers N` drops shorter walks,
+`--thread-index minimizer` threads on the sparse index with the same files, and with `--index-in` the walks run over the records of
+whatever the file indexed, where repeated k-mers (tigs) only shorten them.
 """
 from __future__ import annotations
 
@@ -283,6 +290,23 @@ def main(argv=None) -> int:
     ap.add_argument("--correct-min-solid", type=int, metavar="W",
                     help="a substitution must make at least min(W, the valid k-mers that cover the base) of them solid (W >= 1, default 4)")
     ap.add_argument("--correct-rounds", type=int, metavar="R", help="rounds of correction, each on the text the one before left (1..8, default 2)")
+    ap.add_argument("--thread-fa", action="append", metavar="PATH",
+                    help="reads, genes or haplotypes (fasta or fastq, optionally .gz; any characters) that are threaded through the "
+                         "unitig graph on the GPU: every maximal walk their k-mers take over the unitigs as written; repeatable; needs "
+                         "--thread-gaf-out or --thread-report-out (not in the reference)")
+    ap.add_argument("--thread-gaf-out", metavar="PATH",
+                    help="GAF (.gz => gzip) with one line per walk of all --thread-fa files, in file and query order: the path over the "
+                         "segments of --unitigs-gfa-out, exact, with cg:Z: and km:i: (the walk's k-mers)")
+    ap.add_argument("--thread-report-out", metavar="PATH",
+                    help="TSV (.gz => gzip) with one row per read of all --thread-fa files: file, record, length, kmers, valid, found, "
+                         "walks, steps, longest (the most k-mers of one of its walks)")
+    ap.add_argument("--thread-min-kmers", type=int, metavar="N", help="drop walks of fewer than N k-mers (N >= 1, default 1)")
+    ap.add_argument("--thread-min-base-quality", type=int, metavar="Q",
+                    help="with fastq --thread-fa files: a base whose Phred quality is below Q (0..93) is replaced by N")
+    ap.add_argument("--thread-index", choices=("table", "minimizer"),
+                    help="the locating index the reads are threaded on: table (default) or minimizer (the sparse index: the same files)")
+    ap.add_argument("--thread-minimizer-length", type=int, metavar="M",
+                    help="with --thread-index minimizer: the minimizer length, 1 .. min(k, 31) (default min(19, ceil(2k/3)))")
     ap.add_argument("--index-out", metavar="PATH",
                     help="after the tig outputs: build a locating sparse minimizer index and save it as one file (conventional suffix "
                          ".mtgx) that --index-in reopens (not in the reference)")
@@ -398,6 +422,9 @@ def main(argv=None) -> int:
                             ("--correct-min-solid", args.correct_min_solid), ("--correct-rounds", args.correct_rounds)):
             if value is not None:
                 ap.error(f"{flag} needs --correct-fa")
+    _check_thread(ap, args)
+    if args.thread_minimizer_length is not None and not 1 <= args.thread_minimizer_length <= min(args.k, 31):
+        ap.error(f"--thread-minimizer-length must be in 1..{min(args.k, 31)} (1 .. min(k, 31), as --query-minimizer-length)")
     for over, out in (("greedytigs", args.greedytigs_fa_out), ("eulertigs", args.eulertigs_fa_out)):
         if args.count_index_over == over and not out:
             ap.error(f"--count-index-over {over} needs --{over}-fa-out")
@@ -466,7 +493,7 @@ def main(argv=None) -> int:
                         ("--pseudoalign-min-base-quality", args.pseudoalign_min_base_quality)):
         if value is not None and not 0 <= value <= 93:
             ap.error(f"{flag} must be in 0..93")
-    if not (args.color_classes_out or args.unitig_color_classes_out or args.color_matrix_out or args.unitig_colors_out or args.kmer_spectrum_out or args.unitig_abundance_out or args.unitig_kmer_abundance_out or args.query_fa or args.count_fa or args.pseudoalign_fa or args.correct_fa or args.greedytigs_fa_out or args.eulertigs_fa_out or args.greedytigs_gfa_out or args.eulertigs_gfa_out
+    if not (args.color_classes_out or args.unitig_color_classes_out or args.color_matrix_out or args.unitig_colors_out or args.kmer_spectrum_out or args.unitig_abundance_out or args.unitig_kmer_abundance_out or args.query_fa or args.count_fa or args.pseudoalign_fa or args.correct_fa or args.thread_fa or args.greedytigs_fa_out or args.eulertigs_fa_out or args.greedytigs_gfa_out or args.eulertigs_gfa_out
             or args.greedytigs_duplication_bitvector_out or args.matchtigs_fa_out or args.matchtigs_gfa_out or args.verify_fa or args.unitigs_fa_out
             or args.unitigs_bcalm_out or args.unitigs_gfa_out or args.components_out or args.unitig_components_out or args.index_out):
         ap.error("nothing to do: give --greedytigs-fa-out / --greedytigs-gfa-out and/or --eulertigs-fa-out / --eulertigs-gfa-out")
@@ -476,7 +503,7 @@ def main(argv=None) -> int:
     # FASTQ is told from FASTA by the content; the quality flags need a file they can apply to
     aligned = (args.pseudoalign_fa or []) + (args.pseudoalign_mate_fa or [])
     fastq = {path for path in (args.seq_in or []) + (args.query_fa or []) + (args.count_fa or []) + aligned + (args.correct_fa or [])
-             if api.sequence_file_format(path) == 2}
+             + (args.thread_fa or []) if api.sequence_file_format(path) == 2}
     if args.min_base_quality is not None and not fastq.intersection((args.seq_in or []) + (args.query_fa or [])):
         ap.error("--min-base-quality needs a fastq file among --seq-in / --query-fa")
     if args.query_min_base_quality is not None and not fastq.intersection(args.query_fa or []):
@@ -485,11 +512,32 @@ def main(argv=None) -> int:
         ap.error("--count-min-base-quality needs a fastq file among --count-fa")
     if args.pseudoalign_min_base_quality is not None and not fastq.intersection(aligned):
         ap.error("--pseudoalign-min-base-quality needs a fastq file among --pseudoalign-fa / --pseudoalign-mate-fa")
+    if args.thread_min_base_quality is not None and not fastq.intersection(args.thread_fa):
+        ap.error("--thread-min-base-quality needs a fastq file among --thread-fa")
     try:
         return _run(api, args, fastq)
     except api.FastqFormatError as e:  # an error of the input: the message names file, record, line and reason
         print(e, file=sys.stderr)
         return 2
+
+
+def _check_thread(ap, args) -> None:
+    """The rules of the `--thread-*` flags among themselves (those that need neither k nor a file)."""
+    if args.thread_fa:
+        if not (args.thread_gaf_out or args.thread_report_out):
+            ap.error("--thread-fa needs --thread-gaf-out or --thread-report-out")
+        if args.thread_min_kmers is not None and not 1 <= args.thread_min_kmers < 1 << 63:
+            ap.error("--thread-min-kmers must be >= 1")
+        if args.thread_min_base_quality is not None and not 0 <= args.thread_min_base_quality <= 93:
+            ap.error("--thread-min-base-quality must be in 0..93")
+        if args.thread_minimizer_length is not None and args.thread_index != "minimizer":
+            ap.error("--thread-minimizer-length needs --thread-index minimizer")
+    else:
+        for flag, value in (("--thread-gaf-out", args.thread_gaf_out), ("--thread-report-out", args.thread_report_out),
+                            ("--thread-min-kmers", args.thread_min_kmers), ("--thread-min-base-quality", args.thread_min_base_quality),
+                            ("--thread-index", args.thread_index), ("--thread-minimizer-length", args.thread_minimizer_length)):
+            if value is not None:
+                ap.error(f"{flag} needs --thread-fa")
 
 
 def _check_pseudoalign(ap, args) -> None:
@@ -543,7 +591,8 @@ _INDEX_IN_SERVES = {"help", "index_in", "k", "threads", "device", "compression_l
                     "query_presence_out", "query_index_locate_out", "query_min_base_quality", "query_index", "query_index_abundance_out",
                     "query_index_abundance_profile_out", "query_index_colors_out", "pseudoalign_fa", "pseudoalign_mate_fa", "pseudoalign_out",
                     "pseudoalign_classes_out", "pseudoalign_summary_out", "pseudoalign_threshold", "pseudoalign_over", "pseudoalign_min_kmers",
-                    "pseudoalign_min_base_quality", "pseudoalign_index"}
+                    "pseudoalign_min_base_quality", "pseudoalign_index", "thread_fa", "thread_gaf_out", "thread_report_out", "thread_min_kmers",
+                    "thread_min_base_quality", "thread_index"}
 
 
 def _index_info(path) -> int:
@@ -582,15 +631,18 @@ def _main_index_in(ap, args) -> int:
         flag = action.option_strings[-1]
         if action.dest in ("bcalm_in", "gfa_in", "fa_in", "seq_in"):
             ap.error(f"--index-in cannot be combined with {flag}: the index file is the input")
-        if action.dest in ("query_index_over", "query_minimizer_length", "pseudoalign_minimizer_length"):
+        if action.dest in ("query_index_over", "query_minimizer_length", "pseudoalign_minimizer_length", "thread_minimizer_length"):
             ap.error(f"{flag} cannot be combined with --index-in: what is indexed and its minimizer length are the file's to say")
         ap.error(f"{flag} cannot be combined with --index-in: it needs the sequences of the indexed set, and a run on an index file reads none")
     if args.query_index == "table":
         ap.error("--query-index table cannot be combined with --index-in: the file holds the minimizer index")
     if args.pseudoalign_index == "table":
         ap.error("--pseudoalign-index table cannot be combined with --index-in: the file holds the minimizer index")
-    if not (args.query_fa or args.pseudoalign_fa):
-        ap.error("nothing to do with --index-in: give --query-fa with --query-out and/or --pseudoalign-fa")
+    if args.thread_index == "table":
+        ap.error("--thread-index table cannot be combined with --index-in: the file holds the minimizer index")
+    if not (args.query_fa or args.pseudoalign_fa or args.thread_fa):
+        ap.error("nothing to do with --index-in: give --query-fa with --query-out, --pseudoalign-fa and/or --thread-fa")
+    _check_thread(ap, args)
     if bool(args.query_fa) != bool(args.query_out):
         ap.error("--query-fa needs --query-out" if args.query_fa else "--query-out needs --query-fa")
     for flag, value in (("--query-presence-out", args.query_presence_out), ("--query-index-locate-out", args.query_index_locate_out),
@@ -610,11 +662,13 @@ def _main_index_in(ap, args) -> int:
     from . import api
 
     aligned = (args.pseudoalign_fa or []) + (args.pseudoalign_mate_fa or [])
-    fastq = {path for path in (args.query_fa or []) + aligned if api.sequence_file_format(path) == 2}
+    fastq = {path for path in (args.query_fa or []) + aligned + (args.thread_fa or []) if api.sequence_file_format(path) == 2}
     if args.query_min_base_quality is not None and not fastq.intersection(args.query_fa or []):
         ap.error("--query-min-base-quality needs a fastq file among --query-fa")
     if args.pseudoalign_min_base_quality is not None and not fastq.intersection(aligned):
         ap.error("--pseudoalign-min-base-quality needs a fastq file among --pseudoalign-fa / --pseudoalign-mate-fa")
+    if args.thread_min_base_quality is not None and not fastq.intersection(args.thread_fa):
+        ap.error("--thread-min-base-quality needs a fastq file among --thread-fa")
     try:
         head = api.tig_index_file_info(args.index_in)  # (on the host: what the file can serve is known before the GPU is touched)
         if args.k is not None and args.k != head["info"].k:
@@ -623,7 +677,8 @@ def _main_index_in(ap, args) -> int:
         for flag, value, has, lacks in (("--query-index-locate-out", args.query_index_locate_out, head["locating"], "the positions of its heavy buckets"),
                                         ("--query-index-abundance-out", args.query_index_abundance_out, head["weighted"], "weights (--index-weights)"),
                                         ("--query-index-colors-out", args.query_index_colors_out, head["colored"], "colours (--index-colors)"),
-                                        ("--pseudoalign-fa", args.pseudoalign_fa, head["colored"], "colours (--index-colors)")):
+                                        ("--pseudoalign-fa", args.pseudoalign_fa, head["colored"], "colours (--index-colors)"),
+                                        ("--thread-fa", args.thread_fa, head["locating"], "the positions of its heavy buckets")):
             if value and not has:
                 ap.error(f"{flag} cannot be served by --index-in {args.index_in}: the file keeps no {lacks}")
         names = head["meta"].get("colors") or []
@@ -637,6 +692,8 @@ def _main_index_in(ap, args) -> int:
             if args.query_fa:
                 _query(api, args, None, True if args.query_index_abundance_out else None, fastq, True if args.query_index_colors_out else None,
                        loaded=index)
+            if args.thread_fa:  # (the segments are the records of whatever the file indexed, by number)
+                _thread(api, args, None, fastq, index, keep=True)
             if args.pseudoalign_fa:
                 return _pseudoalign(api, args, None, None, fastq, loaded=index)
         return 0
@@ -895,13 +952,30 @@ def _run(api, args, fastq) -> int:
     share_sparse = bool(count_sparse and args.query_fa and args.query_index == "minimizer"
                         and (args.query_index_over or "input") == (args.count_index_over or "input")
                         and args.count_minimizer_length in (None, args.query_minimizer_length or api.default_minimizer_length(args.k)))
+    # ... or the one the threading asks for: a LOCATING index over the unitig store -- the table if --query-locate-out
+    # made it one, or the sparse index with the same minimizer length, unless a sparse count takes (and closes) that first
+    thread_table = bool(args.thread_fa) and args.thread_index != "minimizer"
+    thread_takes_table = thread_table and bool(args.query_fa and args.query_locate_out)
+    thread_takes_sparse = bool(args.thread_fa and args.thread_index == "minimizer" and not count_sparse and args.query_fa
+                               and args.query_index == "minimizer" and (args.query_index_over or "input") == "input"
+                               and args.thread_minimizer_length in (None, args.query_minimizer_length or api.default_minimizer_length(args.k)))
+    thread_index = None
     if args.query_fa:
         shared_index = _query(api, args, store, abundance.kmer_counts if args.query_abundance_out or args.query_index_abundance_out else None, fastq,
                               colors if args.query_colors_out or args.query_index_colors_out else None,
-                              keep_index=(bool(args.count_fa) and not count_sparse) or bool(args.correct_fa and not args.count_fa),
-                              keep_sparse=share_sparse)
-    if args.count_fa:  # (with --correct-fa a table index it counted on stays open for the correction)
-        shared_index = _count(api, args, store, fastq, shared_index, keep=bool(args.correct_fa))
+                              keep_index=(bool(args.count_fa) and not count_sparse) or bool(args.correct_fa and not args.count_fa)
+                              or thread_takes_table,
+                              keep_sparse=share_sparse or thread_takes_sparse)
+        if thread_takes_sparse or (thread_takes_table and (count_sparse or not args.count_fa)):  # (no table count in between)
+            thread_index, shared_index = shared_index, None
+    if args.count_fa:  # (with --correct-fa or a threading on the table a table index it counted on stays open)
+        shared_index = _count(api, args, store, fastq, shared_index, keep=bool(args.correct_fa) or (thread_takes_table and shared_index is not None))
+    if args.thread_fa:
+        if thread_takes_table and thread_index is None:
+            thread_index, shared_index = shared_index, None
+        # (a table index threaded on serves the correction too, unless the count left one for it already)
+        kept = _thread(api, args, store, fastq, thread_index, keep=bool(args.correct_fa) and thread_table and shared_index is None)
+        shared_index = kept if kept is not None else shared_index
     if args.pseudoalign_fa:
         status = _pseudoalign(api, args, store, colors, fastq)
         if status:
@@ -1299,6 +1373,61 @@ def _count(api, args, store, fastq=(), index=None, keep=False):
             rows = np.stack([np.arange(len(kmers), dtype=np.uint64), kmers] + columns, axis=1).tolist() if len(kmers) else []
             f.writelines("\t".join(map(str, row)) + "\n" for row in rows)
         return index if keep and not sparse else None
+
+
+def _thread(api, args, store, fastq=(), index=None, keep=False):
+    """`--thread-fa`: every file's records threaded through the unitig store. One LOCATING index over the store -- `index`,
+    the one the queries or the count left open, if it is the kind `--thread-index` names, else one built here -- serves all files in
+    turn; the segments of a path are the store's records by number, the `S` names of `--unitigs-gfa-out`. `--thread-gaf-out`: the
+    lines of all files one after the other, formatted by the library; `--thread-report-out`: one row per read. With `--index-in`
+    (store None) `index` is the file's sparse index and the segments are the records of whatever it indexed, by number; over tigs
+    a k-mer that occurs twice is located once, which shortens walks and never makes one wrong. keep: a table index is handed back
+    open instead of closed (`--correct-fa` follows), and the file's index always is."""
+    import contextlib
+    import gzip
+
+    import numpy as np
+
+    with contextlib.ExitStack() as stack:
+        sparse = args.thread_index == "minimizer" or store is None
+        if index is None:
+            index = (api.TigIndex(store, args.k, args.thread_minimizer_length, args.device, locate=True) if sparse
+                     else api.KmerIndex(store, args.k, args.device, locate=True))
+            print(f"Indexing the input for the threading: {_describe_index(index, sparse)}", file=sys.stderr)
+        elif not index.locating or not isinstance(index, api.TigIndex if sparse else api.KmerIndex):
+            raise SystemExit("internal error: the index handed to the threading is not the locating index it asked for")
+        keep = keep and (store is None or not sparse)
+        if not keep:
+            stack.enter_context(index)
+        gaf = None
+        if args.thread_gaf_out:
+            out = args.thread_gaf_out
+            gaf = stack.enter_context(gzip.open(out, "wb", compresslevel=args.compression_level) if out.endswith(".gz") else open(out, "wb"))
+        report = stack.enter_context(_open_text(args, args.thread_report_out)) if args.thread_report_out else None
+        if report is not None:
+            report.write("file\trecord\tlength\tkmers\tvalid\tfound\twalks\tsteps\tlongest\n")
+        for path in args.thread_fa:
+            t0 = time.perf_counter()
+            if path in fastq:
+                seqs, names, _ = api.read_fastq(path, args.thread_min_base_quality or 0, args.device, named=True)
+            else:
+                seqs, names = api.read_sequences_named(path)
+            r = index.thread(seqs, args.thread_min_kmers or 1)
+            if gaf is not None:
+                gaf.write(r.gaf(names))
+            n, w = len(names), r.walks
+            record = w["q_record"].astype(np.int64)
+            walks, steps = np.bincount(record, minlength=n), np.bincount(record, weights=w["steps"].astype(np.float64), minlength=n).astype(np.int64)
+            longest = np.zeros(n, np.uint64)
+            np.maximum.at(longest, record, w["kmers"])
+            if report is not None:
+                columns = [x.tolist() for x in (np.diff(r.offsets), r.kmers, r.valid, r.found, walks, steps, longest)]
+                report.writelines("\t".join([path, name] + [str(c[q]) for c in columns]) + "\n" for q, name in enumerate(names))
+            whole = int(np.count_nonzero((walks == 1) & (longest == r.kmers) & (r.kmers > 0)))
+            r.close()
+            print(f"Threading {path}: {n} reads, {whole} threaded end to end, {len(w)} walks, {int(w['steps'].sum())} steps, "
+                  f"{int(w['kmers'].sum())} k-mers threaded of {int(r.found.sum())} found in {time.perf_counter() - t0:.1f} s", file=sys.stderr)
+        return index if keep and store is not None else None
 
 
 def _pseudoalign(api, args, store, colors, fastq=(), loaded=None) -> int:

@@ -364,6 +364,16 @@ def load():
         "mtg_tig_index_is_locating": (C.c_int, [vp]),
         "mtg_tig_index_locate": (None, [vp, vp, vp, u64, vp, vp, vp, P(vp)]),
         "mtg_last_tig_locate_times": (None, [P(C.c_double)]),
+        "mtg_kmer_index_thread": (None, [vp, vp, vp, u64, u64, vp, vp, vp, P(vp)]),
+        "mtg_tig_index_thread": (None, [vp, vp, vp, u64, u64, vp, vp, vp, P(vp)]),
+        "mtg_kmer_walks_count": (u64, [vp]),
+        "mtg_kmer_walks_steps_count": (u64, [vp]),
+        "mtg_kmer_walks_arrays": (None, [vp, vp]),
+        "mtg_kmer_walks_steps": (vp, [vp]),
+        "mtg_kmer_walks_free": (None, [vp]),
+        "mtg_last_kmer_thread_times": (None, [P(C.c_double)]),
+        "mtg_last_tig_thread_times": (None, [P(C.c_double)]),
+        "mtg_kmer_walks_gaf": (u64, [vp, u64, vp, vp, vp, u64, vp, vp, P(vp)]),
         "mtg_kmer_index_build_weighted": (vp, [vp, vp, u64, u64, vp, u64, C.c_int, C.c_int]),
         "mtg_kmer_index_build_weighted_store": (vp, [vp, u64, vp, u64, C.c_int, C.c_int]),
         "mtg_kmer_index_is_weighted": (C.c_int, [vp]),

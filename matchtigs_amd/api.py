@@ -1605,6 +1605,87 @@ def _take_runs(L, h) -> np.ndarray:
     return runs
 
 
+KMER_WALK_DTYPE = np.dtype([(name, np.uint64) for name in ("q_record", "q_start", "q_end", "kmers", "steps", "first_step", "path_len",
+                                                           "path_start", "path_end")])
+
+
+@dataclass(frozen=True, eq=False)
+class KmerThreadResult:
+    """What KmerIndex.thread found: kmers / valid / found per query record as KmerIndex.query gives them; `walks`, a
+    structured array (KMER_WALK_DTYPE) with one entry per walk in ascending query position; and `steps` (uint64), the steps of all
+    walks one after the other, (t_record << 1) | strand each -- those of walk w are steps[first_step : first_step + steps]. A walk
+    spells query bases [q_start, q_end) as bases [path_start, path_end) of its path, the steps as oriented glued with k - 1
+    overlapping bases, path_len bases long. The result holds the library's handle until close() (or its collection): gaf() formats
+    from it."""
+
+    k: int
+    offsets: np.ndarray
+    kmers: np.ndarray
+    valid: np.ndarray
+    found: np.ndarray
+    walks: np.ndarray
+    steps: np.ndarray
+    _handle: list = None  # [the mtg_kmer_walks handle or None]
+
+    def close(self) -> None:
+        if self._handle and self._handle[0]:
+            _lib.load().mtg_kmer_walks_free(self._handle[0])
+            self._handle[0] = None
+
+    __del__ = close
+
+    def gaf(self, query_names, segment_names=None, query_lengths=None) -> bytes:
+        """The walks as GAF text, one line per walk (mtg_kmer_walks_gaf; made by the library, no Python loop over walks or steps).
+        query_names / segment_names: one name per query record / per index record (list of str, UnitigStore, or (uint8 array,
+        offsets)); segment_names=None names index record u by its decimal number, as --unitigs-gfa-out does. query_lengths: default
+        the lengths of the threaded records."""
+        if not self._handle or not self._handle[0]:
+            raise ValueError("the result is closed")
+        L = _lib.load()
+        qd, qo, qn, keep_q = _sequence_arrays(query_names)
+        if qn != len(self.kmers):
+            raise ValueError(f"{qn} query names for {len(self.kmers)} records")
+        lengths = np.ascontiguousarray(np.diff(self.offsets) if query_lengths is None else query_lengths, np.uint64)
+        if len(lengths) != qn:
+            raise ValueError(f"{len(lengths)} query lengths for {qn} records")
+        sd, so, sn, keep_s = (None, None, 0, None) if segment_names is None else _sequence_arrays(segment_names)
+        if segment_names is not None and sd is None:
+            sd = b""  # (names of no bytes are names all the same)
+        if segment_names is not None and len(self.steps) and int(self.steps.max() >> np.uint64(1)) >= sn:
+            raise ValueError(f"{sn} segment names, but a step on segment {int(self.steps.max() >> np.uint64(1))}")
+        text = C.c_void_p()
+        n = int(L.mtg_kmer_walks_gaf(self._handle[0], qn, qd, qo, _ptr(lengths), sn, sd, so, C.byref(text)))
+        try:
+            return C.string_at(text, n)
+        finally:
+            L.mtg_free(text)
+            del keep_q, keep_s
+
+
+def _take_walks_result(L, h, k, off, kmers, valid, found) -> KmerThreadResult:
+    """The walks of a mtg_kmer_walks handle as arrays of their own; the result keeps the handle for gaf()."""
+    count, n_steps = int(L.mtg_kmer_walks_count(h)), int(L.mtg_kmer_walks_steps_count(h))
+    walks, steps = np.zeros(count, KMER_WALK_DTYPE), np.zeros(n_steps, np.uint64)
+    if count:
+        ptrs = (C.c_void_p * 9)()
+        L.mtg_kmer_walks_arrays(h, ptrs)
+        for name, p in zip(KMER_WALK_DTYPE.names, ptrs):
+            walks[name] = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint64)), shape=(count,))
+        steps[:] = np.ctypeslib.as_array(C.cast(L.mtg_kmer_walks_steps(h), C.POINTER(C.c_uint64)), shape=(n_steps,))
+    return KmerThreadResult(k, off, kmers, valid, found, walks, steps, [h])
+
+
+def _thread(index, call: str, seqs_or_store, min_kmers: int) -> KmerThreadResult:
+    """KmerIndex.thread and TigIndex.thread."""
+    if int(min_kmers) < 0:
+        raise ValueError("min_kmers must be >= 0")
+    d, o, n, keep, off, kmers, valid, found = index._probe_inputs(seqs_or_store, index.locating, "thread() needs an index built with locate=True")
+    h = C.c_void_p()
+    getattr(index._L, call)(index._h, d, o, n, int(min_kmers), _ptr(kmers), _ptr(valid), _ptr(found), C.byref(h))
+    del keep
+    return _take_walks_result(index._L, h, index.info.k, off, kmers, valid, found)
+
+
 def _payload_arrays(seqs_or_store, k: int, weights, colors, n_colors):
     """The per-window payloads of an index as the library takes them (KmerIndex, TigIndex): weights as a uint32 array, colors as a
     uint64 array, None for one not given; ValueError unless each holds one entry per window, n_colors is in 1..64 and no mask has
@@ -1712,6 +1793,13 @@ class KmerIndex:
         self._L.mtg_kmer_index_locate(self._h, d, o, n, _ptr(kmers), _ptr(valid), _ptr(found), C.byref(h))
         del keep
         return KmerLocateResult(self.info.k, off, kmers, valid, found, _take_runs(self._L, h))
+
+    def thread(self, seqs_or_store, min_kmers: int = 1) -> KmerThreadResult:
+        """query()'s counts per record plus the walks of the records through the indexed sequences (KmerThreadResult):
+        the runs of locate() joined wherever one leaves an index record at its end and the next enters another at its start. Over
+        unitigs every walk is a path of the unitig graph. Walks of fewer than min_kmers k-mers are dropped on the device. Needs an
+        index built with locate=True."""
+        return _thread(self, "mtg_kmer_index_thread", seqs_or_store, min_kmers)
 
     def abundance(self, seqs_or_store, per_window: bool = False) -> KmerAbundanceResult:
         """query()'s counts per record plus the sum, the smallest and the largest weight over the record's found windows
@@ -2074,6 +2162,11 @@ class TigIndex:
         return KmerLocateResult(self.info.k, off, kmers, valid, found, _take_runs(self._L, h))
 
     _probe_inputs = KmerIndex._probe_inputs  # (the same checks in the same order: closed first, then the missing payload)
+
+    def thread(self, seqs_or_store, min_kmers: int = 1) -> KmerThreadResult:
+        """KmerIndex.thread's answer, field for field, for every m and bucket_limit. Needs an index built with
+        locate=True."""
+        return _thread(self, "mtg_tig_index_thread", seqs_or_store, min_kmers)
 
     def abundance(self, seqs_or_store, per_window: bool = False) -> KmerAbundanceResult:
         """KmerIndex.abundance's answer: query()'s counts per record plus the sum, the smallest and the largest weight
@@ -2459,6 +2552,15 @@ def last_tig_locate_times() -> dict:
     out = (C.c_double * 4)()
     _lib.load().mtg_last_tig_locate_times(out)
     return dict(zip(("upload_ms", "pack_ms", "probe_ms", "runs_ms"), list(out)))
+
+
+def last_kmer_thread_times(tig: bool = False) -> dict:
+    """Phases of the last KmerIndex.thread (tig=True: TigIndex.thread) on this thread, in ms (HIP events around the kernels; the upload
+    by the host clock): probe and runs as locate() reports them, walks = the walk stage (flag, scans, emit, compaction)."""
+    out = (C.c_double * 5)()
+    L = _lib.load()
+    (L.mtg_last_tig_thread_times if tig else L.mtg_last_kmer_thread_times)(out)
+    return dict(zip(("upload_ms", "pack_ms", "probe_ms", "runs_ms", "walks_ms"), list(out)))
 
 
 def last_tig_index_times() -> dict:

@@ -203,6 +203,19 @@ struct KmerLocateTimes {
 };
 void device_kmer_index_locate(const KmerIndex *ix, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid,
                               uint64_t *found, KmerRuns *runs, KmerLocateTimes *times);
+// The walks of a query through the records of a locating index (kmer_walks_device.hpp; include/mtg_engine.h states the
+// rule), those with at least min_kmers windows, in ascending query position. fields: nine arrays of n words -- q_record, q_start, q_end,
+// kmers, steps, first_step, path_len, path_start, path_end --, steps: (t_record << 1) | strand per step, walk after walk. times: as
+// KmerLocateTimes, plus the walk stage (flag, scans, emit, compaction).
+struct KmerWalks {
+    uint64_t n = 0;
+    std::vector<uint64_t> fields, steps;
+};
+struct KmerThreadTimes {
+    double upload_ms = 0, pack_ms = 0, probe_ms = 0, runs_ms = 0, walks_ms = 0;
+};
+void device_kmer_index_thread(const KmerIndex *ix, const char *seq, const uint64_t *off, uint64_t n, uint64_t min_kmers, uint64_t *kmers,
+                              uint64_t *valid, uint64_t *found, KmerWalks *walks, KmerThreadTimes *times);
 // The query plus, per record over its found windows, the sum, the smallest and the largest weight of their classes (all 0 where
 // nothing is found) and, if per_window is given ([off[n]]), the weight at every found window's global start position, 0 elsewhere.
 // times: host wall clock of the upload and the download, HIP-event time of the kernels.
@@ -266,6 +279,8 @@ void device_tig_index_info(const TigIndex *ix, mtg_tig_index_info *out);
 bool device_tig_index_is_locating(const TigIndex *ix);
 void device_tig_index_locate(const TigIndex *ix, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid,
                              uint64_t *found, KmerRuns *runs, KmerLocateTimes *times);
+void device_tig_index_thread(const TigIndex *ix, const char *seq, const uint64_t *off, uint64_t n, uint64_t min_kmers, uint64_t *kmers,
+                             uint64_t *valid, uint64_t *found, KmerWalks *walks, KmerThreadTimes *times);  // device_kmer_index_thread's contract
 void device_tig_index_query(const TigIndex *ix, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid,
                             uint64_t *found, uint64_t *present_bits, uint64_t *valid_bits, TigIndexTimes *times);
 // payloads by position (tig_payload_device.hpp): a locating index that also keeps one weight and / or one colour mask

@@ -929,6 +929,125 @@ void mtg_last_tig_locate_times(double out[4]) {
     const KmerLocateTimes &t = g_last_tig_locate;
     out[0] = t.upload_ms; out[1] = t.pack_ms; out[2] = t.probe_ms; out[3] = t.runs_ms;
 }
+// ---- ... and which path through the indexed records a query takes: walks, and their GAF text ----
+struct mtg_kmer_walks { KmerWalks w; };
+static thread_local KmerThreadTimes g_last_kmer_thread, g_last_tig_thread;
+void mtg_kmer_index_thread(const mtg_kmer_index *ix, const char *seq, const uint64_t *off, uint64_t n, uint64_t min_kmers, uint64_t *kmers,
+                           uint64_t *valid, uint64_t *found, mtg_kmer_walks **out) {
+    if (!ix || !out) MTG_DIE("mtg_kmer_index_thread: null argument");
+    std::unique_ptr<mtg_kmer_walks> walks(new mtg_kmer_walks());
+    device_kmer_index_thread(ix->ix, seq, off, n, min_kmers, kmers, valid, found, &walks->w, &g_last_kmer_thread);
+    *out = walks.release();
+}
+void mtg_tig_index_thread(const mtg_tig_index *ix, const char *seq, const uint64_t *off, uint64_t n, uint64_t min_kmers, uint64_t *kmers,
+                          uint64_t *valid, uint64_t *found, mtg_kmer_walks **out) {
+    if (!ix || !out) MTG_DIE("mtg_tig_index_thread: null argument");
+    std::unique_ptr<mtg_kmer_walks> walks(new mtg_kmer_walks());
+    device_tig_index_thread(ix->ix, seq, off, n, min_kmers, kmers, valid, found, &walks->w, &g_last_tig_thread);
+    *out = walks.release();
+}
+uint64_t mtg_kmer_walks_count(const mtg_kmer_walks *walks) {
+    if (!walks) MTG_DIE("mtg_kmer_walks_count: null argument");
+    return walks->w.n;
+}
+uint64_t mtg_kmer_walks_steps_count(const mtg_kmer_walks *walks) {
+    if (!walks) MTG_DIE("mtg_kmer_walks_steps_count: null argument");
+    return walks->w.steps.size();
+}
+void mtg_kmer_walks_arrays(const mtg_kmer_walks *walks, const uint64_t *fields[9]) {
+    if (!walks || !fields) MTG_DIE("mtg_kmer_walks_arrays: null argument");
+    for (int f = 0; f < 9; f++) fields[f] = walks->w.fields.data() + (uint64_t)f * walks->w.n;
+}
+const uint64_t *mtg_kmer_walks_steps(const mtg_kmer_walks *walks) {
+    if (!walks) MTG_DIE("mtg_kmer_walks_steps: null argument");
+    return walks->w.steps.data();
+}
+void mtg_kmer_walks_free(mtg_kmer_walks *walks) { delete walks; }
+static void thread_times_out(const KmerThreadTimes &t, double out[5]) {
+    out[0] = t.upload_ms; out[1] = t.pack_ms; out[2] = t.probe_ms; out[3] = t.runs_ms; out[4] = t.walks_ms;
+}
+void mtg_last_kmer_thread_times(double out[5]) { thread_times_out(g_last_kmer_thread, out); }
+void mtg_last_tig_thread_times(double out[5]) { thread_times_out(g_last_tig_thread, out); }
+// The GAF text is made on the host: a line is names and decimal numbers, a few dozen bytes per step, and the walks are on the host
+// already. Two passes over ranges of walks on the host's threads -- the bytes of every line, then the lines at their offsets.
+namespace {
+struct GafNames {
+    const char *text;
+    const uint64_t *off;
+    uint64_t n;
+};
+inline size_t put_u64(char *p, uint64_t v) {
+    char tmp[20];
+    size_t n = 0;
+    do tmp[n++] = (char)('0' + v % 10); while (v /= 10);
+    for (size_t i = 0; i < n; i++) p[i] = tmp[n - 1 - i];
+    return n;
+}
+inline size_t digits(uint64_t v) {
+    size_t n = 1;
+    while (v >= 10) { v /= 10; n++; }
+    return n;
+}
+// one line, written at p if p is given; returns its bytes
+size_t gaf_line(const KmerWalks &w, uint64_t i, const GafNames &q, const uint64_t *q_len, const GafNames &s, char *p) {
+    const uint64_t n = w.n, *f = w.fields.data();
+    const uint64_t qr = f[i], qs = f[n + i], qe = f[2 * n + i], kmers = f[3 * n + i], steps = f[4 * n + i], s0 = f[5 * n + i];
+    const uint64_t nums[] = {q_len[qr], qs, qe};
+    const uint64_t tail[] = {f[6 * n + i], f[7 * n + i], f[8 * n + i], qe - qs, qe - qs};
+    size_t b = 0;
+    auto text = [&](const char *t, size_t len) { if (p) memcpy(p + b, t, len); b += len; };
+    auto num = [&](uint64_t v) { b += p ? put_u64(p + b, v) : digits(v); };
+    auto chr = [&](char c) { if (p) p[b] = c; b++; };
+    text(q.text + q.off[qr], q.off[qr + 1] - q.off[qr]);
+    for (uint64_t v : nums) { chr('\t'); num(v); }
+    text("\t+\t", 3);
+    for (uint64_t j = 0; j < steps; j++) {
+        const uint64_t st = w.steps[s0 + j], u = st >> 1;
+        chr((st & 1) ? '<' : '>');
+        if (s.text) text(s.text + s.off[u], s.off[u + 1] - s.off[u]);
+        else num(u);
+    }
+    for (uint64_t v : tail) { chr('\t'); num(v); }
+    text("\t255\tcg:Z:", 10);
+    num(qe - qs);
+    text("=\tkm:i:", 7);
+    num(kmers);
+    chr('\n');
+    return b;
+}
+}  // namespace
+uint64_t mtg_kmer_walks_gaf(const mtg_kmer_walks *walks, uint64_t n_queries, const char *query_names, const uint64_t *query_name_off,
+                            const uint64_t *query_len, uint64_t n_segments, const char *segment_names, const uint64_t *segment_name_off,
+                            char **text_out) {
+    const char *fn = "mtg_kmer_walks_gaf";
+    if (!walks || !text_out || (n_queries && (!query_name_off || !query_len)) || (segment_names && !segment_name_off)) MTG_DIE("%s: null argument", fn);
+    const KmerWalks &w = walks->w;
+    const uint64_t n = w.n;
+    for (uint64_t i = 0; i < n; i++)
+        if (w.fields[i] >= n_queries) MTG_DIE("%s: walk %llu is of query record %llu; %llu names", fn, (unsigned long long)i, (unsigned long long)w.fields[i], (unsigned long long)n_queries);
+    if (segment_names)
+        for (uint64_t st : w.steps)
+            if ((st >> 1) >= n_segments) MTG_DIE("%s: a step on segment %llu; %llu names", fn, (unsigned long long)(st >> 1), (unsigned long long)n_segments);
+    const GafNames q{query_names ? query_names : "", query_name_off, n_queries}, s{segment_names, segment_name_off, n_segments};
+    constexpr uint64_t CHUNK = 4096;  // walks per task
+    const uint64_t chunks = (n + CHUNK - 1) / CHUNK;
+    std::vector<uint64_t> at(chunks + 1, 0);
+    parallel_tasks(chunks, [&](uint64_t c) {
+        uint64_t b = 0;
+        for (uint64_t i = c * CHUNK; i < std::min(n, (c + 1) * CHUNK); i++) b += gaf_line(w, i, q, query_len, s, nullptr);
+        at[c + 1] = b;
+    });
+    for (uint64_t c = 0; c < chunks; c++) at[c + 1] += at[c];
+    char *text = (char *)malloc(at[chunks] + 1);
+    if (!text) MTG_DIE("%s: out of memory (%llu bytes)", fn, (unsigned long long)at[chunks]);
+    parallel_tasks(chunks, [&](uint64_t c) {
+        char *p = text + at[c];
+        for (uint64_t i = c * CHUNK; i < std::min(n, (c + 1) * CHUNK); i++) p += gaf_line(w, i, q, query_len, s, p);
+    });
+    text[at[chunks]] = 0;
+    *text_out = text;
+    return at[chunks];
+}
 // ---- ... and how heavy they are and which inputs carry them: payloads by position ----
 static thread_local TigPayloadTimes g_last_tig_payload;
 mtg_tig_index *mtg_tig_index_build_annotated(const char *seq, const uint64_t *off, uint64_t n, uint64_t k, uint64_t m, uint64_t bucket_limit,

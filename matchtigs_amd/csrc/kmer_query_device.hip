@@ -48,6 +48,11 @@
 //             writes the fields of each
 // Only the runs and the counts are downloaded. A call takes 8 + 4 + 8 B per query base beside the query's store.
 //
+// Thread (a LOCATING index only). The same pack, probe and runs, the runs left on the device (kr::RunStage), then
+//   walks     (kmer_walks_device.hpp, shared with the sparse index) the runs joined across record ends into walks, those of at least
+//             min_kmers windows compacted with their steps
+// Only the kept walks, their steps and the counts are downloaded.
+//
 // Abundance (a WEIGHTED index only, mtg_kmer_index_build_weighted). The caller gives one uint32 per window of the indexed
 // sequences, in window order; weight(class) = the weight of the class's smallest window start, loc of DESIGN.md 18 -- a function of
 // the input alone. The build runs the locating insert and then weight_gather_kernel, one sweep over the slots: weight[s] =
@@ -100,6 +105,7 @@
 #include "hip_util.hpp"
 #include "kmer_correct_device.hpp"
 #include "kmer_runs_device.hpp"
+#include "kmer_walks_device.hpp"
 #include "kmer_window_device.hpp"
 #include "pack_device.hpp"
 #include "pseudoalign_device.hpp"
@@ -919,6 +925,20 @@ void device_kmer_tally_coverage(const KmerTally *t, const char *seq, const uint6
     }
 }
 
+namespace {
+// the probe of locate and thread, between the marks 0 and 1 of p.ev: d_hit[n_bases] = NO_HIT, then the hits of the found windows
+template <int EVENTS>
+void queue_locate_probe(Probe<EVENTS> &p, const KmerIndex *ix, unsigned long long *d_hit) {
+    const uint64_t n_bases = p.store.n_bases;
+    p.start();
+    HIP_CHECK(hipMemsetAsync(d_hit, 0xFF, n_bases * 8, p.st));
+    if (p.wide) locate_kernel<true><<<p.run_grid(), hu::EB, 0, p.st>>>(p.a, p.store.bad, n_bases, p.n, p.d_counts, ix->where, d_hit);
+    else locate_kernel<false><<<p.run_grid(), hu::EB, 0, p.st>>>(p.a, p.store.bad, n_bases, p.n, p.d_counts, ix->where, d_hit);
+    HIP_CHECK(hipGetLastError());
+    p.ev.mark(1, p.st);
+}
+}  // namespace
+
 void device_kmer_index_locate(const KmerIndex *ix, const char *seq, const uint64_t *off, uint64_t n, uint64_t *kmers, uint64_t *valid,
                               uint64_t *found, KmerRuns *runs, KmerLocateTimes *times) {
     if (!ix->locating) MTG_DIE("mtg_kmer_index_locate: the index keeps no positions (build it with mtg_kmer_index_build_locating)");
@@ -930,12 +950,7 @@ void device_kmer_index_locate(const KmerIndex *ix, const char *seq, const uint64
     Probe<3> p(ix, seq, off, n, 2);
     hipStream_t st = p.st;
     hu::DeviceArray<unsigned long long> d_hit(n_bases);
-    p.start();
-    HIP_CHECK(hipMemsetAsync(d_hit, 0xFF, n_bases * 8, st));
-    if (p.wide) locate_kernel<true><<<p.run_grid(), hu::EB, 0, st>>>(p.a, p.store.bad, n_bases, n, p.d_counts, ix->where, d_hit);
-    else locate_kernel<false><<<p.run_grid(), hu::EB, 0, st>>>(p.a, p.store.bad, n_bases, n, p.d_counts, ix->where, d_hit);
-    HIP_CHECK(hipGetLastError());
-    p.ev.mark(1, st);
+    queue_locate_probe(p, ix, d_hit);
     const kr::RunArgs ra{d_hit, p.store.off, ix->off, n_bases, n, ix->info.records, k};
     kr::runs_from_hits(ra, st, p.device_id, runs, [&](hipStream_t) {
         p.ev.mark(2, st);
@@ -944,6 +959,34 @@ void device_kmer_index_locate(const KmerIndex *ix, const char *seq, const uint64
     if (times) {
         p.booked(&times->upload_ms, &times->pack_ms, &times->probe_ms);
         times->runs_ms = p.ev.ms(1, 2);
+    }
+}
+
+// ---- thread: locate's probe and run stage, then the walks from the runs where they are (kmer_walks_device.hpp) ----
+void device_kmer_index_thread(const KmerIndex *ix, const char *seq, const uint64_t *off, uint64_t n, uint64_t min_kmers, uint64_t *kmers,
+                              uint64_t *valid, uint64_t *found, KmerWalks *walks, KmerThreadTimes *times) {
+    if (!ix->locating) MTG_DIE("mtg_kmer_index_thread: the index keeps no positions (build it with mtg_kmer_index_build_locating)");
+    const uint64_t k = ix->info.k;
+    const uint64_t n_bases = probe_windows("mtg_kmer_index_thread", k, seq, off, n, kmers, valid, found, !walks);
+    *walks = KmerWalks();
+    if (times) *times = KmerThreadTimes();
+    if (n_bases == 0) return;  // nothing to look at
+    Probe<4> p(ix, seq, off, n, 2);
+    hipStream_t st = p.st;
+    hu::DeviceArray<unsigned long long> d_hit(n_bases);
+    queue_locate_probe(p, ix, d_hit);
+    const kr::RunArgs ra{d_hit, p.store.off, ix->off, n_bases, n, ix->info.records, k};
+    kr::RunStage stage(n_bases);
+    stage.queue(ra, st);
+    p.ev.mark(2, st);
+    kwk::walks_from_runs(stage, ix->off, k, min_kmers, st, p.device_id, walks, [&](hipStream_t) {
+        p.ev.mark(3, st);
+        p.download_counts(valid, found);
+    });
+    if (times) {
+        p.booked(&times->upload_ms, &times->pack_ms, &times->probe_ms);
+        times->runs_ms = p.ev.ms(1, 2);
+        times->walks_ms = p.ev.ms(2, 3);
     }
 }
 

@@ -8,7 +8,7 @@
 //   scan   hu::scan_u32 ranks them
 //   mark   run_mark_kernel notes the first and last position of every run
 //   emit   run_emit_kernel writes the fields of each
-// and a sliced download of the runs alone. A call takes 4 + 8 B per query base beside the hits. The kernels are static: every
+// (RunStage, whose arrays the walk stage of kmer_walks_device.hpp reads where they are) and a sliced download of the runs alone. A call takes 4 + 8 B per query base beside the hits. The kernels are static: every
 // translation unit that includes this compiles its own.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -106,43 +106,57 @@ static __global__ __launch_bounds__(hu::EB) void run_emit_kernel(RunArgs a, uint
     strand[i] = (unsigned char)(hs & 1);
 }
 
+// The run stage's device arrays, which own themselves. queue() leaves the runs of ra.hit (filled on st) on the device -- out(): five
+// arrays of n_runs words, strand(): [n_runs] -- for whoever works on from them there (kmer_walks_device.hpp); download() brings them to
+// the host once the stream has been waited for.
+struct RunStage {
+    uint64_t n_runs = 0;
+    hu::DeviceArray<uint32_t> d_starts;
+    hu::DeviceArray<unsigned long long> d_rank;
+    hu::ScanScratch<unsigned long long> scan;
+    hu::DeviceArray<unsigned long long> d_ends;  // first then last position of every run
+    hu::DeviceArray<unsigned char> d_out_bytes;  // five 64-bit fields per run, then the strands
+
+    explicit RunStage(uint64_t n_bases) : d_starts(n_bases), d_rank(n_bases), scan(n_bases) {}
+    unsigned long long *out() const { return reinterpret_cast<unsigned long long *>(d_out_bytes.get()); }
+    unsigned char *strand() const { return d_out_bytes.get() + 5 * n_runs * 8; }
+    void queue(const RunArgs &ra, hipStream_t st) {
+        const uint64_t n_bases = ra.n_bases;
+        const unsigned base_grid = hu::grid_for(n_bases);
+        run_flag_kernel<<<base_grid, hu::EB, 0, st>>>(ra, d_starts);
+        HIP_CHECK(hipGetLastError());
+        scan.scan(st, d_starts, n_bases, d_rank);
+        HIP_CHECK(hipMemcpyAsync(&n_runs, scan.total(), 8, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        if (n_runs) {
+            d_ends.alloc(2 * n_runs);
+            d_out_bytes.alloc(5 * n_runs * 8 + n_runs);
+            run_mark_kernel<<<base_grid, hu::EB, 0, st>>>(ra, d_starts, d_rank, n_runs, d_ends, d_ends + n_runs);
+            run_emit_kernel<<<hu::grid_for(n_runs), hu::EB, 0, st>>>(ra, n_runs, d_ends, d_ends + n_runs, out(), strand());
+            HIP_CHECK(hipGetLastError());
+        }
+    }
+    void download(hipStream_t st, int device_id, KmerRuns *runs) const {
+        if (!n_runs) return;
+        std::vector<uint64_t> *fields[5] = {&runs->q_record, &runs->q_start, &runs->kmers, &runs->t_record, &runs->t_start};
+        for (int f = 0; f < 5; f++) {
+            fields[f]->resize(n_runs);
+            hu::download_sliced(fields[f]->data(), out() + f * n_runs, n_runs * 8, st, device_id);
+        }
+        runs->strand.resize(n_runs);
+        hu::download_sliced(runs->strand.data(), strand(), n_runs, st, device_id);
+    }
+};
+
 // The runs of ra.hit (filled on st) into *runs, in ascending query position. done(st) is called once the kernels are queued, before
 // the stream is waited for: the caller's event mark and the downloads it wants in the same wait.
 template <typename Done>
 inline void runs_from_hits(const RunArgs &ra, hipStream_t st, int device_id, KmerRuns *runs, Done done) {
-    const uint64_t n_bases = ra.n_bases;
-    hu::DeviceArray<uint32_t> d_starts(n_bases);
-    hu::DeviceArray<unsigned long long> d_rank(n_bases);
-    hu::ScanScratch<unsigned long long> scan(n_bases);
-    const unsigned base_grid = hu::grid_for(n_bases);
-    run_flag_kernel<<<base_grid, hu::EB, 0, st>>>(ra, d_starts);
-    HIP_CHECK(hipGetLastError());
-    scan.scan(st, d_starts, n_bases, d_rank);
-    uint64_t n_runs = 0;
-    HIP_CHECK(hipMemcpyAsync(&n_runs, scan.total(), 8, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    hu::DeviceArray<unsigned long long> d_ends;  // first then last position of every run
-    hu::DeviceArray<unsigned char> d_out_bytes;  // five 64-bit fields per run, then the strands
-    unsigned long long *d_out = nullptr;
-    if (n_runs) {
-        d_ends.alloc(2 * n_runs);
-        d_out = reinterpret_cast<unsigned long long *>(d_out_bytes.alloc(5 * n_runs * 8 + n_runs));
-        unsigned char *d_strand = d_out_bytes + 5 * n_runs * 8;
-        run_mark_kernel<<<base_grid, hu::EB, 0, st>>>(ra, d_starts, d_rank, n_runs, d_ends, d_ends + n_runs);
-        run_emit_kernel<<<hu::grid_for(n_runs), hu::EB, 0, st>>>(ra, n_runs, d_ends, d_ends + n_runs, d_out, d_strand);
-        HIP_CHECK(hipGetLastError());
-    }
+    RunStage stage(ra.n_bases);
+    stage.queue(ra, st);
     done(st);
     HIP_CHECK(hipStreamSynchronize(st));
-    if (n_runs) {
-        std::vector<uint64_t> *fields[5] = {&runs->q_record, &runs->q_start, &runs->kmers, &runs->t_record, &runs->t_start};
-        for (int f = 0; f < 5; f++) {
-            fields[f]->resize(n_runs);
-            hu::download_sliced(fields[f]->data(), d_out + f * n_runs, n_runs * 8, st, device_id);
-        }
-        runs->strand.resize(n_runs);
-        hu::download_sliced(runs->strand.data(), d_out + 5 * n_runs, n_runs, st, device_id);
-    }
+    stage.download(st, device_id, runs);
 }
 
 }  // namespace kr

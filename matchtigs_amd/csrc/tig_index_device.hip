@@ -35,7 +35,8 @@
 // of the heavy table (atomicMin behind the inserting heavy_kernel's find_slot); nothing more where no bucket is heavy. tig_locate_kernel
 // is tig_query_kernel's walk without the bit arrays; per found window hit[q] = (t << 1) | strand, t = tig_where -- the MINIMUM over all
 // candidates of the bucket that pass, or heavy_where[slot] -- and strand from one forward compare at t. From the hits to the runs:
-// kmer_runs_device.hpp, shared with the table index.
+// kmer_runs_device.hpp, shared with the table index. Thread: the same, the runs left on the device and joined into
+// walks there (kmer_walks_device.hpp, shared with the table index too).
 //
 // Payloads (mtg_tig_index_build_annotated): a locating index that also keeps win_off[records + 1] and one weight and / or
 // one colour mask per window of the text, dense or as runs (tig_payload_device.hpp). t above is the position whose payload the table
@@ -71,6 +72,7 @@
 #include "device.hpp"
 #include "hip_util.hpp"
 #include "kmer_runs_device.hpp"
+#include "kmer_walks_device.hpp"
 #include "kmer_window_device.hpp"
 #include "pack_device.hpp"
 #include "pseudoalign_device.hpp"
@@ -726,6 +728,37 @@ void device_tig_index_locate(const TigIndex *ix, const char *seq, const uint64_t
         times->pack_ms = p.store.pack_ms;
         times->probe_ms = p.ev.ms(0, 1);
         times->runs_ms = p.ev.ms(1, 2);
+    }
+}
+
+// ---- thread: the same probe and run stage, then the walks from the runs where they are (kmer_walks_device.hpp) ----
+void device_tig_index_thread(const TigIndex *ix, const char *seq, const uint64_t *off, uint64_t n, uint64_t min_kmers, uint64_t *kmers,
+                             uint64_t *valid, uint64_t *found, KmerWalks *walks, KmerThreadTimes *times) {
+    const char *fn = "mtg_tig_index_thread";
+    if (!ix->locating) MTG_DIE("%s: the index keeps no positions of its heavy buckets (build it with mtg_tig_index_build_locating)", fn);
+    const uint64_t n_bases = locate_windows(fn, ix, seq, off, n, kmers, valid, found, !walks);
+    *walks = KmerWalks();
+    if (times) *times = KmerThreadTimes();
+    if (n_bases == 0) return;  // nothing to look at
+    LocateProbe p(ix, seq, off, n);
+    PhaseEvents<1> walked;
+    const kr::RunArgs ra{p.d_hit, p.store.off, ix->off, n_bases, n, ix->info.records, ix->info.k};
+    kr::RunStage stage(n_bases);
+    stage.queue(ra, p.st);
+    p.ev.mark(2, p.st);
+    kwk::walks_from_runs(stage, ix->off, ix->info.k, min_kmers, p.st, ix->device_id, walks, [&](hipStream_t) {
+        walked.mark(0, p.st);
+        p.download_counts(valid, found);
+    });
+    if (times) {
+        times->upload_ms = p.store.upload_ms;
+        times->pack_ms = p.store.pack_ms;
+        times->probe_ms = p.ev.ms(0, 1);
+        times->runs_ms = p.ev.ms(1, 2);
+        float f = 0.f;
+        HIP_CHECK(hipEventSynchronize(walked.ev[0]));
+        HIP_CHECK(hipEventElapsedTime(&f, p.ev.ev[2], walked.ev[0]));
+        times->walks_ms = f;
     }
 }
 
