@@ -1124,6 +1124,64 @@ void mtg_compact_unitigs_simplified_store(const mtg_unitigs *in, uint64_t k, uin
 /* Of the last compaction on this thread: {ms of the list, sums, choose and verdict kernels over all rounds (HIP events; 0 where
  * nothing was to be popped)}. mtg_last_clean_times leaves them out. */
 void mtg_last_bubble_times(double out[1]);
+/* K-MER SELECTION. mtg_compact_unitigs_selected is mtg_compact_unitigs_simplified over the k-mers of S_m that pass a
+ * selection by their colour sets and against FILTER RECORDS, a second sequence store that is looked up in the k-mer table and never
+ * inserted: a filter window creates, counts and colours nothing. Abundance(x), colors(x), creator(x), reading(x) and S_m are those of
+ * the main records alone. Filter record r has the role filter_roles[r]: 0 = subtract, 1 = intersect; its windows follow the rules of
+ * the main records (either case, either strand, a record shorter than k has no window; the caller cuts the records at whatever is
+ * outside ACGT). sub(x) = the windows of subtract records whose k-mer is x or rc(x) (a palindromic window counts once), int(x) the
+ * same over all intersect records. x in S_m is SELECTED iff it passes, in this order,
+ *   1 forbid     colors(x) & forbid == 0
+ *   2 require    colors(x) & require == require
+ *   3 carriers   min_colors <= popcount(colors(x)) <= max_colors
+ *   4 subtract   sub(x) < subtract_min_abundance     (only where a subtract record is given)
+ *   5 intersect  int(x) >= intersect_min_abundance   (only where an intersect record is given)
+ * and a rejected k-mer is counted under the first rule it fails. The selected set S_sel takes the place of S_m in everything behind
+ * it: nodes, successors (split or not), the cleaning rounds, bubbles, the unitigs, sums, ordered counts, masks and classes; the order
+ * and the orientation of the unitigs follow the creators and readings of the main windows.
+ * *stats, *sums, *kmer_counts, *kmer_colors, *classes, *cleaning and *bubbles describe the output store. *abundance keeps its meaning
+ * (distinct_kept = |S_m|), and so does *color_stats: in a selected call it is taken over S_m, also where the call cleans -- the matrix
+ * and its occupancy row are how a carrier threshold is chosen, as the spectrum is for min_abundance. With forbid = require = 0,
+ * min_colors = 0, max_colors = 64 and no filter record every k-mer is selected and store, sums, counts, masks and classes are those of
+ * the call without a selection, byte for byte. An empty S_sel is a result: the store is empty, the statistics are filled.
+ * selection_params == NULL or selection == NULL selects nothing: the call then runs the kernels of mtg_compact_unitigs_simplified and
+ * nothing else. A selection needs the abundance and sums out-pointers (min_abundance may be 1), and the colours' out-pointers if a
+ * colour rule is set (forbid or require != 0, min_colors > 0 or max_colors < 64). Aborts, by name and before any device call: a bit
+ * of require or forbid at or beyond n_colors, require & forbid != 0, min_colors > max_colors, max_colors > 64, either filter
+ * abundance < 1, a role other than 0 or 1, 2^32 or more filter windows of one role. Exact integers that depend on the inputs and the
+ * parameters alone. */
+typedef struct mtg_selection_params {
+    uint64_t require, forbid;         /* colour masks */
+    uint64_t min_colors, max_colors;  /* bounds on the carriers; 0 and 64 bound nothing */
+    uint64_t subtract_min_abundance;  /* A >= 1: a k-mer goes iff sub(x) >= A */
+    uint64_t intersect_min_abundance; /* B >= 1: a k-mer stays iff int(x) >= B */
+} mtg_selection_params;
+typedef struct mtg_selection {
+    uint64_t input_kmers;                    /* |S_m| */
+    uint64_t rejected_forbid, rejected_require, rejected_carriers, rejected_subtract, rejected_intersect; /* by the first rule failed */
+    uint64_t selected, selected_occurrences; /* |S_sel| and the sum of its abundances: the five counts + selected == input_kmers */
+    uint64_t subtract_windows, intersect_windows; /* the windows of the filter records, by role */
+    uint64_t subtract_hits, intersect_hits;  /* those whose class is in the k-mer table at all (of any abundance) */
+    uint64_t per_color_selected[64];         /* the selected k-mers with bit c (zeros in a call without colours) */
+} mtg_selection;
+void mtg_compact_unitigs_selected(const char *data, const uint64_t *offsets, uint64_t n, uint64_t k, uint64_t min_abundance,
+                                  const uint8_t *record_colors, uint64_t n_colors, int split, const mtg_cleaning_params *params,
+                                  const mtg_bubble_params *bubble_params, const mtg_selection_params *selection_params,
+                                  const char *filter_data, const uint64_t *filter_offsets, const uint8_t *filter_roles, uint64_t filter_n,
+                                  int device_id, mtg_unitigs **out, mtg_compaction *stats, mtg_abundance *abundance, mtg_abundance_sums **sums,
+                                  mtg_kmer_counts **kmer_counts, mtg_kmer_colors **kmer_colors, mtg_color_stats *color_stats,
+                                  mtg_color_classes **classes, mtg_cleaning *cleaning, mtg_bubbles *bubbles, mtg_selection *selection);
+void mtg_compact_unitigs_selected_store(const mtg_unitigs *in, uint64_t k, uint64_t min_abundance, const uint8_t *record_colors,
+                                        uint64_t n_colors, int split, const mtg_cleaning_params *params,
+                                        const mtg_bubble_params *bubble_params, const mtg_selection_params *selection_params,
+                                        const char *filter_data, const uint64_t *filter_offsets, const uint8_t *filter_roles,
+                                        uint64_t filter_n, int device_id, mtg_unitigs **out, mtg_compaction *stats, mtg_abundance *abundance,
+                                        mtg_abundance_sums **sums, mtg_kmer_counts **kmer_counts, mtg_kmer_colors **kmer_colors,
+                                        mtg_color_stats *color_stats, mtg_color_classes **classes, mtg_cleaning *cleaning,
+                                        mtg_bubbles *bubbles, mtg_selection *selection);
+/* Of the last compaction on this thread, in ms by HIP events: {the filter probe kernel, the selection (the keep kernel, the scan and
+ * the move)}; 0 in a call without a selection. mtg_last_compact_times' ids phase leaves the probe out. */
+void mtg_last_select_times(double out[2]);
 /* mtg_read_sequences without an alphabet rule: every byte of a sequence line is kept as it is (`N`, IUPAC codes, lower case), for
  * the queries of a k-mer index. *names_out = the record names as a second store with the same accessors: the header text behind `>`
  * up to the first white space. */

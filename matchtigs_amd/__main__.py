@@ -26,6 +26,10 @@ weights and masks hang off the positions of its text, one per window, dense or a
 strand -- sequencing reads, where a k-mer seen once is mostly an error -- before the unitigs are formed (DESIGN.md 19);
 `--kmer-spectrum-out` writes how many distinct k-mers have each abundance, `--unitig-abundance-out` the summed and mean abundance
 of every unitig.
+`--require-colors LIST`, `--forbid-colors LIST`, `--min-colors N`, `--max-colors N` (with `--seq-in`; not in the reference) select, at
+the same place, the k-mers by the files that carry them (LIST: 0-based file numbers in `--seq-in` order, e.g. 0,2,5-7), and
+`--subtract-fa F` / `--intersect-fa F` against the k-mers of other files, which are looked up on the GPU and never inserted: they add
+no k-mer, count or colour. `--selection-out` says what each rule rejected.
 `--query-abundance-out` (with `--seq-in` and `--query-fa`) reports how often the k-mers of each query record were seen in the input: the
 index is weighted with the abundance of every kept k-mer, and a TSV row per query record gives the k-mers found and the sum, the
 smallest, the largest and the mean of their abundances; `--query-abundance-profile-out` adds one abundance per k-mer of every
@@ -231,6 +235,27 @@ def main(argv=None) -> int:
                          "abundance (L >= 2; k + 1 is the least that pops a SNP, 2 k the usual value; not in the reference)")
     ap.add_argument("--bubble-ratio", type=int, metavar="R",
                     help="with --pop-bubbles: pop an arm only if the best arm has at least R times its mean abundance (1..255, default 1)")
+    ap.add_argument("--require-colors", metavar="LIST",
+                    help="with --seq-in: keep only the k-mers that every file of LIST carries; LIST holds 0-based file numbers in "
+                         "--seq-in order as commas and ranges, e.g. 0,2,5-7 (not in the reference)")
+    ap.add_argument("--forbid-colors", metavar="LIST", help="with --seq-in: drop the k-mers that a file of LIST carries")
+    ap.add_argument("--min-colors", type=int, metavar="N",
+                    help="with --seq-in: keep only the k-mers that at least N files carry (N = the number of files: the core)")
+    ap.add_argument("--max-colors", type=int, metavar="N", help="with --seq-in: keep only the k-mers that at most N files carry (1: the private ones)")
+    ap.add_argument("--subtract-fa", action="append", metavar="PATH",
+                    help="with --seq-in: drop the k-mers that the sequences of this file show (fasta or fastq, optionally .gz; either "
+                         "strand); the file is looked up, never inserted: it adds no k-mer, count or colour; repeatable (not in the reference)")
+    ap.add_argument("--subtract-min-abundance", type=int, metavar="A",
+                    help="with --subtract-fa: drop a k-mer only if the files show it at least A times (default 1)")
+    ap.add_argument("--intersect-fa", action="append", metavar="PATH",
+                    help="with --seq-in: keep only the k-mers that the sequences of these files show; repeatable, all files form one set")
+    ap.add_argument("--intersect-min-abundance", type=int, metavar="B",
+                    help="with --intersect-fa: keep a k-mer only if the files show it at least B times (default 1)")
+    ap.add_argument("--filter-min-base-quality", type=int, metavar="Q",
+                    help="with fastq --subtract-fa / --intersect-fa files: a base whose Phred quality is below Q (0..93) splits a read like an N")
+    ap.add_argument("--selection-out", metavar="PATH",
+                    help="TSV (.gz => gzip): name<TAB>k-mers for input, abundance_kept, the k-mers each selection rule rejected (forbid, "
+                         "require, carriers, subtract, intersect) and selected; then per file color<TAB>file<TAB>k-mers<TAB>selected")
     ap.add_argument("--count-fa", action="append", metavar="PATH",
                     help="reads of one sample (fasta or fastq, optionally .gz; any characters) whose k-mers are counted on the k-mers of "
                          "the input's unitigs on the GPU; repeatable, one sample per file; needs --count-out (not in the reference)")
@@ -344,7 +369,7 @@ def main(argv=None) -> int:
 
     classed = bool(args.monochromatic_unitigs or args.color_classes_out or args.unitig_color_classes_out)
     colored = bool(args.color_matrix_out or args.unitig_colors_out or args.query_colors_out or args.query_index_colors_out or classed
-                   or args.pseudoalign_fa or args.index_colors)
+                   or args.pseudoalign_fa or args.index_colors or _selects_by_color(args))
     if colored and args.seq_in is not None and len(args.seq_in) > MAX_COLORS:
         ap.error(f"{len(args.seq_in)} --seq-in files: at most {MAX_COLORS} files can be told apart as colours")
 
@@ -458,9 +483,10 @@ def main(argv=None) -> int:
                         ("--monochromatic-unitigs", args.monochromatic_unitigs or None), ("--color-classes-out", args.color_classes_out),
                         ("--unitig-color-classes-out", args.unitig_color_classes_out), ("--clip-tips", args.clip_tips),
                         ("--remove-isolated", args.remove_isolated), ("--clean-rounds", args.clean_rounds),
-                        ("--pop-bubbles", args.pop_bubbles), ("--bubble-ratio", args.bubble_ratio)):
+                        ("--pop-bubbles", args.pop_bubbles), ("--bubble-ratio", args.bubble_ratio)) + _SELECTION_FLAGS(args):
         if value is not None and args.seq_in is None:
             ap.error(f"{flag} needs --seq-in")
+    _check_selection(ap, args)
     if args.clip_tips is not None and args.clip_tips < 2:
         ap.error("--clip-tips must be >= 2")
     if args.remove_isolated is not None and args.remove_isolated < 1:
@@ -485,15 +511,17 @@ def main(argv=None) -> int:
         for flag, value in (("--color-matrix-out", args.color_matrix_out), ("--unitig-colors-out", args.unitig_colors_out),
                             ("--query-colors-out", args.query_colors_out), ("--query-index-colors-out", args.query_index_colors_out),
                             ("--monochromatic-unitigs", args.monochromatic_unitigs or None), ("--color-classes-out", args.color_classes_out), ("--unitig-color-classes-out", args.unitig_color_classes_out),
-                            ("--pseudoalign-fa", args.pseudoalign_fa)):
+                            ("--pseudoalign-fa", args.pseudoalign_fa), ("--require-colors", args.require_colors),
+                            ("--forbid-colors", args.forbid_colors), ("--min-colors", args.min_colors), ("--max-colors", args.max_colors)):
             if value is not None:
                 ap.error(f"--min-component-kmers cannot be combined with {flag}")
     for flag, value in (("--min-base-quality", args.min_base_quality), ("--query-min-base-quality", args.query_min_base_quality),
                         ("--count-min-base-quality", args.count_min_base_quality),
-                        ("--pseudoalign-min-base-quality", args.pseudoalign_min_base_quality)):
+                        ("--pseudoalign-min-base-quality", args.pseudoalign_min_base_quality),
+                        ("--filter-min-base-quality", args.filter_min_base_quality)):
         if value is not None and not 0 <= value <= 93:
             ap.error(f"{flag} must be in 0..93")
-    if not (args.color_classes_out or args.unitig_color_classes_out or args.color_matrix_out or args.unitig_colors_out or args.kmer_spectrum_out or args.unitig_abundance_out or args.unitig_kmer_abundance_out or args.query_fa or args.count_fa or args.pseudoalign_fa or args.correct_fa or args.thread_fa or args.greedytigs_fa_out or args.eulertigs_fa_out or args.greedytigs_gfa_out or args.eulertigs_gfa_out
+    if not (args.selection_out or args.color_classes_out or args.unitig_color_classes_out or args.color_matrix_out or args.unitig_colors_out or args.kmer_spectrum_out or args.unitig_abundance_out or args.unitig_kmer_abundance_out or args.query_fa or args.count_fa or args.pseudoalign_fa or args.correct_fa or args.thread_fa or args.greedytigs_fa_out or args.eulertigs_fa_out or args.greedytigs_gfa_out or args.eulertigs_gfa_out
             or args.greedytigs_duplication_bitvector_out or args.matchtigs_fa_out or args.matchtigs_gfa_out or args.verify_fa or args.unitigs_fa_out
             or args.unitigs_bcalm_out or args.unitigs_gfa_out or args.components_out or args.unitig_components_out or args.index_out):
         ap.error("nothing to do: give --greedytigs-fa-out / --greedytigs-gfa-out and/or --eulertigs-fa-out / --eulertigs-gfa-out")
@@ -502,8 +530,11 @@ def main(argv=None) -> int:
 
     # FASTQ is told from FASTA by the content; the quality flags need a file they can apply to
     aligned = (args.pseudoalign_fa or []) + (args.pseudoalign_mate_fa or [])
+    filters = (args.subtract_fa or []) + (args.intersect_fa or [])
     fastq = {path for path in (args.seq_in or []) + (args.query_fa or []) + (args.count_fa or []) + aligned + (args.correct_fa or [])
-             + (args.thread_fa or []) if api.sequence_file_format(path) == 2}
+             + (args.thread_fa or []) + filters if api.sequence_file_format(path) == 2}
+    if args.filter_min_base_quality is not None and not fastq.intersection(filters):
+        ap.error("--filter-min-base-quality needs a fastq file among --subtract-fa / --intersect-fa")
     if args.min_base_quality is not None and not fastq.intersection((args.seq_in or []) + (args.query_fa or [])):
         ap.error("--min-base-quality needs a fastq file among --seq-in / --query-fa")
     if args.query_min_base_quality is not None and not fastq.intersection(args.query_fa or []):
@@ -519,6 +550,66 @@ def main(argv=None) -> int:
     except api.FastqFormatError as e:  # an error of the input: the message names file, record, line and reason
         print(e, file=sys.stderr)
         return 2
+
+
+def _SELECTION_FLAGS(args):
+    """(flag, value) of every flag of the k-mer selection."""
+    return (("--require-colors", args.require_colors), ("--forbid-colors", args.forbid_colors), ("--min-colors", args.min_colors),
+            ("--max-colors", args.max_colors), ("--subtract-fa", args.subtract_fa), ("--subtract-min-abundance", args.subtract_min_abundance),
+            ("--intersect-fa", args.intersect_fa), ("--intersect-min-abundance", args.intersect_min_abundance),
+            ("--filter-min-base-quality", args.filter_min_base_quality), ("--selection-out", args.selection_out))
+
+
+def _selects_by_color(args) -> bool:
+    return any(v is not None for v in (args.require_colors, args.forbid_colors, args.min_colors, args.max_colors))
+
+
+def _selects(args) -> bool:
+    return any(value is not None for _, value in _SELECTION_FLAGS(args))
+
+
+def _color_list(text: str):
+    """`0,2,5-7` -> [0, 2, 5, 6, 7]; None for what is no such list."""
+    out = []
+    for part in text.split(","):
+        lo, dash, hi = part.partition("-")
+        if not lo.isdigit() or (dash and not hi.isdigit()) or (dash and int(hi) < int(lo)):
+            return None
+        out += list(range(int(lo), int(hi if dash else lo) + 1))
+    return out
+
+
+def _check_selection(ap, args) -> None:
+    """The argument errors of the selection flags: each names its flag, before any sequence is read."""
+    if not _selects(args):
+        return
+    n = len(args.seq_in)
+    masks = {}
+    for flag, text in (("--require-colors", args.require_colors), ("--forbid-colors", args.forbid_colors)):
+        numbers = _color_list(text) if text is not None else []
+        if numbers is None:
+            ap.error(f"{flag} {text}: a list of 0-based file numbers as commas and ranges, e.g. 0,2,5-7")
+        if numbers and max(numbers) >= n:
+            ap.error(f"{flag} names file {max(numbers)}: there are {n} --seq-in files, numbered from 0")
+        masks[flag] = set(numbers)
+    both = masks["--require-colors"] & masks["--forbid-colors"]
+    if both:
+        ap.error(f"--require-colors and --forbid-colors both name file {min(both)}")
+    for flag, value in (("--min-colors", args.min_colors), ("--max-colors", args.max_colors)):
+        if value is not None and not 0 <= value <= MAX_COLORS:
+            ap.error(f"{flag} must be in 0..{MAX_COLORS}")
+    if (args.min_colors or 0) > (MAX_COLORS if args.max_colors is None else args.max_colors):
+        ap.error(f"--min-colors {args.min_colors} exceeds --max-colors {MAX_COLORS if args.max_colors is None else args.max_colors}")
+    for flag, value, files, needs in (("--subtract-min-abundance", args.subtract_min_abundance, args.subtract_fa, "--subtract-fa"),
+                                      ("--intersect-min-abundance", args.intersect_min_abundance, args.intersect_fa, "--intersect-fa")):
+        if value is not None and not files:
+            ap.error(f"{flag} needs {needs}")
+        if value is not None and value < 1:
+            ap.error(f"{flag} must be >= 1")
+    if args.filter_min_base_quality is not None and not (args.subtract_fa or args.intersect_fa):
+        ap.error("--filter-min-base-quality needs --subtract-fa or --intersect-fa")
+    args.require_mask = sum(1 << c for c in masks["--require-colors"])
+    args.forbid_mask = sum(1 << c for c in masks["--forbid-colors"])
 
 
 def _check_thread(ap, args) -> None:
@@ -722,21 +813,25 @@ def _index_out(api, args, store, kmer_counts, colors, cleaning, bubbles) -> None
                                                       ("monochromatic_unitigs", args.monochromatic_unitigs or None)) if value is not None}
     meta = {"indexed": over, "colors": list(args.seq_in) if colors is not None else [], "min_abundance": args.min_abundance or 1,
             "cleaning": cleaning_flags}
+    if _selects(args):  # (the flags as given, the filter files by their paths)
+        meta["selection"] = {flag.lstrip("-").replace("-", "_"): value for flag, value in _SELECTION_FLAGS(args)
+                             if value is not None and flag != "--selection-out"}
     with index:
         n_bytes = index.save(args.index_out, meta)
         print(f"Writing the index over the {over} to {args.index_out} took {time.perf_counter() - t0:.1f}s: {n_bytes} bytes; "
               f"{index.info.describe()}", file=sys.stderr)
 
 
-def _read_seq_in(api, args, fastq, record_colors=None):
-    """The `--seq-in` files as one sequence set: the store of a single file as it is, else (data, offsets) of the files' stores one
-    after the other, and the non-ACGT / low-quality runs cut. record_colors: a list that takes, per record, the number of its file."""
+def _read_seq_in(api, args, fastq, record_colors=None, paths=None, min_base_quality=None):
+    """The `--seq-in` files (or `paths`, with their own quality threshold: the filter files of a selection) as one sequence set: the
+    store of a single file as it is, else (data, offsets) of the files' stores one after the other, and the non-ACGT / low-quality
+    runs cut. record_colors: a list that takes, per record, the number of its file."""
     import numpy as np
 
     stores = []
-    for path in args.seq_in:
+    for path in args.seq_in if paths is None else paths:
         if path in fastq:
-            st, stats = api.read_fastq(path, args.min_base_quality or 0, args.device)
+            st, stats = api.read_fastq(path, (args.min_base_quality if paths is None else min_base_quality) or 0, args.device)
             print(f"Read {path}: {stats.describe()}", file=sys.stderr)
         else:
             st = api.read_sequences(path, split_non_acgt=True)
@@ -755,27 +850,39 @@ def _read_seq_in(api, args, fastq, record_colors=None):
 
 def _run(api, args, fastq) -> int:
     t0 = time.perf_counter()
-    cleaning = bubbles = abundance = None
+    cleaning = bubbles = abundance = selection = None
     component_filter = args.min_component_kmers is not None  # 
     if args.bcalm_in is not None:
         graph, store = api.read_bcalm2(args.bcalm_in, args.k)
     elif args.seq_in is not None:  # sequences -> unitigs (GPU compaction) -> graph (the --fa-in join on the same store)
         classed = bool(args.monochromatic_unitigs or args.color_classes_out or args.unitig_color_classes_out)  # 
         colored = bool(args.color_matrix_out or args.unitig_colors_out or args.query_colors_out or args.query_index_colors_out or classed
-                       or args.pseudoalign_fa or args.index_colors)  # 
+                       or args.pseudoalign_fa or args.index_colors or _selects_by_color(args))  # 
         record_colors = [] if colored else None
         seqs, pieces_cut = _read_seq_in(api, args, fastq, record_colors)
         abundance = colors = cleaning = None
+        selecting = _selects(args)  # 
+        if selecting:
+            subtract, intersect = (_read_seq_in(api, args, fastq, None, paths, args.filter_min_base_quality)[0] if paths else None
+                                   for paths in (args.subtract_fa, args.intersect_fa))
+            chosen = api.KmerSelection(args.require_mask, args.forbid_mask, args.min_colors or 0, MAX_COLORS if args.max_colors is None else args.max_colors,
+                                       subtract, args.subtract_min_abundance or 1, intersect, args.intersect_min_abundance or 1)
         popping = args.pop_bubbles is not None  # 
         cleaned = args.clip_tips is not None or args.remove_isolated is not None or popping  # 
         per_kmer = bool(args.query_abundance_out or args.query_index_abundance_out or args.unitig_kmer_abundance_out
                         or args.index_weights)  # 
-        counted = not (args.min_abundance is None and not (args.kmer_spectrum_out or args.unitig_abundance_out or per_kmer))
+        counted = selecting or not (args.min_abundance is None and not (args.kmer_spectrum_out or args.unitig_abundance_out or per_kmer))
         if not counted and not colored and not cleaned:
             store, compaction = api.compact_unitigs(seqs, args.k, args.device)
         else:  # the counted compaction; an output flag alone counts without filtering
             min_abundance = args.min_abundance or 1
-            if popping:  # (the cleaned call whose rounds pop bubbles too)
+            if selecting:  # (the simplified call over the selected k-mers; what it does not clean or pop it reports as None, like the calls below)
+                store, compaction, abundance, colors, classes, cleaning, bubbles, selection = api.compact_unitigs_selected(
+                    seqs, args.k, chosen, args.pop_bubbles or 0, args.bubble_ratio or 1, args.clip_tips or 0, args.remove_isolated or 0,
+                    args.clean_rounds or 1, min_abundance, record_colors if colored else None, len(args.seq_in) if colored else 0,
+                    bool(args.monochromatic_unitigs), per_kmer, args.device)
+                cleaning, bubbles = cleaning if cleaned else None, bubbles if popping else None
+            elif popping:  # (the cleaned call whose rounds pop bubbles too)
                 store, compaction, abundance, colors, classes, cleaning, bubbles = api.compact_unitigs_simplified(
                     seqs, args.k, args.pop_bubbles, args.bubble_ratio or 1, args.clip_tips or 0, args.remove_isolated or 0, args.clean_rounds or 1,
                     min_abundance, record_colors if colored else None, len(args.seq_in) if colored else 0, bool(args.monochromatic_unitigs),
@@ -796,8 +903,16 @@ def _run(api, args, fastq) -> int:
                 store, compaction, abundance = api.compact_unitigs_counted(seqs, args.k, min_abundance, args.device)
             if args.kmer_spectrum_out:  # (also when nothing is kept: this is how a threshold that works is found)
                 _write_spectrum(args, abundance)
+            if selecting:  # (also when nothing is selected: the matrix and its occupancy row are how a carrier threshold is found)
+                if args.selection_out:
+                    _write_selection(args, abundance, colors, selection)
+                if args.color_matrix_out:
+                    _write_color_matrix(args, colors)
             if abundance.distinct_kept == 0:
                 print(f"no k-mer reaches --min-abundance {min_abundance} ({abundance.describe()})", file=sys.stderr)
+                return 1
+            if selecting and selection.selected == 0:
+                print(f"no k-mer is selected ({selection.describe()}; {abundance.describe()})", file=sys.stderr)
                 return 1
             if len(store) == 0:
                 print(f"nothing is left after cleaning ({cleaning.describe()}; {bubbles.describe() + '; ' if bubbles is not None else ''}"
@@ -807,7 +922,7 @@ def _run(api, args, fastq) -> int:
                 _write_unitig_abundance(args, store, abundance)
             if args.unitig_kmer_abundance_out and not component_filter:
                 _write_unitig_kmer_abundance(args, store, abundance)
-            if args.color_matrix_out:
+            if args.color_matrix_out and not selecting:
                 _write_color_matrix(args, colors)
             if args.unitig_colors_out:
                 _write_unitig_colors(args, store, colors)
@@ -825,6 +940,7 @@ def _run(api, args, fastq) -> int:
         loaded += f" (compacted from {compaction.describe()}; "
         loaded += f"cut into {compaction.unitigs} monochromatic unitigs; " if args.monochromatic_unitigs else ""
         loaded += f"{abundance.describe()}; " if abundance is not None and counted else ""
+        loaded += f"{selection.describe()}; " if selection is not None else ""
         loaded += f"{cleaning.describe()}; " if cleaning is not None else ""
         loaded += f"{bubbles.describe()}; " if bubbles is not None else ""
         loaded += f"{pieces_cut} non-ACGT runs cut)"
@@ -859,7 +975,8 @@ def _run(api, args, fastq) -> int:
     # what the tigs are verified against: the input as given -- on the --seq-in route the sequences, so that the check covers the compaction
     truth = seqs if args.seq_in is not None else store
     filtered = args.seq_in is not None and abundance is not None and min_abundance > 1
-    if filtered or cleaning is not None or component_filter:  # the tigs spell S_m less what the cleaning took, not the input's set: they are held to the
+    deselected = selection.rejected if selection is not None else 0
+    if filtered or cleaning is not None or component_filter or selection is not None:  # the tigs spell S_m less what the cleaning took, not the input's set: they are held to the
         truth = store                     # unitigs, and the unitigs to the input (below)
     cleaned_away = (cleaning.removed_kmers if cleaning is not None else 0) + (bubbles.arm_kmers if bubbles is not None else 0)
 
@@ -876,19 +993,36 @@ def _run(api, args, fastq) -> int:
         return cmp.equal
 
     all_equal = True
-    if (filtered or cleaning is not None or component_filter) and (args.verify or args.verify_fa):
+    if (filtered or cleaning is not None or component_filter or selection is not None) and (args.verify or args.verify_fa):
         # by the k-mer set comparison, a kernel the compaction does not share: no foreign k-mer survived, and exactly the dropped, the
         # cleaned and those of the removed components are gone
         cmp = api.compare_kmer_sets(seqs if args.seq_in is not None else given, store, args.k, args.device)
         dropped = abundance.dropped if abundance is not None else 0
-        ok = cmp.only_in_b == 0 and cmp.only_in_a == dropped + cleaned_away + component_kmers
+        ok = cmp.only_in_b == 0 and cmp.only_in_a == dropped + deselected + cleaned_away + component_kmers
+        if selection is not None:
+            print(f"Verifying selection: {cmp.distinct_b} of the input's {cmp.distinct_a} distinct k-mers are in the unitigs, "
+                  f"{cmp.only_in_a} are not ({dropped} dropped by the abundance filter, {deselected} deselected, {cleaned_away} cleaned away, "
+                  f"{component_kmers} in removed components), {cmp.only_in_b} foreign: {'as counted' if ok else 'MISMATCH'}", file=sys.stderr)
+            # against the filter files themselves, by the comparison kernel: with A = 1 the unitigs share no k-mer with the subtract
+            # files, with B = 1 every k-mer of the unitigs is in the intersect files
+            if subtract is not None and chosen.subtract_min_abundance == 1:
+                against = api.compare_kmer_sets(store, subtract, args.k, args.device)
+                shared = against.distinct_b - against.only_in_b
+                print(f"Verifying --subtract-fa: the unitigs share {shared} k-mers with the subtracted files: {'none' if shared == 0 else 'MISMATCH'}",
+                      file=sys.stderr)
+                ok = ok and shared == 0
+            if intersect is not None and chosen.intersect_min_abundance == 1:
+                against = api.compare_kmer_sets(intersect, store, args.k, args.device)
+                print(f"Verifying --intersect-fa: {against.only_in_b} k-mers of the unitigs are not in the intersected files: "
+                      f"{'none' if against.only_in_b == 0 else 'MISMATCH'}", file=sys.stderr)
+                ok = ok and against.only_in_b == 0
         if filtered:
             print(f"Verifying abundance filter: {cmp.distinct_b} of the input's {cmp.distinct_a} distinct k-mers are in the unitigs, "
-                  f"{cmp.only_in_a - cleaned_away - component_kmers} are not ({abundance.dropped} dropped by the filter), {cmp.only_in_b} foreign: "
+                  f"{cmp.only_in_a - deselected - cleaned_away - component_kmers} are not ({abundance.dropped} dropped by the filter), {cmp.only_in_b} foreign: "
                   f"{'as counted' if ok else 'MISMATCH'}", file=sys.stderr)
         if cleaning is not None:
             print(f"Verifying cleaning: {cmp.distinct_b} of the input's {cmp.distinct_a} distinct k-mers are in the unitigs, "
-                  f"{cmp.only_in_a - component_kmers} are not ({abundance.dropped} dropped by the filter, {cleaning.tip_kmers} in tips, "
+                  f"{cmp.only_in_a - component_kmers - deselected} are not ({abundance.dropped} dropped by the filter, {cleaning.tip_kmers} in tips, "
                   f"{cleaning.isolated_kmers} in isolated unitigs{f', {bubbles.arm_kmers} in bubble arms' if bubbles is not None else ''}), "
                   f"{cmp.only_in_b} foreign: {'as counted' if ok else 'MISMATCH'}", file=sys.stderr)
         if component_filter:
@@ -1158,6 +1292,18 @@ def _write_unitig_color_classes(args, store, classes) -> None:
         for n in per_line:
             f.write(" ".join(f"{l}:{c}" for l, c in zip(lengths[at:at + n], run_class[at:at + n])) + "\n")
             at += n
+
+
+def _write_selection(args, abundance, colors, selection) -> None:
+    """`--selection-out`: name<TAB>k-mers for the input, what the abundance threshold kept, what each rule rejected and
+    what is selected; then per colour its file, its k-mers among those the threshold kept, and its selected k-mers."""
+    rows = [("input", abundance.distinct_all), ("abundance_kept", selection.input_kmers), ("forbid", selection.rejected_forbid),
+            ("require", selection.rejected_require), ("carriers", selection.rejected_carriers), ("subtract", selection.rejected_subtract),
+            ("intersect", selection.rejected_intersect), ("selected", selection.selected)]
+    with _open_text(args, args.selection_out) as f:
+        f.writelines(f"{name}\t{int(n)}\n" for name, n in rows)
+        if colors is not None:
+            f.writelines(f"color\t{args.seq_in[c]}\t{int(colors.per_color[c])}\t{int(selection.per_color_selected[c])}\n" for c in range(colors.n_colors))
 
 
 def _write_color_matrix(args, colors) -> None:

@@ -133,6 +133,20 @@ class MtgBubbles(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class MtgSelectionParams(C.Structure):
+    """mtg_selection_params (include/mtg_engine.h)."""
+
+    _fields_ = [(n, C.c_uint64) for n in ("require", "forbid", "min_colors", "max_colors", "subtract_min_abundance", "intersect_min_abundance")]
+
+
+class MtgSelection(C.Structure):
+    """mtg_selection (include/mtg_engine.h)."""
+
+    _fields_ = [(n, C.c_uint64) for n in ("input_kmers", "rejected_forbid", "rejected_require", "rejected_carriers", "rejected_subtract",
+                                          "rejected_intersect", "selected", "selected_occurrences", "subtract_windows", "intersect_windows",
+                                          "subtract_hits", "intersect_hits")] + [("per_color_selected", C.c_uint64 * 64)]
+
+
 class MtgColorStats(C.Structure):
     """mtg_color_stats (include/mtg_engine.h)."""
 
@@ -399,6 +413,13 @@ def load():
                                                         P(MtgCompaction), P(MtgAbundance), P(vp), P(vp), P(vp), P(MtgColorStats), P(vp),
                                                         P(MtgCleaning), P(MtgBubbles)]),
         "mtg_last_bubble_times": (None, [P(C.c_double)]),
+        "mtg_compact_unitigs_selected": (None, [vp, vp, u64, u64, u64, vp, u64, C.c_int, P(MtgCleaningParams), P(MtgBubbleParams), P(MtgSelectionParams),
+                                                vp, vp, vp, u64, C.c_int, P(vp), P(MtgCompaction), P(MtgAbundance), P(vp), P(vp), P(vp), P(MtgColorStats),
+                                                P(vp), P(MtgCleaning), P(MtgBubbles), P(MtgSelection)]),
+        "mtg_compact_unitigs_selected_store": (None, [vp, u64, u64, vp, u64, C.c_int, P(MtgCleaningParams), P(MtgBubbleParams), P(MtgSelectionParams),
+                                                      vp, vp, vp, u64, C.c_int, P(vp), P(MtgCompaction), P(MtgAbundance), P(vp), P(vp), P(vp),
+                                                      P(MtgColorStats), P(vp), P(MtgCleaning), P(MtgBubbles), P(MtgSelection)]),
+        "mtg_last_select_times": (None, [P(C.c_double)]),
         "mtg_color_classes_build": (None, [vp, u64, vp, u64, C.c_int, P(vp)]),
         "mtg_color_classes_count": (u64, [vp]),
         "mtg_color_classes_masks": (vp, [vp]),

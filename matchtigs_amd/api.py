@@ -20,6 +20,7 @@ import ctypes as C
 import enum
 import json
 import os
+import re
 from dataclasses import dataclass
 from typing import Iterable, Optional, Sequence
 
@@ -1204,6 +1205,159 @@ def last_bubble_times() -> dict:
     return {"bubble_ms": float(out[0])}
 
 
+def _color_mask(colors, name: str) -> int:
+    """A colour mask given as an int or as an iterable of colour numbers."""
+    if isinstance(colors, bool):
+        raise ValueError(f"{name} must be a mask or an iterable of colour numbers, not {colors!r}")
+    if isinstance(colors, (int, np.integer)):
+        mask = int(colors)
+        if not 0 <= mask < 2 ** MAX_COLORS:
+            raise ValueError(f"{name} must be a mask of {MAX_COLORS} bits, not {colors!r}")
+        return mask
+    mask = 0
+    for c in colors:
+        if isinstance(c, bool) or not isinstance(c, (int, np.integer)) or not 0 <= c < MAX_COLORS:
+            raise ValueError(f"{name} holds colour numbers in 0..{MAX_COLORS - 1}, not {c!r}")
+        mask |= 1 << int(c)
+    return mask
+
+
+_NOT_ACGT = re.compile("[^ACGTacgt]+")
+
+
+class KmerSelection:
+    """Which k-mers of S_m (those that reach min_abundance) a selected compaction keeps (mtg_selection_params and the filter records of
+    mtg_compact_unitigs_selected). A k-mer is selected iff, in this order: none of its colours is in `forbid`; all of
+    `require` are among them; min_colors <= its carriers <= max_colors; it occurs fewer than subtract_min_abundance times in the
+    windows of `subtract`; it occurs at least intersect_min_abundance times in the windows of `intersect`. require / forbid: a mask
+    or an iterable of colour numbers. subtract / intersect: None, a list of str (either case; whatever is outside ACGT ends a piece,
+    as in the `--seq-in` readers), a UnitigStore or (uint8 array, offsets) of ACGT records; a rule applies only if its set has a record.
+    The filter sets are looked up, never inserted: they create, count and colour nothing. The defaults select everything.
+    filter_records: further filter records as (role, str) pairs, role "subtract" or "intersect", stored in the order given behind the
+    two sets (the sets' members are stored set by set; what is selected does not depend on the order)."""
+
+    def __init__(self, require=0, forbid=0, min_colors: int = 0, max_colors: int = MAX_COLORS, subtract=None, subtract_min_abundance: int = 1,
+                 intersect=None, intersect_min_abundance: int = 1, filter_records=None):
+        self.require, self.forbid = _color_mask(require, "require"), _color_mask(forbid, "forbid")
+        for name, v, lo, hi in (("min_colors", min_colors, 0, MAX_COLORS), ("max_colors", max_colors, 0, MAX_COLORS),
+                                ("subtract_min_abundance", subtract_min_abundance, 1, 2 ** 64 - 1),
+                                ("intersect_min_abundance", intersect_min_abundance, 1, 2 ** 64 - 1)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+                raise ValueError(f"{name} must be an integer in {lo}..{hi}, not {v!r}")
+        if self.require & self.forbid:
+            raise ValueError(f"require and forbid share colour {(self.require & self.forbid).bit_length() - 1}")
+        if min_colors > max_colors:
+            raise ValueError(f"min_colors {min_colors} exceeds max_colors {max_colors}")
+        self.min_colors, self.max_colors = int(min_colors), int(max_colors)
+        self.subtract_min_abundance, self.intersect_min_abundance = int(subtract_min_abundance), int(intersect_min_abundance)
+        self.subtract, self.intersect = subtract, intersect
+        self.filter_records = list(filter_records) if filter_records is not None else []
+        if any(role not in ("subtract", "intersect") or not isinstance(seq, str) for role, seq in self.filter_records):
+            raise ValueError('filter_records holds (role, str) pairs with the role "subtract" or "intersect"')
+
+    @property
+    def colour_rule(self) -> bool:
+        return bool(self.require or self.forbid or self.min_colors > 0 or self.max_colors < MAX_COLORS)
+
+    def _params(self, n_colors: int):
+        """The fields of mtg_selection_params; ValueError for a colour the call does not have."""
+        if self.colour_rule and not n_colors:
+            raise ValueError("require, forbid, min_colors and max_colors need record_colors")
+        for name, mask in (("require", self.require), ("forbid", self.forbid)):
+            if n_colors and mask >> n_colors:
+                raise ValueError(f"{name} names colour {mask.bit_length() - 1} of {n_colors}")
+        return (self.require, self.forbid, self.min_colors, self.max_colors, self.subtract_min_abundance, self.intersect_min_abundance)
+
+    @staticmethod
+    def _records(x):
+        """-> (uint8 data, offsets as a list) of one filter set."""
+        if x is None:
+            return np.zeros(0, np.uint8), [0]
+        if isinstance(x, UnitigStore):
+            data, off = x.arrays()
+            return np.array(data, np.uint8), [int(o) for o in off]
+        if isinstance(x, tuple):
+            return np.ascontiguousarray(x[0], np.uint8), [int(o) for o in x[1]]
+        pieces = [p for s in x for p in _NOT_ACGT.split(s) if p]
+        return np.frombuffer("".join(pieces).encode(), np.uint8), [0] + list(np.cumsum([len(p) for p in pieces], dtype=np.int64))
+
+    def _filter_arrays(self):
+        """The filter store of the call: data, offsets, one role byte per record (0 subtract, 1 intersect)."""
+        (ds, os_), (di, oi) = self._records(self.subtract), self._records(self.intersect)
+        off = os_ + [os_[-1] + o for o in oi[1:]]
+        roles = [0] * (len(os_) - 1) + [1] * (len(oi) - 1)
+        more = [(role == "intersect", p) for role, seq in self.filter_records for p in _NOT_ACGT.split(seq) if p]
+        for role, p in more:
+            off.append(off[-1] + len(p))
+            roles.append(int(role))
+        dm = np.frombuffer("".join(p for _, p in more).encode(), np.uint8)
+        return np.ascontiguousarray(np.concatenate([ds, di, dm]), np.uint8), np.array(off, np.uint64), np.array(roles, np.uint8)
+
+
+@dataclass(frozen=True, eq=False)
+class Selection:
+    """mtg_selection (include/mtg_engine.h): what a selected compaction selected, in exact integers. input_kmers = the
+    k-mers that reach min_abundance; a rejected k-mer is counted under the first rule it fails, so the five counts and `selected` add
+    up to input_kmers; *_windows: the windows of the filter records, *_hits: those whose k-mer is in the input at all;
+    per_color_selected[c]: the selected k-mers colour c carries (empty in a call without colours)."""
+
+    input_kmers: int
+    rejected_forbid: int
+    rejected_require: int
+    rejected_carriers: int
+    rejected_subtract: int
+    rejected_intersect: int
+    selected: int
+    selected_occurrences: int
+    subtract_windows: int
+    intersect_windows: int
+    subtract_hits: int
+    intersect_hits: int
+    per_color_selected: np.ndarray  # uint64[n_colors]
+
+    @property
+    def rejected(self) -> int:
+        return self.input_kmers - self.selected
+
+    def describe(self) -> str:
+        rules = [f"{n} by {name}" for name, n in (("forbid", self.rejected_forbid), ("require", self.rejected_require),
+                                                  ("carriers", self.rejected_carriers), ("subtract", self.rejected_subtract),
+                                                  ("intersect", self.rejected_intersect)) if n]
+        return f"{self.selected} of {self.input_kmers} k-mers selected" + (", rejected " + ", ".join(rules) if rules else "")
+
+
+def compact_unitigs_selected(seqs_or_store, k: int, selection: KmerSelection, pop_bubbles: int = 0, bubble_ratio: int = 1, clip_tips: int = 0,
+                             remove_isolated: int = 0, rounds: int = 1, min_abundance: int = 1, record_colors=None, n_colors: int = 0,
+                             split: bool = False, kmer_counts: bool = False, device_id: int = 0):
+    """compact_unitigs_simplified over the k-mers a KmerSelection keeps (mtg_compact_unitigs_selected) -> (UnitigStore,
+    Compaction, Abundance, Colors | None, ColorClasses | None, Cleaning, Bubbles, Selection). The selection acts where min_abundance
+    does, in front of the unitigs: store, Compaction, unitig_sums, kmer_counts, kmer_colors and the classes describe the selected (and
+    then cleaned) set; Abundance's scalars keep their meaning, and Colors' per_color, shared and occupancy are taken over the k-mers
+    that reach min_abundance, before the selection: they are how a carrier threshold is chosen. With KmerSelection() the store and
+    the per-k-mer arrays are compact_unitigs_simplified's. Nothing selected is a result: an empty store, the statistics filled."""
+    if not isinstance(selection, KmerSelection):
+        raise ValueError(f"selection must be a KmerSelection, not {selection!r}")
+    for name, v, lo, hi in (("pop_bubbles", pop_bubbles, 0, 2 ** 64 - 1), ("bubble_ratio", bubble_ratio, 1, MAX_BUBBLE_RATIO),
+                            ("clip_tips", clip_tips, 0, 2 ** 64 - 1), ("remove_isolated", remove_isolated, 0, 2 ** 64 - 1),
+                            ("rounds", rounds, 1, MAX_CLEAN_ROUNDS)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+            raise ValueError(f"{name} must be an integer in {lo}..{hi}, not {v!r}")
+    if min_abundance < 1:
+        raise ValueError("min_abundance must be >= 1")
+    if not isinstance(split, (bool, np.bool_)):
+        raise ValueError(f"split must be True or False, not {split!r}")
+    cleaning, bubbles = (int(clip_tips), int(remove_isolated), int(rounds)), (int(pop_bubbles), int(bubble_ratio))
+    if record_colors is None:
+        if split:
+            raise ValueError("split needs record_colors")
+        selection._params(0)
+        return _compact(_COUNTED_KMERS if kmer_counts else _COUNTED, seqs_or_store, k, device_id, min_abundance, cleaning=cleaning, bubbles=bubbles,
+                        selection=selection)
+    rc = _record_colors(record_colors, n_colors, _record_count(seqs_or_store))
+    selection._params(int(n_colors))
+    return _compact(_CLASSES, seqs_or_store, k, device_id, min_abundance, rc, int(n_colors), split, cleaning=cleaning, bubbles=bubbles, selection=selection)
+
+
 # The rungs of the compaction ladder and the C symbol each reaches (+ "_store" for a UnitigStore). The argument list of a rung is
 # the one below it plus its own (_compact): a new rung is one row here and one `if` there.
 _PLAIN, _COUNTED, _COUNTED_KMERS, _COLORED, _CLASSES = range(5)
@@ -1212,11 +1366,12 @@ _COMPACT_SYMBOLS = ("mtg_compact_unitigs", "mtg_compact_unitigs_counted", "mtg_c
 
 
 def _compact(rung: int, seqs_or_store, k: int, device_id: int, min_abundance: int = 1, record_colors=None, n_colors: int = 0,
-             split: bool = False, cleaning=None, bubbles=None):
+             split: bool = False, cleaning=None, bubbles=None, selection=None):
     """The one body of compact_unitigs* -> (UnitigStore, Compaction, Abundance, Colors, ColorClasses, Cleaning, Bubbles), None above the
     rung. cleaning: None, or (clip_tips, remove_isolated, rounds) -- the call then goes through mtg_compact_unitigs_cleaned, which takes
     the arguments of every rung and null out-pointers above the one asked for; bubbles: None, or (pop_bubbles, bubble_ratio) beside
-    a cleaning -- then through mtg_compact_unitigs_simplified. The arguments are the callers' to check."""
+    a cleaning -- then through mtg_compact_unitigs_simplified; selection: None, or a KmerSelection beside both -- then through
+    mtg_compact_unitigs_selected, and the tuple ends with the Selection. The arguments are the callers' to check."""
     L = _lib.load()
     out, sums, counts, masks, classes = (C.c_void_p() for _ in range(5))
     stats, ab, cs = _lib.MtgCompaction(), _lib.MtgAbundance(), _lib.MtgColorStats()
@@ -1236,18 +1391,24 @@ def _compact(rung: int, seqs_or_store, k: int, device_id: int, min_abundance: in
             outs += [C.byref(classes)]
         ins += [device_id]
     else:
-        symbol = "mtg_compact_unitigs_cleaned" if bubbles is None else "mtg_compact_unitigs_simplified"
+        symbol = "mtg_compact_unitigs_cleaned" if bubbles is None else "mtg_compact_unitigs_simplified" if selection is None else "mtg_compact_unitigs_selected"
         params, cleaned = _lib.MtgCleaningParams(*cleaning), _lib.MtgCleaning()
         ins = [k, min_abundance, _ptr(record_colors) if rung >= _COLORED else None, n_colors, int(bool(split)), C.byref(params)]
         if bubbles is not None:
             bubble_params, popped = _lib.MtgBubbleParams(*bubbles), _lib.MtgBubbles()
             ins += [C.byref(bubble_params)]
+        if selection is not None:
+            sel_params, chosen = _lib.MtgSelectionParams(*selection._params(n_colors if rung >= _COLORED else 0)), _lib.MtgSelection()
+            f_data, f_off, f_roles = selection._filter_arrays()
+            ins += [C.byref(sel_params), _ptr(f_data) if len(f_data) else None, _ptr(f_off), _ptr(f_roles) if len(f_roles) else None, len(f_roles)]
         ins += [device_id]
         outs = [C.byref(out), C.byref(stats), C.byref(ab), C.byref(sums), C.byref(counts) if rung >= _COUNTED_KMERS else None,
                 C.byref(masks) if rung >= _COLORED else None, C.byref(cs) if rung >= _COLORED else None,
                 C.byref(classes) if rung >= _CLASSES else None, C.byref(cleaned)]
         if bubbles is not None:
             outs += [C.byref(popped)]
+        if selection is not None:
+            outs += [C.byref(chosen)]
     if isinstance(seqs_or_store, UnitigStore):
         getattr(L, symbol + "_store")(seqs_or_store.handle, *ins, *outs)
     else:
@@ -1272,8 +1433,13 @@ def _compact(rung: int, seqs_or_store, k: int, device_id: int, min_abundance: in
         L.mtg_kmer_counts_free(counts)
         L.mtg_kmer_colors_free(masks)
         L.mtg_color_classes_free(classes)
-    return (UnitigStore(out.value), Compaction(**stats.as_dict()), abundance, colors, cc,
-            Cleaning(**cleaned.as_dict()) if cleaning is not None else None, Bubbles(**popped.as_dict()) if bubbles is not None else None)
+    result = (UnitigStore(out.value), Compaction(**stats.as_dict()), abundance, colors, cc,
+              Cleaning(**cleaned.as_dict()) if cleaning is not None else None, Bubbles(**popped.as_dict()) if bubbles is not None else None)
+    if selection is None:
+        return result
+    scalars = {name: int(getattr(chosen, name)) for name, _ in chosen._fields_ if name != "per_color_selected"}
+    per_color = np.array(chosen.per_color_selected, dtype=np.uint64)[:n_colors if rung >= _COLORED else 0].copy()
+    return result + (Selection(per_color_selected=per_color, **scalars),)
 
 
 def last_color_class_times() -> dict:
@@ -1302,6 +1468,9 @@ def last_compact_times() -> dict:
     d = dict(zip(names, list(out)))
     for n in names[9:]:
         d[n] = int(d[n])
+    sel = (C.c_double * 2)()
+    _lib.load().mtg_last_select_times(sel)  # (a selected call's filter probe and keep stage; 0.0 elsewhere)
+    d["filter_ms"], d["select_ms"] = float(sel[0]), float(sel[1])
     return d
 
 

@@ -97,11 +97,30 @@
 // Memory added while a round pops: 8 N (flags / list slots per oriented k-mer), 44 B per list slot (36 entry + 8 table), 12 B per
 // k-mer of a candidate arm (4 ordered count + 8 prefix); all freed before the keep flags are scanned.
 //
+// Selected calls (mtg_compact_unitigs_selected): of S_m only the k-mers that pass five rules, in this order and each
+// counted under the first it fails, reach nodes, succ and everything behind them: forbid (colors & forbid == 0), require (colors &
+// require == require), carriers (min <= popcount(colors) <= max), subtract (sub < A) and intersect (int >= B), where sub(x) / int(x) =
+// the windows of the subtract / intersect records of a second store, the FILTER records, whose k-mer is x or rc(x). The filter store is
+// packed on its own and only looked up: filter_probe_kernel runs between insert and ids, while the table lives, one thread per RUN
+// window starts of the filter store, find_slot<false> with the two-store same_class behind the tag (as exact as the insertion for
+// every k), and a hit adds 1 to sub[slot] or inter[slot] by the role of its record; a filter window claims no slot, so it creates,
+// counts and colours nothing. kpos_filter_kernel carries the two counters to dense arrays over S_m beside kcount and kcolor.
+// In front of the first pass, over the ids of S_m: color_stats_kernel (a selected call's colour statistics are those of S_m: they are
+// how a carrier threshold is chosen), then select_keep_kernel, which writes the keep flag and reduces the five rejection counts, the
+// selected k-mers, their occurrences and the per-colour selected counts (ballots and popcounts, never a loop over set bits) per
+// block; the scan of the flags and clean_move_kernel carry kpos, kcount and kcolor to the new ids in creator order, exactly as a
+// cleaning round's move does, and pass, clean_rounds, emit, sums_and_colors and download run over S_sel unchanged. Sums and flags:
+// nothing depends on how the atomics land. Memory added: 0.25 B per filter base (plus 1 B per base while it is packed) and 4 B per
+// slot and role while the table lives, all back before ids ends; 4 N per role until the keep kernel has run; then the move's 4 N
+// keep flags, 4 N new ids and second copy of kpos / kcount / kcolor. The probe is booked under filter_ms (ids_ms leaves it out),
+// the keep kernel, the scan and the move under select_ms. Fewer than 2^32 filter windows per role, fewer than 2^40 - 1 filter bases.
+// A call without a Selected queues exactly the kernels it queued before there was one.
+//
 // All of these enter through device_compact_unitigs(CompactRequest) (device.hpp): one rung of the ladder per pointer of the request --
 // Counted, Colored, Classed --, null where the call does not climb that far; Cleaned stands beside the ladder and goes with any rung,
-// Bubbled beside a Cleaned and a Counted. On the host a call is check_request (no device call), then run() over a Work (the store, the
-// current k-mer set, its node table, succ, pairs) through one function per stage -- insert, ids, pass (build_nodes, succ, rank with
-// rank_closed_walks), clean_rounds (clean_round, move_survivors), emit, sums_and_colors, download --, then finish(), the one way
+// Bubbled beside a Cleaned and a Counted, Selected beside any rung from Counted on (and a Colored where a colour rule is set). On the host a call is check_request (no device call), then run() over a Work (the store, the
+// current k-mer set, its node table, succ, pairs) through one function per stage -- insert, filter_probe, ids, select, pass (build_nodes,
+// succ, rank with rank_closed_walks), clean_rounds (clean_round, move_survivors), emit, sums_and_colors, download --, then finish(), the one way
 // out. Every device array belongs to a hu::DeviceArray and goes back where its owner's scope ends; every scan's block sums and
 // total belong to a hu::ScanScratch, which checks that a scan fits it.
 #include <hip/hip_runtime.h>
@@ -468,6 +487,104 @@ __device__ __forceinline__ void block_add(unsigned long long (&v)[n], unsigned l
         for (int w = 0; w < hu::EB / 64; w++) t += part[threadIdx.x][w];
         if (t) atomicAdd(&sums[threadIdx.x], t);
     }
+}
+
+// ---- the filter probe (selected calls) ----
+// One thread owns RUN window starts of the FILTER store f (packed on its own) and looks every window up in the k-mer table of the
+// main store a: lookup only (find_slot<false>), so nothing is claimed and no filter k-mer ever enters the table. The tag pre-filters,
+// the two-store kw::same_class decides identity base by base: as exact as the insertion, for every k. A hit adds 1 to sub[slot] or
+// inter[slot] by the role of the window's record (roles: [n_rec], 0 subtract, 1 intersect; read again only where the record changes
+// inside the run; each array is there only if its role occurs). Sums: nothing depends on how the atomics land. hits[0 / 1] += the
+// windows of either role whose class is in the table, reduced per wave and per block: at most one global atomic per counter and block.
+template <bool WIDE>
+__global__ __launch_bounds__(hu::EB) void filter_probe_kernel(KmerArgs a, kw::WindowArgs f, uint64_t n_bases, uint64_t n_rec, const uint8_t *roles,
+                                                               uint32_t *sub, uint32_t *inter, unsigned long long *hits) {
+    const uint64_t p0 = hu::gid() * RUN;
+    unsigned long long sub_hits = 0, inter_hits = 0;
+    if (p0 < n_bases) {
+        uint64_t role_rec = ~0ull;
+        uint32_t role = 0;
+        kw::for_each_window<WIDE>(f, p0, p0 + RUN < n_bases ? p0 + RUN : n_bases, 0, n_rec, [&](uint64_t q, uint64_t r, const kw::Window &w) {
+            const unsigned long long tag = kw::tagged_pos(w.hash, 0) >> 40;
+            const kw::Found found = kw::find_slot<false>(a.table, a.slots, w.hash, 0ull, [&](unsigned long long cur) {
+                return (cur >> 40) == tag && kw::same_class(f.packed, q, a.packed, cur & POS_LIMIT, a.k);
+            });
+            if (found.slot == a.slots) return;
+            if (r != role_rec) {
+                role_rec = r;
+                role = roles[r];
+            }
+            if (role) {
+                atomicAdd(&inter[found.slot], 1u);
+                inter_hits++;
+            } else {
+                atomicAdd(&sub[found.slot], 1u);
+                sub_hits++;
+            }
+        });
+    }
+    unsigned long long c[2] = {sub_hits, inter_hits};
+    block_add<2>(c, hits);
+}
+// ksub[id] / kint[id] = the filter counters of k-mer id, carried to the dense ids as kpos_kernel carries kcount (null: the role does not occur)
+__global__ __launch_bounds__(hu::EB) void kpos_filter_kernel(const unsigned long long *table, uint64_t slots, const uint32_t *id_of_pos,
+                                                              const uint32_t *abundance, uint64_t m, const uint32_t *sub, const uint32_t *inter,
+                                                              uint32_t *ksub, uint32_t *kint) {
+    const uint64_t s = hu::gid();
+    if (s >= slots) return;
+    const unsigned long long cur = table[s];
+    if (cur == EMPTY_SLOT || abundance[s] < m) return;
+    const uint32_t id = id_of_pos[cur & POS_LIMIT];
+    if (sub) ksub[id] = sub[s];
+    if (inter) kint[id] = inter[s];
+}
+
+// The five rules over the ids of S_m, in their order (include/mtg_engine.h): keep[i] = 1 where k-mer i passes them all. kcolor: null in
+// a call without colours (the mask counts as empty: check_request lets no colour rule through then); ksub / kint: null where the
+// role has no record (the rule does not apply). counters: [0 .. 5) the k-mers rejected by forbid, require, carriers, subtract,
+// intersect -- each under the first rule it fails --, [5] the selected k-mers, [6] their occurrences, [SELECT_COLOR + c] the selected
+// k-mers with bit c. The scalars are reduced per wave and block (block_add). Per colour: a wave holds 64 masks, one per lane; the
+// ballot of (selected and bit c) is column c of that 64 x 64 bit block and its popcount the wave's count, kept by lane c -- C ballots
+// per wave, never a loop over set bits --, added per workgroup in LDS and leaving by at most one global atomic per colour and block.
+struct SelectArgs {
+    uint64_t require, forbid, min_colors, max_colors, sub_min, int_min;
+};
+constexpr int SELECT_SCALARS = 7, SELECT_COLOR = 8, SELECT_WORDS = SELECT_COLOR + 64;
+__global__ __launch_bounds__(hu::EB) void select_keep_kernel(const unsigned long long *kcolor, const uint32_t *kcount, const uint32_t *ksub,
+                                                              const uint32_t *kint, SelectArgs p, int C, uint64_t N, uint32_t *keep,
+                                                              unsigned long long *counters) {
+    __shared__ uint32_t per_color[64];
+    if (threadIdx.x < 64) per_color[threadIdx.x] = 0;
+    __syncthreads();
+    const uint64_t i = hu::gid();
+    const int lane = threadIdx.x & 63;
+    unsigned long long c[SELECT_SCALARS] = {};
+    unsigned long long mask = 0;
+    bool kept = false;
+    if (i < N) {
+        mask = kcolor ? kcolor[i] : 0ull;
+        const uint64_t carriers = (uint64_t)__popcll(mask);
+        int fail = 5;
+        if (mask & p.forbid) fail = 0;
+        else if ((mask & p.require) != p.require) fail = 1;
+        else if (carriers < p.min_colors || carriers > p.max_colors) fail = 2;
+        else if (ksub && ksub[i] >= p.sub_min) fail = 3;
+        else if (kint && kint[i] < p.int_min) fail = 4;
+        kept = fail == 5;
+        keep[i] = kept;
+#pragma unroll
+        for (int r = 0; r < 6; r++) c[r] = fail == r;
+        c[6] = kept ? kcount[i] : 0u;
+    }
+    uint32_t mine = 0;
+    for (int b = 0; b < C; b++) {  // (uniform: every lane of the wave takes part in the ballot)
+        const unsigned long long t = __ballot(kept && ((mask >> b) & 1));
+        mine = lane == b ? (uint32_t)__popcll(t) : mine;
+    }
+    if (mine) atomicAdd(&per_color[lane], mine);
+    __syncthreads();
+    if (threadIdx.x < 64 && per_color[threadIdx.x]) atomicAdd(&counters[SELECT_COLOR + threadIdx.x], (unsigned long long)per_color[threadIdx.x]);
+    block_add<SELECT_SCALARS>(c, counters);
 }
 
 // One thread per oriented k-mer that ends an open walk (succ == none; the last element of a cut cycle has its head as successor and
@@ -1029,7 +1146,10 @@ struct Call {
     mtg_abundance ab{};
     mtg_cleaning clean{};
     mtg_bubbles popped{};
+    mtg_selection sel{};
+    bool selecting = false;  // a Selected is given: the select stage runs, and the colour statistics are taken in front of it
     double clean_ms = 0, bubble_ms = 0;
+    uint64_t filter_records[2] = {0, 0};  // by role
     UnitigStore *store = nullptr;
 };
 
@@ -1089,6 +1209,38 @@ void check_request(Call &c) {
             MTG_DIE("mtg_compact_unitigs_simplified: min_ratio %llu; 1 .. 255 are served", (unsigned long long)q.bubbles->params.min_ratio);
     }
     c.cleaning = (cleaned && (cleaned->params.tip_kmers || cleaned->params.isolated_kmers)) || c.popping;
+    if (const Selected *sel = q.selected) {
+        const char *const who = "mtg_compact_unitigs_selected";
+        const mtg_selection_params &p = sel->params;
+        if (p.subtract_min_abundance < 1) MTG_DIE("%s: subtract_min_abundance must be >= 1", who);
+        if (p.intersect_min_abundance < 1) MTG_DIE("%s: intersect_min_abundance must be >= 1", who);
+        if (p.require & p.forbid) MTG_DIE("%s: require and forbid share colour %d", who, __builtin_ctzll(p.require & p.forbid));
+        if (p.max_colors > MAX_COLORS) MTG_DIE("%s: max_colors %llu; at most %d", who, (unsigned long long)p.max_colors, MAX_COLORS);
+        if (p.min_colors > p.max_colors) MTG_DIE("%s: min_colors %llu exceeds max_colors %llu", who, (unsigned long long)p.min_colors, (unsigned long long)p.max_colors);
+        if (!counted) MTG_DIE("%s: a selection reports occurrences and needs the abundance and sums out-pointers", who);
+        const bool colour_rule = p.require || p.forbid || p.min_colors > 0 || p.max_colors < MAX_COLORS;
+        if (colour_rule && !colored) MTG_DIE("%s: require, forbid, min_colors and max_colors need the colours' out-pointers", who);
+        if (colored && colored->n_colors < MAX_COLORS) {
+            if (p.require >> colored->n_colors) MTG_DIE("%s: require names colour %d of %llu", who, 63 - __builtin_clzll(p.require), (unsigned long long)colored->n_colors);
+            if (p.forbid >> colored->n_colors) MTG_DIE("%s: forbid names colour %d of %llu", who, 63 - __builtin_clzll(p.forbid), (unsigned long long)colored->n_colors);
+        }
+        const uint64_t fn = sel->filter_n;
+        if (fn && (!sel->filter_off || !sel->filter_roles || (sel->filter_off[fn] && !sel->filter_data))) MTG_DIE("%s: null argument (filter records)", who);
+        if (fn && sel->filter_off[0] != 0) MTG_DIE("%s: filter offsets must start at 0", who);
+        for (uint64_t u = 0; u < fn; u++) {
+            if (sel->filter_off[u + 1] < sel->filter_off[u]) MTG_DIE("%s: filter offsets decrease at record %llu", who, (unsigned long long)u);
+            if (sel->filter_roles[u] > 1) MTG_DIE("%s: filter record %llu has role %u; 0 (subtract) and 1 (intersect) are served", who, (unsigned long long)u,
+                                                  (unsigned)sel->filter_roles[u]);
+            const uint64_t len = sel->filter_off[u + 1] - sel->filter_off[u];
+            c.filter_records[sel->filter_roles[u]]++;
+            if (len >= k) (sel->filter_roles[u] ? c.sel.intersect_windows : c.sel.subtract_windows) += len - k + 1;
+        }
+        if (c.sel.subtract_windows >= (1ull << 32) || c.sel.intersect_windows >= (1ull << 32))
+            MTG_DIE("%s: %llu subtract and %llu intersect windows; the filter counters are 32-bit, the limit is 2^32 - 1 per role", who,
+                    (unsigned long long)c.sel.subtract_windows, (unsigned long long)c.sel.intersect_windows);
+        if (fn && sel->filter_off[fn] >= POS_LIMIT) MTG_DIE("%s: %llu filter bases; the limit is 2^40 - 2", who, (unsigned long long)sel->filter_off[fn]);
+        c.selecting = true;
+    }
     c.split = q.classed && q.classed->split;
 }
 // The one way out of a call, wherever its stages ended: the statistics, the times, the cleaning and the bubble results.
@@ -1106,6 +1258,7 @@ UnitigStore *finish(Call &c) {
         *q.bubbles->out = c.popped;
         *q.bubbles->bubble_ms = c.bubble_ms;
     }
+    if (q.selected) *q.selected->out = c.sel;
     return c.store;
 }
 // The (k-1)-mer classes of the current k-mer set: key, and per side the incident oriented k-mer (NodeArgs). Assigning an empty one frees it.
@@ -1125,6 +1278,8 @@ struct Work {
     uint64_t slots = 0, N = 0;  // slots of the k-mer table
     hu::DeviceArray<unsigned long long> kpos, kcolor;
     hu::DeviceArray<uint32_t> kcount;
+    hu::DeviceArray<uint32_t> ksub, kint;  // selected calls, from ids to select: the filter counters of S_m's k-mers (empty: the role has no record)
+    bool color_stats_done = false;         // selected calls: the statistics were taken over S_m and are with the caller already
     NodeTable nodes;
     hu::DeviceArray<uint32_t> succ;
     hu::DeviceArray<unsigned long long> pairs;
@@ -1208,9 +1363,55 @@ KmerTable insert(Work &w) {
     return kt;
 }
 
+// The filter counters per slot of the k-mer table (selected calls): zeroed, one array per role that occurs. They go back with the table.
+struct FilterCounts {
+    hu::DeviceArray<uint32_t> sub, inter;  // [slots]
+};
+// Stage 2b, filter (selected calls with filter records): the filter store packed on its own, every window of it looked
+// up in the live table. Its packed text goes back here, the counters with the caller's scope. Books filter_ms and the hits.
+FilterCounts filter_probe(Work &w, const KmerTable &kt) {
+    Call &c = w.c;
+    const Selected &sel = *c.rq.selected;
+    FilterCounts fc;
+    PhaseEvents<2> fe;
+    if (c.filter_records[0]) {
+        fc.sub.alloc(w.slots);
+        HIP_CHECK(hipMemsetAsync(fc.sub, 0, w.slots * 4, w.st));
+    }
+    if (c.filter_records[1]) {
+        fc.inter.alloc(w.slots);
+        HIP_CHECK(hipMemsetAsync(fc.inter, 0, w.slots * 4, w.st));
+    }
+    unsigned long long h_hits[2] = {0, 0};
+    if (c.sel.subtract_windows + c.sel.intersect_windows) {  // (else no record is as long as k: the counters stay zero)
+        SeqStore fs("filter sequences", sel.filter_data, sel.filter_off, sel.filter_n, w.st, c.rq.device_id);
+        fe.mark(0, w.st);
+        hu::DeviceArray<uint8_t> roles(sel.filter_n);
+        hu::DeviceArray<unsigned long long> hits(2);
+        hu::upload_sliced(roles, sel.filter_roles, sel.filter_n, w.st, c.rq.device_id);
+        HIP_CHECK(hipMemsetAsync(hits, 0, sizeof h_hits, w.st));
+        kw::WindowArgs fa{};
+        fa.packed = fs.packed; fa.off = fs.off;
+        kw::window_args_set_k(fa, w.k);
+        auto *kernel = w.k >= 32 ? filter_probe_kernel<true> : filter_probe_kernel<false>;
+        kernel<<<hu::grid_for((fs.n_bases + RUN - 1) / RUN), hu::EB, 0, w.st>>>(kt.ka, fa, fs.n_bases, sel.filter_n, roles, fc.sub, fc.inter, hits);
+        HIP_CHECK(hipGetLastError());
+        fe.mark(1, w.st);
+        HIP_CHECK(hipMemcpyAsync(h_hits, hits, sizeof h_hits, hipMemcpyDeviceToHost, w.st));
+        HIP_CHECK(hipStreamSynchronize(w.st));
+        c.t.filter_ms = fe.ms(0, 1);
+    }
+    c.sel.subtract_hits = h_hits[0];
+    c.sel.intersect_hits = h_hits[1];
+    if (h_hits[0] > c.sel.subtract_windows || h_hits[1] > c.sel.intersect_windows)
+        MTG_DIE("unitig compaction: internal error (%llu and %llu filter hits in %llu and %llu windows)", h_hits[0], h_hits[1],
+                (unsigned long long)c.sel.subtract_windows, (unsigned long long)c.sel.intersect_windows);
+    return fc;
+}
+
 // Stage 3, ids: the creators flagged and scanned -> dense ids in creator order: N, kpos (kcount, kcolor). false: no k-mer is kept
 // (a counted call whose threshold none reaches). The flags and the scan's scratch go back here, the table with the caller's scope.
-bool ids(Work &w, const KmerTable &kt) {
+bool ids(Work &w, const KmerTable &kt, const FilterCounts &fc) {
     Call &c = w.c;
     hu::DeviceArray<uint32_t> id_of_pos(w.n_bases);
     HIP_CHECK(hipMemsetAsync(id_of_pos, 0, w.n_bases * 4, w.st));
@@ -1227,10 +1428,24 @@ bool ids(Work &w, const KmerTable &kt) {
     if (c.rq.counted) w.kcount.alloc(N);
     if (c.rq.colored) w.kcolor.alloc(N);
     launch_kpos(w, kt, id_of_pos);
+    if (fc.sub || fc.inter) {
+        if (fc.sub) w.ksub.alloc(N);
+        if (fc.inter) w.kint.alloc(N);
+        kpos_filter_kernel<<<hu::grid_for(w.slots), hu::EB, 0, w.st>>>(kt.table, w.slots, id_of_pos, kt.count, c.m, fc.sub, fc.inter, w.ksub, w.kint);
+        HIP_CHECK(hipGetLastError());
+    }
     w.ev.mark(2, w.st);
     return true;
 }
 
+// the words of color_stats_kernel as the caller's statistics
+void take_color_stats(const std::vector<unsigned long long> &h, mtg_color_stats &cs) {
+    for (int i = 0; i < MAX_COLORS; i++) {
+        cs.per_color[i] = h[i * MAX_COLORS + i];
+        for (int j = 0; j < MAX_COLORS; j++) cs.shared[i * MAX_COLORS + j] = h[i * MAX_COLORS + j];
+    }
+    for (int j = 0; j <= MAX_COLORS; j++) cs.occupancy[j] = h[COLOR_OCC + j];
+}
 // Stage 4, nodes: the table of T's (k-1)-mer classes with their incident words, and room for succ
 void build_nodes(Work &w) {
     const uint64_t slots = std::max<uint64_t>(8, 4 * w.N);
@@ -1350,8 +1565,8 @@ uint64_t clean_round(Work &w, hu::DeviceArray<uint32_t> &keep) {
     return removed;
 }
 // Stage 7: the scan of the keep flags gives the survivors' new ids (creator order is kept); kpos, kcount and kcolor move there and T
-// shrinks. The node table, succ and the pairs of the old ids are gone by now.
-void move_survivors(Work &w, const uint32_t *keep, uint64_t removed) {
+// shrinks. The node table, succ and the pairs of the old ids are gone by now. booked_ms: the clock of the stage that removes.
+void move_survivors(Work &w, const uint32_t *keep, uint64_t removed, double &booked_ms) {
     Call &c = w.c;
     const uint64_t N = w.N, N_left = N - removed;
     if (N_left) {
@@ -1370,13 +1585,63 @@ void move_survivors(Work &w, const uint32_t *keep, uint64_t removed) {
         me.mark(1, w.st);
         HIP_CHECK(hipMemcpyAsync(&n_left, scan.total(), 4, hipMemcpyDeviceToHost, w.st));
         HIP_CHECK(hipStreamSynchronize(w.st));
-        c.clean_ms += me.ms(0, 1);
+        booked_ms += me.ms(0, 1);
         if (n_left != N_left) MTG_DIE("unitig compaction: internal error (%llu k-mers kept, %llu counted)", (unsigned long long)n_left, (unsigned long long)N_left);
         w.kpos = std::move(kpos_to);
         w.kcount = std::move(kcount_to);
         w.kcolor = std::move(kcolor_to);
     }
     w.N = c.r.distinct_kmers = N_left;
+}
+// Stage 3b, select (selected calls), over the ids of S_m and in front of the first pass: the colour statistics of a
+// coloured call (over S_m: they are how a carrier threshold is chosen), the keep flags of the five rules with their counters, then the
+// scan and the move of a cleaning round. The filter counters go back here. false: nothing is selected.
+bool select(Work &w) {
+    Call &c = w.c;
+    const Colored *colored = c.rq.colored;
+    const mtg_selection_params &p = c.rq.selected->params;
+    const uint64_t N = w.N;
+    const int device_id = c.rq.device_id;
+    if (colored) {
+        PhaseEvents<2> ev_stats;
+        std::vector<unsigned long long> h(COLOR_STATS_WORDS);
+        hu::DeviceArray<unsigned long long> color_stats(COLOR_STATS_WORDS);
+        HIP_CHECK(hipMemsetAsync(color_stats, 0, COLOR_STATS_WORDS * 8, w.st));
+        ev_stats.mark(0, w.st);
+        color_stats_kernel<<<(unsigned)std::min<uint64_t>(hu::grid_for(N), 512), hu::EB, 0, w.st>>>(w.kcolor, N, (int)colored->n_colors, color_stats);
+        ev_stats.mark(1, w.st);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipStreamSynchronize(w.st));
+        hu::download_sliced(h.data(), color_stats, h.size() * 8, w.st, device_id);
+        *colored->stats_ms = ev_stats.ms(0, 1);
+        take_color_stats(h, *colored->stats);
+        w.color_stats_done = true;
+    }
+    PhaseEvents<2> se;
+    unsigned long long h[SELECT_WORDS] = {};
+    hu::DeviceArray<uint32_t> keep(N);
+    hu::DeviceArray<unsigned long long> counters(SELECT_WORDS);
+    HIP_CHECK(hipMemsetAsync(counters, 0, sizeof h, w.st));
+    se.mark(0, w.st);
+    const SelectArgs sa{p.require, p.forbid, p.min_colors, p.max_colors, p.subtract_min_abundance, p.intersect_min_abundance};
+    select_keep_kernel<<<hu::grid_for(N), hu::EB, 0, w.st>>>(w.kcolor, w.kcount, w.ksub, w.kint, sa, colored ? (int)colored->n_colors : 0, N, keep, counters);
+    HIP_CHECK(hipGetLastError());
+    se.mark(1, w.st);
+    HIP_CHECK(hipMemcpyAsync(h, counters, sizeof h, hipMemcpyDeviceToHost, w.st));
+    w.small.read(w.st, STAGE);
+    c.t.select_ms = se.ms(0, 1);
+    w.ksub.release();
+    w.kint.release();
+    mtg_selection &s = c.sel;
+    s.input_kmers = N;
+    s.rejected_forbid = h[0]; s.rejected_require = h[1]; s.rejected_carriers = h[2]; s.rejected_subtract = h[3]; s.rejected_intersect = h[4];
+    s.selected = h[5];
+    s.selected_occurrences = h[6];
+    for (int b = 0; b < MAX_COLORS; b++) s.per_color_selected[b] = h[SELECT_COLOR + b];
+    if (h[0] + h[1] + h[2] + h[3] + h[4] + h[5] != N)
+        MTG_DIE("unitig compaction: internal error (%llu k-mers rejected and %llu selected of %llu)", h[0] + h[1] + h[2] + h[3] + h[4], h[5], (unsigned long long)N);
+    if (s.selected < N) move_survivors(w, keep, N - s.selected, c.t.select_ms);
+    return w.N > 0;
 }
 // The rounds of a cleaned call and how they end.
 enum class Rounds {
@@ -1398,7 +1663,7 @@ Rounds clean_rounds(Work &w) {
         w.nodes = NodeTable{};
         w.succ.release();
         w.pairs.release();
-        move_survivors(w, keep, removed);
+        move_survivors(w, keep, removed, w.c.clean_ms);
         if (w.N == 0) return Rounds::NOTHING_LEFT;
         if (w.c.clean.rounds_run == w.c.rq.cleaned->params.rounds) return Rounds::USED_UP;
     }
@@ -1465,16 +1730,18 @@ void sums_and_colors(Work &w, Output &o) {
         if (!counted->kmer_counts) o.ordered.release();
     }
     if (colored) {
-        PhaseEvents<2> ev_stats;
-        o.color_stats.alloc(COLOR_STATS_WORDS);
         o.ordered_colors.alloc(N);
-        HIP_CHECK(hipMemsetAsync(o.color_stats, 0, COLOR_STATS_WORDS * 8, w.st));
         order_counts_kernel<unsigned long long><<<hu::grid_for(n_or), hu::EB, 0, w.st>>>(w.pairs, o.wmin, o.char_off, o.lead_flag, w.kcolor, n_or, w.k, o.ordered_colors);
-        ev_stats.mark(0, w.st);
-        color_stats_kernel<<<(unsigned)std::min<uint64_t>(hu::grid_for(N), 512), hu::EB, 0, w.st>>>(w.kcolor, N, (int)colored->n_colors, o.color_stats);
-        ev_stats.mark(1, w.st);
-        HIP_CHECK(hipGetLastError());
-        *colored->stats_ms = ev_stats.ms(0, 1);
+        if (!w.color_stats_done) {  // (a selected call has taken them over S_m)
+            PhaseEvents<2> ev_stats;
+            o.color_stats.alloc(COLOR_STATS_WORDS);
+            HIP_CHECK(hipMemsetAsync(o.color_stats, 0, COLOR_STATS_WORDS * 8, w.st));
+            ev_stats.mark(0, w.st);
+            color_stats_kernel<<<(unsigned)std::min<uint64_t>(hu::grid_for(N), 512), hu::EB, 0, w.st>>>(w.kcolor, N, (int)colored->n_colors, o.color_stats);
+            ev_stats.mark(1, w.st);
+            HIP_CHECK(hipGetLastError());
+            *colored->stats_ms = ev_stats.ms(0, 1);
+        }
     }
 }
 // Stage 10: the store, and what the rungs of the call hand out
@@ -1499,14 +1766,11 @@ void download(Work &w, const Output &o) {
         }
     }
     if (colored) {
-        std::vector<unsigned long long> h(COLOR_STATS_WORDS);
-        hu::download_sliced(h.data(), o.color_stats, h.size() * 8, w.st, device_id);
-        mtg_color_stats &cs = *colored->stats;
-        for (int i = 0; i < MAX_COLORS; i++) {
-            cs.per_color[i] = h[i * MAX_COLORS + i];
-            for (int j = 0; j < MAX_COLORS; j++) cs.shared[i * MAX_COLORS + j] = h[i * MAX_COLORS + j];
+        if (!w.color_stats_done) {
+            std::vector<unsigned long long> h(COLOR_STATS_WORDS);
+            hu::download_sliced(h.data(), o.color_stats, h.size() * 8, w.st, device_id);
+            take_color_stats(h, *colored->stats);
         }
-        for (int j = 0; j <= MAX_COLORS; j++) cs.occupancy[j] = h[COLOR_OCC + j];
         colored->kmer_colors->resize(N);
         hu::download_sliced(colored->kmer_colors->data(), o.ordered_colors, N * 8, w.st, device_id);
     }
@@ -1528,9 +1792,11 @@ void run(Call &c) {
     w.ev.mark(0, w.st);
     {
         const KmerTable kt = insert(w);
-        if (!ids(w, kt)) return;
+        const FilterCounts fc = c.selecting && c.rq.selected->filter_n ? filter_probe(w, kt) : FilterCounts{};
+        if (!ids(w, kt, fc)) return;
     }
-    c.t.ids_ms = w.ev.ms(1, 2);
+    c.t.ids_ms = w.ev.ms(1, 2) - c.t.filter_ms;
+    if (c.selecting && !select(w)) return;
     // nodes, succ and rank: once, or in a cleaned call once per round and, unless a round settled it, once more over the final set
     const Rounds rounds = c.cleaning ? clean_rounds(w) : Rounds::USED_UP;
     if (rounds == Rounds::NOTHING_LEFT) return;

@@ -354,6 +354,7 @@ struct CompactTimes {
     double upload_ms = 0, pack_ms = 0, insert_ms = 0, ids_ms = 0, nodes_ms = 0, rank_ms = 0, emit_ms = 0, download_ms = 0, total_ms = 0;
     int rounds = 0;
     uint64_t bytes = 0, peak_arena_bytes = 0;
+    double filter_ms = 0, select_ms = 0;  // selected calls: the filter probe (ids_ms leaves it out), the keep kernel and the move
 };
 // What a counted call adds: the k-mers whose abundance reaches m, the statistics of the counting and, per unitig in the
 // store's order, the sum of its k-mers' abundances. The spectrum sweep is booked under ids_ms, the sums under emit_ms.
@@ -407,6 +408,19 @@ struct Bubbled {
     mtg_bubbles *out;
     double *bubble_ms;
 };
+// What a selected call adds (include/mtg_engine.h states the rules): of S_m only the k-mers that pass the colour rules
+// and the rules against the filter records -- a second store (data, off, n_rec, one role byte per record: 0 subtract, 1 intersect)
+// that is probed in the k-mer table while it lives and never inserted -- reach nodes, succ and everything behind them. It stands
+// beside the ladder like Cleaned, needs a Counted (m may be 1) and, if a colour rule is set, a Colored, whose statistics are then
+// taken over S_m. The probe is booked under CompactTimes::filter_ms, the keep kernel with its scan and move under select_ms.
+struct Selected {
+    mtg_selection_params params;
+    const char *filter_data;
+    const uint64_t *filter_off;
+    const uint8_t *filter_roles;
+    uint64_t filter_n;
+    mtg_selection *out;
+};
 // One compaction. who: the public entry point that was called, for the messages. Each rung of the ladder is one pointer, null where
 // the call does not climb that far; a rung needs the ones below it.
 struct CompactRequest {
@@ -422,6 +436,7 @@ struct CompactRequest {
     const Classed *classed;
     const Cleaned *cleaned = nullptr;
     const Bubbled *bubbles = nullptr;
+    const Selected *selected = nullptr;
 };
 UnitigStore *device_compact_unitigs(const CompactRequest &rq);
 // ... of masks and unitig lengths handed in (kmer_colors: n masks in window order, none 0; unitig_kmers: n_unitigs lengths that sum to n)

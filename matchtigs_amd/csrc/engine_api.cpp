@@ -1373,6 +1373,11 @@ struct CompactIn {
     int split = 0;                           // CLASSES
     const mtg_cleaning_params *cleaning = nullptr;  // mtg_compact_unitigs_cleaned, at any rung
     const mtg_bubble_params *bubbles = nullptr;     // mtg_compact_unitigs_simplified, from COUNTED on
+    const mtg_selection_params *selection = nullptr;  // mtg_compact_unitigs_selected, from COUNTED on; the filter store: data, offsets, roles
+    const char *filter_data = nullptr;
+    const uint64_t *filter_offsets = nullptr;
+    const uint8_t *filter_roles = nullptr;
+    uint64_t filter_n = 0;
 };
 struct CompactOut {
     mtg_unitigs **out;
@@ -1385,6 +1390,7 @@ struct CompactOut {
     mtg_color_classes **classes = nullptr;    // CLASSES
     mtg_cleaning *cleaning = nullptr;         // mtg_compact_unitigs_cleaned
     mtg_bubbles *bubbles = nullptr;           // mtg_compact_unitigs_simplified
+    mtg_selection *selection = nullptr;       // mtg_compact_unitigs_selected
 };
 // what all mtg_compact_unitigs* share: the argument checks, the handles and their way to the out-pointers (who: the entry point)
 static void compact_call(const char *who, CompactRung rung, const CompactIn &in, const CompactOut &o) {
@@ -1408,11 +1414,16 @@ static void compact_call(const char *who, CompactRung rung, const CompactIn &in,
     if (pop && !clean) MTG_DIE("%s: popping bubbles needs the cleaning parameters (they carry the rounds) and the cleaning out-pointer", who);
     if (pop && rung < COUNTED) MTG_DIE("%s: popping bubbles compares abundances and needs the abundance and sums out-pointers", who);
     const Bubbled bubbled{pop ? *in.bubbles : mtg_bubble_params{0, 1}, pop ? o.bubbles : &none_popped, &g_last_bubble};
+    const bool select = in.selection && o.selection;
+    if (select && rung < COUNTED) MTG_DIE("%s: a selection reports occurrences and needs the abundance and sums out-pointers", who);
+    const Selected selected{select ? *in.selection : mtg_selection_params{0, 0, 0, 64, 1, 1}, in.filter_data, in.filter_offsets, in.filter_roles, in.filter_n,
+                            o.selection};
     *o.out = new mtg_unitigs{device_compact_unitigs({who, in.data, in.offsets, in.n, in.k, in.device_id, o.stats, &g_last_compact, s ? &counted : nullptr,
-                                                     m ? &colored : nullptr, cl ? &classed : nullptr, &cleaned, &bubbled})};
+                                                     m ? &colored : nullptr, cl ? &classed : nullptr, &cleaned, &bubbled, select ? &selected : nullptr})};
     g_last_clean[1] = (double)cleaned.out->rounds_run;
     if (o.cleaning && !clean) *o.cleaning = none;
     if (o.bubbles && !pop) *o.bubbles = none_popped;
+    if (o.selection && !select) *o.selection = mtg_selection{};
     if (s) *o.sums = s;
     if (c) *o.kmer_counts = c;
     if (m) *o.kmer_colors = m;
@@ -1531,6 +1542,43 @@ void mtg_compact_unitigs_simplified_store(const mtg_unitigs *in, uint64_t k, uin
                                    bubbles);
 }
 void mtg_last_bubble_times(double out[1]) { out[0] = g_last_bubble; }
+void mtg_compact_unitigs_selected(const char *data, const uint64_t *offsets, uint64_t n, uint64_t k, uint64_t min_abundance,
+                                  const uint8_t *record_colors, uint64_t n_colors, int split, const mtg_cleaning_params *params,
+                                  const mtg_bubble_params *bubble_params, const mtg_selection_params *selection_params,
+                                  const char *filter_data, const uint64_t *filter_offsets, const uint8_t *filter_roles, uint64_t filter_n,
+                                  int device_id, mtg_unitigs **out, mtg_compaction *stats, mtg_abundance *abundance, mtg_abundance_sums **sums,
+                                  mtg_kmer_counts **kmer_counts, mtg_kmer_colors **kmer_colors, mtg_color_stats *color_stats,
+                                  mtg_color_classes **classes, mtg_cleaning *cleaning, mtg_bubbles *bubbles, mtg_selection *selection) {
+    const char *const who = "mtg_compact_unitigs_selected";
+    const CompactRung rung = !sums ? PLAIN : !kmer_counts ? COUNTED : (!kmer_colors || !color_stats) ? COUNTED_KMERS : !classes ? COLORED : CLASSES;
+    if (rung < COUNTED && min_abundance != 1) MTG_DIE("%s: min_abundance %llu needs the sums' out-pointer", who, (unsigned long long)min_abundance);
+    if (rung < CLASSES && split != 0) MTG_DIE("%s: split needs the classes' out-pointer", who);
+    if (rung >= COUNTED && bubble_params && bubbles && bubble_params->max_arm_kmers && !abundance)
+        MTG_DIE("%s: popping bubbles compares abundances and needs the abundance and sums out-pointers", who);
+    CompactIn in{data, offsets, n, k, device_id, min_abundance, record_colors, n_colors, split, params, bubble_params, selection_params};
+    in.filter_data = filter_data;
+    in.filter_offsets = filter_offsets;
+    in.filter_roles = filter_roles;
+    in.filter_n = filter_n;
+    compact_call(who, rung, in, {out, stats, abundance, sums, kmer_counts, kmer_colors, color_stats, classes, cleaning, bubbles, selection});
+}
+void mtg_compact_unitigs_selected_store(const mtg_unitigs *in, uint64_t k, uint64_t min_abundance, const uint8_t *record_colors,
+                                        uint64_t n_colors, int split, const mtg_cleaning_params *params,
+                                        const mtg_bubble_params *bubble_params, const mtg_selection_params *selection_params,
+                                        const char *filter_data, const uint64_t *filter_offsets, const uint8_t *filter_roles,
+                                        uint64_t filter_n, int device_id, mtg_unitigs **out, mtg_compaction *stats, mtg_abundance *abundance,
+                                        mtg_abundance_sums **sums, mtg_kmer_counts **kmer_counts, mtg_kmer_colors **kmer_colors,
+                                        mtg_color_stats *color_stats, mtg_color_classes **classes, mtg_cleaning *cleaning,
+                                        mtg_bubbles *bubbles, mtg_selection *selection) {
+    if (!in) MTG_DIE("mtg_compact_unitigs_selected_store: null argument");
+    mtg_compact_unitigs_selected(in->s->data.data(), in->s->off.data(), in->s->off.size() - 1, k, min_abundance, record_colors, n_colors, split, params,
+                                 bubble_params, selection_params, filter_data, filter_offsets, filter_roles, filter_n, device_id, out, stats, abundance,
+                                 sums, kmer_counts, kmer_colors, color_stats, classes, cleaning, bubbles, selection);
+}
+void mtg_last_select_times(double out[2]) {
+    out[0] = g_last_compact.filter_ms;
+    out[1] = g_last_compact.select_ms;
+}
 // the vector behind one of the handles above (who: the entry point, for the message)
 extern "C++" {
 template <class Handle>
