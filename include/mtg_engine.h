@@ -1300,6 +1300,42 @@ void mtg_last_unitig_components_times(double out[10]);
 /* Measurement switch: 0 sends every unitig's statistics to its component's counters by itself; the default (1) aggregates the lanes
  * of a wave that share a component first. The results are the same. */
 void mtg_set_unitig_components_aggregation(int on);
+/* ---- the bubbles of the unitig graph as variant calls, on the GPU ----------------------------------------------
+ * Oriented unitig 2u is record u as written, 2u + 1 its reverse complement; x = from(edge 2u) and y = to(edge 2u) are its end nodes
+ * and n(u) its k-mers. Unitig u is a candidate arm iff n(u) < max_arm_kmers and it has no self-mirror end (x = mirror(x) or
+ * y = mirror(y)), is no loop (x = y) and no hairpin (x = mirror(y)). Its key is the smaller of the node pairs (x, y) and
+ * (mirror(y), mirror(x)); the candidates of one key are a bundle, and a bundle of two or more arms is a bubble. Arm a is better than b
+ * iff unitig_kc[a] n(b) > unitig_kc[b] n(a), taken in 128 bits, on equality the smaller unitig; the best arm is the reference arm r.
+ * Bubbles are numbered by their smallest unitig, ascending; the arms of bubble b are entries arm_off[b] .. arm_off[b + 1] - 1, r
+ * first, the others ascending by unitig. arm_strand: 0 where the arm runs between the same two nodes as record r as written, 1 where
+ * its reverse complement does; the allele is the oriented unitig 2 arm_unitig + arm_strand. arm_kmers = n, arm_abundance = unitig_kc
+ * (n without it). For every other arm against R = record r: suffix = the longest common suffix of R and the allele, at most the
+ * shorter length; prefix = the longest common prefix, at most the shorter length less the suffix (so indels are left-aligned);
+ * ref = R[prefix, |R| - suffix), alt likewise; differences = the positions at which ref and alt differ where their lengths agree,
+ * else 0. All three are 0 for arm 0. carried[arm * n_colors + c] = the arm's k-mers whose mask has bit c. This is NOT mtg_bubbles,
+ * which counts what the compaction popped: that one keeps its meaning. */
+typedef struct mtg_unitig_bubble_arrays {
+    uint64_t *arm_off;       /* [bubbles + 1] */
+    uint32_t *arm_unitig;    /* [arms] */
+    uint8_t *arm_strand;     /* [arms] */
+    uint32_t *arm_kmers;     /* [arms] */
+    uint64_t *arm_abundance; /* [arms] */
+    uint32_t *prefix;        /* [arms] */
+    uint32_t *suffix;        /* [arms] */
+    uint32_t *differences;   /* [arms] */
+    uint32_t *carried;       /* [arms * n_colors], NULL without kmer_colors */
+} mtg_unitig_bubble_arrays;
+/* unitig_seqs / seq_offsets: the n_unitigs records of g's unitigs (ACGT), offsets from 0. unitig_kc: the abundance sum of every
+ * unitig, or NULL. kmer_colors: NULL, or one 64-bit mask per k-mer in the order of the store's windows (record by record), with
+ * n_colors in 1..64. Every array of *arrays is released with mtg_free. Fewer than 2^31 - 1 unitigs; an arm has fewer than 2^31 k-mers
+ * whatever max_arm_kmers says. An empty graph, max_arm_kmers <= 1 and a graph without bubbles give 0 and arm_off = {0}. Returns the
+ * bubbles. Aborts without a GPU: there is no CPU path. */
+uint64_t mtg_unitig_bubbles(const mtg_graph *g, const char *unitig_seqs, const uint64_t *seq_offsets, uint64_t n_unitigs, uint64_t k,
+                            uint64_t max_arm_kmers, const uint64_t *unitig_kc, const uint64_t *kmer_colors, uint32_t n_colors, int device_id,
+                            mtg_unitig_bubble_arrays *arrays);
+/* Of the last mtg_unitig_bubbles on this thread: {upload with the pack (host clock, ms), keys + group + number, allele kernel,
+ * carrier kernel -- HIP events, ms --, download (host clock, ms), bubbles, arms, peak of the device arena's live bytes}. */
+void mtg_last_unitig_bubbles_times(double out[8]);
 /* Duplication bitvectors (implementation/mod.rs:668-702): one line per tig with `weight` characters per edge, '1' for an
  * original edge and '0' for a dummy edge (k-mers that repeat ones spelled elsewhere). */
 uint64_t mtg_write_duplication_bitvector(const mtg_graph *g, uint64_t n_walks, const uint64_t *limits, const uint32_t *edges,

@@ -63,6 +63,11 @@ the component of every unitig, line i for record i of `--unitigs-fa-out`; the la
 link lists. `--min-component-kmers N` (`--seq-in`, `--fa-in`) removes every component of fewer than N k-mers -- the clusters of two
 or three short unitigs that are neither tip nor isolated nor bubble -- once, before `--verify` and every output; links exist only
 inside a component, so what stays is still maximal and nothing is compacted again.
+`--bubbles-out` (`--seq-in`, `--fa-in`; not in the reference) says what the variation is that the cleaning left: every bubble of that
+graph -- two or more unitigs of fewer than `--bubbles-max-kmers` (default 2 k) k-mers between the same two nodes -- is a site, the arm
+with the largest mean abundance its reference allele, and the TSV gets one row per arm with its unitig and strand, k-mers, abundance,
+the kind of the difference (snp, mnp, ins, del, complex), its 0-based position on the reference arm's record, both alleles
+(left-aligned, `-` for none) and, with several `--seq-in` files, how many of the arm's k-mers each file carries.
 `--count-fa` with `--count-out` (any input; not in the reference) asks the opposite of `--query-fa`: how much of the input's k-mer set
 did OTHER reads see? Every `--count-fa` file is a sample (FASTA or FASTQ, `.gz` or not, told apart by the content); its k-mers are
 counted on the k-mers of the unitigs -- as written, after cleaning, splitting and the component filter -- on the GPU, either strand,
@@ -135,6 +140,12 @@ def main(argv=None) -> int:
     ap.add_argument("--min-component-kmers", type=int, metavar="N",
                     help="with --seq-in or --fa-in: remove the connected components of fewer than N k-mers before --verify and every "
                          "output (not in the reference)")
+    ap.add_argument("--bubbles-out", metavar="PATH",
+                    help="with --seq-in or --fa-in: write the bubbles of the unitig graph as variant calls, one TSV row per arm: bubble, "
+                         "arm, unitig, strand, kmers, abundance, mean, type, pos, ref, alt, differences and, with several --seq-in files, "
+                         "the k-mers of the arm each file carries (.gz => gzip) (not in the reference)")
+    ap.add_argument("--bubbles-max-kmers", type=int, metavar="L",
+                    help="with --bubbles-out: an arm has fewer than L k-mers (default 2 k; at least 2)")
     ap.add_argument("-k", type=int, help="k-mer size used to build the de Bruijn graph (bin.rs:139-141)")
     ap.add_argument("-t", "--threads", type=int, default=1, help="accepted; results always equal the 1-thread order (bin.rs:148-149)")
     ap.add_argument("--greedytigs-fa-out", help="write greedy matchtigs as fasta (.gz => gzip) (bin.rs:107-109)")
@@ -369,7 +380,7 @@ def main(argv=None) -> int:
 
     classed = bool(args.monochromatic_unitigs or args.color_classes_out or args.unitig_color_classes_out)
     colored = bool(args.color_matrix_out or args.unitig_colors_out or args.query_colors_out or args.query_index_colors_out or classed
-                   or args.pseudoalign_fa or args.index_colors or _selects_by_color(args))
+                   or args.pseudoalign_fa or args.index_colors or _selects_by_color(args) or args.bubbles_out is not None)
     if colored and args.seq_in is not None and len(args.seq_in) > MAX_COLORS:
         ap.error(f"{len(args.seq_in)} --seq-in files: at most {MAX_COLORS} files can be told apart as colours")
 
@@ -515,6 +526,16 @@ def main(argv=None) -> int:
                             ("--forbid-colors", args.forbid_colors), ("--min-colors", args.min_colors), ("--max-colors", args.max_colors)):
             if value is not None:
                 ap.error(f"--min-component-kmers cannot be combined with {flag}")
+    if args.bubbles_max_kmers is not None:
+        if args.bubbles_out is None:
+            ap.error("--bubbles-max-kmers needs --bubbles-out")
+        if args.bubbles_max_kmers < 2:
+            ap.error("--bubbles-max-kmers must be >= 2")
+    if args.bubbles_out is not None:
+        if args.bcalm_in is not None:  # (a graph built from links does not join two unitig ends that merely leave the same (k-1)-mer)
+            ap.error("--bubbles-out needs --seq-in or --fa-in")
+        if args.monochromatic_unitigs:  # (unitigs cut at the colour changes are no arms)
+            ap.error("--bubbles-out cannot be combined with --monochromatic-unitigs")
     for flag, value in (("--min-base-quality", args.min_base_quality), ("--query-min-base-quality", args.query_min_base_quality),
                         ("--count-min-base-quality", args.count_min_base_quality),
                         ("--pseudoalign-min-base-quality", args.pseudoalign_min_base_quality),
@@ -523,7 +544,8 @@ def main(argv=None) -> int:
             ap.error(f"{flag} must be in 0..93")
     if not (args.selection_out or args.color_classes_out or args.unitig_color_classes_out or args.color_matrix_out or args.unitig_colors_out or args.kmer_spectrum_out or args.unitig_abundance_out or args.unitig_kmer_abundance_out or args.query_fa or args.count_fa or args.pseudoalign_fa or args.correct_fa or args.thread_fa or args.greedytigs_fa_out or args.eulertigs_fa_out or args.greedytigs_gfa_out or args.eulertigs_gfa_out
             or args.greedytigs_duplication_bitvector_out or args.matchtigs_fa_out or args.matchtigs_gfa_out or args.verify_fa or args.unitigs_fa_out
-            or args.unitigs_bcalm_out or args.unitigs_gfa_out or args.components_out or args.unitig_components_out or args.index_out):
+            or args.unitigs_bcalm_out or args.unitigs_gfa_out or args.components_out or args.unitig_components_out or args.index_out
+            or args.bubbles_out):
         ap.error("nothing to do: give --greedytigs-fa-out / --greedytigs-gfa-out and/or --eulertigs-fa-out / --eulertigs-gfa-out")
 
     from . import api
@@ -857,7 +879,8 @@ def _run(api, args, fastq) -> int:
     elif args.seq_in is not None:  # sequences -> unitigs (GPU compaction) -> graph (the --fa-in join on the same store)
         classed = bool(args.monochromatic_unitigs or args.color_classes_out or args.unitig_color_classes_out)  # 
         colored = bool(args.color_matrix_out or args.unitig_colors_out or args.query_colors_out or args.query_index_colors_out or classed
-                       or args.pseudoalign_fa or args.index_colors or _selects_by_color(args))  # 
+                       or args.pseudoalign_fa or args.index_colors or _selects_by_color(args)
+                       or (args.bubbles_out is not None and len(args.seq_in) > 1))  # (the carriers of DESIGN.md 38)
         record_colors = [] if colored else None
         seqs, pieces_cut = _read_seq_in(api, args, fastq, record_colors)
         abundance = colors = cleaning = None
@@ -1057,6 +1080,21 @@ def _run(api, args, fastq) -> int:
             with _open_text(args, args.unitig_components_out) as f:
                 f.write("".join(f"{c}\n" for c in comps.component_of.tolist()))
         print(f"Writing components took {time.perf_counter() - t1:.1f}s ({comps.describe()})", file=sys.stderr)
+    if args.bubbles_out:  # what the variation is that the cleaning left
+        import os
+
+        import numpy as np
+
+        t1 = time.perf_counter()
+        masks = colors.kmer_colors if args.seq_in is not None and len(args.seq_in) > 1 else None
+        if masks is not None and component_filter:  # (the masks of the kept unitigs' k-mers)
+            masks = masks[np.repeat(keep, (np.diff(given.arrays()[1]) - np.uint64(args.k - 1)).astype(np.int64))]
+        found = api.unitig_bubbles(graph, store, args.k, 2 * args.k if args.bubbles_max_kmers is None else args.bubbles_max_kmers,
+                                   abundance.unitig_sums if args.seq_in is not None and abundance is not None else None, masks,
+                                   len(args.seq_in) if masks is not None else 0, args.device)
+        with _open_text(args, args.bubbles_out) as f:
+            f.write(found.tsv(store, args.k, [os.path.basename(path) for path in args.seq_in] if masks is not None else None))
+        print(f"Bubbles: {found.describe()} (found and written in {time.perf_counter() - t1:.1f}s)", file=sys.stderr)
     for name, alg, out, gfa, dup in (("matchtigs", 4, args.matchtigs_fa_out, args.matchtigs_gfa_out,
                                       args.matchtigs_duplication_bitvector_out),
                                      ("eulertigs", 3, args.eulertigs_fa_out, args.eulertigs_gfa_out, None),

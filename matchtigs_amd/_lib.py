@@ -203,6 +203,14 @@ class MtgComponentArrays(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("first_unitig", "unitigs", "kmers", "abundance", "links", "dead_ends", "irregular")]
 
 
+class MtgUnitigBubbleArrays(C.Structure):
+    """mtg_unitig_bubble_arrays (include/mtg_engine.h): arm_off has bubbles + 1 entries, carried arms x n_colors (NULL without masks),
+    the others one per arm; each goes back through mtg_free."""
+
+    _fields_ = [(n, C.c_void_p) for n in ("arm_off", "arm_unitig", "arm_strand", "arm_kmers", "arm_abundance", "prefix", "suffix",
+                                          "differences", "carried")]
+
+
 class MtgDijkstraPerformanceData(C.Structure):
     _fields_ = [
         ("dijkstras", C.c_uint64),
@@ -507,6 +515,8 @@ def load():
         "mtg_unitig_components": (u64, [vp, vp, vp, C.c_int, P(vp), P(MtgComponentArrays)]),
         "mtg_last_unitig_components_times": (None, [P(C.c_double)]),
         "mtg_set_unitig_components_aggregation": (None, [C.c_int]),
+        "mtg_unitig_bubbles": (u64, [vp, vp, vp, u64, u64, u64, vp, vp, C.c_uint32, C.c_int, P(MtgUnitigBubbleArrays)]),
+        "mtg_last_unitig_bubbles_times": (None, [P(C.c_double)]),
         "mtg_unitigs_select": (None, [vp, vp, P(vp)]),
         "mtg_write_duplication_bitvector": (u64, [vp, u64, vp, vp, P(vp)]),
         "mtg_write_tigs_duplication_bitvector_file": (u64, [vp, vp, C.c_char_p]),

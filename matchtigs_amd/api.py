@@ -3042,6 +3042,185 @@ def last_unitig_components_times() -> dict:
     return {name: (float(v) if name.endswith("_ms") else int(v)) for name, v in zip(names, out)}
 
 
+_BUBBLE_KINDS = ("snp", "mnp", "ins", "del", "complex", "identical")
+_COMPLEMENT = str.maketrans("ACGTacgt", "TGCATGCA")
+
+
+def _record_reader(store):
+    """record(u) -> the upper-case string of record u of a UnitigStore, a list of str or (uint8 array, offsets)."""
+    if isinstance(store, UnitigStore):
+        store = store.arrays()
+    if isinstance(store, tuple):
+        data, off = np.asarray(store[0], np.uint8), np.asarray(store[1], np.uint64)
+        return lambda u: data[int(off[u]):int(off[u + 1])].tobytes().decode().upper()
+    return lambda u: store[u].upper()
+
+
+@dataclass(frozen=True, eq=False)
+class UnitigBubbles:
+    """The bubbles of a unitig graph as variant calls (mtg_unitig_bubbles). The arms of bubble b are the entries
+    arm_off[b] .. arm_off[b + 1] - 1: the reference arm (the largest mean abundance, then the smallest unitig) first, the others
+    ascending by unitig; bubbles are numbered by their smallest unitig. arm_strand: 0 (+) where the arm runs the way the reference
+    arm's record is written, 1 (-) where its reverse complement does. prefix / suffix / differences describe an arm's allele against
+    the reference arm's record R: ref = R[prefix : len(R) - suffix], alt the same slice of the arm as oriented; all 0 for arm 0.
+    carried[arm, c]: the arm's k-mers that colour c carries (None without masks)."""
+
+    arm_off: np.ndarray        # uint64[bubbles + 1]
+    arm_unitig: np.ndarray     # uint32[arms]
+    arm_strand: np.ndarray     # uint8[arms]
+    arm_kmers: np.ndarray      # uint32[arms]
+    arm_abundance: np.ndarray  # uint64[arms]
+    prefix: np.ndarray         # uint32[arms]
+    suffix: np.ndarray         # uint32[arms]
+    differences: np.ndarray    # uint32[arms]
+    k: int                     # the k-mer length of the call: an arm has arm_kmers + k - 1 bases
+    carried: Optional[np.ndarray] = None  # uint32[arms, n_colors]
+
+    def __len__(self) -> int:
+        return len(self.arm_off) - 1
+
+    def _ref_arm(self) -> np.ndarray:
+        """The index of arm 0 of every arm's bubble."""
+        return np.repeat(self.arm_off[:-1], np.diff(self.arm_off).astype(np.int64)).astype(np.int64)
+
+    def allele_lengths(self):
+        """(len(ref), len(alt)) of every arm as int64 arrays; both 0 for arm 0."""
+        first = self._ref_arm()
+        cut = self.prefix.astype(np.int64) + self.suffix.astype(np.int64) - (self.k - 1)
+        n_ref, n_alt = self.arm_kmers[first].astype(np.int64) - cut, self.arm_kmers.astype(np.int64) - cut
+        is_ref = first == np.arange(len(first))
+        n_ref[is_ref] = 0
+        n_alt[is_ref] = 0
+        return n_ref, n_alt
+
+    def kinds(self) -> list:
+        """The kind of every arm: "ref" for arm 0, else snp (both alleles one base), mnp (equal lengths above 1), del (alt empty),
+        ins (ref empty), complex (anything else), or identical (both empty: a repeated record)."""
+        first = self._ref_arm()
+        n_ref, n_alt = self.allele_lengths()
+        out = []
+        for a, (r, v) in enumerate(zip(n_ref.tolist(), n_alt.tolist())):
+            if a == first[a]:
+                out.append("ref")
+            elif r == 0 and v == 0:
+                out.append("identical")
+            elif v == 0:
+                out.append("del")
+            elif r == 0:
+                out.append("ins")
+            elif r == v:
+                out.append("snp" if r == 1 else "mnp")
+            else:
+                out.append("complex")
+        return out
+
+    def alleles(self, store) -> list:
+        """(ref, alt) of every arm as strings, read from the unitigs the call was made on (a UnitigStore, a list of str or (uint8
+        array, offsets)); an empty allele is "", arm 0 gets (".", ".")."""
+        record = _record_reader(store)
+        first = self._ref_arm()
+        out = []
+        for a in range(len(self.arm_unitig)):
+            if a == first[a]:
+                out.append((".", "."))
+                continue
+            ref, arm = record(int(self.arm_unitig[first[a]])), record(int(self.arm_unitig[a]))
+            if self.arm_strand[a]:
+                arm = arm.translate(_COMPLEMENT)[::-1]
+            p, s = int(self.prefix[a]), int(self.suffix[a])
+            out.append((ref[p:len(ref) - s], arm[p:len(arm) - s]))
+        return out
+
+    def tsv(self, store, k: int, names=None) -> str:
+        """`--bubbles-out`: one row per arm -- bubble, arm, unitig, strand, kmers, abundance, mean (abundance / kmers with one
+        decimal, rounded half up in integers), type, pos (0-based in the reference arm's record), ref, alt, differences -- and one
+        column per colour with `carried` (headed by names, or c0, c1, ...). Arm 0 has `ref . . . 0`; an empty allele is `-`."""
+        if k != self.k:
+            raise ValueError(f"k = {k}, but the bubbles were called with k = {self.k}")
+        n_colors = 0 if self.carried is None else self.carried.shape[1]
+        if names is not None and len(names) != n_colors:
+            raise ValueError(f"{len(names)} names for {n_colors} colours")
+        head = ["bubble", "arm", "unitig", "strand", "kmers", "abundance", "mean", "type", "pos", "ref", "alt", "differences"]
+        head += list(names) if names is not None else [f"c{c}" for c in range(n_colors)]
+        rows = ["\t".join(head) + "\n"]
+        kinds, alleles = self.kinds(), self.alleles(store)
+        bubble_of = np.repeat(np.arange(len(self)), np.diff(self.arm_off).astype(np.int64))
+        first = self._ref_arm()
+        for a in range(len(self.arm_unitig)):
+            n, kc = int(self.arm_kmers[a]), int(self.arm_abundance[a])
+            t = (10 * kc + n // 2) // n
+            ref, alt = alleles[a]
+            pos = "." if kinds[a] == "ref" else str(int(self.prefix[a]))
+            row = [int(bubble_of[a]), a - int(first[a]), int(self.arm_unitig[a]), "-" if self.arm_strand[a] else "+", n, kc, f"{t // 10}.{t % 10}",
+                   kinds[a], pos, ref or "-", alt or "-", int(self.differences[a])]
+            row += self.carried[a].tolist() if n_colors else []
+            rows.append("\t".join(str(x) for x in row) + "\n")
+        return "".join(rows)
+
+    def describe(self) -> str:
+        kinds = self.kinds()
+        n = {name: kinds.count(name) for name in _BUBBLE_KINDS}
+        largest = int(np.diff(self.arm_off).max()) if len(self) else 0
+        return (f"{len(self)} bubbles, {len(self.arm_unitig)} arms: {n['snp']} snp, {n['mnp']} mnp, {n['ins']} ins, {n['del']} del, "
+                f"{n['complex']} complex; the largest has {largest} arms")
+
+
+def unitig_bubbles(graph: Bigraph, store, k: int, max_arm_kmers: int, kc=None, kmer_colors=None, n_colors: int = 0,
+                   device_id: int = 0) -> UnitigBubbles:
+    """The bubbles of the unitig graph -- two or more unitigs of fewer than max_arm_kmers k-mers between the same two nodes -- with
+    their alleles, found and described on the GPU (mtg_unitig_bubbles). store: the unitigs of `graph` as a UnitigStore,
+    a list of str or (uint8 array, offsets). kc: the abundance sum of every unitig (Abundance.unitig_sums), or None for its number of
+    k-mers. kmer_colors: the mask of every k-mer in window order of the store (Colors.kmer_colors) with n_colors in 1..64, or None.
+    Only the original edges count, so dummy edges a tig computation left in the graph change nothing."""
+    L = _lib.load()
+    data, off, n, keep = _sequence_arrays(store)
+    U = graph.original_edge_count() // 2
+    if n != U:
+        raise ValueError(f"{n} sequences for a graph of {U} unitigs")
+    kmers = _unitig_kmers(store, k)
+    if max_arm_kmers < 0:
+        raise ValueError("max_arm_kmers must be >= 0")
+    if kc is not None:
+        kc = np.ascontiguousarray(kc, dtype=np.uint64)
+        if kc.ndim != 1 or len(kc) != U:
+            raise ValueError(f"{len(kc)} abundance sums for {U} unitigs")
+    if kmer_colors is not None:
+        if not 1 <= n_colors <= MAX_COLORS:
+            raise ValueError(f"n_colors must be in 1..{MAX_COLORS}")
+        kmer_colors = np.ascontiguousarray(kmer_colors, dtype=np.uint64)
+        if kmer_colors.ndim != 1 or len(kmer_colors) != int(kmers.sum()):
+            raise ValueError(f"{len(kmer_colors)} colour masks for {int(kmers.sum())} k-mers")
+    arrays = _lib.MtgUnitigBubbleArrays()
+    B = int(L.mtg_unitig_bubbles(graph.handle, data, off, n, k, max_arm_kmers, _ptr(kc) if kc is not None and U else None,
+                                 _ptr(kmer_colors) if kmer_colors is not None and len(kmer_colors) else None,
+                                 n_colors if kmer_colors is not None else 0, device_id, C.byref(arrays)))
+    del keep
+
+    def take(p, ctype, dtype, count):
+        a = np.ctypeslib.as_array(C.cast(p, C.POINTER(ctype)), shape=(count,)).copy() if count else np.zeros(0, dtype)
+        L.mtg_free(p)
+        return a
+
+    arm_off = take(arrays.arm_off, C.c_uint64, np.uint64, B + 1)
+    A = int(arm_off[B])
+    u32 = {name: take(getattr(arrays, name), C.c_uint32, np.uint32, A) for name in ("arm_unitig", "arm_kmers", "prefix", "suffix", "differences")}
+    carried = None
+    if kmer_colors is not None:
+        carried = take(arrays.carried, C.c_uint32, np.uint32, A * n_colors).reshape(A, n_colors)
+    return UnitigBubbles(arm_off=arm_off, arm_strand=take(arrays.arm_strand, C.c_uint8, np.uint8, A),
+                         arm_abundance=take(arrays.arm_abundance, C.c_uint64, np.uint64, A), k=k, carried=carried, **u32)
+
+
+def last_unitig_bubbles_times() -> dict:
+    """Of the last unitig_bubbles on this thread: the uploads (with the pack) and the download by the host clock, keys + group +
+    number, the allele kernel and the carrier kernel by HIP events (ms); the bubbles, the arms and the peak of the device arena's
+    live bytes."""
+    out = (C.c_double * 8)()
+    _lib.load().mtg_last_unitig_bubbles_times(out)
+    names = ("upload_ms", "group_ms", "allele_ms", "carrier_ms", "download_ms", "bubbles", "arms", "peak_arena_bytes")
+    return {name: (float(v) if name.endswith("_ms") else int(v)) for name, v in zip(names, out)}
+
+
 def last_spell_kernel() -> dict:
     L = _lib.load()
     return {"ms": float(L.mtg_last_spell_kernel_ms()), "bytes": int(L.mtg_last_spell_bytes())}

@@ -143,6 +143,28 @@ struct UnitigComponentsTimes {
 // default; off only to measure it). *component_of_out[U] is malloc'd. Returns the components.
 uint64_t device_unitig_components(const HostGraph &g, const uint64_t *unitig_kmers, const uint64_t *unitig_kc, int device_id, bool aggregate,
                                   uint32_t **component_of_out, UnitigComponentArrays *out, UnitigComponentsTimes *times);
+// unitig_bubbles_device.hip: the bubbles of the unitig graph as variant calls (the file's header and DESIGN.md 38 state the
+// contract). arm_off has bubbles + 1 entries, carried arms x n_colors (null without masks), the others one per arm; all malloc'd
+// (the caller frees).
+struct UnitigBubbleArrays {
+    uint64_t *arm_off = nullptr;
+    uint32_t *arm_unitig = nullptr;
+    uint8_t *arm_strand = nullptr;
+    uint32_t *arm_kmers = nullptr;
+    uint64_t *arm_abundance = nullptr;
+    uint32_t *prefix = nullptr, *suffix = nullptr, *differences = nullptr, *carried = nullptr;
+};
+// host wall clock of the uploads (with the pack) and the download, HIP-event time of keys + group + number, of the allele kernel and
+// of the carrier kernel, the bubbles, the arms, the arena's peak of live bytes
+struct UnitigBubblesTimes {
+    double upload_ms = 0, group_ms = 0, allele_ms = 0, carrier_ms = 0, download_ms = 0;
+    uint64_t bubbles = 0, arms = 0, peak_arena_bytes = 0;
+};
+// the records data[off[u], off[u + 1]) of the graph's unitigs; unitig_kc[U] or null (then the abundance is the k-mers); kmer_colors:
+// null, or one mask per k-mer in window order of the store, with n_colors in 1..64. Returns the bubbles.
+uint64_t device_unitig_bubbles(const HostGraph &g, const char *seqs, const uint64_t *seq_off, uint64_t n_unitigs, uint64_t k, uint64_t max_arm_kmers,
+                               const uint64_t *unitig_kc, const uint64_t *kmer_colors, uint32_t n_colors, int device_id, UnitigBubbleArrays *out,
+                               UnitigBubblesTimes *times);
 // fasta_in_device.hip: the plain unitig FASTA route -- graph of the (k-1)-mer overlaps of the unitig ends, joined on the GPU
 // (records: data[off[u], off[u + 1]), off[0] = 0). times: host wall clock of upload / download / graph build, HIP-event time of the
 // join kernels, and the bytes those kernels must move at the least.

@@ -638,6 +638,26 @@ void mtg_last_unitig_components_times(double out[10]) {
     out[7] = t.rep_ms; out[8] = t.union_ms; out[9] = t.flatten_ms;
 }
 
+// ---- the bubbles of the unitig graph as variant calls (unitig_bubbles_device.hip) ----
+static thread_local UnitigBubblesTimes g_last_unitig_bubbles;
+uint64_t mtg_unitig_bubbles(const mtg_graph *g, const char *unitig_seqs, const uint64_t *seq_offsets, uint64_t n_unitigs, uint64_t k,
+                            uint64_t max_arm_kmers, const uint64_t *unitig_kc, const uint64_t *kmer_colors, uint32_t n_colors, int device_id,
+                            mtg_unitig_bubble_arrays *arrays) {
+    if (!g || !arrays || !seq_offsets || (n_unitigs && !unitig_seqs)) MTG_DIE("mtg_unitig_bubbles: null argument");
+    UnitigBubbleArrays a;
+    const uint64_t n = device_unitig_bubbles(g->g, unitig_seqs, seq_offsets, n_unitigs, k, max_arm_kmers, unitig_kc, kmer_colors, n_colors, device_id,
+                                             &a, &g_last_unitig_bubbles);
+    arrays->arm_off = a.arm_off; arrays->arm_unitig = a.arm_unitig; arrays->arm_strand = a.arm_strand; arrays->arm_kmers = a.arm_kmers;
+    arrays->arm_abundance = a.arm_abundance; arrays->prefix = a.prefix; arrays->suffix = a.suffix; arrays->differences = a.differences;
+    arrays->carried = a.carried;
+    return n;
+}
+void mtg_last_unitig_bubbles_times(double out[8]) {
+    const UnitigBubblesTimes &t = g_last_unitig_bubbles;
+    out[0] = t.upload_ms; out[1] = t.group_ms; out[2] = t.allele_ms; out[3] = t.carrier_ms; out[4] = t.download_ms;
+    out[5] = (double)t.bubbles; out[6] = (double)t.arms; out[7] = (double)t.peak_arena_bytes;
+}
+
 uint64_t mtg_write_duplication_bitvector(const mtg_graph *g, uint64_t n_walks, const uint64_t *limits, const uint32_t *edges,
                                          char **text_out) {
     if (!g || !text_out || (n_walks && (!limits || !edges))) MTG_DIE("mtg_write_duplication_bitvector: null argument");
